@@ -14,8 +14,10 @@ exchange), so the scaling is weak and there is no data-path coll
 
 The step is captured once into a HIP graph (two kernel launches + no host work per
 replay) and replayed K times; --no-graph times the eager autograd path instead.  The K-step
-block (barrier + synchronize on both sides, max over ranks) is repeated --repeats times and the
-MEDIAN block is reported, so a short driver run (--steps 20 = 0.4 ms) is not a single sample;
+block (barrier + synchronize on both sides, max over ranks) is timed once, so --steps K times
+exactly K steps; --repeats R times R such blocks and reports the MEDIAN block.
+--dump-outputs DIR writes what the last timed step computed (the forward output and the three
+gradients, rank 0) as DIR/<name>.npy, for comparing two builds on the same seeded inputs;
 the same line also carries `eager_ms_per_step` (plain autograd calls, what a drop-in user of the
 module runs) and `graph1_ms_per_step` (one graph launch per step) next to the headline.
 Rank 0 prints ONE JSON line (contract in the task statement) with two extra
@@ -46,6 +48,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 METRIC = "MSDeformAttn fwd+bwd samples/sec @ Swin-L 4-scale, 300 queries, 1/2/4/8 MI355X"      # BASELINE.json "metric"
+DUMP_LIMIT_BYTES = 64 * 10 ** 6                                                                  # --dump-outputs, all files together
 
 WORKLOADS = {
     # name: (N per GPU, [(H, W)...], M, D, Lq, P)
@@ -110,6 +113,28 @@ def make_inputs(workload, seed, device, dist_kind="uniform"):
     host = dict(value=value, shapes=shapes_t, lsi=lsi, loc=loc, attn=attn, go=go)
     dev = {k: v.to(device) for k, v in host.items()} if device is not None else None
     return host, dev, (N, S, M, D, L, Lq, P)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """Write each named tensor as out_dir/<name>.npy in float32 (float64 stays float64).  When the arrays together exceed
+    `limit_bytes`, each one is replaced by the same fraction of its elements, flattened, at sorted indices drawn from a
+    fixed seed: the indices depend only on the array's size, so two builds dump the same elements.  Returns
+    {name: (shape written, sampled?)}."""
+    import numpy as np
+    host = {name: t.detach().cpu().to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+            for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    budget = limit_bytes - 4096 * len(host)                                  # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        sampled = total > budget
+        if sampled:
+            k = a.size * budget // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (a.shape, sampled)
+    return written
 
 
 def usable_cores():
@@ -406,14 +431,21 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-table", action="store_true",
                     help="skip the `workloads` / `modules` arrays (the other shapes of DESIGN.md's performance table, ~2 s each)")
-    ap.add_argument("--repeats", type=int, default=50,
-                    help="repetitions of the timed --steps block (each bracketed by barrier + synchronize); the median is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of --steps steps each (each bracketed by barrier + synchronize); the median block is "
+                         "reported.  The default, 1, times exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (output, grad_value, grad_sampling_loc, "
+                         "grad_attn_weight; rank 0) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded "
+                         "sample of each array when they are larger)")
     ap.add_argument("--kernel-iters", type=int, default=200)
     ap.add_argument("--locations", default="uniform", choices=["uniform", "model"],
                     help="sampling-location distribution: uniform in [0,1) (headline) or model-like (SURVEY §8d B)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="storage type of value/out/grad tensors (bf16 = BASELINE config 3, MSDeformAttnBF16Function)")
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
 
     from uvhand_amd import harness
     rank, local_rank, world = harness.dist_env()
@@ -451,11 +483,13 @@ def main():
     attn = d["attn"].requires_grad_(True)
     shapes, lsi = d["shapes"], d["lsi"]
     go = d["go"].to(torch.bfloat16) if bf16 else d["go"]
+    last = {}
 
     def step():
         value.grad = loc.grad = attn.grad = None
         out = fn_apply(value, shapes, lsi, loc, attn, 64)
         out.backward(go)
+        last["output"] = out.detach()                     # under graph capture: the buffer every replay rewrites
 
     stream = torch.cuda.Stream(device)
     torch.cuda.synchronize()
@@ -499,12 +533,13 @@ def main():
 
         for _ in range((args.warmup + per_graph - 1) // per_graph):
             run()
-        # --repeats blocks, but no more than fit in ~5 s of timed work (the first block tells how long one takes)
-        blocks = [timed_block(run, args.steps // per_graph)]
-        fit = int(5.0 / max(blocks[0], 1e-6))
-        n_blocks = max(1, min(args.repeats, max(3, fit)))
-        n_blocks = int(harness.max_over_ranks(n_blocks, device) + 0.5) if world > 1 else n_blocks    # same count on every rank
-        blocks += [timed_block(run, args.steps // per_graph) for _ in range(n_blocks - 1)]
+        blocks = [timed_block(run, args.steps // per_graph) for _ in range(args.repeats)]
+        if args.dump_outputs and rank == 0:
+            # the last timed step's results, before the side measurements below run the step again
+            written = dump_outputs(args.dump_outputs, {"output": last["output"], "grad_value": value.grad,
+                                                       "grad_sampling_loc": loc.grad, "grad_attn_weight": attn.grad})
+            print("bench: outputs of the last timed step -> %s: %s" % (args.dump_outputs, ", ".join(
+                "%s %s%s" % (k, list(s), " (sampled)" if smp else "") for k, (s, smp) in written.items())), file=sys.stderr, flush=True)
 
         # the other two launch modes of the same step, for the record (not `value`)
         side = {}

@@ -359,6 +359,16 @@ int msda_add_layernorm_forward_f32(const float *x, const float *residual, const 
 int msda_add_layernorm_backward_f32(const float *grad_y, const float *x, const float *residual, const float *gamma,
                                     const float *mean, const float *rstd, long long rows, int d, float *grad_sum,
                                     float *grad_gamma, float *grad_beta, void *workspace, msda_stream_t stream);
+/* The same with a bf16 `residual` (required, rows 8-byte aligned) next to the fp32 x: what the layers pass under
+ * bf16 autocast (x the fp32 residual stream, residual the dropout of a bf16 projection output).  The residual is widened
+ * exactly on load and the arithmetic is the fp32 entries'; the backward writes grad_x (fp32) and, in the same pass, the same
+ * values rounded to bf16 into grad_residual (8-byte aligned). */
+int msda_add_layernorm_forward_f32_bf16res(const float *x, const uint16_t *residual, const float *gamma, const float *beta,
+                                           long long rows, int d, float eps, float *y, float *mean, float *rstd, msda_stream_t stream);
+int msda_add_layernorm_backward_f32_bf16res(const float *grad_y, const float *x, const uint16_t *residual, const float *gamma,
+                                            const float *mean, const float *rstd, long long rows, int d, float *grad_x,
+                                            uint16_t *grad_residual, float *grad_gamma, float *grad_beta, void *workspace,
+                                            msda_stream_t stream);
 
 /* ---- FFN of the layers (models/arctic_transformer.py:283-287, :366-370) ---------------------------
  * linear2(dropout(relu(linear1(x)))): with act = dropout(relu(h)) — the tensor linear2 consumed, saved for its weight gradient
@@ -389,6 +399,23 @@ int msda_attn32_backward_f32(const float *q, long long q_sn, long long q_sl, con
                              float scale, float dropout_p, const unsigned long long *seed, float *grad_q, long long gq_sn,
                              long long gq_sl, float *grad_k, long long gk_sn, long long gk_sl, float *grad_v, long long gv_sn,
                              long long gv_sl, msda_stream_t stream);
+/* The same core with bf16 q, k, v, out, grad_out, grad_q, grad_k, grad_v (uint16_t) — what the decoder's self-attention
+ * runs under bf16 autocast.  Same views (strides in elements, multiples of 8; 16-byte aligned bases), same geometry
+ * (msda_attn32_supported), lse still fp32 [N*H, Lq].  Arithmetic: q k^T accumulated in fp32, softmax / log-sum-exp in fp32,
+ * P rounded to bf16 only as the operand of P v (fp32 accumulate), out rounded once; the backward recomputes P from lse and
+ * takes delta = rowsum(dO * O) and dP = dO v^T in fp32, rounds dS = P * (dP - delta) to bf16 only as the operand of dQ and
+ * dK, and rounds dQ, dK, dV once.  Dropout: the fp32 entries' hash and threshold — for one seed the two cores drop the same
+ * (pair, query, key) entries.  No float atomics: the backward is bitwise reproducible.  At most 53.8 KB of LDS per workgroup. */
+int msda_attn32_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                             const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                             float dropout_p, const unsigned long long *seed, uint16_t *out, long long o_sn, long long o_sl,
+                             float *lse, msda_stream_t stream);
+int msda_attn32_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                              const uint16_t *v, long long v_sn, long long v_sl, const uint16_t *out, long long o_sn, long long o_sl,
+                              const float *lse, const uint16_t *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                              int Lk, float scale, float dropout_p, const unsigned long long *seed, uint16_t *grad_q,
+                              long long gq_sn, long long gq_sl, uint16_t *grad_k, long long gk_sn, long long gk_sl,
+                              uint16_t *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream);
 
 /* ---- Transformer input assembly -----------------------------------------------------
  * The flatten block of DeformableTransformer.forward (models/arctic_transformer.py:162-173): per level
@@ -411,8 +438,9 @@ const char *msda_last_error(void);
 
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
- * it changes whenever a declaration in this file does. */
-#define MSDA_ABI_VERSION 115
+ * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and
+ * msda_add_layernorm_{forward,backward}_f32_bf16res (the bf16-autocast forms of the attention core and add + LayerNorm). */
+#define MSDA_ABI_VERSION 116
 int msda_version(void);
 int msda_path_for(int elem_bytes, int M, int D, int L, int P);
 

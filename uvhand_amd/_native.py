@@ -31,7 +31,8 @@ _SYMBOLS = (
     "msda_relu_dropout_backward_f32", "msda_cast_bf16_multi_f32",
     "msda_flatten_levels_f32", "msda_unflatten_levels_f32", "msda_unflatten_workspace_bytes",
     "msda_linear_wgrad_f32", "msda_linear_wgrad_masked_f32", "msda_linear_wgrad_masked_bf16", "msda_linear_wgrad_multi_f32", "msda_linear_wgrad_multi", "msda_attn32_supported", "msda_attn32_forward_f32",
-    "msda_attn32_backward_f32", "msda_linear_wgrad_workspace_bytes",
+    "msda_attn32_backward_f32", "msda_attn32_forward_bf16", "msda_attn32_backward_bf16", "msda_add_layernorm_forward_f32_bf16res",
+    "msda_add_layernorm_backward_f32_bf16res", "msda_linear_wgrad_workspace_bytes",
     "msda_zero_masked_rows_f32", "msda_linear_forward_f32", "msda_linear_dgrad_f32",
     "msda_prologue_supported", "msda_forward_prologue_f32", "msda_backward_prologue_f32",
     "msda_last_error", "msda_version", "msda_path_for", "msda_force_path", "msda_describe_plan",
@@ -625,12 +626,18 @@ def relu_dropout_backward_(grad, act, scale):
     return grad
 
 
-def _attn_view(t, name, heads):
-    """[L, N, heads*32] float32 CUDA view with the last dimension contiguous -> (pointer, batch stride, sequence stride)."""
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == heads * 32
+def _attn_view(t, name, heads, dtype=torch.float32):
+    """[L, N, heads*32] float32 (bfloat16) CUDA view with the last dimension contiguous -> (pointer, batch stride, sequence stride)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.shape[2] == heads * 32
             and t.stride(2) == 1):
-        raise RuntimeError("attn32: %s must be a float32 CUDA tensor [L, N, heads*32] with a contiguous last dimension" % name)
+        raise RuntimeError("attn32: %s must be a %s CUDA tensor [L, N, heads*32] with a contiguous last dimension"
+                           % (name, str(dtype).replace("torch.", "")))
     return t.data_ptr(), t.stride(1), t.stride(0)
+
+
+def _attn_dtype(q):
+    """The core's operand type: bfloat16 -> the msda_attn32_*_bf16 entries, anything else -> the fp32 ones (which check it)."""
+    return torch.bfloat16 if torch.is_tensor(q) and q.dtype == torch.bfloat16 else torch.float32
 
 
 def attn32_supported(Lq, Lk, head_dim):
@@ -641,17 +648,19 @@ def attn32_supported(Lq, Lk, head_dim):
 def attn32_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None):
     """msda_attn32_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale)) v per (batch, head), head_dim 32.
     q [Lq, N, E], k / v [Lk, N, E] (sequence first, as nn.MultiheadAttention projects them; column-block views allowed);
-    seed: a one-element int64 CUDA tensor (required when dropout_p > 0).  Returns (out [Lq, N, E], lse [N*heads, Lq])."""
+    seed: a one-element int64 CUDA tensor (required when dropout_p > 0).  Returns (out [Lq, N, E], lse [N*heads, Lq]).
+    bfloat16 q, k, v take msda_attn32_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
     lib = _lib or load()
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
-    qv, kv, vv = _attn_view(q, "q", heads), _attn_view(k, "k", heads), _attn_view(v, "v", heads)
+    dt = _attn_dtype(q)
+    qv, kv, vv = _attn_view(q, "q", heads, dt), _attn_view(k, "k", heads, dt), _attn_view(v, "v", heads, dt)
     if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise RuntimeError("attn32_forward: dropout needs a one-element int64 CUDA seed tensor")
     with _DeviceGuard(q.device):
-        out = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device)
+        out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
         lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
-        ov = _attn_view(out, "out", heads)
-        rc = _entry(lib, "msda_attn32_forward_f32", [_VP, _LL, _LL] * 3 + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP] + [_VP, _LL, _LL] + [_VP, _VP])(
+        ov = _attn_view(out, "out", heads, dt)
+        rc = _entry(lib, "msda_attn32_forward_bf16" if dt == torch.bfloat16 else "msda_attn32_forward_f32", [_VP, _LL, _LL] * 3 + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP] + [_VP, _LL, _LL] + [_VP, _VP])(
             *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *ov,
             lse.data_ptr(), _raw_stream(q.device))
     if rc != 0:
@@ -661,19 +670,21 @@ def attn32_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None):
 
 def attn32_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, grad_q=None, grad_k=None, grad_v=None):
     """msda_attn32_backward_f32: gradients of q, k, v (written into grad_q / grad_k / grad_v when given — views like the inputs,
-    e.g. the two column blocks of one packed [L, N, 2E] tensor — else into new contiguous tensors)."""
+    e.g. the two column blocks of one packed [L, N, 2E] tensor — else into new contiguous tensors).  bfloat16 q takes
+    msda_attn32_backward_bf16: every tensor but lse bfloat16, gradients included."""
     lib = _lib or load()
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
+    dt = _attn_dtype(q)
     with _DeviceGuard(q.device):
-        grad_q = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device) if grad_q is None else grad_q
-        grad_k = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_k is None else grad_k
-        grad_v = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_v is None else grad_v
+        grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
+        grad_k = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_k is None else grad_k
+        grad_v = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_v is None else grad_v
         if grad_out.stride(2) != 1:
             grad_out = grad_out.contiguous()
-        views = [_attn_view(t, nm, heads) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
-        gov = _attn_view(grad_out, "grad_out", heads)
-        gviews = [_attn_view(t, nm, heads) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
-        rc = _entry(lib, "msda_attn32_backward_f32", [_VP, _LL, _LL] * 4 + [_VP] + [_VP, _LL, _LL] + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP]
+        views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
+        gov = _attn_view(grad_out, "grad_out", heads, dt)
+        gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
+        rc = _entry(lib, "msda_attn32_backward_bf16" if dt == torch.bfloat16 else "msda_attn32_backward_f32", [_VP, _LL, _LL] * 4 + [_VP] + [_VP, _LL, _LL] + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP]
                     + [_VP, _LL, _LL] * 3 + [_VP])(
             *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p),
             seed.data_ptr() if dropout_p > 0 else None, *gviews[0], *gviews[1], *gviews[2], _raw_stream(q.device))
@@ -691,6 +702,50 @@ def add_layernorm_supported(x, residual, weight, bias):
             and (residual is None or residual.shape == x.shape)
             and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
                     and t.device == x.device for t in ts))
+
+
+def add_layernorm_bf16res_supported(x, residual, weight, bias):
+    """fp32 x (and parameters) as add_layernorm_supported, residual a bfloat16 tensor of x's shape, contiguous, 8-byte aligned."""
+    return (torch.is_tensor(residual) and residual.dtype == torch.bfloat16 and residual.is_cuda and residual.is_contiguous()
+            and residual.shape == x.shape and residual.device == x.device and residual.data_ptr() % 8 == 0
+            and add_layernorm_supported(x, None, weight, bias))
+
+
+def add_layernorm_forward_bf16res(x, residual, weight, bias, eps):
+    """(y, mean, rstd) = LayerNorm(x + residual) for fp32 x and bfloat16 residual — msda_add_layernorm_forward_f32_bf16res."""
+    lib = _lib or load()
+    d = x.shape[-1]
+    rows = x.numel() // d
+    with _DeviceGuard(x.device):
+        y = torch.empty_like(x)
+        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        rc = _entry(lib, "msda_add_layernorm_forward_f32_bf16res", [_VP] * 4 + [_LL, _CI, ctypes.c_float] + [_VP] * 4)(
+            x.data_ptr(), residual.data_ptr(), weight.data_ptr(), bias.data_ptr(), rows, d, float(eps), y.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), _raw_stream(x.device))
+    if rc != 0:
+        _raise(lib, rc, "add_layernorm_forward_bf16res")
+    return y, mean, rstd
+
+
+def add_layernorm_backward_bf16res(grad_y, x, residual, weight, mean, rstd):
+    """(grad_x fp32, grad_residual bf16 = grad_x rounded, grad_weight, grad_bias) — msda_add_layernorm_backward_f32_bf16res."""
+    lib = _lib or load()
+    d = x.shape[-1]
+    rows = x.numel() // d
+    with _DeviceGuard(x.device):
+        gx = torch.empty_like(x)
+        gr = torch.empty_like(residual)
+        gw = torch.empty((d,), dtype=torch.float32, device=x.device)
+        gb = torch.empty((d,), dtype=torch.float32, device=x.device)
+        nbytes = max(16, int(lib.msda_add_layernorm_workspace_bytes(rows, d)))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+        rc = _entry(lib, "msda_add_layernorm_backward_f32_bf16res", [_VP] * 6 + [_LL, _CI] + [_VP] * 6)(
+            grad_y.data_ptr(), x.data_ptr(), residual.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, d,
+            gx.data_ptr(), gr.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), _raw_stream(x.device))
+    if rc != 0:
+        _raise(lib, rc, "add_layernorm_backward_bf16res")
+    return gx, gr, gw, gb
 
 
 def add_layernorm_forward(x, residual, weight, bias, eps):

@@ -724,6 +724,42 @@ int msda_add_layernorm_backward_f32(const float *grad_y, const float *x, const f
                                           static_cast<float *>(workspace), (hipStream_t)stream);
 }
 
+// x fp32, residual bf16 (8-byte aligned rows: a bf16 projection output under autocast); the arithmetic of the fp32 entries
+int msda_add_layernorm_forward_f32_bf16res(const float *x, const uint16_t *residual, const float *gamma, const float *beta,
+                                           long long rows, int d, float eps, float *y, float *mean, float *rstd, msda_stream_t stream)
+{
+    const void *ptrs[] = {x, gamma, beta, y};
+    if (int rc = check_layernorm_args("msda_add_layernorm_forward_f32_bf16res", rows, d, ptrs, 4)) return rc;
+    if (rows > 0 && (mean == nullptr || rstd == nullptr || residual == nullptr || ((uintptr_t)residual & 7)))
+        return msda::set_error(MSDA_ERR_ARGUMENT,
+                               "msda_add_layernorm_forward_f32_bf16res: null mean / rstd / residual or residual not 8-byte aligned");
+    msda::begin_call();
+    if (rows == 0) return MSDA_OK;
+    return msda::launch_add_layernorm_fwd_bf16res(x, residual, gamma, beta, rows, d, eps, y, mean, rstd, (hipStream_t)stream);
+}
+
+int msda_add_layernorm_backward_f32_bf16res(const float *grad_y, const float *x, const uint16_t *residual, const float *gamma,
+                                            const float *mean, const float *rstd, long long rows, int d, float *grad_x,
+                                            uint16_t *grad_residual, float *grad_gamma, float *grad_beta, void *workspace,
+                                            msda_stream_t stream)
+{
+    const void *ptrs[] = {grad_y, x, gamma, grad_x, workspace};
+    if (int rc = check_layernorm_args("msda_add_layernorm_backward_f32_bf16res", rows, d, ptrs, 5)) return rc;
+    if (grad_gamma == nullptr || grad_beta == nullptr ||
+        (rows > 0 && (mean == nullptr || rstd == nullptr || residual == nullptr || grad_residual == nullptr ||
+                      ((uintptr_t)residual & 7) || ((uintptr_t)grad_residual & 7))))
+        return msda::set_error(MSDA_ERR_ARGUMENT,
+                               "msda_add_layernorm_backward_f32_bf16res: null pointer or residual / grad_residual not 8-byte aligned");
+    msda::begin_call();
+    if (rows == 0) {
+        hipError_t e = hipMemsetAsync(grad_gamma, 0, sizeof(float) * (size_t)d, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemsetAsync(grad_beta, 0, sizeof(float) * (size_t)d, (hipStream_t)stream);
+        return e == hipSuccess ? MSDA_OK : msda::set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
+    }
+    return msda::launch_add_layernorm_bwd_bf16res(grad_y, x, residual, gamma, mean, rstd, rows, d, grad_x, grad_residual, grad_gamma,
+                                                  grad_beta, static_cast<float *>(workspace), (hipStream_t)stream);
+}
+
 int msda_cast_bf16_multi_f32(int count, const float *const *src, uint16_t *const *dst, const long long *n, msda_stream_t stream)
 {
     if (count < 1 || count > 4 || src == nullptr || dst == nullptr || n == nullptr)

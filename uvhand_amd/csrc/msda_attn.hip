@@ -351,10 +351,303 @@ static bool at_view_ok(const AtView &v)
     return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 3) == 0 && (v.sl & 3) == 0;
 }
 
+
+// ---- bf16 operands (msda_attn32_*_bf16) ------------------------------------------------------------------------------------------
+// The same three kernels and the same work split with q, k, v, out, dO and the gradients in bf16 and every product on
+// v_mfma_f32_16x16x32_bf16 (fp32 accumulate): one instruction covers a 16 x 16 score tile's whole head dimension.  Softmax,
+// log-sum-exp, delta = <dO, O> and dP stay fp32; P (forward, dV) and dS (dK, dQ) are rounded to bf16 only as the operands of
+// the products that sum over them; out and the gradients are rounded once.  The pair's operands sit in LDS as bf16 rows
+// ([rows][40]: 80-byte rows, 16-byte aligned) and are read two ways: a row (8 channels of one key / query) with one
+// ds_read_b128 as the operand of the products over channels, and transposed (4 keys / queries of one channel) with
+// ds_read_b64_tr_b16 as the operand of the products over keys / queries.  Every kernel keeps its loops wave-uniform: the
+// transposed read needs all 64 lanes active.  LDS <= 2 * 320 * 80 B + 2 * 320 * 4 B = 53.8 KB: no opt-in.
+//
+// Relabelling.  A bf16 operand holds 8 consecutive k per lane (k = 8 (lane >> 4) + j), an accumulator 4 rows per lane (4 (lane >> 4)
+// + v).  The score tiles come in pairs b = 0, 1 covering 32 keys (or queries) 32T .. 32T + 31, and tile b's row i is taken to
+// be key 32T + 8 (i >> 2) + 4b + (i & 3): the row operand of the first product is read for that key, so the accumulators of the
+// pair give lane (c, r) keys 32T + 8r + j in natural order (j = 4b + v) — exactly the 8 k of the next product's operand.
+// Padding: rows up to a multiple of 32 are zero in LDS; padding keys get -inf scores / zero probabilities, padding queries
+// an lse of +inf.  The dropout hash takes the real (query, key) indices: the mask is the fp32 kernels' bit for bit.
+constexpr int kAbRow = 40;
+using at_bf8 = __attribute__((ext_vector_type(8))) __bf16;
+using at_bf4 = __attribute__((ext_vector_type(4))) __bf16;
+typedef __attribute__((address_space(3))) at_bf4 at_lds_bf4;
+
+__device__ __forceinline__ at_bf8 ab_ld8(const uint16_t *p) { return *reinterpret_cast<const at_bf8 *>(p); }
+__device__ __forceinline__ at_bf8 ab_zero8() { return at_bf8{}; }
+__device__ __forceinline__ float ab_f(__bf16 x) { return (float)x; }
+
+// rows [0, L) of two [L][32] bf16 slices -> dst0 / dst1 [Lp][kAbRow]; rows [L, Lp) zero (Lp * 4 16-byte chunks per slice)
+__device__ __forceinline__ void ab_load_rows2(uint16_t *dst0, const uint16_t *src0, long long sl0, uint16_t *dst1,
+                                              const uint16_t *src1, long long sl1, int L, int Lp)
+{
+    constexpr int R = (kAtMaxLen * 4 + kAtBlock - 1) / kAtBlock;
+    at_bf8 v0[R], v1[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int i = threadIdx.x + k * kAtBlock, row = i >> 2, c = (i & 3) * 8;
+        const bool live = row < L;
+        v0[k] = live ? ab_ld8(src0 + (long long)row * sl0 + c) : ab_zero8();
+        v1[k] = live ? ab_ld8(src1 + (long long)row * sl1 + c) : ab_zero8();
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int i = threadIdx.x + k * kAtBlock, row = i >> 2, c = (i & 3) * 8;
+        if (row < Lp) {
+            *reinterpret_cast<at_bf8 *>(dst0 + row * kAbRow + c) = v0[k];
+            *reinterpret_cast<at_bf8 *>(dst1 + row * kAbRow + c) = v1[k];
+        }
+    }
+}
+
+#define AB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+
+// the score-tile pair T: acc[b] = rows(X) . bop over the 32 channels, X = LDS slice, rows relabelled as above
+__device__ __forceinline__ void ab_pair(const uint16_t *xs, int T, int r, int c, const at_bf8 &bop, at_f4 &acc0, at_f4 &acc1)
+{
+    const uint16_t *row = xs + (32 * T + 8 * (c >> 2) + (c & 3)) * kAbRow + 8 * r;
+    const at_bf8 a0 = ab_ld8(row), a1 = ab_ld8(row + 4 * kAbRow);
+    const at_f4 z = {0.f, 0.f, 0.f, 0.f};
+    acc0 = AB_MFMA(a0, bop, z);
+    acc1 = AB_MFMA(a1, bop, z);
+}
+
+// the transposed operand: lane (c, r) gets X[32T + 8r + j][16 half + c], j = 0..7 (X = LDS slice, rows = keys / queries)
+__device__ __forceinline__ at_bf8 ab_tr(const uint16_t *xs, int T, int half, int r, int c)
+{
+    const uint16_t *p = xs + (32 * T + 8 * r + (c >> 2)) * kAbRow + 16 * half + 4 * (c & 3);
+    const at_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((at_lds_bf4 *)p);
+    const at_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((at_lds_bf4 *)(p + 4 * kAbRow));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ at_bf8 ab_pack(const at_f4 &x0, const at_f4 &x1)
+{
+    return at_bf8{(__bf16)x0[0], (__bf16)x0[1], (__bf16)x0[2], (__bf16)x0[3], (__bf16)x1[0], (__bf16)x1[1], (__bf16)x1[2], (__bf16)x1[3]};
+}
+
+// 4 accumulator values (scaled) -> 4 bf16 at p (8 bytes)
+__device__ __forceinline__ void ab_st4(uint16_t *p, const at_f4 &x, float s)
+{
+    *reinterpret_cast<at_bf4 *>(p) = at_bf4{(__bf16)(x[0] * s), (__bf16)(x[1] * s), (__bf16)(x[2] * s), (__bf16)(x[3] * s)};
+}
+
+struct AbView { uint16_t *p; long long sn, sl; };
+struct AbArgs {
+    AbView q, k, v, o, go, gq, gk, gv;
+    float *lse;
+    const unsigned long long *seed;
+    int H, Lq, Lk;
+    float scale, scale2, keep_scale;
+    unsigned thresh;
+};
+
+__global__ __launch_bounds__(kAtBlock) void attn32_fwd_bf16_kernel(const AbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
+    const int Lkp = (a.Lk + 31) & ~31, npair = Lkp >> 5, ntq = (a.Lq + 15) >> 4;
+    uint16_t *Ks = ab_smem, *Vs = ab_smem + Lkp * kAbRow;
+    const int pair = (int)blockIdx.x, n = pair / a.H, h = pair % a.H;
+    ab_load_rows2(Ks, a.k.p + n * a.k.sn + h * 32, a.k.sl, Vs, a.v.p + n * a.v.sn + h * 32, a.v.sl, a.Lk, Lkp);
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const uint16_t *qp = a.q.p + n * a.q.sn + h * 32;
+    uint16_t *op = a.o.p + n * a.o.sn + h * 32;
+    for (int tq = wave; tq < ntq; tq += kAtWaves) {
+        const int qi = tq * 16 + c;
+        const bool qok = qi < a.Lq;
+        at_bf8 qf = ab_zero8();
+        if (qok) qf = ab_ld8(qp + (long long)qi * a.q.sl + 8 * r);
+        // s[2T + b][v] = score of key 32T + 8r + 4b + v for query qi (raw, then times scale * log2 e)
+        at_f4 s[kAtMaxTiles];
+#pragma unroll
+        for (int T = 0; T < kAtMaxTiles / 2; ++T)
+            if (T < npair) ab_pair(Ks, T, r, c, qf, s[2 * T], s[2 * T + 1]);
+        float m = -INFINITY;
+#pragma unroll
+        for (int T = 0; T < kAtMaxTiles / 2; ++T) {
+            if (T < npair) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float x = s[2 * T + (j >> 2)][j & 3] * a.scale2;        // (base 2, like the fp32 kernels)
+                    if (T == npair - 1) x = 32 * T + 8 * r + j < a.Lk ? x : -INFINITY;
+                    s[2 * T + (j >> 2)][j & 3] = x;
+                    m = fmaxf(m, x);
+                }
+            }
+        }
+        m = at_rmax(m);
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < kAtMaxTiles; ++t) {
+            if (t < 2 * npair) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) { s[t][v] = __builtin_amdgcn_exp2f(s[t][v] - m); sum += s[t][v]; }
+            }
+        }
+        sum = at_rsum(sum);
+        if (qok && r == 0) a.lse[(long long)pair * a.Lq + qi] = (m + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f;
+        const float inv = a.keep_scale / sum;
+        at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+        const unsigned ctr = ((unsigned)qi << 16) + 8 * r + mix;
+#pragma unroll
+        for (int T = 0; T < kAtMaxTiles / 2; ++T) {
+            if (T < npair) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const bool keep = at_hash(ctr + (32 * T + j)) >= a.thresh;
+                    s[2 * T + (j >> 2)][j & 3] = keep ? s[2 * T + (j >> 2)][j & 3] * inv : 0.f;
+                }
+                const at_bf8 pb = ab_pack(s[2 * T], s[2 * T + 1]);          // P^T[key 32T + 8r + j][query qi]
+                o0 = AB_MFMA(ab_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
+                o1 = AB_MFMA(ab_tr(Vs, T, 1, r, c), pb, o1);
+            }
+        }
+        if (qok) {
+            uint16_t *orow = op + (long long)qi * a.o.sl + 4 * r;
+            ab_st4(orow, o0, 1.f);
+            ab_st4(orow + 16, o1, 1.f);
+        }
+    }
+}
+
+// dK, dV: a wavefront owns 16 keys and walks the query pairs
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_bf16_kernel(const AbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
+    const int Lqp = (a.Lq + 31) & ~31, npair = Lqp >> 5, ntk = (a.Lk + 15) >> 4;
+    uint16_t *Qs = ab_smem, *Gs = ab_smem + Lqp * kAbRow;
+    float *lse_s = reinterpret_cast<float *>(Gs + Lqp * kAbRow), *del_s = lse_s + Lqp;
+    const int pair = (int)blockIdx.x, n = pair / a.H, h = pair % a.H;
+    ab_load_rows2(Qs, a.q.p + n * a.q.sn + h * 32, a.q.sl, Gs, a.go.p + n * a.go.sn + h * 32, a.go.sl, a.Lq, Lqp);
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    __syncthreads();
+    for (int qi = threadIdx.x; qi < Lqp; qi += kAtBlock) {
+        float d = 0.f;
+        if (qi < a.Lq) {
+            const uint16_t *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl, *grow = Gs + qi * kAbRow;
+#pragma unroll
+            for (int k8 = 0; k8 < 4; ++k8) {
+                const at_bf8 ov = ab_ld8(orow + 8 * k8), gv = ab_ld8(grow + 8 * k8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d += ab_f(ov[j]) * ab_f(gv[j]);
+            }
+        }
+        del_s[qi] = d;
+        lse_s[qi] = qi < a.Lq ? a.lse[(long long)pair * a.Lq + qi] * 1.4426950408889634f : INFINITY;
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    for (int tk = wave; tk < ntk; tk += kAtWaves) {
+        const int key = tk * 16 + c;
+        const bool kok = key < a.Lk;
+        at_bf8 kf = ab_zero8(), vf = ab_zero8();
+        if (kok) {
+            kf = ab_ld8(a.k.p + n * a.k.sn + h * 32 + (long long)key * a.k.sl + 8 * r);
+            vf = ab_ld8(a.v.p + n * a.v.sn + h * 32 + (long long)key * a.v.sl + 8 * r);
+        }
+        const unsigned ctr = (unsigned)key + ((unsigned)(8 * r) << 16) + mix;
+        at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+#pragma unroll 1
+        for (int T = 0; T < npair; ++T) {
+            // S and dP tiles of the pair: entry (b, v) = (query 32T + 8r + 4b + v, key)
+            at_f4 s[2], dp[2];
+            ab_pair(Qs, T, r, c, kf, s[0], s[1]);
+            ab_pair(Gs, T, r, c, vf, dp[0], dp[1]);
+            const float *lq = lse_s + 32 * T + 8 * r, *dq = del_s + 32 * T + 8 * r;
+            const float4 l0 = *reinterpret_cast<const float4 *>(lq), l1 = *reinterpret_cast<const float4 *>(lq + 4);
+            const float4 d0 = *reinterpret_cast<const float4 *>(dq), d1 = *reinterpret_cast<const float4 *>(dq + 4);
+            const float lsv[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w}, dlv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+            at_f4 pd[2], ds[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int b = j >> 2, v = j & 3;
+                const float p = __builtin_amdgcn_exp2f(fmaf(s[b][v], a.scale2, -lsv[j]));
+                const bool keep = at_hash(ctr + ((unsigned)(32 * T + j) << 16)) >= a.thresh;
+                pd[b][v] = keep ? p * a.keep_scale : 0.f;
+                ds[b][v] = p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - dlv[j]);
+            }
+            const at_bf8 pb = ab_pack(pd[0], pd[1]), sb = ab_pack(ds[0], ds[1]);
+            dv0 = AB_MFMA(ab_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P_drop
+            dv1 = AB_MFMA(ab_tr(Gs, T, 1, r, c), pb, dv1);
+            dk0 = AB_MFMA(ab_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
+            dk1 = AB_MFMA(ab_tr(Qs, T, 1, r, c), sb, dk1);
+        }
+        if (kok) {
+            uint16_t *gvr = a.gv.p + n * a.gv.sn + h * 32 + (long long)key * a.gv.sl + 4 * r;
+            uint16_t *gkr = a.gk.p + n * a.gk.sn + h * 32 + (long long)key * a.gk.sl + 4 * r;
+            ab_st4(gvr, dv0, 1.f); ab_st4(gvr + 16, dv1, 1.f);
+            ab_st4(gkr, dk0, a.scale); ab_st4(gkr + 16, dk1, a.scale);
+        }
+    }
+}
+
+// dQ: a wavefront owns 16 queries and walks the key pairs
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_bf16_kernel(const AbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
+    const int Lkp = (a.Lk + 31) & ~31, npair = Lkp >> 5, ntq = (a.Lq + 15) >> 4;
+    uint16_t *Ks = ab_smem, *Vs = ab_smem + Lkp * kAbRow;
+    const int pair = (int)blockIdx.x, n = pair / a.H, h = pair % a.H;
+    ab_load_rows2(Ks, a.k.p + n * a.k.sn + h * 32, a.k.sl, Vs, a.v.p + n * a.v.sn + h * 32, a.v.sl, a.Lk, Lkp);
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    for (int tq = wave; tq < ntq; tq += kAtWaves) {
+        const int qi = tq * 16 + c;
+        const bool qok = qi < a.Lq;
+        at_bf8 qf = ab_zero8(), gf = ab_zero8(), of = ab_zero8();
+        float lse = INFINITY;
+        if (qok) {
+            qf = ab_ld8(a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 8 * r);
+            gf = ab_ld8(a.go.p + n * a.go.sn + h * 32 + (long long)qi * a.go.sl + 8 * r);
+            of = ab_ld8(a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 8 * r);
+            lse = a.lse[(long long)pair * a.Lq + qi] * 1.4426950408889634f;
+        }
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += ab_f(gf[j]) * ab_f(of[j]);
+        const float delta = at_rsum(d);
+        const unsigned ctr = ((unsigned)qi << 16) + 8 * r + mix;
+        at_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+#pragma unroll 1
+        for (int T = 0; T < npair; ++T) {
+            // S^T and dP^T tiles of the pair: entry (b, v) = (key 32T + 8r + 4b + v, query qi)
+            at_f4 s[2], dp[2];
+            ab_pair(Ks, T, r, c, qf, s[0], s[1]);
+            ab_pair(Vs, T, r, c, gf, dp[0], dp[1]);
+            at_f4 ds[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int b = j >> 2, v = j & 3;
+                float p = __builtin_amdgcn_exp2f(fmaf(s[b][v], a.scale2, -lse));
+                p = 32 * T + 8 * r + j < a.Lk ? p : 0.f;
+                const bool keep = at_hash(ctr + (32 * T + j)) >= a.thresh;
+                ds[b][v] = p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - delta);
+            }
+            const at_bf8 sb = ab_pack(ds[0], ds[1]);
+            dq0 = AB_MFMA(ab_tr(Ks, T, 0, r, c), sb, dq0);                  // dQ^T[channel][query] += K^T . dS^T
+            dq1 = AB_MFMA(ab_tr(Ks, T, 1, r, c), sb, dq1);
+        }
+        if (qok) {
+            uint16_t *gq = a.gq.p + n * a.gq.sn + h * 32 + (long long)qi * a.gq.sl + 4 * r;
+            ab_st4(gq, dq0, a.scale); ab_st4(gq + 16, dq1, a.scale);
+        }
+    }
+}
+
+static bool ab_view_ok(const AbView &v)
+{
+    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 7) == 0 && (v.sl & 7) == 0;
+}
+
 }  // namespace msda
 
 using msda::AtArgs;
 using msda::AtView;
+using msda::AbArgs;
+using msda::AbView;
 
 extern "C" {
 
@@ -420,6 +713,61 @@ int msda_attn32_backward_f32(const float *q, long long q_sn, long long q_sl, con
     if (int rc = msda::check_launch("msda attention backward (dK, dV)")) return rc;
     hipLaunchKernelGGL(msda::attn32_bwd_q_kernel, grid, dim3(msda::kAtBlock), lds_q, (hipStream_t)stream, a);
     return msda::check_launch("msda attention backward (dQ)");
+}
+
+// bf16 operands: the same checks (all of them before any launch), the fp32 entries' random stream
+static int ab_fill(AbArgs &a, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p, const unsigned long long *seed)
+{
+    AtArgs t{};
+    if (int rc = at_fill(t, who, N, H, Lq, Lk, scale, dropout_p, seed)) return rc;
+    a.H = t.H; a.Lq = t.Lq; a.Lk = t.Lk; a.scale = t.scale; a.scale2 = t.scale2; a.keep_scale = t.keep_scale; a.thresh = t.thresh;
+    a.seed = t.seed;
+    return MSDA_OK;
+}
+
+int msda_attn32_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                             const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                             float dropout_p, const unsigned long long *seed, uint16_t *out, long long o_sn, long long o_sl,
+                             float *lse, msda_stream_t stream)
+{
+    AbArgs a{};
+    if (int rc = ab_fill(a, "msda_attn32_forward_bf16: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq,
+                         Lk, scale, dropout_p, seed)) return rc;
+    a.q = AbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AbView{const_cast<uint16_t *>(k), k_sn, k_sl};
+    a.v = AbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AbView{out, o_sn, o_sl}; a.lse = lse;
+    if (!msda::ab_view_ok(a.q) || !msda::ab_view_ok(a.k) || !msda::ab_view_ok(a.v) || !msda::ab_view_ok(a.o) || lse == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_forward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
+    const size_t lds = (size_t)2 * ((Lk + 31) & ~31) * msda::kAbRow * sizeof(uint16_t);
+    hipLaunchKernelGGL(msda::attn32_fwd_bf16_kernel, dim3((unsigned)(N * H)), dim3(msda::kAtBlock), lds, (hipStream_t)stream, a);
+    return msda::check_launch("msda attention forward (head_dim 32, bf16)");
+}
+
+int msda_attn32_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                              const uint16_t *v, long long v_sn, long long v_sl, const uint16_t *out, long long o_sn, long long o_sl,
+                              const float *lse, const uint16_t *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                              int Lk, float scale, float dropout_p, const unsigned long long *seed, uint16_t *grad_q,
+                              long long gq_sn, long long gq_sl, uint16_t *grad_k, long long gk_sn, long long gk_sl,
+                              uint16_t *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream)
+{
+    AbArgs a{};
+    if (int rc = ab_fill(a, "msda_attn32_backward_bf16: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq,
+                         Lk, scale, dropout_p, seed)) return rc;
+    a.q = AbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AbView{const_cast<uint16_t *>(k), k_sn, k_sl};
+    a.v = AbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AbView{const_cast<uint16_t *>(out), o_sn, o_sl};
+    a.go = AbView{const_cast<uint16_t *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
+    a.gq = AbView{grad_q, gq_sn, gq_sl}; a.gk = AbView{grad_k, gk_sn, gk_sl}; a.gv = AbView{grad_v, gv_sn, gv_sl};
+    for (const AbView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
+        if (!msda::ab_view_ok(*w))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
+    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_bf16: lse required");
+    const int Lqp = (Lq + 31) & ~31, Lkp = (Lk + 31) & ~31;
+    const size_t lds_kv = (size_t)2 * Lqp * msda::kAbRow * sizeof(uint16_t) + (size_t)2 * Lqp * sizeof(float);
+    const size_t lds_q = (size_t)2 * Lkp * msda::kAbRow * sizeof(uint16_t);
+    const dim3 grid((unsigned)(N * H));
+    hipLaunchKernelGGL(msda::attn32_bwd_kv_bf16_kernel, grid, dim3(msda::kAtBlock), lds_kv, (hipStream_t)stream, a);
+    if (int rc = msda::check_launch("msda attention backward (dK, dV; bf16)")) return rc;
+    hipLaunchKernelGGL(msda::attn32_bwd_q_bf16_kernel, grid, dim3(msda::kAtBlock), lds_q, (hipStream_t)stream, a);
+    return msda::check_launch("msda attention backward (dQ; bf16)");
 }
 
 }  // extern "C"

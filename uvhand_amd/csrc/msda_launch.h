@@ -144,6 +144,11 @@ int launch_add_layernorm_fwd(const float *x, const float *res, const float *gamm
 int launch_add_layernorm_bwd(const float *dy, const float *x, const float *res, const float *gamma, const float *mean,
                              const float *rstd, long long rows, int d, float *ds, float *dgamma, float *dbeta, float *workspace,
                              hipStream_t stream);
+int launch_add_layernorm_fwd_bf16res(const float *x, const uint16_t *res, const float *gamma, const float *beta, long long rows,
+                                     int d, float eps, float *y, float *mean, float *rstd, hipStream_t stream);
+int launch_add_layernorm_bwd_bf16res(const float *dy, const float *x, const uint16_t *res, const float *gamma, const float *mean,
+                                     const float *rstd, long long rows, int d, float *ds, uint16_t *ds_bf16, float *dgamma,
+                                     float *dbeta, float *workspace, hipStream_t stream);
 
 // ---- FFN of the layers: backward of dropout(relu(h)) in one in-place pass (msda_layernorm.hip) ----
 int launch_relu_dropout_bwd(float *grad, const float *act, float scale, long long n, hipStream_t stream);

@@ -26,17 +26,25 @@ constexpr int kLnWaves = kLnBlock / kWave;
 constexpr int kLnMaxVec = 4;                      // float4 per lane: d <= 1024
 
 __device__ __forceinline__ float4 ld_f4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+// residual rows: fp32, or bf16 widened exactly (msda_add_layernorm_*_f32_bf16res: the bf16 output of a projection under autocast)
+__device__ __forceinline__ float4 ld_f4(const uint16_t *p)
+{
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+}
 
-template <int NV>
+template <int NV, typename R>
 __global__ __launch_bounds__(kLnBlock) void add_layernorm_fwd_kernel(
-    const float *__restrict__ x, const float *__restrict__ res, const float *__restrict__ gamma,
+    const float *__restrict__ x, const R *__restrict__ res, const float *__restrict__ gamma,
     const float *__restrict__ beta, long long rows, int d, float eps, float *__restrict__ y,
     float *__restrict__ mean_out, float *__restrict__ rstd_out)
 {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * kLnWaves + wave;
     if (row >= rows) return;                                             // whole wavefront leaves together
-    const float *xr = x + row * d, *rr = res ? res + row * d : nullptr;
+    const float *xr = x + row * d;
+    const R *rr = res ? res + row * d : nullptr;
     float4 v[NV];
     float sum = 0.f;
 #pragma unroll
@@ -75,12 +83,13 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_fwd_kernel(
 }
 
 // Workgroup w owns the rows [w * rows_per_wg, (w+1) * rows_per_wg); its 4 wavefronts take them round-robin and keep
-// the dgamma / dbeta column sums of their rows in registers; partial[w][2][d] is the workgroup's total.
-template <int NV>
+// the dgamma / dbeta column sums of their rows in registers; partial[w][2][d] is the workgroup's total.  ds_bf16 (bf16 residual
+// only; may be null): the same gradient rounded to bf16, written in the same pass.
+template <int NV, typename R>
 __global__ __launch_bounds__(kLnBlock) void add_layernorm_bwd_kernel(
-    const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ res,
+    const float *__restrict__ dy, const float *__restrict__ x, const R *__restrict__ res,
     const float *__restrict__ gamma, const float *__restrict__ mean_in, const float *__restrict__ rstd_in,
-    long long rows, int d, int rows_per_wg, float *__restrict__ ds, float *__restrict__ partial)
+    long long rows, int d, int rows_per_wg, float *__restrict__ ds, uint16_t *__restrict__ ds_bf16, float *__restrict__ partial)
 {
     __shared__ __attribute__((aligned(16))) float red[kLnWaves][2][kLnMaxVec * kWave * 4];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -95,7 +104,8 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_bwd_kernel(
     }
     for (long long row = r0 + wave; row < r1; row += kLnWaves) {
         const float mean = mean_in[row], rstd = rstd_in[row];
-        const float *xr = x + row * d, *rr = res ? res + row * d : nullptr, *gr = dy + row * d;
+        const float *xr = x + row * d, *gr = dy + row * d;
+        const R *rr = res ? res + row * d : nullptr;
         float4 xh[NV], g[NV];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -123,6 +133,10 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_bwd_kernel(
                 o.x = rstd * (g[k].x - c1 - xh[k].x * c2); o.y = rstd * (g[k].y - c1 - xh[k].y * c2);
                 o.z = rstd * (g[k].z - c1 - xh[k].z * c2); o.w = rstd * (g[k].w - c1 - xh[k].w * c2);
                 *reinterpret_cast<float4 *>(ds + row * d + c) = o;
+                if (sizeof(R) == 2 && ds_bf16) {                         // (folds away for an fp32 residual)
+                    typedef __attribute__((ext_vector_type(4))) __bf16 bf4;
+                    *reinterpret_cast<bf4 *>(ds_bf16 + row * d + c) = bf4{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
+                }
             }
         }
     }
@@ -178,28 +192,56 @@ static int ln_bwd_wgs(long long rows)
 
 size_t add_layernorm_workspace_bytes(long long rows, int d) { return (size_t)ln_bwd_wgs(rows) * 2 * d * sizeof(float); }
 
-int launch_add_layernorm_fwd(const float *x, const float *res, const float *gamma, const float *beta, long long rows, int d,
-                             float eps, float *y, float *mean, float *rstd, hipStream_t stream)
+template <typename R>
+static int ln_fwd(const float *x, const R *res, const float *gamma, const float *beta, long long rows, int d, float eps, float *y,
+                  float *mean, float *rstd, hipStream_t stream)
 {
     const dim3 grid((unsigned)((rows + kLnWaves - 1) / kLnWaves)), block(kLnBlock);
-#define MSDA_LN_F(NV) hipLaunchKernelGGL((add_layernorm_fwd_kernel<NV>), grid, block, 0, stream, x, res, gamma, beta, rows, d, eps, y, mean, rstd)
+#define MSDA_LN_F(NV) hipLaunchKernelGGL((add_layernorm_fwd_kernel<NV, R>), grid, block, 0, stream, x, res, gamma, beta, rows, d, eps, y, mean, rstd)
     if (d <= 256) MSDA_LN_F(1); else if (d <= 512) MSDA_LN_F(2); else MSDA_LN_F(4);
 #undef MSDA_LN_F
     return check_launch("msda add+layernorm forward");
+}
+
+int launch_add_layernorm_fwd(const float *x, const float *res, const float *gamma, const float *beta, long long rows, int d,
+                             float eps, float *y, float *mean, float *rstd, hipStream_t stream)
+{
+    return ln_fwd(x, res, gamma, beta, rows, d, eps, y, mean, rstd, stream);
+}
+
+int launch_add_layernorm_fwd_bf16res(const float *x, const uint16_t *res, const float *gamma, const float *beta, long long rows,
+                                     int d, float eps, float *y, float *mean, float *rstd, hipStream_t stream)
+{
+    return ln_fwd(x, res, gamma, beta, rows, d, eps, y, mean, rstd, stream);
+}
+
+template <typename R>
+static int ln_bwd(const float *dy, const float *x, const R *res, const float *gamma, const float *mean, const float *rstd,
+                  long long rows, int d, float *ds, uint16_t *ds_bf16, float *dgamma, float *dbeta, float *workspace,
+                  hipStream_t stream)
+{
+    const int nwg = ln_bwd_wgs(rows);
+    const int rows_per_wg = (int)((rows + nwg - 1) / nwg);
+#define MSDA_LN_B(NV) hipLaunchKernelGGL((add_layernorm_bwd_kernel<NV, R>), dim3(nwg), dim3(kLnBlock), 0, stream, dy, x, res, gamma, mean, rstd, rows, d, rows_per_wg, ds, ds_bf16, workspace)
+    if (d <= 256) MSDA_LN_B(1); else if (d <= 512) MSDA_LN_B(2); else MSDA_LN_B(4);
+#undef MSDA_LN_B
+    if (int rc = check_launch("msda add+layernorm backward")) return rc;
+    hipLaunchKernelGGL(layernorm_param_reduce_kernel, dim3((d + 15) / 16, 2), dim3(256), 0, stream, workspace, nwg, d, dgamma, dbeta);
+    return check_launch("msda layernorm parameter gradients");
 }
 
 int launch_add_layernorm_bwd(const float *dy, const float *x, const float *res, const float *gamma, const float *mean,
                              const float *rstd, long long rows, int d, float *ds, float *dgamma, float *dbeta, float *workspace,
                              hipStream_t stream)
 {
-    const int nwg = ln_bwd_wgs(rows);
-    const int rows_per_wg = (int)((rows + nwg - 1) / nwg);
-#define MSDA_LN_B(NV) hipLaunchKernelGGL((add_layernorm_bwd_kernel<NV>), dim3(nwg), dim3(kLnBlock), 0, stream, dy, x, res, gamma, mean, rstd, rows, d, rows_per_wg, ds, workspace)
-    if (d <= 256) MSDA_LN_B(1); else if (d <= 512) MSDA_LN_B(2); else MSDA_LN_B(4);
-#undef MSDA_LN_B
-    if (int rc = check_launch("msda add+layernorm backward")) return rc;
-    hipLaunchKernelGGL(layernorm_param_reduce_kernel, dim3((d + 15) / 16, 2), dim3(256), 0, stream, workspace, nwg, d, dgamma, dbeta);
-    return check_launch("msda layernorm parameter gradients");
+    return ln_bwd(dy, x, res, gamma, mean, rstd, rows, d, ds, nullptr, dgamma, dbeta, workspace, stream);
+}
+
+int launch_add_layernorm_bwd_bf16res(const float *dy, const float *x, const uint16_t *res, const float *gamma, const float *mean,
+                                     const float *rstd, long long rows, int d, float *ds, uint16_t *ds_bf16, float *dgamma,
+                                     float *dbeta, float *workspace, hipStream_t stream)
+{
+    return ln_bwd(dy, x, res, gamma, mean, rstd, rows, d, ds, ds_bf16, dgamma, dbeta, workspace, stream);
 }
 
 // ---- FFN of the layers (models/arctic_transformer.py:283-287, :366-370): linear2(dropout(relu(linear1(x)))) ----------------

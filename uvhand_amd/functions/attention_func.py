@@ -1,7 +1,7 @@
 """Decoder self-attention of the drop-in layers (UVHand models/arctic_transformer.py:351, :374-376:
 ``nn.MultiheadAttention(d_model, n_heads, dropout)`` called sequence-first with q = k = tgt + query_pos, v = tgt, no masks) with
 the attention core — ``dropout(softmax(q k^T / sqrt(d))) v`` — on the library's own kernels (msda_attn32_*_f32, include/msda.h)
-when it fits them: head_dim 32, at most 320 queries, fp32, no masks.  The module, its parameters and state_dict keys stay
+when it fits them: head_dim 32, at most 320 queries, fp32 inputs outside autocast or under bf16 autocast, no masks.  The module, its parameters and state_dict keys stay
 ``nn.MultiheadAttention``'s; the in- and out-projections are ``nn.Linear``'s arithmetic on the module's own weights (q and k share
 their input, so their two projections are ONE GEMM on the first two thirds of ``in_proj_weight``), with the weight gradients on the
 library's MFMA kernel like every other projection of the drop-in layers (``functions/linear_func.py``).
@@ -9,7 +9,13 @@ library's MFMA kernel like every other projection of the drop-in layers (``funct
 What differs from the stock module: no [N*heads, L, L] tensor is ever written (scores, probabilities, dropout mask), and the
 attention dropout draws its mask from the kernel's own hash of (seed, head, query, key) — the seed comes from torch's generator
 (one ``random_()`` on a device scalar: reproducible under ``manual_seed``, capturable in a HIP graph), the stream is not
-``nn.functional.dropout``'s.  Anything the kernels do not take goes to the module itself."""
+``nn.functional.dropout``'s.  Anything the kernels do not take goes to the module itself.
+
+Under ``torch.autocast("cuda", dtype=torch.bfloat16)`` the inputs are still the fp32 residual stream; the projections take their
+amp path and return bf16, and the core runs on the bf16 kernels (msda_attn32_*_bf16): bf16 operands, fp32 softmax and
+accumulation, bf16 output and bf16 gradients of the projections' outputs — the dtypes the stock module has under the same
+autocast.  The attention dropout then draws from the same kernel hash (for one seed the bf16 and fp32 cores drop the same
+entries), not from ``nn.functional.dropout``.  fp16 autocast stays with the module."""
 import math
 
 import torch
@@ -18,11 +24,11 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _native as MSDA
-from .linear_func import bracket_linear_wb
+from .linear_func import _autocast_dtype, bracket_linear_wb
 
 
 class _Attn32Fn(Function):
-    """core(qk [L, N, 2E] = packed q | k projections, v [L, N, E]) -> [L, N, E]"""
+    """core(qk [L, N, 2E] = packed q | k projections, v [L, N, E]) -> [L, N, E]; fp32 or bf16 (dispatch on qk's dtype)"""
 
     @staticmethod
     def forward(ctx, qk, v, heads, dropout_p):
@@ -42,6 +48,8 @@ class _Attn32Fn(Function):
         seed = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
         E = v.shape[2]
         g_qk = torch.empty_like(qk, memory_format=torch.contiguous_format)
+        if grad_out.dtype != qk.dtype:                   # (the core's output type: fp32, or bf16 under autocast)
+            grad_out = grad_out.to(qk.dtype)
         _, _, g_v = MSDA.attn32_backward(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, ctx.scale, ctx.dropout_p, seed,
                                          grad_q=g_qk[..., :E], grad_k=g_qk[..., E:])
         return g_qk, g_v, None, None
@@ -52,7 +60,8 @@ def _takes(mha, x_qk, x_v):
     return (type(mha) is nn.MultiheadAttention and mha._qkv_same_embed_dim and not mha.batch_first and mha.bias_k is None
             and mha.bias_v is None and not mha.add_zero_attn and mha.in_proj_bias is not None and mha.head_dim == 32
             and x_qk.is_cuda and x_qk.dtype == torch.float32 and x_v.dtype == torch.float32 and x_qk.dim() == 3
-            and x_qk.shape == x_v.shape and x_qk.shape[2] == E and not torch.is_autocast_enabled()
+            and x_qk.shape == x_v.shape and x_qk.shape[2] == E
+            and (not torch.is_autocast_enabled() or _autocast_dtype() == torch.bfloat16)
             and MSDA.attn32_supported(x_qk.shape[0], x_v.shape[0], mha.head_dim))
 
 

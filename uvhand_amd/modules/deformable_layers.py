@@ -18,7 +18,8 @@ in the epilogue of linear1's GEMM, PyTorch's own dropout kernel (same random str
 in-place pass, and both weight gradients on the split-M MFMA kernel — with N*S = 33 440 rows per rank at the training shape
 the weight gradient is the GEMM the vendor BLAS runs worst; the decoder's self-attention keeps the ``nn.MultiheadAttention``
 module and its parameters, but unless a hook on ``attn_matrix`` asks for the head-averaged attention matrix (or
-``always_attention_matrix``) its core runs on the library's fp32-MFMA attention kernels (``functions/attention_func.py``).
+``always_attention_matrix``) its core runs on the library's MFMA attention kernels (``functions/attention_func.py``: fp32,
+or bf16 under bf16 autocast, where the add+LayerNorm pairs also take the fp32-x / bf16-residual kernel).
 """
 import copy
 import os
@@ -112,7 +113,8 @@ class DeformableTransformerDecoderLayer(nn.Module):
         q = k = self.with_pos_embed(tgt, query_pos)
         # The head-averaged attention matrix exists for whoever hooks `attn_matrix`; with no hook registered nothing reads it,
         # and the attention core runs without ever writing a [N*heads, L, L] tensor (same values in eval; in training the
-        # attention dropout then draws from that kernel's random stream, not nn.functional.dropout's).
+        # attention dropout then draws from that kernel's random stream, not nn.functional.dropout's — under bf16 autocast
+        # too: the core then runs on the bf16 kernels, with the same mask for the same seed).
         listened = self.always_attention_matrix or _has_listener(self.attn_matrix)
         if listened:
             tgt2, attn_matrix = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1), need_weights=True)

@@ -436,6 +436,38 @@ unsigned long long msda_unflatten_workspace_bytes(int L, const int *heights, con
 
 const char *msda_last_error(void);
 
+/* ---- Two-stage query selection of the transformer (models/arctic_transformer.py:91-142, :196-232) ----------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the five entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ *   msda_two_stage_proposals_f32  gen_encoder_output_proposals (:106-142), forward: memory [N, S, C] fp32 (C % 4 == 0,
+ *       16-byte aligned), padding_mask [N, S] bytes (non-zero = padded), the L levels' heights / widths as HOST int arrays
+ *       (S must be their sum of H*W), learnedxy [40] fp32 device or NULL (= 0.05 * 2^lvl).  Writes proposals [N, S, 42]
+ *       (logits; +inf at padded rows and rows outside (0.01, 0.99)), memory_out [N, S, C] (memory, those rows zeroed) and
+ *       row_mask [N, S] (1 at those rows).  Per level the valid extent is counted on the mask's first column / first row.
+ *   msda_two_stage_select_f32     the query selection (:208-232): cls [N, S, K], hand / obj / proposals [N, S, 42]; per frame
+ *       the top Q rows by the max class logit, descending (ties: lower row index first; NaN above every number), the class
+ *       argmax of each (first maximum; NaN wins) picks the source: hand if it is hand_class0 / hand_class1, object if it
+ *       is neither and not 0, the proposal otherwise.  Writes topk [N, Q] int64 (may be NULL), refpoint_unsig [N, Q, 42]
+ *       and reference_points = sigmoid(refpoint_unsig) * 2 - 1.  One launch, no synchronisation.  Q > S and
+ *       S > 8192 return MSDA_ERR_ARGUMENT; msda_two_stage_select_supported(S, K, Q) tells beforehand (1 = the call runs).
+ *   msda_proposal_pos_embed_f32   get_proposal_pos_embed (:91-104): pe [M, 5376] from refpoint_unsig [M, 42];
+ *       pe[m, 128c + 2i + s] = s ? cos(u) : sin(u), u = sigmoid(r[m, c]) * 2pi / dim_t[i], dim_t [64] = torch's table at
+ *       even indices (:96-97).  pe 16-byte aligned.
+ *   msda_proposal_pos_linear_relu_f32  y [M, out] = relu(pe(r) @ weight^T + bias) with weight [out, 5376] (out % 4 == 0,
+ *       16-byte aligned), bias [out] or NULL — pos_trans[0:2] without the [M, 5376] table in memory; fp32 MFMA, fixed
+ *       summation order. */
+int msda_two_stage_proposals_f32(const float *memory, const uint8_t *padding_mask, int N, int S, int C, int L, const int *heights,
+                                 const int *widths, const float *learnedxy, float *proposals, float *memory_out, uint8_t *row_mask,
+                                 msda_stream_t stream);
+int msda_two_stage_select_supported(int S, int K, int Q);
+int msda_two_stage_select_f32(const float *cls, const float *hand, const float *obj, const float *proposals, int N, int S, int K,
+                              int Q, int hand_class0, int hand_class1, int64_t *topk, float *refpoint_unsig,
+                              float *reference_points, msda_stream_t stream);
+int msda_proposal_pos_embed_f32(const float *refpoint_unsig, const float *dim_t, long long M, float *pe, msda_stream_t stream);
+int msda_proposal_pos_linear_relu_f32(const float *refpoint_unsig, const float *dim_t, const float *weight, const float *bias,
+                                      long long M, int out_features, float *y, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

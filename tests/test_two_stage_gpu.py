@@ -1,0 +1,236 @@
+"""The two-stage kernels (csrc/msda_two_stage.hip) on the GPU: proposals against the reference formula in fp64, the query
+selection against the torch.topk composition (bitwise: gathers plus sigmoid), no host synchronisation and graph capture,
+the proposal embedding against fp64, and the fused pos_trans[0] node against fp64 at the cfg-2 / cfg-4 row counts."""
+import math
+
+import pytest
+import torch
+from torch import nn
+
+from uvhand_amd import _native as MSDA
+from uvhand_amd.functions import two_stage_func as TS
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+PE_BOUND = 2e-6                        # |PE - fp64|
+
+
+def _mask(N, hw, g):
+    parts = []
+    for (h, w) in hw:
+        m = torch.zeros(N, h, w, dtype=torch.bool)
+        for n in range(1, N):
+            m[n, :, w - 1 - (n % max(1, w // 2)):] = True
+            m[n, h - 1 - (n % max(1, h // 2)):, :] = True
+        m[0, 0, w - max(1, w // 3):] = True                 # ragged first row: valid width from the first row only
+        if h > 2:
+            m[0, 2, 0] = True                               # a padded pixel outside the first row / column
+        parts.append(m.flatten(1))
+    return torch.cat(parts, 1)
+
+
+@pytest.mark.parametrize("learn", [True, False])
+def test_proposals_match_fp64_formula(learn):
+    g = torch.Generator().manual_seed(5)
+    hw = [(28, 28), (14, 14), (7, 7), (4, 4)]
+    N, C = 3, 256
+    S = sum(h * w for h, w in hw)
+    memory = torch.randn(N, S, C, generator=g)
+    mask = _mask(N, hw, g)
+    xy = (torch.randn(40, generator=g) * 0.5 - 2.9) if learn else None
+    mem_d = memory.to(DEV).requires_grad_(True)
+    xy_d = xy.to(DEV).requires_grad_(True) if learn else None
+    out_mem, props = TS.encoder_output_proposals(mem_d, mask.to(DEV), hw, xy_d)
+    ref_mem, ref_props = TS.proposals_composition(memory.double(), mask, hw, xy.double() if learn else None)
+    got = props.cpu().double()
+    inf_ref = torch.isinf(ref_props)
+    assert torch.equal(torch.isinf(got), inf_ref)
+    assert (got[inf_ref] > 0).all()
+    assert inf_ref.all(-1).sum() > mask.sum()            # rows outside (0.01, 0.99) besides the padded ones
+    assert (got[~inf_ref] - ref_props[~inf_ref]).abs().max() < 2e-6
+    assert torch.equal(out_mem.cpu().double(), ref_mem)
+    go = torch.randn(N, S, C, generator=g).to(DEV)
+    torch.autograd.backward([out_mem], [go])
+    dead = inf_ref.all(-1)
+    exp = go.cpu().masked_fill(dead.unsqueeze(-1), 0.0)
+    assert torch.equal(mem_d.grad.cpu(), exp)
+    if learn:
+        assert xy_d.grad is not None and torch.count_nonzero(xy_d.grad) == 0
+
+
+def _select_inputs(N, S, K, seed, ties=False):
+    g = torch.Generator().manual_seed(seed)
+    cls = torch.randn(N, S, K, generator=g)
+    if ties:
+        cls = (cls * 2).round() / 2                          # many equal maxima
+    cls[..., 12] += 0.3                                      # make every branch occur
+    hand, obj, prop = (torch.randn(N, S, 42, generator=g) for _ in range(3))
+    prop[:, ::17] = float("inf")
+    return [t.to(DEV) for t in (cls, hand, obj, prop)]
+
+
+@pytest.mark.parametrize("N,S,Q", [(2, 1045, 300), (4, 3060, 300), (1, 8192, 300), (2, 300, 300)])
+def test_selection_matches_topk_composition_bitwise(N, S, Q):
+    cls, hand, obj, prop = _select_inputs(N, S, 14, 7 + S)
+    ref, refp, idx = TS.select_queries(cls, hand, obj, prop, Q, return_indices=True)
+    tk = torch.topk(cls.max(-1)[0], Q, dim=1)[1]
+    c_ref, c_refp = TS.select_composition(cls, hand, obj, prop, Q)
+    assert torch.equal(idx, tk)
+    assert torch.equal(ref, c_ref)
+    assert torch.equal(refp, c_refp)
+
+
+def test_selection_with_ties_selects_the_same_multiset():
+    cls, hand, obj, prop = _select_inputs(2, 1045, 14, 11, ties=True)
+    _, _, idx = TS.select_queries(cls, hand, obj, prop, 300, return_indices=True)
+    mx = cls.max(-1)[0]
+    got = torch.gather(mx, 1, idx)
+    ref = torch.topk(mx, 300, dim=1)[0]
+    assert torch.equal(got, ref)                               # same values, same (descending) order
+    for n in range(2):                                         # ties: lower row index first
+        same = got[n, 1:] == got[n, :-1]
+        assert (idx[n, 1:][same] > idx[n, :-1][same]).all()
+
+
+def test_selection_q_above_s_raises():
+    cls, hand, obj, prop = _select_inputs(1, 100, 14, 1)
+    with pytest.raises(RuntimeError):
+        TS.select_queries(cls, hand, obj, prop, 101)
+
+
+def _pos_trans(seed=0):
+    torch.manual_seed(seed)
+    pt = nn.Sequential(nn.Linear(5376, 1024), nn.ReLU(), nn.Linear(1024, 1024), nn.ReLU(), nn.Linear(1024, 512), nn.ReLU())
+    return pt.to(DEV), nn.LayerNorm(512).to(DEV)
+
+
+def test_selection_no_sync_and_graph_capture():
+    cls, hand, obj, prop = _select_inputs(2, 1045, 14, 3)
+    pt, norm = _pos_trans()
+    TS.select_queries(cls, hand, obj, prop, 300)              # warm up (library load, allocations)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        ref, refp = TS.select_queries(cls, hand, obj, prop, 300)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    r2 = ref.reshape(-1, 42)
+    lin = pt[0]
+    with torch.no_grad():
+        y_eager = TS.pos_embed_linear_relu(r2, lin)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                TS.select_queries(cls, hand, obj, prop, 300)
+                TS.pos_embed_linear_relu(r2, lin)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            g_ref, g_refp = TS.select_queries(cls, hand, obj, prop, 300)
+            g_y = TS.pos_embed_linear_relu(g_ref.reshape(-1, 42), lin)
+        graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(g_ref, ref) and torch.equal(g_refp, refp) and torch.equal(g_y, y_eager)
+
+
+def _refpoints(M, seed):
+    g = torch.Generator().manual_seed(seed)
+    r = torch.randn(M, 42, generator=g) * 2.5
+    r[::37] = float("inf")                                     # selected masked proposals
+    return r
+
+
+def _pe64(r):
+    dim_t = TS.pe_dim_t("cpu").double()
+    u = r.double().sigmoid() * (2 * math.pi)
+    pos = u[..., None] / dim_t
+    return torch.stack((pos[..., 0::2].sin(), pos[..., 1::2].cos()), -1).flatten(-3)
+
+
+def test_pe_matches_fp64():
+    r = _refpoints(2000, 1)
+    pe = TS.proposal_pos_embed(r.to(DEV).view(4, 500, 42)).view(2000, -1).cpu().double()
+    err = (pe - _pe64(r)).abs().max().item()
+    print("PE max abs error vs fp64: %.3e" % err)
+    assert err <= PE_BOUND
+    assert torch.allclose(pe.float(), TS.pos_embed_composition(r.to(DEV)).cpu(), atol=1e-6, rtol=0)
+
+
+@pytest.mark.parametrize("M", [600, 9600])
+def test_fused_node_matches_fp64(M):
+    pt, _ = _pos_trans(1)
+    lin = pt[0]
+    r = _refpoints(M, M)
+    rd = r.to(DEV)
+    w = lin.weight.detach().clone().requires_grad_(True)
+    b = lin.bias.detach().clone().requires_grad_(True)
+    dim_t = TS.pe_dim_t(DEV)[0::2].contiguous()
+    y = TS._PosEmbedLinearReluFn.apply(rd, dim_t, w, b)
+    gy = torch.randn(M, 1024, generator=torch.Generator().manual_seed(2)).to(DEV)
+    y.backward(gy)
+    pe = _pe64(r).to(DEV)
+    w64, b64 = lin.weight.detach().double(), lin.bias.detach().double()
+    h = pe @ w64.t() + b64
+    y64 = h.clamp_min(0)
+    gh = gy.double() * (y.detach() > 0)                      # the kernel's ReLU mask: a flip at |h| ~ 1e-6 is not GEMM error
+    gw64, gb64 = gh.t() @ pe, gh.sum(0)
+    for name, got, ref in (("y", y, y64), ("grad_w", w.grad, gw64), ("grad_b", b.grad, gb64)):
+        err = ((got.double() - ref).abs().max() / ref.abs().max()).item()
+        print("M=%d %s: max err / max %.3e" % (M, name, err))
+        assert err < 2e-5, name
+
+
+def test_fused_node_gradients_bitwise_reproducible():
+    pt, _ = _pos_trans(2)
+    lin = pt[0]
+    rd = _refpoints(9600, 3).to(DEV)
+    gy = torch.randn(9600, 1024, device=DEV)
+    grads = []
+    for _ in range(2):
+        lin.zero_grad(set_to_none=True)
+        TS.pos_embed_linear_relu(rd, lin).backward(gy)
+        grads.append((lin.weight.grad.clone(), lin.bias.grad.clone()))
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+
+
+def test_fused_node_saves_no_pe_table():
+    pt, norm = _pos_trans(4)
+    rd = _refpoints(9600, 4).to(DEV).view(32, 300, 42)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        out = fn()
+        torch.cuda.synchronize()
+        retained = torch.cuda.memory_allocated() - base
+        used = torch.cuda.max_memory_allocated() - base
+        del out
+        return used, retained
+
+    fused = peak(lambda: TS.pos_trans_embed(pt, norm, rd))
+    assert TS.pos_trans_fusable(pt, rd)
+    comp = peak(lambda: norm(pt(TS.pos_embed_composition(rd))))
+    print("forward peak / retained MB: fused %.1f / %.1f, composition %.1f / %.1f"
+          % (fused[0] / 2 ** 20, fused[1] / 2 ** 20, comp[0] / 2 ** 20, comp[1] / 2 ** 20))
+    assert comp[0] - fused[0] >= 200e6
+    # what autograd keeps for the node itself: r and the ReLU output, against the [9600, 5376] table and the output
+    lin = pt[0]
+    node = peak(lambda: TS.pos_embed_linear_relu(rd.reshape(-1, 42), lin))
+    stock = peak(lambda: torch.relu(lin(TS.pos_embed_composition(rd.reshape(-1, 42)))))
+    print("pos_trans[0:2] retained MB: fused %.1f, composition %.1f" % (node[1] / 2 ** 20, stock[1] / 2 ** 20))
+    assert stock[1] - node[1] >= 200e6
+
+
+def test_fused_route_conditions():
+    pt, norm = _pos_trans(5)
+    r = _refpoints(60, 5).to(DEV).view(2, 30, 42)
+    assert TS.pos_trans_fusable(pt, r)
+    h = pt[0].register_forward_hook(lambda *a: None)
+    assert not TS.pos_trans_fusable(pt, r)
+    out = TS.pos_trans_embed(pt, norm, r)                      # the Sequential itself: the hook runs
+    h.remove()
+    ref = norm(pt(TS.pos_embed_composition(r)))
+    fused = TS.pos_trans_embed(pt, norm, r)
+    assert torch.allclose(out, ref) and torch.allclose(fused, ref, atol=2e-4, rtol=0)

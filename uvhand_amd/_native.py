@@ -38,6 +38,8 @@ _SYMBOLS = (
     "msda_last_error", "msda_version", "msda_path_for", "msda_force_path", "msda_describe_plan",
     "msda_forward_workspace_bytes", "msda_forward_ws_f32", "msda_forward_ws_bf16", "msda_forward_prologue_ws_f32",
     "msda_forward_prologue_ws_bf16", "msda_probe_row_gather", "msda_launch_count",
+    "msda_two_stage_proposals_f32", "msda_two_stage_select_supported", "msda_two_stage_select_f32",
+    "msda_proposal_pos_embed_f32", "msda_proposal_pos_linear_relu_f32",
 )
 
 
@@ -71,6 +73,8 @@ def load():
     lib.msda_forward_workspace_bytes.restype = ctypes.c_ulonglong
     lib.msda_forward_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_uint]
     lib.msda_launch_count.restype = ctypes.c_ulonglong
+    lib.msda_two_stage_select_supported.restype = ctypes.c_int
+    lib.msda_two_stage_select_supported.argtypes = [ctypes.c_int] * 3
     lib.msda_describe_plan.restype = ctypes.c_int
     lib.msda_describe_plan.argtypes = [ctypes.c_int] * 9 + [ctypes.c_uint, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     _lib = lib
@@ -908,3 +912,102 @@ def force_path(path):
     global _forced_path
     load()
     _forced_path = int(path)
+
+
+# ---- two-stage query selection of the transformer (csrc/msda_two_stage.hip) ----------------------------------------------
+PE_WIDTH = 5376                                       # 42 coordinates x 128 sin / cos features (get_proposal_pos_embed)
+
+
+def _f32_cuda(t):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def two_stage_proposals(memory, padding_mask, level_hw, learnedxy=None):
+    """(proposals [N,S,42], memory_out [N,S,C], row_mask [N,S] bool) — msda_two_stage_proposals_f32: the forward of
+    gen_encoder_output_proposals with `level_hw` the levels' (H, W) as Python ints."""
+    lib = _lib or load()
+    if not (_f32_cuda(memory) and memory.dim() == 3 and padding_mask.dtype == torch.bool and padding_mask.is_contiguous()
+            and padding_mask.device == memory.device and tuple(padding_mask.shape) == tuple(memory.shape[:2])
+            and (learnedxy is None or (_f32_cuda(learnedxy) and learnedxy.numel() == 40 and learnedxy.device == memory.device))):
+        raise RuntimeError("two_stage_proposals: expected contiguous fp32 CUDA memory [N,S,C], a bool mask [N,S] and learnedxy [40] or None")
+    N, S, C = memory.shape
+    L = len(level_hw)
+    hs = (ctypes.c_int * max(1, L))(*[int(h) for h, _ in level_hw])
+    ws = (ctypes.c_int * max(1, L))(*[int(w) for _, w in level_hw])
+    with _DeviceGuard(memory.device):
+        props = torch.empty((N, S, 42), dtype=torch.float32, device=memory.device)
+        mem_out = torch.empty_like(memory)
+        row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
+        rc = _entry(lib, "msda_two_stage_proposals_f32", [_VP, _VP, _CI, _CI, _CI, _CI, _VP, _VP, _VP, _VP, _VP, _VP, _VP])(
+            memory.data_ptr(), padding_mask.data_ptr(), N, S, C, L, ctypes.cast(hs, _VP), ctypes.cast(ws, _VP),
+            learnedxy.data_ptr() if learnedxy is not None else None, props.data_ptr(), mem_out.data_ptr(), row_mask.data_ptr(),
+            _raw_stream(memory.device))
+    if rc != 0:
+        _raise(lib, rc, "two_stage_proposals")
+    return props, mem_out, row_mask
+
+
+def two_stage_select_supported(S, K, Q):
+    """Whether msda_two_stage_select_f32 takes a frame of S rows, K classes and Q queries (S <= 8192, Q <= S)."""
+    return bool((_lib or load()).msda_two_stage_select_supported(int(S), int(K), int(Q)))
+
+
+def two_stage_select(cls, hand, obj, proposals, num_queries, hand_classes=(12, 13)):
+    """(topk [N,Q] int64, refpoint_unsig [N,Q,42], reference_points [N,Q,42]) — msda_two_stage_select_f32: one launch, no
+    host synchronisation.  Raises RuntimeError when Q exceeds the rows per frame (as torch.topk does)."""
+    lib = _lib or load()
+    ts = (cls, hand, obj, proposals)
+    if not (all(_f32_cuda(t) and t.dim() == 3 and t.device == cls.device for t in ts)
+            and all(tuple(t.shape) == tuple(cls.shape[:2]) + (42,) for t in ts[1:])):
+        raise RuntimeError("two_stage_select: expected contiguous fp32 CUDA cls [N,S,K] and hand / obj / proposals [N,S,42]")
+    N, S, K = cls.shape
+    Q = int(num_queries)
+    if Q > S:
+        raise RuntimeError("selected index k out of range")
+    with _DeviceGuard(cls.device):
+        topk = torch.empty((N, Q), dtype=torch.int64, device=cls.device)
+        unsig = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
+        refp = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
+        rc = _entry(lib, "msda_two_stage_select_f32", [_VP] * 4 + [_CI] * 6 + [_VP] * 4)(
+            cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), proposals.data_ptr(), N, S, K, Q, int(hand_classes[0]),
+            int(hand_classes[1]), topk.data_ptr(), unsig.data_ptr(), refp.data_ptr(), _raw_stream(cls.device))
+    if rc != 0:
+        _raise(lib, rc, "two_stage_select")
+    return topk, unsig, refp
+
+
+def _check_pe_inputs(r2, dim_t):
+    if not (_f32_cuda(r2) and r2.dim() == 2 and r2.shape[1] == 42 and _f32_cuda(dim_t) and dim_t.numel() == 64
+            and dim_t.device == r2.device):
+        raise RuntimeError("proposal_pos_embed: expected contiguous fp32 CUDA refpoints [M,42] and dim_t [64]")
+
+
+def proposal_pos_embed(r2, dim_t):
+    """PE [M, 5376] of refpoint_unsig [M, 42] — msda_proposal_pos_embed_f32 (dim_t: torch's table at even indices)."""
+    lib = _lib or load()
+    _check_pe_inputs(r2, dim_t)
+    with _DeviceGuard(r2.device):
+        pe = torch.empty((r2.shape[0], PE_WIDTH), dtype=torch.float32, device=r2.device)
+        rc = _entry(lib, "msda_proposal_pos_embed_f32", [_VP, _VP, _LL, _VP, _VP])(
+            r2.data_ptr(), dim_t.data_ptr(), r2.shape[0], pe.data_ptr(), _raw_stream(r2.device))
+    if rc != 0:
+        _raise(lib, rc, "proposal_pos_embed")
+    return pe
+
+
+def proposal_pos_linear_relu(r2, dim_t, weight, bias):
+    """relu(PE(r2) @ weight^T + bias) [M, out] without the PE table in memory — msda_proposal_pos_linear_relu_f32."""
+    lib = _lib or load()
+    _check_pe_inputs(r2, dim_t)
+    if not (_f32_cuda(weight) and weight.dim() == 2 and weight.shape[1] == PE_WIDTH and weight.shape[0] % 4 == 0
+            and weight.device == r2.device and weight.data_ptr() % 16 == 0
+            and (bias is None or (_f32_cuda(bias) and bias.numel() == weight.shape[0] and bias.device == r2.device))):
+        raise RuntimeError("proposal_pos_linear_relu: expected contiguous fp32 CUDA weight [out, 5376] (out % 4 == 0) and bias [out]")
+    with _DeviceGuard(r2.device):
+        y = torch.empty((r2.shape[0], weight.shape[0]), dtype=torch.float32, device=r2.device)
+        rc = _entry(lib, "msda_proposal_pos_linear_relu_f32", [_VP, _VP, _VP, _VP, _LL, _CI, _VP, _VP])(
+            r2.data_ptr(), dim_t.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, r2.shape[0],
+            weight.shape[0], y.data_ptr(), _raw_stream(r2.device))
+    if rc != 0:
+        _raise(lib, rc, "proposal_pos_linear_relu")
+    return y

@@ -885,4 +885,77 @@ int msda_describe_plan(int row_bytes, int grad_value_bytes, int N, int S, int M,
     return k < buf_len ? k : buf_len - 1;
 }
 
+/* ---- two-stage query selection (msda_two_stage.hip) ---- */
+static bool misaligned16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
+int msda_two_stage_proposals_f32(const float *memory, const uint8_t *padding_mask, int N, int S, int C, int L, const int *heights,
+                                 const int *widths, const float *learnedxy, float *proposals, float *memory_out, uint8_t *row_mask,
+                                 msda_stream_t stream)
+{
+    if (N < 0 || S < 0 || C <= 0 || (C & 3) || L <= 0 || L > msda::kMaxLevels)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: need N, S >= 0, C > 0 and a multiple of 4, "
+                                                  "1 <= L <= 16");
+    if (heights == nullptr || widths == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: null level table");
+    long long total = 0;
+    for (int l = 0; l < L; ++l) {
+        if (heights[l] <= 0 || widths[l] <= 0) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: empty level");
+        total += (long long)heights[l] * widths[l];
+    }
+    if (total != S) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: S is not the sum of H_l * W_l");
+    if ((long long)N * S * (C > 42 ? C : 42) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: tensors beyond 2^31 elements");
+    if (N > 0 && S > 0 && (memory == nullptr || padding_mask == nullptr || proposals == nullptr || memory_out == nullptr ||
+                           row_mask == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: null device pointer");
+    if (misaligned16(memory) || misaligned16(memory_out))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_proposals_f32: memory rows must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_two_stage_proposals(memory, padding_mask, N, S, C, L, heights, widths, learnedxy, proposals, memory_out,
+                                            row_mask, (hipStream_t)stream);
+}
+
+int msda_two_stage_select_supported(int S, int K, int Q) { return S > 0 && S <= msda::kSelMaxRows && K > 0 && Q >= 0 && Q <= S; }
+
+int msda_two_stage_select_f32(const float *cls, const float *hand, const float *obj, const float *proposals, int N, int S, int K,
+                              int Q, int hand_class0, int hand_class1, int64_t *topk, float *refpoint_unsig,
+                              float *reference_points, msda_stream_t stream)
+{
+    if (N < 0 || S <= 0 || K <= 0 || Q < 0)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_select_f32: need N >= 0, S > 0, K > 0, Q >= 0");
+    if (Q > S) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_select_f32: selected index k out of range (Q > S)");
+    if (S > msda::kSelMaxRows) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_select_f32: S above 8192 rows per frame");
+    if ((long long)N * S * (K > 42 ? K : 42) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_select_f32: tensors beyond 2^31 elements");
+    if (N > 0 && Q > 0 && (cls == nullptr || hand == nullptr || obj == nullptr || proposals == nullptr ||
+                           refpoint_unsig == nullptr || reference_points == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_two_stage_select_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_two_stage_select(cls, hand, obj, proposals, N, S, K, Q, hand_class0, hand_class1, topk, refpoint_unsig,
+                                         reference_points, (hipStream_t)stream);
+}
+
+int msda_proposal_pos_embed_f32(const float *refpoint_unsig, const float *dim_t, long long M, float *pe, msda_stream_t stream)
+{
+    if (M < 0 || M > (1LL << 31) / 5376) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_embed_f32: need 0 <= M < 399458");
+    if (M > 0 && (refpoint_unsig == nullptr || dim_t == nullptr || pe == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_embed_f32: null device pointer");
+    if (misaligned16(pe)) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_embed_f32: pe must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_pe(refpoint_unsig, dim_t, M, pe, (hipStream_t)stream);
+}
+
+int msda_proposal_pos_linear_relu_f32(const float *refpoint_unsig, const float *dim_t, const float *weight, const float *bias,
+                                      long long M, int out_features, float *y, msda_stream_t stream)
+{
+    if (M < 0 || out_features <= 0 || (out_features & 3) || M > (1LL << 31) / 5376)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_linear_relu_f32: need 0 <= M < 399458, out_features > 0 and "
+                                                  "a multiple of 4");
+    if (weight == nullptr || dim_t == nullptr || (M > 0 && (refpoint_unsig == nullptr || y == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_linear_relu_f32: null device pointer");
+    if (misaligned16(weight)) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_proposal_pos_linear_relu_f32: weight must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_pe_linear_relu(refpoint_unsig, dim_t, weight, bias, M, out_features, y, (hipStream_t)stream);
+}
+
 }  // extern "C"

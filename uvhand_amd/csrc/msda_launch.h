@@ -153,4 +153,15 @@ int launch_add_layernorm_bwd_bf16res(const float *dy, const float *x, const uint
 // ---- FFN of the layers: backward of dropout(relu(h)) in one in-place pass (msda_layernorm.hip) ----
 int launch_relu_dropout_bwd(float *grad, const float *act, float scale, long long n, hipStream_t stream);
 
+// ---- two-stage query selection of the transformer (msda_two_stage.hip) ----
+constexpr int kSelMaxRows = 8192;  // rows per frame the selection sorts in LDS (64 KB of 64-bit keys)
+int launch_two_stage_proposals(const float *memory, const uint8_t *pad, int N, int S, int C, int L, const int *heights,
+                               const int *widths, const float *learnedxy, float *proposals, float *memory_out, uint8_t *row_mask,
+                               hipStream_t stream);
+int launch_two_stage_select(const float *cls, const float *hand, const float *obj, const float *prop, int N, int S, int K, int Q,
+                            int hand0, int hand1, int64_t *topk, float *unsig, float *refp, hipStream_t stream);
+int launch_pe(const float *r, const float *dim_t, long long M, float *pe, hipStream_t stream);
+int launch_pe_linear_relu(const float *r, const float *dim_t, const float *w, const float *bias, long long M, int Nc, float *y,
+                          hipStream_t stream);
+
 }  // namespace msda

@@ -1,6 +1,7 @@
 from .deformable_layers import (DeformableTransformerDecoder, DeformableTransformerDecoderLayer,
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
+from .deformable_transformer import DeformableTransformer
 from .ms_deform_attn import MSDeformAttn
 
 __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTransformerDecoderLayer",
-           "DeformableTransformerEncoder", "DeformableTransformerDecoder"]
+           "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer"]

@@ -468,6 +468,34 @@ int msda_proposal_pos_embed_f32(const float *refpoint_unsig, const float *dim_t,
 int msda_proposal_pos_linear_relu_f32(const float *refpoint_unsig, const float *dim_t, const float *weight, const float *bias,
                                       long long M, int out_features, float *y, msda_stream_t stream);
 
+/* ---- The AssemblyHands transformer (models/assembly_transformer.py:23-251, :387-465) ----------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ *   msda_assembly_refine_f32      the decoder's keypoint refinement (:407-465), replacing the boolean-mask add of :442:
+ *       reference_points [M, width] (width 2 or 42), cls [M, K] logits, keypoints [M, 63] (21 (x, y, z) triples), all fp32
+ *       contiguous; out [M, 42].  hand = argmax(cls) != 0 (first maximum, NaN highest); base = inverse_sigmoid(r) (width 2)
+ *       or inverse_sigmoid(((mean of the 21 x, mean of the 21 y) + 0.5) / 2) (width 42), repeated 21 times; hand rows add
+ *       each triple's (x, y); out = sigmoid(.) * 2 - 0.5.  inverse_sigmoid: util/misc.py:614-618.  One launch, no sync.
+ *   msda_assembly_proposals_f32   gen_encoder_output_proposals (:106-141) for ONE level of H x W rows, as the forward calls
+ *       it on the last level (:184): memory points at the level's first row of frame 0, memory_frame_stride (elements, a
+ *       multiple of 4) steps frames, C % 4 == 0, 16-byte aligned; padding_mask likewise with mask_frame_stride (bytes).
+ *       Writes proposals [N, H*W, 2] (logits; +inf at padded rows and rows outside (0.01, 0.99)), memory_out [N, H*W, C]
+ *       (the rows, those zeroed) and row_mask [N, H*W] (1 at those rows).  Valid extent off the mask's first column / row.
+ *   msda_assembly_select_f32      the two-stage selection (:202-226), replacing the boolean-mask loop of :204-207: cls
+ *       [N, S, K], hand / obj [N, S, 63].  Per frame: object row = the reference's loop (best 0, row 0; for classes
+ *       obj_first..obj_last in order, torch.max over rows, update on best < score only), left / right = the argmax rows
+ *       of classes left / right (first maximum, NaN highest).  Writes indices [N, 3] int64 (left, right, object; may be
+ *       NULL) and reference_points [N, 3, 2] = means of sigmoid over the x / y columns of the gathered rows (left, right
+ *       from hand, object from obj).  Every class index must be < K; at most 14 object classes.  One launch per call. */
+int msda_assembly_refine_f32(const float *reference_points, int width, const float *cls, int K, const float *keypoints, long long M,
+                             float *out, msda_stream_t stream);
+int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stride, const uint8_t *padding_mask,
+                                long long mask_frame_stride, int N, int H, int W, int C, float *proposals, float *memory_out,
+                                uint8_t *row_mask, msda_stream_t stream);
+int msda_assembly_select_f32(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
+                             int left, int right, int64_t *indices, float *reference_points, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

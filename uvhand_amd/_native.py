@@ -40,6 +40,7 @@ _SYMBOLS = (
     "msda_forward_prologue_ws_bf16", "msda_probe_row_gather", "msda_launch_count",
     "msda_two_stage_proposals_f32", "msda_two_stage_select_supported", "msda_two_stage_select_f32",
     "msda_proposal_pos_embed_f32", "msda_proposal_pos_linear_relu_f32",
+    "msda_assembly_refine_f32", "msda_assembly_proposals_f32", "msda_assembly_select_f32",
 )
 
 
@@ -1011,3 +1012,72 @@ def proposal_pos_linear_relu(r2, dim_t, weight, bias):
     if rc != 0:
         _raise(lib, rc, "proposal_pos_linear_relu")
     return y
+
+
+# ---- the AssemblyHands transformer's refinement and two-stage block (csrc/msda_assembly.hip) ------------------------------
+def assembly_refine(reference_points, cls, keypoints):
+    """next reference_points [..., 42] — msda_assembly_refine_f32: reference_points [..., 2 | 42], the layer's class logits
+    [..., K] and keypoint head output [..., 63], all contiguous fp32 CUDA with the same leading shape.  One launch."""
+    lib = _lib or load()
+    lead = tuple(reference_points.shape[:-1])
+    if not (all(_f32_cuda(t) and t.device == reference_points.device for t in (reference_points, cls, keypoints))
+            and reference_points.shape[-1] in (2, 42) and tuple(cls.shape[:-1]) == lead
+            and tuple(keypoints.shape) == lead + (63,) and cls.shape[-1] > 0):
+        raise RuntimeError("assembly_refine: expected contiguous fp32 CUDA reference_points [..., 2|42], cls [..., K] and "
+                           "keypoints [..., 63] with the same leading shape")
+    M = reference_points.numel() // reference_points.shape[-1]
+    with _DeviceGuard(reference_points.device):
+        out = torch.empty(lead + (42,), dtype=torch.float32, device=reference_points.device)
+        rc = _entry(lib, "msda_assembly_refine_f32", [_VP, _CI, _VP, _CI, _VP, _LL, _VP, _VP])(
+            reference_points.data_ptr(), reference_points.shape[-1], cls.data_ptr(), cls.shape[-1], keypoints.data_ptr(), M,
+            out.data_ptr(), _raw_stream(reference_points.device))
+    if rc != 0:
+        _raise(lib, rc, "assembly_refine")
+    return out
+
+
+def assembly_proposals(memory, padding_mask, hw):
+    """(proposals [N,H*W,2], memory_out [N,H*W,C], row_mask [N,H*W] bool) — msda_assembly_proposals_f32 for one level of
+    hw = (H, W) rows: memory [N, H*W, C] fp32 and padding_mask [N, H*W] bool may be slices of the full flattened tensors
+    (rows contiguous inside a frame, any frame stride)."""
+    lib = _lib or load()
+    H, W = int(hw[0]), int(hw[1])
+    if not (memory.is_cuda and memory.dtype == torch.float32 and memory.dim() == 3 and memory.shape[1] == H * W
+            and memory.stride(2) == 1 and memory.stride(1) == memory.shape[2] and padding_mask.dtype == torch.bool
+            and padding_mask.device == memory.device and tuple(padding_mask.shape) == tuple(memory.shape[:2])
+            and padding_mask.stride(1) == 1):
+        raise RuntimeError("assembly_proposals: expected fp32 CUDA memory [N,H*W,C] and a bool mask [N,H*W], rows contiguous")
+    N, S, C = memory.shape
+    with _DeviceGuard(memory.device):
+        props = torch.empty((N, S, 2), dtype=torch.float32, device=memory.device)
+        mem_out = torch.empty((N, S, C), dtype=torch.float32, device=memory.device)
+        row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
+        rc = _entry(lib, "msda_assembly_proposals_f32", [_VP, _LL, _VP, _LL, _CI, _CI, _CI, _CI, _VP, _VP, _VP, _VP])(
+            memory.data_ptr(), memory.stride(0), padding_mask.data_ptr(), padding_mask.stride(0), N, H, W, C, props.data_ptr(),
+            mem_out.data_ptr(), row_mask.data_ptr(), _raw_stream(memory.device))
+    if rc != 0:
+        _raise(lib, rc, "assembly_proposals")
+    return props, mem_out, row_mask
+
+
+def assembly_select(cls, hand, obj, obj_classes=(1, 8), left=9, right=10):
+    """(indices [N,3] int64 (left, right, object), reference_points [N,3,2]) — msda_assembly_select_f32: one launch, no host
+    synchronisation.  Raises IndexError when a class index is not below K, as the reference's column indexing does."""
+    lib = _lib or load()
+    ts = (cls, hand, obj)
+    if not (all(_f32_cuda(t) and t.dim() == 3 and t.device == cls.device for t in ts)
+            and all(tuple(t.shape) == tuple(cls.shape[:2]) + (63,) for t in ts[1:])):
+        raise RuntimeError("assembly_select: expected contiguous fp32 CUDA cls [N,S,K] and hand / obj [N,S,63]")
+    N, S, K = cls.shape
+    top = max(int(obj_classes[1]), int(left), int(right))
+    if top >= K:
+        raise IndexError("index %d is out of bounds for dimension 2 with size %d" % (top, K))
+    with _DeviceGuard(cls.device):
+        idx = torch.empty((N, 3), dtype=torch.int64, device=cls.device)
+        refp = torch.empty((N, 3, 2), dtype=torch.float32, device=cls.device)
+        rc = _entry(lib, "msda_assembly_select_f32", [_VP] * 3 + [_CI] * 7 + [_VP] * 3)(
+            cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), N, S, K, int(obj_classes[0]), int(obj_classes[1]), int(left),
+            int(right), idx.data_ptr(), refp.data_ptr(), _raw_stream(cls.device))
+    if rc != 0:
+        _raise(lib, rc, "assembly_select")
+    return idx, refp

@@ -958,4 +958,59 @@ int msda_proposal_pos_linear_relu_f32(const float *refpoint_unsig, const float *
     return msda::launch_pe_linear_relu(refpoint_unsig, dim_t, weight, bias, M, out_features, y, (hipStream_t)stream);
 }
 
+/* ---- the AssemblyHands transformer (msda_assembly.hip) ---- */
+int msda_assembly_refine_f32(const float *reference_points, int width, const float *cls, int K, const float *keypoints, long long M,
+                             float *out, msda_stream_t stream)
+{
+    if (M < 0 || (width != 2 && width != 42) || K <= 0)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_refine_f32: need M >= 0, width 2 or 42 and K > 0");
+    if (M * (K > 63 ? K : 63) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_refine_f32: tensors beyond 2^31 elements");
+    if (M > 0 && (reference_points == nullptr || cls == nullptr || keypoints == nullptr || out == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_refine_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_assembly_refine(reference_points, width, cls, K, keypoints, M, out, (hipStream_t)stream);
+}
+
+int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stride, const uint8_t *padding_mask,
+                                long long mask_frame_stride, int N, int H, int W, int C, float *proposals, float *memory_out,
+                                uint8_t *row_mask, msda_stream_t stream)
+{
+    if (N < 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_proposals_f32: need N >= 0, H, W > 0 and C > 0 a multiple of 4");
+    const long long rows = (long long)H * W;
+    if (memory_frame_stride < rows * C || (memory_frame_stride & 3) || mask_frame_stride < rows)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_proposals_f32: frame strides must cover H*W rows and the memory "
+                                                  "stride be a multiple of 4");
+    if ((long long)N * memory_frame_stride >= (1LL << 31) || (long long)N * rows * C >= (1LL << 31) ||
+        (long long)N * mask_frame_stride >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_proposals_f32: tensors beyond 2^31 elements");
+    if (N > 0 && (memory == nullptr || padding_mask == nullptr || proposals == nullptr || memory_out == nullptr || row_mask == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_proposals_f32: null device pointer");
+    if (misaligned16(memory) || misaligned16(memory_out))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_proposals_f32: memory rows must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_assembly_level_proposals(memory, memory_frame_stride, padding_mask, mask_frame_stride, N, H, W, C, proposals,
+                                                 memory_out, row_mask, (hipStream_t)stream);
+}
+
+int msda_assembly_select_f32(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
+                             int left, int right, int64_t *indices, float *reference_points, msda_stream_t stream)
+{
+    if (N < 0 || S <= 0 || K <= 0)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_select_f32: need N >= 0, S > 0 and K > 0");
+    if (obj_first < 0 || obj_last < obj_first || obj_last - obj_first + 1 > msda::kAssemblySelMaxObj)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_select_f32: need 0 <= obj_first <= obj_last and at most 14 object "
+                                                  "classes");
+    if (obj_last >= K || left < 0 || left >= K || right < 0 || right >= K)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_select_f32: class index out of range for K classes");
+    if ((long long)N * S * (K > 63 ? K : 63) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_select_f32: tensors beyond 2^31 elements");
+    if (N > 0 && (cls == nullptr || hand == nullptr || obj == nullptr || reference_points == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_assembly_select_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_assembly_select(cls, hand, obj, N, S, K, obj_first, obj_last, left, right, indices, reference_points,
+                                        (hipStream_t)stream);
+}
+
 }  // extern "C"

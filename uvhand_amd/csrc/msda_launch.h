@@ -164,4 +164,14 @@ int launch_pe(const float *r, const float *dim_t, long long M, float *pe, hipStr
 int launch_pe_linear_relu(const float *r, const float *dim_t, const float *w, const float *bias, long long M, int Nc, float *y,
                           hipStream_t stream);
 
+// ---- the AssemblyHands transformer's refinement and two-stage block (msda_assembly.hip) ----
+constexpr int kAssemblySelMaxObj = 14;  // object classes one selection reduces over
+int launch_assembly_refine(const float *ref, int width, const float *cls, int K, const float *kp, long long M, float *out,
+                           hipStream_t stream);
+int launch_assembly_level_proposals(const float *memory, long long mem_frame_stride, const uint8_t *pad, long long pad_frame_stride,
+                                    int N, int H, int W, int C, float *proposals, float *memory_out, uint8_t *row_mask,
+                                    hipStream_t stream);
+int launch_assembly_select(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
+                           int left, int right, int64_t *indices, float *refp, hipStream_t stream);
+
 }  // namespace msda

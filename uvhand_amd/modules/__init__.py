@@ -1,7 +1,10 @@
+from .assembly_transformer import DeformableTransformer as AssemblyDeformableTransformer
+from .assembly_transformer import DeformableTransformerDecoder as AssemblyDeformableTransformerDecoder
 from .deformable_layers import (DeformableTransformerDecoder, DeformableTransformerDecoderLayer,
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
 from .deformable_transformer import DeformableTransformer
 from .ms_deform_attn import MSDeformAttn
 
 __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTransformerDecoderLayer",
-           "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer"]
+           "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
+           "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder"]

@@ -496,6 +496,40 @@ int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stri
 int msda_assembly_select_f32(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
                              int left, int right, int64_t *indices, float *reference_points, msda_stream_t stream);
 
+/* ---- The Hungarian matchers (models/matcher.py: ArcticMatcher :20-125, AssemblyMatcher :128-230) -------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ *   msda_match_arctic_f32    one launch matches `sets` prediction sets (HOST arrays of `sets` device pointers, sets <= 16):
+ *       pred_logits [bs, Q, K], pred_hand_key / pred_obj_key [bs, Q, D] (Q <= 1024, D <= 64; ignored, D = 0, when
+ *       keypoints is NULL), all fp32 contiguous, against the targets of every frame: labels [n_targets] int64, keypoints
+ *       [n_targets, D] fp32 or NULL, offsets [bs + 1] int64 (frame f owns targets offsets[f]..offsets[f+1]-1, at most
+ *       t_max <= 16 of them) and is_valid [bs] int32 (non-zero = valid).  Output slot k of every set pairs output frame k
+ *       with the k-th VALID frame's targets, as the reference's split does (:122-123).  Per slot, on chip: the cost block
+ *       C = cost_keypoint * L1 + cost_class * (focal pos - neg) (L1 against the hand head for labels 12 / 13, none for
+ *       label 0, the object head otherwise; no L1 term without keypoints) and scipy's linear_sum_assignment of it (the
+ *       same shortest augmenting path with fp64 duals and scipy's tie rule).
+ *       out int64 [2 * sets * bs * t_max + 2 * sets * bs + 1]: query_idx [sets, bs, t_max] (ascending), target_idx
+ *       [sets, bs, t_max] (-1 padding), count [sets, bs] (min(Q, T); -1 past the valid frames), status [sets, bs]
+ *       (0 ok, 1 a NaN or -inf cost, 2 infeasible, 3 a label outside [0, K), 4 offsets outside [0, n_targets] or a frame
+ *       above t_max targets), and the number of valid frames.  cost_debug [sets, bs, Q, t_max] fp32 or NULL receives
+ *       each block (entries past a frame's targets are not written).  One launch, no synchronisation, nothing read on
+ *       the host; bs = 0 launches nothing.
+ *   msda_match_assembly_f32  the same for AssemblyMatcher: one keypoint head pred_keypoints [bs, Q, D], L1 where the label
+ *       is not 0, no is_valid (slot k = frame k; the last output word is bs).
+ *   msda_lsap_f32            scipy's linear_sum_assignment of B fp32 blocks cost [B, Q, T] (min(Q, T) <= 16,
+ *       max(Q, T) <= 1024) with the same solver; out int64 [2 * B * W + 2 * B], W = min(Q, T): row (query) indices
+ *       ascending, column indices, count and status per block as above. */
+int msda_match_arctic_f32(const float *const *pred_logits, const float *const *pred_hand_key, const float *const *pred_obj_key,
+                          int sets, int bs, int Q, int K, int D, const int64_t *labels, const float *keypoints,
+                          const int64_t *offsets, long long n_targets, const int32_t *is_valid, int t_max, float cost_class,
+                          float cost_keypoint, int64_t *out, float *cost_debug, msda_stream_t stream);
+int msda_match_assembly_f32(const float *const *pred_logits, const float *const *pred_keypoints, int sets, int bs, int Q, int K,
+                            int D, const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                            int t_max, float cost_class, float cost_keypoint, int64_t *out, float *cost_debug,
+                            msda_stream_t stream);
+int msda_lsap_f32(const float *cost, int B, int Q, int T, int64_t *out, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

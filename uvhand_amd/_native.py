@@ -41,6 +41,7 @@ _SYMBOLS = (
     "msda_two_stage_proposals_f32", "msda_two_stage_select_supported", "msda_two_stage_select_f32",
     "msda_proposal_pos_embed_f32", "msda_proposal_pos_linear_relu_f32",
     "msda_assembly_refine_f32", "msda_assembly_proposals_f32", "msda_assembly_select_f32",
+    "msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32",
 )
 
 
@@ -1081,3 +1082,102 @@ def assembly_select(cls, hand, obj, obj_classes=(1, 8), left=9, right=10):
     if rc != 0:
         _raise(lib, rc, "assembly_select")
     return idx, refp
+
+
+# ---- the Hungarian matchers (csrc/msda_matcher.hip) ----------------------------------------------------------------------
+MATCH_MAX_QUERIES, MATCH_MAX_TARGETS, MATCH_MAX_SETS, MATCH_MAX_DIM = 1024, 16, 16, 64
+MATCH_OK, MATCH_INVALID, MATCH_INFEASIBLE, MATCH_BAD_LABEL, MATCH_BAD_TARGETS = 0, 1, 2, 3, 4
+
+
+def _ptr_array(ts):
+    return (_VP * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _match_checks(what, logits, heads, labels, keypoints, offsets, t_max):
+    dev = logits[0].device
+    if not (0 < len(logits) <= MATCH_MAX_SETS and all(len(h) == len(logits) for h in heads)):
+        raise RuntimeError("%s: 1 to %d prediction sets" % (what, MATCH_MAX_SETS))
+    shape = tuple(logits[0].shape)
+    if not (len(shape) == 3 and all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == shape for t in logits)):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA pred_logits [bs, Q, K] of one shape in every set" % what)
+    D = keypoints.shape[1] if keypoints is not None else 0
+    for h in heads:
+        if not all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == shape[:2] + (D,) for t in h):
+            raise RuntimeError("%s: expected contiguous fp32 CUDA keypoint heads [bs, Q, %d]" % (what, D))
+    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 1
+            and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous()
+            and tuple(offsets.shape) == (shape[0] + 1,) and labels.device == dev and offsets.device == dev):
+        raise RuntimeError("%s: expected int64 CUDA labels [n] and offsets [bs + 1]" % what)
+    if keypoints is not None and not (_f32_cuda(keypoints) and keypoints.dim() == 2 and keypoints.device == dev
+                                      and keypoints.shape[0] == labels.shape[0]):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA target keypoints [n, D]" % what)
+    if not 0 <= int(t_max) <= MATCH_MAX_TARGETS:
+        raise RuntimeError("%s: at most %d targets per frame" % (what, MATCH_MAX_TARGETS))
+    return dev, shape, D
+
+
+def _match_out(dev, sets, bs, t_max, Q, cost_debug):
+    out = torch.empty(2 * sets * bs * t_max + 2 * sets * bs + 1, dtype=torch.int64, device=dev)
+    if cost_debug is not None and not (_f32_cuda(cost_debug) and cost_debug.device == dev
+                                       and tuple(cost_debug.shape) == (sets, bs, Q, t_max)):
+        raise RuntimeError("match: cost_debug must be contiguous fp32 CUDA [sets, bs, Q, t_max]")
+    return out
+
+
+def match_arctic(logits, hand, obj, labels, keypoints, offsets, is_valid, t_max, cost_class, cost_keypoint, cost_debug=None):
+    """The int64 result buffer of msda_match_arctic_f32 (include/msda.h): lists of per-set pred_logits [bs, Q, K] and (with
+    target keypoints) pred_hand_key / pred_obj_key [bs, Q, D]; labels [n] / offsets [bs + 1] int64, keypoints [n, D] fp32 or
+    None, is_valid [bs] int32 on the same device.  One launch, no host synchronisation."""
+    lib = _lib or load()
+    heads = (hand, obj) if keypoints is not None else ()
+    dev, (bs, Q, K), D = _match_checks("match_arctic", logits, heads, labels, keypoints, offsets, t_max)
+    if not (is_valid.is_cuda and is_valid.dtype == torch.int32 and is_valid.is_contiguous() and tuple(is_valid.shape) == (bs,)
+            and is_valid.device == dev):
+        raise RuntimeError("match_arctic: expected int32 CUDA is_valid [bs]")
+    sets = len(logits)
+    with _DeviceGuard(dev):
+        out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
+        rc = _entry(lib, "msda_match_arctic_f32", [_VP, _VP, _VP] + [_CI] * 5 + [_VP, _VP, _VP, _LL, _VP, _CI,
+                                                                               ctypes.c_float, ctypes.c_float, _VP, _VP, _VP])(
+            _ptr_array(logits), _ptr_array(hand) if heads else None, _ptr_array(obj) if heads else None, sets, bs, Q, K, D,
+            labels.data_ptr(), keypoints.data_ptr() if keypoints is not None else None, offsets.data_ptr(), labels.shape[0],
+            is_valid.data_ptr(), int(t_max), float(cost_class), float(cost_keypoint), out.data_ptr(),
+            cost_debug.data_ptr() if cost_debug is not None else None, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "match_arctic")
+    return out
+
+
+def match_assembly(logits, pred_keypoints, labels, keypoints, offsets, t_max, cost_class, cost_keypoint, cost_debug=None):
+    """The int64 result buffer of msda_match_assembly_f32: as match_arctic with one keypoint head per set and no is_valid."""
+    lib = _lib or load()
+    dev, (bs, Q, K), D = _match_checks("match_assembly", logits, (pred_keypoints,), labels, keypoints, offsets, t_max)
+    sets = len(logits)
+    with _DeviceGuard(dev):
+        out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
+        rc = _entry(lib, "msda_match_assembly_f32", [_VP, _VP] + [_CI] * 5 + [_VP, _VP, _VP, _LL, _CI, ctypes.c_float,
+                                                                           ctypes.c_float, _VP, _VP, _VP])(
+            _ptr_array(logits), _ptr_array(pred_keypoints), sets, bs, Q, K, D, labels.data_ptr(), keypoints.data_ptr(),
+            offsets.data_ptr(), labels.shape[0], int(t_max), float(cost_class), float(cost_keypoint), out.data_ptr(),
+            cost_debug.data_ptr() if cost_debug is not None else None, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "match_assembly")
+    return out
+
+
+def lsap(cost):
+    """(query_idx [B, W], target_idx [B, W], count [B], status [B]) int64 — msda_lsap_f32: scipy's linear_sum_assignment of
+    each [Q, T] block of a contiguous fp32 CUDA cost [B, Q, T] (min(Q, T) <= 16, max(Q, T) <= 1024), W = min(Q, T)."""
+    lib = _lib or load()
+    if not (_f32_cuda(cost) and cost.dim() == 3):
+        raise RuntimeError("lsap: expected a contiguous fp32 CUDA cost [B, Q, T]")
+    B, Q, T = cost.shape
+    W = min(Q, T)
+    with _DeviceGuard(cost.device):
+        out = torch.empty(2 * B * W + 2 * B, dtype=torch.int64, device=cost.device)
+        rc = _entry(lib, "msda_lsap_f32", [_VP, _CI, _CI, _CI, _VP, _VP])(cost.data_ptr(), B, Q, T, out.data_ptr(),
+                                                                          _raw_stream(cost.device))
+    if rc != 0:
+        _raise(lib, rc, "lsap")
+    return (out[:B * W].view(B, W), out[B * W:2 * B * W].view(B, W), out[2 * B * W:2 * B * W + B],
+            out[2 * B * W + B:])

@@ -1013,4 +1013,86 @@ int msda_assembly_select_f32(const float *cls, const float *hand, const float *o
                                         (hipStream_t)stream);
 }
 
+/* ---- the Hungarian matchers (msda_matcher.hip) ---- */
+static int check_match(const char *who, int sets, int bs, int Q, int K, int D, bool has_kp, const int64_t *labels,
+                       const int64_t *offsets, long long n_targets, int t_max, const int64_t *out)
+{
+    char buf[256];
+    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 0 || bs > msda::kMatchMaxQueries) {
+        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 0 <= bs <= %d", who, msda::kMatchMaxSets, msda::kMatchMaxQueries);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (Q < 1 || Q > msda::kMatchMaxQueries || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets) {
+        std::snprintf(buf, sizeof(buf), "%s: need 1 <= Q <= %d, K >= 1 and 0 <= t_max <= %d", who, msda::kMatchMaxQueries,
+                      msda::kMatchMaxTargets);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (has_kp ? (D < 1 || D > msda::kMatchMaxDim) : D != 0) {
+        std::snprintf(buf, sizeof(buf), "%s: need 1 <= D <= %d with target keypoints, D = 0 without", who, msda::kMatchMaxDim);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (n_targets < 0 || n_targets * (D > 1 ? D : 1) >= (1LL << 31) || (long long)bs * Q * (K > D ? K : D) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: tensors beyond 2^31 elements");
+    if (bs > 0 && (offsets == nullptr || out == nullptr || (n_targets > 0 && labels == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+    return MSDA_OK;
+}
+
+int msda_match_arctic_f32(const float *const *pred_logits, const float *const *pred_hand_key, const float *const *pred_obj_key,
+                          int sets, int bs, int Q, int K, int D, const int64_t *labels, const float *keypoints,
+                          const int64_t *offsets, long long n_targets, const int32_t *is_valid, int t_max, float cost_class,
+                          float cost_keypoint, int64_t *out, float *cost_debug, msda_stream_t stream)
+{
+    const bool has_kp = keypoints != nullptr;
+    int rc = check_match("msda_match_arctic_f32", sets, bs, Q, K, D, has_kp, labels, offsets, n_targets, t_max, out);
+    if (rc != MSDA_OK) return rc;
+    if (bs > 0 && is_valid == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+    if (pred_logits == nullptr || (has_kp && (pred_hand_key == nullptr || pred_obj_key == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+    msda::MatchSets ms = {};
+    for (int s = 0; s < sets; ++s) {
+        if (pred_logits[s] == nullptr || (has_kp && (pred_hand_key[s] == nullptr || pred_obj_key[s] == nullptr)))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+        ms.logits[s] = pred_logits[s];
+        ms.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
+        ms.obj[s] = has_kp ? pred_obj_key[s] : nullptr;
+    }
+    msda::begin_call();
+    return msda::launch_match(ms, sets, bs, Q, K, D, labels, keypoints, offsets, n_targets, is_valid, t_max, cost_class,
+                              cost_keypoint, out, cost_debug, (hipStream_t)stream);
+}
+
+int msda_match_assembly_f32(const float *const *pred_logits, const float *const *pred_keypoints, int sets, int bs, int Q, int K,
+                            int D, const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                            int t_max, float cost_class, float cost_keypoint, int64_t *out, float *cost_debug,
+                            msda_stream_t stream)
+{
+    int rc = check_match("msda_match_assembly_f32", sets, bs, Q, K, D, true, labels, offsets, n_targets, t_max, out);
+    if (rc != MSDA_OK) return rc;
+    if (pred_logits == nullptr || pred_keypoints == nullptr || (bs > 0 && n_targets > 0 && keypoints == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+    msda::MatchSets ms = {};
+    for (int s = 0; s < sets; ++s) {
+        if (pred_logits[s] == nullptr || pred_keypoints[s] == nullptr)
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+        ms.logits[s] = pred_logits[s];
+        ms.hand[s] = ms.obj[s] = pred_keypoints[s];
+    }
+    msda::begin_call();
+    return msda::launch_match(ms, sets, bs, Q, K, D, labels, keypoints, offsets, n_targets, nullptr, t_max, cost_class,
+                              cost_keypoint, out, cost_debug, (hipStream_t)stream);
+}
+
+int msda_lsap_f32(const float *cost, int B, int Q, int T, int64_t *out, msda_stream_t stream)
+{
+    const int lo = Q < T ? Q : T, hi = Q < T ? T : Q;
+    if (B < 0 || B > 65535 || Q < 1 || T < 0 || lo > msda::kMatchMaxTargets || hi > msda::kMatchMaxQueries)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_lsap_f32: need 0 <= B <= 65535, Q >= 1, T >= 0, min(Q, T) <= 16 and "
+                                                  "max(Q, T) <= 1024");
+    if (B > 0 && (out == nullptr || (T > 0 && cost == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_lsap_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_lsap(cost, B, Q, T, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -174,4 +174,21 @@ int launch_assembly_level_proposals(const float *memory, long long mem_frame_str
 int launch_assembly_select(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
                            int left, int right, int64_t *indices, float *refp, hipStream_t stream);
 
+// ---- the Hungarian matchers: cost block + assignment per (prediction set, frame) (msda_matcher.hip) ----
+constexpr int kMatchMaxQueries = 1024;  // queries of a frame (one workgroup, one thread per query)
+constexpr int kMatchMaxTargets = 16;    // targets of a frame (rows of the solved problem, held per thread)
+constexpr int kMatchMaxSets = 16;       // prediction sets per launch (their pointers travel as kernel arguments)
+constexpr int kMatchMaxDim = 64;        // keypoint values per target
+// per-slot status codes (include/msda.h)
+constexpr int kMatchInvalid = 1, kMatchInfeasible = 2, kMatchBadLabel = 3, kMatchBadTargets = 4;
+struct MatchSets {
+    const float *logits[kMatchMaxSets];
+    const float *hand[kMatchMaxSets];
+    const float *obj[kMatchMaxSets];
+};
+int launch_match(const MatchSets &sets, int n_sets, int bs, int Q, int K, int D, const int64_t *labels, const float *tgt_kp,
+                 const int64_t *offsets, long long n_targets, const int32_t *is_valid, int t_max, float w_cls, float w_kp,
+                 int64_t *out, float *cost_debug, hipStream_t stream);
+int launch_lsap(const float *cost, int B, int Q, int T, int64_t *out, hipStream_t stream);
+
 }  // namespace msda

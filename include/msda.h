@@ -530,6 +530,44 @@ int msda_match_assembly_f32(const float *const *pred_logits, const float *const 
                             msda_stream_t stream);
 int msda_lsap_f32(const float *cost, int B, int Q, int T, int64_t *out, msda_stream_t stream);
 
+/* ---- The set criteria's matched losses (models/actic_detr.py SetArcticCriterion :365-569, models/assembly_detr.py
+ * SetAssemblyCriterion :248-446) over the matcher's device result ------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump, as the matcher block above: purely additive entries.
+ *
+ *   msda_criterion_fwd_f32  one launch, one workgroup per prediction set.  kind 0 = ARCTIC, 1 = AssemblyHands.  HOST arrays
+ *       of `sets` device pointers (sets <= 16): pred_logits [bs, Q, K] and, with target keypoints, pred_hand_key [bs, Q, D]
+ *       (AssemblyHands: pred_keypoints) and pred_obj_key [bs, Q, D] (ARCTIC only; NULL for AssemblyHands), all fp32
+ *       contiguous.  match: the int64 result of msda_match_{arctic,assembly}_f32 for the same sets and t_max.  The targets as
+ *       for the matcher (labels, keypoints [n_targets, D] or NULL with D = 0, offsets [bs + 1], is_valid [bs] for ARCTIC:
+ *       slot k pairs with the k-th valid frame; NULL for AssemblyHands), joint_valid uint8 [n_targets, D] (AssemblyHands
+ *       with keypoints, else NULL), hand_mask (bit l for each hand label l < 64: 12 and 13 for ARCTIC, cfg.hand_idx for
+ *       AssemblyHands), num_boxes a device fp32 scalar, focal_alpha.
+ *       losses fp32 [sets, 4]: ARCTIC loss_ce, loss_hand_keypoint, loss_obj_keypoint, cardinality_error (all 0 when no
+ *       valid frame has a target); AssemblyHands loss_ce, loss_hand_keypoint, cardinality_error, class_error.
+ *       stats int32 [sets, 4]: status bits (1 a matched label outside [0, K), 2 offsets / target indices that do not
+ *       describe the targets, 4 AssemblyHands joint_valid mask mismatch: a matched label outside hand_mask or a frame
+ *       with unmatched targets, loss_hand_keypoint is then nan, 8 a matcher slot status), hand rows, object rows, and 1
+ *       when no valid frame has a target (ARCTIC).  Reductions in a fixed order: bitwise reproducible.
+ *   msda_criterion_bwd_f32  one launch: from grad_losses fp32 [sets, 4] (the forward's columns; cardinality_error and
+ *       class_error get none) and the forward's stats, writes every element of grad_logits and, with keypoints, of
+ *       grad_hand_key / grad_obj_key (HOST arrays of device pointers shaped as the predictions): zero except matched rows.
+ *   Limits: 1 <= bs <= 1024, 1 <= Q, 1 <= K, 0 <= t_max <= 16.  No synchronisation, nothing read on the host. */
+#define MSDA_CRITERION_ARCTIC 0
+#define MSDA_CRITERION_ASSEMBLY 1
+int msda_criterion_fwd_f32(int kind, const float *const *pred_logits, const float *const *pred_hand_key,
+                           const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
+                           int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
+                           long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
+                           unsigned long long hand_mask, const float *num_boxes, float focal_alpha, float *losses,
+                           int32_t *stats, msda_stream_t stream);
+int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const float *const *pred_hand_key,
+                           const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
+                           int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
+                           long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
+                           unsigned long long hand_mask, const float *num_boxes, float focal_alpha,
+                           const float *grad_losses, const int32_t *stats, float *const *grad_logits,
+                           float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -42,6 +42,7 @@ _SYMBOLS = (
     "msda_proposal_pos_embed_f32", "msda_proposal_pos_linear_relu_f32",
     "msda_assembly_refine_f32", "msda_assembly_proposals_f32", "msda_assembly_select_f32",
     "msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32",
+    "msda_criterion_fwd_f32", "msda_criterion_bwd_f32",
 )
 
 
@@ -1181,3 +1182,76 @@ def lsap(cost):
         _raise(lib, rc, "lsap")
     return (out[:B * W].view(B, W), out[B * W:2 * B * W].view(B, W), out[2 * B * W:2 * B * W + B],
             out[2 * B * W + B:])
+
+
+# ---- the set criteria's matched losses (csrc/msda_criterion.hip) ---------------------------------------------------------
+CRIT_ARCTIC, CRIT_ASSEMBLY = 0, 1
+CRIT_TERMS = 4
+CRIT_BAD_LABEL, CRIT_BAD_TARGETS, CRIT_MASK_MISMATCH, CRIT_MATCH_STATUS = 1, 2, 4, 8
+_CRIT_ARGS = [_CI, _VP, _VP, _VP] + [_CI] * 5 + [_VP, _CI, _VP, _VP, _VP, _LL, _VP, _VP, ctypes.c_ulonglong, _VP, ctypes.c_float]
+
+
+def _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
+                 num_boxes, focal_alpha):
+    """Checks shared by criterion_fwd / criterion_bwd; returns the C arguments in order and (dev, sets, bs, Q, K, D)."""
+    arctic = kind == CRIT_ARCTIC
+    heads = ((hand, obj) if arctic else (hand,)) if keypoints is not None else ()
+    dev, (bs, Q, K), D = _match_checks("criterion", logits, heads, labels, keypoints, offsets, t_max)
+    sets = len(logits)
+    if not (match.is_cuda and match.dtype == torch.int64 and match.is_contiguous() and match.device == dev
+            and match.numel() == 2 * sets * bs * t_max + 2 * sets * bs + 1):
+        raise RuntimeError("criterion: expected the matcher's int64 CUDA result for %d sets" % sets)
+    if arctic and not (is_valid is not None and is_valid.is_cuda and is_valid.dtype == torch.int32
+                       and tuple(is_valid.shape) == (bs,) and is_valid.is_contiguous() and is_valid.device == dev):
+        raise RuntimeError("criterion: expected int32 CUDA is_valid [bs]")
+    jv_needed = not arctic and keypoints is not None
+    if jv_needed and not (joint_valid is not None and joint_valid.is_cuda and joint_valid.dtype == torch.uint8
+                          and joint_valid.is_contiguous() and tuple(joint_valid.shape) == (labels.shape[0], D)
+                          and joint_valid.device == dev):
+        raise RuntimeError("criterion: expected uint8 CUDA joint_valid [n, %d]" % D)
+    if not (_f32_cuda(num_boxes) and num_boxes.numel() == 1 and num_boxes.device == dev):
+        raise RuntimeError("criterion: expected an fp32 CUDA num_boxes scalar")
+    args = [kind, _ptr_array(logits), _ptr_array(hand) if heads else None, _ptr_array(obj) if heads and arctic else None,
+            sets, bs, Q, K, D, match.data_ptr(), int(t_max), labels.data_ptr(),
+            keypoints.data_ptr() if keypoints is not None else None, offsets.data_ptr(), labels.shape[0],
+            is_valid.data_ptr() if arctic else None, joint_valid.data_ptr() if jv_needed else None, int(hand_mask),
+            num_boxes.data_ptr(), float(focal_alpha)]
+    return args, (dev, sets, bs, Q, K, D)
+
+
+def criterion_fwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
+                  num_boxes, focal_alpha):
+    """(losses fp32 [sets, 4], stats int32 [sets, 4]) — msda_criterion_fwd_f32 (include/msda.h).  One launch, no host
+    synchronisation."""
+    lib = _lib or load()
+    args, (dev, sets, *_rest) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
+                                            joint_valid, hand_mask, num_boxes, focal_alpha)
+    with _DeviceGuard(dev):
+        losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
+        stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
+        rc = _entry(lib, "msda_criterion_fwd_f32", _CRIT_ARGS + [_VP, _VP, _VP])(
+            *args, losses.data_ptr(), stats.data_ptr(), _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "criterion_fwd")
+    return losses, stats
+
+
+def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
+                  num_boxes, focal_alpha, grad_losses, stats):
+    """(grad_logits, grad_hand, grad_obj) lists, every element written — msda_criterion_bwd_f32.  One launch."""
+    lib = _lib or load()
+    args, (dev, sets, bs, Q, K, D) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
+                                                  joint_valid, hand_mask, num_boxes, focal_alpha)
+    if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
+            and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
+        raise RuntimeError("criterion_bwd: expected fp32 grad_losses and int32 stats [%d, 4]" % sets)
+    with _DeviceGuard(dev):
+        g_logits = [torch.empty(bs, Q, K, dtype=torch.float32, device=dev) for _ in range(sets)]
+        g_hand = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D else []
+        g_obj = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D and kind == CRIT_ARCTIC else []
+        rc = _entry(lib, "msda_criterion_bwd_f32", _CRIT_ARGS + [_VP, _VP, _VP, _VP, _VP, _VP])(
+            *args, grad_losses.data_ptr(), stats.data_ptr(), _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None,
+            _ptr_array(g_obj) if g_obj else None, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "criterion_bwd")
+    return g_logits, g_hand, g_obj

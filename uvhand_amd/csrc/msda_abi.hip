@@ -1095,4 +1095,116 @@ int msda_lsap_f32(const float *cost, int B, int Q, int T, int64_t *out, msda_str
     return msda::launch_lsap(cost, B, Q, T, out, (hipStream_t)stream);
 }
 
+/* ---- the set criteria's matched losses (msda_criterion.hip) ---- */
+static int check_criterion(const char *who, int kind, const float *const *pred_logits, const float *const *pred_hand_key,
+                           const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
+                           int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
+                           long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
+                           const float *num_boxes, msda::CritArgs &a, msda::CritSets &p)
+{
+    char buf[256];
+    if (kind != MSDA_CRITERION_ARCTIC && kind != MSDA_CRITERION_ASSEMBLY) {
+        std::snprintf(buf, sizeof(buf), "%s: kind must be 0 (ARCTIC) or 1 (AssemblyHands)", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 1 || bs > msda::kMatchMaxQueries) {
+        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 1 <= bs <= %d", who, msda::kMatchMaxSets,
+                      msda::kMatchMaxQueries);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (Q < 1 || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets || D < 0) {
+        std::snprintf(buf, sizeof(buf), "%s: need Q >= 1, K >= 1, D >= 0 and 0 <= t_max <= %d", who, msda::kMatchMaxTargets);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    const bool has_kp = keypoints != nullptr;
+    if (has_kp != (D > 0)) {
+        std::snprintf(buf, sizeof(buf), "%s: need D >= 1 with target keypoints, D = 0 without", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (n_targets < 0 || n_targets * (D > 1 ? D : 1) >= (1LL << 31) || (long long)bs * Q * (K > D ? K : D) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: tensors beyond 2^31 elements");
+    if (pred_logits == nullptr || match == nullptr || offsets == nullptr || num_boxes == nullptr
+        || (n_targets > 0 && labels == nullptr) || (kind == MSDA_CRITERION_ARCTIC && is_valid == nullptr)
+        || (has_kp && pred_hand_key == nullptr) || (has_kp && kind == MSDA_CRITERION_ARCTIC && pred_obj_key == nullptr)
+        || (has_kp && kind == MSDA_CRITERION_ASSEMBLY && joint_valid == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
+    p = {};
+    for (int s = 0; s < sets; ++s) {
+        if (pred_logits[s] == nullptr || (has_kp && pred_hand_key[s] == nullptr)
+            || (has_kp && kind == MSDA_CRITERION_ARCTIC && pred_obj_key[s] == nullptr))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
+        p.logits[s] = pred_logits[s];
+        p.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
+        p.obj[s] = has_kp && kind == MSDA_CRITERION_ARCTIC ? pred_obj_key[s] : nullptr;
+    }
+    a = {};
+    a.kind = kind;
+    a.sets = sets;
+    a.bs = bs;
+    a.Q = Q;
+    a.K = K;
+    a.D = D;
+    a.t_max = t_max;
+    a.match = match;
+    a.labels = labels;
+    a.tgt_kp = keypoints;
+    a.offsets = offsets;
+    a.n_targets = n_targets;
+    a.is_valid = kind == MSDA_CRITERION_ARCTIC ? is_valid : nullptr;
+    a.joint_valid = kind == MSDA_CRITERION_ASSEMBLY && has_kp ? joint_valid : nullptr;
+    a.num_boxes = num_boxes;
+    return MSDA_OK;
+}
+
+int msda_criterion_fwd_f32(int kind, const float *const *pred_logits, const float *const *pred_hand_key,
+                           const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
+                           int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
+                           long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
+                           unsigned long long hand_mask, const float *num_boxes, float focal_alpha, float *losses,
+                           int32_t *stats, msda_stream_t stream)
+{
+    msda::CritArgs a;
+    msda::CritSets p;
+    int rc = check_criterion("msda_criterion_fwd_f32", kind, pred_logits, pred_hand_key, pred_obj_key, sets, bs, Q, K, D, match,
+                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, num_boxes, a, p);
+    if (rc != MSDA_OK) return rc;
+    if (losses == nullptr || stats == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
+    a.hand_mask = hand_mask;
+    a.alpha = focal_alpha;
+    msda::begin_call();
+    return msda::launch_criterion_fwd(a, p, losses, stats, (hipStream_t)stream);
+}
+
+int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const float *const *pred_hand_key,
+                           const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
+                           int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
+                           long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
+                           unsigned long long hand_mask, const float *num_boxes, float focal_alpha,
+                           const float *grad_losses, const int32_t *stats, float *const *grad_logits,
+                           float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream)
+{
+    msda::CritArgs a;
+    msda::CritSets p;
+    int rc = check_criterion("msda_criterion_bwd_f32", kind, pred_logits, pred_hand_key, pred_obj_key, sets, bs, Q, K, D, match,
+                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, num_boxes, a, p);
+    if (rc != MSDA_OK) return rc;
+    const bool has_kp = keypoints != nullptr;
+    if (grad_losses == nullptr || stats == nullptr || grad_logits == nullptr || (has_kp && grad_hand_key == nullptr)
+        || (has_kp && kind == MSDA_CRITERION_ARCTIC && grad_obj_key == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
+    msda::CritGrads g = {};
+    for (int s = 0; s < sets; ++s) {
+        if (grad_logits[s] == nullptr || (has_kp && grad_hand_key[s] == nullptr)
+            || (has_kp && kind == MSDA_CRITERION_ARCTIC && grad_obj_key[s] == nullptr))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
+        g.logits[s] = grad_logits[s];
+        g.hand[s] = has_kp ? grad_hand_key[s] : nullptr;
+        g.obj[s] = has_kp && kind == MSDA_CRITERION_ARCTIC ? grad_obj_key[s] : nullptr;
+    }
+    a.hand_mask = hand_mask;
+    a.alpha = focal_alpha;
+    msda::begin_call();
+    return msda::launch_criterion_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
+}
+
 }  // extern "C"

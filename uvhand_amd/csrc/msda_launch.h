@@ -191,4 +191,36 @@ int launch_match(const MatchSets &sets, int n_sets, int bs, int Q, int K, int D,
                  int64_t *out, float *cost_debug, hipStream_t stream);
 int launch_lsap(const float *cost, int B, int Q, int T, int64_t *out, hipStream_t stream);
 
+// ---- the set criteria's matched losses over the matcher's device result (msda_criterion.hip) ----
+constexpr int kCritArctic = 0, kCritAssembly = 1;
+constexpr int kCritTerms = 4;   // loss columns per set (include/msda.h)
+constexpr int kCritStats = 4;   // status bits, hand rows, object rows, no valid target (ARCTIC)
+constexpr int kCritBadLabel = 1, kCritBadTargets = 2, kCritMaskMismatch = 4, kCritMatchStatus = 8;
+struct CritArgs {
+    int kind, sets, bs, Q, K, D, t_max;
+    const int64_t *match;       // the matcher's result buffer
+    const int64_t *labels;
+    const float *tgt_kp;        // [n_targets, D] or NULL (D = 0)
+    const int64_t *offsets;
+    long long n_targets;
+    const int32_t *is_valid;    // ARCTIC: slot k pairs with the k-th valid frame; NULL: frame k
+    const uint8_t *joint_valid; // AssemblyHands [n_targets, D]
+    unsigned long long hand_mask;
+    const float *num_boxes;     // device scalar
+    float alpha;
+};
+struct CritSets {
+    const float *logits[kMatchMaxSets];
+    const float *hand[kMatchMaxSets];
+    const float *obj[kMatchMaxSets];
+};
+struct CritGrads {
+    float *logits[kMatchMaxSets];
+    float *hand[kMatchMaxSets];
+    float *obj[kMatchMaxSets];
+};
+int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, int32_t *stats, hipStream_t stream);
+int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
+                         const int32_t *stats, hipStream_t stream);
+
 }  // namespace msda

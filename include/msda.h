@@ -568,6 +568,52 @@ int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const floa
                            const float *grad_losses, const int32_t *stats, float *const *grad_logits,
                            float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream);
 
+/* ---- The DeformableDETR prediction heads (models/actic_detr.py DeformableDETR.forward :245-287, models/assembly_detr.py
+ * DeformableDETR.forward :172-210) as grouped fp32 GEMMs --------------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Per decoder level l < L (M = B * Q rows, hidden C): the class Linear (K classes), n_mlp 3-layer keypoint MLPs C -> C -> C ->
+ * D (ARCTIC: key_embed, obj_key_embed, D = 42, n_mlp 2 for two-stage models, 0 otherwise; AssemblyHands: keypoint_embed,
+ * D = 63, n_mlp 1) and, ARCTIC only, the six shared Linears mano_pose 48, mano_beta 10, hand_cam 3, obj_cam 3, obj_rot 3,
+ * obj_rad 1 (:264-270).  Keypoint epilogues: ARCTIC sigmoid(y + inverse_sigmoid(ref)) * 2 - 1 (:250-256); AssemblyHands adds
+ * inverse_sigmoid(ref) (2-d) or the means of its 21 x / 21 y values (42-d) to the x and y of each of the 21 points, then
+ * sigmoid * 2 - 0.5 (:186-206).  ref is init_ref [M, R] for level 0 and inter_ref [L - 1, M, R] after (AssemblyHands
+ * maps those r -> (r + 0.5) / 2 first, :180).  All tensors fp32 contiguous, hs [L, M, C]; C % 4 == 0, 4 <= C <= 4096,
+ * 1 <= L <= 8, L * M * max(C, K) < 2^31.
+ *   HOST pointer arrays: cls_w / cls_b [L] ([1] with MSDA_HEADS_SHARED_CLS: one module repeated over the levels),
+ *   mlp_w / mlp_b [n_mlp * 3 * L] at (head * 3 + layer) * L + l ([n_mlp * 3], index head * 3 + layer, with
+ *   MSDA_HEADS_SHARED_MLP), shared_w / shared_b [6] (ARCTIC; NULL for AssemblyHands).  Weights [n_out, n_in] as nn.Linear.
+ *
+ *   msda_heads_forward_f32   at most 3 launches (one per MLP depth, every head of every level in each).  Writes logits
+ *       [L, M, K], kp_out[h] [L, M, D], shared_out[g] [L, M, n_g] (the reference's torch.stack'ed tensors), and saves the
+ *       hidden activations hidden [n_mlp, 2, L, M, C] and the keypoint sigmoids sig [n_mlp, L, M, D] for the backward.
+ *   msda_heads_backward_f32  at most 5 launches: input gradients per depth (the depth-1 one reduces over every head that
+ *       reads hs[l]; ReLU masks from the saved activations), one grouped weight-gradient pass in row chunks, one chunk-ordered
+ *       reduce.  Writes every element of grad_hs [L, M, C] and of every weight / bias gradient (host arrays shaped as the
+ *       weights').  workspace: at least msda_heads_workspace_bytes(...) bytes.
+ *   msda_heads_supported     1 when the kernels take hidden size C.
+ * Fixed summation order: bitwise reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+#define MSDA_HEADS_ARCTIC 0
+#define MSDA_HEADS_ASSEMBLY 1
+#define MSDA_HEADS_SHARED_CLS 1u
+#define MSDA_HEADS_SHARED_MLP 2u
+int msda_heads_supported(int C);
+unsigned long long msda_heads_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
+int msda_heads_forward_f32(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
+                           const float *init_ref, const float *inter_ref, const float *const *cls_w,
+                           const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,
+                           const float *const *shared_w, const float *const *shared_b, float *logits, float *const *kp_out,
+                           float *const *shared_out, float *hidden, float *sig, msda_stream_t stream);
+int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
+                            const float *init_ref, const float *inter_ref, const float *const *cls_w,
+                            const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,
+                            const float *const *shared_w, const float *const *shared_b, const float *hidden,
+                            const float *sig, const float *grad_logits, const float *const *grad_kp,
+                            const float *const *grad_shared, float *grad_hs, float *const *grad_cls_w,
+                            float *const *grad_cls_b, float *const *grad_mlp_w, float *const *grad_mlp_b,
+                            float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
+                            unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

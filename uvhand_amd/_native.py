@@ -43,6 +43,7 @@ _SYMBOLS = (
     "msda_assembly_refine_f32", "msda_assembly_proposals_f32", "msda_assembly_select_f32",
     "msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32",
     "msda_criterion_fwd_f32", "msda_criterion_bwd_f32",
+    "msda_heads_supported", "msda_heads_workspace_bytes", "msda_heads_forward_f32", "msda_heads_backward_f32",
 )
 
 
@@ -79,6 +80,10 @@ def load():
     lib.msda_two_stage_select_supported.restype = ctypes.c_int
     lib.msda_two_stage_select_supported.argtypes = [ctypes.c_int] * 3
     lib.msda_describe_plan.restype = ctypes.c_int
+    lib.msda_heads_supported.restype = ctypes.c_int
+    lib.msda_heads_supported.argtypes = [ctypes.c_int]
+    lib.msda_heads_workspace_bytes.restype = ctypes.c_ulonglong
+    lib.msda_heads_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_uint]
     lib.msda_describe_plan.argtypes = [ctypes.c_int] * 9 + [ctypes.c_uint, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     _lib = lib
     return lib
@@ -1255,3 +1260,85 @@ def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
     if rc != 0:
         _raise(lib, rc, "criterion_bwd")
     return g_logits, g_hand, g_obj
+
+
+# ---- the DeformableDETR prediction heads (csrc/msda_heads.hip) ------------------------------------------------------------
+HEADS_ARCTIC, HEADS_ASSEMBLY = 0, 1
+HEADS_SHARED_CLS, HEADS_SHARED_MLP = 1, 2
+HEADS_SHARED_WIDTHS = (48, 10, 3, 3, 3, 1)
+_HEADS_ARGS = [_CI, _CI, _LL, _CI, _CI, _CI, _CI, ctypes.c_uint] + [_VP] * 9
+
+
+def heads_supported(C):
+    """msda_heads_supported (include/msda.h): 1 when the heads kernels take hidden size C."""
+    return bool((_lib or load()).msda_heads_supported(int(C)))
+
+
+def heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
+    return int((_lib or load()).msda_heads_workspace_bytes(int(kind), int(L), int(M), int(C), int(K), int(n_mlp), int(flags)))
+
+
+def _ptrs_or_none(ts):
+    return _ptr_array(ts) if ts else None
+
+
+def _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
+    """hs [L, M, C]; cls = (weights, biases); mlp = (weights, biases) in (head, layer, level) order; shared likewise."""
+    L, M, C = hs.shape
+    K = cls[0][0].shape[0]
+    n_mlp = len(mlp[0]) // (3 * (1 if flags & HEADS_SHARED_MLP else L)) if mlp[0] else 0
+    R = init_ref.shape[-1] if init_ref is not None else 0
+    tensors = [hs] + list(cls[0]) + list(cls[1]) + list(mlp[0]) + list(mlp[1]) + list(shared[0]) + list(shared[1])
+    tensors += [t for t in (init_ref, inter_ref) if t is not None]
+    if not all(_f32_cuda(t) and t.device == hs.device for t in tensors):
+        raise RuntimeError("detr_heads: expected contiguous fp32 CUDA tensors on one device")
+    return [int(kind), int(L), int(M), int(C), int(K), int(n_mlp), int(R), int(flags), hs.data_ptr(),
+            init_ref.data_ptr() if init_ref is not None else None, inter_ref.data_ptr() if inter_ref is not None else None,
+            _ptr_array(cls[0]), _ptr_array(cls[1]), _ptrs_or_none(mlp[0]), _ptrs_or_none(mlp[1]), _ptrs_or_none(shared[0]),
+            _ptrs_or_none(shared[1])], (L, M, C, K, n_mlp)
+
+
+def heads_forward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
+    """msda_heads_forward_f32: (logits [L, M, K], kp outputs [L, M, D] per MLP head, shared outputs [L, M, n_g],
+    hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D]).  At most 3 launches, no host synchronisation."""
+    lib = _lib or load()
+    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
+    D = 42 if kind == HEADS_ARCTIC else 63
+    dev = hs.device
+    with _DeviceGuard(dev):
+        logits = torch.empty(L, M, K, dtype=torch.float32, device=dev)
+        kp = [torch.empty(L, M, D, dtype=torch.float32, device=dev) for _ in range(n_mlp)]
+        sh = [torch.empty(L, M, n, dtype=torch.float32, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
+        hidden = torch.empty(n_mlp, 2, L, M, C, dtype=torch.float32, device=dev)
+        sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
+        rc = _entry(lib, "msda_heads_forward_f32", _HEADS_ARGS + [_VP] * 6)(
+            *args, logits.data_ptr(), _ptrs_or_none(kp), _ptrs_or_none(sh), hidden.data_ptr() if n_mlp else None,
+            sig.data_ptr() if n_mlp else None, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "heads_forward")
+    return logits, kp, sh, hidden, sig
+
+
+def heads_backward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
+    """msda_heads_backward_f32: (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases),
+    every element written.  At most 5 launches, no host synchronisation."""
+    lib = _lib or load()
+    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
+    grads = [grad_logits] + list(grad_kp) + list(grad_shared)
+    if not all(_f32_cuda(t) and t.device == hs.device for t in grads):
+        raise RuntimeError("detr_heads: expected contiguous fp32 CUDA output gradients")
+    dev = hs.device
+    with _DeviceGuard(dev):
+        ws = torch.empty(max(1, heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags) // 4), dtype=torch.float32, device=dev)
+        grad_hs = torch.empty_like(hs)
+        g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
+        g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
+        g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
+        rc = _entry(lib, "msda_heads_backward_f32", _HEADS_ARGS + [_VP] * 13 + [ctypes.c_ulonglong, _VP])(
+            *args, hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(),
+            _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared), grad_hs.data_ptr(), _ptr_array(g_cls[0]),
+            _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]), _ptrs_or_none(g_sh[0]),
+            _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "heads_backward")
+    return grad_hs, g_cls, g_mlp, g_sh

@@ -223,4 +223,105 @@ int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, in
 int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
                          const int32_t *stats, hipStream_t stream);
 
+// ---- the DeformableDETR prediction heads as grouped fp32 GEMMs (msda_heads.hip) ----
+// Every problem table travels by value in the kernel arguments (each struct below stays under 4 KB).
+constexpr int kHeadsMaxLevels = 8, kHeadsMaxMlp = 2, kHeadsShared = 6;
+constexpr int kHeadsWgradChunk = 2048;                              // rows per weight-gradient partial
+constexpr int kHeadsEpiBias = 0, kHeadsEpiRelu = 1, kHeadsEpiArctic = 2, kHeadsEpiAssembly = 3;
+constexpr int kHeadsModePlain = 0, kHeadsModeSigmoid = 1, kHeadsModeRelu = 2;
+struct HeadsFwdGroup {          // columns [off, off + n) of a problem: one weight [n, C], its bias, its output [L * M, n]
+    const float *w, *b;
+    float *out;
+    int n, off;
+};
+struct HeadsFwdProb {           // rows [row0, row0 + rows) of the flattened input a [L * M, C]
+    const float *a;
+    float *sig;                 // keypoint epilogues: the saved sigmoid [L * M, n]
+    int row0, rows, n, epi, g0, ng, tile0, pad;
+};
+constexpr int kHeadsFwdMaxProbs = kHeadsMaxLevels * (1 + kHeadsMaxMlp) + 1;
+constexpr int kHeadsFwdMaxGroups = kHeadsFwdMaxProbs + kHeadsShared;
+struct HeadsFwdArgs {
+    HeadsFwdProb p[kHeadsFwdMaxProbs];
+    HeadsFwdGroup g[kHeadsFwdMaxGroups];
+    const float *init_ref, *inter_ref;
+    int nprob, M, C, R;
+};
+struct HeadsDgradSeg {          // one reduction segment: dy [L * M, k] (o mode, aux of the same layout) times w [k, C]
+    const float *a, *aux, *w;
+    int k, mode;
+};
+struct HeadsDgradProb {
+    float *out;                 // [L * M, C]
+    int row0, rows, s0, ns, tile0, pad;
+};
+constexpr int kHeadsDgradMaxProbs = kHeadsMaxLevels * kHeadsMaxMlp;
+constexpr int kHeadsDgradMaxSegs = kHeadsMaxLevels * (1 + kHeadsMaxMlp + kHeadsShared);
+struct HeadsDgradArgs {
+    HeadsDgradProb p[kHeadsDgradMaxProbs];
+    HeadsDgradSeg s[kHeadsDgradMaxSegs];
+    int nprob, C;
+};
+struct HeadsWgradProb {         // dW [n, C] of one weight over rows [row0, row0 + rows): dy / aux [L * M, n], x [L * M, C]
+    const float *dy, *aux, *x;
+    long long part;             // float offset of its partials in the workspace: [chunks][n][C], then [chunks][n]
+    int row0, rows, n, mode, chunks, tile0;
+};
+constexpr int kHeadsWgradMaxProbs = kHeadsMaxLevels * (1 + 3 * kHeadsMaxMlp) + kHeadsShared;
+struct HeadsWgradArgs {
+    HeadsWgradProb p[kHeadsWgradMaxProbs];
+    float *ws;
+    int nprob, C;
+};
+struct HeadsReduceProb {
+    long long part;
+    float *dw, *db;
+    int n, chunks, blk0, pad;
+};
+struct HeadsReduceArgs {
+    HeadsReduceProb p[kHeadsWgradMaxProbs];
+    const float *ws;
+    int nprob, C;
+};
+static_assert(sizeof(HeadsFwdArgs) <= 4000 && sizeof(HeadsDgradArgs) <= 4000 && sizeof(HeadsWgradArgs) <= 4000
+              && sizeof(HeadsReduceArgs) <= 4000, "kernel argument tables");
+int launch_heads_forward(const HeadsFwdArgs &a, int tiles, hipStream_t stream);
+int launch_heads_dgrad(const HeadsDgradArgs &a, int tiles, hipStream_t stream);
+int launch_heads_wgrad(const HeadsWgradArgs &a, int tiles, hipStream_t stream);
+int launch_heads_reduce(const HeadsReduceArgs &a, int blocks, hipStream_t stream);
+
+// One call's operands as the C entries receive them (include/msda.h, msda_heads_*); the plan functions check them and build
+// the problem tables without launching anything, the run functions launch.
+struct HeadsCall {
+    int kind, L, n_mlp, R, C, K;
+    long long M;
+    unsigned flags;
+    const float *hs, *init_ref, *inter_ref;
+    const float *const *cls_w, *const *cls_b, *const *mlp_w, *const *mlp_b, *const *shared_w, *const *shared_b;
+    float *logits, *const *kp_out, *const *shared_out, *hidden, *sig;
+    const float *grad_logits, *const *grad_kp, *const *grad_shared;
+    float *grad_hs, *const *grad_cls_w, *const *grad_cls_b, *const *grad_mlp_w, *const *grad_mlp_b, *const *grad_shared_w,
+        *const *grad_shared_b;
+    void *ws;
+    unsigned long long ws_bytes;
+};
+struct HeadsFwdPlan {
+    HeadsFwdArgs a[3];
+    int tiles[3];
+};
+struct HeadsBwdPlan {
+    HeadsDgradArgs d[3];
+    int dtiles[3];
+    HeadsWgradArgs w;
+    int wtiles;
+    HeadsReduceArgs r;
+    int rblocks;
+};
+int heads_check(const HeadsCall &c, bool backward);
+unsigned long long heads_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
+int heads_plan_forward(const HeadsCall &c, HeadsFwdPlan &plan);
+int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan);
+int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream);
+int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream);
+
 }  // namespace msda

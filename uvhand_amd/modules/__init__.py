@@ -3,8 +3,10 @@ from .assembly_transformer import DeformableTransformerDecoder as AssemblyDeform
 from .deformable_layers import (DeformableTransformerDecoder, DeformableTransformerDecoderLayer,
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
 from .deformable_transformer import DeformableTransformer
+from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
 from .ms_deform_attn import MSDeformAttn
 
 __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTransformerDecoderLayer",
            "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
-           "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder"]
+           "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
+           "ArcticDeformableDETR", "AssemblyDeformableDETR"]

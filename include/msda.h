@@ -614,6 +614,55 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
                             float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                             unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- SmoothNet (models/smoothnet.py:7-178): MotionSmoother modules as grouped fp32 GEMMs, and get_arctic_item's query
+ * selection (arctic_tools/process.py:20-70) ---------------------------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Smoother geometry: window T, output size O, hidden H, residual hidden R, num_blocks nb (3 <= T, O <= 4096, H and R multiples
+ * of 4 in [4, 4096], nb <= 4); n_mod <= 6 MotionSmoother modules; n_calls <= 12 calls, call i runs module call_mod[i] (at
+ * most 4 calls per module) on x[i] [call_B[i] * T, call_C[i]] (the reference's view(B, T, C)) and writes out[i]
+ * [call_B[i] * O, call_C[i]].  params: HOST array of n_mod * (3 * (4 + 4 * nb) + 2) pointers, each module's parameters in its
+ * parameters() order (pos, vel, acc Smoothers: encoder weight, bias, per block linear1 weight, bias, linear2 weight, bias,
+ * decoder weight, bias; then fusion weight, bias), hidden-layer weights 16-byte aligned.  Dropout (training != 0 and p > 0):
+ * keep probability 1 - p, scale 1 / (1 - p), the mask a hash of (*seed, problem = module * 3 + smoother, layer, module row,
+ * column) — layer 2j - 1 / 2j: the two Linears of block j — regenerated in the backward; not nn.Dropout's stream.
+ *   msda_smoother_workspace_bytes  which 0: the activation buffer the forward fills (and the backward reads); which 1: the
+ *       backward workspace.  0 for an invalid geometry.
+ *   msda_smoother_forward_f32      2 nb + 3 launches (one per depth over every Smoother of every module, then the fusions).
+ *   msda_smoother_backward_f32     at most 2 nb + 5 launches: input gradients per depth (the encoders' only when some grad_x[i]
+ *       is non-null), one weight-gradient launch over every layer, one fold of the pos / vel / acc adjoints onto grad_x[i]
+ *       [B * T, C].  grad_params: one flat buffer, the modules' parameters concatenated in the order of `params`; every
+ *       element written.  grad_x: host array (may be NULL), entries NULL where no input gradient is wanted.
+ *   msda_smoother_dropout_mask_f32 (tests) the keep mask (1 / 0) of (problem, layer) over [rows, cols], from the kernels'
+ *       own device function.
+ * Selection: logits [bs, Q, K]; sources (HOST array of 6, fp32 contiguous): hand_cam [bs, Q, 3], obj_cam [bs, Q, 3],
+ * mano_pose [bs, Q, 48], mano_shape [bs, Q, 10], obj_rad [bs, Q, 1], obj_rot [bs, Q, 3]; out (HOST array of 9): root_l,
+ * root_r, root_o [bs, 3], pose_l, pose_r [bs, 48], shape_l, shape_r [bs, 10], obj_rot [bs, 3], obj_rad [bs, 1]; idx [bs, 3]
+ * (left, right, object query).  The object rule runs over classes 1 .. obj_end - 1 (obj_end = cfg.hand_idx[0]).
+ *   msda_arctic_item_forward_f32   one launch.  msda_arctic_item_backward_f32: one launch; writes every element of the six
+ *       source gradients; grad_out entries may be NULL (no gradient).
+ * Fixed summation order, no atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any
+ * launch. */
+int msda_smoother_supported(int T, int O, int H, int R, int num_blocks);
+unsigned long long msda_smoother_workspace_bytes(int T, int O, int H, int R, int num_blocks, int n_mod, int n_calls,
+                                                 const int *call_mod, const int *call_B, const int *call_C, int which);
+int msda_smoother_forward_f32(int T, int O, int H, int R, int num_blocks, int n_mod, int n_calls, const int *call_mod,
+                              const int *call_B, const int *call_C, const float *const *x, const float *const *params,
+                              float *const *out, float *act, unsigned long long act_bytes, int training, float p,
+                              const unsigned long long *seed, msda_stream_t stream);
+int msda_smoother_backward_f32(int T, int O, int H, int R, int num_blocks, int n_mod, int n_calls, const int *call_mod,
+                               const int *call_B, const int *call_C, const float *const *x, const float *const *params,
+                               const float *act, unsigned long long act_bytes, const float *const *grad_out,
+                               float *const *grad_x, float *grad_params, int training, float p,
+                               const unsigned long long *seed, void *workspace, unsigned long long workspace_bytes,
+                               msda_stream_t stream);
+int msda_smoother_dropout_mask_f32(const unsigned long long *seed, int problem, int layer, int rows, int cols, float p, float *mask,
+                                   msda_stream_t stream);
+int msda_arctic_item_forward_f32(int bs, int Q, int K, int obj_end, int hand_l, int hand_r, const float *logits,
+                                 const float *const *sources, float *const *out, int64_t *idx, msda_stream_t stream);
+int msda_arctic_item_backward_f32(int bs, int Q, const int64_t *idx, const float *const *grad_out, float *const *grad_sources,
+                                  msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -44,6 +44,8 @@ _SYMBOLS = (
     "msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32",
     "msda_criterion_fwd_f32", "msda_criterion_bwd_f32",
     "msda_heads_supported", "msda_heads_workspace_bytes", "msda_heads_forward_f32", "msda_heads_backward_f32",
+    "msda_smoother_supported", "msda_smoother_workspace_bytes", "msda_smoother_forward_f32", "msda_smoother_backward_f32",
+    "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32", "msda_arctic_item_backward_f32",
 )
 
 
@@ -85,6 +87,10 @@ def load():
     lib.msda_heads_workspace_bytes.restype = ctypes.c_ulonglong
     lib.msda_heads_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_uint]
     lib.msda_describe_plan.argtypes = [ctypes.c_int] * 9 + [ctypes.c_uint, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    lib.msda_smoother_supported.restype = ctypes.c_int
+    lib.msda_smoother_supported.argtypes = [ctypes.c_int] * 5
+    lib.msda_smoother_workspace_bytes.restype = ctypes.c_ulonglong
+    lib.msda_smoother_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_void_p] * 3 + [ctypes.c_int]
     _lib = lib
     return lib
 
@@ -1342,3 +1348,146 @@ def heads_backward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidde
     if rc != 0:
         _raise(lib, rc, "heads_backward")
     return grad_hs, g_cls, g_mlp, g_sh
+
+
+# ---- SmoothNet: MotionSmoother modules and get_arctic_item's selection (msda_smoother.hip, msda_arctic_item.hip) ----------
+SMOOTHER_MAX_MODULES, SMOOTHER_MAX_CALLS, SMOOTHER_MAX_CALLS_PER_MODULE = 6, 12, 4
+_SM_GEO = [_CI] * 7 + [_VP] * 3
+
+
+def smoother_supported(T, O, H, R, num_blocks):
+    """msda_smoother_supported (include/msda.h): 1 when the smoother kernels take this geometry."""
+    return bool((_lib or load()).msda_smoother_supported(int(T), int(O), int(H), int(R), int(num_blocks)))
+
+
+def _int_array(vals):
+    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+
+
+def _smoother_geo(dims, n_mod, call_mod, call_B, call_C):
+    T, O, H, R, nb = dims
+    return [int(T), int(O), int(H), int(R), int(nb), int(n_mod), len(call_mod), _int_array(call_mod), _int_array(call_B),
+            _int_array(call_C)]
+
+
+def smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, which):
+    """msda_smoother_workspace_bytes: which 0 = the activation buffer, 1 = the backward workspace (0: invalid geometry)."""
+    lib = _lib or load()
+    return int(lib.msda_smoother_workspace_bytes(*_smoother_geo(dims, n_mod, call_mod, call_B, call_C), int(which)))
+
+
+def _smoother_check(what, xs, params, call_mod, call_C, T):
+    dev = xs[0].device
+    if not all(_f32_cuda(t) and t.device == dev for t in list(xs) + list(params)):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+    if len(xs) != len(call_mod) or any(x.dim() != 2 or x.shape[1] != c or x.shape[0] % T for x, c in zip(xs, call_C)):
+        raise RuntimeError("%s: every input must be [B * T, C]" % what)
+    return dev
+
+
+def smoother_forward(dims, n_mod, call_mod, xs, params, training=False, p=0.0, seed=None):
+    """msda_smoother_forward_f32.  xs: per call [B * T, C]; params: every module's parameters in parameters() order.
+    Returns (outputs [B * O, C] per call, the activation buffer the backward reads).  2 nb + 3 launches, no host sync."""
+    lib = _lib or load()
+    T, O = dims[0], dims[1]
+    call_C = [x.shape[1] for x in xs]
+    call_B = [x.shape[0] // T if T else 0 for x in xs]
+    dev = _smoother_check("smoother_forward", xs, params, call_mod, call_C, T)
+    geo = _smoother_geo(dims, n_mod, call_mod, call_B, call_C)
+    if training and p > 0 and (seed is None or not seed.is_cuda or seed.dtype != torch.int64):
+        raise RuntimeError("smoother_forward: training with p > 0 needs a one-element int64 CUDA seed")
+    with _DeviceGuard(dev):
+        nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 0)
+        act = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        outs = [torch.empty(b * O, c, dtype=torch.float32, device=dev) for b, c in zip(call_B, call_C)]
+        rc = _entry(lib, "msda_smoother_forward_f32", _SM_GEO + [_VP] * 4 + [ctypes.c_ulonglong, _CI, ctypes.c_float, _VP, _VP])(
+            *geo, _ptr_array(xs), _ptr_array(params), _ptr_array(outs), act.data_ptr(), act.numel() * 4, int(bool(training)),
+            float(p), seed.data_ptr() if seed is not None else None, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "smoother_forward")
+    return outs, act
+
+
+def smoother_backward(dims, n_mod, call_mod, xs, params, act, grad_outs, want_grad_x, training=False, p=0.0, seed=None):
+    """msda_smoother_backward_f32: (input gradients per call — None where not wanted —, one flat buffer of every parameter's
+    gradient in the order of `params`).  At most 2 nb + 5 launches, no host sync."""
+    lib = _lib or load()
+    T = dims[0]
+    call_C = [x.shape[1] for x in xs]
+    call_B = [x.shape[0] // T for x in xs]
+    dev = _smoother_check("smoother_backward", xs, params, call_mod, call_C, T)
+    if not all(_f32_cuda(g) and g.device == dev for g in grad_outs):
+        raise RuntimeError("smoother_backward: expected contiguous fp32 CUDA output gradients")
+    geo = _smoother_geo(dims, n_mod, call_mod, call_B, call_C)
+    with _DeviceGuard(dev):
+        nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 1)
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        gp = torch.empty(sum(t.numel() for t in params), dtype=torch.float32, device=dev)
+        gx = [torch.empty_like(x) if w else None for x, w in zip(xs, want_grad_x)]
+        gx_arr = (_VP * len(gx))(*[g.data_ptr() if g is not None else None for g in gx]) if any(want_grad_x) else None
+        rc = _entry(lib, "msda_smoother_backward_f32", _SM_GEO + [_VP, _VP, _VP, ctypes.c_ulonglong, _VP, _VP, _VP, _CI,
+                                                                   ctypes.c_float, _VP, _VP, ctypes.c_ulonglong, _VP])(
+            *geo, _ptr_array(xs), _ptr_array(params), act.data_ptr(), act.numel() * 4, _ptr_array(grad_outs), gx_arr,
+            gp.data_ptr(), int(bool(training)), float(p), seed.data_ptr() if seed is not None else None, ws.data_ptr(),
+            ws.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "smoother_backward")
+    return gx, gp
+
+
+def smoother_dropout_mask(seed, problem, layer, rows, cols, p):
+    """msda_smoother_dropout_mask_f32 (tests): the kernels' keep mask (1 / 0) of (problem, layer) over [rows, cols]."""
+    lib = _lib or load()
+    if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise RuntimeError("smoother_dropout_mask: seed must be a one-element int64 CUDA tensor")
+    dev = seed.device
+    with _DeviceGuard(dev):
+        mask = torch.empty(rows, cols, dtype=torch.float32, device=dev)
+        rc = _entry(lib, "msda_smoother_dropout_mask_f32", [_VP, _CI, _CI, _CI, _CI, ctypes.c_float, _VP, _VP])(
+            seed.data_ptr(), int(problem), int(layer), int(rows), int(cols), float(p), mask.data_ptr(), _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "smoother_dropout_mask")
+    return mask
+
+
+ARCTIC_ITEM_WIDTHS = (3, 3, 48, 10, 1, 3)             # hand_cam, obj_cam, mano_pose, mano_shape, obj_rad, obj_rot
+ARCTIC_ITEM_OUT_SOURCES = (0, 0, 1, 2, 2, 3, 3, 5, 4)  # root_l, root_r, root_o, pose_l, pose_r, shape_l, shape_r, rot, rad
+
+
+def arctic_item_forward(logits, sources, obj_end, hand_l, hand_r):
+    """msda_arctic_item_forward_f32: (nine gathered outputs, idx [bs, 3] int64: left, right, object).  One launch."""
+    lib = _lib or load()
+    bs, Q, K = logits.shape
+    dev = logits.device
+    if not all(_f32_cuda(t) and t.device == dev for t in [logits] + list(sources)):
+        raise RuntimeError("arctic_item: expected contiguous fp32 CUDA tensors on one device")
+    if any(tuple(s.shape) != (bs, Q, w) for s, w in zip(sources, ARCTIC_ITEM_WIDTHS)):
+        raise RuntimeError("arctic_item: sources must be [bs, Q, w] with w = %s" % (ARCTIC_ITEM_WIDTHS,))
+    with _DeviceGuard(dev):
+        outs = [torch.empty(bs, ARCTIC_ITEM_WIDTHS[s], dtype=torch.float32, device=dev) for s in ARCTIC_ITEM_OUT_SOURCES]
+        idx = torch.empty(bs, 3, dtype=torch.int64, device=dev)
+        rc = _entry(lib, "msda_arctic_item_forward_f32", [_CI] * 6 + [_VP] * 5)(
+            bs, Q, K, int(obj_end), int(hand_l), int(hand_r), logits.data_ptr(), _ptr_array(sources), _ptr_array(outs),
+            idx.data_ptr(), _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "arctic_item_forward")
+    return outs, idx
+
+
+def arctic_item_backward(idx, Q, grad_outs):
+    """msda_arctic_item_backward_f32: the six source gradients [bs, Q, w], every element written.  One launch."""
+    lib = _lib or load()
+    bs = idx.shape[0]
+    dev = idx.device
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()):
+        raise RuntimeError("arctic_item_backward: idx must be a contiguous int64 CUDA tensor")
+    if not all(g is None or (_f32_cuda(g) and g.device == dev) for g in grad_outs):
+        raise RuntimeError("arctic_item_backward: expected contiguous fp32 CUDA output gradients")
+    with _DeviceGuard(dev):
+        gsrc = [torch.empty(bs, Q, w, dtype=torch.float32, device=dev) for w in ARCTIC_ITEM_WIDTHS]
+        garr = (_VP * len(grad_outs))(*[g.data_ptr() if g is not None else None for g in grad_outs])
+        rc = _entry(lib, "msda_arctic_item_backward_f32", [_CI, _CI] + [_VP] * 4)(
+            bs, int(Q), idx.data_ptr(), garr, _ptr_array(gsrc), _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "arctic_item_backward")
+    return gsrc

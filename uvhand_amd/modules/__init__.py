@@ -5,8 +5,10 @@ from .deformable_layers import (DeformableTransformerDecoder, DeformableTransfor
 from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
 from .ms_deform_attn import MSDeformAttn
+from .smoothnet import ArcticSmoother, MotionSmoother, Smoother, SmootherResBlock
 
 __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTransformerDecoderLayer",
            "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
            "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
-           "ArcticDeformableDETR", "AssemblyDeformableDETR"]
+           "ArcticDeformableDETR", "AssemblyDeformableDETR",
+           "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother"]

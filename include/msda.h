@@ -663,6 +663,33 @@ int msda_arctic_item_forward_f32(int bs, int Q, int K, int obj_end, int hand_l, 
 int msda_arctic_item_backward_f32(int bs, int Q, const int64_t *idx, const float *const *grad_out, float *const *grad_sources,
                                   msda_stream_t stream);
 
+/* ---- Swin window attention (models/swin_transformer.py:126-142 WindowAttention.forward, :210-240 SwinTransformerBlock's pad /
+ * roll / partition / reverse / crop, :339-357 BasicLayer's shift mask) for head_dim 32 -----------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Geometry: B images of H x W real tokens, C = 32 nH channels, window ws (1 <= ws <= 12), shift 0 <= shift < ws.  qkv
+ * [B H W, 3 C]: the qkv Linear's output on the real tokens only, columns (3, nH, 32); qkv_bias [3 C] or NULL (no bias: padded
+ * tokens' k and v are 0); table [(2 ws - 1)^2, nH] (relative_position_bias_table); out [B H W, C], columns (nH, 32).  The map
+ * is padded to Hp = ceil(H / ws) ws, Wp likewise, and rolled by -shift: window position (Y, X) reads token ((Y + shift) mod Hp,
+ * (X + shift) mod Wp); one outside H x W is padded (k, v = the bias's parts, its output cropped).  q is scaled by 32^-0.5; the
+ * bias index and the -100 shift mask are computed from coordinates.
+ *   msda_swin_attn_workspace_bytes  which 0: the lse buffer the forward fills and the backward reads; which 1: the backward
+ *       workspace.  0 for an unsupported geometry.
+ *   msda_swin_attn_forward_f32   one launch: out for every real token, the log-sum-exp of every real query.
+ *   msda_swin_attn_backward_f32  three launches: grad_qkv [B H W, 3 C] (every element written), grad_table [(2 ws - 1)^2, nH],
+ *       grad_qkv_bias [3 C] (may be NULL): the k and v gradients summed over padded tokens, q part 0 — the extra gradient of
+ *       qkv.bias that the padded rows carry (autograd adds the Linear's own).
+ * Fixed summation order, no atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any
+ * launch. */
+int msda_swin_attn_supported(int B, int H, int W, int C, int nH, int ws, int shift);
+unsigned long long msda_swin_attn_workspace_bytes(int B, int H, int W, int C, int nH, int ws, int shift, int which);
+int msda_swin_attn_forward_f32(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *qkv_bias,
+                               const float *table, float *out, float *lse, unsigned long long lse_bytes, msda_stream_t stream);
+int msda_swin_attn_backward_f32(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *qkv_bias,
+                                const float *table, const float *out, const float *lse, unsigned long long lse_bytes,
+                                const float *grad_out, float *grad_qkv, float *grad_table, float *grad_qkv_bias, void *workspace,
+                                unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -46,6 +46,7 @@ _SYMBOLS = (
     "msda_heads_supported", "msda_heads_workspace_bytes", "msda_heads_forward_f32", "msda_heads_backward_f32",
     "msda_smoother_supported", "msda_smoother_workspace_bytes", "msda_smoother_forward_f32", "msda_smoother_backward_f32",
     "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32", "msda_arctic_item_backward_f32",
+    "msda_swin_attn_supported", "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_f32", "msda_swin_attn_backward_f32",
 )
 
 
@@ -91,6 +92,10 @@ def load():
     lib.msda_smoother_supported.argtypes = [ctypes.c_int] * 5
     lib.msda_smoother_workspace_bytes.restype = ctypes.c_ulonglong
     lib.msda_smoother_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_void_p] * 3 + [ctypes.c_int]
+    lib.msda_swin_attn_supported.restype = ctypes.c_int
+    lib.msda_swin_attn_supported.argtypes = [ctypes.c_int] * 7
+    lib.msda_swin_attn_workspace_bytes.restype = ctypes.c_ulonglong
+    lib.msda_swin_attn_workspace_bytes.argtypes = [ctypes.c_int] * 8
     _lib = lib
     return lib
 
@@ -1491,3 +1496,70 @@ def arctic_item_backward(idx, Q, grad_outs):
     if rc != 0:
         _raise(lib, rc, "arctic_item_backward")
     return gsrc
+
+
+# ---- Swin window attention, head_dim 32 (msda_swin.hip) ------------------------------------------------------------------
+SWIN_MAX_WINDOW = 12
+
+
+def swin_attn_supported(geo):
+    """msda_swin_attn_supported: geo = (B, H, W, C, nH, ws, shift)."""
+    return bool((_lib or load()).msda_swin_attn_supported(*[int(g) for g in geo]))
+
+
+def swin_attn_workspace_bytes(geo, which):
+    """msda_swin_attn_workspace_bytes: which 0 = the lse buffer, 1 = the backward workspace (0: unsupported geometry)."""
+    return int((_lib or load()).msda_swin_attn_workspace_bytes(*[int(g) for g in geo], int(which)))
+
+
+def _swin_check(what, geo, tensors):
+    dev = tensors[0].device
+    if not all(t is None or (_f32_cuda(t) and t.device == dev) for t in tensors):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+    B, H, W, C, nH, ws, _ = geo
+    qkv, bias, table = tensors[:3]
+    if tuple(qkv.shape) != (B * H * W, 3 * C) or (bias is not None and tuple(bias.shape) != (3 * C,)) \
+            or tuple(table.shape) != ((2 * ws - 1) ** 2, nH):
+        raise RuntimeError("%s: expected qkv [B*H*W, 3C], qkv_bias [3C], table [(2ws-1)^2, nH]" % what)
+    return dev
+
+
+def _vp(t):
+    return t.data_ptr() if t is not None else None
+
+
+def swin_attn_forward(geo, qkv, bias, table):
+    """msda_swin_attn_forward_f32: (out [B*H*W, C], lse).  One launch, no host sync."""
+    lib = _lib or load()
+    geo = tuple(int(g) for g in geo)
+    dev = _swin_check("swin_attn_forward", geo, [qkv, bias, table])
+    with _DeviceGuard(dev):
+        out = torch.empty(qkv.shape[0], geo[3], dtype=torch.float32, device=dev)
+        nbytes = swin_attn_workspace_bytes(geo, 0)
+        lse = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        rc = _entry(lib, "msda_swin_attn_forward_f32", [_CI] * 7 + [_VP] * 5 + [ctypes.c_ulonglong, _VP])(
+            *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(), out.data_ptr(), lse.data_ptr(), lse.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "swin_attn_forward")
+    return out, lse
+
+
+def swin_attn_backward(geo, qkv, bias, table, out, lse, grad_out):
+    """msda_swin_attn_backward_f32: (grad_qkv [B*H*W, 3C], grad_table, grad_bias [3C] — the padded tokens' part, q part 0 —
+    or None without a bias).  Three launches, no host sync."""
+    lib = _lib or load()
+    geo = tuple(int(g) for g in geo)
+    dev = _swin_check("swin_attn_backward", geo, [qkv, bias, table, out, lse, grad_out])
+    with _DeviceGuard(dev):
+        gq = torch.empty_like(qkv)
+        gt = torch.empty_like(table)
+        gb = torch.empty_like(bias) if bias is not None else None
+        nbytes = swin_attn_workspace_bytes(geo, 1)
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        rc = _entry(lib, "msda_swin_attn_backward_f32", [_CI] * 7 + [_VP] * 5 + [ctypes.c_ulonglong] + [_VP] * 5
+                    + [ctypes.c_ulonglong, _VP])(
+            *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(), out.data_ptr(), lse.data_ptr(), lse.numel() * 4,
+            grad_out.data_ptr(), gq.data_ptr(), gt.data_ptr(), _vp(gb), ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "swin_attn_backward")
+    return gq, gt, gb

@@ -1267,4 +1267,34 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
     return msda::heads_run_backward(plan, (hipStream_t)stream);
 }
 
+/* ---- Swin window attention (msda_swin.hip): replaces models/swin_transformer.py:126-142 (WindowAttention.forward's scores,
+ * relative position bias, mask, softmax and weighted sum), :210-240 (SwinTransformerBlock's pad, roll, partition, reverse, roll
+ * back and crop) and :339-357 (BasicLayer's shift mask) ---- */
+int msda_swin_attn_supported(int B, int H, int W, int C, int nH, int ws, int shift)
+{
+    return msda::swin_supported(B, H, W, C, nH, ws, shift) ? 1 : 0;
+}
+
+unsigned long long msda_swin_attn_workspace_bytes(int B, int H, int W, int C, int nH, int ws, int shift, int which)
+{
+    return msda::swin_workspace_bytes(B, H, W, C, nH, ws, shift, which);
+}
+
+int msda_swin_attn_forward_f32(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *qkv_bias,
+                               const float *table, float *out, float *lse, unsigned long long lse_bytes, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::swin_forward(B, H, W, C, nH, ws, shift, qkv, qkv_bias, table, out, lse, lse_bytes, (hipStream_t)stream);
+}
+
+int msda_swin_attn_backward_f32(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *qkv_bias,
+                                const float *table, const float *out, const float *lse, unsigned long long lse_bytes,
+                                const float *grad_out, float *grad_qkv, float *grad_table, float *grad_qkv_bias, void *workspace,
+                                unsigned long long workspace_bytes, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::swin_backward(B, H, W, C, nH, ws, shift, qkv, qkv_bias, table, out, lse, lse_bytes, grad_out, grad_qkv,
+                               grad_table, grad_qkv_bias, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -324,4 +324,13 @@ int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan);
 int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream);
 int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream);
 
+// ---- Swin window attention, head_dim 32, windows up to 12 x 12 (msda_swin.hip; C entries msda_swin_attn_*) ----
+bool swin_supported(int B, int H, int W, int C, int nH, int ws, int shift);
+unsigned long long swin_workspace_bytes(int B, int H, int W, int C, int nH, int ws, int shift, int which);
+int swin_forward(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *bias, const float *table,
+                 float *out, float *lse, unsigned long long lse_bytes, hipStream_t stream);
+int swin_backward(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *bias, const float *table,
+                  const float *out, const float *lse, unsigned long long lse_bytes, const float *grad_out, float *grad_qkv,
+                  float *grad_table, float *grad_bias, void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
+
 }  // namespace msda

@@ -6,9 +6,13 @@ from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
 from .ms_deform_attn import MSDeformAttn
 from .smoothnet import ArcticSmoother, MotionSmoother, Smoother, SmootherResBlock
+from .swin import (BasicLayer, Joiner, Mlp, PatchEmbed, PatchMerging, PositionEmbeddingSine, SwinTransformer,
+                   SwinTransformerBlock, WindowAttention, build_backbone, build_swin_transformer)
 
 __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTransformerDecoderLayer",
            "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
            "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
            "ArcticDeformableDETR", "AssemblyDeformableDETR",
-           "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother"]
+           "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother",
+           "Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
+           "build_swin_transformer", "PositionEmbeddingSine", "Joiner", "build_backbone"]

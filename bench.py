@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MSDeformAttn fwd+bwd samples/s at the Swin-L 4-scale / 300-query shape.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2_decoder] [--no-graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2_decoder] [--no-graph] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one MSDeformAttnFunction.apply forward plus its backward (all three
@@ -17,15 +17,17 @@ replay) and replayed K times; --no-graph times the eager autograd path instead. 
 block (barrier + synchronize on both sides, max over ranks) is timed once, so --steps K times
 exactly K steps; --repeats R times R such blocks and reports the MEDIAN block.
 --dump-outputs DIR writes what the last timed step computed (the forward output and the three
-gradients, rank 0) as DIR/<name>.npy, for comparing two builds on the same seeded inputs;
-the same line also carries `eager_ms_per_step` (plain autograd calls, what a drop-in user of the
-module runs) and `graph1_ms_per_step` (one graph launch per step) next to the headline.
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
+gradients, rank 0) as DIR/<name>.npy, for comparing two builds on the same seeded inputs.
+Rank 0 prints ONE JSON line.  A plain run does only what its headline (`value`, `ms_per_step`)
+needs: set-up, warm-up, the timed steps, the dump and the line.  Everything else is measured
+after the timed steps and only with --full: `eager_ms_per_step` (plain autograd calls, what a
+drop-in user of the module runs) and `graph1_ms_per_step` (one graph launch per step) next to the
+headline, `kernels` (the forward and the backward on their own), and two extra
 objects: `roofline` (dominant kernel = backward; algorithmic bytes / HIP-event time
 against the 8 TB/s HBM peak; `traffic` = HBM bytes per launch from the PMC passes, only
 while the kernel sources are the profiled ones) and `cpu_baseline` (the PyTorch-CPU
 fallback port timed on the host cores of this node; test infrastructure under oracle/,
-never the thing measured as `value`).  At N = 1 the same line carries the rest of
+never the thing measured as `value`; --no-cpu-baseline skips it).  At N = 1 a --full line carries the rest of
 DESIGN.md's performance table, measured in the same run (none of it is `value`):
 `workloads` — cfg2_encoder / cfg4_decoder / cfg4_encoder in fp32, cfg2_decoder with
 bf16 rows, model-like locations (SURVEY 8d distribution B) at cfg2_decoder / cfg4_encoder and one
@@ -428,9 +430,14 @@ def main():
     ap.add_argument("--graph-steps", type=int, default=10,
                     help="steps captured per HIP graph (the timed loop replays it steps/graph-steps times; "
                          "reduced to a divisor of --steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the eager and one-step-per-graph launch modes, the kernels on "
+                         "their own (roofline), the rest of the performance table and the CPU baseline; a plain run "
+                         "measures only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-table", action="store_true",
-                    help="skip the `workloads` / `modules` arrays (the other shapes of DESIGN.md's performance table, ~2 s each)")
+                    help="with --full: skip the `workloads` / `modules` / `layers` arrays (the other shapes of DESIGN.md's "
+                         "performance table, ~2 s each)")
     ap.add_argument("--repeats", type=int, default=1,
                     help="timed blocks of --steps steps each (each bracketed by barrier + synchronize); the median block is "
                          "reported.  The default, 1, times exactly --steps steps")
@@ -438,7 +445,7 @@ def main():
                     help="after the timed steps, write what the last one computed (output, grad_value, grad_sampling_loc, "
                          "grad_attn_weight; rank 0) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded "
                          "sample of each array when they are larger)")
-    ap.add_argument("--kernel-iters", type=int, default=200)
+    ap.add_argument("--kernel-iters", type=int, default=200, help="with --full: calls per kernel timing of the roofline")
     ap.add_argument("--locations", default="uniform", choices=["uniform", "model"],
                     help="sampling-location distribution: uniform in [0,1) (headline) or model-like (SURVEY §8d B)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
@@ -543,7 +550,7 @@ def main():
 
         # the other two launch modes of the same step, for the record (not `value`)
         side = {}
-        if graph is not None and world == 1:
+        if args.full and graph is not None and world == 1:
             for _ in range(min(args.warmup, 20)):
                 step()
             n_eager = min(args.steps, 200)
@@ -560,32 +567,33 @@ def main():
                 print("bench: single-step graph failed (%s)" % exc, file=sys.stderr)
 
         # ---- per-kernel timing for the roofline (HIP events on the launch stream) ----
-        vd, ld, ad = value.detach(), loc.detach(), attn.detach()
-        if bf16:
-            ld, ad = ld.float(), ad.float()
-        # (as the autograd step runs them: the forward leaves its point table where the backward's plan reads one)
-        table = _native.ms_deform_attn_forward(vd, shapes, lsi, ld, ad, 64, with_table=True)[1]
-        fwd = lambda: _native.ms_deform_attn_forward(vd, shapes, lsi, ld, ad, 64, with_table=True if table is not None else None)
-        # bf16 rows: the kernel variant MSDeformAttnBF16Function picks for a bf16 `value` (fp32 grad_value
-        # when the backward takes several passes)
-        gv32 = bf16 and _native.backward_passes(Lq, P) > 1
-        bwd = lambda: _native.ms_deform_attn_backward(vd, shapes, lsi, ld, ad, go, 64, fp32_grad_value=gv32, table=table)
-        kt = {}
-        for name, fn in (("fwd", fwd), ("bwd", bwd)):
-            g2 = None
-            try:
-                fn(); stream.synchronize()
-                g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, stream=stream):
-                    for _ in range(10):
-                        fn()
-                call, per = g2.replay, 10
-            except Exception:
-                call, per = fn, 1
-            for _ in range(5):
-                call()
-            kt[name] = event_time_ms(call, max(1, args.kernel_iters // per), stream) / per
-        stream.synchronize()
+        if args.full:
+            vd, ld, ad = value.detach(), loc.detach(), attn.detach()
+            if bf16:
+                ld, ad = ld.float(), ad.float()
+            # (as the autograd step runs them: the forward leaves its point table where the backward's plan reads one)
+            table = _native.ms_deform_attn_forward(vd, shapes, lsi, ld, ad, 64, with_table=True)[1]
+            fwd = lambda: _native.ms_deform_attn_forward(vd, shapes, lsi, ld, ad, 64, with_table=True if table is not None else None)
+            # bf16 rows: the kernel variant MSDeformAttnBF16Function picks for a bf16 `value` (fp32 grad_value
+            # when the backward takes several passes)
+            gv32 = bf16 and _native.backward_passes(Lq, P) > 1
+            bwd = lambda: _native.ms_deform_attn_backward(vd, shapes, lsi, ld, ad, go, 64, fp32_grad_value=gv32, table=table)
+            kt = {}
+            for name, fn in (("fwd", fwd), ("bwd", bwd)):
+                g2 = None
+                try:
+                    fn(); stream.synchronize()
+                    g2 = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g2, stream=stream):
+                        for _ in range(10):
+                            fn()
+                    call, per = g2.replay, 10
+                except Exception:
+                    call, per = fn, 1
+                for _ in range(5):
+                    call()
+                kt[name] = event_time_ms(call, max(1, args.kernel_iters // per), stream) / per
+            stream.synchronize()
 
     total_samples = harness.sum_over_ranks(N * args.steps, device)
     # every block: the slowest rank's time (what the whole job waited for); then the median block
@@ -601,9 +609,6 @@ def main():
         identities[rank]["pci_bus_id"], os.getpid()), file=sys.stderr, flush=True)
 
     if rank == 0:
-        fwd_b, bwd_b = algorithmic_bytes(N, S, M, D, L, Lq, P, e=esize)
-        ach = bwd_b / (kt["bwd"] * 1e-3) / 1e9
-        traffic, traffic_at = pmc_traffic(args.workload + ("_bf16" if bf16 else ""), "bwd")
         result = {
             "metric": METRIC,
             "value": total_samples / elapsed,
@@ -619,10 +624,6 @@ def main():
                        "step": "MSDeformAttnFunction.apply forward + backward (3 grads)",
                        "launch": ("hipGraph replay, %d step(s) per graph" % per_graph) if graph is not None
                                  else "eager autograd",
-                       # the same step launched the way the reference's training loop does (plain autograd calls, no graph)
-                       # and as one graph launch per step: NOT `value`, here so that the launch mode cannot be missed
-                       "eager_ms_per_step": side.get("eager_ms_per_step"),
-                       "graph1_ms_per_step": side.get("graph1_ms_per_step"),
                        "sharding": "batch-sharded, no collective",
                        "timing": "median of %d blocks of %d steps, each bracketed by barrier + synchronize; max over ranks "
                                  "per block (min %.4f / max %.4f ms per step)" % (len(block_max), args.steps,
@@ -630,73 +631,81 @@ def main():
                                                                                   1e3 * block_max[-1] / args.steps),
                        "backend": backend if world > 1 else None},
             "ranks": ranks_seen, "runtime": runtime,
-            "roofline": {"bound": "hbm", "kernel": "backward: msda::bwd_fused_d32_kernel (grad_value sort+gather "
-                                                    "workgroups and grad_loc/grad_attn workgroups in one launch)",
-                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_ratio": (traffic / bwd_b) if traffic else None,
-                         "traffic_profiled_at": traffic_at, "sources_sha16": kernel_sources_sha16(),
-                         "algorithmic_bytes": bwd_b, "ms": kt["bwd"]},
-            "kernels": {"fwd": {"ms": kt["fwd"], "algorithmic_bytes": fwd_b,
-                                "GBps": fwd_b / (kt["fwd"] * 1e-3) / 1e9},
-                        "bwd": {"ms": kt["bwd"], "algorithmic_bytes": bwd_b, "GBps": ach}},
         }
-        result.update(side)
-        # The HBM fraction above is a CACHE-RESIDENT figure: the timed loop replays the same buffers, and the whole working set
-        # (fwd + bwd tensors, ~23 MB at cfg-2) sits in the 8 L2s / the 256 MB Infinity Cache (BASELINE.md says to state this).
-        working_set = fwd_b + bwd_b - esize * (N * S * M * D + N * Lq * M * D) - 4 * 3 * N * Lq * M * L * P   # inputs counted once
-        result["roofline"]["cache_resident"] = True
-        result["roofline"]["forward_table_bytes"] = int(table.numel()) if table is not None else 0   # extra (not algorithmic) traffic: written by the forward, read by the backward
-        result["roofline"]["working_set_bytes"] = working_set
-        if world == 1:
-            result["roofline"]["copy_GBps_measured"] = copy_bandwidth_gbs(device)
-            # second ceiling: on cache-resident data a gather kernel is bound by the ROW REQUESTS the vector memory path serves,
-            # not by HBM bytes.  Measured live (msda_probe_row_gather: the kernels' access pattern and nothing else) on a table
-            # of the size of `value`; achieved = the tap rows the backward has to gather (4 per sampling point for grad_loc /
-            # grad_attn plus 4 per point for grad_value) / its time.
-            try:
-                with torch.cuda.stream(stream):
-                    ceiling = _native.probe_row_gather(esize * N * S * M * D, device, row_bytes=128 if esize == 4 else 64)
-                    stream.synchronize()
-                tap_rows = 2 * 4 * N * Lq * M * L * P
-                ach_rows = tap_rows / (kt["bwd"] * 1e-3)
-                result["roofline"]["secondary"] = {"bound": "tap rows/s (vector memory path, cache-resident table)",
-                                                   "achieved": ach_rows, "ceiling": ceiling, "frac": ach_rows / ceiling,
-                                                   "unit": "rows/s", "rows_per_launch": tap_rows,
-                                                   "ceiling_source": "msda_probe_row_gather on a %d-byte table, same box, same run" % (esize * N * S * M * D)}
-            except Exception as exc:
-                result["roofline"]["secondary"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        if world == 1 and not args.no_table:
-            # the rest of DESIGN.md's performance table, measured in the same run (none of it is `value`)
-            seed = harness.rank_seed(1000, rank)
-            table = [(w, "f32", "uniform", False) for w in WORKLOADS if (w, "f32") != (args.workload, args.dtype)]
-            table += [("cfg2_decoder", "bf16", "uniform", False)] if (args.workload, args.dtype) != ("cfg2_decoder", "bf16") else []
-            # SURVEY 8d distribution B (model-like locations) on the headline shape and the training encoder shape, and the
-            # deterministic flag's cost on every shape
-            table += [("cfg2_decoder", "f32", "model", False), ("cfg4_encoder", "f32", "model", False)]
-            table += [(w, "f32", "uniform", True) for w in WORKLOADS]
-            result["workloads"] = []
-            for w, dt, locs, det in table:
+        if args.full:
+            fwd_b, bwd_b = algorithmic_bytes(N, S, M, D, L, Lq, P, e=esize)
+            ach = bwd_b / (kt["bwd"] * 1e-3) / 1e9
+            traffic, traffic_at = pmc_traffic(args.workload + ("_bf16" if bf16 else ""), "bwd")
+            # the same step launched the way the reference's training loop does (plain autograd calls, no graph)
+            # and as one graph launch per step: NOT `value`, here so that the launch mode cannot be missed
+            result["config"]["eager_ms_per_step"] = side.get("eager_ms_per_step")
+            result["config"]["graph1_ms_per_step"] = side.get("graph1_ms_per_step")
+            result["roofline"] = {"bound": "hbm", "kernel": "backward: msda::bwd_fused_d32_kernel (grad_value sort+gather "
+                                                             "workgroups and grad_loc/grad_attn workgroups in one launch)",
+                                  "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                                  "traffic": traffic, "traffic_ratio": (traffic / bwd_b) if traffic else None,
+                                  "traffic_profiled_at": traffic_at, "sources_sha16": kernel_sources_sha16(),
+                                  "algorithmic_bytes": bwd_b, "ms": kt["bwd"]}
+            result["kernels"] = {"fwd": {"ms": kt["fwd"], "algorithmic_bytes": fwd_b,
+                                         "GBps": fwd_b / (kt["fwd"] * 1e-3) / 1e9},
+                                 "bwd": {"ms": kt["bwd"], "algorithmic_bytes": bwd_b, "GBps": ach}}
+            result.update(side)
+            # The HBM fraction above is a CACHE-RESIDENT figure: the timed loop replays the same buffers, and the whole working set
+            # (fwd + bwd tensors, ~23 MB at cfg-2) sits in the 8 L2s / the 256 MB Infinity Cache (BASELINE.md says to state this).
+            working_set = fwd_b + bwd_b - esize * (N * S * M * D + N * Lq * M * D) - 4 * 3 * N * Lq * M * L * P   # inputs counted once
+            result["roofline"]["cache_resident"] = True
+            result["roofline"]["forward_table_bytes"] = int(table.numel()) if table is not None else 0   # extra (not algorithmic) traffic: written by the forward, read by the backward
+            result["roofline"]["working_set_bytes"] = working_set
+            if world == 1:
+                result["roofline"]["copy_GBps_measured"] = copy_bandwidth_gbs(device)
+                # second ceiling: on cache-resident data a gather kernel is bound by the ROW REQUESTS the vector memory path serves,
+                # not by HBM bytes.  Measured live (msda_probe_row_gather: the kernels' access pattern and nothing else) on a table
+                # of the size of `value`; achieved = the tap rows the backward has to gather (4 per sampling point for grad_loc /
+                # grad_attn plus 4 per point for grad_value) / its time.
                 try:
-                    result["workloads"].append(measure_op(w, dt, device, stream, seed, locs, 0.4 if (det or locs != "uniform") else 0.6, det))
-                except Exception as exc:                  # a row that cannot be measured says so; the headline stands
-                    result["workloads"].append({"workload": w, "dtype": dt, "locations": locs, "deterministic": det,
-                                                "error": "%s: %s" % (type(exc).__name__, exc)})
-                torch.cuda.empty_cache()
-            result["modules"] = []
-            for w, amp in (("cfg2_decoder", False), ("cfg4_encoder", False), ("cfg2_decoder", True), ("cfg4_encoder", True)):
-                try:
-                    result["modules"].append(measure_module(w, device, stream, amp))
+                    with torch.cuda.stream(stream):
+                        ceiling = _native.probe_row_gather(esize * N * S * M * D, device, row_bytes=128 if esize == 4 else 64)
+                        stream.synchronize()
+                    tap_rows = 2 * 4 * N * Lq * M * L * P
+                    ach_rows = tap_rows / (kt["bwd"] * 1e-3)
+                    result["roofline"]["secondary"] = {"bound": "tap rows/s (vector memory path, cache-resident table)",
+                                                       "achieved": ach_rows, "ceiling": ceiling, "frac": ach_rows / ceiling,
+                                                       "unit": "rows/s", "rows_per_launch": tap_rows,
+                                                       "ceiling_source": "msda_probe_row_gather on a %d-byte table, same box, same run" % (esize * N * S * M * D)}
                 except Exception as exc:
-                    result["modules"].append({"workload": w, "amp": amp, "error": "%s: %s" % (type(exc).__name__, exc)})
+                    result["roofline"]["secondary"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+            if world == 1 and not args.no_table:
+                # the rest of DESIGN.md's performance table, measured in the same run (none of it is `value`)
+                seed = harness.rank_seed(1000, rank)
+                table = [(w, "f32", "uniform", False) for w in WORKLOADS if (w, "f32") != (args.workload, args.dtype)]
+                table += [("cfg2_decoder", "bf16", "uniform", False)] if (args.workload, args.dtype) != ("cfg2_decoder", "bf16") else []
+                # SURVEY 8d distribution B (model-like locations) on the headline shape and the training encoder shape, and the
+                # deterministic flag's cost on every shape
+                table += [("cfg2_decoder", "f32", "model", False), ("cfg4_encoder", "f32", "model", False)]
+                table += [(w, "f32", "uniform", True) for w in WORKLOADS]
+                result["workloads"] = []
+                for w, dt, locs, det in table:
+                    try:
+                        result["workloads"].append(measure_op(w, dt, device, stream, seed, locs, 0.4 if (det or locs != "uniform") else 0.6, det))
+                    except Exception as exc:                  # a row that cannot be measured says so; the headline stands
+                        result["workloads"].append({"workload": w, "dtype": dt, "locations": locs, "deterministic": det,
+                                                    "error": "%s: %s" % (type(exc).__name__, exc)})
+                    torch.cuda.empty_cache()
+                result["modules"] = []
+                for w, amp in (("cfg2_decoder", False), ("cfg4_encoder", False), ("cfg2_decoder", True), ("cfg4_encoder", True)):
+                    try:
+                        result["modules"].append(measure_module(w, device, stream, amp))
+                    except Exception as exc:
+                        result["modules"].append({"workload": w, "amp": amp, "error": "%s: %s" % (type(exc).__name__, exc)})
+                    torch.cuda.empty_cache()
+                try:
+                    result["layers"] = [measure_attention(device, stream)]
+                except Exception as exc:
+                    result["layers"] = [{"what": "decoder self-attention core", "error": "%s: %s" % (type(exc).__name__, exc)}]
                 torch.cuda.empty_cache()
-            try:
-                result["layers"] = [measure_attention(device, stream)]
-            except Exception as exc:
-                result["layers"] = [{"what": "decoder self-attention core", "error": "%s: %s" % (type(exc).__name__, exc)}]
-            torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = time_cpu_baseline(args.workload)
-            result["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = time_cpu_baseline(args.workload)
+                result["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

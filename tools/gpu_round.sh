@@ -1,15 +1,17 @@
 #!/bin/bash
-# Runs ON THE GPU BOX from the repo root: the GPU suite, then the bench line (headline + table) and the four workloads' kernel times.
-mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_gpu.log 2>&1
-echo "pytest exit $?" >> gpurun_out/pytest_gpu.log
-tail -4 gpurun_out/pytest_gpu.log
-timeout -k 10 400 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
+# Runs ON THE GPU BOX from the repo root: the GPU suite, then the full bench line (headline + table) and the four workloads'
+# kernel times, written under OUT_DIR.
+OUT=${1:?usage: tools/gpu_round.sh OUT_DIR}
+mkdir -p "$OUT"
+timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.log" 2>&1
+echo "pytest exit $?" >> "$OUT/pytest_gpu.log"
+tail -4 "$OUT/pytest_gpu.log"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "bench exit $?"
-python - <<'PY'
-import json
+python - "$OUT/bench_default.json" <<'PY'
+import json, sys
 try:
-    r = json.loads([l for l in open("gpurun_out/bench_default.json") if l.startswith("{")][-1])
+    r = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 except Exception as e:
     print("bench line unreadable:", e); raise SystemExit(0)
 print("headline %.0f samples/s  %.4f ms/step  fwd %.2f us  bwd %.2f us  frac %.3f  eager %.1f us  cpu %s" % (

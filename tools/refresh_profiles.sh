@@ -5,11 +5,11 @@ set -u
 OUT=gpurun_out/bench
 mkdir -p $OUT
 for w in cfg2_decoder cfg2_encoder cfg4_decoder cfg4_encoder; do
-  timeout -k 10 300 python bench.py --workload $w > $OUT/${w}.json 2> $OUT/${w}.err && echo "$w done"
-  timeout -k 10 300 python bench.py --workload $w --locations model --no-cpu-baseline > $OUT/${w}_model_locations.json 2>> $OUT/${w}.err && echo "$w model done"
+  timeout -k 10 300 python bench.py --full --workload $w > $OUT/${w}.json 2> $OUT/${w}.err && echo "$w done"
+  timeout -k 10 300 python bench.py --full --workload $w --locations model --no-cpu-baseline > $OUT/${w}_model_locations.json 2>> $OUT/${w}.err && echo "$w model done"
 done
-timeout -k 10 300 python bench.py --dtype bf16 --no-cpu-baseline > $OUT/cfg2_decoder_bf16.json 2>> $OUT/cfg2_decoder.err
-timeout -k 10 300 python bench.py --graph-steps 1 --no-cpu-baseline > $OUT/cfg2_decoder_graph1.json 2>> $OUT/cfg2_decoder.err
+timeout -k 10 300 python bench.py --full --dtype bf16 --no-cpu-baseline > $OUT/cfg2_decoder_bf16.json 2>> $OUT/cfg2_decoder.err
+timeout -k 10 300 python bench.py --full --graph-steps 1 --no-cpu-baseline > $OUT/cfg2_decoder_graph1.json 2>> $OUT/cfg2_decoder.err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/bench/*.json")):

@@ -690,6 +690,36 @@ int msda_swin_attn_backward_f32(int B, int H, int W, int C, int nH, int ws, int 
                                 const float *grad_out, float *grad_qkv, float *grad_table, float *grad_qkv_bias, void *workspace,
                                 unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- MANO hand layer (smplx MANO with use_pca=False: lbs = Rodrigues, shape and pose blend shapes, kinematic chain, linear
+ * blend skinning) over several groups of hands -------------------------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * V vertices (1 <= V <= 8192), 16 joints, n_betas shape coefficients (1 .. 16), n_extra extra joints (0 .. 8: vertex ids).
+ * n_layers <= 4 models; layer_tensors: HOST array of 7 pointers per layer, fp32 contiguous: v_template [V, 3], shapedirs
+ * [V, 3, n_betas], posedirs [135, 3 V] (smplx's layout), J_template [16, 3] = J_regressor . v_template, J_shapedirs
+ * [16, 3, n_betas] = J_regressor . shapedirs, lbs_weights [V, 16], pose_mean [48].  layer_index: HOST ints, 16 + n_extra per
+ * layer: parents (parents[0] = -1, 0 <= parents[j] < j), then the extra-joint vertex ids.
+ * n_groups <= 16 groups; group i runs layer group_layer[i] over group_B[i] >= 0 hands; group_bcast (may be NULL): nonzero = one
+ * betas row for every hand.  inputs: HOST array of 4 per group: betas [B or 1, n_betas], global_orient [B, 3], hand_pose
+ * [B, 45], transl [B, 3] (NULL: none).  outputs: 2 per group: vertices [B, V, 3], joints [B, 16 + n_extra, 3] (the posed
+ * joints, then the extra vertices; transl added to both).
+ *   msda_mano_workspace_bytes  the backward workspace; 0 for an unsupported geometry.
+ *   msda_mano_forward_f32      one launch.
+ *   msda_mano_backward_f32     two launches.  grad_outputs: 2 per group, g_vertices and g_joints, either may be NULL (zero).
+ *       grads: 4 per group: g_betas [B, n_betas] per hand (the caller sums them for a broadcast betas row), g_global_orient
+ *       [B, 3], g_hand_pose [B, 45], g_transl [B, 3] (NULL: not wanted).  No gradient of the model tensors.
+ * Fixed summation order, no atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any
+ * launch. */
+int msda_mano_supported(int V, int n_betas, int n_extra);
+unsigned long long msda_mano_workspace_bytes(int V, int n_betas, int n_extra, int n_groups, const int *group_B);
+int msda_mano_forward_f32(int V, int n_betas, int n_extra, int n_layers, const float *const *layer_tensors, const int *layer_index,
+                          int n_groups, const int *group_layer, const int *group_B, const int *group_bcast,
+                          const float *const *inputs, float *const *outputs, msda_stream_t stream);
+int msda_mano_backward_f32(int V, int n_betas, int n_extra, int n_layers, const float *const *layer_tensors, const int *layer_index,
+                           int n_groups, const int *group_layer, const int *group_B, const int *group_bcast,
+                           const float *const *inputs, const float *const *grad_outputs, float *const *grads, void *workspace,
+                           unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

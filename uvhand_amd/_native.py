@@ -47,6 +47,7 @@ _SYMBOLS = (
     "msda_smoother_supported", "msda_smoother_workspace_bytes", "msda_smoother_forward_f32", "msda_smoother_backward_f32",
     "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32", "msda_arctic_item_backward_f32",
     "msda_swin_attn_supported", "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_f32", "msda_swin_attn_backward_f32",
+    "msda_mano_supported", "msda_mano_workspace_bytes", "msda_mano_forward_f32", "msda_mano_backward_f32",
 )
 
 
@@ -1563,3 +1564,84 @@ def swin_attn_backward(geo, qkv, bias, table, out, lse, grad_out):
     if rc != 0:
         _raise(lib, rc, "swin_attn_backward")
     return gq, gt, gb
+
+
+# ---- MANO hand layer: grouped lbs (msda_mano.hip) -----------------------------------------------------------------------------
+MANO_MAX_LAYERS, MANO_MAX_GROUPS, MANO_MAX_EXTRA, MANO_MAX_BETAS, MANO_MAX_VERTS = 4, 16, 8, 16, 8192
+_MANO_GEO = [_CI] * 4 + [_VP, _VP, _CI, _VP, _VP, _VP]
+
+
+def mano_supported(V, n_betas, n_extra):
+    """msda_mano_supported (include/msda.h): 1 when the MANO kernels take this model size."""
+    lib = _lib or load()
+    fn = _entry(lib, "msda_mano_supported", [_CI] * 3)
+    return bool(fn(int(V), int(n_betas), int(n_extra)))
+
+
+def _mano_geo(dims, layers, group_layer, group_B, group_bcast):
+    """dims (V, n_betas, n_extra); layers: per layer (seven fp32 tensors in msda.h's order, parents + extra ids as ints)."""
+    V, nb, E = dims
+    tensors = [t for lay in layers for t in lay[0]]
+    index = [int(i) for lay in layers for i in lay[1]]
+    return [int(V), int(nb), int(E), len(layers), _ptr_array(tensors), _int_array(index), len(group_B), _int_array(group_layer),
+            _int_array(group_B), _int_array(group_bcast)]
+
+
+def _mano_check(what, dev, tensors):
+    if not all(t is None or (_f32_cuda(t) and t.device == dev) for t in tensors):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+
+
+def mano_workspace_bytes(dims, group_B):
+    lib = _lib or load()
+    fn = _entry(lib, "msda_mano_workspace_bytes", [_CI] * 4 + [_VP])
+    fn.restype = ctypes.c_ulonglong
+    return int(fn(int(dims[0]), int(dims[1]), int(dims[2]), len(group_B), _int_array(group_B)))
+
+
+def mano_forward(dims, layers, group_layer, group_bcast, inputs):
+    """msda_mano_forward_f32.  inputs: per group (betas, global_orient, hand_pose, transl or None).  Returns per group
+    (vertices [B, V, 3], joints [B, 16 + E, 3]).  One launch, no host sync."""
+    lib = _lib or load()
+    V, _, E = dims
+    dev = inputs[0][1].device
+    _mano_check("mano_forward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp])
+    group_B = [grp[1].shape[0] for grp in inputs]
+    geo = _mano_geo(dims, layers, group_layer, group_B, group_bcast)
+    with _DeviceGuard(dev):
+        outs = [(torch.empty(b, V, 3, dtype=torch.float32, device=dev), torch.empty(b, 16 + E, 3, dtype=torch.float32, device=dev))
+                for b in group_B]
+        ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
+        o = (_VP * (2 * len(outs)))(*[t.data_ptr() for pair in outs for t in pair])
+        rc = _entry(lib, "msda_mano_forward_f32", _MANO_GEO + [_VP, _VP, _VP])(*geo, ins, o, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "mano_forward")
+    return outs
+
+
+def mano_backward(dims, layers, group_layer, group_bcast, inputs, grad_outputs):
+    """msda_mano_backward_f32.  grad_outputs: per group (g_vertices, g_joints), either None.  Returns per group (g_betas per
+    hand [B, n_betas], g_global_orient [B, 3], g_hand_pose [B, 45], g_transl [B, 3] or None without transl).  Two launches,
+    no host sync."""
+    lib = _lib or load()
+    _, nb, _ = dims
+    dev = inputs[0][1].device
+    _mano_check("mano_backward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp]
+                + [t for grp in grad_outputs for t in grp])
+    group_B = [grp[1].shape[0] for grp in inputs]
+    geo = _mano_geo(dims, layers, group_layer, group_B, group_bcast)
+    with _DeviceGuard(dev):
+        nbytes = mano_workspace_bytes(dims, group_B)
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        grads = [(torch.empty(b, nb, dtype=torch.float32, device=dev), torch.empty(b, 3, dtype=torch.float32, device=dev),
+                  torch.empty(b, 45, dtype=torch.float32, device=dev),
+                  torch.empty(b, 3, dtype=torch.float32, device=dev) if grp[3] is not None else None)
+                 for b, grp in zip(group_B, inputs)]
+        ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
+        gos = (_VP * (2 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
+        gs = (_VP * (4 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
+        rc = _entry(lib, "msda_mano_backward_f32", _MANO_GEO + [_VP, _VP, _VP, _VP, ctypes.c_ulonglong, _VP])(
+            *geo, ins, gos, gs, ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "mano_backward")
+    return grads

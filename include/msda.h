@@ -720,6 +720,49 @@ int msda_mano_backward_f32(int V, int n_betas, int n_extra, int n_layers, const 
                            const float *const *inputs, const float *const *grad_outputs, float *const *grads, void *workspace,
                            unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- ARCTIC object layer and small losses (csrc/msda_small_loss.hip) ------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Object layer (arctic_tools ObjectTensors.forward_7d_batch).  dims: HOST ints {n_objects (1 .. 64), Lm padded template rows
+ * (1 .. 65536), NS sub-vertices (0 .. 4096), NBt, NBb bbox corners (sum <= 64), NKt, NKb keypoints (sum <= 256)}.  model: HOST
+ * array of 8 device pointers: v [N, Lm, 3] f32, parts_ids [N, Lm] int64, v_sub [N, NS, 3] f32, parts_sub_ids [N, NS] int64,
+ * bbox_top [N, NBt, 3], bbox_bottom [N, NBb, 3], kp_top [N, NKt, 3], kp_bottom [N, NKb, 3] (f32; metres).  n_groups <= 16;
+ * group i has group_B[i] >= 0 frames and group_len[i] (1 .. Lm) output template rows.  inputs: 4 per group: obj_idx [B] int64,
+ * angles [B], global_orient [B, 3], transl [B, 3] (NULL: none).  outputs: 4 per group: v [B, len, 3], v_sub [B, NS, 3], bbox3d
+ * [B, NBt + NBb, 3], kp3d [B, NKt + NKb, 3] (top rows first).  An obj_idx outside 0 .. N - 1 gives NaN rows.
+ *   msda_object_forward_f32   one launch.
+ *   msda_object_backward_f32  one launch.  grad_outputs: 4 per group (NULL: zero); grads: 3 per group: g_angles [B],
+ *       g_global_orient [B, 3], g_transl [B, 3] (each NULL: not wanted).
+ *
+ * Small losses (compute_small_loss) of S sets (1 .. 8) over B frames.  dims: HOST ints {S, B, J hand joints (1 .. 32), NV hand
+ * vertices (1 .. 1024), KO object keypoints (even, 2 .. 64), NB betas (1 .. 16), L object rows (1 .. 65536)}.  targets: HOST
+ * array of 25 device pointers, fp32 contiguous unless noted: mano.pose.l [B, 48], mano.pose.r, mano.beta.l [B, NB],
+ * mano.beta.r, mano.j3d.cam.l [B, J, 3], mano.j3d.cam.r, object.kp3d.cam [B, KO, 3], mano.j2d.norm.l [B, J, 2], mano.j2d.norm.r,
+ * object kp2d (norm.t then norm.b) [B, KO, 2], object.rot [B, 3], object.radian [B], mano.cam_t.wp.l [B, 3], mano.cam_t.wp.r,
+ * object.cam_t.wp, is_valid [B], left_valid [B], right_valid [B], joints_valid_l [B, J], joints_valid_r, dist.ro [B, NV],
+ * dist.lo, intrinsics [B, 3, 3], idx.ro [B, NV] int64, idx.lo.  inputs: HOST array of 15 per set: root_l, root_r, root_o
+ * [B, 3], pose_l, pose_r [B, 48], betas_l, betas_r [B, NB], rot [B, 3], radian [B], MANO vertices l, r [B, NV, 3] and joints
+ * l, r [B, J, 3] (no camera translation), object v [B, L, 3] and kp3d [B, KO, 3].  losses: [S, 19] in compute_small_loss's
+ * key order.
+ *   msda_small_loss_workspace_bytes  the forward's workspace, which the backward reads; 0 for an unsupported geometry.
+ *   msda_small_loss_forward_f32      two launches (none for B = 0: the losses are then left unwritten).
+ *   msda_small_loss_backward_f32     one launch.  grad_losses [S, 19]; grads: 15 per set, shaped as the inputs.
+ * Fixed summation order, no atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any
+ * launch. */
+int msda_object_supported(int n_objects, int max_len, int n_sub, int n_bbox_top, int n_bbox_bottom, int n_kp_top, int n_kp_bottom);
+int msda_object_forward_f32(const int *dims, const void *const *model, int n_groups, const int *group_B, const int *group_len,
+                            const void *const *inputs, float *const *outputs, msda_stream_t stream);
+int msda_object_backward_f32(const int *dims, const void *const *model, int n_groups, const int *group_B, const int *group_len,
+                             const void *const *inputs, const float *const *grad_outputs, float *const *grads,
+                             msda_stream_t stream);
+int msda_small_loss_supported(int S, int B, int J, int NV, int KO, int NB, int L);
+unsigned long long msda_small_loss_workspace_bytes(int S, int B, int J, int NV, int KO, int NB, int L);
+int msda_small_loss_forward_f32(const int *dims, float img_res, const void *const *targets, const float *const *inputs,
+                                float *losses, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+int msda_small_loss_backward_f32(const int *dims, float img_res, const void *const *targets, const float *const *inputs,
+                                 const float *grad_losses, float *const *grads, const void *workspace,
+                                 unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -48,6 +48,8 @@ _SYMBOLS = (
     "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32", "msda_arctic_item_backward_f32",
     "msda_swin_attn_supported", "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_f32", "msda_swin_attn_backward_f32",
     "msda_mano_supported", "msda_mano_workspace_bytes", "msda_mano_forward_f32", "msda_mano_backward_f32",
+    "msda_object_supported", "msda_object_forward_f32", "msda_object_backward_f32", "msda_small_loss_supported",
+    "msda_small_loss_workspace_bytes", "msda_small_loss_forward_f32", "msda_small_loss_backward_f32",
 )
 
 
@@ -1644,4 +1646,126 @@ def mano_backward(dims, layers, group_layer, group_bcast, inputs, grad_outputs):
             *geo, ins, gos, gs, ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
     if rc != 0:
         _raise(lib, rc, "mano_backward")
+    return grads
+
+
+# ---- ARCTIC object layer and small losses (msda_small_loss.hip) ---------------------------------------------------------------
+OBJECT_MAX_GROUPS, SMALL_LOSS_MAX_SETS = 16, 8
+SMALL_LOSS_TERMS, SMALL_LOSS_INPUTS, SMALL_LOSS_TARGETS = 19, 15, 25
+_OBJ_ARGS = [_VP, _VP, _CI, _VP, _VP, _VP]
+
+
+def object_supported(n_objects, max_len, n_sub, n_bbox_top, n_bbox_bottom, n_kp_top, n_kp_bottom):
+    """msda_object_supported (include/msda.h): 1 when the object kernels take this model size."""
+    lib = _lib or load()
+    fn = _entry(lib, "msda_object_supported", [_CI] * 7)
+    return bool(fn(int(n_objects), int(max_len), int(n_sub), int(n_bbox_top), int(n_bbox_bottom), int(n_kp_top),
+                   int(n_kp_bottom)))
+
+
+def _obj_geo(dims, model, inputs, lens):
+    """dims (n_objects, Lm, NS, NBt, NBb, NKt, NKb); model: the 8 model tensors of msda.h; inputs: per group (obj_idx,
+    angles, global_orient, transl or None); lens: per group output template rows."""
+    group_B = [grp[0].shape[0] for grp in inputs]
+    return [_int_array(dims), _ptr_array(model), len(inputs), _int_array(group_B), _int_array(lens),
+            (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])], group_B
+
+
+def _obj_check(what, dev, model, tensors):
+    ok = all(t.is_cuda and t.device == dev and t.is_contiguous() for t in model + [t for t in tensors if t is not None])
+    if not ok or any(t is not None and t.dtype not in (torch.float32, torch.int64) for t in tensors):
+        raise RuntimeError("%s: expected contiguous CUDA tensors on one device" % what)
+
+
+def object_forward(dims, model, inputs, lens):
+    """msda_object_forward_f32.  Returns per group (v [B, len, 3], v_sub [B, NS, 3], bbox3d [B, NBt + NBb, 3], kp3d
+    [B, NKt + NKb, 3]).  One launch, no host sync."""
+    lib = _lib or load()
+    dev = inputs[0][1].device
+    _obj_check("object_forward", dev, list(model), [t for grp in inputs for t in grp])
+    geo, group_B = _obj_geo(dims, model, inputs, lens)
+    _, _, NS, NBt, NBb, NKt, NKb = dims
+    with _DeviceGuard(dev):
+        e = dict(dtype=torch.float32, device=dev)
+        outs = [(torch.empty(b, n, 3, **e), torch.empty(b, NS, 3, **e), torch.empty(b, NBt + NBb, 3, **e),
+                 torch.empty(b, NKt + NKb, 3, **e)) for b, n in zip(group_B, lens)]
+        o = (_VP * (4 * len(outs)))(*[t.data_ptr() for grp in outs for t in grp])
+        rc = _entry(lib, "msda_object_forward_f32", _OBJ_ARGS + [_VP, _VP])(*geo, o, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "object_forward")
+    return outs
+
+
+def object_backward(dims, model, inputs, lens, grad_outputs, want_transl):
+    """msda_object_backward_f32.  grad_outputs: per group 4 tensors or None.  Returns per group (g_angles [B], g_global_orient
+    [B, 3], g_transl [B, 3] or None).  One launch, no host sync."""
+    lib = _lib or load()
+    dev = inputs[0][1].device
+    _obj_check("object_backward", dev, list(model), [t for grp in inputs for t in grp] + [t for grp in grad_outputs for t in grp])
+    geo, group_B = _obj_geo(dims, model, inputs, lens)
+    with _DeviceGuard(dev):
+        e = dict(dtype=torch.float32, device=dev)
+        grads = [(torch.empty(b, **e), torch.empty(b, 3, **e), torch.empty(b, 3, **e) if w else None)
+                 for b, w in zip(group_B, want_transl)]
+        gos = (_VP * (4 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
+        gs = (_VP * (3 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
+        rc = _entry(lib, "msda_object_backward_f32", _OBJ_ARGS + [_VP, _VP, _VP])(*geo, gos, gs, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "object_backward")
+    return grads
+
+
+def small_loss_supported(S, B, J, NV, KO, NB, L):
+    lib = _lib or load()
+    return bool(_entry(lib, "msda_small_loss_supported", [_CI] * 7)(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
+
+
+def small_loss_workspace_bytes(S, B, J, NV, KO, NB, L):
+    lib = _lib or load()
+    fn = _entry(lib, "msda_small_loss_workspace_bytes", [_CI] * 7)
+    fn.restype = ctypes.c_ulonglong
+    return int(fn(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
+
+
+_SL_ARGS = [_VP, ctypes.c_float, _VP, _VP]
+
+
+def _sl_check(what, dev, tensors):
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() and t.dtype in (torch.float32, torch.int64) for t in tensors):
+        raise RuntimeError("%s: expected contiguous CUDA tensors on one device" % what)
+
+
+def small_loss_forward(dims, img_res, targets, inputs):
+    """msda_small_loss_forward_f32.  targets: the 25 tensors of msda.h; inputs: per set 15 tensors.  Returns (losses [S, 19],
+    workspace for the backward).  Two launches, no host sync."""
+    lib = _lib or load()
+    dev = inputs[0][0].device
+    _sl_check("small_loss_forward", dev, list(targets) + [t for grp in inputs for t in grp])
+    with _DeviceGuard(dev):
+        losses = torch.empty(dims[0], SMALL_LOSS_TERMS, dtype=torch.float32, device=dev)
+        nbytes = small_loss_workspace_bytes(*dims)
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+        ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
+        rc = _entry(lib, "msda_small_loss_forward_f32", _SL_ARGS + [_VP, _VP, ctypes.c_ulonglong, _VP])(
+            _int_array(dims), float(img_res), _ptr_array(targets), ins, losses.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+            _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "small_loss_forward")
+    return losses, ws
+
+
+def small_loss_backward(dims, img_res, targets, inputs, grad_losses, ws):
+    """msda_small_loss_backward_f32.  Returns per set the 15 input gradients, shaped as the inputs.  One launch."""
+    lib = _lib or load()
+    dev = inputs[0][0].device
+    _sl_check("small_loss_backward", dev, list(targets) + [t for grp in inputs for t in grp] + [grad_losses, ws])
+    with _DeviceGuard(dev):
+        grads = [[torch.empty_like(t) for t in grp] for grp in inputs]
+        ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
+        gs = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in grads for t in grp])
+        rc = _entry(lib, "msda_small_loss_backward_f32", _SL_ARGS + [_VP, _VP, _VP, ctypes.c_ulonglong, _VP])(
+            _int_array(dims), float(img_res), _ptr_array(targets), ins, grad_losses.data_ptr(), gs, ws.data_ptr(),
+            ws.numel() * 4, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, "small_loss_backward")
     return grads

@@ -13,7 +13,7 @@ again backward.  Here:
     dict keys.  A step is one ``match`` over all sets, one loss launch, ``num_boxes`` from host lengths (``all_reduce``d
     and clamped on the device under torch.distributed); the values are 0-d device views.  The AssemblyHands forward makes
     no host sync; the ARCTIC one makes none besides the MANO / ARCTIC small losses, which stay the reference's code
-    (``small_loss``).
+    (``small_loss``) unless ``small_loss`` is a ``small_loss.ArcticSmallLoss``, whose ``many`` covers every set sync-free.
 
 Reference behaviour kept: slot k of a set pairs output frame k with the k-th VALID frame's targets (ARCTIC, as the matcher);
 AssemblyHands' ``joint_valid`` rows go with matched rows in query order (row r of a frame's matched block uses the frame's
@@ -325,6 +325,14 @@ class SetArcticCriterion(nn.Module):
             self.small_loss = reference_small_loss
         return self.small_loss(outputs, targets, meta_info, args, suffix)
 
+    def _small_many(self, final, aux, targets, meta_info, args):
+        """Every set's small-loss dict from one ``small_loss.many(...)`` call (``ArcticSmallLoss``), or None when the
+        ``small_loss`` has no callable ``many`` (the per-set calls then run as before)."""
+        many = getattr(self.small_loss, "many", None)
+        if not callable(many):
+            return None
+        return many([final] + aux, targets, meta_info, args, [""] + [f"_{i}" for i in range(len(aux))])
+
     @staticmethod
     def _sets(outputs):
         final = {k: v for k, v in outputs.items() if k not in ("aux_outputs", "interm_outputs")}
@@ -357,10 +365,11 @@ class SetArcticCriterion(nn.Module):
         col = {name: c for c, name in enumerate(ARCTIC_TERMS)}
         keys = _arctic_keys(self.losses)
         losses = {k: L[0, col[k]] for k in keys}
-        losses.update(self._small(final, targets, meta_info, args, ""))
+        small = self._small_many(final, aux, targets, meta_info, args)
+        losses.update(small[0] if small else self._small(final, targets, meta_info, args, ""))
         for i, a in enumerate(aux):
             losses.update({k + f"_{i}": L[1 + i, col[k]] for k in keys})
-            losses.update(self._small(a, targets, meta_info, args, f"_{i}"))
+            losses.update(small[1 + i] if small else self._small(a, targets, meta_info, args, f"_{i}"))
         if interm is not None:
             losses.update({k + "_interm": L[len(sets) - 1, col[k]] for k in keys})
         return losses
@@ -371,11 +380,12 @@ class SetArcticCriterion(nn.Module):
         kw = dict(losses=self.losses, num_classes=self.num_classes, focal_alpha=self.focal_alpha)
         nb = _num_boxes_host(sum(len(t) for t in targets["labels"]), final["pred_logits"].device)
         losses = dict(arctic_set_losses(final, targets, self.matcher(final, targets), nb, **kw))
-        losses.update(self._small(final, targets, meta_info, args, ""))
+        small = self._small_many(final, aux, targets, meta_info, args)
+        losses.update(small[0] if small else self._small(final, targets, meta_info, args, ""))
         for i, a in enumerate(aux):
             losses.update({k + f"_{i}": v for k, v in arctic_set_losses(a, targets, self.matcher(a, targets), nb,
                                                                           **kw).items()})
-            losses.update(self._small(a, targets, meta_info, args, f"_{i}"))
+            losses.update(small[1 + i] if small else self._small(a, targets, meta_info, args, f"_{i}"))
         if interm is not None:
             losses.update({k + "_interm": v for k, v in arctic_set_losses(interm, targets, self.matcher(interm, targets),
                                                                            nb, **kw).items()})

@@ -12,10 +12,41 @@ import torch
 from conftest import ROOT, load_golden
 
 
-def _declared_functions():
+def _header_text():
     text = open(os.path.join(ROOT, "include", "msda.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(msda_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _declared_functions():
+    return sorted(set(re.findall(r"\b(msda_[a-z0-9_]+)\s*\(", _header_text())))
+
+
+_C_SCALARS = {"void": None, "int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong,
+              "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float, "double": ctypes.c_double,
+              "int64_t": ctypes.c_longlong}
+
+
+def _c_type(text):
+    """A return or parameter type of msda.h: the ctypes scalar it must be bound as, "pointer" for every pointer type and
+    msda_stream_t, None for void.  A type this table does not know is a KeyError."""
+    text = " ".join(re.sub(r"\bconst\b", " ", text).split())
+    return "pointer" if "*" in text or text == "msda_stream_t" else _C_SCALARS[text]
+
+
+def _header_signatures():
+    """{name: (return type, [parameter types])} of every declaration of include/msda.h, types as _c_type gives them."""
+    text = re.sub(r"^\s*#.*$", "", _header_text(), flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(msda_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_c_type(ret), [_c_type(re.sub(r"\w+\s*$", "", p.strip())) for p in params])    # drop the parameter's name
+    return out
+
+
+def _bound_as(ctype):
+    """A ctypes type of the binding's table in _c_type's terms."""
+    pointer = ctype in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+    return "pointer" if pointer else ctype
 
 
 @pytest.fixture(scope="module")
@@ -34,13 +65,29 @@ def test_header_declares_the_expected_entry_points():
         assert must in names
 
 
+def test_signature_table_equals_the_header():
+    """uvhand_amd/_native.py declares every C function once, in SIGNATURES; this is the check that the table says what
+    include/msda.h says: the same names, and per function the same return type, argument count and type at every position
+    (scalars exactly, int64_t as long long; every pointer and msda_stream_t as a pointer).  No library, no GPU."""
+    from uvhand_amd import _native
+    header = _header_signatures()
+    assert sorted(header) == _declared_functions()                    # the parser saw every declaration
+    assert sorted(set(header) - set(_native.SIGNATURES)) == [], "declared in msda.h, missing from _native.SIGNATURES"
+    assert sorted(set(_native.SIGNATURES) - set(header)) == [], "in _native.SIGNATURES, not declared in msda.h"
+    for name, (ret, params) in header.items():
+        restype, argtypes = _native.signature(name)
+        assert _bound_as(restype) == ret, "%s: returns %s in msda.h, %s in the table" % (name, ret, restype)
+        assert len(argtypes) == len(params), "%s: %d parameters in msda.h, %d in the table" % (name, len(params), len(argtypes))
+        for i, (got, want) in enumerate(zip(argtypes, params)):
+            assert _bound_as(got) == want, "%s: parameter %d is %s in msda.h, %s in the table" % (name, i, want, got)
+
+
 def test_library_exports_every_declared_symbol(native):
     lib = ctypes.CDLL(native.LIB_PATH)
     for name in _declared_functions():
         assert hasattr(lib, name), "libmsda_hip.so does not export %s" % name
-    lib.msda_version.restype = ctypes.c_int
+    native.declare(lib)
     assert lib.msda_version() >= 100
-    lib.msda_last_error.restype = ctypes.c_char_p
     assert lib.msda_last_error() == b""
 
 
@@ -210,35 +257,26 @@ def test_torch_extension_loads_and_matches_the_library(native):
 
 def test_argument_errors_are_reported_before_anything_is_launched(native):
     """Bad sizes / null pointers come back as MSDA_ERR_ARGUMENT with a message — no GPU needed, nothing is enqueued."""
-    lib = ctypes.CDLL(native.LIB_PATH)
-    lib.msda_last_error.restype = ctypes.c_char_p
-    V, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    lib = native.declare(ctypes.CDLL(native.LIB_PATH))
+    I = ctypes.c_int
     # residual add + LayerNorm: row width must be a multiple of 4, at most 1024
     fn = lib.msda_add_layernorm_forward_f32
-    fn.argtypes = [V, V, V, V, LL, I, ctypes.c_float, V, V, V, V]
-    fn.restype = I
     assert fn(None, None, None, None, 4, 6, 1e-5, None, None, None, None) == 1
     assert b"multiple of 4" in lib.msda_last_error()
     assert fn(None, None, None, None, 4, 2048, 1e-5, None, None, None, None) == 1
     assert fn(None, None, None, None, 4, 256, 1e-5, None, None, None, None) == 1        # null pointers with rows > 0
     # the op with flags / scratch: null tensors with a non-empty problem
     fn = lib.msda_backward_ws_f32
-    fn.argtypes = [V] * 6 + [I] * 7 + [V] * 4 + [ctypes.c_ulonglong, ctypes.c_uint, V]
-    fn.restype = I
     assert fn(None, None, None, None, None, None, 1, 4, 8, 32, 1, 2, 4, None, None, None, None, 0, 1, None) == 1
     assert b"null device pointer" in lib.msda_last_error()
     assert fn(None, None, None, None, None, None, 1, 4, 0, 32, 1, 2, 4, None, None, None, None, 0, 1, None) == 1   # M = 0
     # pyramid flatten: level count and channel width
     fn = lib.msda_flatten_levels_f32
-    fn.argtypes = [I, V, V, V, V, V, I, I, V, V, V]
-    fn.restype = I
     hs, ws = (I * 1)(4), (I * 1)(4)
     assert fn(0, None, None, None, hs, ws, 1, 8, None, None, None) == 1
     assert fn(1, None, None, None, hs, ws, 1, 6, None, None, None) == 1
     assert fn(17, None, None, None, hs, ws, 1, 8, None, None, None) == 1
     # sizes only (no pointers, no launch)
-    lib.msda_backward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_backward_workspace_bytes.argtypes = [I] * 7 + [ctypes.c_uint]
     assert lib.msda_backward_workspace_bytes(2, 3060, 8, 32, 4, 300, 4, 1) == 0           # deterministic: counters in LDS
     assert lib.msda_backward_workspace_bytes(2, 3060, 8, 32, 4, 3060, 4, 1) == 0
     assert lib.msda_backward_workspace_bytes(2, 3060, 8, 32, 4, 3060, 4, 0) == 0           # default kernels need none
@@ -249,16 +287,12 @@ def test_argument_errors_are_reported_before_anything_is_launched(native):
     assert lib.msda_attn32_supported(300, 300, 32) == 1 and lib.msda_attn32_supported(321, 300, 32) == 0
     assert lib.msda_attn32_supported(300, 0, 32) == 0 and lib.msda_attn32_supported(300, 300, 64) == 0
     fn = lib.msda_attn32_forward_f32
-    fn.argtypes = [V, LL, LL] * 3 + [I] * 4 + [ctypes.c_float] * 2 + [V] + [V, LL, LL] + [V, V]
-    fn.restype = I
     assert fn(*([None, 256, 256] * 3), 2, 8, 400, 400, 0.17, 0.0, None, None, 256, 256, None, None) == 1      # too long
     assert b"320" in lib.msda_last_error()
     assert fn(*([None, 256, 256] * 3), 2, 8, 300, 300, 0.17, 0.1, None, None, 256, 256, None, None) == 1      # dropout without a seed
     assert fn(*([None, 256, 256] * 3), 2, 8, 300, 300, 0.17, 1.0, None, None, 256, 256, None, None) == 1      # p = 1
     assert fn(*([None, 256, 256] * 3), 2, 8, 300, 300, 0.17, 0.0, None, None, 256, 256, None, None) == 1      # null tensors
     assert b"aligned" in lib.msda_last_error()
-    lib.msda_unflatten_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_unflatten_workspace_bytes.argtypes = [I, V, V, I, I]
     hs4, ws4 = (I * 4)(28, 14, 7, 4), (I * 4)(28, 14, 7, 4)
     assert lib.msda_unflatten_workspace_bytes(4, hs4, ws4, 32, 256) == 32 * (13 + 4 + 1 + 1) * 4 * 64 * 4
 
@@ -268,9 +302,6 @@ def test_deterministic_work_bound_is_host_logic(native):
     tests; msda_deterministic_supported says on which side a geometry falls (hosts under warn_only=True ask, warn, and run the
     default kernels instead of raising)."""
     lib = native._lib
-    I = ctypes.c_int
-    lib.msda_deterministic_supported.restype = I
-    lib.msda_deterministic_supported.argtypes = [I] * 8
     assert lib.msda_deterministic_supported(4, 2, 3060, 8, 32, 4, 3060, 4) == 1           # D = 32 family: always
     assert lib.msda_deterministic_supported(4, 32, 1045, 8, 32, 4, 1045, 4) == 1
     # fp64 (generic family): 4 * 65536 * 8 rows x 32768 * 1 points = 2^36 exactly -> allowed; one more query -> refused
@@ -302,11 +333,6 @@ def test_warn_only_clears_the_flag_for_geometries_without_a_deterministic_kernel
 def test_a_backward_workspace_with_the_forward_table_is_table_then_scratch(native):
     """MSDA_FLAG_FORWARD_TABLE: the forward's buffer first (rounded up to 256 bytes), the call's own scratch behind it."""
     lib = native._lib
-    I = ctypes.c_int
-    lib.msda_backward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_backward_workspace_bytes.argtypes = [I] * 7 + [ctypes.c_uint]
-    lib.msda_forward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_forward_workspace_bytes.argtypes = [I] * 7 + [ctypes.c_uint]
     enc = (2, 3060, 8, 32, 4, 3060, 4)                                                    # cfg-2 encoder: range masks + per-head scratch
     masks = lib.msda_forward_workspace_bytes(*enc, 2)
     heads = lib.msda_backward_workspace_bytes(*enc, 2)
@@ -325,8 +351,6 @@ def test_range_masks_are_planned_from_four_ranges_per_level_on(native):
     where the backward's kept-taps pass cuts the levels into 4..8 ranges — never for single-pass plans, small problems, the
     deterministic flag, or two / three ranges (measured: the forward's bytes cost more than those scans, profiles/r05_notes.md)."""
     lib = native._lib
-    lib.msda_forward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_forward_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_uint]
     cases = [  # (N, shapes, Lq, W in the plan text, masks?)
         (2, [(48, 48), (24, 24), (12, 12), (6, 6)], 3060, "W=6", True),           # cfg-2 encoder
         (4, [(40, 40), (20, 20), (10, 10)], 2100, "W=4", True),
@@ -347,10 +371,8 @@ def test_int32_row_offsets_bound_the_d32_family():
     """Role B's gathers read a (batch, head) pair's grad_out rows through a buffer descriptor with 32-bit BYTE offsets
     q * M * 128: the tiled family only takes geometries with Lq * M * 128 B < 2^31 (others go to the generic kernels, whose
     indices are 64-bit).  Host logic only: no launch."""
-    import ctypes
-    lib = ctypes.CDLL(os.path.join(ROOT, "uvhand_amd", "libmsda_hip.so"))
-    lib.msda_prologue_supported.restype = ctypes.c_int
-    lib.msda_prologue_supported.argtypes = [ctypes.c_int] * 7
+    from uvhand_amd import _native
+    lib = _native.declare(ctypes.CDLL(os.path.join(ROOT, "uvhand_amd", "libmsda_hip.so")))
     # N = 1, M = 8, L = 1, P = 4: every other limit of the family (items * 32 < 2^31, items*L*P*2 < 2^31) still holds at Lq = 2^21
     assert lib.msda_prologue_supported(1, 64, 8, 32, 1, (1 << 21) - 1, 4) == 1          # 2^31 - 1024 bytes of a pair's rows
     assert lib.msda_prologue_supported(1, 64, 8, 32, 1, 1 << 21, 4) == 0               # exactly 2^31

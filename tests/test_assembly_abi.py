@@ -5,7 +5,6 @@ import ctypes
 
 import pytest
 
-V, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 P = 0x10000                      # 16-byte aligned fake device address, only passed next to an argument the checks refuse
 ERR_ARGUMENT = 1
 
@@ -18,13 +17,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_assembly_refine_f32.argtypes = [V, I, V, I, V, LL, V, V]
-    h.msda_assembly_proposals_f32.argtypes = [V, LL, V, LL, I, I, I, I, V, V, V, V]
-    h.msda_assembly_select_f32.argtypes = [V, V, V] + [I] * 7 + [V, V, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _err(lib):

@@ -5,7 +5,6 @@ import ctypes
 
 import pytest
 
-V, I, LL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 OK_PTR = 0x10000                 # 16-byte aligned; only ever passed next to an argument the checks refuse
 
 NEW_ENTRIES = ("msda_attn32_forward_bf16", "msda_attn32_backward_bf16", "msda_add_layernorm_forward_f32_bf16res",
@@ -18,13 +17,10 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    handle = ctypes.CDLL(_native.LIB_PATH)
-    handle.msda_last_error.restype = ctypes.c_char_p
+    handle = _native.declare(ctypes.CDLL(_native.LIB_PATH))
     yield handle
     # leave no error text behind for later tests in this process: an empty problem passes every check and launches nothing
     fn = handle.msda_add_layernorm_forward_f32_bf16res
-    fn.argtypes = [V, V, V, V, LL, I, F, V, V, V, V]
-    fn.restype = I
     assert fn(None, None, None, None, 0, 256, 1e-5, None, None, None, None) == 0
     assert handle.msda_last_error() == b""
 
@@ -32,22 +28,15 @@ def lib():
 def test_library_exports_the_bf16_entries_at_abi_116(lib):
     for name in NEW_ENTRIES:
         assert hasattr(lib, name), name
-    lib.msda_version.restype = I
     assert lib.msda_version() == 116
 
 
 def _fwd(lib):
-    fn = lib.msda_attn32_forward_bf16
-    fn.argtypes = [V, LL, LL] * 3 + [I] * 4 + [F] * 2 + [V] + [V, LL, LL] + [V, V]
-    fn.restype = I
-    return fn
+    return lib.msda_attn32_forward_bf16
 
 
 def _bwd(lib):
-    fn = lib.msda_attn32_backward_bf16
-    fn.argtypes = [V, LL, LL] * 4 + [V] + [V, LL, LL] + [I] * 4 + [F] * 2 + [V] + [V, LL, LL] * 3 + [V]
-    fn.restype = I
-    return fn
+    return lib.msda_attn32_backward_bf16
 
 
 def test_attention_bf16_forward_argument_errors(lib):
@@ -99,8 +88,6 @@ def test_attention_bf16_backward_argument_errors(lib):
 
 def test_add_layernorm_bf16res_argument_errors(lib):
     fwd = lib.msda_add_layernorm_forward_f32_bf16res
-    fwd.argtypes = [V, V, V, V, LL, I, F, V, V, V, V]
-    fwd.restype = I
     assert fwd(None, None, None, None, 4, 6, 1e-5, None, None, None, None) == 1            # width not a multiple of 4
     assert b"multiple of 4" in lib.msda_last_error()
     assert fwd(None, None, None, None, 4, 2048, 1e-5, None, None, None, None) == 1
@@ -112,8 +99,6 @@ def test_add_layernorm_bf16res_argument_errors(lib):
     assert fwd(p, p, p, p, 4, 256, 1e-5, p, None, p, None) == 1                            # null mean
     assert fwd(p + 8, p, p, p, 4, 256, 1e-5, p, p, p, None) == 1                           # x not 16-byte aligned
     bwd = lib.msda_add_layernorm_backward_f32_bf16res
-    bwd.argtypes = [V] * 6 + [LL, I] + [V] * 6
-    bwd.restype = I
     assert bwd(None, None, None, None, None, None, 4, 6, None, None, None, None, None, None) == 1
     assert b"multiple of 4" in lib.msda_last_error()
     assert bwd(p, p, p, p, p, p, 4, 256, p, None, p, p, p, None) == 1                       # no bf16 gradient for the residual

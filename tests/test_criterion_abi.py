@@ -5,10 +5,9 @@ import ctypes
 
 import pytest
 
-V, I, LL, ULL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_float
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
-COMMON = [I, V, V, V] + [I] * 5 + [V, I, V, V, V, LL, V, V, ULL, V, F]
 
 
 @pytest.fixture(scope="module")
@@ -17,13 +16,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ctypes.c_ulonglong
-    h.msda_criterion_fwd_f32.argtypes = COMMON + [V, V, V]
-    h.msda_criterion_bwd_f32.argtypes = COMMON + [V, V, V, V, V, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ptrs(n, value=P):

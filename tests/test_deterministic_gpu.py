@@ -74,13 +74,10 @@ def test_deterministic_mode_needs_no_scratch(native, oracle):
     z = make_case(9, *case)
     through_python = _backward(native, z)
     _check(z, through_python, oracle)
-    import ctypes
     t = {k: dev(z[k]) for k in ("value", "loc", "attn", "grad_out")}
     sh, ls = dev(z["shapes"]), dev(z["level_start"])
     gv, gl, ga = torch.empty_like(t["value"]), torch.empty_like(t["loc"]), torch.empty_like(t["attn"])
     fn = lib.msda_backward_ws_f32
-    fn.argtypes = native._BWD_WS_ARGTYPES
-    fn.restype = ctypes.c_int
     scratch = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
     rc = fn(t["grad_out"].data_ptr(), t["value"].data_ptr(), sh.data_ptr(), ls.data_ptr(), t["loc"].data_ptr(),
             t["attn"].data_ptr(), N, S, M, D, len(shapes), Lq, P, gv.data_ptr(), gl.data_ptr(), ga.data_ptr(), scratch.data_ptr(),

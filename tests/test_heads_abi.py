@@ -5,10 +5,9 @@ import ctypes
 
 import pytest
 
-V, I, LL, U, ULL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_uint, ctypes.c_ulonglong
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
-COMMON = [I, I, LL, I, I, I, I, U] + [V] * 9
 
 
 @pytest.fixture(scope="module")
@@ -17,16 +16,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ULL
-    h.msda_heads_supported.argtypes = [I]
-    h.msda_heads_workspace_bytes.restype = ULL
-    h.msda_heads_workspace_bytes.argtypes = [I, I, LL, I, I, I, U]
-    h.msda_heads_forward_f32.argtypes = COMMON + [V] * 6
-    h.msda_heads_backward_f32.argtypes = COMMON + [V] * 13 + [ULL, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ptrs(n, value=P):

@@ -279,13 +279,10 @@ def test_several_weight_gradients_in_one_call_equal_the_single_calls():
     single = [_native.linear_wgrad(dy, x, want_bias=True, row_mask=mk) for dy, x, mk in zip(dys, xs, masks)]
     gws = [torch.empty(n, k, device="cuda") for m, n, k, _ in probs]
     gbs = [torch.empty(n, device="cuda") for m, n, k, _ in probs]
-    lib.msda_linear_wgrad_workspace_bytes.restype = ctypes.c_ulonglong
     wss = [torch.empty(max(16, int(lib.msda_linear_wgrad_workspace_bytes(m, n, k))), dtype=torch.uint8, device="cuda") for m, n, k, _ in probs]
     VP, I = ctypes.c_void_p, ctypes.c_int
     arr = lambda ts: (VP * 4)(*[t.data_ptr() if t is not None else None for t in ts])
     ints = lambda vs: (I * 4)(*vs)
-    lib.msda_linear_wgrad_multi_f32.restype = I
-    lib.msda_linear_wgrad_multi_f32.argtypes = [I] + [VP] * 10
     rc = lib.msda_linear_wgrad_multi_f32(4, arr(dys), arr(xs), arr(masks), ints([p[0] for p in probs]), ints([p[1] for p in probs]),
                                          ints([p[2] for p in probs]), arr(gws), arr(gbs), arr(wss), torch.cuda.current_stream().cuda_stream)
     assert rc == 0, _native._lib.msda_last_error()
@@ -310,13 +307,10 @@ def test_mixed_operand_weight_gradients_in_one_call_equal_the_single_calls():
     single = [_native.linear_wgrad(dy, x, want_bias=True) for dy, x in zip(dys, xs)]
     gws = [torch.empty(n, k, device="cuda") for m, n, k, _ in probs]
     gbs = [torch.empty(n, device="cuda") for m, n, k, _ in probs]
-    lib.msda_linear_wgrad_workspace_bytes.restype = ctypes.c_ulonglong
     wss = [torch.empty(max(16, int(lib.msda_linear_wgrad_workspace_bytes(m, n, k))), dtype=torch.uint8, device="cuda") for m, n, k, _ in probs]
     VP, I = ctypes.c_void_p, ctypes.c_int
     arr = lambda ts: (VP * 4)(*[t.data_ptr() for t in ts])
     ints = lambda vs: (I * 4)(*vs)
-    lib.msda_linear_wgrad_multi.restype = I
-    lib.msda_linear_wgrad_multi.argtypes = [I] + [VP] * 11
     rc = lib.msda_linear_wgrad_multi(3, arr(dys), arr(xs), ints([int(p[3]) for p in probs]), None, ints([p[0] for p in probs]),
                                      ints([p[1] for p in probs]), ints([p[2] for p in probs]), arr(gws), arr(gbs), arr(wss),
                                      torch.cuda.current_stream().cuda_stream)

@@ -5,12 +5,11 @@ import ctypes
 
 import pytest
 
-V, I, ULL = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
 PARENTS = [-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14]
 TIPS = [744, 320, 443, 554, 671]
-GEO = [I] * 4 + [V, V, I, V, V, V]
 SYMBOLS = ("msda_mano_supported", "msda_mano_workspace_bytes", "msda_mano_forward_f32", "msda_mano_backward_f32")
 
 
@@ -20,16 +19,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ULL
-    h.msda_mano_supported.argtypes = [I] * 3
-    h.msda_mano_workspace_bytes.restype = ULL
-    h.msda_mano_workspace_bytes.argtypes = [I] * 4 + [V]
-    h.msda_mano_forward_f32.argtypes = GEO + [V, V, V]
-    h.msda_mano_backward_f32.argtypes = GEO + [V, V, V, V, ULL, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ints(vals):

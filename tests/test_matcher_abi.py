@@ -5,7 +5,7 @@ import ctypes
 
 import pytest
 
-V, I, LL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
 NEW_ENTRIES = ("msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32")
@@ -17,14 +17,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ctypes.c_ulonglong
-    h.msda_match_arctic_f32.argtypes = [V, V, V] + [I] * 5 + [V, V, V, LL, V, I, F, F, V, V, V]
-    h.msda_match_assembly_f32.argtypes = [V, V] + [I] * 5 + [V, V, V, LL, I, F, F, V, V, V]
-    h.msda_lsap_f32.argtypes = [V, I, I, I, V, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ptrs(n, value=P):

@@ -6,7 +6,7 @@ import ctypes
 
 import pytest
 
-V, I, ULL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_float
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
 SYMBOLS = ("msda_object_supported", "msda_object_forward_f32", "msda_object_backward_f32", "msda_small_loss_supported",
@@ -21,18 +21,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_launch_count.restype = ULL
-    h.msda_object_supported.argtypes = [I] * 7
-    h.msda_object_forward_f32.argtypes = [V, V, I, V, V, V, V, V]
-    h.msda_object_backward_f32.argtypes = [V, V, I, V, V, V, V, V, V]
-    h.msda_small_loss_supported.argtypes = [I] * 7
-    h.msda_small_loss_workspace_bytes.argtypes = [I] * 7
-    h.msda_small_loss_workspace_bytes.restype = ULL
-    h.msda_small_loss_forward_f32.argtypes = [V, F, V, V, V, V, ULL, V]
-    h.msda_small_loss_backward_f32.argtypes = [V, F, V, V, V, V, V, ULL, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ints(vals):

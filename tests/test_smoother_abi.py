@@ -5,10 +5,9 @@ import ctypes
 
 import pytest
 
-V, I, ULL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_float
+V = ctypes.c_void_p
 P = 0x10000
 ERR_ARGUMENT = 1
-GEO = [I] * 7 + [V] * 3
 SYMBOLS = ("msda_smoother_supported", "msda_smoother_workspace_bytes", "msda_smoother_forward_f32",
            "msda_smoother_backward_f32", "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32",
            "msda_arctic_item_backward_f32")
@@ -20,19 +19,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ULL
-    h.msda_smoother_supported.argtypes = [I] * 5
-    h.msda_smoother_workspace_bytes.restype = ULL
-    h.msda_smoother_workspace_bytes.argtypes = GEO + [I]
-    h.msda_smoother_forward_f32.argtypes = GEO + [V] * 4 + [ULL, I, F, V, V]
-    h.msda_smoother_backward_f32.argtypes = GEO + [V, V, V, ULL, V, V, V, I, F, V, V, ULL, V]
-    h.msda_smoother_dropout_mask_f32.argtypes = [V, I, I, I, I, F, V, V]
-    h.msda_arctic_item_forward_f32.argtypes = [I] * 6 + [V] * 5
-    h.msda_arctic_item_backward_f32.argtypes = [I, I] + [V] * 4
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _ints(vals):

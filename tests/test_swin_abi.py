@@ -6,10 +6,8 @@ import ctypes
 
 import pytest
 
-V, I, ULL = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
 P = 0x10000
 ERR_ARGUMENT = 1
-GEO = [I] * 7
 SYMBOLS = ("msda_swin_attn_supported", "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_f32",
            "msda_swin_attn_backward_f32")
 
@@ -20,16 +18,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_launch_count.restype = ULL
-    h.msda_swin_attn_supported.argtypes = GEO
-    h.msda_swin_attn_workspace_bytes.restype = ULL
-    h.msda_swin_attn_workspace_bytes.argtypes = GEO + [I]
-    h.msda_swin_attn_forward_f32.argtypes = GEO + [V] * 5 + [ULL, V]
-    h.msda_swin_attn_backward_f32.argtypes = GEO + [V] * 5 + [ULL] + [V] * 5 + [ULL, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def test_symbols_and_version(lib):

@@ -5,7 +5,7 @@ import ctypes
 
 import pytest
 
-V, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+V = ctypes.c_void_p
 P = 0x10000                      # 16-byte aligned fake device address, only passed next to an argument the checks refuse
 ERR_ARGUMENT = 1
 
@@ -19,15 +19,7 @@ def lib():
     __graft_entry__.build()
     from uvhand_amd import _native
     _native.load()
-    h = ctypes.CDLL(_native.LIB_PATH)
-    h.msda_last_error.restype = ctypes.c_char_p
-    h.msda_version.restype = I
-    h.msda_two_stage_proposals_f32.argtypes = [V, V, I, I, I, I, V, V, V, V, V, V, V]
-    h.msda_two_stage_select_supported.argtypes = [I, I, I]
-    h.msda_two_stage_select_f32.argtypes = [V] * 4 + [I] * 6 + [V] * 4
-    h.msda_proposal_pos_embed_f32.argtypes = [V, V, LL, V, V]
-    h.msda_proposal_pos_linear_relu_f32.argtypes = [V, V, V, V, LL, I, V, V]
-    yield h
+    yield _native.declare(ctypes.CDLL(_native.LIB_PATH))
 
 
 def _err(lib):

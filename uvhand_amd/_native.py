@@ -21,36 +21,142 @@ LIB_PATH = os.path.join(_PKG_DIR, "libmsda_hip.so")
 
 _lib = None
 
-_SYMBOLS = (
-    "msda_forward_f32", "msda_backward_f32", "msda_forward_f64", "msda_backward_f64",
-    "msda_forward_bf16", "msda_backward_bf16", "msda_backward_bf16_gv32", "msda_backward_passes",
-    "msda_backward_workspace_bytes", "msda_deterministic_supported", "msda_backward_ws_f32", "msda_backward_ws_f64", "msda_backward_ws_bf16",
-    "msda_backward_ws_bf16_gv32",
-    "msda_backward_prologue_ws_f32", "msda_forward_prologue_bf16", "msda_backward_prologue_bf16_gv32",
-    "msda_add_layernorm_workspace_bytes", "msda_add_layernorm_forward_f32", "msda_add_layernorm_backward_f32",
-    "msda_relu_dropout_backward_f32", "msda_cast_bf16_multi_f32",
-    "msda_flatten_levels_f32", "msda_unflatten_levels_f32", "msda_unflatten_workspace_bytes",
-    "msda_linear_wgrad_f32", "msda_linear_wgrad_masked_f32", "msda_linear_wgrad_masked_bf16", "msda_linear_wgrad_multi_f32", "msda_linear_wgrad_multi", "msda_attn32_supported", "msda_attn32_forward_f32",
-    "msda_attn32_backward_f32", "msda_attn32_forward_bf16", "msda_attn32_backward_bf16", "msda_add_layernorm_forward_f32_bf16res",
-    "msda_add_layernorm_backward_f32_bf16res", "msda_linear_wgrad_workspace_bytes",
-    "msda_zero_masked_rows_f32", "msda_linear_forward_f32", "msda_linear_dgrad_f32",
-    "msda_prologue_supported", "msda_forward_prologue_f32", "msda_backward_prologue_f32",
-    "msda_last_error", "msda_version", "msda_path_for", "msda_force_path", "msda_describe_plan",
-    "msda_forward_workspace_bytes", "msda_forward_ws_f32", "msda_forward_ws_bf16", "msda_forward_prologue_ws_f32",
-    "msda_forward_prologue_ws_bf16", "msda_probe_row_gather", "msda_launch_count",
-    "msda_two_stage_proposals_f32", "msda_two_stage_select_supported", "msda_two_stage_select_f32",
-    "msda_proposal_pos_embed_f32", "msda_proposal_pos_linear_relu_f32",
-    "msda_assembly_refine_f32", "msda_assembly_proposals_f32", "msda_assembly_select_f32",
-    "msda_match_arctic_f32", "msda_match_assembly_f32", "msda_lsap_f32",
-    "msda_criterion_fwd_f32", "msda_criterion_bwd_f32",
-    "msda_heads_supported", "msda_heads_workspace_bytes", "msda_heads_forward_f32", "msda_heads_backward_f32",
-    "msda_smoother_supported", "msda_smoother_workspace_bytes", "msda_smoother_forward_f32", "msda_smoother_backward_f32",
-    "msda_smoother_dropout_mask_f32", "msda_arctic_item_forward_f32", "msda_arctic_item_backward_f32",
-    "msda_swin_attn_supported", "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_f32", "msda_swin_attn_backward_f32",
-    "msda_mano_supported", "msda_mano_workspace_bytes", "msda_mano_forward_f32", "msda_mano_backward_f32",
-    "msda_object_supported", "msda_object_forward_f32", "msda_object_backward_f32", "msda_small_loss_supported",
-    "msda_small_loss_workspace_bytes", "msda_small_loss_forward_f32", "msda_small_loss_backward_f32",
-)
+# Every function of include/msda.h: "<return> <arguments>", one letter per C type (spaces only group them for the eye).
+# tests/test_abi.py holds this table against the header, name by name and position by position.
+_CTYPE = {"v": None, "i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "U": ctypes.c_ulonglong,
+          "f": ctypes.c_float, "d": ctypes.c_double, "p": ctypes.c_void_p,      # p: any pointer, msda_stream_t included
+          "s": ctypes.c_char_p, "q": ctypes.POINTER(ctypes.c_ulonglong)}          # the two pointers ctypes converts itself
+SIGNATURES = {
+    # the op
+    "msda_forward_f32": "i ppppp iiiiiii pp",
+    "msda_backward_f32": "i pppppp iiiiiii pppp",
+    "msda_forward_f64": "i ppppp iiiiiii pp",
+    "msda_backward_f64": "i pppppp iiiiiii pppp",
+    "msda_forward_bf16": "i ppppp iiiiiii pp",
+    "msda_backward_bf16": "i pppppp iiiiiii pppp",
+    "msda_backward_bf16_gv32": "i pppppp iiiiiii pppp",
+    "msda_backward_passes": "i ii",
+    # backward with flags and caller-provided scratch
+    "msda_backward_workspace_bytes": "U iiiiiii u",
+    "msda_deterministic_supported": "i iiiiiiii",
+    "msda_backward_ws_f32": "i pppppp iiiiiii pppp U u p",
+    "msda_backward_ws_f64": "i pppppp iiiiiii pppp U u p",
+    "msda_backward_ws_bf16": "i pppppp iiiiiii pppp U u p",
+    "msda_backward_ws_bf16_gv32": "i pppppp iiiiiii pppp U u p",
+    # forward that prepares its backward
+    "msda_forward_workspace_bytes": "U iiiiiii u",
+    "msda_forward_ws_f32": "i ppppp iiiiiii pp U p",
+    "msda_forward_ws_bf16": "i ppppp iiiiiii pp U p",
+    # fused module prologue
+    "msda_prologue_supported": "i iiiiiii",
+    "msda_forward_prologue_f32": "i pppppp iiiiiii ll pppp",
+    "msda_backward_prologue_f32": "i pppppp iiiiiii ll ppppp",
+    "msda_forward_prologue_ws_f32": "i pppppp iiiiiii ll pppp U p",
+    "msda_backward_prologue_ws_f32": "i pppppp iiiiiii ll ppppp U u p",
+    "msda_forward_prologue_bf16": "i pppppp iiiiiii ll pppp",
+    "msda_forward_prologue_ws_bf16": "i pppppp iiiiiii ll pppp U p",
+    "msda_backward_prologue_bf16_gv32": "i pppppp iiiiiii ll ppppp U u p",
+    # bracketing projections
+    "msda_linear_wgrad_workspace_bytes": "U iii",
+    "msda_linear_wgrad_f32": "i pp iii pppp",
+    "msda_linear_wgrad_masked_f32": "i ppp iii pppp",
+    "msda_linear_wgrad_masked_bf16": "i ppp iii pppp",
+    "msda_linear_wgrad_multi": "i i pppp ppp pppp",
+    "msda_linear_wgrad_multi_f32": "i i ppp ppp pppp",
+    "msda_zero_masked_rows_f32": "i pp l i p",
+    "msda_cast_bf16_multi_f32": "i i pppp",
+    "msda_linear_forward_f32": "i pppp l ii pp",
+    "msda_linear_dgrad_f32": "i ppp l ii pp",
+    # residual add + LayerNorm, FFN
+    "msda_add_layernorm_workspace_bytes": "U l i",
+    "msda_add_layernorm_forward_f32": "i pppp l i f pppp",
+    "msda_add_layernorm_backward_f32": "i pppppp l i ppppp",
+    "msda_add_layernorm_forward_f32_bf16res": "i pppp l i f pppp",
+    "msda_add_layernorm_backward_f32_bf16res": "i pppppp l i pppppp",
+    "msda_relu_dropout_backward_f32": "i pp f l p",
+    # decoder self-attention core
+    "msda_attn32_supported": "i iii",
+    "msda_attn32_forward_f32": "i pll pll pll iiii ff p pll pp",
+    "msda_attn32_backward_f32": "i pll pll pll pll p pll iiii ff p pll pll pll p",
+    "msda_attn32_forward_bf16": "i pll pll pll iiii ff p pll pp",
+    "msda_attn32_backward_bf16": "i pll pll pll pll p pll iiii ff p pll pll pll p",
+    # transformer input assembly
+    "msda_flatten_levels_f32": "i i ppppp ii ppp",
+    "msda_unflatten_levels_f32": "i i pppp ii ppppp",
+    "msda_unflatten_workspace_bytes": "U i pp ii",
+    "msda_last_error": "s",
+    # two-stage query selection
+    "msda_two_stage_proposals_f32": "i pp iiii ppppppp",
+    "msda_two_stage_select_supported": "i iii",
+    "msda_two_stage_select_f32": "i pppp iiiiii pppp",
+    "msda_proposal_pos_embed_f32": "i pp l pp",
+    "msda_proposal_pos_linear_relu_f32": "i pppp l i pp",
+    # the AssemblyHands transformer
+    "msda_assembly_refine_f32": "i p i p i p l pp",
+    "msda_assembly_proposals_f32": "i p l p l iiii pppp",
+    "msda_assembly_select_f32": "i ppp iiiiiii ppp",
+    # the Hungarian matchers
+    "msda_match_arctic_f32": "i ppp iiiii ppp l p i ff ppp",
+    "msda_match_assembly_f32": "i pp iiiii ppp l i ff ppp",
+    "msda_lsap_f32": "i p iii pp",
+    # the set criteria's matched losses
+    "msda_criterion_fwd_f32": "i i ppp iiiii p i ppp l pp U p f ppp",
+    "msda_criterion_bwd_f32": "i i ppp iiiii p i ppp l pp U p f pppppp",
+    # the DeformableDETR prediction heads
+    "msda_heads_supported": "i i",
+    "msda_heads_workspace_bytes": "U ii l iii u",
+    "msda_heads_forward_f32": "i ii l iiii u ppppppppp pppppp",
+    "msda_heads_backward_f32": "i ii l iiii u ppppppppp ppppp pppppppp U p",
+    # SmoothNet and get_arctic_item's selection
+    "msda_smoother_supported": "i iiiii",
+    "msda_smoother_workspace_bytes": "U iiiiiii ppp i",
+    "msda_smoother_forward_f32": "i iiiiiii ppp pppp U i f pp",
+    "msda_smoother_backward_f32": "i iiiiiii ppp ppp U ppp i f pp U p",
+    "msda_smoother_dropout_mask_f32": "i p iiii f pp",
+    "msda_arctic_item_forward_f32": "i iiiiii ppppp",
+    "msda_arctic_item_backward_f32": "i ii pppp",
+    # Swin window attention
+    "msda_swin_attn_supported": "i iiiiiii",
+    "msda_swin_attn_workspace_bytes": "U iiiiiiii",
+    "msda_swin_attn_forward_f32": "i iiiiiii ppppp U p",
+    "msda_swin_attn_backward_f32": "i iiiiiii ppppp U ppppp U p",
+    # MANO hand layer
+    "msda_mano_supported": "i iii",
+    "msda_mano_workspace_bytes": "U iiii p",
+    "msda_mano_forward_f32": "i iiii pp i ppp ppp",
+    "msda_mano_backward_f32": "i iiii pp i ppp pppp U p",
+    # ARCTIC object layer and small losses
+    "msda_object_supported": "i iiiiiii",
+    "msda_object_forward_f32": "i pp i ppp pp",
+    "msda_object_backward_f32": "i pp i ppp ppp",
+    "msda_small_loss_supported": "i iiiiiii",
+    "msda_small_loss_workspace_bytes": "U iiiiiii",
+    "msda_small_loss_forward_f32": "i p f pp pp U p",
+    "msda_small_loss_backward_f32": "i p f pp ppp U p",
+    # introspection and test hooks
+    "msda_version": "i",
+    "msda_path_for": "i iiiii",
+    "msda_describe_plan": "i iiiiiiiii u i s i",
+    "msda_probe_row_gather": "i p U iii p q p",
+    "msda_launch_count": "U",
+    "msda_force_path": "v i",
+}
+
+
+def signature(name):
+    """(restype, argtypes) of one C function, as ctypes types."""
+    ret, _, args = SIGNATURES[name].partition(" ")
+    return _CTYPE[ret], [_CTYPE[c] for c in args.replace(" ", "")]
+
+
+def declare(lib):
+    """Set restype and argtypes of every function of the table on a ctypes handle of the library; returns the handle."""
+    for name in SIGNATURES:
+        if not hasattr(lib, name):
+            raise RuntimeError("uvhand_amd: %s does not export %s (stale build?)" % (LIB_PATH, name))
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = signature(name)
+    return lib
 
 
 def load():
@@ -62,45 +168,8 @@ def load():
         raise RuntimeError(
             "uvhand_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C uvhand_amd/csrc`). There is no non-HIP fallback for this op." % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    for name in _SYMBOLS:
-        if not hasattr(lib, name):
-            raise RuntimeError("uvhand_amd: %s does not export %s (stale build?)" % (LIB_PATH, name))
-    lib.msda_last_error.restype = ctypes.c_char_p
-    lib.msda_version.restype = ctypes.c_int
-    lib.msda_path_for.restype = ctypes.c_int
-    lib.msda_force_path.restype = None
-    lib.msda_prologue_supported.restype = ctypes.c_int
-    lib.msda_prologue_supported.argtypes = [ctypes.c_int] * 7
-    lib.msda_backward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_backward_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_uint]
-    lib.msda_unflatten_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_unflatten_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    lib.msda_add_layernorm_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_add_layernorm_workspace_bytes.argtypes = [ctypes.c_longlong, ctypes.c_int]
-    lib.msda_linear_wgrad_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_linear_wgrad_workspace_bytes.argtypes = [ctypes.c_int] * 3
-    lib.msda_forward_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_forward_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_uint]
-    lib.msda_launch_count.restype = ctypes.c_ulonglong
-    lib.msda_two_stage_select_supported.restype = ctypes.c_int
-    lib.msda_two_stage_select_supported.argtypes = [ctypes.c_int] * 3
-    lib.msda_describe_plan.restype = ctypes.c_int
-    lib.msda_heads_supported.restype = ctypes.c_int
-    lib.msda_heads_supported.argtypes = [ctypes.c_int]
-    lib.msda_heads_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_heads_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_uint]
-    lib.msda_describe_plan.argtypes = [ctypes.c_int] * 9 + [ctypes.c_uint, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-    lib.msda_smoother_supported.restype = ctypes.c_int
-    lib.msda_smoother_supported.argtypes = [ctypes.c_int] * 5
-    lib.msda_smoother_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_smoother_workspace_bytes.argtypes = [ctypes.c_int] * 7 + [ctypes.c_void_p] * 3 + [ctypes.c_int]
-    lib.msda_swin_attn_supported.restype = ctypes.c_int
-    lib.msda_swin_attn_supported.argtypes = [ctypes.c_int] * 7
-    lib.msda_swin_attn_workspace_bytes.restype = ctypes.c_ulonglong
-    lib.msda_swin_attn_workspace_bytes.argtypes = [ctypes.c_int] * 8
-    _lib = lib
-    return lib
+    _lib = declare(ctypes.CDLL(LIB_PATH))
+    return _lib
 
 
 def _suffix(dtype):
@@ -200,10 +269,7 @@ def _raise(lib, rc, what):
     raise RuntimeError("%s failed (code %d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
-_VP, _CI = ctypes.c_void_p, ctypes.c_int
-_FWD_ARGTYPES = [_VP] * 5 + [_CI] * 7 + [_VP, _VP]
-_BWD_ARGTYPES = [_VP] * 6 + [_CI] * 7 + [_VP] * 4
-_BWD_WS_ARGTYPES = [_VP] * 6 + [_CI] * 7 + [_VP] * 4 + [ctypes.c_ulonglong, ctypes.c_uint, _VP]
+_VP = ctypes.c_void_p
 FLAG_DETERMINISTIC = 1                                # MSDA_FLAG_DETERMINISTIC (include/msda.h)
 FLAG_PROLOGUE = 2                                     # MSDA_FLAG_PROLOGUE
 FLAG_FORWARD_TABLE = 4                                # MSDA_FLAG_FORWARD_TABLE
@@ -236,27 +302,11 @@ def _deterministic_for(lib, det, elem_bytes, N, S, M, D, L, Lq, P):
     use_deterministic_algorithms(True, warn_only=True) — then a warning and the default kernels, as torch does for its own
     ops without a deterministic form.  Without warn_only the library's refusal is raised."""
     if det and torch.is_deterministic_algorithms_warn_only_enabled():
-        lib.msda_deterministic_supported.argtypes = [ctypes.c_int] * 8
         if not lib.msda_deterministic_supported(elem_bytes, N, S, M, D, L, Lq, P):
             warnings.warn("ms_deform_attn_backward: no deterministic grad_value kernel for this geometry within the work bound "
                           "(include/msda.h, MSDA_FLAG_DETERMINISTIC); running the default (atomic) kernel [warn_only]")
             return False
     return det
-
-
-_entry_cache = {}
-
-
-def _entry(lib, name, argtypes):
-    """ctypes function with declared argtypes (plain ints go straight through: the call costs a few us
-    of host time, which matters when a kernel takes 5)."""
-    fn = _entry_cache.get(name)
-    if fn is None:
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _CI
-        _entry_cache[name] = fn
-    return fn
 
 
 def _raw_stream(device):
@@ -287,7 +337,16 @@ class _DeviceGuard:
         return False
 
 
-_FWD_WS_ARGTYPES = [_VP] * 5 + [_CI] * 7 + [_VP, _VP, ctypes.c_ulonglong, _VP]
+def _launch(dev, name, what, *args):
+    """The launch a wrapper ends in: on the tensors' device, msda.h's `name` with PyTorch's current stream there as the
+    last argument; a non-zero status raises with the library's message.  The deformable-attention op's own four wrappers
+    keep this sequence inline: they also hold _ForcedPathScope, and the extra frame showed in the backward's host time
+    (profiles/native_signatures_host_time.md)."""
+    lib = _lib or load()
+    with _DeviceGuard(dev):
+        rc = getattr(lib, name)(*args, _raw_stream(dev))
+    if rc != 0:
+        _raise(lib, rc, what)
 
 
 def _forward_table(lib, N, S, M, D, L, Lq, P, device, prologue=False):
@@ -319,12 +378,12 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
         if with_table and suf != "f64":
             table = _forward_table(lib, N, S, M, D, L, Lq, P, value.device)
         if table is not None:
-            rc = _entry(lib, "msda_forward_ws_" + suf, _FWD_WS_ARGTYPES)(
+            rc = getattr(lib, "msda_forward_ws_" + suf)(
                 value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
                 attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), table.data_ptr(), table.numel(),
                 _raw_stream(value.device))
         else:
-            rc = _entry(lib, "msda_forward_" + suf, _FWD_ARGTYPES)(
+            rc = getattr(lib, "msda_forward_" + suf)(
                 value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
                 attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), _raw_stream(value.device))
     if rc != 0:
@@ -344,7 +403,7 @@ def _backward_workspace(lib, N, S, M, D, L, Lq, P, device, flags=FLAG_DETERMINIS
 
 def backward_passes(Lq, P):
     """Query chunks the D = 32 backward takes for Lq*P sampling points per (batch, head, level); 1 = single pass."""
-    return int((_lib or load()).msda_backward_passes(ctypes.c_int(Lq), ctypes.c_int(P)))
+    return int((_lib or load()).msda_backward_passes(Lq, P))
 
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
@@ -377,7 +436,7 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
             ws, nbytes, flags = table, table.numel(), flags | FLAG_FORWARD_TABLE
         else:
             ws, nbytes = _backward_workspace(lib, N, S, M, D, L, Lq, P, value.device, flags)
-        rc = _entry(lib, "msda_backward_ws_" + suf + ("_gv32" if fp32_grad_value else ""), _BWD_WS_ARGTYPES)(
+        rc = getattr(lib, "msda_backward_ws_" + suf + ("_gv32" if fp32_grad_value else ""))(
             grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
             sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P,
             grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
@@ -385,10 +444,6 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     if rc != 0:
         _raise(lib, rc, "ms_deform_attn_backward")
     return grad_value, grad_loc, grad_attn
-
-
-_LL = ctypes.c_longlong
-_WGRAD_ARGTYPES = [_VP, _VP, _VP, _CI, _CI, _CI, _VP, _VP, _VP, _VP]
 
 
 def linear_wgrad_supported(grad_out, inp):
@@ -412,14 +467,10 @@ def _row_mask_ptr(row_mask, rows, device):
 
 def zero_masked_rows_(x, row_mask):
     """In place: x[r, :] = 0 where row_mask[r] (x: contiguous fp32 [rows, cols], cols % 4 == 0) — include/msda.h."""
-    lib = _lib or load()
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] % 4 == 0):
         raise RuntimeError("zero_masked_rows_: expected a contiguous fp32 CUDA matrix with cols % 4 == 0")
-    with _DeviceGuard(x.device):
-        rc = _entry(lib, "msda_zero_masked_rows_f32", [_VP, _VP, _LL, _CI, _VP])(
-            x.data_ptr(), _row_mask_ptr(row_mask, x.shape[0], x.device), x.shape[0], x.shape[1], _raw_stream(x.device))
-    if rc != 0:
-        _raise(lib, rc, "zero_masked_rows_")
+    _launch(x.device, "msda_zero_masked_rows_f32", "zero_masked_rows_", x.data_ptr(),
+            _row_mask_ptr(row_mask, x.shape[0], x.device), x.shape[0], x.shape[1])
     return x
 
 
@@ -431,17 +482,13 @@ def linear_wgrad(grad_out, inp, want_bias=True, row_mask=None):
         raise RuntimeError("linear_wgrad: expected contiguous fp32 (or both bf16) CUDA matrices [M,N] and [M,K] with N, K % 4 == 0")
     M, N = grad_out.shape
     K = inp.shape[1]
-    with _DeviceGuard(inp.device):
-        gw = torch.empty((N, K), dtype=torch.float32, device=inp.device)
-        gb = torch.empty((N,), dtype=torch.float32, device=inp.device) if want_bias else None
-        nbytes = lib.msda_linear_wgrad_workspace_bytes(M, N, K)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=inp.device) if nbytes else None
-        rc = _entry(lib, "msda_linear_wgrad_masked_" + ("bf16" if grad_out.dtype == torch.bfloat16 else "f32"), _WGRAD_ARGTYPES)(
-            grad_out.data_ptr(), inp.data_ptr(), _row_mask_ptr(row_mask, M, inp.device), M, N, K, gw.data_ptr(),
-            gb.data_ptr() if want_bias else None,
-            ws.data_ptr() if ws is not None else None, _raw_stream(inp.device))
-    if rc != 0:
-        _raise(lib, rc, "linear_wgrad")
+    gw = torch.empty((N, K), dtype=torch.float32, device=inp.device)
+    gb = torch.empty((N,), dtype=torch.float32, device=inp.device) if want_bias else None
+    nbytes = lib.msda_linear_wgrad_workspace_bytes(M, N, K)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=inp.device) if nbytes else None
+    _launch(inp.device, "msda_linear_wgrad_masked_" + ("bf16" if grad_out.dtype == torch.bfloat16 else "f32"),
+            "linear_wgrad", grad_out.data_ptr(), inp.data_ptr(), _row_mask_ptr(row_mask, M, inp.device), M, N, K,
+            gw.data_ptr(), gb.data_ptr() if want_bias else None, ws.data_ptr() if ws is not None else None)
     return gw, gb
 
 
@@ -456,35 +503,26 @@ def linear_rows_supported(a, weight, reduce_dim):
 def linear_forward(inp, weight, bias=None, row_mask=None):
     """inp[rows, in] @ weight[out, in].T + bias, rows with row_mask[r] True written as zeros — include/msda.h
     (msda_linear_forward_f32): one fp32-MFMA launch, fixed summation order."""
-    lib = _lib or load()
     if not linear_rows_supported(inp, weight, 1) or (bias is not None and not (
             bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == weight.shape[0]
             and bias.device == inp.device and bias.data_ptr() % 16 == 0)):
         raise RuntimeError("linear_forward: expected contiguous fp32 CUDA [rows, in] and [out, in] (+ [out]) with in, out % 4 == 0")
     rows, out_f, in_f = inp.shape[0], weight.shape[0], weight.shape[1]
-    with _DeviceGuard(inp.device):
-        y = torch.empty((rows, out_f), dtype=torch.float32, device=inp.device)
-        rc = _entry(lib, "msda_linear_forward_f32", [_VP, _VP, _VP, _VP, _LL, _CI, _CI, _VP, _VP])(
-            inp.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-            _row_mask_ptr(row_mask, rows, inp.device), rows, out_f, in_f, y.data_ptr(), _raw_stream(inp.device))
-    if rc != 0:
-        _raise(lib, rc, "linear_forward")
+    y = torch.empty((rows, out_f), dtype=torch.float32, device=inp.device)
+    _launch(inp.device, "msda_linear_forward_f32", "linear_forward", inp.data_ptr(), weight.data_ptr(),
+            bias.data_ptr() if bias is not None else None, _row_mask_ptr(row_mask, rows, inp.device), rows, out_f, in_f,
+            y.data_ptr())
     return y
 
 
 def linear_dgrad(grad_out, weight, row_mask=None):
     """grad_out[rows, out] @ weight[out, in], rows with row_mask[r] True written as zeros — include/msda.h (msda_linear_dgrad_f32)."""
-    lib = _lib or load()
     if not linear_rows_supported(grad_out, weight, 0):
         raise RuntimeError("linear_dgrad: expected contiguous fp32 CUDA [rows, out] and [out, in] with in, out % 4 == 0")
     rows, out_f, in_f = grad_out.shape[0], weight.shape[0], weight.shape[1]
-    with _DeviceGuard(grad_out.device):
-        gx = torch.empty((rows, in_f), dtype=torch.float32, device=grad_out.device)
-        rc = _entry(lib, "msda_linear_dgrad_f32", [_VP, _VP, _VP, _LL, _CI, _CI, _VP, _VP])(
-            grad_out.data_ptr(), weight.data_ptr(), _row_mask_ptr(row_mask, rows, grad_out.device), rows, out_f, in_f,
-            gx.data_ptr(), _raw_stream(grad_out.device))
-    if rc != 0:
-        _raise(lib, rc, "linear_dgrad")
+    gx = torch.empty((rows, in_f), dtype=torch.float32, device=grad_out.device)
+    _launch(grad_out.device, "msda_linear_dgrad_f32", "linear_dgrad", grad_out.data_ptr(), weight.data_ptr(),
+            _row_mask_ptr(row_mask, rows, grad_out.device), rows, out_f, in_f, gx.data_ptr())
     return gx
 
 
@@ -519,9 +557,6 @@ def _row_stride(t, name):
     if ld < inner or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld):
         raise RuntimeError("%s tensor has to be contiguous or a column block of a row-major matrix" % name)
     return ld
-
-
-_LL = ctypes.c_longlong
 
 
 def prologue_geometry_supported(N, S, M, D, L, Lq, P):
@@ -574,8 +609,7 @@ def ms_deform_attn_forward_prologue(value, spatial_shapes, level_start_index, re
         loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=value.device)
         attn = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=value.device)
         table = _forward_table(lib, N, S, M, D, L, Lq, P, value.device, prologue=True) if with_table else None
-        rc = _entry(lib, "msda_forward_prologue_ws_" + ("bf16" if bf16 else "f32"),
-                    [_VP] * 6 + [_CI] * 7 + [_LL] * 2 + [_VP] * 4 + [ctypes.c_ulonglong, _VP])(
+        rc = getattr(lib, "msda_forward_prologue_ws_" + ("bf16" if bf16 else "f32"))(
             value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(),
             sampling_offsets.data_ptr(), attn_logits.data_ptr(), N, S, M, D, L, Lq, P, ld_off, ld_log, out.data_ptr(),
             loc.data_ptr(), attn.data_ptr(), table.data_ptr() if table is not None else None,
@@ -625,8 +659,7 @@ def ms_deform_attn_backward_prologue(value, spatial_shapes, level_start_index, s
         else:
             ws, nbytes = _backward_workspace(lib, N, S, M, D, L, Lq, P, value.device,
                                              FLAG_PROLOGUE | (FLAG_DETERMINISTIC if det else 0)) if use_workspace else (None, 0)
-        rc = _entry(lib, "msda_backward_prologue_bf16_gv32" if bf16 else "msda_backward_prologue_ws_f32",
-                    [_VP] * 6 + [_CI] * 7 + [_LL] * 2 + [_VP] * 5 + [ctypes.c_ulonglong, ctypes.c_uint, _VP])(
+        rc = getattr(lib, "msda_backward_prologue_bf16_gv32" if bf16 else "msda_backward_prologue_ws_f32")(
             grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
             sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, ld_off, ld_log, gv.data_ptr(),
             goff.data_ptr(), glog.data_ptr(), gref.data_ptr(), ws.data_ptr() if ws is not None else None, nbytes,
@@ -639,16 +672,12 @@ def ms_deform_attn_backward_prologue(value, spatial_shapes, level_start_index, s
 def relu_dropout_backward_(grad, act, scale):
     """grad *= scale * (act > 0), in place (msda_relu_dropout_backward_f32, include/msda.h): the backward of
     dropout(relu(h)) from act = dropout(relu(h)).  fp32 CUDA tensors of the same size, contiguous, 16-byte aligned."""
-    lib = _lib or load()
     n = grad.numel()
     if not (grad.is_cuda and act.is_cuda and grad.dtype == act.dtype == torch.float32 and act.numel() == n
             and grad.is_contiguous() and act.is_contiguous()):
         raise RuntimeError("relu_dropout_backward_: expected two contiguous float32 CUDA tensors of one size")
-    with _DeviceGuard(grad.device):
-        rc = _entry(lib, "msda_relu_dropout_backward_f32", [_VP, _VP, ctypes.c_float, _LL, _VP])(
-            grad.data_ptr(), act.data_ptr(), float(scale), n, _raw_stream(grad.device))
-    if rc != 0:
-        _raise(lib, rc, "relu_dropout_backward_")
+    _launch(grad.device, "msda_relu_dropout_backward_f32", "relu_dropout_backward_", grad.data_ptr(), act.data_ptr(),
+            float(scale), n)
     return grad
 
 
@@ -676,21 +705,17 @@ def attn32_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None):
     q [Lq, N, E], k / v [Lk, N, E] (sequence first, as nn.MultiheadAttention projects them; column-block views allowed);
     seed: a one-element int64 CUDA tensor (required when dropout_p > 0).  Returns (out [Lq, N, E], lse [N*heads, Lq]).
     bfloat16 q, k, v take msda_attn32_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
-    lib = _lib or load()
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
     dt = _attn_dtype(q)
     qv, kv, vv = _attn_view(q, "q", heads, dt), _attn_view(k, "k", heads, dt), _attn_view(v, "v", heads, dt)
     if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise RuntimeError("attn32_forward: dropout needs a one-element int64 CUDA seed tensor")
-    with _DeviceGuard(q.device):
-        out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
-        lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
-        ov = _attn_view(out, "out", heads, dt)
-        rc = _entry(lib, "msda_attn32_forward_bf16" if dt == torch.bfloat16 else "msda_attn32_forward_f32", [_VP, _LL, _LL] * 3 + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP] + [_VP, _LL, _LL] + [_VP, _VP])(
+    out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
+    lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
+    ov = _attn_view(out, "out", heads, dt)
+    _launch(q.device, "msda_attn32_forward_bf16" if dt == torch.bfloat16 else "msda_attn32_forward_f32", "attn32_forward",
             *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *ov,
-            lse.data_ptr(), _raw_stream(q.device))
-    if rc != 0:
-        _raise(lib, rc, "attn32_forward")
+            lse.data_ptr())
     return out, lse
 
 
@@ -698,24 +723,19 @@ def attn32_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, se
     """msda_attn32_backward_f32: gradients of q, k, v (written into grad_q / grad_k / grad_v when given — views like the inputs,
     e.g. the two column blocks of one packed [L, N, 2E] tensor — else into new contiguous tensors).  bfloat16 q takes
     msda_attn32_backward_bf16: every tensor but lse bfloat16, gradients included."""
-    lib = _lib or load()
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
     dt = _attn_dtype(q)
-    with _DeviceGuard(q.device):
-        grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
-        grad_k = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_k is None else grad_k
-        grad_v = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_v is None else grad_v
-        if grad_out.stride(2) != 1:
-            grad_out = grad_out.contiguous()
-        views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
-        gov = _attn_view(grad_out, "grad_out", heads, dt)
-        gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
-        rc = _entry(lib, "msda_attn32_backward_bf16" if dt == torch.bfloat16 else "msda_attn32_backward_f32", [_VP, _LL, _LL] * 4 + [_VP] + [_VP, _LL, _LL] + [_CI] * 4 + [ctypes.c_float] * 2 + [_VP]
-                    + [_VP, _LL, _LL] * 3 + [_VP])(
-            *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p),
-            seed.data_ptr() if dropout_p > 0 else None, *gviews[0], *gviews[1], *gviews[2], _raw_stream(q.device))
-    if rc != 0:
-        _raise(lib, rc, "attn32_backward")
+    grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
+    grad_k = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_k is None else grad_k
+    grad_v = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_v is None else grad_v
+    if grad_out.stride(2) != 1:
+        grad_out = grad_out.contiguous()
+    views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
+    gov = _attn_view(grad_out, "grad_out", heads, dt)
+    gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
+    _launch(q.device, "msda_attn32_backward_bf16" if dt == torch.bfloat16 else "msda_attn32_backward_f32", "attn32_backward",
+            *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale),
+            float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *gviews[0], *gviews[1], *gviews[2])
     return grad_q, grad_k, grad_v
 
 
@@ -739,18 +759,14 @@ def add_layernorm_bf16res_supported(x, residual, weight, bias):
 
 def add_layernorm_forward_bf16res(x, residual, weight, bias, eps):
     """(y, mean, rstd) = LayerNorm(x + residual) for fp32 x and bfloat16 residual — msda_add_layernorm_forward_f32_bf16res."""
-    lib = _lib or load()
     d = x.shape[-1]
     rows = x.numel() // d
-    with _DeviceGuard(x.device):
-        y = torch.empty_like(x)
-        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = _entry(lib, "msda_add_layernorm_forward_f32_bf16res", [_VP] * 4 + [_LL, _CI, ctypes.c_float] + [_VP] * 4)(
-            x.data_ptr(), residual.data_ptr(), weight.data_ptr(), bias.data_ptr(), rows, d, float(eps), y.data_ptr(),
-            mean.data_ptr(), rstd.data_ptr(), _raw_stream(x.device))
-    if rc != 0:
-        _raise(lib, rc, "add_layernorm_forward_bf16res")
+    y = torch.empty_like(x)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _launch(x.device, "msda_add_layernorm_forward_f32_bf16res", "add_layernorm_forward_bf16res", x.data_ptr(),
+            residual.data_ptr(), weight.data_ptr(), bias.data_ptr(), rows, d, float(eps), y.data_ptr(), mean.data_ptr(),
+            rstd.data_ptr())
     return y, mean, rstd
 
 
@@ -759,35 +775,28 @@ def add_layernorm_backward_bf16res(grad_y, x, residual, weight, mean, rstd):
     lib = _lib or load()
     d = x.shape[-1]
     rows = x.numel() // d
-    with _DeviceGuard(x.device):
-        gx = torch.empty_like(x)
-        gr = torch.empty_like(residual)
-        gw = torch.empty((d,), dtype=torch.float32, device=x.device)
-        gb = torch.empty((d,), dtype=torch.float32, device=x.device)
-        nbytes = max(16, int(lib.msda_add_layernorm_workspace_bytes(rows, d)))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        rc = _entry(lib, "msda_add_layernorm_backward_f32_bf16res", [_VP] * 6 + [_LL, _CI] + [_VP] * 6)(
-            grad_y.data_ptr(), x.data_ptr(), residual.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, d,
-            gx.data_ptr(), gr.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), _raw_stream(x.device))
-    if rc != 0:
-        _raise(lib, rc, "add_layernorm_backward_bf16res")
+    gx = torch.empty_like(x)
+    gr = torch.empty_like(residual)
+    gw = torch.empty((d,), dtype=torch.float32, device=x.device)
+    gb = torch.empty((d,), dtype=torch.float32, device=x.device)
+    nbytes = max(16, int(lib.msda_add_layernorm_workspace_bytes(rows, d)))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    _launch(x.device, "msda_add_layernorm_backward_f32_bf16res", "add_layernorm_backward_bf16res", grad_y.data_ptr(),
+            x.data_ptr(), residual.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, d, gx.data_ptr(),
+            gr.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr())
     return gx, gr, gw, gb
 
 
 def add_layernorm_forward(x, residual, weight, bias, eps):
     """(y, mean, rstd) = LayerNorm(x + residual) — msda_add_layernorm_forward_f32 (include/msda.h)."""
-    lib = _lib or load()
     d = x.shape[-1]
     rows = x.numel() // d
-    with _DeviceGuard(x.device):
-        y = torch.empty_like(x)
-        mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = _entry(lib, "msda_add_layernorm_forward_f32", [_VP] * 4 + [_LL, _CI, ctypes.c_float] + [_VP] * 4)(
-            x.data_ptr(), residual.data_ptr() if residual is not None else None, weight.data_ptr(), bias.data_ptr(), rows, d,
-            float(eps), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _raw_stream(x.device))
-    if rc != 0:
-        _raise(lib, rc, "add_layernorm_forward")
+    y = torch.empty_like(x)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _launch(x.device, "msda_add_layernorm_forward_f32", "add_layernorm_forward", x.data_ptr(),
+            residual.data_ptr() if residual is not None else None, weight.data_ptr(), bias.data_ptr(), rows, d, float(eps),
+            y.data_ptr(), mean.data_ptr(), rstd.data_ptr())
     return y, mean, rstd
 
 
@@ -796,18 +805,14 @@ def add_layernorm_backward(grad_y, x, residual, weight, mean, rstd):
     lib = _lib or load()
     d = x.shape[-1]
     rows = x.numel() // d
-    with _DeviceGuard(x.device):
-        gs = torch.empty_like(x)
-        gw = torch.empty((d,), dtype=torch.float32, device=x.device)
-        gb = torch.empty((d,), dtype=torch.float32, device=x.device)
-        nbytes = max(16, int(lib.msda_add_layernorm_workspace_bytes(rows, d)))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        rc = _entry(lib, "msda_add_layernorm_backward_f32", [_VP] * 6 + [_LL, _CI] + [_VP] * 5)(
-            grad_y.data_ptr(), x.data_ptr(), residual.data_ptr() if residual is not None else None, weight.data_ptr(),
-            mean.data_ptr(), rstd.data_ptr(), rows, d, gs.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(),
-            _raw_stream(x.device))
-    if rc != 0:
-        _raise(lib, rc, "add_layernorm_backward")
+    gs = torch.empty_like(x)
+    gw = torch.empty((d,), dtype=torch.float32, device=x.device)
+    gb = torch.empty((d,), dtype=torch.float32, device=x.device)
+    nbytes = max(16, int(lib.msda_add_layernorm_workspace_bytes(rows, d)))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    _launch(x.device, "msda_add_layernorm_backward_f32", "add_layernorm_backward", grad_y.data_ptr(), x.data_ptr(),
+            residual.data_ptr() if residual is not None else None, weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows,
+            d, gs.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr())
     return gs, gw, gb
 
 
@@ -834,19 +839,14 @@ def _level_arrays(tensors):
 
 def flatten_levels(srcs, poss, level_embed):
     """(src_flatten[N,S,C], lvl_pos_embed_flatten[N,S,C]) — msda_flatten_levels_f32 (include/msda.h)."""
-    lib = _lib or load()
     L, (N, C) = len(srcs), srcs[0].shape[:2]
     S = sum(t.shape[2] * t.shape[3] for t in srcs)
     sp, hs, ws = _level_arrays(srcs)
     pp, _, _ = _level_arrays(poss)
-    with _DeviceGuard(srcs[0].device):
-        src_flat = torch.empty((N, S, C), dtype=torch.float32, device=srcs[0].device)
-        pos_flat = torch.empty((N, S, C), dtype=torch.float32, device=srcs[0].device)
-        rc = _entry(lib, "msda_flatten_levels_f32", [_CI] + [_VP] * 5 + [_CI, _CI] + [_VP] * 3)(
-            L, sp, pp, level_embed.data_ptr(), hs, ws, N, C, src_flat.data_ptr(), pos_flat.data_ptr(),
-            _raw_stream(srcs[0].device))
-    if rc != 0:
-        _raise(lib, rc, "flatten_levels")
+    src_flat = torch.empty((N, S, C), dtype=torch.float32, device=srcs[0].device)
+    pos_flat = torch.empty((N, S, C), dtype=torch.float32, device=srcs[0].device)
+    _launch(srcs[0].device, "msda_flatten_levels_f32", "flatten_levels", L, sp, pp, level_embed.data_ptr(), hs, ws, N, C,
+            src_flat.data_ptr(), pos_flat.data_ptr())
     return src_flat, pos_flat
 
 
@@ -857,24 +857,21 @@ def unflatten_levels(grad_src_flat, grad_pos_flat, shapes_nchw, want_level_embed
     ref = grad_src_flat if grad_src_flat is not None else grad_pos_flat
     N, S, C = ref.shape
     L = len(shapes_nchw)
-    with _DeviceGuard(ref.device):
-        gs = [torch.empty(sh, dtype=torch.float32, device=ref.device) for sh in shapes_nchw] if grad_src_flat is not None else None
-        gp = [torch.empty(sh, dtype=torch.float32, device=ref.device) for sh in shapes_nchw] if grad_pos_flat is not None else None
-        hs = (ctypes.c_int * L)(*[sh[2] for sh in shapes_nchw])
-        ws_ = (ctypes.c_int * L)(*[sh[3] for sh in shapes_nchw])
-        sp = _level_arrays(gs)[0] if gs is not None else None
-        pp = _level_arrays(gp)[0] if gp is not None else None
-        gembed = ws = None
-        if want_level_embed and grad_pos_flat is not None:
-            gembed = torch.empty((L, C), dtype=torch.float32, device=ref.device)
-            nbytes = max(16, int(lib.msda_unflatten_workspace_bytes(L, hs, ws_, N, C)))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=ref.device)
-        rc = _entry(lib, "msda_unflatten_levels_f32", [_CI] + [_VP] * 4 + [_CI, _CI] + [_VP] * 5)(
-            L, sp, pp, hs, ws_, N, C, grad_src_flat.data_ptr() if grad_src_flat is not None else None,
+    gs = [torch.empty(sh, dtype=torch.float32, device=ref.device) for sh in shapes_nchw] if grad_src_flat is not None else None
+    gp = [torch.empty(sh, dtype=torch.float32, device=ref.device) for sh in shapes_nchw] if grad_pos_flat is not None else None
+    hs = (ctypes.c_int * L)(*[sh[2] for sh in shapes_nchw])
+    ws_ = (ctypes.c_int * L)(*[sh[3] for sh in shapes_nchw])
+    sp = _level_arrays(gs)[0] if gs is not None else None
+    pp = _level_arrays(gp)[0] if gp is not None else None
+    gembed = ws = None
+    if want_level_embed and grad_pos_flat is not None:
+        gembed = torch.empty((L, C), dtype=torch.float32, device=ref.device)
+        nbytes = max(16, int(lib.msda_unflatten_workspace_bytes(L, hs, ws_, N, C)))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=ref.device)
+    _launch(ref.device, "msda_unflatten_levels_f32", "unflatten_levels", L, sp, pp, hs, ws_, N, C,
+            grad_src_flat.data_ptr() if grad_src_flat is not None else None,
             grad_pos_flat.data_ptr() if grad_pos_flat is not None else None,
-            gembed.data_ptr() if gembed is not None else None, ws.data_ptr() if ws is not None else None, _raw_stream(ref.device))
-    if rc != 0:
-        _raise(lib, rc, "unflatten_levels")
+            gembed.data_ptr() if gembed is not None else None, ws.data_ptr() if ws is not None else None)
     return gs, gp, gembed
 
 
@@ -883,8 +880,7 @@ PATH_GENERIC, PATH_D32 = 0, 1          # MSDA_PATH_* (include/msda.h)
 
 def path_for(elem_bytes, M, D, L, P):
     with _ForcedPathScope(load()):
-        return int(load().msda_path_for(ctypes.c_int(elem_bytes), ctypes.c_int(M), ctypes.c_int(D),
-                                        ctypes.c_int(L), ctypes.c_int(P)))
+        return int(load().msda_path_for(elem_bytes, M, D, L, P))
 
 
 def describe_plan(N, S, M, D, L, Lq, P, row_bytes=4, grad_value_bytes=None, prologue=False, deterministic=False,
@@ -907,7 +903,7 @@ def probe_row_gather(table_bytes, device, row_bytes=128, blocks=4096, iters=16, 
     table = torch.ones((max(int(table_bytes), row_bytes) // 4,), dtype=torch.float32, device=device)
     sink = torch.zeros((1,), dtype=torch.float32, device=device)
     rows = ctypes.c_ulonglong(0)
-    fn = _entry(lib, "msda_probe_row_gather", [_VP, ctypes.c_ulonglong, _CI, _CI, _CI, _VP, ctypes.POINTER(ctypes.c_ulonglong), _VP])
+    fn = lib.msda_probe_row_gather
     with _DeviceGuard(device):
         stream = torch.cuda.current_stream(device)
         call = lambda: fn(table.data_ptr(), table.numel() * 4, row_bytes, blocks, iters, sink.data_ptr(), ctypes.byref(rows),
@@ -944,10 +940,15 @@ def _f32_cuda(t):
     return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
 
 
+def _check_f32(what, dev, tensors):
+    """Every tensor (None entries skipped) contiguous fp32 on `dev`."""
+    if not all(t is None or (_f32_cuda(t) and t.device == dev) for t in tensors):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+
+
 def two_stage_proposals(memory, padding_mask, level_hw, learnedxy=None):
     """(proposals [N,S,42], memory_out [N,S,C], row_mask [N,S] bool) — msda_two_stage_proposals_f32: the forward of
     gen_encoder_output_proposals with `level_hw` the levels' (H, W) as Python ints."""
-    lib = _lib or load()
     if not (_f32_cuda(memory) and memory.dim() == 3 and padding_mask.dtype == torch.bool and padding_mask.is_contiguous()
             and padding_mask.device == memory.device and tuple(padding_mask.shape) == tuple(memory.shape[:2])
             and (learnedxy is None or (_f32_cuda(learnedxy) and learnedxy.numel() == 40 and learnedxy.device == memory.device))):
@@ -956,16 +957,12 @@ def two_stage_proposals(memory, padding_mask, level_hw, learnedxy=None):
     L = len(level_hw)
     hs = (ctypes.c_int * max(1, L))(*[int(h) for h, _ in level_hw])
     ws = (ctypes.c_int * max(1, L))(*[int(w) for _, w in level_hw])
-    with _DeviceGuard(memory.device):
-        props = torch.empty((N, S, 42), dtype=torch.float32, device=memory.device)
-        mem_out = torch.empty_like(memory)
-        row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
-        rc = _entry(lib, "msda_two_stage_proposals_f32", [_VP, _VP, _CI, _CI, _CI, _CI, _VP, _VP, _VP, _VP, _VP, _VP, _VP])(
-            memory.data_ptr(), padding_mask.data_ptr(), N, S, C, L, ctypes.cast(hs, _VP), ctypes.cast(ws, _VP),
-            learnedxy.data_ptr() if learnedxy is not None else None, props.data_ptr(), mem_out.data_ptr(), row_mask.data_ptr(),
-            _raw_stream(memory.device))
-    if rc != 0:
-        _raise(lib, rc, "two_stage_proposals")
+    props = torch.empty((N, S, 42), dtype=torch.float32, device=memory.device)
+    mem_out = torch.empty_like(memory)
+    row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
+    _launch(memory.device, "msda_two_stage_proposals_f32", "two_stage_proposals", memory.data_ptr(), padding_mask.data_ptr(),
+            N, S, C, L, ctypes.cast(hs, _VP), ctypes.cast(ws, _VP), learnedxy.data_ptr() if learnedxy is not None else None,
+            props.data_ptr(), mem_out.data_ptr(), row_mask.data_ptr())
     return props, mem_out, row_mask
 
 
@@ -977,7 +974,6 @@ def two_stage_select_supported(S, K, Q):
 def two_stage_select(cls, hand, obj, proposals, num_queries, hand_classes=(12, 13)):
     """(topk [N,Q] int64, refpoint_unsig [N,Q,42], reference_points [N,Q,42]) — msda_two_stage_select_f32: one launch, no
     host synchronisation.  Raises RuntimeError when Q exceeds the rows per frame (as torch.topk does)."""
-    lib = _lib or load()
     ts = (cls, hand, obj, proposals)
     if not (all(_f32_cuda(t) and t.dim() == 3 and t.device == cls.device for t in ts)
             and all(tuple(t.shape) == tuple(cls.shape[:2]) + (42,) for t in ts[1:])):
@@ -986,15 +982,12 @@ def two_stage_select(cls, hand, obj, proposals, num_queries, hand_classes=(12, 1
     Q = int(num_queries)
     if Q > S:
         raise RuntimeError("selected index k out of range")
-    with _DeviceGuard(cls.device):
-        topk = torch.empty((N, Q), dtype=torch.int64, device=cls.device)
-        unsig = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
-        refp = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
-        rc = _entry(lib, "msda_two_stage_select_f32", [_VP] * 4 + [_CI] * 6 + [_VP] * 4)(
-            cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), proposals.data_ptr(), N, S, K, Q, int(hand_classes[0]),
-            int(hand_classes[1]), topk.data_ptr(), unsig.data_ptr(), refp.data_ptr(), _raw_stream(cls.device))
-    if rc != 0:
-        _raise(lib, rc, "two_stage_select")
+    topk = torch.empty((N, Q), dtype=torch.int64, device=cls.device)
+    unsig = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
+    refp = torch.empty((N, Q, 42), dtype=torch.float32, device=cls.device)
+    _launch(cls.device, "msda_two_stage_select_f32", "two_stage_select", cls.data_ptr(), hand.data_ptr(), obj.data_ptr(),
+            proposals.data_ptr(), N, S, K, Q, int(hand_classes[0]), int(hand_classes[1]), topk.data_ptr(), unsig.data_ptr(),
+            refp.data_ptr())
     return topk, unsig, refp
 
 
@@ -1006,32 +999,23 @@ def _check_pe_inputs(r2, dim_t):
 
 def proposal_pos_embed(r2, dim_t):
     """PE [M, 5376] of refpoint_unsig [M, 42] — msda_proposal_pos_embed_f32 (dim_t: torch's table at even indices)."""
-    lib = _lib or load()
     _check_pe_inputs(r2, dim_t)
-    with _DeviceGuard(r2.device):
-        pe = torch.empty((r2.shape[0], PE_WIDTH), dtype=torch.float32, device=r2.device)
-        rc = _entry(lib, "msda_proposal_pos_embed_f32", [_VP, _VP, _LL, _VP, _VP])(
-            r2.data_ptr(), dim_t.data_ptr(), r2.shape[0], pe.data_ptr(), _raw_stream(r2.device))
-    if rc != 0:
-        _raise(lib, rc, "proposal_pos_embed")
+    pe = torch.empty((r2.shape[0], PE_WIDTH), dtype=torch.float32, device=r2.device)
+    _launch(r2.device, "msda_proposal_pos_embed_f32", "proposal_pos_embed", r2.data_ptr(), dim_t.data_ptr(), r2.shape[0],
+            pe.data_ptr())
     return pe
 
 
 def proposal_pos_linear_relu(r2, dim_t, weight, bias):
     """relu(PE(r2) @ weight^T + bias) [M, out] without the PE table in memory — msda_proposal_pos_linear_relu_f32."""
-    lib = _lib or load()
     _check_pe_inputs(r2, dim_t)
     if not (_f32_cuda(weight) and weight.dim() == 2 and weight.shape[1] == PE_WIDTH and weight.shape[0] % 4 == 0
             and weight.device == r2.device and weight.data_ptr() % 16 == 0
             and (bias is None or (_f32_cuda(bias) and bias.numel() == weight.shape[0] and bias.device == r2.device))):
         raise RuntimeError("proposal_pos_linear_relu: expected contiguous fp32 CUDA weight [out, 5376] (out % 4 == 0) and bias [out]")
-    with _DeviceGuard(r2.device):
-        y = torch.empty((r2.shape[0], weight.shape[0]), dtype=torch.float32, device=r2.device)
-        rc = _entry(lib, "msda_proposal_pos_linear_relu_f32", [_VP, _VP, _VP, _VP, _LL, _CI, _VP, _VP])(
-            r2.data_ptr(), dim_t.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None, r2.shape[0],
-            weight.shape[0], y.data_ptr(), _raw_stream(r2.device))
-    if rc != 0:
-        _raise(lib, rc, "proposal_pos_linear_relu")
+    y = torch.empty((r2.shape[0], weight.shape[0]), dtype=torch.float32, device=r2.device)
+    _launch(r2.device, "msda_proposal_pos_linear_relu_f32", "proposal_pos_linear_relu", r2.data_ptr(), dim_t.data_ptr(),
+            weight.data_ptr(), bias.data_ptr() if bias is not None else None, r2.shape[0], weight.shape[0], y.data_ptr())
     return y
 
 
@@ -1039,7 +1023,6 @@ def proposal_pos_linear_relu(r2, dim_t, weight, bias):
 def assembly_refine(reference_points, cls, keypoints):
     """next reference_points [..., 42] — msda_assembly_refine_f32: reference_points [..., 2 | 42], the layer's class logits
     [..., K] and keypoint head output [..., 63], all contiguous fp32 CUDA with the same leading shape.  One launch."""
-    lib = _lib or load()
     lead = tuple(reference_points.shape[:-1])
     if not (all(_f32_cuda(t) and t.device == reference_points.device for t in (reference_points, cls, keypoints))
             and reference_points.shape[-1] in (2, 42) and tuple(cls.shape[:-1]) == lead
@@ -1047,13 +1030,9 @@ def assembly_refine(reference_points, cls, keypoints):
         raise RuntimeError("assembly_refine: expected contiguous fp32 CUDA reference_points [..., 2|42], cls [..., K] and "
                            "keypoints [..., 63] with the same leading shape")
     M = reference_points.numel() // reference_points.shape[-1]
-    with _DeviceGuard(reference_points.device):
-        out = torch.empty(lead + (42,), dtype=torch.float32, device=reference_points.device)
-        rc = _entry(lib, "msda_assembly_refine_f32", [_VP, _CI, _VP, _CI, _VP, _LL, _VP, _VP])(
-            reference_points.data_ptr(), reference_points.shape[-1], cls.data_ptr(), cls.shape[-1], keypoints.data_ptr(), M,
-            out.data_ptr(), _raw_stream(reference_points.device))
-    if rc != 0:
-        _raise(lib, rc, "assembly_refine")
+    out = torch.empty(lead + (42,), dtype=torch.float32, device=reference_points.device)
+    _launch(reference_points.device, "msda_assembly_refine_f32", "assembly_refine", reference_points.data_ptr(),
+            reference_points.shape[-1], cls.data_ptr(), cls.shape[-1], keypoints.data_ptr(), M, out.data_ptr())
     return out
 
 
@@ -1061,7 +1040,6 @@ def assembly_proposals(memory, padding_mask, hw):
     """(proposals [N,H*W,2], memory_out [N,H*W,C], row_mask [N,H*W] bool) — msda_assembly_proposals_f32 for one level of
     hw = (H, W) rows: memory [N, H*W, C] fp32 and padding_mask [N, H*W] bool may be slices of the full flattened tensors
     (rows contiguous inside a frame, any frame stride)."""
-    lib = _lib or load()
     H, W = int(hw[0]), int(hw[1])
     if not (memory.is_cuda and memory.dtype == torch.float32 and memory.dim() == 3 and memory.shape[1] == H * W
             and memory.stride(2) == 1 and memory.stride(1) == memory.shape[2] and padding_mask.dtype == torch.bool
@@ -1069,22 +1047,18 @@ def assembly_proposals(memory, padding_mask, hw):
             and padding_mask.stride(1) == 1):
         raise RuntimeError("assembly_proposals: expected fp32 CUDA memory [N,H*W,C] and a bool mask [N,H*W], rows contiguous")
     N, S, C = memory.shape
-    with _DeviceGuard(memory.device):
-        props = torch.empty((N, S, 2), dtype=torch.float32, device=memory.device)
-        mem_out = torch.empty((N, S, C), dtype=torch.float32, device=memory.device)
-        row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
-        rc = _entry(lib, "msda_assembly_proposals_f32", [_VP, _LL, _VP, _LL, _CI, _CI, _CI, _CI, _VP, _VP, _VP, _VP])(
-            memory.data_ptr(), memory.stride(0), padding_mask.data_ptr(), padding_mask.stride(0), N, H, W, C, props.data_ptr(),
-            mem_out.data_ptr(), row_mask.data_ptr(), _raw_stream(memory.device))
-    if rc != 0:
-        _raise(lib, rc, "assembly_proposals")
+    props = torch.empty((N, S, 2), dtype=torch.float32, device=memory.device)
+    mem_out = torch.empty((N, S, C), dtype=torch.float32, device=memory.device)
+    row_mask = torch.empty((N, S), dtype=torch.bool, device=memory.device)
+    _launch(memory.device, "msda_assembly_proposals_f32", "assembly_proposals", memory.data_ptr(), memory.stride(0),
+            padding_mask.data_ptr(), padding_mask.stride(0), N, H, W, C, props.data_ptr(), mem_out.data_ptr(),
+            row_mask.data_ptr())
     return props, mem_out, row_mask
 
 
 def assembly_select(cls, hand, obj, obj_classes=(1, 8), left=9, right=10):
     """(indices [N,3] int64 (left, right, object), reference_points [N,3,2]) — msda_assembly_select_f32: one launch, no host
     synchronisation.  Raises IndexError when a class index is not below K, as the reference's column indexing does."""
-    lib = _lib or load()
     ts = (cls, hand, obj)
     if not (all(_f32_cuda(t) and t.dim() == 3 and t.device == cls.device for t in ts)
             and all(tuple(t.shape) == tuple(cls.shape[:2]) + (63,) for t in ts[1:])):
@@ -1093,14 +1067,10 @@ def assembly_select(cls, hand, obj, obj_classes=(1, 8), left=9, right=10):
     top = max(int(obj_classes[1]), int(left), int(right))
     if top >= K:
         raise IndexError("index %d is out of bounds for dimension 2 with size %d" % (top, K))
-    with _DeviceGuard(cls.device):
-        idx = torch.empty((N, 3), dtype=torch.int64, device=cls.device)
-        refp = torch.empty((N, 3, 2), dtype=torch.float32, device=cls.device)
-        rc = _entry(lib, "msda_assembly_select_f32", [_VP] * 3 + [_CI] * 7 + [_VP] * 3)(
-            cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), N, S, K, int(obj_classes[0]), int(obj_classes[1]), int(left),
-            int(right), idx.data_ptr(), refp.data_ptr(), _raw_stream(cls.device))
-    if rc != 0:
-        _raise(lib, rc, "assembly_select")
+    idx = torch.empty((N, 3), dtype=torch.int64, device=cls.device)
+    refp = torch.empty((N, 3, 2), dtype=torch.float32, device=cls.device)
+    _launch(cls.device, "msda_assembly_select_f32", "assembly_select", cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), N, S,
+            K, int(obj_classes[0]), int(obj_classes[1]), int(left), int(right), idx.data_ptr(), refp.data_ptr())
     return idx, refp
 
 
@@ -1148,57 +1118,41 @@ def match_arctic(logits, hand, obj, labels, keypoints, offsets, is_valid, t_max,
     """The int64 result buffer of msda_match_arctic_f32 (include/msda.h): lists of per-set pred_logits [bs, Q, K] and (with
     target keypoints) pred_hand_key / pred_obj_key [bs, Q, D]; labels [n] / offsets [bs + 1] int64, keypoints [n, D] fp32 or
     None, is_valid [bs] int32 on the same device.  One launch, no host synchronisation."""
-    lib = _lib or load()
     heads = (hand, obj) if keypoints is not None else ()
     dev, (bs, Q, K), D = _match_checks("match_arctic", logits, heads, labels, keypoints, offsets, t_max)
     if not (is_valid.is_cuda and is_valid.dtype == torch.int32 and is_valid.is_contiguous() and tuple(is_valid.shape) == (bs,)
             and is_valid.device == dev):
         raise RuntimeError("match_arctic: expected int32 CUDA is_valid [bs]")
     sets = len(logits)
-    with _DeviceGuard(dev):
-        out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
-        rc = _entry(lib, "msda_match_arctic_f32", [_VP, _VP, _VP] + [_CI] * 5 + [_VP, _VP, _VP, _LL, _VP, _CI,
-                                                                               ctypes.c_float, ctypes.c_float, _VP, _VP, _VP])(
-            _ptr_array(logits), _ptr_array(hand) if heads else None, _ptr_array(obj) if heads else None, sets, bs, Q, K, D,
-            labels.data_ptr(), keypoints.data_ptr() if keypoints is not None else None, offsets.data_ptr(), labels.shape[0],
+    out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
+    _launch(dev, "msda_match_arctic_f32", "match_arctic", _ptr_array(logits), _ptr_array(hand) if heads else None,
+            _ptr_array(obj) if heads else None, sets, bs, Q, K, D, labels.data_ptr(),
+            keypoints.data_ptr() if keypoints is not None else None, offsets.data_ptr(), labels.shape[0],
             is_valid.data_ptr(), int(t_max), float(cost_class), float(cost_keypoint), out.data_ptr(),
-            cost_debug.data_ptr() if cost_debug is not None else None, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "match_arctic")
+            cost_debug.data_ptr() if cost_debug is not None else None)
     return out
 
 
 def match_assembly(logits, pred_keypoints, labels, keypoints, offsets, t_max, cost_class, cost_keypoint, cost_debug=None):
     """The int64 result buffer of msda_match_assembly_f32: as match_arctic with one keypoint head per set and no is_valid."""
-    lib = _lib or load()
     dev, (bs, Q, K), D = _match_checks("match_assembly", logits, (pred_keypoints,), labels, keypoints, offsets, t_max)
     sets = len(logits)
-    with _DeviceGuard(dev):
-        out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
-        rc = _entry(lib, "msda_match_assembly_f32", [_VP, _VP] + [_CI] * 5 + [_VP, _VP, _VP, _LL, _CI, ctypes.c_float,
-                                                                           ctypes.c_float, _VP, _VP, _VP])(
-            _ptr_array(logits), _ptr_array(pred_keypoints), sets, bs, Q, K, D, labels.data_ptr(), keypoints.data_ptr(),
-            offsets.data_ptr(), labels.shape[0], int(t_max), float(cost_class), float(cost_keypoint), out.data_ptr(),
-            cost_debug.data_ptr() if cost_debug is not None else None, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "match_assembly")
+    out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
+    _launch(dev, "msda_match_assembly_f32", "match_assembly", _ptr_array(logits), _ptr_array(pred_keypoints), sets, bs, Q, K,
+            D, labels.data_ptr(), keypoints.data_ptr(), offsets.data_ptr(), labels.shape[0], int(t_max), float(cost_class),
+            float(cost_keypoint), out.data_ptr(), cost_debug.data_ptr() if cost_debug is not None else None)
     return out
 
 
 def lsap(cost):
     """(query_idx [B, W], target_idx [B, W], count [B], status [B]) int64 — msda_lsap_f32: scipy's linear_sum_assignment of
     each [Q, T] block of a contiguous fp32 CUDA cost [B, Q, T] (min(Q, T) <= 16, max(Q, T) <= 1024), W = min(Q, T)."""
-    lib = _lib or load()
     if not (_f32_cuda(cost) and cost.dim() == 3):
         raise RuntimeError("lsap: expected a contiguous fp32 CUDA cost [B, Q, T]")
     B, Q, T = cost.shape
     W = min(Q, T)
-    with _DeviceGuard(cost.device):
-        out = torch.empty(2 * B * W + 2 * B, dtype=torch.int64, device=cost.device)
-        rc = _entry(lib, "msda_lsap_f32", [_VP, _CI, _CI, _CI, _VP, _VP])(cost.data_ptr(), B, Q, T, out.data_ptr(),
-                                                                          _raw_stream(cost.device))
-    if rc != 0:
-        _raise(lib, rc, "lsap")
+    out = torch.empty(2 * B * W + 2 * B, dtype=torch.int64, device=cost.device)
+    _launch(cost.device, "msda_lsap_f32", "lsap", cost.data_ptr(), B, Q, T, out.data_ptr())
     return (out[:B * W].view(B, W), out[B * W:2 * B * W].view(B, W), out[2 * B * W:2 * B * W + B],
             out[2 * B * W + B:])
 
@@ -1207,7 +1161,6 @@ def lsap(cost):
 CRIT_ARCTIC, CRIT_ASSEMBLY = 0, 1
 CRIT_TERMS = 4
 CRIT_BAD_LABEL, CRIT_BAD_TARGETS, CRIT_MASK_MISMATCH, CRIT_MATCH_STATUS = 1, 2, 4, 8
-_CRIT_ARGS = [_CI, _VP, _VP, _VP] + [_CI] * 5 + [_VP, _CI, _VP, _VP, _VP, _LL, _VP, _VP, ctypes.c_ulonglong, _VP, ctypes.c_float]
 
 
 def _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
@@ -1242,37 +1195,27 @@ def criterion_fwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
                   num_boxes, focal_alpha):
     """(losses fp32 [sets, 4], stats int32 [sets, 4]) — msda_criterion_fwd_f32 (include/msda.h).  One launch, no host
     synchronisation."""
-    lib = _lib or load()
     args, (dev, sets, *_rest) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
                                             joint_valid, hand_mask, num_boxes, focal_alpha)
-    with _DeviceGuard(dev):
-        losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
-        stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
-        rc = _entry(lib, "msda_criterion_fwd_f32", _CRIT_ARGS + [_VP, _VP, _VP])(
-            *args, losses.data_ptr(), stats.data_ptr(), _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "criterion_fwd")
+    losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
+    stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
+    _launch(dev, "msda_criterion_fwd_f32", "criterion_fwd", *args, losses.data_ptr(), stats.data_ptr())
     return losses, stats
 
 
 def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
                   num_boxes, focal_alpha, grad_losses, stats):
     """(grad_logits, grad_hand, grad_obj) lists, every element written — msda_criterion_bwd_f32.  One launch."""
-    lib = _lib or load()
     args, (dev, sets, bs, Q, K, D) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
                                                   joint_valid, hand_mask, num_boxes, focal_alpha)
     if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
             and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
         raise RuntimeError("criterion_bwd: expected fp32 grad_losses and int32 stats [%d, 4]" % sets)
-    with _DeviceGuard(dev):
-        g_logits = [torch.empty(bs, Q, K, dtype=torch.float32, device=dev) for _ in range(sets)]
-        g_hand = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D else []
-        g_obj = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D and kind == CRIT_ARCTIC else []
-        rc = _entry(lib, "msda_criterion_bwd_f32", _CRIT_ARGS + [_VP, _VP, _VP, _VP, _VP, _VP])(
-            *args, grad_losses.data_ptr(), stats.data_ptr(), _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None,
-            _ptr_array(g_obj) if g_obj else None, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "criterion_bwd")
+    g_logits = [torch.empty(bs, Q, K, dtype=torch.float32, device=dev) for _ in range(sets)]
+    g_hand = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D else []
+    g_obj = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D and kind == CRIT_ARCTIC else []
+    _launch(dev, "msda_criterion_bwd_f32", "criterion_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
+            _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None, _ptr_array(g_obj) if g_obj else None)
     return g_logits, g_hand, g_obj
 
 
@@ -1280,7 +1223,6 @@ def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
 HEADS_ARCTIC, HEADS_ASSEMBLY = 0, 1
 HEADS_SHARED_CLS, HEADS_SHARED_MLP = 1, 2
 HEADS_SHARED_WIDTHS = (48, 10, 3, 3, 3, 1)
-_HEADS_ARGS = [_CI, _CI, _LL, _CI, _CI, _CI, _CI, ctypes.c_uint] + [_VP] * 9
 
 
 def heads_supported(C):
@@ -1304,8 +1246,7 @@ def _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
     R = init_ref.shape[-1] if init_ref is not None else 0
     tensors = [hs] + list(cls[0]) + list(cls[1]) + list(mlp[0]) + list(mlp[1]) + list(shared[0]) + list(shared[1])
     tensors += [t for t in (init_ref, inter_ref) if t is not None]
-    if not all(_f32_cuda(t) and t.device == hs.device for t in tensors):
-        raise RuntimeError("detr_heads: expected contiguous fp32 CUDA tensors on one device")
+    _check_f32("detr_heads", hs.device, tensors)
     return [int(kind), int(L), int(M), int(C), int(K), int(n_mlp), int(R), int(flags), hs.data_ptr(),
             init_ref.data_ptr() if init_ref is not None else None, inter_ref.data_ptr() if inter_ref is not None else None,
             _ptr_array(cls[0]), _ptr_array(cls[1]), _ptrs_or_none(mlp[0]), _ptrs_or_none(mlp[1]), _ptrs_or_none(shared[0]),
@@ -1315,52 +1256,41 @@ def _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
 def heads_forward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
     """msda_heads_forward_f32: (logits [L, M, K], kp outputs [L, M, D] per MLP head, shared outputs [L, M, n_g],
     hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D]).  At most 3 launches, no host synchronisation."""
-    lib = _lib or load()
     args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
     D = 42 if kind == HEADS_ARCTIC else 63
     dev = hs.device
-    with _DeviceGuard(dev):
-        logits = torch.empty(L, M, K, dtype=torch.float32, device=dev)
-        kp = [torch.empty(L, M, D, dtype=torch.float32, device=dev) for _ in range(n_mlp)]
-        sh = [torch.empty(L, M, n, dtype=torch.float32, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
-        hidden = torch.empty(n_mlp, 2, L, M, C, dtype=torch.float32, device=dev)
-        sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
-        rc = _entry(lib, "msda_heads_forward_f32", _HEADS_ARGS + [_VP] * 6)(
-            *args, logits.data_ptr(), _ptrs_or_none(kp), _ptrs_or_none(sh), hidden.data_ptr() if n_mlp else None,
-            sig.data_ptr() if n_mlp else None, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "heads_forward")
+    logits = torch.empty(L, M, K, dtype=torch.float32, device=dev)
+    kp = [torch.empty(L, M, D, dtype=torch.float32, device=dev) for _ in range(n_mlp)]
+    sh = [torch.empty(L, M, n, dtype=torch.float32, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
+    hidden = torch.empty(n_mlp, 2, L, M, C, dtype=torch.float32, device=dev)
+    sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
+    _launch(dev, "msda_heads_forward_f32", "heads_forward", *args, logits.data_ptr(), _ptrs_or_none(kp), _ptrs_or_none(sh),
+            hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None)
     return logits, kp, sh, hidden, sig
 
 
 def heads_backward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
     """msda_heads_backward_f32: (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases),
     every element written.  At most 5 launches, no host synchronisation."""
-    lib = _lib or load()
     args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
     grads = [grad_logits] + list(grad_kp) + list(grad_shared)
     if not all(_f32_cuda(t) and t.device == hs.device for t in grads):
         raise RuntimeError("detr_heads: expected contiguous fp32 CUDA output gradients")
     dev = hs.device
-    with _DeviceGuard(dev):
-        ws = torch.empty(max(1, heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags) // 4), dtype=torch.float32, device=dev)
-        grad_hs = torch.empty_like(hs)
-        g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
-        g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
-        g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
-        rc = _entry(lib, "msda_heads_backward_f32", _HEADS_ARGS + [_VP] * 13 + [ctypes.c_ulonglong, _VP])(
-            *args, hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(),
-            _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared), grad_hs.data_ptr(), _ptr_array(g_cls[0]),
-            _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]), _ptrs_or_none(g_sh[0]),
-            _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "heads_backward")
+    ws = torch.empty(max(1, heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags) // 4), dtype=torch.float32, device=dev)
+    grad_hs = torch.empty_like(hs)
+    g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
+    g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
+    g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
+    _launch(dev, "msda_heads_backward_f32", "heads_backward", *args, hidden.data_ptr() if n_mlp else None,
+            sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(), _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared),
+            grad_hs.data_ptr(), _ptr_array(g_cls[0]), _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]),
+            _ptrs_or_none(g_sh[0]), _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4)
     return grad_hs, g_cls, g_mlp, g_sh
 
 
 # ---- SmoothNet: MotionSmoother modules and get_arctic_item's selection (msda_smoother.hip, msda_arctic_item.hip) ----------
 SMOOTHER_MAX_MODULES, SMOOTHER_MAX_CALLS, SMOOTHER_MAX_CALLS_PER_MODULE = 6, 12, 4
-_SM_GEO = [_CI] * 7 + [_VP] * 3
 
 
 def smoother_supported(T, O, H, R, num_blocks):
@@ -1386,8 +1316,7 @@ def smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, which):
 
 def _smoother_check(what, xs, params, call_mod, call_C, T):
     dev = xs[0].device
-    if not all(_f32_cuda(t) and t.device == dev for t in list(xs) + list(params)):
-        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+    _check_f32(what, dev, list(xs) + list(params))
     if len(xs) != len(call_mod) or any(x.dim() != 2 or x.shape[1] != c or x.shape[0] % T for x, c in zip(xs, call_C)):
         raise RuntimeError("%s: every input must be [B * T, C]" % what)
     return dev
@@ -1396,7 +1325,6 @@ def _smoother_check(what, xs, params, call_mod, call_C, T):
 def smoother_forward(dims, n_mod, call_mod, xs, params, training=False, p=0.0, seed=None):
     """msda_smoother_forward_f32.  xs: per call [B * T, C]; params: every module's parameters in parameters() order.
     Returns (outputs [B * O, C] per call, the activation buffer the backward reads).  2 nb + 3 launches, no host sync."""
-    lib = _lib or load()
     T, O = dims[0], dims[1]
     call_C = [x.shape[1] for x in xs]
     call_B = [x.shape[0] // T if T else 0 for x in xs]
@@ -1404,22 +1332,17 @@ def smoother_forward(dims, n_mod, call_mod, xs, params, training=False, p=0.0, s
     geo = _smoother_geo(dims, n_mod, call_mod, call_B, call_C)
     if training and p > 0 and (seed is None or not seed.is_cuda or seed.dtype != torch.int64):
         raise RuntimeError("smoother_forward: training with p > 0 needs a one-element int64 CUDA seed")
-    with _DeviceGuard(dev):
-        nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 0)
-        act = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        outs = [torch.empty(b * O, c, dtype=torch.float32, device=dev) for b, c in zip(call_B, call_C)]
-        rc = _entry(lib, "msda_smoother_forward_f32", _SM_GEO + [_VP] * 4 + [ctypes.c_ulonglong, _CI, ctypes.c_float, _VP, _VP])(
-            *geo, _ptr_array(xs), _ptr_array(params), _ptr_array(outs), act.data_ptr(), act.numel() * 4, int(bool(training)),
-            float(p), seed.data_ptr() if seed is not None else None, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "smoother_forward")
+    nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 0)
+    act = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    outs = [torch.empty(b * O, c, dtype=torch.float32, device=dev) for b, c in zip(call_B, call_C)]
+    _launch(dev, "msda_smoother_forward_f32", "smoother_forward", *geo, _ptr_array(xs), _ptr_array(params), _ptr_array(outs),
+            act.data_ptr(), act.numel() * 4, int(bool(training)), float(p), seed.data_ptr() if seed is not None else None)
     return outs, act
 
 
 def smoother_backward(dims, n_mod, call_mod, xs, params, act, grad_outs, want_grad_x, training=False, p=0.0, seed=None):
     """msda_smoother_backward_f32: (input gradients per call — None where not wanted —, one flat buffer of every parameter's
     gradient in the order of `params`).  At most 2 nb + 5 launches, no host sync."""
-    lib = _lib or load()
     T = dims[0]
     call_C = [x.shape[1] for x in xs]
     call_B = [x.shape[0] // T for x in xs]
@@ -1427,34 +1350,25 @@ def smoother_backward(dims, n_mod, call_mod, xs, params, act, grad_outs, want_gr
     if not all(_f32_cuda(g) and g.device == dev for g in grad_outs):
         raise RuntimeError("smoother_backward: expected contiguous fp32 CUDA output gradients")
     geo = _smoother_geo(dims, n_mod, call_mod, call_B, call_C)
-    with _DeviceGuard(dev):
-        nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 1)
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        gp = torch.empty(sum(t.numel() for t in params), dtype=torch.float32, device=dev)
-        gx = [torch.empty_like(x) if w else None for x, w in zip(xs, want_grad_x)]
-        gx_arr = (_VP * len(gx))(*[g.data_ptr() if g is not None else None for g in gx]) if any(want_grad_x) else None
-        rc = _entry(lib, "msda_smoother_backward_f32", _SM_GEO + [_VP, _VP, _VP, ctypes.c_ulonglong, _VP, _VP, _VP, _CI,
-                                                                   ctypes.c_float, _VP, _VP, ctypes.c_ulonglong, _VP])(
-            *geo, _ptr_array(xs), _ptr_array(params), act.data_ptr(), act.numel() * 4, _ptr_array(grad_outs), gx_arr,
-            gp.data_ptr(), int(bool(training)), float(p), seed.data_ptr() if seed is not None else None, ws.data_ptr(),
-            ws.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "smoother_backward")
+    nbytes = smoother_workspace_bytes(dims, n_mod, call_mod, call_B, call_C, 1)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    gp = torch.empty(sum(t.numel() for t in params), dtype=torch.float32, device=dev)
+    gx = [torch.empty_like(x) if w else None for x, w in zip(xs, want_grad_x)]
+    gx_arr = (_VP * len(gx))(*[g.data_ptr() if g is not None else None for g in gx]) if any(want_grad_x) else None
+    _launch(dev, "msda_smoother_backward_f32", "smoother_backward", *geo, _ptr_array(xs), _ptr_array(params), act.data_ptr(),
+            act.numel() * 4, _ptr_array(grad_outs), gx_arr, gp.data_ptr(), int(bool(training)), float(p),
+            seed.data_ptr() if seed is not None else None, ws.data_ptr(), ws.numel() * 4)
     return gx, gp
 
 
 def smoother_dropout_mask(seed, problem, layer, rows, cols, p):
     """msda_smoother_dropout_mask_f32 (tests): the kernels' keep mask (1 / 0) of (problem, layer) over [rows, cols]."""
-    lib = _lib or load()
     if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise RuntimeError("smoother_dropout_mask: seed must be a one-element int64 CUDA tensor")
     dev = seed.device
-    with _DeviceGuard(dev):
-        mask = torch.empty(rows, cols, dtype=torch.float32, device=dev)
-        rc = _entry(lib, "msda_smoother_dropout_mask_f32", [_VP, _CI, _CI, _CI, _CI, ctypes.c_float, _VP, _VP])(
-            seed.data_ptr(), int(problem), int(layer), int(rows), int(cols), float(p), mask.data_ptr(), _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "smoother_dropout_mask")
+    mask = torch.empty(rows, cols, dtype=torch.float32, device=dev)
+    _launch(dev, "msda_smoother_dropout_mask_f32", "smoother_dropout_mask", seed.data_ptr(), int(problem), int(layer),
+            int(rows), int(cols), float(p), mask.data_ptr())
     return mask
 
 
@@ -1464,40 +1378,29 @@ ARCTIC_ITEM_OUT_SOURCES = (0, 0, 1, 2, 2, 3, 3, 5, 4)  # root_l, root_r, root_o,
 
 def arctic_item_forward(logits, sources, obj_end, hand_l, hand_r):
     """msda_arctic_item_forward_f32: (nine gathered outputs, idx [bs, 3] int64: left, right, object).  One launch."""
-    lib = _lib or load()
     bs, Q, K = logits.shape
     dev = logits.device
-    if not all(_f32_cuda(t) and t.device == dev for t in [logits] + list(sources)):
-        raise RuntimeError("arctic_item: expected contiguous fp32 CUDA tensors on one device")
+    _check_f32("arctic_item", dev, [logits] + list(sources))
     if any(tuple(s.shape) != (bs, Q, w) for s, w in zip(sources, ARCTIC_ITEM_WIDTHS)):
         raise RuntimeError("arctic_item: sources must be [bs, Q, w] with w = %s" % (ARCTIC_ITEM_WIDTHS,))
-    with _DeviceGuard(dev):
-        outs = [torch.empty(bs, ARCTIC_ITEM_WIDTHS[s], dtype=torch.float32, device=dev) for s in ARCTIC_ITEM_OUT_SOURCES]
-        idx = torch.empty(bs, 3, dtype=torch.int64, device=dev)
-        rc = _entry(lib, "msda_arctic_item_forward_f32", [_CI] * 6 + [_VP] * 5)(
-            bs, Q, K, int(obj_end), int(hand_l), int(hand_r), logits.data_ptr(), _ptr_array(sources), _ptr_array(outs),
-            idx.data_ptr(), _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "arctic_item_forward")
+    outs = [torch.empty(bs, ARCTIC_ITEM_WIDTHS[s], dtype=torch.float32, device=dev) for s in ARCTIC_ITEM_OUT_SOURCES]
+    idx = torch.empty(bs, 3, dtype=torch.int64, device=dev)
+    _launch(dev, "msda_arctic_item_forward_f32", "arctic_item_forward", bs, Q, K, int(obj_end), int(hand_l), int(hand_r),
+            logits.data_ptr(), _ptr_array(sources), _ptr_array(outs), idx.data_ptr())
     return outs, idx
 
 
 def arctic_item_backward(idx, Q, grad_outs):
     """msda_arctic_item_backward_f32: the six source gradients [bs, Q, w], every element written.  One launch."""
-    lib = _lib or load()
     bs = idx.shape[0]
     dev = idx.device
     if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()):
         raise RuntimeError("arctic_item_backward: idx must be a contiguous int64 CUDA tensor")
     if not all(g is None or (_f32_cuda(g) and g.device == dev) for g in grad_outs):
         raise RuntimeError("arctic_item_backward: expected contiguous fp32 CUDA output gradients")
-    with _DeviceGuard(dev):
-        gsrc = [torch.empty(bs, Q, w, dtype=torch.float32, device=dev) for w in ARCTIC_ITEM_WIDTHS]
-        garr = (_VP * len(grad_outs))(*[g.data_ptr() if g is not None else None for g in grad_outs])
-        rc = _entry(lib, "msda_arctic_item_backward_f32", [_CI, _CI] + [_VP] * 4)(
-            bs, int(Q), idx.data_ptr(), garr, _ptr_array(gsrc), _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "arctic_item_backward")
+    gsrc = [torch.empty(bs, Q, w, dtype=torch.float32, device=dev) for w in ARCTIC_ITEM_WIDTHS]
+    garr = (_VP * len(grad_outs))(*[g.data_ptr() if g is not None else None for g in grad_outs])
+    _launch(dev, "msda_arctic_item_backward_f32", "arctic_item_backward", bs, int(Q), idx.data_ptr(), garr, _ptr_array(gsrc))
     return gsrc
 
 
@@ -1517,8 +1420,7 @@ def swin_attn_workspace_bytes(geo, which):
 
 def _swin_check(what, geo, tensors):
     dev = tensors[0].device
-    if not all(t is None or (_f32_cuda(t) and t.device == dev) for t in tensors):
-        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+    _check_f32(what, dev, tensors)
     B, H, W, C, nH, ws, _ = geo
     qkv, bias, table = tensors[:3]
     if tuple(qkv.shape) != (B * H * W, 3 * C) or (bias is not None and tuple(bias.shape) != (3 * C,)) \
@@ -1533,51 +1435,39 @@ def _vp(t):
 
 def swin_attn_forward(geo, qkv, bias, table):
     """msda_swin_attn_forward_f32: (out [B*H*W, C], lse).  One launch, no host sync."""
-    lib = _lib or load()
     geo = tuple(int(g) for g in geo)
     dev = _swin_check("swin_attn_forward", geo, [qkv, bias, table])
-    with _DeviceGuard(dev):
-        out = torch.empty(qkv.shape[0], geo[3], dtype=torch.float32, device=dev)
-        nbytes = swin_attn_workspace_bytes(geo, 0)
-        lse = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        rc = _entry(lib, "msda_swin_attn_forward_f32", [_CI] * 7 + [_VP] * 5 + [ctypes.c_ulonglong, _VP])(
-            *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(), out.data_ptr(), lse.data_ptr(), lse.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "swin_attn_forward")
+    out = torch.empty(qkv.shape[0], geo[3], dtype=torch.float32, device=dev)
+    nbytes = swin_attn_workspace_bytes(geo, 0)
+    lse = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    _launch(dev, "msda_swin_attn_forward_f32", "swin_attn_forward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
+            out.data_ptr(), lse.data_ptr(), lse.numel() * 4)
     return out, lse
 
 
 def swin_attn_backward(geo, qkv, bias, table, out, lse, grad_out):
     """msda_swin_attn_backward_f32: (grad_qkv [B*H*W, 3C], grad_table, grad_bias [3C] — the padded tokens' part, q part 0 —
     or None without a bias).  Three launches, no host sync."""
-    lib = _lib or load()
     geo = tuple(int(g) for g in geo)
     dev = _swin_check("swin_attn_backward", geo, [qkv, bias, table, out, lse, grad_out])
-    with _DeviceGuard(dev):
-        gq = torch.empty_like(qkv)
-        gt = torch.empty_like(table)
-        gb = torch.empty_like(bias) if bias is not None else None
-        nbytes = swin_attn_workspace_bytes(geo, 1)
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        rc = _entry(lib, "msda_swin_attn_backward_f32", [_CI] * 7 + [_VP] * 5 + [ctypes.c_ulonglong] + [_VP] * 5
-                    + [ctypes.c_ulonglong, _VP])(
-            *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(), out.data_ptr(), lse.data_ptr(), lse.numel() * 4,
-            grad_out.data_ptr(), gq.data_ptr(), gt.data_ptr(), _vp(gb), ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "swin_attn_backward")
+    gq = torch.empty_like(qkv)
+    gt = torch.empty_like(table)
+    gb = torch.empty_like(bias) if bias is not None else None
+    nbytes = swin_attn_workspace_bytes(geo, 1)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    _launch(dev, "msda_swin_attn_backward_f32", "swin_attn_backward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
+            out.data_ptr(), lse.data_ptr(), lse.numel() * 4, grad_out.data_ptr(), gq.data_ptr(), gt.data_ptr(), _vp(gb),
+            ws.data_ptr(), ws.numel() * 4)
     return gq, gt, gb
 
 
 # ---- MANO hand layer: grouped lbs (msda_mano.hip) -----------------------------------------------------------------------------
 MANO_MAX_LAYERS, MANO_MAX_GROUPS, MANO_MAX_EXTRA, MANO_MAX_BETAS, MANO_MAX_VERTS = 4, 16, 8, 16, 8192
-_MANO_GEO = [_CI] * 4 + [_VP, _VP, _CI, _VP, _VP, _VP]
 
 
 def mano_supported(V, n_betas, n_extra):
     """msda_mano_supported (include/msda.h): 1 when the MANO kernels take this model size."""
-    lib = _lib or load()
-    fn = _entry(lib, "msda_mano_supported", [_CI] * 3)
-    return bool(fn(int(V), int(n_betas), int(n_extra)))
+    return bool((_lib or load()).msda_mano_supported(int(V), int(n_betas), int(n_extra)))
 
 
 def _mano_geo(dims, layers, group_layer, group_B, group_bcast):
@@ -1589,35 +1479,24 @@ def _mano_geo(dims, layers, group_layer, group_B, group_bcast):
             _int_array(group_B), _int_array(group_bcast)]
 
 
-def _mano_check(what, dev, tensors):
-    if not all(t is None or (_f32_cuda(t) and t.device == dev) for t in tensors):
-        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
-
-
 def mano_workspace_bytes(dims, group_B):
-    lib = _lib or load()
-    fn = _entry(lib, "msda_mano_workspace_bytes", [_CI] * 4 + [_VP])
-    fn.restype = ctypes.c_ulonglong
-    return int(fn(int(dims[0]), int(dims[1]), int(dims[2]), len(group_B), _int_array(group_B)))
+    return int((_lib or load()).msda_mano_workspace_bytes(int(dims[0]), int(dims[1]), int(dims[2]), len(group_B),
+                                                          _int_array(group_B)))
 
 
 def mano_forward(dims, layers, group_layer, group_bcast, inputs):
     """msda_mano_forward_f32.  inputs: per group (betas, global_orient, hand_pose, transl or None).  Returns per group
     (vertices [B, V, 3], joints [B, 16 + E, 3]).  One launch, no host sync."""
-    lib = _lib or load()
     V, _, E = dims
     dev = inputs[0][1].device
-    _mano_check("mano_forward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp])
+    _check_f32("mano_forward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp])
     group_B = [grp[1].shape[0] for grp in inputs]
     geo = _mano_geo(dims, layers, group_layer, group_B, group_bcast)
-    with _DeviceGuard(dev):
-        outs = [(torch.empty(b, V, 3, dtype=torch.float32, device=dev), torch.empty(b, 16 + E, 3, dtype=torch.float32, device=dev))
-                for b in group_B]
-        ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
-        o = (_VP * (2 * len(outs)))(*[t.data_ptr() for pair in outs for t in pair])
-        rc = _entry(lib, "msda_mano_forward_f32", _MANO_GEO + [_VP, _VP, _VP])(*geo, ins, o, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "mano_forward")
+    outs = [(torch.empty(b, V, 3, dtype=torch.float32, device=dev), torch.empty(b, 16 + E, 3, dtype=torch.float32, device=dev))
+            for b in group_B]
+    ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
+    o = (_VP * (2 * len(outs)))(*[t.data_ptr() for pair in outs for t in pair])
+    _launch(dev, "msda_mano_forward_f32", "mano_forward", *geo, ins, o)
     return outs
 
 
@@ -1625,42 +1504,34 @@ def mano_backward(dims, layers, group_layer, group_bcast, inputs, grad_outputs):
     """msda_mano_backward_f32.  grad_outputs: per group (g_vertices, g_joints), either None.  Returns per group (g_betas per
     hand [B, n_betas], g_global_orient [B, 3], g_hand_pose [B, 45], g_transl [B, 3] or None without transl).  Two launches,
     no host sync."""
-    lib = _lib or load()
     _, nb, _ = dims
     dev = inputs[0][1].device
-    _mano_check("mano_backward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp]
+    _check_f32("mano_backward", dev, [t for lay in layers for t in lay[0]] + [t for grp in inputs for t in grp]
                 + [t for grp in grad_outputs for t in grp])
     group_B = [grp[1].shape[0] for grp in inputs]
     geo = _mano_geo(dims, layers, group_layer, group_B, group_bcast)
-    with _DeviceGuard(dev):
-        nbytes = mano_workspace_bytes(dims, group_B)
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        grads = [(torch.empty(b, nb, dtype=torch.float32, device=dev), torch.empty(b, 3, dtype=torch.float32, device=dev),
-                  torch.empty(b, 45, dtype=torch.float32, device=dev),
-                  torch.empty(b, 3, dtype=torch.float32, device=dev) if grp[3] is not None else None)
-                 for b, grp in zip(group_B, inputs)]
-        ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
-        gos = (_VP * (2 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
-        gs = (_VP * (4 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
-        rc = _entry(lib, "msda_mano_backward_f32", _MANO_GEO + [_VP, _VP, _VP, _VP, ctypes.c_ulonglong, _VP])(
-            *geo, ins, gos, gs, ws.data_ptr(), ws.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "mano_backward")
+    nbytes = mano_workspace_bytes(dims, group_B)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    grads = [(torch.empty(b, nb, dtype=torch.float32, device=dev), torch.empty(b, 3, dtype=torch.float32, device=dev),
+              torch.empty(b, 45, dtype=torch.float32, device=dev),
+              torch.empty(b, 3, dtype=torch.float32, device=dev) if grp[3] is not None else None)
+             for b, grp in zip(group_B, inputs)]
+    ins = (_VP * (4 * len(inputs)))(*[_vp(t) for grp in inputs for t in grp])
+    gos = (_VP * (2 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
+    gs = (_VP * (4 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
+    _launch(dev, "msda_mano_backward_f32", "mano_backward", *geo, ins, gos, gs, ws.data_ptr(), ws.numel() * 4)
     return grads
 
 
 # ---- ARCTIC object layer and small losses (msda_small_loss.hip) ---------------------------------------------------------------
 OBJECT_MAX_GROUPS, SMALL_LOSS_MAX_SETS = 16, 8
 SMALL_LOSS_TERMS, SMALL_LOSS_INPUTS, SMALL_LOSS_TARGETS = 19, 15, 25
-_OBJ_ARGS = [_VP, _VP, _CI, _VP, _VP, _VP]
 
 
 def object_supported(n_objects, max_len, n_sub, n_bbox_top, n_bbox_bottom, n_kp_top, n_kp_bottom):
     """msda_object_supported (include/msda.h): 1 when the object kernels take this model size."""
-    lib = _lib or load()
-    fn = _entry(lib, "msda_object_supported", [_CI] * 7)
-    return bool(fn(int(n_objects), int(max_len), int(n_sub), int(n_bbox_top), int(n_bbox_bottom), int(n_kp_top),
-                   int(n_kp_bottom)))
+    return bool((_lib or load()).msda_object_supported(int(n_objects), int(max_len), int(n_sub), int(n_bbox_top),
+                                                       int(n_bbox_bottom), int(n_kp_top), int(n_kp_bottom)))
 
 
 def _obj_geo(dims, model, inputs, lens):
@@ -1680,54 +1551,39 @@ def _obj_check(what, dev, model, tensors):
 def object_forward(dims, model, inputs, lens):
     """msda_object_forward_f32.  Returns per group (v [B, len, 3], v_sub [B, NS, 3], bbox3d [B, NBt + NBb, 3], kp3d
     [B, NKt + NKb, 3]).  One launch, no host sync."""
-    lib = _lib or load()
     dev = inputs[0][1].device
     _obj_check("object_forward", dev, list(model), [t for grp in inputs for t in grp])
     geo, group_B = _obj_geo(dims, model, inputs, lens)
     _, _, NS, NBt, NBb, NKt, NKb = dims
-    with _DeviceGuard(dev):
-        e = dict(dtype=torch.float32, device=dev)
-        outs = [(torch.empty(b, n, 3, **e), torch.empty(b, NS, 3, **e), torch.empty(b, NBt + NBb, 3, **e),
-                 torch.empty(b, NKt + NKb, 3, **e)) for b, n in zip(group_B, lens)]
-        o = (_VP * (4 * len(outs)))(*[t.data_ptr() for grp in outs for t in grp])
-        rc = _entry(lib, "msda_object_forward_f32", _OBJ_ARGS + [_VP, _VP])(*geo, o, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "object_forward")
+    e = dict(dtype=torch.float32, device=dev)
+    outs = [(torch.empty(b, n, 3, **e), torch.empty(b, NS, 3, **e), torch.empty(b, NBt + NBb, 3, **e),
+             torch.empty(b, NKt + NKb, 3, **e)) for b, n in zip(group_B, lens)]
+    o = (_VP * (4 * len(outs)))(*[t.data_ptr() for grp in outs for t in grp])
+    _launch(dev, "msda_object_forward_f32", "object_forward", *geo, o)
     return outs
 
 
 def object_backward(dims, model, inputs, lens, grad_outputs, want_transl):
     """msda_object_backward_f32.  grad_outputs: per group 4 tensors or None.  Returns per group (g_angles [B], g_global_orient
     [B, 3], g_transl [B, 3] or None).  One launch, no host sync."""
-    lib = _lib or load()
     dev = inputs[0][1].device
     _obj_check("object_backward", dev, list(model), [t for grp in inputs for t in grp] + [t for grp in grad_outputs for t in grp])
     geo, group_B = _obj_geo(dims, model, inputs, lens)
-    with _DeviceGuard(dev):
-        e = dict(dtype=torch.float32, device=dev)
-        grads = [(torch.empty(b, **e), torch.empty(b, 3, **e), torch.empty(b, 3, **e) if w else None)
-                 for b, w in zip(group_B, want_transl)]
-        gos = (_VP * (4 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
-        gs = (_VP * (3 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
-        rc = _entry(lib, "msda_object_backward_f32", _OBJ_ARGS + [_VP, _VP, _VP])(*geo, gos, gs, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "object_backward")
+    e = dict(dtype=torch.float32, device=dev)
+    grads = [(torch.empty(b, **e), torch.empty(b, 3, **e), torch.empty(b, 3, **e) if w else None)
+             for b, w in zip(group_B, want_transl)]
+    gos = (_VP * (4 * len(grad_outputs)))(*[_vp(t) for grp in grad_outputs for t in grp])
+    gs = (_VP * (3 * len(grads)))(*[_vp(t) for grp in grads for t in grp])
+    _launch(dev, "msda_object_backward_f32", "object_backward", *geo, gos, gs)
     return grads
 
 
 def small_loss_supported(S, B, J, NV, KO, NB, L):
-    lib = _lib or load()
-    return bool(_entry(lib, "msda_small_loss_supported", [_CI] * 7)(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
+    return bool((_lib or load()).msda_small_loss_supported(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
 
 
 def small_loss_workspace_bytes(S, B, J, NV, KO, NB, L):
-    lib = _lib or load()
-    fn = _entry(lib, "msda_small_loss_workspace_bytes", [_CI] * 7)
-    fn.restype = ctypes.c_ulonglong
-    return int(fn(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
-
-
-_SL_ARGS = [_VP, ctypes.c_float, _VP, _VP]
+    return int((_lib or load()).msda_small_loss_workspace_bytes(int(S), int(B), int(J), int(NV), int(KO), int(NB), int(L)))
 
 
 def _sl_check(what, dev, tensors):
@@ -1738,34 +1594,24 @@ def _sl_check(what, dev, tensors):
 def small_loss_forward(dims, img_res, targets, inputs):
     """msda_small_loss_forward_f32.  targets: the 25 tensors of msda.h; inputs: per set 15 tensors.  Returns (losses [S, 19],
     workspace for the backward).  Two launches, no host sync."""
-    lib = _lib or load()
     dev = inputs[0][0].device
     _sl_check("small_loss_forward", dev, list(targets) + [t for grp in inputs for t in grp])
-    with _DeviceGuard(dev):
-        losses = torch.empty(dims[0], SMALL_LOSS_TERMS, dtype=torch.float32, device=dev)
-        nbytes = small_loss_workspace_bytes(*dims)
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
-        rc = _entry(lib, "msda_small_loss_forward_f32", _SL_ARGS + [_VP, _VP, ctypes.c_ulonglong, _VP])(
-            _int_array(dims), float(img_res), _ptr_array(targets), ins, losses.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-            _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "small_loss_forward")
+    losses = torch.empty(dims[0], SMALL_LOSS_TERMS, dtype=torch.float32, device=dev)
+    nbytes = small_loss_workspace_bytes(*dims)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
+    _launch(dev, "msda_small_loss_forward_f32", "small_loss_forward", _int_array(dims), float(img_res), _ptr_array(targets),
+            ins, losses.data_ptr(), ws.data_ptr(), ws.numel() * 4)
     return losses, ws
 
 
 def small_loss_backward(dims, img_res, targets, inputs, grad_losses, ws):
     """msda_small_loss_backward_f32.  Returns per set the 15 input gradients, shaped as the inputs.  One launch."""
-    lib = _lib or load()
     dev = inputs[0][0].device
     _sl_check("small_loss_backward", dev, list(targets) + [t for grp in inputs for t in grp] + [grad_losses, ws])
-    with _DeviceGuard(dev):
-        grads = [[torch.empty_like(t) for t in grp] for grp in inputs]
-        ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
-        gs = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in grads for t in grp])
-        rc = _entry(lib, "msda_small_loss_backward_f32", _SL_ARGS + [_VP, _VP, _VP, ctypes.c_ulonglong, _VP])(
-            _int_array(dims), float(img_res), _ptr_array(targets), ins, grad_losses.data_ptr(), gs, ws.data_ptr(),
-            ws.numel() * 4, _raw_stream(dev))
-    if rc != 0:
-        _raise(lib, rc, "small_loss_backward")
+    grads = [[torch.empty_like(t) for t in grp] for grp in inputs]
+    ins = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in inputs for t in grp])
+    gs = (_VP * (SMALL_LOSS_INPUTS * len(inputs)))(*[t.data_ptr() for grp in grads for t in grp])
+    _launch(dev, "msda_small_loss_backward_f32", "small_loss_backward", _int_array(dims), float(img_res),
+            _ptr_array(targets), ins, grad_losses.data_ptr(), gs, ws.data_ptr(), ws.numel() * 4)
     return grads

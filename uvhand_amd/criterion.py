@@ -69,7 +69,7 @@ def pack_joint_valid(targets, device):
     """AssemblyHands' per-target ``joint_valid`` ([T_k, 21, 3] bool per frame) as one uint8 [n, 63] device tensor, in
     target order (``torch.cat`` on the device; no sync)."""
     device = torch.device(device)
-    parts = [v["joint_valid"].to(device, non_blocking=True).reshape(len(v["joint_valid"]), -1) for v in targets]
+    parts = [v["joint_valid"].to(device, non_blocking=True).flatten(1) for v in targets]   # (a frame may have no target)
     return torch.cat(parts).to(torch.uint8).contiguous()
 
 

@@ -763,6 +763,45 @@ int msda_small_loss_backward_f32(const int *dims, float img_res, const void *con
                                  const float *grad_losses, float *const *grads, const void *workspace,
                                  unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- ARCTIC evaluation: nearest neighbour and metrics (csrc/msda_arctic_eval.hip) ------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Nearest neighbour (arctic_tools/src/utils/loss_modules.py get_NN, i.e. pytorch3d knn_points with K = 1 and full lengths).
+ * n_pairs (1 .. 8) pairs share B (0 .. 65535), N1 (1 .. 8192) and N2 (1 .. 1024).  src, trg: HOST arrays of n_pairs device
+ * pointers, src [B, N1, 3], trg [B, N2, 3], fp32 contiguous.  dists [B, N1] fp32: the SQUARED distance to the nearest target,
+ * dx dx + dy dy + dz dz summed in that order; idx [B, N1] int64.  The minimum moves on strict < only: the lowest index wins a
+ * tie, a NaN distance never wins (no finite candidate: +inf, index 0).
+ *   msda_nn_supported     1 when the kernels take this geometry.
+ *   msda_nn_forward_f32   one launch (none for B = 0).
+ *   msda_nn_backward_f32  one launch.  grad_dists [B, N1]; grad_src [B, N1, 3] = 2 g (a - b_idx), grad_trg [B, N2, 3] =
+ *       -sum over the sources with idx == j, in source order without atomics (bitwise reproducible); either output pointer
+ *       may be NULL (not wanted).  An idx outside 0 .. N2 - 1 contributes nothing.
+ *
+ * Metrics (arctic_tools/process.py measure_error over src/utils/eval_modules.py eval_degree, eval_mpjpe_ra, eval_mrrpe,
+ * eval_v2v_success, eval_contact_deviation and common/metrics.py).  dims: HOST ints {B frames, J hand joints (1 .. 32), NV hand
+ * vertices (1 .. 1024), L_pred rows of pred object.v.cam, L_gt rows of targets object.v.cam, L_parts rows of part_ids (each
+ * 1 .. 65536)}.  floats: HOST array of 16 device pointers, fp32 contiguous: pred object.radian [B], targets object.radian [B],
+ * pred mano.j3d.cam.r, pred mano.j3d.cam.l, targets mano.j3d.cam.r, targets mano.j3d.cam.l [B, J, 3], pred object.v.cam
+ * [B, L_pred, 3], targets object.v.cam [B, L_gt, 3], diameter [B], is_valid, left_valid, right_valid [B], pred mano.v3d.cam.r,
+ * pred mano.v3d.cam.l [B, NV, 3], targets dist.ro, dist.lo [B, NV].  longs: HOST array of 4 device pointers, int64: object.v_len
+ * [B], part_ids [B, L_parts], idx.ro, idx.lo [B, NV].  out [6, B]: aae (degrees), mpjpe/ra/h, mrrpe/r/l, mrrpe/r/o (mm),
+ * success_rate/0.05 (percent), cdev/ho (mm); NaN where the reference has NaN.
+ *   msda_arctic_metrics_f32             one launch, one workgroup per frame, fixed reduction order.
+ *   msda_arctic_metrics_accumulate_f32  engine.py test_pose's per-key step mean and MetricLogger.update: per key the mean over
+ *       the non-NaN frames of values [6, B]; where one exists it is added to total[key] and 1 to count[key] (fp64 device arrays
+ *       of 6).  One launch of one workgroup.
+ * No allocation, no synchronisation; argument errors before any launch. */
+int msda_nn_supported(int B, int N1, int N2);
+int msda_nn_forward_f32(int n_pairs, int B, int N1, int N2, const float *const *src, const float *const *trg, float *const *dists,
+                        long long *const *idx, msda_stream_t stream);
+int msda_nn_backward_f32(int n_pairs, int B, int N1, int N2, const float *const *src, const float *const *trg,
+                         const long long *const *idx, const float *const *grad_dists, float *const *grad_src,
+                         float *const *grad_trg, msda_stream_t stream);
+int msda_arctic_metrics_supported(int B, int J, int NV, int L_pred, int L_gt, int L_parts);
+int msda_arctic_metrics_f32(const int *dims, const float *const *floats, const long long *const *longs, float *out,
+                            msda_stream_t stream);
+int msda_arctic_metrics_accumulate_f32(const float *values, int B, double *total, double *count, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

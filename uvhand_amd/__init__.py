@@ -14,5 +14,15 @@ from .functions import MSDeformAttnFunction
 from .graphs import graphed
 from .modules import MSDeformAttn
 
-__all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"]
+# the ARCTIC evaluation step (uvhand_amd/arctic_eval.py), resolved on first use so that importing the op stays light
+_ARCTIC_EVAL = ("get_NN", "nn_many", "make_output", "post_process_arctic_output", "prepare_data", "measure_error",
+                "arctic_metrics", "ArcticEvaluator")
+__all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"] + list(_ARCTIC_EVAL)
+
+
+def __getattr__(name):
+    if name in _ARCTIC_EVAL:
+        from . import arctic_eval
+        return getattr(arctic_eval, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 __version__ = "0.1.0"

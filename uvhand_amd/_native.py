@@ -133,6 +133,13 @@ SIGNATURES = {
     "msda_small_loss_workspace_bytes": "U iiiiiii",
     "msda_small_loss_forward_f32": "i p f pp pp U p",
     "msda_small_loss_backward_f32": "i p f pp ppp U p",
+    # ARCTIC evaluation: nearest neighbour and metrics
+    "msda_nn_supported": "i iii",
+    "msda_nn_forward_f32": "i iiii pppp p",
+    "msda_nn_backward_f32": "i iiii pppppp p",
+    "msda_arctic_metrics_supported": "i iiiiii",
+    "msda_arctic_metrics_f32": "i ppp p p",
+    "msda_arctic_metrics_accumulate_f32": "i p i pp p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -1615,3 +1622,70 @@ def small_loss_backward(dims, img_res, targets, inputs, grad_losses, ws):
     _launch(dev, "msda_small_loss_backward_f32", "small_loss_backward", _int_array(dims), float(img_res),
             _ptr_array(targets), ins, grad_losses.data_ptr(), gs, ws.data_ptr(), ws.numel() * 4)
     return grads
+
+
+# ---- ARCTIC evaluation: nearest neighbour and metrics (msda_arctic_eval.hip) --------------------------------------------------
+NN_MAX_PAIRS = 8
+ARCTIC_METRICS = 6
+
+
+def nn_supported(B, N1, N2):
+    """msda_nn_supported (include/msda.h): 1 when the nearest-neighbour kernels take this geometry."""
+    return bool((_lib or load()).msda_nn_supported(int(B), int(N1), int(N2)))
+
+
+def _nn_check(what, dev, tensors):
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() and t.dtype in (torch.float32, torch.int64) for t in tensors):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA tensors on one device" % what)
+
+
+def nn_forward(pairs):
+    """msda_nn_forward_f32.  pairs: [(src [B, N1, 3], trg [B, N2, 3])] sharing B, N1, N2.  Returns per pair (dists [B, N1] fp32
+    squared, idx [B, N1] int64).  One launch, no host sync."""
+    dev = pairs[0][0].device
+    _nn_check("nn_forward", dev, [t for p in pairs for t in p])
+    B, N1, _ = pairs[0][0].shape
+    N2 = pairs[0][1].shape[1]
+    outs = [(torch.empty(B, N1, dtype=torch.float32, device=dev), torch.empty(B, N1, dtype=torch.int64, device=dev)) for _ in pairs]
+    _launch(dev, "msda_nn_forward_f32", "nn_forward", len(pairs), B, N1, N2, _ptr_array([p[0] for p in pairs]),
+            _ptr_array([p[1] for p in pairs]), _ptr_array([o[0] for o in outs]), _ptr_array([o[1] for o in outs]))
+    return outs
+
+
+def nn_backward(pairs, idxs, grad_dists, want):
+    """msda_nn_backward_f32.  want: per pair (want grad_src, want grad_trg).  Returns per pair (grad_src or None, grad_trg or
+    None).  One launch, no atomics."""
+    dev = pairs[0][0].device
+    _nn_check("nn_backward", dev, [t for p in pairs for t in p] + list(idxs) + list(grad_dists))
+    grads = [(torch.empty_like(s) if ws else None, torch.empty_like(t) if wt else None) for (s, t), (ws, wt) in zip(pairs, want)]
+    B, N1, _ = pairs[0][0].shape
+    N2 = pairs[0][1].shape[1]
+    _launch(dev, "msda_nn_backward_f32", "nn_backward", len(pairs), B, N1, N2, _ptr_array([p[0] for p in pairs]),
+            _ptr_array([p[1] for p in pairs]), _ptr_array(idxs), _ptr_array(grad_dists),
+            (_VP * len(grads))(*[_vp(g[0]) for g in grads]), (_VP * len(grads))(*[_vp(g[1]) for g in grads]))
+    return grads
+
+
+def arctic_metrics_supported(B, J, NV, L_pred, L_gt, L_parts):
+    return bool((_lib or load()).msda_arctic_metrics_supported(int(B), int(J), int(NV), int(L_pred), int(L_gt), int(L_parts)))
+
+
+def arctic_metrics(dims, floats, longs):
+    """msda_arctic_metrics_f32.  floats: the 16 fp32 tensors, longs: the 4 int64 tensors of msda.h.  Returns [6, B] fp32."""
+    dev = floats[0].device
+    _nn_check("arctic_metrics", dev, list(floats) + list(longs))
+    out = torch.empty(ARCTIC_METRICS, dims[0], dtype=torch.float32, device=dev)
+    _launch(dev, "msda_arctic_metrics_f32", "arctic_metrics", _int_array(dims), _ptr_array(floats), _ptr_array(longs),
+            out.data_ptr())
+    return out
+
+
+def arctic_metrics_accumulate(values, total, count):
+    """msda_arctic_metrics_accumulate_f32: values [6, B] fp32 into total / count (fp64 [6]), in place."""
+    dev = values.device
+    if not (values.is_cuda and values.is_contiguous() and values.dtype == torch.float32 and values.shape[0] == ARCTIC_METRICS
+            and all(t.device == dev and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == ARCTIC_METRICS
+                    for t in (total, count))):
+        raise RuntimeError("arctic_metrics_accumulate: expected values [6, B] fp32 and fp64 total / count of 6 on one device")
+    _launch(dev, "msda_arctic_metrics_accumulate_f32", "arctic_metrics_accumulate", values.data_ptr(), int(values.shape[1]),
+            total.data_ptr(), count.data_ptr())

@@ -74,7 +74,6 @@ static int check_row_strides(const char *who, int M, int L, int P, const void *o
 // The D = 32 kernels move rows as 16-byte (fp32) / 8-byte (bf16) vectors and locations as (x, y) pairs.
 // Tensors straight from an allocator always qualify; a contiguous VIEW at an odd element offset does not —
 // fp32 / bf16 op calls then take the generic kernels (element-wise accesses); the prologue and wgrad entries refuse.
-static bool aligned_to(const void *p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 static int refuse_unaligned(const char *who)
 {
@@ -89,31 +88,6 @@ static bool use_d32(int N, int S, int M, int D, int L, int Lq, int P)
     const int f = g_force_path;
     if (f == MSDA_PATH_GENERIC) return false;
     return d32_supported(N, S, M, D, L, Lq, P);
-}
-
-// MSDA_FLAG_FORWARD_TABLE: `workspace` starts with the point table a msda_forward_ws_* call of the same geometry filled
-// (include/msda.h).  Used only where the backward's plan reads one and the caller's buffer holds all of it.
-static const void *table_of(const void *workspace, size_t ws_bytes, unsigned flags, int N, int S, int M, int D, int L, int Lq, int P,
-                            bool prologue)
-{
-    if (!(flags & MSDA_FLAG_FORWARD_TABLE) || !workspace || !aligned_to(workspace, 16)) return nullptr;
-    const size_t need = forward_table_bytes(N, S, M, D, L, Lq, P, prologue);
-    return (need > 0 && ws_bytes >= need) ? workspace : nullptr;
-}
-
-// The scratch part of a backward call's workspace: all of it, or — with MSDA_FLAG_FORWARD_TABLE on a geometry whose forward
-// leaves a table — what follows the table (include/msda.h: the table first, rounded up to 256 bytes, then the scratch).
-struct Scratch { void *p; size_t bytes; };
-static size_t table_span(int N, int S, int M, int D, int L, int Lq, int P, bool prologue)
-{
-    return (forward_table_bytes(N, S, M, D, L, Lq, P, prologue) + 255) & ~(size_t)255;
-}
-static Scratch scratch_of(void *workspace, size_t ws_bytes, unsigned flags, int N, int S, int M, int D, int L, int Lq, int P, bool prologue)
-{
-    if (!workspace || !(flags & MSDA_FLAG_FORWARD_TABLE)) return Scratch{workspace, workspace ? ws_bytes : 0};
-    const size_t span = table_span(N, S, M, D, L, Lq, P, prologue);
-    if (ws_bytes <= span) return Scratch{nullptr, 0};
-    return Scratch{static_cast<unsigned char *>(workspace) + span, ws_bytes - span};
 }
 
 template <typename T>
@@ -131,7 +105,7 @@ static int forward_impl(const T *value, const int64_t *shapes, const int64_t *le
     }
     if constexpr (sizeof(T) == 4) {
         if (d32 && aligned_to(value, 16) && aligned_to(out, 16) && aligned_to(loc, 8))
-            return launch_fwd_d32(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, stream, table);
+            return launch_fwd_d32<float>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, stream, table);
     }
     // (the generic kernels write no table: a buffer the caller handed over gets its stamp cleared)
     if (table) if (int rc = invalidate_forward_table(table, N, S, M, L, Lq, P, stream)) return rc;
@@ -162,12 +136,10 @@ static int backward_impl(const T *grad_out, const T *value, const int64_t *shape
         if (d32 && aligned_to(grad_out, 16) && aligned_to(value, 16) && aligned_to(grad_value, 16) && aligned_to(loc, 8) &&
             aligned_to(grad_loc, 8))
         {
-            const Scratch sc = scratch_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false);
-            return launch_bwd_d32(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P,
-                                  grad_value, grad_loc, grad_attn, stream, sc.p, sc.bytes,
-                                  (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                  table_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false),
-                                  (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+            return launch_bwd_d32<float, float>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
+                                                grad_loc, grad_attn, stream, (flags & MSDA_FLAG_DETERMINISTIC) != 0, workspace,
+                                                ws_bytes, (flags & MSDA_FLAG_FORWARD_TABLE) != 0,
+                                                (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
         }
     }
     return launch_bwd_generic<T>(grad_out, value, shapes, level_start, loc, attn, N, S, M, D, L, Lq, P,
@@ -200,29 +172,20 @@ static int backward_bf16_impl(const uint16_t *grad_out, const uint16_t *value, c
     const bool d32 = msda::use_d32(N, S, M, D, L, Lq, P) && msda::aligned_to(grad_out, 8) && msda::aligned_to(value, 8) &&
                      msda::aligned_to(grad_value, sizeof(GT) * 4) && msda::aligned_to(sampling_loc, 8) &&
                      msda::aligned_to(grad_sampling_loc, 8);
-    if constexpr (sizeof(GT) == 2) {
-        if (!d32)
+    if (!d32) {
+        if constexpr (sizeof(GT) == 2)
             return msda::set_error(MSDA_ERR_ARGUMENT, "msda_backward_bf16: bf16 grad_value needs the D=32 kernel family (D == 32, "
                                                       "L <= 16, L*P <= 32, 8-byte aligned rows); msda_backward_bf16_gv32 serves "
                                                       "every other shape");
-        const msda::Scratch sc = msda::scratch_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false);
-        return msda::launch_bwd_d32_bf16(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M,
-                                         L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream,
-                                         sc.p, sc.bytes, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                         msda::table_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false),
-                                  (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
-    } else {
-        if (!d32)                                                   // element-wise accesses: any D, any element offset
+        else                                                        // element-wise accesses: any D, any element offset
             return msda::launch_bwd_generic<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N,
                                                    S, M, D, L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight,
                                                    (hipStream_t)stream, (flags & MSDA_FLAG_DETERMINISTIC) != 0);
-        const msda::Scratch sc = msda::scratch_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false);
-        return msda::launch_bwd_d32_bf16_gv32(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S,
-                                              M, L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight,
-                                              (hipStream_t)stream, sc.p, sc.bytes, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                              msda::table_of(workspace, ws_bytes, flags, N, S, M, D, L, Lq, P, false),
-                                  (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
     }
+    return msda::launch_bwd_d32<uint16_t, GT>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
+                                              Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream,
+                                              (flags & MSDA_FLAG_DETERMINISTIC) != 0, workspace, ws_bytes,
+                                              (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
 }
 
 extern "C" {
@@ -280,14 +243,13 @@ static int forward_bf16_impl(const uint16_t *value, const int64_t *spatial_shape
     }
     if (!msda::use_d32(N, S, M, D, L, Lq, P) || !msda::aligned_to(value, 8) || !msda::aligned_to(out, 8) ||
         !msda::aligned_to(sampling_loc, 8)) {
+        // (the generic kernels write no table: a buffer the caller handed over gets its stamp cleared)
         if (table) if (int rc = msda::invalidate_forward_table(table, N, S, M, L, Lq, P, (hipStream_t)stream)) return rc;
-    }
-    if (!msda::use_d32(N, S, M, D, L, Lq, P) || !msda::aligned_to(value, 8) || !msda::aligned_to(out, 8) ||
-        !msda::aligned_to(sampling_loc, 8))
         return msda::launch_fwd_generic<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq,
                                                P, out, (hipStream_t)stream);
-    return msda::launch_fwd_d32_bf16(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L, Lq, P,
-                                     out, (hipStream_t)stream, table);
+    }
+    return msda::launch_fwd_d32<uint16_t>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L, Lq, P,
+                                          out, (hipStream_t)stream, table);
 }
 
 int msda_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -305,21 +267,14 @@ unsigned long long msda_forward_workspace_bytes(int N, int S, int M, int D, int 
     return (unsigned long long)msda::forward_table_bytes(N, S, M, D, L, Lq, P, (flags & MSDA_FLAG_PROLOGUE) != 0);
 }
 
-static void *fwd_table(void *workspace, unsigned long long workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P, bool prologue)
-{
-    if (!workspace || !msda::aligned_to(workspace, 16) || N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return nullptr;
-    if (msda::g_force_path == MSDA_PATH_GENERIC) return nullptr;
-    const size_t need = msda::forward_table_bytes(N, S, M, D, L, Lq, P, prologue);
-    return (need > 0 && workspace_bytes >= need) ? workspace : nullptr;
-}
-
 int msda_forward_ws_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start, const float *sampling_loc,
                         const float *attn_weight, int N, int S, int M, int D, int L, int Lq, int P, float *out, void *workspace,
                         unsigned long long workspace_bytes, msda_stream_t stream)
 {
     return msda::forward_impl<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, out,
                                      (hipStream_t)stream, msda::use_d32(N, S, M, D, L, Lq, P),
-                                     fwd_table(workspace, workspace_bytes, N, S, M, D, L, Lq, P, false));
+                                     msda::table_of(workspace, (size_t)workspace_bytes,
+                                                    (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, 0)));
 }
 
 int msda_forward_ws_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start, const float *sampling_loc,
@@ -327,7 +282,8 @@ int msda_forward_ws_bf16(const uint16_t *value, const int64_t *spatial_shapes, c
                          unsigned long long workspace_bytes, msda_stream_t stream)
 {
     return forward_bf16_impl(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, out, stream,
-                             fwd_table(workspace, workspace_bytes, N, S, M, D, L, Lq, P, false));
+                             msda::table_of(workspace, (size_t)workspace_bytes,
+                                            (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, 0)));
 }
 
 int msda_backward_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -359,7 +315,7 @@ unsigned long long msda_backward_workspace_bytes(int N, int S, int M, int D, int
     const size_t table = (flags & MSDA_FLAG_FORWARD_TABLE) ? msda::forward_table_bytes(N, S, M, D, L, Lq, P, prologue) : 0;
     const size_t scratch = msda::backward_workspace_bytes(N, S, M, D, L, Lq, P, flags);
     if (table == 0) return (unsigned long long)scratch;
-    return (unsigned long long)(scratch ? msda::table_span(N, S, M, D, L, Lq, P, prologue) + scratch : table);
+    return (unsigned long long)(scratch ? msda::table_span(table) + scratch : table);
 }
 
 int msda_deterministic_supported(int elem_bytes, int N, int S, int M, int D, int L, int Lq, int P)
@@ -447,9 +403,10 @@ int msda_forward_prologue_ws_f32(const float *value, const int64_t *spatial_shap
         !msda::aligned_to(sampling_loc_out, 8))
         return msda::refuse_unaligned("msda_forward_prologue_f32");
     msda::begin_call();
-    return msda::launch_fwd_prologue(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits, N,
-                                     S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
-                                     (hipStream_t)stream, fwd_table(workspace, workspace_bytes, N, S, M, D, L, Lq, P, true));
+    const size_t table = (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, MSDA_FLAG_PROLOGUE);
+    return msda::launch_fwd_prologue<float>(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits, N,
+                                            S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
+                                            (hipStream_t)stream, msda::table_of(workspace, (size_t)workspace_bytes, table));
 }
 
 int msda_backward_prologue_f32(const float *grad_out, const float *value, const int64_t *spatial_shapes,
@@ -481,13 +438,11 @@ int msda_backward_prologue_ws_f32(const float *grad_out, const float *value, con
         !msda::aligned_to(sampling_loc, 8) || !msda::aligned_to(grad_reference_points, 8))
         return msda::refuse_unaligned("msda_backward_prologue_f32");
     msda::begin_call();
-    const msda::Scratch sc = msda::scratch_of(workspace, (size_t)workspace_bytes, flags, N, S, M, D, L, Lq, P, true);
-    return msda::launch_bwd_prologue(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
-                                     Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets,
-                                     grad_attn_logits, grad_reference_points, (hipStream_t)stream, sc.p,
-                                     sc.bytes, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                     msda::table_of(workspace, (size_t)workspace_bytes, flags, N, S, M, D, L, Lq, P, true),
-                                  (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+    return msda::launch_bwd_prologue<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
+                                            Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets, grad_attn_logits,
+                                            grad_reference_points, (hipStream_t)stream, workspace, (size_t)workspace_bytes,
+                                            (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
+                                            (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
 }
 
 int msda_forward_prologue_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -515,9 +470,10 @@ int msda_forward_prologue_ws_bf16(const uint16_t *value, const int64_t *spatial_
         !msda::aligned_to(sampling_loc_out, 8))
         return msda::refuse_unaligned("msda_forward_prologue_bf16");
     msda::begin_call();
-    return msda::launch_fwd_prologue_bf16(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits,
-                                          N, S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
-                                          (hipStream_t)stream, fwd_table(workspace, workspace_bytes, N, S, M, D, L, Lq, P, true));
+    const size_t table = (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, MSDA_FLAG_PROLOGUE);
+    return msda::launch_fwd_prologue<uint16_t>(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits,
+                                               N, S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
+                                               (hipStream_t)stream, msda::table_of(workspace, (size_t)workspace_bytes, table));
 }
 
 int msda_backward_prologue_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -538,13 +494,11 @@ int msda_backward_prologue_bf16_gv32(const uint16_t *grad_out, const uint16_t *v
         !msda::aligned_to(sampling_loc, 8) || !msda::aligned_to(grad_reference_points, 8))
         return msda::refuse_unaligned("msda_backward_prologue_bf16_gv32");
     msda::begin_call();
-    const msda::Scratch sc = msda::scratch_of(workspace, (size_t)workspace_bytes, flags, N, S, M, D, L, Lq, P, true);
-    return msda::launch_bwd_prologue_bf16(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
-                                          Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets,
-                                          grad_attn_logits, grad_reference_points, (hipStream_t)stream, sc.p,
-                                          sc.bytes, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                          msda::table_of(workspace, (size_t)workspace_bytes, flags, N, S, M, D, L, Lq, P, true),
-                                  (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+    return msda::launch_bwd_prologue<uint16_t>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
+                                               Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets, grad_attn_logits,
+                                               grad_reference_points, (hipStream_t)stream, workspace, (size_t)workspace_bytes,
+                                               (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
+                                               (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
 }
 
 unsigned long long msda_linear_wgrad_workspace_bytes(int M, int N, int K)

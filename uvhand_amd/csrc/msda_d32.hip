@@ -726,7 +726,7 @@ __global__ __launch_bounds__(kSBlock, 4) void bwd_fused_lds_d32_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers
+// host side
 // ------------------------------------------------------------------------------------------
 #if MSDA_D32_HAS(0)
 bool d32_supported(int N, int S, int M, int D, int L, int Lq, int P)
@@ -788,8 +788,18 @@ static int pick_split(int items, int LP)
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-static int allow_lds(const void *fn, size_t bytes);
+static int allow_lds(const void *fn, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return MSDA_OK;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
+}
 
+// ------------------------------------------------------------------------------------------
+// plans (host side; only S, the batch and Lq*P are known here — the level geometry lives on the device).  plan_lds,
+// plan_value, plan_fused and plan_masks are the building blocks; plan_table and plan_backward combine them and are the only
+// places that do: the launchers, the workspace sizes and msda_describe_plan read their results.
+// ------------------------------------------------------------------------------------------
 // Large problems take the LDS-stage kernels of msda_d32_lds.h: `chunks` workgroups per (batch, head) pair, each staging the
 // pair's coarse levels once and serving `qw` queries in sub-batches of 64.  At least ~1024 workgroups (two resident per
 // CU, 512 threads each) unless that would leave fewer than one sub-batch per workgroup; MSDA_LDS=0/1 overrides (tuning).
@@ -827,86 +837,15 @@ static LdsPlan plan_lds(int N, int S, int M, int L, int Lq, int P, long long rol
     const bool large = items >= 32768 && Lq >= kLItems;                       // below that the launch is latency-bound
     // (a batch element's slice of `value` is addressed through a buffer descriptor with 32-bit byte offsets)
     // L*P <= 16: two point slots per lane and octet (with more, role A's look-ahead registers spill)
+    // For a geometry d32_supported() admits neither bound below can fail (the slice stays under 2^31 bytes as fp32 rows,
+    // chunks <= Lq / 8 + 1), so `use` is ONE answer per geometry, whatever VT and role_b_wgs: the forward (role_b_wgs = 0),
+    // the backward and plan_table agree on it.
     pl.use = (mode < 0 ? large : mode != 0) && pairs * pl.chunks <= 0x7fffffffLL && Lq > 0 && L * P <= 16 &&
              (long long)S * M * kD * (long long)sizeof(VT) < (1LL << 31);
     return pl;
 }
 
-template <typename VT, bool FUSED>
-static int launch_fwd_lds(const LdsPlan &lp, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                          const float *attn, int N, int S, int M, int L, int Lq, int P, VT *out, const PrologueIn &pro,
-                          hipStream_t stream, const MaskOut mo = MaskOut{nullptr, nullptr, 0})
-{
-    const dim3 grid((unsigned)(N * M * lp.chunks));
-    // (with masks to write: the ranges' first pixels [L][W + 1] and a float scale per level behind the records)
-    const size_t lds = lp.lds + (mo.masks ? (size_t)(L * (mo.W + 1) + L) * sizeof(int) : 0);
-#define MSDA_LAUNCH_FL(NS_)                                                                            \
-    do { if (int rc = allow_lds(reinterpret_cast<const void *>(fwd_d32_lds_kernel<VT, FUSED, NS_>), lds)) return rc;               \
-         hipLaunchKernelGGL((fwd_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lds, stream, value, shapes, level_start,    \
-                            loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw, lp.stage_rows, out,   \
-                            pro, xcd_remap(), mo); } while (0)
-    if (8 * L * P <= kWave) MSDA_LAUNCH_FL(1); else MSDA_LAUNCH_FL(2);             // plan_lds: L*P <= 16
-#undef MSDA_LAUNCH_FL
-    return check_launch("msda forward (d32, LDS stage)");
-}
-
-template <typename VT, bool FUSED>
-static int launch_query_lds(const LdsPlan &lp, const VT *grad_out, const VT *value, const int64_t *shapes,
-                            const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L, int Lq,
-                            int P, float *grad_loc, float *grad_attn, const PrologueOut &pro, hipStream_t stream)
-{
-    const dim3 grid((unsigned)(N * M * lp.chunks));
-#define MSDA_LAUNCH_QL(NS_)                                                                            \
-    do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_query_d32_lds_kernel<VT, FUSED, NS_>), lp.lds)) return rc;      \
-         hipLaunchKernelGGL((bwd_query_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lp.lds, stream, grad_out, value,      \
-                            shapes, level_start, loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw,  \
-                            lp.stage_rows, grad_loc, grad_attn, pro, xcd_remap()); } while (0)
-    if (8 * L * P <= kWave) MSDA_LAUNCH_QL(1); else MSDA_LAUNCH_QL(2);             // plan_lds: L*P <= 16
-#undef MSDA_LAUNCH_QL
-    return check_launch("msda backward (d32, query-major, LDS stage)");
-}
-
-// ranges per level / rows per range of the backward's role-B plan, for the header the forward writes behind the point table
-static void table_header_plan(int N, int S, int M, int L, int Lq, int P, int &W, int &tp_cap);
-// the header behind the point entries of a table (null: no table)
-static const RangeHeader *table_header_of(const PointEntry *table, int N, int M, int L, int Lq, int P, int W)
-{
-    if (!table) return nullptr;
-    return reinterpret_cast<const RangeHeader *>(table + (long long)N * M * L * Lq * P);
-}
-
-// per-point range masks of large problems (MaskHeader): plan_masks below
-static MaskOut mask_out(void *table, int N, int S, int M, int L, int Lq, int P);
-
-template <typename VT>
-static int launch_fwd_d32_t(const VT *value, const int64_t *shapes, const int64_t *level_start,
-                            const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P,
-                            VT *out, hipStream_t stream, PointEntry *table = nullptr)
-{
-    const LdsPlan lp = plan_lds<VT>(N, S, M, L, Lq, P);
-    if (lp.use)
-        return launch_fwd_lds<VT, false>(lp, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out,
-                                         PrologueIn{nullptr, nullptr, nullptr, 0, 0}, stream, mask_out(table, N, S, M, L, Lq, P));
-    const int items = N * Lq * M, LP = L * P;
-    const int item_stride = LP * kRecBytes + kItemPad;
-    const int split = pick_split(items, LP);
-    const int ipw = 32 / split;
-    const size_t lds = (size_t)ipw * item_stride + (split > 1 ? 4096 : 0);
-    int hdr_W = 0, hdr_tp_cap = 0;
-    if (table) table_header_plan(N, S, M, L, Lq, P, hdr_W, hdr_tp_cap);
-    const dim3 grid((items + ipw - 1) / ipw + (hdr_W > 0 ? 1 : 0)), block(kBlock);      // (+ the header's workgroup)
-#define MSDA_LAUNCH_FWD(SP)                                                                            \
-    hipLaunchKernelGGL((fwd_d32_kernel<SP, VT>), grid, block, lds, stream, value, shapes, level_start, loc, attn, \
-                       S, M, L, Lq, P, items, pow2_shift(P), pow2_shift(LP), pow2_shift(M), out,                  \
-                       PrologueIn{nullptr, nullptr, nullptr, 0, 0}, xcd, table, hdr_W, hdr_tp_cap, kSmallRecCap)
-    const int xcd = xcd_remap();
-    if (split == 4) MSDA_LAUNCH_FWD(4); else if (split == 2) MSDA_LAUNCH_FWD(2); else MSDA_LAUNCH_FWD(1);
-#undef MSDA_LAUNCH_FWD
-    return check_launch("msda forward (d32)");
-}
-
-// Role-B plan (host side; only S, the batch and Lq*P are known here — the level geometry lives on
-// the device): W ranges per level, PPT points per thread per pass, accumulation mode.
+// Role B: W ranges per level, PPT points per thread per pass, accumulation mode.
 struct ValuePlan { int W, tp_cap, ppt, acc; size_t lds; };
 
 template <typename VT>
@@ -957,18 +896,14 @@ static ValuePlan plan_value(int N, int S, int M, int L, int Lq, int P, int targe
     return pl;
 }
 
-static ValuePlan plan_value_f32(int N, int S, int M, int L, int Lq, int P) { return plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), false); }
-
-// Per-point range masks (MaskHeader): where the forward is the LDS-stage kernel and role B the kept-taps pass with W <= 8
-// ranges per level — the same plan functions the launchers run, so the forward's writer and the backward's reader agree
-// (the header repeats the plan and role B checks it).  Row storage does not matter.
+// Per-point range masks (MaskHeader) for role B plan `pl` of a large problem: only the kept-taps pass with 4 .. 8 ranges per
+// level reads them.
 struct MaskPlan { bool use; int W; size_t bytes; };
-static MaskPlan plan_masks(int N, int S, int M, int L, int Lq, int P)
+static MaskPlan plan_masks(const ValuePlan &pl, int N, int M, int L, int Lq, int P)
 {
     static const int enabled = env_int("MSDA_MASKS", 1);                // A/B knob (tuning build): 0 = role B scans sampling_loc
     MaskPlan mp{false, 0, 0};
-    if (!enabled || !plan_lds<float>(N, S, M, L, Lq, P).use) return mp;
-    const ValuePlan pl = plan_value_f32(N, S, M, L, Lq, P);
+    if (!enabled) return mp;
     const long long NP = (long long)Lq * P;
     // W >= kMinMaskRanges: the byte costs the forward ~35 instructions per point lane (+10 % of its time), and each range's
     // workgroup saves the strided float scan of all Lq*P points — a trade that pays from four ranges per level on (cfg-2
@@ -979,32 +914,6 @@ static MaskPlan plan_masks(int N, int S, int M, int L, int Lq, int P)
     mp.use = true; mp.W = pl.W;
     mp.bytes = sizeof(MaskHeader) + (size_t)N * M * L * (size_t)NP;
     return mp;
-}
-static MaskOut mask_out(void *table, int N, int S, int M, int L, int Lq, int P)
-{
-    MaskOut mo{nullptr, nullptr, 0};
-    if (!table) return mo;
-    const MaskPlan mp = plan_masks(N, S, M, L, Lq, P);
-    if (!mp.use) return mo;
-    unsigned char *b = static_cast<unsigned char *>(table);
-    return MaskOut{reinterpret_cast<MaskHeader *>(b), b + sizeof(MaskHeader), mp.W};
-}
-// (role B reads them only where its own plan is the kept-taps pass with the same W; never under the deterministic flag)
-static MaskIn mask_in(const void *table, int N, int S, int M, int L, int Lq, int P, int acc, int W, bool deterministic)
-{
-    MaskIn mi{nullptr, nullptr};
-    if (!table || deterministic || acc != kAccWide) return mi;
-    const MaskPlan mp = plan_masks(N, S, M, L, Lq, P);
-    if (!mp.use || mp.W != W) return mi;
-    const unsigned char *b = static_cast<const unsigned char *>(table);
-    return MaskIn{reinterpret_cast<const MaskHeader *>(b), b + sizeof(MaskHeader)};
-}
-
-static int allow_lds(const void *fn, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return MSDA_OK;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
 }
 
 // The fused backward launch of a SMALL problem.  The fused kernel keeps two 512-thread workgroups per CU (its
@@ -1032,13 +941,208 @@ static FusedPlan plan_fused(int items, int LP, int split, long long nB, int acc,
 // per-head reference-point gradients of the fused-prologue backward on large problems, padded to 16 bytes
 static size_t prologue_heads_bytes(int N, int M, int L, int Lq) { return ((size_t)N * Lq * M * L * sizeof(float2) + 15) & ~(size_t)15; }
 
-static void table_header_plan(int N, int S, int M, int L, int Lq, int P, int &W, int &tp_cap)
+// What a forward leaves in the table buffer for the backward of the same autograd node (msda_forward_ws_*): large problems
+// (LDS-stage forward) the per-point range masks, where role B reads them; small ones the point table and its range header,
+// where the backward takes the small-problem role B (plan_fused.fixed: single pass, every workgroup resident).
+// The forward writes the buffer and the backward reads it whatever the row storage and the flags of either call, so the
+// layout is planned for ONE combination — fp32 rows, fp32 grad_value, no deterministic flag — here and nowhere else.  (A
+// backward reads masks only where its own role-B plan is that one: plan_backward.)
+// prologue: the fused-prologue entry points (whole queries per role-A workgroup change the split).
+struct TablePlan { bool large; ValuePlan value; MaskPlan masks; size_t bytes; };
+static TablePlan plan_table(int N, int S, int M, int L, int Lq, int P, bool prologue)
 {
-    // (W >= 1 always: the header's magic is the table's "written" stamp; a plan with more slots than the header holds gets
-    // the stamp and no entries — write_range_header)
-    const ValuePlan pl = plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), false);
-    W = pl.W;
-    tp_cap = pl.tp_cap;
+    TablePlan tp{};
+    tp.large = plan_lds<float>(N, S, M, L, Lq, P).use;
+    // (value.W >= 1 always: the range header's magic is the point table's "written" stamp; a plan with more slots than the
+    // header holds gets the stamp and no entries — write_range_header)
+    tp.value = plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), false);
+    if (tp.large) {
+        tp.masks = plan_masks(tp.value, N, M, L, Lq, P);
+        tp.bytes = tp.masks.use ? tp.masks.bytes : 0;
+    } else if (tp.value.acc == kAccNone && tp.value.ppt == kSinglePPT) {
+        const int items = N * Lq * M;
+        const FusedPlan fp = plan_fused(items, L * P, pick_split(items, L * P), (long long)tp.value.W * N * M * L, tp.value.acc,
+                                        prologue ? M : 0, false);
+        if (fp.fixed) tp.bytes = (size_t)N * M * L * Lq * P * sizeof(PointEntry) + range_header_bytes();
+    }
+    return tp;
+}
+
+// The whole decision of a D = 32 backward call.  Every threshold on the way from a geometry to a launch, and every bound
+// on a grid size, is in this function; launch_bwd_d32_t launches what it says, msda_describe_plan prints it and
+// backward_workspace_bytes sizes the scratch from it.
+//   kBwdFusedLds     one launch: role B, and role A on the LDS-stage body (large problems)
+//   kBwdFused        one launch: role B, and role A on the tiled body (`fused.fixed`: the small-problem role B)
+//   kBwdTwoLaunches  role B (or, tuning builds, the v1 atomic scatter: `atomic`), then role A (`lds_a.use`: LDS stage,
+//                    else tiled with `fused.split` wavefronts per octet in 256-thread workgroups)
+//   kBwdUnsupported  the call is refused with `why` (the fused prologue has no two-launch kernels)
+enum BwdKind { kBwdFusedLds, kBwdFused, kBwdTwoLaunches, kBwdUnsupported };
+struct BwdPlan {
+    BwdKind kind;
+    const char *why;
+    bool det, atomic;
+    ValuePlan value;          // role B
+    LdsPlan lds_a;            // role A on the LDS stage, cut for the slots role B leaves
+    FusedPlan fused;
+    long long nB, nA;         // workgroups of role B and of role A
+    size_t lds;               // dynamic LDS of the launch that holds role A (role B alone: value.lds)
+    bool dense, masks;        // kBwdFusedLds: coarse levels on the matrix cores; role B reads the forward's range masks
+    bool heads_scratch;       // kBwdFusedLds with the prologue: role A sees one head per workgroup and leaves grad_ref per head
+                              // ([N, Lq, M, L, 2]) in the caller's scratch for ref_heads_reduce_kernel
+};
+
+// VT = storage of value / grad_out, GT = storage of grad_value (VT, or float for bf16 rows).  table: the plan of the
+// forward's table where the call has one (plan_table), else null; scratch_bytes / scratch_aligned: the scratch the caller
+// handed over (8-byte alignment).
+template <typename VT, typename GT>
+static BwdPlan plan_backward(int N, int S, int M, int L, int Lq, int P, bool prologue, bool deterministic, bool no_dense,
+                             const TablePlan *table, size_t scratch_bytes, bool scratch_aligned)
+{
+    constexpr long long kMaxGrid = 0x7fffffffLL;
+    const int items = N * Lq * M, LP = L * P;
+    const int item_stride = LP * kRecBytes + kItemPad;
+    BwdPlan bp{};
+    // deterministic (MSDA_FLAG_DETERMINISTIC): the same launches with role B's DET instantiations (per-wavefront counters,
+    // msda_d32_value.h) and without the short sort, which ranks a row's records in arrival order
+    bp.det = deterministic;
+    bp.fused = FusedPlan{pick_split(items, LP), false};
+    auto refuse = [&](const char *why) { bp.kind = kBwdUnsupported; bp.why = why; return bp; };
+    auto tiled_lds = [&](int ipw) { return (size_t)ipw * item_stride + (size_t)ipw * LP * 16; };   // role A's records and results
+    // tuning / A-B knob, read once per process: MSDA_BWD_MODE=atomic selects the v1 global-atomic scatter (fp32 only),
+    // =split launches role B and role A as two kernels.  (Never with the prologue: prologue_supported.)
+    static const int mode_env = [] {                       // 0 fused (default), 1 split launches, 2 v1 atomics
+        const char *v = tuning_str("MSDA_BWD_MODE");
+        return (v && !strcmp(v, "atomic")) ? 2 : (v && !strcmp(v, "split")) ? 1 : 0; }();
+    const int mode = (prologue || (mode_env == 2 && (sizeof(VT) != 4 || deterministic))) ? 0 : mode_env;
+    const int ipw_alone = 32 / bp.fused.split;             // role A as its own 256-thread launch
+    if (mode == 2) {
+        bp.kind = kBwdTwoLaunches; bp.atomic = true;
+        bp.nA = ceil_div(items, ipw_alone); bp.lds = tiled_lds(ipw_alone);
+        return bp;
+    }
+    // (an fp32 grad_value without the deterministic flag is the combination the table was planned for: role B is planned once)
+    const bool as_table = table && sizeof(GT) == 4 && !deterministic;
+    const ValuePlan &pl = bp.value = as_table ? table->value : plan_value<GT>(N, S, M, L, Lq, P, bwd_target_wgs(), deterministic);
+    bp.nB = (long long)pl.W * N * M * L;
+    bp.lds_a = plan_lds<VT>(N, S, M, L, Lq, P, bp.nB);
+    // the fused kernels hold the single-pass and the kept-taps role B
+    const bool fusable = mode == 0 && pl.ppt == kSinglePPT && pl.acc != kAccTile;
+    const FusedPlan fp = (prologue || !bp.lds_a.use) ? plan_fused(items, LP, bp.fused.split, bp.nB, pl.acc, prologue ? M : 0, deterministic)
+                                                     : bp.fused;
+    const int ipw_f = kSWaves * 8 / fp.split;              // 512-thread role-A workgroups
+    const long long nA_tiled = ceil_div(items, ipw_f), nA_lds = (long long)N * M * bp.lds_a.chunks;
+    if (prologue && (!fusable || bp.nB + nA_tiled > kMaxGrid)) return refuse("msda backward (fused prologue): geometry not supported");
+    const bool scratch_ok = !prologue || (scratch_aligned && scratch_bytes >= prologue_heads_bytes(N, M, L, Lq));
+    if (fusable && bp.lds_a.use && (pl.acc == kAccNone || pl.acc == kAccWide) && scratch_ok && bp.nB + nA_lds <= kMaxGrid) {
+        bp.kind = kBwdFusedLds;
+        bp.nA = nA_lds;
+        // (at least what the dense coarse-level body needs: two such workgroups still share a CU)
+        bp.lds = max(max(pl.lds, bp.lds_a.lds), (size_t)dense_lds_bytes());
+        bp.dense = dense_on() && pl.W <= MSDA_DENSE_MAX_W && !no_dense;
+        // (only for the role-B plan the forward wrote them for; table->large is lds_a.use: see plan_lds)
+        bp.masks = as_table && table->masks.use;
+        bp.heads_scratch = prologue;
+    } else if (fusable && (prologue || !bp.lds_a.use) && bp.nB + nA_tiled <= kMaxGrid) {
+        // whole backward in one launch when role A's workgroups can share the CUs (LDS)
+        bp.kind = kBwdFused;
+        bp.fused = fp;
+        bp.nA = nA_tiled;
+        bp.lds = max(pl.lds, tiled_lds(ipw_f));
+        if (fp.fixed) bp.lds = max(bp.lds, (size_t)small_lds_bytes(pl.tp_cap, deterministic));
+    } else {
+        // role B as its own launch (large record arrays / bf16 tile / A-B knob)
+        if (bp.nB > kMaxGrid) return refuse("msda backward (d32): too many grad_value workgroups");
+        bp.kind = kBwdTwoLaunches;
+        bp.nA = bp.lds_a.use ? nA_lds : ceil_div(items, ipw_alone);
+        bp.lds = bp.lds_a.use ? bp.lds_a.lds : tiled_lds(ipw_alone);
+    }
+    return bp;
+}
+
+// the table buffer as the forward's mask writer and role B's mask reader see it (use: plan_table / plan_backward say so)
+static MaskOut mask_out(void *table, const MaskPlan &mp)
+{
+    if (!table || !mp.use) return MaskOut{nullptr, nullptr, 0};
+    unsigned char *b = static_cast<unsigned char *>(table);
+    return MaskOut{reinterpret_cast<MaskHeader *>(b), b + sizeof(MaskHeader), mp.W};
+}
+static MaskIn mask_in(const void *table, bool use)
+{
+    if (!table || !use) return MaskIn{nullptr, nullptr};
+    const unsigned char *b = static_cast<const unsigned char *>(table);
+    return MaskIn{reinterpret_cast<const MaskHeader *>(b), b + sizeof(MaskHeader)};
+}
+// the header behind the point entries of a table (null: no table)
+static const RangeHeader *table_header_of(const PointEntry *table, int N, int M, int L, int Lq, int P)
+{
+    if (!table) return nullptr;
+    return reinterpret_cast<const RangeHeader *>(table + (long long)N * M * L * Lq * P);
+}
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+template <typename VT, bool FUSED>
+static int launch_fwd_lds(const LdsPlan &lp, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
+                          const float *attn, int N, int S, int M, int L, int Lq, int P, VT *out, const PrologueIn &pro,
+                          hipStream_t stream, const MaskOut mo = MaskOut{nullptr, nullptr, 0})
+{
+    const dim3 grid((unsigned)(N * M * lp.chunks));
+    // (with masks to write: the ranges' first pixels [L][W + 1] and a float scale per level behind the records)
+    const size_t lds = lp.lds + (mo.masks ? (size_t)(L * (mo.W + 1) + L) * sizeof(int) : 0);
+#define MSDA_LAUNCH_FL(NS_)                                                                            \
+    do { if (int rc = allow_lds(reinterpret_cast<const void *>(fwd_d32_lds_kernel<VT, FUSED, NS_>), lds)) return rc;               \
+         hipLaunchKernelGGL((fwd_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lds, stream, value, shapes, level_start,    \
+                            loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw, lp.stage_rows, out,   \
+                            pro, xcd_remap(), mo); } while (0)
+    if (8 * L * P <= kWave) MSDA_LAUNCH_FL(1); else MSDA_LAUNCH_FL(2);             // plan_lds: L*P <= 16
+#undef MSDA_LAUNCH_FL
+    return check_launch("msda forward (d32, LDS stage)");
+}
+
+template <typename VT, bool FUSED>
+static int launch_query_lds(const LdsPlan &lp, const VT *grad_out, const VT *value, const int64_t *shapes,
+                            const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L, int Lq,
+                            int P, float *grad_loc, float *grad_attn, const PrologueOut &pro, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(N * M * lp.chunks));
+#define MSDA_LAUNCH_QL(NS_)                                                                            \
+    do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_query_d32_lds_kernel<VT, FUSED, NS_>), lp.lds)) return rc;      \
+         hipLaunchKernelGGL((bwd_query_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lp.lds, stream, grad_out, value,      \
+                            shapes, level_start, loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw,  \
+                            lp.stage_rows, grad_loc, grad_attn, pro, xcd_remap()); } while (0)
+    if (8 * L * P <= kWave) MSDA_LAUNCH_QL(1); else MSDA_LAUNCH_QL(2);             // plan_lds: L*P <= 16
+#undef MSDA_LAUNCH_QL
+    return check_launch("msda backward (d32, query-major, LDS stage)");
+}
+
+// The forward, plain (FUSED = false: `loc` / `attn` are the sampling locations and attention weights, `pro` is empty) or with
+// the fused prologue (raw offsets and logits; see PrologueIn).  table (may be null): the buffer to fill per plan_table.
+template <typename VT, bool FUSED>
+static int launch_fwd_d32_t(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
+                            const float *attn, int N, int S, int M, int L, int Lq, int P, VT *out, const PrologueIn &pro,
+                            hipStream_t stream, PointEntry *table)
+{
+    const TablePlan tp = table ? plan_table(N, S, M, L, Lq, P, FUSED) : TablePlan{};
+    const LdsPlan lp = plan_lds<VT>(N, S, M, L, Lq, P);
+    if (lp.use)
+        return launch_fwd_lds<VT, FUSED>(lp, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, pro, stream,
+                                         mask_out(table, tp.masks));
+    const int items = N * Lq * M, LP = L * P;
+    const int item_stride = LP * kRecBytes + kItemPad;
+    const int split = pick_split(items, LP);
+    const int ipw = 32 / split;
+    const size_t lds = (size_t)ipw * item_stride + (split > 1 ? 4096 : 0);
+    const int hdr_W = table ? tp.value.W : 0, hdr_tp_cap = table ? tp.value.tp_cap : 0;   // role B's ranges, for the table's header
+    const dim3 grid((items + ipw - 1) / ipw + (hdr_W > 0 ? 1 : 0)), block(kBlock);      // (+ the header's workgroup)
+#define MSDA_LAUNCH_FWD(SP)                                                                            \
+    hipLaunchKernelGGL((fwd_d32_kernel<SP, VT, FUSED>), grid, block, lds, stream, value, shapes, level_start, loc, attn, \
+                       S, M, L, Lq, P, items, pow2_shift(P), pow2_shift(LP), pow2_shift(M), out, pro, xcd, table, hdr_W,  \
+                       hdr_tp_cap, kSmallRecCap)
+    const int xcd = xcd_remap();
+    if (split == 4) MSDA_LAUNCH_FWD(4); else if (split == 2) MSDA_LAUNCH_FWD(2); else MSDA_LAUNCH_FWD(1);
+#undef MSDA_LAUNCH_FWD
+    return check_launch(FUSED ? "msda forward (d32, fused prologue)" : "msda forward (d32)");
 }
 
 #if MSDA_D32_HAS(0)
@@ -1047,173 +1151,145 @@ static void table_header_plan(int N, int S, int M, int L, int Lq, int P, int &W,
 // allocator may hand the same block out again — for this call's.
 int invalidate_forward_table(void *table, int N, int S, int M, int L, int Lq, int P, hipStream_t stream)
 {
-    const size_t off = plan_lds<float>(N, S, M, L, Lq, P).use ? 0 : (size_t)N * M * L * Lq * P * sizeof(PointEntry);
+    const size_t off = plan_table(N, S, M, L, Lq, P, false).large ? 0 : (size_t)N * M * L * Lq * P * sizeof(PointEntry);
     static_assert(offsetof(RangeHeader, magic) == 0 && offsetof(MaskHeader, magic) == 0, "the stamp is the header's first word");
     const hipError_t e = hipMemsetAsync(static_cast<unsigned char *>(table) + off, 0, sizeof(int), stream);
     return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
 }
 
-// Bytes of the point table a forward of this geometry can leave for its backward (msda_forward_workspace_bytes): non-zero
-// exactly where the backward would take the small-problem role B (plan_fused.fixed: single pass, every workgroup resident,
-// no LDS stage) — the same plan functions the launchers run.  prologue: the fused-prologue entry points (whole queries per
-// role-A workgroup change the split).
+// Bytes of the table a forward of this geometry can leave for its backward (msda_forward_workspace_bytes): plan_table.
 size_t forward_table_bytes(int N, int S, int M, int D, int L, int Lq, int P, bool prologue)
 {
     if (!d32_supported(N, S, M, D, L, Lq, P) || (prologue && !prologue_supported(N, S, M, D, L, Lq, P))) return 0;
-    if (plan_lds<float>(N, S, M, L, Lq, P).use) {                       // large problems: per-point range masks, if role B reads them
-        const MaskPlan mm = plan_masks(N, S, M, L, Lq, P);
-        return mm.use ? mm.bytes : 0;
-    }
-    const ValuePlan pl = plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), false);
-    if (pl.acc != kAccNone || pl.ppt != kSinglePPT) return 0;
-    const FusedPlan fp = plan_fused(N * Lq * M, L * P, pick_split(N * Lq * M, L * P), (long long)pl.W * N * M * L, pl.acc, prologue ? M : 0, false);
-    return fp.fixed ? (size_t)N * M * L * Lq * P * sizeof(PointEntry) + range_header_bytes() : 0;
+    return plan_table(N, S, M, L, Lq, P, prologue).bytes;
 }
 
-
+// Only the fused-prologue backward on large problems needs scratch (BwdPlan::heads_scratch): the deterministic kernels
+// (MSDA_FLAG_DETERMINISTIC) order a row's records through per-wavefront counters in LDS.  Like the table, the answer must not
+// depend on the row storage of the call that follows: it is planned for fp32 rows.
 size_t backward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags)
 {
-    if (!d32_supported(N, S, M, D, L, Lq, P)) return 0;
-    // The fused-prologue backward on large problems: role A sees one head per workgroup and leaves the reference-point
-    // gradient per head ([N, Lq, M, L, 2]) for ref_heads_reduce_kernel.  Nothing else needs scratch: the deterministic
-    // kernels (MSDA_FLAG_DETERMINISTIC) order a row's records through per-wavefront counters in LDS.
-    if ((flags & MSDA_FLAG_PROLOGUE) && plan_lds<float>(N, S, M, L, Lq, P).use) return prologue_heads_bytes(N, M, L, Lq);
-    return 0;
+    if (!d32_supported(N, S, M, D, L, Lq, P) || !(flags & MSDA_FLAG_PROLOGUE)) return 0;
+    const BwdPlan bp = plan_backward<float, float>(N, S, M, L, Lq, P, true, (flags & MSDA_FLAG_DETERMINISTIC) != 0, false, nullptr,
+                                                   ~(size_t)0, true);
+    return bp.heads_scratch ? prologue_heads_bytes(N, M, L, Lq) : 0;
 }
 #endif
 
-// VT = storage of value / grad_out, GT = storage of grad_value (VT, or float for bf16 rows)
-template <typename VT, typename GT = VT>
-static int launch_bwd_d32_t(const VT *grad_out, const VT *value, const int64_t *shapes,
-                            const int64_t *level_start, const float *loc, const float *attn, int N, int S,
-                            int M, int L, int Lq, int P, GT *grad_value, float *grad_loc, float *grad_attn,
-                            hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool deterministic = false,
-                            const PointEntry *table = nullptr, bool no_dense = false)
+// Launches what `bp` says (plan_backward) and decides nothing.  FUSED: the fused prologue — grad_loc / grad_attn are the
+// gradients of the raw offsets / logits and `pro` carries grad_ref and their row padding (PrologueOut); its kernels exist for
+// an fp32 grad_value and the single-launch plans only.  scratch: BwdPlan::heads_scratch.  table: the forward's, or null.
+template <typename VT, typename GT, bool FUSED>
+static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *value, const int64_t *shapes,
+                            const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L, int Lq,
+                            int P, GT *grad_value, float *grad_loc, float *grad_attn, const PrologueOut &pro, void *scratch,
+                            const void *table, hipStream_t stream)
 {
+    if (bp.kind == kBwdUnsupported) return set_error(MSDA_ERR_ARGUMENT, bp.why);
     const int items = N * Lq * M, LP = L * P;
-    const int item_stride = LP * kRecBytes + kItemPad;
-    // deterministic (MSDA_FLAG_DETERMINISTIC): the same launches with role B's DET instantiations (per-wavefront counters,
-    // msda_d32_value.h) and without the short sort, which ranks a row's records in arrival order
-    // tuning / A-B knobs, read once per process: MSDA_BWD_MODE=atomic selects the v1 global-atomic
-    // scatter (fp32 only), =split launches role B and role A as two kernels; MSDA_BWD_WGS is the number
-    // of role-B workgroups to aim for on small problems.
-    static const int bwd_mode_env = [] {                   // 0 fused (default), 1 split launches, 2 v1 atomics
-        const char *v = tuning_str("MSDA_BWD_MODE");
-        return (v && !strcmp(v, "atomic")) ? 2 : (v && !strcmp(v, "split")) ? 1 : 0; }();
-    const int bwd_mode = (bwd_mode_env == 2 && (sizeof(VT) != 4 || deterministic)) ? 0 : bwd_mode_env;
-    const int target_wgs = bwd_target_wgs();
-    const int split = pick_split(items, LP);
     const int ps = pow2_shift(P), lps = pow2_shift(LP), ms = pow2_shift(M);
     const int xcd = xcd_remap();
-    // large problems: role A as its own launch with the coarse levels in LDS (msda_d32_lds.h), role B as its own launch
-    LdsPlan lds_a = plan_lds<VT>(N, S, M, L, Lq, P);
-    if (bwd_mode == 2) lds_a.use = false;
-
-#ifdef MSDA_TUNING
-    if (bwd_mode == 2) {
-        hipError_t e = hipMemsetAsync(grad_value, 0, sizeof(GT) * (size_t)N * S * M * kD, stream);
-        if (e != hipSuccess) return set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
-    } else
-#endif
-    {
-        const ValuePlan pl = plan_value<GT>(N, S, M, L, Lq, P, target_wgs, deterministic);
-        const long long nB = (long long)pl.W * N * M * L;
-        // ---- large problems: one launch, role A on the LDS-stage body ----
-        if (lds_a.use) lds_a = plan_lds<VT>(N, S, M, L, Lq, P, nB);      // cut role A for the slots role B leaves
-        if (bwd_mode == 0 && lds_a.use && pl.ppt == kSinglePPT && (pl.acc == kAccNone || pl.acc == kAccWide) &&
-            nB + (long long)N * M * lds_a.chunks <= 0x7fffffffLL) {
-            const dim3 fgrid((unsigned)(nB + (long long)N * M * lds_a.chunks));
-            // (at least what the dense coarse-level body needs: two such workgroups still share a CU)
-            const size_t flds = max(max(pl.lds, lds_a.lds), (size_t)dense_lds_bytes());
-            const bool dense = dense_on() && pl.W <= MSDA_DENSE_MAX_W && !no_dense;
-            const MaskIn masks = mask_in(table, N, S, M, L, Lq, P, pl.acc, pl.W, deterministic);
+    const ValuePlan &pl = bp.value;
+    const LdsPlan &la = bp.lds_a;
+    const dim3 fgrid((unsigned)(bp.nB + bp.nA));           // both roles in one launch
+    if (bp.kind == kBwdFusedLds) {
+        PrologueOut pro_a = pro;
+        if (bp.heads_scratch) pro_a.grad_ref = static_cast<float *>(scratch);
+        const MaskIn masks = mask_in(table, bp.masks);
 #define MSDA_LAUNCH_FLD__(AC, NS_, DT, DN)                                                             \
-            do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_lds_d32_kernel<AC, VT, false, GT, NS_, DT, DN>), flds)) return rc; \
-            hipLaunchKernelGGL((bwd_fused_lds_d32_kernel<AC, VT, false, GT, NS_, DT, DN>), fgrid, dim3(kSBlock), flds, stream, grad_out,  \
-                               value, shapes, level_start, loc, attn, S, M, L, Lq, P, ps, lps, pl.tp_cap, pl.W, (int)nB,          \
-                               lds_a.chunks, lds_a.qw, lds_a.stage_rows, grad_value, grad_loc, grad_attn,                        \
-                               PrologueOut{nullptr, 0, 0}, xcd, (DN) ? (int)flds : 0, masks); } while (0)
-#define MSDA_LAUNCH_FLD_(AC, NS_, DT) do { if (dense) MSDA_LAUNCH_FLD__(AC, NS_, DT, true); else MSDA_LAUNCH_FLD__(AC, NS_, DT, false); } while (0)
-#define MSDA_LAUNCH_FLD(AC, NS_) do { if (deterministic) MSDA_LAUNCH_FLD_(AC, NS_, true); else MSDA_LAUNCH_FLD_(AC, NS_, false); } while (0)
-            const bool one_slot = 8 * LP <= kWave;
-            if (pl.acc == kAccNone) { if (one_slot) MSDA_LAUNCH_FLD(kAccNone, 1); else MSDA_LAUNCH_FLD(kAccNone, 2); }
-            else                    { if (one_slot) MSDA_LAUNCH_FLD(kAccWide, 1); else MSDA_LAUNCH_FLD(kAccWide, 2); }
+        do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_lds_d32_kernel<AC, VT, FUSED, GT, NS_, DT, DN>), bp.lds)) return rc; \
+        hipLaunchKernelGGL((bwd_fused_lds_d32_kernel<AC, VT, FUSED, GT, NS_, DT, DN>), fgrid, dim3(kSBlock), bp.lds, stream, grad_out, \
+                           value, shapes, level_start, loc, attn, S, M, L, Lq, P, ps, lps, pl.tp_cap, pl.W, (int)bp.nB,          \
+                           la.chunks, la.qw, la.stage_rows, grad_value, grad_loc, grad_attn, pro_a, xcd,                         \
+                           (DN) ? (int)bp.lds : 0, masks); } while (0)
+#define MSDA_LAUNCH_FLD_(AC, NS_, DT) do { if (bp.dense) MSDA_LAUNCH_FLD__(AC, NS_, DT, true); else MSDA_LAUNCH_FLD__(AC, NS_, DT, false); } while (0)
+#define MSDA_LAUNCH_FLD(AC, NS_) do { if (bp.det) MSDA_LAUNCH_FLD_(AC, NS_, true); else MSDA_LAUNCH_FLD_(AC, NS_, false); } while (0)
+        const bool one_slot = 8 * LP <= kWave;
+        if (pl.acc == kAccNone) { if (one_slot) MSDA_LAUNCH_FLD(kAccNone, 1); else MSDA_LAUNCH_FLD(kAccNone, 2); }
+        else                    { if (one_slot) MSDA_LAUNCH_FLD(kAccWide, 1); else MSDA_LAUNCH_FLD(kAccWide, 2); }
 #undef MSDA_LAUNCH_FLD
 #undef MSDA_LAUNCH_FLD_
 #undef MSDA_LAUNCH_FLD__
-            return check_launch("msda backward (d32, fused, LDS stage)");
+        const int rc = check_launch(FUSED ? "msda backward (d32, fused prologue, LDS stage)" : "msda backward (d32, fused, LDS stage)");
+        if constexpr (FUSED) {
+            if (rc) return rc;
+            const long long cells = (long long)N * Lq * L;
+            hipLaunchKernelGGL(ref_heads_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream,
+                               reinterpret_cast<const float2 *>(scratch), N * Lq, M, L, reinterpret_cast<float2 *>(pro.grad_ref));
+            return check_launch("msda backward (d32, reference-point gradient over heads)");
         }
-        // ---- whole backward in one launch when role A's workgroups can share the CUs (LDS) ----
-        if (bwd_mode == 0 && pl.ppt == kSinglePPT && pl.acc != kAccTile && !lds_a.use) {
-            const FusedPlan fp = plan_fused(items, LP, split, nB, pl.acc, 0, deterministic);
-            const int ipw_f = 64 / fp.split;                            // 512-thread role-A workgroups
-            const size_t lds_a = (size_t)ipw_f * item_stride + (size_t)ipw_f * LP * 16;
-            const long long nA = (items + ipw_f - 1) / ipw_f;
-            if (nB + nA <= 0x7fffffffLL) {
-                const dim3 fgrid((unsigned)(nB + nA));
-                size_t flds = pl.lds > lds_a ? pl.lds : lds_a;
-                if (fp.fixed) flds = max(flds, small_lds_bytes(pl.tp_cap, deterministic));
+        return rc;
+    }
+    if (bp.kind == kBwdFused) {
+        const FusedPlan &fp = bp.fused;
+        const PointEntry *points = static_cast<const PointEntry *>(table);    // read by the small-problem role B only
 #define MSDA_LAUNCH_F_(SP, AC, FX, DT)                                                                 \
-                do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_d32_kernel<SP, AC, VT, false, GT, FX, DT>), flds)) return rc; \
-                hipLaunchKernelGGL((bwd_fused_d32_kernel<SP, AC, VT, false, GT, FX, DT>), fgrid, dim3(kSBlock), flds, stream,  \
-                                   grad_out, value, shapes, level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms,  \
-                                   pl.tp_cap, pl.W, (int)nB, grad_value, grad_loc, grad_attn, PrologueOut{nullptr, 0, 0}, xcd,  \
-                                   (FX) ? table : nullptr, (FX) ? table_header_of(table, N, M, L, Lq, P, pl.W) : nullptr); } while (0)
-#define MSDA_LAUNCH_F(SP, AC, FX) do { if (deterministic) MSDA_LAUNCH_F_(SP, AC, FX, true); else MSDA_LAUNCH_F_(SP, AC, FX, false); } while (0)
-                if (fp.fixed)                { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, true); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, true); else MSDA_LAUNCH_F(1, kAccNone, true); }
-                else if (pl.acc == kAccNone) { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, false); else MSDA_LAUNCH_F(1, kAccNone, false); }
-                else if (pl.acc == kAccWide) { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccWide, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccWide, false); else MSDA_LAUNCH_F(1, kAccWide, false); }
-#ifdef MSDA_TUNING                                                       // kAccRmw is only ever planned with MSDA_BWD_WIDE=0
-                else                         { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccRmw, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccRmw, false); else MSDA_LAUNCH_F(1, kAccRmw, false); }
-#else
-                else return set_error(MSDA_ERR_LAUNCH, "msda backward (d32): unplanned accumulation mode");
-#endif
-#undef MSDA_LAUNCH_F
-#undef MSDA_LAUNCH_F_
-                return check_launch("msda backward (d32, fused)");
-            }
-        }
-        // ---- role B as its own launch (large record arrays / bf16 tile / A-B knob) ----
-        if (nB > 0x7fffffffLL) return set_error(MSDA_ERR_ARGUMENT, "msda backward (d32): too many grad_value workgroups");
-        const dim3 grid((unsigned)nB);
-#define MSDA_LAUNCH_B_(AC, PPT_, DT)                                                                   \
-        do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), pl.lds)) return rc; \
-             hipLaunchKernelGGL((bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), grid, dim3(kSBlock), pl.lds, stream, grad_out,    \
-                                shapes, level_start, loc, attn, S, M, L, Lq, P, ps, pl.tp_cap, pl.W, grad_value, xcd); } while (0)
-#define MSDA_LAUNCH_B(AC, PPT_) do { if (deterministic) MSDA_LAUNCH_B_(AC, PPT_, true); else MSDA_LAUNCH_B_(AC, PPT_, false); } while (0)
-        if (pl.acc == kAccNone) MSDA_LAUNCH_B(kAccNone, kSinglePPT);
-        else if (pl.acc == kAccTile) MSDA_LAUNCH_B(kAccTile, kMultiPPT);
-        else if (pl.acc == kAccWide) MSDA_LAUNCH_B(kAccWide, kSinglePPT);
-#ifdef MSDA_TUNING
-        else if (pl.ppt == kMultiPPT) MSDA_LAUNCH_B(kAccRmw, kMultiPPT);
-        else MSDA_LAUNCH_B(kAccRmw, kSinglePPT);
+        do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_d32_kernel<SP, AC, VT, FUSED, GT, FX, DT>), bp.lds)) return rc; \
+        hipLaunchKernelGGL((bwd_fused_d32_kernel<SP, AC, VT, FUSED, GT, FX, DT>), fgrid, dim3(kSBlock), bp.lds, stream,      \
+                           grad_out, value, shapes, level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms,              \
+                           pl.tp_cap, pl.W, (int)bp.nB, grad_value, grad_loc, grad_attn, pro, xcd,                           \
+                           (FX) ? points : nullptr, (FX) ? table_header_of(points, N, M, L, Lq, P) : nullptr); } while (0)
+#define MSDA_LAUNCH_F(SP, AC, FX) do { if (bp.det) MSDA_LAUNCH_F_(SP, AC, FX, true); else MSDA_LAUNCH_F_(SP, AC, FX, false); } while (0)
+        if (fp.fixed)                { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, true); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, true); else MSDA_LAUNCH_F(1, kAccNone, true); }
+        else if (pl.acc == kAccNone) { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, false); else MSDA_LAUNCH_F(1, kAccNone, false); }
+        else if (pl.acc == kAccWide) { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccWide, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccWide, false); else MSDA_LAUNCH_F(1, kAccWide, false); }
+#ifdef MSDA_TUNING                                               // kAccRmw is only ever planned with MSDA_BWD_WIDE=0
+        else                         { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccRmw, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccRmw, false); else MSDA_LAUNCH_F(1, kAccRmw, false); }
 #else
         else return set_error(MSDA_ERR_LAUNCH, "msda backward (d32): unplanned accumulation mode");
 #endif
+#undef MSDA_LAUNCH_F
+#undef MSDA_LAUNCH_F_
+        return check_launch(FUSED ? "msda backward (d32, fused prologue)" : "msda backward (d32, fused)");
+    }
+    if constexpr (FUSED) {
+        return set_error(MSDA_ERR_ARGUMENT, "msda backward (fused prologue): geometry not supported");
+    } else {
+        // ---- kBwdTwoLaunches: role B (large record arrays / bf16 tile / A-B knob), then role A ----
+#ifdef MSDA_TUNING
+        if (bp.atomic) {
+            const hipError_t e = hipMemsetAsync(grad_value, 0, sizeof(GT) * (size_t)N * S * M * kD, stream);
+            if (e != hipSuccess) return set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
+        } else
+#endif
+        {
+            const dim3 grid((unsigned)bp.nB);
+#define MSDA_LAUNCH_B_(AC, PPT_, DT)                                                                   \
+            do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), pl.lds)) return rc; \
+                 hipLaunchKernelGGL((bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), grid, dim3(kSBlock), pl.lds, stream, grad_out,    \
+                                    shapes, level_start, loc, attn, S, M, L, Lq, P, ps, pl.tp_cap, pl.W, grad_value, xcd); } while (0)
+#define MSDA_LAUNCH_B(AC, PPT_) do { if (bp.det) MSDA_LAUNCH_B_(AC, PPT_, true); else MSDA_LAUNCH_B_(AC, PPT_, false); } while (0)
+            if (pl.acc == kAccNone) MSDA_LAUNCH_B(kAccNone, kSinglePPT);
+            else if (pl.acc == kAccTile) MSDA_LAUNCH_B(kAccTile, kMultiPPT);
+            else if (pl.acc == kAccWide) MSDA_LAUNCH_B(kAccWide, kSinglePPT);
+#ifdef MSDA_TUNING
+            else if (pl.ppt == kMultiPPT) MSDA_LAUNCH_B(kAccRmw, kMultiPPT);
+            else MSDA_LAUNCH_B(kAccRmw, kSinglePPT);
+#else
+            else return set_error(MSDA_ERR_LAUNCH, "msda backward (d32): unplanned accumulation mode");
+#endif
 #undef MSDA_LAUNCH_B
 #undef MSDA_LAUNCH_B_
-        if (int rc = check_launch("msda backward (d32, grad_value sort+gather)")) return rc;
-    }
-    if (lds_a.use)
-        return launch_query_lds<VT, false>(lds_a, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_loc,
-                                           grad_attn, PrologueOut{nullptr, 0, 0}, stream);
-    {
-        const int ipw = 32 / split;
-        const size_t lds = (size_t)ipw * item_stride + (size_t)ipw * LP * 16;
-        const dim3 grid((items + ipw - 1) / ipw), block(kBlock);
+            if (int rc = check_launch("msda backward (d32, grad_value sort+gather)")) return rc;
+        }
+        if (la.use)
+            return launch_query_lds<VT, false>(la, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_loc,
+                                               grad_attn, pro, stream);
+        const int split = bp.fused.split;
+        const dim3 grid((unsigned)bp.nA), block(kBlock);
 #define MSDA_LAUNCH_A(SP, AT)                                                                          \
-        hipLaunchKernelGGL((bwd_query_d32_kernel<SP, AT, VT>), grid, block, lds, stream, grad_out, value, shapes, \
+        hipLaunchKernelGGL((bwd_query_d32_kernel<SP, AT, VT>), grid, block, bp.lds, stream, grad_out, value, shapes, \
                            level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms, gv_atomic, grad_loc, grad_attn, xcd)
         VT *gv_atomic = nullptr;                                        // only the v1 atomic scatter writes grad_value here
         if constexpr (sizeof(VT) == sizeof(GT)) gv_atomic = grad_value;
 #ifdef MSDA_TUNING
-        if (bwd_mode == 2) { if (split == 4) MSDA_LAUNCH_A(4, true); else if (split == 2) MSDA_LAUNCH_A(2, true); else MSDA_LAUNCH_A(1, true); }
+        if (bp.atomic) { if (split == 4) MSDA_LAUNCH_A(4, true); else if (split == 2) MSDA_LAUNCH_A(2, true); else MSDA_LAUNCH_A(1, true); }
         else
 #endif
         { if (split == 4) MSDA_LAUNCH_A(4, false); else if (split == 2) MSDA_LAUNCH_A(2, false); else MSDA_LAUNCH_A(1, false); }
 #undef MSDA_LAUNCH_A
+        return check_launch("msda backward (d32, query-major)");
     }
-    return check_launch("msda backward (d32, query-major)");
 }
 
 // ---- fused prologue (fp32 only): see PrologueIn / PrologueOut ----
@@ -1230,204 +1306,90 @@ bool prologue_supported(int N, int S, int M, int D, int L, int Lq, int P)
 }
 #endif
 
-template <typename VT>
-static int launch_fwd_prologue_t(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
-                                 const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                                 long long ld_offsets, long long ld_logits, VT *out, float *loc_out, float *attn_out,
-                                 hipStream_t stream, PointEntry *table = nullptr)
-{
-    const int items = N * Lq * M, LP = L * P;
-    const int item_stride = LP * kRecBytes + kItemPad;
-    const int split = pick_split(items, LP);
-    const int ipw = 32 / split;
-    const size_t lds = (size_t)ipw * item_stride + (split > 1 ? 4096 : 0);
-    int hdr_W = 0, hdr_tp_cap = 0;
-    if (table) table_header_plan(N, S, M, L, Lq, P, hdr_W, hdr_tp_cap);
-    const dim3 grid((items + ipw - 1) / ipw + (hdr_W > 0 ? 1 : 0)), block(kBlock);      // (+ the header's workgroup)
-    const PrologueIn pro{ref, loc_out, attn_out, (int)((ld_offsets - 2LL * M * LP) / 2), (int)(ld_logits - (long long)M * LP)};
-    const LdsPlan lp = plan_lds<VT>(N, S, M, L, Lq, P);
-    if (lp.use)
-        return launch_fwd_lds<VT, true>(lp, value, shapes, level_start, offsets, logits, N, S, M, L, Lq, P, out, pro, stream,
-                                        mask_out(table, N, S, M, L, Lq, P));
-    const int xcd = xcd_remap();
-#define MSDA_LAUNCH_FP(SP)                                                                             \
-    hipLaunchKernelGGL((fwd_d32_kernel<SP, VT, true>), grid, block, lds, stream, value, shapes, level_start, offsets, \
-                       logits, S, M, L, Lq, P, items, pow2_shift(P), pow2_shift(LP), pow2_shift(M), out, pro, xcd, table,   \
-                       hdr_W, hdr_tp_cap, kSmallRecCap)
-    if (split == 4) MSDA_LAUNCH_FP(4); else if (split == 2) MSDA_LAUNCH_FP(2); else MSDA_LAUNCH_FP(1);
-#undef MSDA_LAUNCH_FP
-    return check_launch("msda forward (d32, fused prologue)");
-}
+// ---- exported entries (msda_launch.h): each storage-type combination is instantiated in the object that holds its kernels ----
+// (row padding of the raw offsets / logits and of their gradients, PrologueIn / PrologueOut: ld_* minus the dense width)
+static int offsets_pad(long long ld, int M, int LP) { return (int)((ld - 2LL * M * LP) / 2); }
+static int logits_pad(long long ld, int M, int LP) { return (int)(ld - (long long)M * LP); }
 
-// VT = storage of grad_out / value; grad_value is fp32 for both (bf16 rows: nothing rounded between passes)
 template <typename VT>
-static int launch_bwd_prologue_t(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start,
-                                 const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
-                                 long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                                 float *grad_ref, hipStream_t stream, void *workspace, size_t ws_bytes, bool deterministic,
-                                 const PointEntry *table = nullptr, bool no_dense = false)
+int launch_fwd_d32(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc, const float *attn,
+                   int N, int S, int M, int L, int Lq, int P, VT *out, hipStream_t stream, void *table)
 {
-    const int items = N * Lq * M, LP = L * P;
-    const int item_stride = LP * kRecBytes + kItemPad;
-    const int split = pick_split(items, LP);
-    const int ps = pow2_shift(P), lps = pow2_shift(LP), ms = pow2_shift(M);
-    const ValuePlan pl = plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), deterministic);
-    const long long nB = (long long)pl.W * N * M * L;
-    const FusedPlan fp = plan_fused(items, LP, split, nB, pl.acc, M, deterministic);
-    const int ipw_f = kSWaves * 8 / fp.split;
-    const size_t lds_a = (size_t)ipw_f * item_stride + (size_t)ipw_f * LP * 16;
-    const long long nA = (items + ipw_f - 1) / ipw_f;
-    if (pl.ppt != kSinglePPT || pl.acc == kAccTile || nB + nA > 0x7fffffffLL)
-        return set_error(MSDA_ERR_ARGUMENT, "msda backward (fused prologue): geometry not supported");
-    const PrologueOut pro{grad_ref, (int)((ld_grad_offsets - 2LL * M * LP) / 2), (int)(ld_grad_logits - (long long)M * LP)};
-    // ---- large problems: role A on the LDS-stage body; it leaves grad_ref per head in the caller's scratch ----
-    const LdsPlan lq = plan_lds<VT>(N, S, M, L, Lq, P, nB);
-    const size_t heads_bytes = prologue_heads_bytes(N, M, L, Lq);
-    if (lq.use && workspace != nullptr && ws_bytes >= heads_bytes && ((uintptr_t)workspace & 7) == 0 &&
-        (pl.acc == kAccNone || pl.acc == kAccWide) && nB + (long long)N * M * lq.chunks <= 0x7fffffffLL) {
-        const PrologueOut pro_h{static_cast<float *>(workspace), pro.off_pad, pro.log_pad};
-        const dim3 lgrid((unsigned)(nB + (long long)N * M * lq.chunks));
-        const size_t llds = max(max(pl.lds, lq.lds), (size_t)dense_lds_bytes());
-#define MSDA_LAUNCH_BPL(AC, NS_) do { if (deterministic) MSDA_LAUNCH_BPL_(AC, NS_, true); else MSDA_LAUNCH_BPL_(AC, NS_, false); } while (0)
-        const bool dense = dense_on() && pl.W <= MSDA_DENSE_MAX_W && !no_dense;
-        const MaskIn masks = mask_in(table, N, S, M, L, Lq, P, pl.acc, pl.W, deterministic);
-#define MSDA_LAUNCH_BPL_(AC, NS_, DT) do { if (dense) MSDA_LAUNCH_BPL__(AC, NS_, DT, true); else MSDA_LAUNCH_BPL__(AC, NS_, DT, false); } while (0)
-#define MSDA_LAUNCH_BPL__(AC, NS_, DT, DN)                                                             \
-        do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_lds_d32_kernel<AC, VT, true, float, NS_, DT, DN>), llds)) return rc; \
-        hipLaunchKernelGGL((bwd_fused_lds_d32_kernel<AC, VT, true, float, NS_, DT, DN>), lgrid, dim3(kSBlock), llds, stream, grad_out,   \
-                           value, shapes, level_start, loc, attn, S, M, L, Lq, P, ps, lps, pl.tp_cap, pl.W, (int)nB, lq.chunks,   \
-                           lq.qw, lq.stage_rows, grad_value, grad_offsets, grad_logits, pro_h, xcd_remap(), (DN) ? (int)llds : 0, masks); } while (0)
-        const bool one_slot = 8 * LP <= kWave;
-        if (pl.acc == kAccNone) { if (one_slot) MSDA_LAUNCH_BPL(kAccNone, 1); else MSDA_LAUNCH_BPL(kAccNone, 2); }
-        else                    { if (one_slot) MSDA_LAUNCH_BPL(kAccWide, 1); else MSDA_LAUNCH_BPL(kAccWide, 2); }
-#undef MSDA_LAUNCH_BPL
-#undef MSDA_LAUNCH_BPL_
-#undef MSDA_LAUNCH_BPL__
-        if (int rc = check_launch("msda backward (d32, fused prologue, LDS stage)")) return rc;
-        const long long cells = (long long)N * Lq * L;
-        hipLaunchKernelGGL(ref_heads_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream,
-                           reinterpret_cast<const float2 *>(workspace), N * Lq, M, L, reinterpret_cast<float2 *>(grad_ref));
-        return check_launch("msda backward (d32, reference-point gradient over heads)");
-    }
-    const dim3 fgrid((unsigned)(nB + nA));
-    size_t flds = pl.lds > lds_a ? pl.lds : lds_a;
-    if (fp.fixed) flds = max(flds, small_lds_bytes(pl.tp_cap, deterministic));
-#define MSDA_LAUNCH_BP(SP, AC, FX) do { if (deterministic) MSDA_LAUNCH_BP_(SP, AC, FX, true); else MSDA_LAUNCH_BP_(SP, AC, FX, false); } while (0)
-#define MSDA_LAUNCH_BP_(SP, AC, FX, DT)                                                                \
-    do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_d32_kernel<SP, AC, VT, true, float, FX, DT>), flds)) return rc; \
-    hipLaunchKernelGGL((bwd_fused_d32_kernel<SP, AC, VT, true, float, FX, DT>), fgrid, dim3(kSBlock), flds, stream, grad_out, \
-                       value, shapes, level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms, pl.tp_cap, pl.W, (int)nB,  \
-                       grad_value, grad_offsets, grad_logits, pro, xcd_remap(), (FX) ? table : nullptr,                          \
-                       (FX) ? table_header_of(table, N, M, L, Lq, P, pl.W) : nullptr); } while (0)
-    if (fp.fixed)                { if (fp.split == 4) MSDA_LAUNCH_BP(4, kAccNone, true); else if (fp.split == 2) MSDA_LAUNCH_BP(2, kAccNone, true); else MSDA_LAUNCH_BP(1, kAccNone, true); }
-    else if (pl.acc == kAccNone) { if (fp.split == 4) MSDA_LAUNCH_BP(4, kAccNone, false); else if (fp.split == 2) MSDA_LAUNCH_BP(2, kAccNone, false); else MSDA_LAUNCH_BP(1, kAccNone, false); }
-    else if (pl.acc == kAccWide) { if (fp.split == 4) MSDA_LAUNCH_BP(4, kAccWide, false); else if (fp.split == 2) MSDA_LAUNCH_BP(2, kAccWide, false); else MSDA_LAUNCH_BP(1, kAccWide, false); }
-#ifdef MSDA_TUNING
-    else                         { if (fp.split == 4) MSDA_LAUNCH_BP(4, kAccRmw, false); else if (fp.split == 2) MSDA_LAUNCH_BP(2, kAccRmw, false); else MSDA_LAUNCH_BP(1, kAccRmw, false); }
-#else
-    else return set_error(MSDA_ERR_LAUNCH, "msda backward (d32, fused prologue): unplanned accumulation mode");
-#endif
-#undef MSDA_LAUNCH_BP
-#undef MSDA_LAUNCH_BP_
-    return check_launch("msda backward (d32, fused prologue)");
+    return launch_fwd_d32_t<VT, false>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out,
+                                       PrologueIn{nullptr, nullptr, nullptr, 0, 0}, stream, static_cast<PointEntry *>(table));
 }
-
-#if MSDA_D32_HAS(0)
-int launch_fwd_prologue(const float *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
+template <typename VT>
+int launch_fwd_prologue(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
                         const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                        long long ld_offsets, long long ld_logits, float *out, float *loc_out, float *attn_out,
+                        long long ld_offsets, long long ld_logits, VT *out, float *loc_out, float *attn_out,
                         hipStream_t stream, void *table)
 {
-    return launch_fwd_prologue_t<float>(value, shapes, level_start, ref, offsets, logits, N, S, M, L, Lq, P, ld_offsets, ld_logits,
-                                        out, loc_out, attn_out, stream, static_cast<PointEntry *>(table));
+    const PrologueIn pro{ref, loc_out, attn_out, offsets_pad(ld_offsets, M, L * P), logits_pad(ld_logits, M, L * P)};
+    return launch_fwd_d32_t<VT, true>(value, shapes, level_start, offsets, logits, N, S, M, L, Lq, P, out, pro, stream,
+                                      static_cast<PointEntry *>(table));
 }
-#endif
-#if MSDA_D32_HAS(1)
-int launch_fwd_prologue_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
-                             const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                             long long ld_offsets, long long ld_logits, uint16_t *out, float *loc_out, float *attn_out,
-                             hipStream_t stream, void *table)
+template <typename VT, typename GT>
+int launch_bwd_d32(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
+                   const float *attn, int N, int S, int M, int L, int Lq, int P, GT *grad_value, float *grad_loc,
+                   float *grad_attn, hipStream_t stream, bool deterministic, void *workspace, size_t ws_bytes, bool forward_table,
+                   bool no_dense)
 {
-    return launch_fwd_prologue_t<bf16_t>(value, shapes, level_start, ref, offsets, logits, N, S, M, L, Lq, P, ld_offsets, ld_logits,
-                                         out, loc_out, attn_out, stream, static_cast<PointEntry *>(table));
+    const TablePlan tp = forward_table ? plan_table(N, S, M, L, Lq, P, false) : TablePlan{};
+    const void *table = table_of(workspace, ws_bytes, tp.bytes);
+    const BwdPlan bp = plan_backward<VT, GT>(N, S, M, L, Lq, P, false, deterministic, no_dense, table ? &tp : nullptr, 0, false);
+    return launch_bwd_d32_t<VT, GT, false>(bp, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
+                                           grad_loc, grad_attn, PrologueOut{nullptr, 0, 0}, nullptr, table, stream);
 }
-#endif
-#if MSDA_D32_HAS(0)
-int launch_bwd_prologue(const float *grad_out, const float *value, const int64_t *shapes, const int64_t *level_start,
+template <typename VT>
+int launch_bwd_prologue(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start,
                         const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
                         long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                        float *grad_ref, hipStream_t stream, void *workspace, size_t ws_bytes, bool deterministic, const void *table,
-                        bool no_dense)
+                        float *grad_ref, hipStream_t stream, void *workspace, size_t ws_bytes, bool forward_table,
+                        bool deterministic, bool no_dense)
 {
-    return launch_bwd_prologue_t<float>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                        ld_grad_offsets, ld_grad_logits, grad_offsets, grad_logits, grad_ref, stream, workspace,
-                                        ws_bytes, deterministic, static_cast<const PointEntry *>(table), no_dense);
+    const TablePlan tp = forward_table ? plan_table(N, S, M, L, Lq, P, true) : TablePlan{};
+    const void *table = table_of(workspace, ws_bytes, tp.bytes);
+    const Scratch sc = scratch_behind(workspace, ws_bytes, tp.bytes);
+    const BwdPlan bp = plan_backward<VT, float>(N, S, M, L, Lq, P, true, deterministic, no_dense, table ? &tp : nullptr, sc.bytes,
+                                                aligned_to(sc.p, 8));
+    const PrologueOut pro{grad_ref, offsets_pad(ld_grad_offsets, M, L * P), logits_pad(ld_grad_logits, M, L * P)};
+    return launch_bwd_d32_t<VT, float, true>(bp, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
+                                             grad_offsets, grad_logits, pro, sc.p, table, stream);
 }
-#endif
-#if MSDA_D32_HAS(2)
-int launch_bwd_prologue_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes, const int64_t *level_start,
-                             const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
-                             long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                             float *grad_ref, hipStream_t stream, void *workspace, size_t ws_bytes, bool deterministic,
-                             const void *table, bool no_dense)
-{
-    return launch_bwd_prologue_t<bf16_t>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                         ld_grad_offsets, ld_grad_logits, grad_offsets, grad_logits, grad_ref, stream, workspace,
-                                         ws_bytes, deterministic, static_cast<const PointEntry *>(table), no_dense);
-}
-#endif
 
+#define MSDA_GEOMETRY int, int, int, int, int, int
+#define MSDA_INSTANTIATE_FWD(VT)                                                                                                 \
+    template int launch_fwd_d32<VT>(const VT *, const int64_t *, const int64_t *, const float *, const float *, MSDA_GEOMETRY,   \
+                                    VT *, hipStream_t, void *);                                                                  \
+    template int launch_fwd_prologue<VT>(const VT *, const int64_t *, const int64_t *, const float *, const float *, const float *, \
+                                         MSDA_GEOMETRY, long long, long long, VT *, float *, float *, hipStream_t, void *)
+#define MSDA_INSTANTIATE_BWD(VT, GT)                                                                                             \
+    template int launch_bwd_d32<VT, GT>(const VT *, const VT *, const int64_t *, const int64_t *, const float *, const float *,  \
+                                        MSDA_GEOMETRY, GT *, float *, float *, hipStream_t, bool, void *, size_t, bool, bool)
+#define MSDA_INSTANTIATE_BWD_PROLOGUE(VT)                                                                                        \
+    template int launch_bwd_prologue<VT>(const VT *, const VT *, const int64_t *, const int64_t *, const float *, const float *, \
+                                         MSDA_GEOMETRY, float *, long long, long long, float *, float *, float *, hipStream_t,   \
+                                         void *, size_t, bool, bool, bool)
 #if MSDA_D32_HAS(0)
-int launch_fwd_d32(const float *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                   const float *attn, int N, int S, int M, int L, int Lq, int P, float *out, hipStream_t stream, void *table)
-{
-    return launch_fwd_d32_t<float>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, stream, static_cast<PointEntry *>(table));
-}
-#endif
-#if MSDA_D32_HAS(0)
-int launch_bwd_d32(const float *grad_out, const float *value, const int64_t *shapes, const int64_t *level_start,
-                   const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P,
-                   float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream, void *workspace, size_t ws_bytes,
-                   bool deterministic, const void *table, bool no_dense)
-{
-    return launch_bwd_d32_t<float>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                   grad_loc, grad_attn, stream, workspace, ws_bytes, deterministic, static_cast<const PointEntry *>(table), no_dense);
-}
+MSDA_INSTANTIATE_FWD(float);
+MSDA_INSTANTIATE_BWD(float, float);
+MSDA_INSTANTIATE_BWD_PROLOGUE(float);
 #endif
 #if MSDA_D32_HAS(1)
-int launch_fwd_d32_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                        const float *attn, int N, int S, int M, int L, int Lq, int P, uint16_t *out,
-                        hipStream_t stream, void *table)
-{
-    return launch_fwd_d32_t<bf16_t>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, stream, static_cast<PointEntry *>(table));
-}
-#endif
-#if MSDA_D32_HAS(1)
-int launch_bwd_d32_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes,
-                        const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L,
-                        int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream,
-                        void *workspace, size_t ws_bytes, bool deterministic, const void *table, bool no_dense)
-{
-    return launch_bwd_d32_t<bf16_t>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                    grad_loc, grad_attn, stream, workspace, ws_bytes, deterministic, static_cast<const PointEntry *>(table), no_dense);
-}
+MSDA_INSTANTIATE_FWD(bf16_t);
+MSDA_INSTANTIATE_BWD(bf16_t, bf16_t);
 #endif
 #if MSDA_D32_HAS(2)
-int launch_bwd_d32_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes,
-                             const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L,
-                             int Lq, int P, float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream,
-                             void *workspace, size_t ws_bytes, bool deterministic, const void *table, bool no_dense)
-{
-    return launch_bwd_d32_t<bf16_t, float>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                           grad_loc, grad_attn, stream, workspace, ws_bytes, deterministic, static_cast<const PointEntry *>(table), no_dense);
-}
+MSDA_INSTANTIATE_BWD(bf16_t, float);
+MSDA_INSTANTIATE_BWD_PROLOGUE(bf16_t);
 #endif
 
 #if MSDA_D32_HAS(0)
 int backward_passes(int Lq, int P) { return (Lq * P + kSingleMaxPoints - 1) / kSingleMaxPoints; }
 
-// What the launchers above would do for a geometry, as text (msda_describe_plan, include/msda.h): the same plan functions,
-// nothing launched.  row_bytes = 4 (fp32 rows) or 2 (bf16 rows); gv_bytes the same for grad_value.
+// What the launchers above would do for a geometry, as text (msda_describe_plan, include/msda.h): the forward's plan_lds /
+// pick_split and the BwdPlan launch_bwd_d32_t would be handed — with the forward's table, and with or without enough
+// scratch (has_ws) — nothing launched.  row_bytes = 4 (fp32 rows) or 2 (bf16 rows); gv_bytes the same for grad_value.
 template <typename VT, typename GT>
 static int describe_plan_t(int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det, char *buf, int len, bool no_dense)
 {
@@ -1437,23 +1399,31 @@ static int describe_plan_t(int N, int S, int M, int L, int Lq, int P, bool prolo
     const LdsPlan lf = plan_lds<VT>(N, S, M, L, Lq, P);
     if (lf.use) put("fwd=lds(chunks=%d,qw=%d,stage_rows=%d,wgs=%d)", lf.chunks, lf.qw, lf.stage_rows, N * M * lf.chunks);
     else { const int sp = pick_split(items, LP); put("fwd=tiled(split=%d,wgs=%d)", sp, (items + 32 / sp - 1) / (32 / sp)); }
-    const ValuePlan pl = plan_value<GT>(N, S, M, L, Lq, P, bwd_target_wgs(), det);
-    const long long nB = (long long)pl.W * N * M * L;
-    const char *acc = pl.acc == kAccNone ? "single" : pl.acc == kAccWide ? "wide" : pl.acc == kAccTile ? "tile" : "rmw";
-    const LdsPlan la = plan_lds<VT>(N, S, M, L, Lq, P, nB);
-    const bool lds_ok = la.use && pl.ppt == kSinglePPT && (pl.acc == kAccNone || pl.acc == kAccWide) && (!prologue || has_ws);
-    if (lds_ok)
+    const TablePlan tp = plan_table(N, S, M, L, Lq, P, prologue);
+    const BwdPlan bp = plan_backward<VT, GT>(N, S, M, L, Lq, P, prologue, det, no_dense, &tp, has_ws ? ~(size_t)0 : 0, true);
+    const ValuePlan &pl = bp.value;
+    const char *acc = bp.atomic ? "atomic" : pl.acc == kAccNone ? "single" : pl.acc == kAccWide ? "wide" : pl.acc == kAccTile ? "tile" : "rmw";
+    const int nA = (int)bp.nA;
+    switch (bp.kind) {
+    case kBwdFusedLds:
         // dense_px: a level of at most this many pixels (that the launch deals W workgroups) goes to the matrix cores
         // masks: role B finds its points through the per-point range masks a forward with a workspace leaves (msda_forward_ws_*)
-        put(" bwd=fused_lds(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%d,qw=%d,dense_px=%d%s%s%s)", acc, pl.W, pl.tp_cap, nB, N * M * la.chunks, la.qw,
-            !dense_on() || no_dense || pl.W > MSDA_DENSE_MAX_W ? 0 : pl.W >= 2 ? kDenseMaxRows : kDensePassRows, det ? ",det" : "", prologue ? ",heads_reduce" : "",
-            (!det && pl.acc == kAccWide && plan_masks(N, S, M, L, Lq, P).use && plan_masks(N, S, M, L, Lq, P).W == pl.W) ? ",masks" : "");
-    else if (pl.ppt == kSinglePPT && pl.acc != kAccTile) {
-        const FusedPlan fp = plan_fused(items, LP, pick_split(items, LP), nB, pl.acc, prologue ? M : 0, det);
-        put(" bwd=fused(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%d,split=%d,%s%s)", acc, pl.W, pl.tp_cap, nB,
-            (items + 64 / fp.split - 1) / (64 / fp.split), fp.split, fp.fixed ? "fixed" : "prefix", det ? ",det" : "");
-    } else
-        put(" bwd=two_launches(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%s%s)", acc, pl.W, pl.tp_cap, nB, la.use ? "lds" : "tiled", det ? ",det" : "");
+        put(" bwd=fused_lds(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%d,qw=%d,dense_px=%d%s%s%s)", acc, pl.W, pl.tp_cap, bp.nB, nA, bp.lds_a.qw,
+            !bp.dense ? 0 : pl.W >= 2 ? kDenseMaxRows : kDensePassRows, det ? ",det" : "", bp.heads_scratch ? ",heads_reduce" : "",
+            bp.masks ? ",masks" : "");
+        break;
+    case kBwdFused:
+        put(" bwd=fused(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%d,split=%d,%s%s)", acc, pl.W, pl.tp_cap, bp.nB, nA, bp.fused.split,
+            bp.fused.fixed ? "fixed" : "prefix", det ? ",det" : "");
+        break;
+    case kBwdTwoLaunches:
+        put(" bwd=two_launches(acc=%s,W=%d,tp_cap=%d,roleB=%lld,roleA=%s%s)", acc, pl.W, pl.tp_cap, bp.nB, bp.lds_a.use ? "lds" : "tiled",
+            det ? ",det" : "");
+        break;
+    case kBwdUnsupported:
+        put(" bwd=unsupported(acc=%s,W=%d,tp_cap=%d,roleB=%lld)", acc, pl.W, pl.tp_cap, bp.nB);
+        break;
+    }
     return n;
 }
 int describe_plan(int row_bytes, int gv_bytes, int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det,

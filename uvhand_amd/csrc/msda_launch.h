@@ -37,72 +37,66 @@ int launch_bwd_generic(const VT *grad_out, const VT *value, const int64_t *shape
                        int D, int L, int Lq, int P, T *grad_value, T *grad_loc, T *grad_attn,
                        hipStream_t stream, bool deterministic = false);
 
-// ---- D = 32 fp32 family (msda_d32.hip): the model's shape ------------------------------------
+// ---- D = 32 family (msda_d32.hip): the model's shape -------------------------------------------
+// VT = storage of value / out / grad_out: float, or uint16_t (bf16 bits); loc, attn and their gradients are fp32.
+// GT = storage of grad_value: VT, or float for bf16 rows (nothing is rounded between the passes of a multi-pass backward,
+// and a caller whose value tensor is fp32 needs no conversion of the result).
+// table: the buffer a forward can leave for its backward (forward: written, backward: read), or null.
+// A backward call's workspace: with forward_table (MSDA_FLAG_FORWARD_TABLE) that table first, the call's scratch behind it.
 bool d32_supported(int N, int S, int M, int D, int L, int Lq, int P);
-int launch_fwd_d32(const float *value, const int64_t *shapes, const int64_t *level_start,
-                   const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P,
-                   float *out, hipStream_t stream, void *table = nullptr);
-int launch_bwd_d32(const float *grad_out, const float *value, const int64_t *shapes,
-                   const int64_t *level_start, const float *loc, const float *attn, int N, int S,
-                   int M, int L, int Lq, int P, float *grad_value, float *grad_loc, float *grad_attn,
-                   hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool deterministic = false,
-                   const void *table = nullptr, bool no_dense = false);
-// the point table a small problem's forward can leave for its backward (bytes; 0 = the backward's plan reads none); `table`
-// arguments of the launchers below: that table (forward: written, backward: read), or null
+template <typename VT>
+int launch_fwd_d32(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc, const float *attn,
+                   int N, int S, int M, int L, int Lq, int P, VT *out, hipStream_t stream, void *table = nullptr);
+template <typename VT, typename GT>
+int launch_bwd_d32(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
+                   const float *attn, int N, int S, int M, int L, int Lq, int P, GT *grad_value, float *grad_loc,
+                   float *grad_attn, hipStream_t stream, bool deterministic = false, void *workspace = nullptr, size_t ws_bytes = 0,
+                   bool forward_table = false, bool no_dense = false);
+// bytes of that table (0 = the backward's plan reads none)
 size_t forward_table_bytes(int N, int S, int M, int D, int L, int Lq, int P, bool prologue);
+inline bool aligned_to(const void *p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+// The table inside `workspace` (include/msda.h: msda_forward_ws_* fills the start of it, a backward call with
+// MSDA_FLAG_FORWARD_TABLE finds it there).  `need` = forward_table_bytes of the geometry: used only where the plan has a
+// table and the caller's buffer holds all of it.
+inline void *table_of(void *workspace, size_t ws_bytes, size_t need)
+{
+    return (workspace && aligned_to(workspace, 16) && need > 0 && ws_bytes >= need) ? workspace : nullptr;
+}
+// ... and the scratch of that backward call: what follows the table, rounded up to 256 bytes (no table: all of the workspace)
+inline size_t table_span(size_t table_bytes) { return (table_bytes + 255) & ~(size_t)255; }
+struct Scratch { void *p; size_t bytes; };
+inline Scratch scratch_behind(void *workspace, size_t ws_bytes, size_t table_bytes)
+{
+    const size_t span = table_span(table_bytes);
+    if (!workspace || ws_bytes <= span) return Scratch{nullptr, 0};
+    return Scratch{static_cast<unsigned char *>(workspace) + span, ws_bytes - span};
+}
 // clears the 'written' stamp of a table buffer that a forward call could not fill (see msda_d32.hip)
 int invalidate_forward_table(void *table, int N, int S, int M, int L, int Lq, int P, hipStream_t stream);
-// scratch the D = 32 backward can use to cut long levels into query chunks (0 = none needed); see msda.h
+// scratch a D = 32 backward call with these flags can use (0 = none needed); see msda.h
 size_t backward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags);
-
-// bf16 storage (uint16_t bits) of value / out / grad_out / grad_value; loc, attn and their gradients fp32.
-int launch_fwd_d32_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *level_start,
-                        const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P,
-                        uint16_t *out, hipStream_t stream, void *table = nullptr);
-int launch_bwd_d32_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes,
-                        const int64_t *level_start, const float *loc, const float *attn, int N, int S,
-                        int M, int L, int Lq, int P, uint16_t *grad_value, float *grad_loc, float *grad_attn,
-                        hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool deterministic = false,
-                        const void *table = nullptr, bool no_dense = false);
-
-// bf16 rows in, fp32 grad_value out: nothing is rounded between the passes of a multi-pass backward (and a
-// caller whose value tensor is fp32 needs no conversion of the result)
-int launch_bwd_d32_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes,
-                             const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L,
-                             int Lq, int P, float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream,
-                             void *workspace = nullptr, size_t ws_bytes = 0, bool deterministic = false, const void *table = nullptr,
-                             bool no_dense = false);
 // number of query chunks ("passes") role B of the D = 32 backward takes for Lq*P sampling points per (b, m, l)
 int backward_passes(int Lq, int P);
 // text form of the launch plan of a D = 32 geometry (msda_describe_plan); returns the length written
 int describe_plan(int row_bytes, int gv_bytes, int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det,
                   char *buf, int len, bool no_dense = false);
 
-// ---- fused prologue (fp32, D = 32 family): softmax over L*P and loc = ref + offset/(W,H) inside the kernels.
+// ---- fused prologue (D = 32 family): softmax over L*P and loc = ref + offset/(W,H) inside the kernels.  Offsets, logits,
+// reference points and every gradient are fp32 (grad_value included, for bf16 rows too).
 // ld_* = floats between consecutive (batch, query) rows of the raw offsets / logits and of their gradients
 // (validated by the ABI layer: >= the dense width, offsets' even).
 bool prologue_supported(int N, int S, int M, int D, int L, int Lq, int P);
-int launch_fwd_prologue(const float *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
+template <typename VT>
+int launch_fwd_prologue(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
                         const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                        long long ld_offsets, long long ld_logits, float *out, float *loc_out, float *attn_out,
+                        long long ld_offsets, long long ld_logits, VT *out, float *loc_out, float *attn_out,
                         hipStream_t stream, void *table = nullptr);
-int launch_bwd_prologue(const float *grad_out, const float *value, const int64_t *shapes, const int64_t *level_start,
+template <typename VT>
+int launch_bwd_prologue(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start,
                         const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
                         long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                        float *grad_ref, hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool deterministic = false,
-                        const void *table = nullptr, bool no_dense = false);
-
-// bf16 rows (value, out, grad_out); offsets / logits / reference points and every gradient fp32 (grad_value included)
-int launch_fwd_prologue_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
-                             const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                             long long ld_offsets, long long ld_logits, uint16_t *out, float *loc_out, float *attn_out,
-                             hipStream_t stream, void *table = nullptr);
-int launch_bwd_prologue_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *shapes, const int64_t *level_start,
-                             const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
-                             long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                             float *grad_ref, hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0,
-                             bool deterministic = false, const void *table = nullptr,
-                             bool no_dense = false);
+                        float *grad_ref, hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool forward_table = false,
+                        bool deterministic = false, bool no_dense = false);
 
 // ---- weight / bias gradient of the bracketing nn.Linear layers (msda_linear.hip) -----------------
 size_t linear_wgrad_workspace_bytes(int M, int N, int K);

@@ -802,6 +802,36 @@ int msda_arctic_metrics_f32(const int *dims, const float *const *floats, const l
                             msda_stream_t stream);
 int msda_arctic_metrics_accumulate_f32(const float *values, int B, double *total, double *count, msda_stream_t stream);
 
+/* ---- the input-projection neck: conv bias + GroupNorm + feature mask (csrc/msda_neck.hip) ----------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * The input_proj loop of DeformableDETR.forward (models/actic_detr.py:191-225, models/assembly_detr.py:145-171) after the
+ * convolution: per feature level l,  out_l = GroupNorm(groups, C)(y_l + bias_l) * (uniform_l > 0.3f),  where y_l [N, C, H_l, W_l]
+ * is the Conv2d output taken WITHOUT its bias.  Every table is a HOST array of L (1 .. 8) device pointers to fp32 contiguous
+ * tensors: bias_l, gamma_l, beta_l [C]; uniform_l, out_l of y_l's shape; mean_l, rstd_l [N, groups]; mask_l one byte per
+ * element of y_l (1 = kept).  heights, widths: HOST ints.  The bias table or single entries of it may be NULL (a conv without
+ * bias); the uniform table may be NULL: no mask factor, mask is not touched.  The statistics are nn.GroupNorm's (biased
+ * variance, eps inside the root), the variance is the centred sum of (x - mean)^2.
+ *   msda_neck_supported        1 when the kernels take this geometry: C a multiple of groups, any H_l * W_l >= 1.
+ *   msda_neck_workspace_bytes  scratch of the backward: 3 [N, C] fp32 partials per level.
+ *   msda_neck_forward_f32      one launch for all levels (none for N = 0); writes out, mean, rstd and, with uniforms, mask.
+ *   msda_neck_backward_f32     two launches.  With g' = grad_out * mask and x^ = (y + bias - mean) rstd per (frame, group):
+ *       grad_y = rstd (g' gamma - mean_grp(g' gamma) - x^ mean_grp(g' gamma x^)); grad_gamma = sum g' x^, grad_beta = sum g',
+ *       grad_bias = sum grad_y over frames and pixels (each table or entry may be NULL: not wanted).  mask table NULL: no mask.
+ * Every sum runs in a fixed order without atomics: all results are bitwise reproducible.  No allocation, no
+ * synchronisation; argument errors before any launch. */
+int msda_neck_supported(int L, int N, int C, int groups, const int *heights, const int *widths);
+unsigned long long msda_neck_workspace_bytes(int L, int N, int C);
+int msda_neck_forward_f32(int L, const float *const *y, const float *const *bias, const float *const *gamma,
+                          const float *const *beta, const float *const *uniform, const int *heights, const int *widths, int N, int C,
+                          int groups, float eps, float *const *out, float *const *mean, float *const *rstd,
+                          unsigned char *const *mask, msda_stream_t stream);
+int msda_neck_backward_f32(int L, const float *const *grad_out, const float *const *y, const float *const *bias,
+                           const float *const *gamma, const float *const *mean, const float *const *rstd,
+                           const unsigned char *const *mask, const int *heights, const int *widths, int N, int C, int groups,
+                           float *const *grad_y, float *const *grad_gamma, float *const *grad_beta, float *const *grad_bias,
+                           void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

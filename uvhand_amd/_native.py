@@ -140,6 +140,11 @@ SIGNATURES = {
     "msda_arctic_metrics_supported": "i iiiiii",
     "msda_arctic_metrics_f32": "i ppp p p",
     "msda_arctic_metrics_accumulate_f32": "i p i pp p",
+    # the input-projection neck: conv bias + GroupNorm + feature mask
+    "msda_neck_supported": "i iiii pp",
+    "msda_neck_workspace_bytes": "U iii",
+    "msda_neck_forward_f32": "i i ppppp pp iii f pppp p",
+    "msda_neck_backward_f32": "i i ppppppp pp iii pppp p U p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -880,6 +885,63 @@ def unflatten_levels(grad_src_flat, grad_pos_flat, shapes_nchw, want_level_embed
             grad_pos_flat.data_ptr() if grad_pos_flat is not None else None,
             gembed.data_ptr() if gembed is not None else None, ws.data_ptr() if ws is not None else None)
     return gs, gp, gembed
+
+
+NECK_MAX_LEVELS = 8                     # kNeckMaxLevels (csrc/msda_launch.h)
+
+
+def _ptr_table(tensors):
+    """A host array of device pointers (None entries stay NULL), or None for no table."""
+    if tensors is None:
+        return None
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def neck_supported(ys, groups):
+    """msda_neck_supported for per-level conv outputs [N, C, H_l, W_l] of one batch size and channel count."""
+    L = len(ys)
+    if not 1 <= L <= NECK_MAX_LEVELS:
+        return False
+    N, C = ys[0].shape[:2]
+    hs = (ctypes.c_int * L)(*[t.shape[2] for t in ys])
+    ws = (ctypes.c_int * L)(*[t.shape[3] for t in ys])
+    return bool((_lib or load()).msda_neck_supported(L, N, C, groups, hs, ws))
+
+
+def neck_forward(ys, biases, gammas, betas, uniforms, groups, eps):
+    """(outs, means, rstds, masks) — msda_neck_forward_f32 (include/msda.h): one launch for all levels.  ys: contiguous fp32
+    conv outputs without bias; biases: per-level tensors or None entries; uniforms: None or one tensor per level (masks is then
+    a list of uint8 tensors, else None)."""
+    L, (N, C) = len(ys), ys[0].shape[:2]
+    dev = ys[0].device
+    _, hs, ws = _level_arrays(ys)
+    outs = [torch.empty_like(y) for y in ys]
+    means = [torch.empty((N, groups), dtype=torch.float32, device=dev) for _ in ys]
+    rstds = [torch.empty((N, groups), dtype=torch.float32, device=dev) for _ in ys]
+    masks = [torch.empty(y.shape, dtype=torch.uint8, device=dev) for y in ys] if uniforms is not None else None
+    _launch(dev, "msda_neck_forward_f32", "neck_forward", L, _ptr_table(ys), _ptr_table(biases), _ptr_table(gammas),
+            _ptr_table(betas), _ptr_table(uniforms), hs, ws, N, C, groups, float(eps), _ptr_table(outs), _ptr_table(means),
+            _ptr_table(rstds), _ptr_table(masks))
+    return outs, means, rstds, masks
+
+
+def neck_backward(grad_outs, ys, biases, gammas, means, rstds, masks, groups):
+    """(grad_ys, grad_gammas, grad_betas, grad_biases) — msda_neck_backward_f32: two launches for all levels.  grad_biases has
+    None where the level's conv has no bias."""
+    lib = _lib or load()
+    L, (N, C) = len(ys), ys[0].shape[:2]
+    dev = ys[0].device
+    _, hs, ws = _level_arrays(ys)
+    gys = [torch.empty_like(y) for y in ys]
+    ggs = [torch.empty((C,), dtype=torch.float32, device=dev) for _ in ys]
+    gbs = [torch.empty((C,), dtype=torch.float32, device=dev) for _ in ys]
+    gcs = [torch.empty((C,), dtype=torch.float32, device=dev) if b is not None else None for b in biases]
+    nbytes = max(16, int(lib.msda_neck_workspace_bytes(L, N, C)))
+    wsp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _launch(dev, "msda_neck_backward_f32", "neck_backward", L, _ptr_table(grad_outs), _ptr_table(ys), _ptr_table(biases),
+            _ptr_table(gammas), _ptr_table(means), _ptr_table(rstds), _ptr_table(masks), hs, ws, N, C, groups, _ptr_table(gys),
+            _ptr_table(ggs), _ptr_table(gbs), _ptr_table(gcs), wsp.data_ptr(), nbytes)
+    return gys, ggs, gbs, gcs
 
 
 PATH_GENERIC, PATH_D32 = 0, 1          # MSDA_PATH_* (include/msda.h)

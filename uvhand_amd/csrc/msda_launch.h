@@ -327,4 +327,29 @@ int swin_backward(int B, int H, int W, int C, int nH, int ws, int shift, const f
                   const float *out, const float *lse, unsigned long long lse_bytes, const float *grad_out, float *grad_qkv,
                   float *grad_table, float *grad_bias, void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
 
+// ---- the input-projection neck: bias + GroupNorm + feature mask of every level (msda_neck.hip; C entries msda_neck_*) ----
+// Both level tables travel by value in the kernel arguments, as FlattenPlan does.
+constexpr int kNeckMaxLevels = 8;
+struct NeckFwdPlan {
+    int L;
+    const float *y[kNeckMaxLevels], *bias[kNeckMaxLevels], *gamma[kNeckMaxLevels], *beta[kNeckMaxLevels], *u[kNeckMaxLevels];
+    float *out[kNeckMaxLevels], *mean[kNeckMaxLevels], *rstd[kNeckMaxLevels];
+    unsigned char *mask[kNeckMaxLevels];
+    int hw[kNeckMaxLevels], vec[kNeckMaxLevels], first_block[kNeckMaxLevels];
+};
+struct NeckBwdPlan {
+    int L;
+    const float *grad_out[kNeckMaxLevels], *y[kNeckMaxLevels], *bias[kNeckMaxLevels], *gamma[kNeckMaxLevels];
+    const float *mean[kNeckMaxLevels], *rstd[kNeckMaxLevels];
+    const unsigned char *mask[kNeckMaxLevels];
+    float *grad_y[kNeckMaxLevels], *grad_gamma[kNeckMaxLevels], *grad_beta[kNeckMaxLevels], *grad_bias[kNeckMaxLevels];
+    float *partial[kNeckMaxLevels];      // [3][N][C] per level
+    int hw[kNeckMaxLevels], vec[kNeckMaxLevels], first_block[kNeckMaxLevels];
+};
+static_assert(sizeof(NeckFwdPlan) <= 2000 && sizeof(NeckBwdPlan) <= 2000, "kernel argument tables");
+bool neck_supported(int L, int N, int C, int groups, const int *heights, const int *widths);
+size_t neck_workspace_bytes(int L, int N, int C);
+int launch_neck_forward(const NeckFwdPlan &plan, int N, int C, int groups, float eps, hipStream_t stream);
+int launch_neck_backward(const NeckBwdPlan &plan, int N, int C, int groups, hipStream_t stream);
+
 }  // namespace msda

@@ -7,7 +7,11 @@ output dict are the reference's, so a reference checkpoint loads with ``strict=T
 on CUDA fp32, three forward and five backward HIP launches instead of the reference's per-level Linears and stacks.
 
 One deliberate change: ARCTIC's ``local_fm`` path builds its all-false masks on the device (``torch.zeros(..., device=)``)
-instead of ``torch.zeros(...).to(device)``, which costs a host-to-device copy per level; the values are identical."""
+instead of ``torch.zeros(...).to(device)``, which costs a host-to-device copy per level; the values are identical.
+
+The backbone path's ``input_proj`` loop (Conv2d, GroupNorm, ARCTIC's training feature mask) runs through
+``functions.neck_func.input_proj_levels``: the convolutions stay torch's, everything after them is one HIP launch for all
+levels (``csrc/msda_neck.hip``)."""
 import copy
 import math
 
@@ -16,6 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..functions.heads_func import ARCTIC, ASSEMBLY, detr_heads, inverse_sigmoid
+from ..functions.neck_func import input_proj_levels, output_shapes
 
 __all__ = ["ArcticDeformableDETR", "AssemblyDeformableDETR", "MLP", "NestedTensor", "inverse_sigmoid"]
 
@@ -91,38 +96,50 @@ def _input_proj(backbone, hidden_dim, num_feature_levels):
 
 
 def _backbone_inputs(model, samples, random_mask):
-    """The multi-scale inputs of the backbone path (models/actic_detr.py:189-230, models/assembly_detr.py:145-171)."""
+    """The multi-scale inputs of the backbone path (models/actic_detr.py:189-230, models/assembly_detr.py:145-171).
+
+    The input_proj loop runs through ``functions.neck_func.input_proj_levels``: on CUDA fp32 the GroupNorm and the 30 %
+    feature mask of all levels are one HIP launch (two backward); ``MSDA_NECK_FUSED=0`` or any other dtype / device is the
+    reference's composition.  The masks are drawn from the same generator, in the same order and with the same shapes as the
+    reference's, so one seed gives the same masks.  The extra levels' positional encoding is built from the masked
+    projection where the reference passes the unmasked one: the encodings (sine, learned) read its shape, device and mask
+    only."""
     if not _is_nested(samples):
         samples = nested_tensor_from_tensor_list(samples)
     features, pos = model.backbone(samples)
-    srcs, masks = [], []
-    for l, feat in enumerate(features):
-        src, mask = feat.decompose()
-        src_input = model.input_proj[l](src)
-        if random_mask and model.training:
-            src_mask = torch.cuda.FloatTensor(src_input.shape).uniform_() > 0.3
-            srcs.append(src_input * src_mask)
-        else:
-            srcs.append(src_input)
+    masked = random_mask and model.training
+    n_backbone = len(features)
+
+    def project(first, xs):
+        # levels first .. first + len(xs) - 1 in one call of the neck node; the uniforms are drawn per level in level order,
+        # as the reference's torch.cuda.FloatTensor(shape).uniform_() after each projection draws them (the projections
+        # themselves take nothing from the generator)
+        convs = [model.input_proj[first + i][0] for i in range(len(xs))]
+        norms = [model.input_proj[first + i][1] for i in range(len(xs))]
+        uniforms = None
+        if masked:
+            uniforms = [torch.empty(shape, device=x.device).uniform_() for shape, x in zip(output_shapes(xs, convs), xs)]
+        return input_proj_levels(xs, convs, norms, uniforms)
+
+    # every level whose conv input is a backbone feature goes in one call: the backbone's own levels and the first extra
+    # one, which reads features[-1].tensors; a later extra level reads the previous (masked) output, in a call of its own
+    xs = [feat.tensors for feat in features]
+    if model.num_feature_levels > n_backbone:
+        xs.append(features[-1].tensors)
+    srcs = project(0, xs)
+    masks = []
+    for feat in features:
+        assert feat.mask is not None
+        masks.append(feat.mask)
+    for l in range(n_backbone, model.num_feature_levels):
+        if l > n_backbone:
+            srcs += project(l, [srcs[-1]])
+        src = srcs[l]
+        m = samples.mask
+        mask = F.interpolate(m[None].float(), size=src.shape[-2:]).to(torch.bool)[0]
+        pos_l = model.backbone[1](NestedTensor(src, mask)).to(src.dtype)
         masks.append(mask)
-        assert mask is not None
-    if model.num_feature_levels > len(srcs):
-        _len_srcs = len(srcs)
-        for l in range(_len_srcs, model.num_feature_levels):
-            if l == _len_srcs:
-                src = model.input_proj[l](features[-1].tensors)
-            else:
-                src = model.input_proj[l](srcs[-1])
-            m = samples.mask
-            mask = F.interpolate(m[None].float(), size=src.shape[-2:]).to(torch.bool)[0]
-            pos_l = model.backbone[1](NestedTensor(src, mask)).to(src.dtype)
-            if random_mask and model.training:
-                src_mask = torch.cuda.FloatTensor(src.shape).uniform_() > 0.3
-                srcs.append(src * src_mask)
-            else:
-                srcs.append(src)
-            masks.append(mask)
-            pos.append(pos_l)
+        pos.append(pos_l)
     return srcs, masks, pos
 
 

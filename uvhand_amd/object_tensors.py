@@ -20,7 +20,8 @@ tensors, other dtypes, autocast, ``MSDA_OBJECT_FUSED=0``) runs ``object_tensors_
 Kept from the reference: ``transl`` is added in metres (its ``*1000`` in ``_sanity_check`` changes only a local variable);
 articulation is ``q p q*`` about -z with ``q`` from pytorch3d's ``axis_angle_to_quaternion`` (the ``|theta| < 1e-6`` series),
 not renormalised; an unknown name raises ``ValueError`` (the reference's ``list.index``).  An out-of-range ``obj_idx`` gives NaN
-rows on the kernel path (the reference would raise; checking would need a sync)."""
+rows on the kernel path (the reference would raise; checking would need a sync); the template entries of such a frame are those
+of the nearest valid index."""
 import os
 
 import numpy as np
@@ -191,7 +192,8 @@ def objects_many(calls):
         outs = _native.object_forward(dims, model, inputs, lens)
     res = []
     for (layer, _, _, _, idx, max_len), (v, v_sub, bbox, kp) in zip(calls, outs):
-        out = _template(layer.obj_tensors, idx, max_len)
+        # an out-of-range index has NaN rows from the kernel; the template gather must not read outside the model for it
+        out = _template(layer.obj_tensors, idx.clamp(0, dims[0] - 1), max_len)
         out["v"], out["v_sub"], out["bbox3d"], out["kp3d"] = v, v_sub, bbox, kp
         res.append(out)
     return res

@@ -23,9 +23,10 @@ orders: two runs, and grouped against per-set calls, are bitwise equal.
 pytorch3d, cv2 or loguru), in fp32 as the reference or in fp64 as the tests' yardstick.  It runs for CPU tensors, non-fp32
 inputs, autocast, geometries over the kernel limits, more than ``SMALL_LOSS_MAX_SETS`` sets and ``MSDA_SMALL_LOSS_FUSED=0``.
 
-The one deviation: a skipped hand block (no frame with ``is_valid * hand_valid``) returns shape ``[1]`` zeros where the
+The first deviation: a skipped hand block (no frame with ``is_valid * hand_valid``) returns shape ``[1]`` zeros where the
 reference returns 0-d zeros, since a data-dependent shape would need a sync.  ``loss/cd`` and ``loss/object/v3d_smoothing``
-are 0-d as in the reference."""
+are 0-d as in the reference.  A second one: with a single frame the reference's ``obj_smt_loss`` raises (it reads ``v[1]``);
+the kernel path returns ``loss/object/v3d_smoothing`` = 0 with a zero gradient, as there is no consecutive pair."""
 import os
 
 import torch

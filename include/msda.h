@@ -832,6 +832,62 @@ int msda_neck_backward_f32(int L, const float *const *grad_out, const float *con
                            float *const *grad_y, float *const *grad_gamma, float *const *grad_beta, float *const *grad_bias,
                            void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- make_output's pose, camera and projection glue (csrc/msda_arctic_output.hip) --------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * What runs between get_arctic_item, the MANO / object layers and get_NN in arctic_tools/process.py make_output (107-149) and
+ * prepare_data (249-299).  Every table is a HOST array of device pointers to fp32 contiguous tensors; B = 0 .. 65535 frames.
+ *
+ * Pose heads.  Replaces make_output's axis_angle_to_matrix (process.py:118-119), MANOHead.forward's matrix_to_axis_angle
+ * (src/nets/hand_heads/mano_head.py:30, common/rot.py:180) for n_hands (0 .. 2) poses [B, 48], and the
+ * weak_perspective_to_perspective_torch calls of MANOHead / ArtiHead (mano_head.py:40, src/nets/obj_heads/obj_head.py:39) for
+ * n_roots (0 .. 3) roots [B, 3] with K [B, 3, 3] (f = (K00 + K11) / 2).
+ *   msda_arctic_pose_supported     1 when the kernels take this geometry (n_hands + n_roots >= 1).
+ *   msda_arctic_pose_forward_f32   one launch, one thread per (hand, frame, joint) and per (root, frame): mats [B, 16, 3, 3]
+ *       (pytorch3d's quaternion route, 1/2 - theta^2/48 below 1e-6), aa [B, 48] (x > 0 before the root, 2 max(|q|, 0.1), the
+ *       largest |q| with the lowest index on a tie, atan2, the polynomial below 1e-6), cam_t [B, 3] = (tx, ty,
+ *       2 f / (img_res max(s, 0.1) + 1e-9)).
+ *   msda_arctic_pose_backward_f32  one launch.  grad_mats / grad_aa / grad_cam_t entries may be NULL (zero); grad_poses /
+ *       grad_roots entries may be NULL (not wanted).  The chosen candidate and the branches are constants; the clamps pass the
+ *       gradient at equality as torch.clamp does; K has no gradient.
+ *
+ * Matrix to axis-angle.  Replaces prepare_data's overwrite of mano.pose.r / .l (process.py:275-280) for n_hands (1 .. 2) given
+ * mats [B, 16, 3, 3] -> aa [B, 16, 3]: the second half of the pose heads, forward and backward one launch each.
+ *
+ * Place and project.  Replaces the `+ cam_t[:, None, :]` translations and project2d + normalisation of MANOHead / ArtiHead
+ * (mano_head.py:44-47, obj_head.py:44-49 and :74) and prepare_data's unormalize_kp2d of the prediction
+ * (process.py:266-268).  n_segments (1 .. 8) segments; rows, camera, project: HOST ints per segment (1 .. 8192 rows, camera
+ * 0 .. 2, project 0 / 1); points [B, rows, 3]; cam_t: HOST array of 3 device pointers [B, 3] (an unused camera may be NULL).
+ *   msda_arctic_place_supported    1 when the kernels take n_segments segments of at most max_rows rows.
+ *   msda_arctic_place_forward_f32  one launch: placed = points + cam_t (padded rows like any other); for projected segments
+ *       norm2d [B, rows, 2] = 2 (K x)_xy / (K x)_z / img_res - 1 and pix2d = 0.5 img_res (norm2d + 1); their entries may be
+ *       NULL for the other segments.
+ *   msda_arctic_place_backward_f32 one launch: the blocks that own rows write grad_points, one more block per (camera, frame)
+ *       sums that camera's rows of all its segments in a fixed order into grad_cam_t [B, 3].  grad_placed / grad_norm2d /
+ *       grad_pix2d entries may be NULL (zero); grad_points / grad_cam_t entries may be NULL (not wanted).  K has no gradient.
+ * fp32, no atomics, fixed summation order: bitwise reproducible.  No allocation, no synchronisation; argument errors before
+ * any launch; B = 0 launches nothing. */
+int msda_arctic_pose_supported(int n_hands, int n_roots, int B);
+int msda_arctic_pose_forward_f32(int n_hands, int n_roots, int B, float img_res, const float *const *poses,
+                                 const float *const *roots, const float *K, float *const *mats, float *const *aa,
+                                 float *const *cam_t, msda_stream_t stream);
+int msda_arctic_pose_backward_f32(int n_hands, int n_roots, int B, float img_res, const float *const *poses,
+                                  const float *const *roots, const float *K, const float *const *grad_mats,
+                                  const float *const *grad_aa, const float *const *grad_cam_t, float *const *grad_poses,
+                                  float *const *grad_roots, msda_stream_t stream);
+int msda_arctic_m2aa_forward_f32(int n_hands, int B, const float *const *mats, float *const *aa, msda_stream_t stream);
+int msda_arctic_m2aa_backward_f32(int n_hands, int B, const float *const *mats, const float *const *grad_aa,
+                                  float *const *grad_mats, msda_stream_t stream);
+int msda_arctic_place_supported(int n_segments, int B, int max_rows);
+int msda_arctic_place_forward_f32(int n_segments, int B, float img_res, const int *rows, const int *camera, const int *project,
+                                  const float *const *points, const float *const *cam_t, const float *K, float *const *placed,
+                                  float *const *norm2d, float *const *pix2d, msda_stream_t stream);
+int msda_arctic_place_backward_f32(int n_segments, int B, float img_res, const int *rows, const int *camera, const int *project,
+                                   const float *const *points, const float *const *cam_t, const float *K,
+                                   const float *const *grad_placed, const float *const *grad_norm2d,
+                                   const float *const *grad_pix2d, float *const *grad_points, float *const *grad_cam_t,
+                                   msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -145,6 +145,15 @@ SIGNATURES = {
     "msda_neck_workspace_bytes": "U iii",
     "msda_neck_forward_f32": "i i ppppp pp iii f pppp p",
     "msda_neck_backward_f32": "i i ppppppp pp iii pppp p U p",
+    # make_output's pose, camera and projection glue
+    "msda_arctic_pose_supported": "i iii",
+    "msda_arctic_pose_forward_f32": "i iiif ppp ppp p",
+    "msda_arctic_pose_backward_f32": "i iiif ppp ppp pp p",
+    "msda_arctic_m2aa_forward_f32": "i ii pp p",
+    "msda_arctic_m2aa_backward_f32": "i ii ppp p",
+    "msda_arctic_place_supported": "i iii",
+    "msda_arctic_place_forward_f32": "i iif ppp ppp ppp p",
+    "msda_arctic_place_backward_f32": "i iif ppp ppp ppp pp p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -1751,3 +1760,101 @@ def arctic_metrics_accumulate(values, total, count):
         raise RuntimeError("arctic_metrics_accumulate: expected values [6, B] fp32 and fp64 total / count of 6 on one device")
     _launch(dev, "msda_arctic_metrics_accumulate_f32", "arctic_metrics_accumulate", values.data_ptr(), int(values.shape[1]),
             total.data_ptr(), count.data_ptr())
+
+
+# ---- make_output's pose, camera and projection glue (msda_arctic_output.hip) ---------------------------------------------------
+ARCTIC_PLACE_MAX_SEGMENTS = 8
+ARCTIC_PLACE_MAX_ROWS = 8192
+
+
+def _opt_ptr_array(ts):
+    return (_VP * max(1, len(ts)))(*[_vp(t) for t in ts])
+
+
+def arctic_pose_supported(n_hands, n_roots, B):
+    """msda_arctic_pose_supported (include/msda.h)."""
+    return bool((_lib or load()).msda_arctic_pose_supported(int(n_hands), int(n_roots), int(B)))
+
+
+def arctic_place_supported(n_segments, B, max_rows):
+    """msda_arctic_place_supported (include/msda.h)."""
+    return bool((_lib or load()).msda_arctic_place_supported(int(n_segments), int(B), int(max_rows)))
+
+
+def arctic_pose_forward(poses, roots, K, img_res):
+    """msda_arctic_pose_forward_f32.  poses: [B, 48] each, roots: [B, 3] each, K [B, 3, 3].  Returns (mats [B, 16, 3, 3] per
+    pose, aa [B, 48] per pose, cam_t [B, 3] per root).  One launch, no host sync."""
+    dev, B = K.device, K.shape[0]
+    _nn_check("arctic_pose_forward", dev, list(poses) + list(roots) + [K])
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    mats, aas, cts = [new(B, 16, 3, 3) for _ in poses], [new(B, 48) for _ in poses], [new(B, 3) for _ in roots]
+    _launch(dev, "msda_arctic_pose_forward_f32", "arctic_pose_forward", len(poses), len(roots), B, float(img_res),
+            _opt_ptr_array(poses), _opt_ptr_array(roots), K.data_ptr(), _opt_ptr_array(mats), _opt_ptr_array(aas),
+            _opt_ptr_array(cts))
+    return mats, aas, cts
+
+
+def arctic_pose_backward(poses, roots, K, img_res, grad_mats, grad_aa, grad_cam_t, want_poses, want_roots):
+    """msda_arctic_pose_backward_f32.  The gradient lists hold None for an output without gradient; want_*: per input.
+    Returns (grad_poses, grad_roots) with None where not wanted.  One launch."""
+    dev, B = K.device, K.shape[0]
+    given = [g for g in list(grad_mats) + list(grad_aa) + list(grad_cam_t) if g is not None]
+    _nn_check("arctic_pose_backward", dev, list(poses) + list(roots) + [K] + given)
+    gp = [torch.empty_like(p) if w else None for p, w in zip(poses, want_poses)]
+    gr = [torch.empty_like(r) if w else None for r, w in zip(roots, want_roots)]
+    _launch(dev, "msda_arctic_pose_backward_f32", "arctic_pose_backward", len(poses), len(roots), B, float(img_res),
+            _opt_ptr_array(poses), _opt_ptr_array(roots), K.data_ptr(), _opt_ptr_array(grad_mats), _opt_ptr_array(grad_aa),
+            _opt_ptr_array(grad_cam_t), _opt_ptr_array(gp), _opt_ptr_array(gr))
+    return gp, gr
+
+
+def arctic_m2aa_forward(mats):
+    """msda_arctic_m2aa_forward_f32.  mats: [B, 16, 3, 3] each (1 .. 2).  Returns aa [B, 16, 3] each.  One launch."""
+    dev, B = mats[0].device, mats[0].shape[0]
+    _nn_check("arctic_m2aa_forward", dev, list(mats))
+    aas = [torch.empty(B, 16, 3, dtype=torch.float32, device=dev) for _ in mats]
+    _launch(dev, "msda_arctic_m2aa_forward_f32", "arctic_m2aa_forward", len(mats), B, _ptr_array(mats), _ptr_array(aas))
+    return aas
+
+
+def arctic_m2aa_backward(mats, grad_aa, want):
+    """msda_arctic_m2aa_backward_f32.  grad_aa holds None for an output without gradient.  One launch."""
+    dev, B = mats[0].device, mats[0].shape[0]
+    _nn_check("arctic_m2aa_backward", dev, list(mats) + [g for g in grad_aa if g is not None])
+    gm = [torch.empty_like(m) if w else None for m, w in zip(mats, want)]
+    _launch(dev, "msda_arctic_m2aa_backward_f32", "arctic_m2aa_backward", len(mats), B, _ptr_array(mats), _opt_ptr_array(grad_aa),
+            _opt_ptr_array(gm))
+    return gm
+
+
+def _place_geo(points, cameras, projects):
+    return (_int_array([p.shape[1] for p in points]), _int_array(cameras), _int_array([1 if p else 0 for p in projects]))
+
+
+def arctic_place_forward(points, cameras, projects, cam_ts, K, img_res):
+    """msda_arctic_place_forward_f32.  points: [B, n, 3] each; cam_ts: three [B, 3] or None.  Returns per segment (placed,
+    norm2d or None, pix2d or None).  One launch, no host sync."""
+    dev, B = points[0].device, points[0].shape[0]
+    _nn_check("arctic_place_forward", dev, list(points) + [c for c in cam_ts if c is not None] + [K])
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    placed = [torch.empty_like(p) for p in points]
+    n2 = [new(B, p.shape[1], 2) if pr else None for p, pr in zip(points, projects)]
+    px = [new(B, p.shape[1], 2) if pr else None for p, pr in zip(points, projects)]
+    _launch(dev, "msda_arctic_place_forward_f32", "arctic_place_forward", len(points), B, float(img_res),
+            *_place_geo(points, cameras, projects), _ptr_array(points), _opt_ptr_array(cam_ts), K.data_ptr(), _ptr_array(placed),
+            _opt_ptr_array(n2), _opt_ptr_array(px))
+    return list(zip(placed, n2, px))
+
+
+def arctic_place_backward(points, cameras, projects, cam_ts, K, img_res, grad_placed, grad_n2, grad_px, want_points, want_cams):
+    """msda_arctic_place_backward_f32.  The gradient lists hold None for an output without gradient.  Returns (grad_points,
+    grad_cam_ts) with None where not wanted.  One launch, no atomics."""
+    dev, B = points[0].device, points[0].shape[0]
+    given = [g for g in list(grad_placed) + list(grad_n2) + list(grad_px) if g is not None]
+    _nn_check("arctic_place_backward", dev, list(points) + [c for c in cam_ts if c is not None] + [K] + given)
+    gp = [torch.empty_like(p) if w else None for p, w in zip(points, want_points)]
+    gc = [torch.empty(B, 3, dtype=torch.float32, device=dev) if w else None for w in want_cams]
+    _launch(dev, "msda_arctic_place_backward_f32", "arctic_place_backward", len(points), B, float(img_res),
+            *_place_geo(points, cameras, projects), _ptr_array(points), _opt_ptr_array(cam_ts), K.data_ptr(),
+            _opt_ptr_array(grad_placed), _opt_ptr_array(grad_n2), _opt_ptr_array(grad_px), _opt_ptr_array(gp), _opt_ptr_array(gc))
+    return gp, gc

@@ -31,10 +31,12 @@ import numpy as np
 import torch
 
 from . import _native
+from . import arctic_output as _ao
 from .arctic_item import get_arctic_item
+from .arctic_output import matrix_to_axis_angle, matrix_to_quaternion, quaternion_to_axis_angle  # noqa: F401  (restated there)
 from .mano import mano_many
-from .object_tensors import ObjectTensors, axis_angle_to_matrix, objects_many
-from .small_loss import _convert, contact_deviation, project_normalise, weak_perspective_to_perspective
+from .object_tensors import ObjectTensors, objects_many
+from .small_loss import _convert, contact_deviation
 
 NN_MAX_PAIRS = _native.NN_MAX_PAIRS
 METRIC_KEYS = ("aae", "mpjpe/ra/h", "mrrpe/r/l", "mrrpe/r/o", "success_rate/0.05", "cdev/ho")
@@ -203,36 +205,6 @@ def get_NN(src_xyz, trg_xyz, k=1):
     return nn_many([(src_xyz, trg_xyz)], k=k)[0]
 
 
-# ---- rotations (common/rot.py restated without boolean indexing, so without a sync) ---------------------------------------------
-def matrix_to_quaternion(matrix):
-    batch = matrix.shape[:-2]
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = torch.unbind(matrix.reshape(batch + (9,)), dim=-1)
-    x = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], dim=-1)
-    pos = x > 0
-    q_abs = torch.where(pos, torch.sqrt(torch.where(pos, x, torch.ones_like(x))), torch.zeros_like(x))
-    by_rijk = torch.stack([torch.stack([q_abs[..., 0] ** 2, m21 - m12, m02 - m20, m10 - m01], dim=-1),
-                           torch.stack([m21 - m12, q_abs[..., 1] ** 2, m10 + m01, m02 + m20], dim=-1),
-                           torch.stack([m02 - m20, m10 + m01, q_abs[..., 2] ** 2, m12 + m21], dim=-1),
-                           torch.stack([m10 - m01, m20 + m02, m21 + m12, q_abs[..., 3] ** 2], dim=-1)], dim=-2)
-    cand = by_rijk / (2.0 * q_abs[..., None].clamp(min=0.1))
-    pick = q_abs.argmax(dim=-1)[..., None, None].expand(batch + (1, 4))
-    return torch.gather(cand, -2, pick).squeeze(-2)
-
-
-def quaternion_to_axis_angle(quaternions):
-    norms = torch.norm(quaternions[..., 1:], p=2, dim=-1, keepdim=True)
-    half = torch.atan2(norms, quaternions[..., :1])
-    angles = 2 * half
-    small = angles.abs() < 1e-6
-    safe = torch.where(small, torch.ones_like(angles), angles)
-    s = torch.where(small, 0.5 - (angles * angles) / 48, torch.sin(half) / safe)
-    return quaternions[..., 1:] / s
-
-
-def matrix_to_axis_angle(matrix):
-    return quaternion_to_axis_angle(matrix_to_quaternion(matrix))
-
-
 # ---- glue -----------------------------------------------------------------------------------------------------------------------
 _DEFAULT_MODELS = None
 
@@ -254,72 +226,92 @@ def _models(models):
     return _convert(models)
 
 
-def _unnormalise(kp2d, img_res):
-    return 0.5 * img_res * (kp2d + 1)
+_unnormalise = _ao.unnormalise
 
 
-def make_output(args, root, mano_pose, mano_shape, obj_angle, query_names, K, models=None, obj_idx=None, max_len=None):
-    """process.py:107-149: every key of MANOHead.forward (r, then l) and ArtiHead.forward, prefixed, in the reference's
-    order.  ``obj_idx`` (int64 device tensor) with a host ``max_len`` replaces ``query_names`` for graph capture."""
+def _make_output(args, root, mano_pose, mano_shape, obj_angle, query_names, K, models=None, obj_idx=None, max_len=None):
+    """``make_output`` and, on the device with the kernels switched on, what ``prepare_data`` derives from it and the launches
+    have already produced: the pixel-space 2d keys and the axis-angle of ``mano.pose.*`` (else None)."""
     m = _models(models)
     root_l, root_r, root_o = root
     pose_l, pose_r = mano_pose
     shape_l, shape_r = mano_shape
     obj_rot, obj_rad = obj_angle
     img_res = args.img_res
-    rotmat = {s: axis_angle_to_matrix(p.reshape(-1, 3)).reshape(-1, 16, 3, 3) for s, p in (("r", pose_r), ("l", pose_l))}
-    aa = {s: matrix_to_axis_angle(rotmat[s].reshape(-1, 3, 3)).reshape(-1, 48) for s in ("r", "l")}
-    hands = mano_many([(m["mano_r"], shape_r, aa["r"][:, :3], aa["r"][:, 3:]), (m["mano_l"], shape_l, aa["l"][:, :3], aa["l"][:, 3:])])
-    focal = (K[:, 0, 0] + K[:, 1, 1]) / 2.0
-    output = XDict()
-    for s, hand, cam, shape in (("r", hands[0], root_r, shape_r), ("l", hands[1], root_l, shape_l)):
-        cam_t = weak_perspective_to_perspective(cam, focal, img_res)
-        j3d = hand.joints + cam_t[:, None, :]
-        for k, v in (("cam_t.wp", cam), ("cam_t", cam_t), ("joints3d", hand.joints), ("vertices", hand.vertices),
-                     ("j3d.cam", j3d), ("v3d.cam", hand.vertices + cam_t[:, None, :]),
-                     ("j2d.norm", project_normalise(K, j3d, img_res)), ("beta", shape), ("pose", rotmat[s])):
-            output["mano.%s.%s" % (k, s)] = v
+    fused = K.is_cuda and _ao.fused_enabled()
+    (mat_r, mat_l), (aa_r, aa_l), cam_ts = _ao.pose_heads((pose_r, pose_l), (root_r, root_l, root_o), K, img_res)
+    hands = mano_many([(m["mano_r"], shape_r, aa_r[:, :3], aa_r[:, 3:]), (m["mano_l"], shape_l, aa_l[:, :3], aa_l[:, 3:])])
     obj = m["arti_head"]
     if obj_idx is None:
         obj_idx, max_len = obj.obj_index(query_names)
     elif max_len is None:
         raise ValueError("obj_idx needs a host max_len")
     out = objects_many([(obj, obj_rad.view(-1, 1), obj_rot, None, obj_idx, int(max_len))])[0]
-    cam_t = weak_perspective_to_perspective(root_o, focal, img_res)
-    kp3d_cam, bbox3d_cam = out["kp3d"] + cam_t[:, None, :], out["bbox3d"] + cam_t[:, None, :]
-    kp2d, bbox2d = project_normalise(K, kp3d_cam, img_res), project_normalise(K, bbox3d_cam, img_res)
+    placed = _ao.place_many([(hands[0].vertices, 0, False), (hands[1].vertices, 1, False), (hands[0].joints, 0, True),
+                             (hands[1].joints, 1, True), (out["kp3d"], 2, True), (out["bbox3d"], 2, True), (out["v"], 2, False)],
+                            cam_ts, K, img_res, pixels=fused)
+    output = XDict()
+    extras = {} if fused else None
+    for i, (s, hand, cam, shape, mat, aa) in enumerate((("r", hands[0], root_r, shape_r, mat_r, aa_r),
+                                                        ("l", hands[1], root_l, shape_l, mat_l, aa_l))):
+        for k, v in (("cam_t.wp", cam), ("cam_t", cam_ts[i]), ("joints3d", hand.joints), ("vertices", hand.vertices),
+                     ("j3d.cam", placed[2 + i][0]), ("v3d.cam", placed[i][0]), ("j2d.norm", placed[2 + i][1]), ("beta", shape),
+                     ("pose", mat)):
+            output["mano.%s.%s" % (k, s)] = v
+        if fused:
+            extras["mano.j2d." + s] = placed[2 + i][2]
+            extras["mano.pose." + s] = aa.reshape(-1, 16, 3)
+    (kp3d_cam, kp2d, kp_px), (bbox3d_cam, bbox2d, bbox_px) = placed[4], placed[5]
     nk = kp2d.shape[1] // 2
-    for k, v in (("rot", obj_rot), ("cam_t.wp", root_o), ("cam_t", cam_t), ("kp3d", out["kp3d"]), ("bbox3d", out["bbox3d"]),
+    for k, v in (("rot", obj_rot), ("cam_t.wp", root_o), ("cam_t", cam_ts[2]), ("kp3d", out["kp3d"]), ("bbox3d", out["bbox3d"]),
                  ("bbox3d.cam", bbox3d_cam), ("kp3d.cam", kp3d_cam), ("kp2d.norm", kp2d), ("kp2d.norm.t", kp2d[:, :nk]),
                  ("kp2d.norm.b", kp2d[:, nk:]), ("bbox2d.norm.t", bbox2d[:, :8]), ("bbox2d.norm.b", bbox2d[:, 8:]),
-                 ("radian", obj_rad), ("v.cam", out["v"] + cam_t[:, None, :]), ("v_len", out["v_len"]), ("f", out["f"]),
+                 ("radian", obj_rad), ("v.cam", placed[6][0]), ("v_len", out["v_len"]), ("f", out["f"]),
                  ("f_len", out["f_len"])):
         output["object." + k] = v
-    return output
+    if fused:
+        extras.update({"object.kp2d": kp_px, "object.kp2d.t": kp_px[:, :nk], "object.kp2d.b": kp_px[:, nk:],
+                       "object.bbox2d.t": bbox_px[:, :8], "object.bbox2d.b": bbox_px[:, 8:]})
+    return output, extras
+
+
+def make_output(args, root, mano_pose, mano_shape, obj_angle, query_names, K, models=None, obj_idx=None, max_len=None):
+    """process.py:107-149: every key of MANOHead.forward (r, then l) and ArtiHead.forward, prefixed, in the reference's
+    order.  ``obj_idx`` (int64 device tensor) with a host ``max_len`` replaces ``query_names`` for graph capture.  Device data:
+    ``pose_heads``, ``mano_many``, ``objects_many``, ``place_many`` (four launches) and views."""
+    return _make_output(args, root, mano_pose, mano_shape, obj_angle, query_names, K, models=models, obj_idx=obj_idx,
+                        max_len=max_len)[0]
+
+
+def _post_process(outputs, meta_info, args, cfg, models=None):
+    root, mano_pose, mano_shape, obj_angle = get_arctic_item(outputs, cfg, getattr(args, "device", None))
+    return _make_output(args, root, mano_pose, mano_shape, obj_angle, meta_info.get("query_names"), meta_info["intrinsics"],
+                        models=models, obj_idx=meta_info.get("obj_idx"), max_len=meta_info.get("max_len"))
 
 
 def post_process_arctic_output(outputs, meta_info, args, cfg, models=None):
     """process.py:95-105: query selection, then ``make_output``."""
-    root, mano_pose, mano_shape, obj_angle = get_arctic_item(outputs, cfg, getattr(args, "device", None))
-    return make_output(args, root, mano_pose, mano_shape, obj_angle, meta_info.get("query_names"), meta_info["intrinsics"],
-                       models=models, obj_idx=meta_info.get("obj_idx"), max_len=meta_info.get("max_len"))
+    return _post_process(outputs, meta_info, args, cfg, models=models)[0]
 
 
 def prepare_data(args, outputs, targets, meta_info, cfg, pred=None, flag='eval', models=None):
     """process.py:249-299.  ``flag``: 'eval' moves the result to the CPU (the reference), 'device' keeps it on the device for
     ``arctic_metrics`` / ``ArcticEvaluator``, 'train' keeps it (and the graph) for the SmoothNet criterion."""
     targets, meta_info = XDict(targets), XDict(meta_info)
+    extras = None                                # what make_output's launches already hold of the keys derived below
     if pred is None:
         assert outputs is not None
-        pred = post_process_arctic_output(outputs, meta_info, args, cfg, models=models)
+        pred, extras = _post_process(outputs, meta_info, args, cfg, models=models)
     for key in list(pred.keys()):
         if "2d.norm" in key:
             denorm = key.replace(".norm", "")
             assert key in targets.keys(), "Do not have key %s" % key
-            pred[denorm] = _unnormalise(pred[key], args.img_res)
+            pred[denorm] = extras[denorm] if extras is not None else _unnormalise(pred[key], args.img_res)
             targets[denorm] = _unnormalise(targets[key], args.img_res)
-    pred.overwrite("mano.pose.r", matrix_to_axis_angle(pred["mano.pose.r"]))
-    pred.overwrite("mano.pose.l", matrix_to_axis_angle(pred["mano.pose.l"]))
+    aa_r, aa_l = (extras["mano.pose.r"], extras["mano.pose.l"]) if extras is not None \
+        else _ao.matrix_to_axis_angle_many([pred["mano.pose.r"], pred["mano.pose.l"]])
+    pred.overwrite("mano.pose.r", aa_r)
+    pred.overwrite("mano.pose.l", aa_l)
     (dr, ir), (dl, il) = nn_many([(pred["object.v.cam"], pred["mano.v3d.cam.r"]), (pred["object.v.cam"], pred["mano.v3d.cam.l"])])
     pred['nn_dist_r'], pred['nn_idx_r'] = dr, ir
     pred['nn_dist_l'], pred['nn_idx_l'] = dl, il

@@ -888,6 +888,41 @@ int msda_arctic_place_backward_f32(int n_segments, int B, float img_res, const i
                                    const float *const *grad_pix2d, float *const *grad_points, float *const *grad_cam_t,
                                    msda_stream_t stream);
 
+/* ---- the SmoothNet criterion: contact deviation and acceleration errors (csrc/msda_smooth_loss.hip) ------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * compute_smoothnet_loss (arctic_tools/src/callbacks/loss/loss_arctic_sf.py:402-548): `loss/cd` of compute_contact_devi_loss
+ * (src/utils/loss_modules.py:186-226) and `acc/h`, `acc/o` of eval_acc_pose / compute_error_accel
+ * (src/utils/eval_modules.py:254-368) over N frames.  dims: HOST ints (N, NV, J, L): frames, hand vertices, hand joints, padded
+ * object rows.  floats: HOST array of 15 device pointers to fp32 contiguous tensors, in this order: the prediction's
+ * mano.v3d.cam.r, .l [N, NV, 3], mano.j3d.cam.r, .l [N, J, 3], object.v.cam [N, L, 3]; the same five of the targets; dist.ro,
+ * dist.lo [N, NV]; is_valid, left_valid, right_valid [N].  longs: 3 device pointers to int64 tensors: idx.ro, idx.lo [N, NV],
+ * object.parts_ids [N, L] (row 0 names the bottom columns, == 2, of every frame).  fps: the stencil is [1, -2, 1] fps^2.
+ *   msda_smooth_loss_supported        1 when the kernels take this geometry: N 1 .. 8192, NV 1 .. 1024, J 1 .. 64,
+ *       L 1 .. 65536.  Any number of bottom columns (none: the object terms are NaN-gated away, as in torch).
+ *   msda_smooth_loss_workspace_bytes  the workspace of a forward call, which its backward call reads (0: unsupported): 6 N
+ *       doubles (the object roots of prediction and gt) followed by 10 N + 4 floats.  It must be 8-byte aligned.
+ *   msda_smooth_loss_forward_f32      three launches whatever the data holds.  losses [3] = loss/cd, acc/h, acc/o; frames
+ *       (may be NULL) [2, N]: eval_acc_pose's acc/h [N] (NaN at both ends and where no hand counts) and acc/o [N - 2] (then
+ *       padding).  A centre frame t counts iff the validity product at t - 1, t, t + 1 sums (fp64) to 3 after truncation to
+ *       int64; the contact deviation counts a frame iff valid * is_valid == 1 and a vertex iff dist <= 3e-3 (a NaN distance
+ *       or an index outside 0 .. L - 1 is left out as nanmean leaves a NaN out).  No counted frame: 0.
+ *   msda_smooth_loss_backward_f32     one launch.  grad_losses [3]; grads: HOST array of 5 device pointers shaped as the
+ *       prediction's five tensors, all written in full; acc_grad = 0 writes the contact gradient only and the two joint
+ *       entries may be NULL.  A zero acceleration difference has a zero gradient.
+ * fp32 inputs, outputs and arithmetic with two exceptions: the object root, a mean of coordinates at the camera's depth whose
+ * fp32 rounding the stencil would multiply by fps^2, is summed, stored and subtracted in fp64 (x - root is then rounded to fp32
+ * once), and the validity sum is fp64 as numpy's.  A NaN or infinite validity flag never counts.  No atomics, fixed summation
+ * order: bitwise reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+int msda_smooth_loss_supported(int N, int NV, int J, int L);
+unsigned long long msda_smooth_loss_workspace_bytes(int N, int NV, int J, int L);
+int msda_smooth_loss_forward_f32(const int *dims, float fps, const float *const *floats, const long long *const *longs,
+                                 float *losses, float *frames, void *workspace, unsigned long long workspace_bytes,
+                                 msda_stream_t stream);
+int msda_smooth_loss_backward_f32(const int *dims, float fps, const float *const *floats, const long long *const *longs,
+                                  const float *grad_losses, int acc_grad, float *const *grads, const void *workspace,
+                                  unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

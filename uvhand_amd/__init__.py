@@ -17,12 +17,21 @@ from .modules import MSDeformAttn
 # the ARCTIC evaluation step (uvhand_amd/arctic_eval.py), resolved on first use so that importing the op stays light
 _ARCTIC_EVAL = ("get_NN", "nn_many", "make_output", "post_process_arctic_output", "prepare_data", "measure_error",
                 "arctic_metrics", "ArcticEvaluator")
-__all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"] + list(_ARCTIC_EVAL)
+# the SmoothNet criterion's losses (uvhand_amd/smooth_loss.py), resolved the same way
+_SMOOTH_LOSS = ("compute_smoothnet_loss", "smooth_loss_reference", "eval_acc_pose", "compute_error_accel")
+__all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"] + list(_ARCTIC_EVAL) + list(_SMOOTH_LOSS) \
+    + ["SmoothCriterion"]
 
 
 def __getattr__(name):
     if name in _ARCTIC_EVAL:
         from . import arctic_eval
         return getattr(arctic_eval, name)
+    if name in _SMOOTH_LOSS:
+        from . import smooth_loss
+        return getattr(smooth_loss, name)
+    if name == "SmoothCriterion":
+        from .modules import SmoothCriterion
+        return SmoothCriterion
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 __version__ = "0.1.0"

@@ -154,6 +154,11 @@ SIGNATURES = {
     "msda_arctic_place_supported": "i iii",
     "msda_arctic_place_forward_f32": "i iif ppp ppp ppp p",
     "msda_arctic_place_backward_f32": "i iif ppp ppp ppp pp p",
+    # the SmoothNet criterion: contact deviation and acceleration errors
+    "msda_smooth_loss_supported": "i iiii",
+    "msda_smooth_loss_workspace_bytes": "U iiii",
+    "msda_smooth_loss_forward_f32": "i p f pp pp p U p",
+    "msda_smooth_loss_backward_f32": "i p f pp p i p p U p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -1858,3 +1863,40 @@ def arctic_place_backward(points, cameras, projects, cam_ts, K, img_res, grad_pl
             *_place_geo(points, cameras, projects), _ptr_array(points), _opt_ptr_array(cam_ts), K.data_ptr(),
             _opt_ptr_array(grad_placed), _opt_ptr_array(grad_n2), _opt_ptr_array(grad_px), _opt_ptr_array(gp), _opt_ptr_array(gc))
     return gp, gc
+
+
+# ---- the SmoothNet criterion: contact deviation and acceleration errors (msda_smooth_loss.hip) ---------------------------------
+SMOOTH_LOSS_TERMS, SMOOTH_LOSS_FLOATS, SMOOTH_LOSS_LONGS, SMOOTH_LOSS_GRADS = 3, 15, 3, 5
+
+
+def smooth_loss_supported(N, NV, J, L):
+    """msda_smooth_loss_supported (include/msda.h): 1 when the kernels take this geometry."""
+    return bool((_lib or load()).msda_smooth_loss_supported(int(N), int(NV), int(J), int(L)))
+
+
+def smooth_loss_workspace_bytes(N, NV, J, L):
+    return int((_lib or load()).msda_smooth_loss_workspace_bytes(int(N), int(NV), int(J), int(L)))
+
+
+def smooth_loss_forward(dims, fps, floats, longs, want_frames=False):
+    """msda_smooth_loss_forward_f32.  floats: the 15 fp32 tensors, longs: the 3 int64 tensors of msda.h.  Returns (losses [3],
+    frames [2, N] or None, workspace for the backward).  Three launches, no host sync."""
+    dev = floats[0].device
+    _nn_check("smooth_loss_forward", dev, list(floats) + list(longs))
+    losses = torch.empty(SMOOTH_LOSS_TERMS, dtype=torch.float32, device=dev)
+    frames = torch.empty(2, dims[0], dtype=torch.float32, device=dev) if want_frames else None
+    ws = torch.empty(max(1, smooth_loss_workspace_bytes(*dims) // 4), dtype=torch.float32, device=dev)
+    _launch(dev, "msda_smooth_loss_forward_f32", "smooth_loss_forward", _int_array(dims), float(fps), _ptr_array(floats),
+            _ptr_array(longs), losses.data_ptr(), _vp(frames), ws.data_ptr(), ws.numel() * 4)
+    return losses, frames, ws
+
+
+def smooth_loss_backward(dims, fps, floats, longs, grad_losses, ws, acc_grad):
+    """msda_smooth_loss_backward_f32.  Returns the gradients of the prediction's five tensors (the two joint tensors: None
+    without acc_grad).  One launch, no atomics."""
+    dev = floats[0].device
+    _nn_check("smooth_loss_backward", dev, list(floats) + list(longs) + [grad_losses, ws])
+    grads = [torch.empty_like(t) if (acc_grad or i not in (2, 3)) else None for i, t in enumerate(floats[:SMOOTH_LOSS_GRADS])]
+    _launch(dev, "msda_smooth_loss_backward_f32", "smooth_loss_backward", _int_array(dims), float(fps), _ptr_array(floats),
+            _ptr_array(longs), grad_losses.data_ptr(), 1 if acc_grad else 0, _opt_ptr_array(grads), ws.data_ptr(), ws.numel() * 4)
+    return grads

@@ -5,7 +5,7 @@ from .deformable_layers import (DeformableTransformerDecoder, DeformableTransfor
 from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
 from .ms_deform_attn import MSDeformAttn
-from .smoothnet import ArcticSmoother, MotionSmoother, Smoother, SmootherResBlock
+from .smoothnet import ArcticSmoother, MotionSmoother, SmoothCriterion, Smoother, SmootherResBlock
 from .swin import (BasicLayer, Joiner, Mlp, PatchEmbed, PatchMerging, PositionEmbeddingSine, SwinTransformer,
                    SwinTransformerBlock, WindowAttention, build_backbone, build_swin_transformer)
 
@@ -13,6 +13,6 @@ __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTrans
            "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
            "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
            "ArcticDeformableDETR", "AssemblyDeformableDETR",
-           "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother",
+           "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother", "SmoothCriterion",
            "Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
            "build_swin_transformer", "PositionEmbeddingSine", "Joiner", "build_backbone"]

@@ -1,18 +1,23 @@
-"""Drop-in SmoothNet modules (models/smoothnet.py:7-178): ``SmootherResBlock``, ``Smoother``, ``MotionSmoother`` and
-``ArcticSmoother``.
+"""Drop-in SmoothNet modules (models/smoothnet.py:7-178 and 202-217): ``SmootherResBlock``, ``Smoother``, ``MotionSmoother``,
+``ArcticSmoother`` and ``SmoothCriterion``.
 
 Constructors, submodule names and creation order and ``ArcticSmoother._reset_parameters`` are the reference's, so a
 reference checkpoint loads with ``strict=True`` and one seed builds a bit-identical ``state_dict``.  ``MotionSmoother.forward``
 and ``ArcticSmoother.forward`` run through one autograd node (``functions.smoother_func.motion_smoothers``): on CUDA fp32 the
 nine MotionSmoother calls of ``ArcticSmoother`` take 9 HIP launches forward instead of several hundred.  Dropout then draws
 from the kernels' own hash, not from ``nn.Dropout``'s stream.  ``SmootherResBlock`` and ``Smoother`` keep the reference's
-forward (they are the parameter containers; called on their own they run torch)."""
+forward (they are the parameter containers; called on their own they run torch).
+
+``SmoothCriterion`` keeps the reference's constructor, ``weight_dict`` and ``forward(args, data, targets, meta_info)`` over
+``prepare_data``'s ``XDict``; its losses come from ``uvhand_amd.smooth_loss.compute_smoothnet_loss`` (three HIP launches
+forward, one backward, no host sync).  ``acc_grad=True`` lets ``acc/h`` and ``acc/o`` carry gradients, which the reference's
+numpy round trip drops."""
 import torch
 from torch import nn
 
 from ..functions.smoother_func import motion_smoothers
 
-__all__ = ["SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother"]
+__all__ = ["SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother", "SmoothCriterion"]
 
 
 class SmootherResBlock(nn.Module):
@@ -127,3 +132,19 @@ class ArcticSmoother(nn.Module):
         outs = motion_smoothers(calls, modules, self.training)
         r = [o.reshape(-1, w) for o, (_, w) in zip(outs, _ARCTIC_CALLS)]
         return r[0:3], r[3:5], r[5:7], r[7:9]
+
+
+class SmoothCriterion(nn.Module):
+    """The SmoothNet criterion: ``forward(args, data, targets, meta_info)`` over ``prepare_data``'s ``XDict`` returns
+    ``{"loss/cd", "acc/h", "acc/o"}``; ``weight_dict`` is the caller's to apply.  It has no parameters."""
+
+    def __init__(self, batch_size, window_size, weight_dict, pre_process_models, acc_grad=False):
+        super().__init__()
+        self.batch_size, self.window_size = batch_size, window_size
+        self.weight_dict, self.pre_process_models = weight_dict, pre_process_models
+        self.acc_grad = acc_grad
+
+    def forward(self, args, data, targets, meta_info):
+        from ..smooth_loss import compute_smoothnet_loss       # resolved on first use: importing the modules stays light
+        return dict(compute_smoothnet_loss(data.search("pred.", ""), data.search("targets.", ""), meta_info,
+                                           self.pre_process_models, args.img_res, acc_grad=self.acc_grad))

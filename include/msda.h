@@ -690,6 +690,20 @@ int msda_swin_attn_backward_f32(int B, int H, int W, int C, int nH, int ws, int 
                                 const float *grad_out, float *grad_qkv, float *grad_table, float *grad_qkv_bias, void *workspace,
                                 unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* The bf16-autocast form of the same node.  Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ * qkv, out, grad_out and grad_qkv are bf16 (uint16_t bit patterns, 16-byte aligned bases); qkv_bias, table, lse, grad_table,
+ * grad_qkv_bias and the workspace stay fp32, and msda_swin_attn_supported / msda_swin_attn_workspace_bytes serve both forms
+ * with the same sizes.  A padded token's k and v are the bias's parts rounded to bf16 (what a bf16 Linear gives a zero row).
+ * Every product runs on the bf16 MFMA with fp32 accumulation; scores (scale, table term, shift mask), softmax, log-sum-exp,
+ * delta and dP stay fp32; P and dS are rounded to bf16 only as matrix operands, out and grad_qkv once.  Same launch counts
+ * (one forward, three backward), same fixed summation order, same argument checks before any launch. */
+int msda_swin_attn_forward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *qkv_bias,
+                                const float *table, uint16_t *out, float *lse, unsigned long long lse_bytes, msda_stream_t stream);
+int msda_swin_attn_backward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv,
+                                 const float *qkv_bias, const float *table, const uint16_t *out, const float *lse,
+                                 unsigned long long lse_bytes, const uint16_t *grad_out, uint16_t *grad_qkv, float *grad_table,
+                                 float *grad_qkv_bias, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* ---- MANO hand layer (smplx MANO with use_pca=False: lbs = Rodrigues, shape and pose blend shapes, kinematic chain, linear
  * blend skinning) over several groups of hands -------------------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

@@ -11,8 +11,13 @@ route: GPU ms per step from device events after warm-up, kernels per step (torch
 geometry (the window-attention node forward + backward on [32 * H * W, 3 C] rows, both routes).  One JSON line each, on
 stdout and appended to --out (default profiles/swin_time.jsonl).
 
-    python tools/swin_time.py [--steps K] [--warmup W] [--only composition|dropin] [--no-attn] [--out FILE]"""
+--autocast runs the same model and step under torch.autocast("cuda", dtype=torch.bfloat16) and times the routes
+`autocast_composition` (what every block takes under autocast by default) and `autocast_bf16` (MSDA_SWIN_BF16=1: the opt-in bf16
+form of the node); the attention-only rows then take bf16 qkv rows.  The default remains the fp32 A/B.
+
+    python tools/swin_time.py [--autocast] [--steps K] [--warmup W] [--only ROUTE] [--no-attn] [--no-backbone] [--out FILE]"""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -80,15 +85,25 @@ def emit(args, rec):
             f.write(line + "\n")
 
 
+def set_route(route):
+    """The environment a route reads at call time."""
+    os.environ["MSDA_SWIN_FUSED"] = "0" if route.endswith("composition") else "1"
+    os.environ["MSDA_SWIN_BF16"] = "1" if route == "autocast_bf16" else "0"
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--autocast", action="store_true", help="bf16 autocast: the composition against MSDA_SWIN_BF16=1")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default=None)
     ap.add_argument("--no-attn", action="store_true")
+    ap.add_argument("--no-backbone", action="store_true", help="only the attention-only rows")
     ap.add_argument("--no-counts", action="store_true", help="skip the profiler / sync / memory passes (for rocprofv3)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "swin_time.jsonl"))
     args = ap.parse_args()
+    routes = ("autocast_composition", "autocast_bf16") if args.autocast else ("composition", "dropin")
+    amp = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.autocast else contextlib.nullcontext
     torch.manual_seed(0)
     body = build_swin_transformer("swin_L_384_22k", pretrain_img_size=384, out_indices=(1, 2, 3), dilation=False,
                                   use_checkpoint=True, drop_path_rate=0.2)
@@ -102,20 +117,21 @@ def main():
 
     def step():
         nonlocal weights
-        feats, _ = model(NestedTensor(img, mask))
+        with amp():
+            feats, _ = model(NestedTensor(img, mask))
         if weights is None:
             weights = [torch.randn(f.tensors.shape, generator=g).to(DEV) for f in feats]
         loss = sum((f.tensors * w).sum() for f, w in zip(feats, weights))
         torch.autograd.grad(loss, params)
 
-    for route in ("composition", "dropin"):
-        if args.only and route != args.only:
+    for route in routes:
+        if args.no_backbone or (args.only and route != args.only):
             continue
-        os.environ["MSDA_SWIN_FUSED"] = "0" if route == "composition" else "1"
+        set_route(route)
         ms = gpu_ms(step, args.steps, args.warmup)
         rec = {"tool": "swin_time", "what": "backbone_fwd_bwd", "route": route, "backbone": "swin_L_384_22k", "frames": FRAMES,
                "img": IMG, "checkpoint": True, "drop_path_rate": 0.2, "gpu_event_ms_per_step": round(ms, 3),
-               "steps": args.steps, "warmup": args.warmup}
+               "steps": args.steps, "warmup": args.warmup, "autocast": "bf16" if args.autocast else None}
         if not args.no_counts:
             rec.update(kernels_per_step=count_kernels(step), host_syncs_per_step=count_syncs(step),
                        max_memory_allocated_mb=round(peak_mb(step), 1))
@@ -125,20 +141,22 @@ def main():
     if not args.no_attn:
         for (H, W, C, nH) in STAGES:
             ws = 12
-            qkv = torch.randn(FRAMES * H * W, 3 * C, device=DEV, requires_grad=True)
+            act = torch.bfloat16 if args.autocast else torch.float32
+            qkv = torch.randn(FRAMES * H * W, 3 * C, device=DEV).to(act).requires_grad_(True)
             bias = torch.randn(3 * C, device=DEV, requires_grad=True)
             table = torch.randn((2 * ws - 1) ** 2, nH, device=DEV, requires_grad=True)
-            go = torch.randn(FRAMES * H * W, C, device=DEV)
+            go = torch.randn(FRAMES * H * W, C, device=DEV).to(act)
             geo = (FRAMES, H, W, C, nH, ws, ws // 2)
 
             def attn():
-                out = window_attention(qkv, bias, table, geo)
+                with amp():
+                    out = window_attention(qkv, bias, table, geo)
                 torch.autograd.grad(out, (qkv, bias, table), go)
 
-            for route in ("composition", "dropin"):
+            for route in routes:
                 if args.only and route != args.only:
                     continue
-                os.environ["MSDA_SWIN_FUSED"] = "0" if route == "composition" else "1"
+                set_route(route)
                 rec = {"tool": "swin_time", "what": "attention_fwd_bwd", "route": route, "frames": FRAMES, "H": H, "W": W,
                        "C": C, "heads": nH, "window": ws, "shift": ws // 2,
                        "gpu_event_ms": round(gpu_ms(attn, args.steps, args.warmup), 4)}
@@ -146,6 +164,7 @@ def main():
                     rec.update(kernels=count_kernels(attn), max_memory_allocated_mb=round(peak_mb(attn), 1))
                 emit(args, rec)
     os.environ.pop("MSDA_SWIN_FUSED", None)
+    os.environ.pop("MSDA_SWIN_BF16", None)
 
 
 if __name__ == "__main__":

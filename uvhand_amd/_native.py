@@ -120,6 +120,8 @@ SIGNATURES = {
     "msda_swin_attn_workspace_bytes": "U iiiiiiii",
     "msda_swin_attn_forward_f32": "i iiiiiii ppppp U p",
     "msda_swin_attn_backward_f32": "i iiiiiii ppppp U ppppp U p",
+    "msda_swin_attn_forward_bf16": "i iiiiiii ppppp U p",
+    "msda_swin_attn_backward_bf16": "i iiiiiii ppppp U ppppp U p",
     # MANO hand layer
     "msda_mano_supported": "i iii",
     "msda_mano_workspace_bytes": "U iiii p",
@@ -1487,7 +1489,7 @@ def arctic_item_backward(idx, Q, grad_outs):
     return gsrc
 
 
-# ---- Swin window attention, head_dim 32 (msda_swin.hip) ------------------------------------------------------------------
+# ---- Swin window attention, head_dim 32, fp32 and bf16 (msda_swin.hip) ---------------------------------------------------
 SWIN_MAX_WINDOW = 12
 
 
@@ -1502,14 +1504,22 @@ def swin_attn_workspace_bytes(geo, which):
 
 
 def _swin_check(what, geo, tensors):
+    """qkv's dtype picks the form: fp32 (every tensor fp32) or bfloat16 (qkv, out and grad_out bfloat16, the rest fp32)."""
     dev = tensors[0].device
-    _check_f32(what, dev, tensors)
-    B, H, W, C, nH, ws, _ = geo
     qkv, bias, table = tensors[:3]
+    bf16 = qkv.dtype == torch.bfloat16
+    _check_f32(what, dev, [bias, table] + ([] if bf16 else [qkv]))
+    acts = [t for t in tensors[3:] if t is not None]
+    if len(acts) == 3:                                              # out, lse, grad_out
+        _check_f32(what, dev, [acts[1]] + ([] if bf16 else [acts[0], acts[2]]))
+    if bf16 and not all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and t.device == dev
+                        for t in [qkv] + acts[:1] + acts[2:]):
+        raise RuntimeError("%s: bfloat16 qkv needs contiguous bfloat16 out and grad_out on its device" % what)
+    B, H, W, C, nH, ws, _ = geo
     if tuple(qkv.shape) != (B * H * W, 3 * C) or (bias is not None and tuple(bias.shape) != (3 * C,)) \
             or tuple(table.shape) != ((2 * ws - 1) ** 2, nH):
         raise RuntimeError("%s: expected qkv [B*H*W, 3C], qkv_bias [3C], table [(2ws-1)^2, nH]" % what)
-    return dev
+    return dev, "bf16" if bf16 else "f32"
 
 
 def _vp(t):
@@ -1517,28 +1527,30 @@ def _vp(t):
 
 
 def swin_attn_forward(geo, qkv, bias, table):
-    """msda_swin_attn_forward_f32: (out [B*H*W, C], lse).  One launch, no host sync."""
+    """msda_swin_attn_forward_f32 / _bf16 by qkv's dtype: (out [B*H*W, C] of that dtype, lse fp32).  One launch, no host sync."""
     geo = tuple(int(g) for g in geo)
-    dev = _swin_check("swin_attn_forward", geo, [qkv, bias, table])
-    out = torch.empty(qkv.shape[0], geo[3], dtype=torch.float32, device=dev)
+    dev, suf = _swin_check("swin_attn_forward", geo, [qkv, bias, table])
+    out = torch.empty(qkv.shape[0], geo[3], dtype=qkv.dtype, device=dev)
     nbytes = swin_attn_workspace_bytes(geo, 0)
     lse = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-    _launch(dev, "msda_swin_attn_forward_f32", "swin_attn_forward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
+    _launch(dev, "msda_swin_attn_forward_" + suf, "swin_attn_forward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
             out.data_ptr(), lse.data_ptr(), lse.numel() * 4)
     return out, lse
 
 
 def swin_attn_backward(geo, qkv, bias, table, out, lse, grad_out):
-    """msda_swin_attn_backward_f32: (grad_qkv [B*H*W, 3C], grad_table, grad_bias [3C] — the padded tokens' part, q part 0 —
-    or None without a bias).  Three launches, no host sync."""
+    """msda_swin_attn_backward_f32 / _bf16 by qkv's dtype: (grad_qkv [B*H*W, 3C] of that dtype, grad_table fp32, grad_bias
+    [3C] fp32 — the padded tokens' part, q part 0 — or None without a bias).  Three launches, no host sync."""
     geo = tuple(int(g) for g in geo)
-    dev = _swin_check("swin_attn_backward", geo, [qkv, bias, table, out, lse, grad_out])
+    dev, suf = _swin_check("swin_attn_backward", geo, [qkv, bias, table, out, lse, grad_out])
+    if tuple(out.shape) != (qkv.shape[0], geo[3]) or out.shape != grad_out.shape:
+        raise RuntimeError("swin_attn_backward: expected out and grad_out [B*H*W, C]")
     gq = torch.empty_like(qkv)
     gt = torch.empty_like(table)
     gb = torch.empty_like(bias) if bias is not None else None
     nbytes = swin_attn_workspace_bytes(geo, 1)
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-    _launch(dev, "msda_swin_attn_backward_f32", "swin_attn_backward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
+    _launch(dev, "msda_swin_attn_backward_" + suf, "swin_attn_backward", *geo, qkv.data_ptr(), _vp(bias), table.data_ptr(),
             out.data_ptr(), lse.data_ptr(), lse.numel() * 4, grad_out.data_ptr(), gq.data_ptr(), gt.data_ptr(), _vp(gb),
             ws.data_ptr(), ws.numel() * 4)
     return gq, gt, gb

@@ -1251,4 +1251,21 @@ int msda_swin_attn_backward_f32(int B, int H, int W, int C, int nH, int ws, int 
                                grad_table, grad_qkv_bias, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int msda_swin_attn_forward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *qkv_bias,
+                                const float *table, uint16_t *out, float *lse, unsigned long long lse_bytes, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::swin_forward_bf16(B, H, W, C, nH, ws, shift, qkv, qkv_bias, table, out, lse, lse_bytes, (hipStream_t)stream);
+}
+
+int msda_swin_attn_backward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv,
+                                 const float *qkv_bias, const float *table, const uint16_t *out, const float *lse,
+                                 unsigned long long lse_bytes, const uint16_t *grad_out, uint16_t *grad_qkv, float *grad_table,
+                                 float *grad_qkv_bias, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::swin_backward_bf16(B, H, W, C, nH, ws, shift, qkv, qkv_bias, table, out, lse, lse_bytes, grad_out, grad_qkv,
+                                    grad_table, grad_qkv_bias, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -326,6 +326,13 @@ int swin_forward(int B, int H, int W, int C, int nH, int ws, int shift, const fl
 int swin_backward(int B, int H, int W, int C, int nH, int ws, int shift, const float *qkv, const float *bias, const float *table,
                   const float *out, const float *lse, unsigned long long lse_bytes, const float *grad_out, float *grad_qkv,
                   float *grad_table, float *grad_bias, void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
+// bf16 qkv / out / grad_out / grad_qkv (bf16 MFMA, fp32 softmax); bias, table, lse, grad_table, grad_bias and the partials fp32
+int swin_forward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *bias,
+                      const float *table, uint16_t *out, float *lse, unsigned long long lse_bytes, hipStream_t stream);
+int swin_backward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *bias,
+                       const float *table, const uint16_t *out, const float *lse, unsigned long long lse_bytes,
+                       const uint16_t *grad_out, uint16_t *grad_qkv, float *grad_table, float *grad_bias, void *workspace,
+                       unsigned long long workspace_bytes, hipStream_t stream);
 
 // ---- the input-projection neck: bias + GroupNorm + feature mask of every level (msda_neck.hip; C entries msda_neck_*) ----
 // Both level tables travel by value in the kernel arguments, as FlattenPlan does.

@@ -467,6 +467,396 @@ int sw_allow_lds(const void *fn, size_t bytes)
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---- bf16 operands (msda_swin_attn_*_bf16) ---------------------------------------------------------------------------------------
+// The same four launches and the same work split with qkv, out, dO and grad_qkv in bf16 and every product on
+// v_mfma_f32_16x16x32_bf16 (fp32 accumulate), following the bf16 block of msda_attn.hip: the pair's operands sit in LDS as bf16
+// rows [Np][40] (N padded to a multiple of 32, padding rows zero), read as a row (ds_read_b128) for the products over channels and
+// transposed (ds_read_b64_tr_b16) for the products over keys / queries; score tiles come in pairs covering 32 keys (queries), tile
+// b's row i being key 32T + 8 (i >> 2) + 4b + (i & 3), so that the accumulators of a pair are the next product's 8-wide operand.
+// fp32: the scores (scale on the fp32 dot product, table term, shift mask), softmax, log-sum-exp, delta, dP, the dS rows the table
+// pass sums (LDS) and every partial.  bf16: P and dS as MFMA operands only; out and grad_qkv, rounded once.  A padded token's k and
+// v are the bias's parts rounded to bf16 (a bf16 Linear on a zero row).  Every loop around a transposed read is wave-uniform.
+// LDS of the q kernel at ws 12: 2 * 160 * 80 + 532 * 4 + 144 * 164 * 4 + 2 * 160 * 4 = 123472 B (the fp32 one: 130000 B).
+constexpr int kSbRow = 40, kSbMaxPairs = (kSwMaxN + 31) / 32;
+using sb_bf8 = __attribute__((ext_vector_type(8))) __bf16;
+using sb_bf4 = __attribute__((ext_vector_type(4))) __bf16;
+typedef __attribute__((address_space(3))) sb_bf4 sb_lds_bf4;
+
+#define SB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+
+__device__ __forceinline__ sb_bf8 sb_ld8(const uint16_t *p) { return *reinterpret_cast<const sb_bf8 *>(p); }
+__device__ __forceinline__ sb_bf8 sb_zero8() { return sb_bf8{}; }
+__device__ __forceinline__ float sb_f(__bf16 x) { return (float)x; }
+
+// the score-tile pair T: acc[b] = rows(X) . bop over the 32 channels, X = LDS slice, rows relabelled as above
+__device__ __forceinline__ void sb_pair(const uint16_t *xs, int T, int r, int c, const sb_bf8 &bop, sw_f4 &acc0, sw_f4 &acc1)
+{
+    const uint16_t *row = xs + (32 * T + 8 * (c >> 2) + (c & 3)) * kSbRow + 8 * r;
+    const sb_bf8 a0 = sb_ld8(row), a1 = sb_ld8(row + 4 * kSbRow);
+    const sw_f4 z = {0.f, 0.f, 0.f, 0.f};
+    acc0 = SB_MFMA(a0, bop, z);
+    acc1 = SB_MFMA(a1, bop, z);
+}
+
+// the transposed operand: lane (c, r) gets X[32T + 8r + j][16 half + c], j = 0..7 (X = LDS slice, rows = keys / queries)
+__device__ __forceinline__ sb_bf8 sb_tr(const uint16_t *xs, int T, int half, int r, int c)
+{
+    const uint16_t *p = xs + (32 * T + 8 * r + (c >> 2)) * kSbRow + 16 * half + 4 * (c & 3);
+    const sb_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sb_lds_bf4 *)p);
+    const sb_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sb_lds_bf4 *)(p + 4 * kSbRow));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ sb_bf8 sb_pack(const sw_f4 &x0, const sw_f4 &x1)
+{
+    return sb_bf8{(__bf16)x0[0], (__bf16)x0[1], (__bf16)x0[2], (__bf16)x0[3], (__bf16)x1[0], (__bf16)x1[1], (__bf16)x1[2], (__bf16)x1[3]};
+}
+
+// 4 accumulator values (scaled) -> 4 bf16 at p (8 bytes)
+__device__ __forceinline__ void sb_st4(uint16_t *p, const sw_f4 &x, float s)
+{
+    *reinterpret_cast<sb_bf4 *>(p) = sb_bf4{(__bf16)(x[0] * s), (__bf16)(x[1] * s), (__bf16)(x[2] * s), (__bf16)(x[3] * s)};
+}
+
+// g: geometry, bias, table, lse, gtable, gbias, pt, pb (its fp32 tensor pointers stay null); the bf16 tensors
+struct SbArgs {
+    SwArgs g;
+    const uint16_t *qkv, *out, *gout;
+    uint16_t *o, *gqkv;
+};
+
+// the k (part 1) or v (part 2) channels c8 .. c8 + 7 of token `row` (padded: the bias's rounded to bf16, or zero), head h
+__device__ __forceinline__ sb_bf8 sb_kv8(const SbArgs &a, int row, int part, int h, int c8)
+{
+    if (row >= 0) return sb_ld8(a.qkv + (long long)row * 3 * a.g.C + part * a.g.C + h * 32 + c8);
+    if (a.g.bias == nullptr) return sb_zero8();
+    const float *bp = a.g.bias + part * a.g.C + h * 32 + c8;
+    const float4 b0 = sw_ld4(bp), b1 = sw_ld4(bp + 4);
+    return sb_bf8{(__bf16)b0.x, (__bf16)b0.y, (__bf16)b0.z, (__bf16)b0.w, (__bf16)b1.x, (__bf16)b1.y, (__bf16)b1.z, (__bf16)b1.w};
+}
+
+// the window's keys: info and qkv row per token, k and v rows into LDS (rows N .. Np - 1 zero)
+__device__ __forceinline__ void sb_fill_kv(const SbArgs &a, int b, int w, int h, int Np, uint16_t *Ks, uint16_t *Vs, int *kinf, int *rows)
+{
+    for (int t = threadIdx.x; t < Np; t += blockDim.x) {
+        SwTok k = {-1, 0, 0};
+        if (t < a.g.N) k = sw_token(a.g, b, w, t, true);
+        kinf[t] = k.rel | (k.reg << 16);
+        rows[t] = k.row;
+    }
+    for (int i = threadIdx.x; i < Np * 4; i += blockDim.x) {
+        const int t = i >> 2, c8 = (i & 3) * 8;
+        sb_bf8 kv = sb_zero8(), vv = sb_zero8();
+        if (t < a.g.N) {
+            const int row = sw_token(a.g, b, w, t, true).row;
+            kv = sb_kv8(a, row, 1, h, c8);
+            vv = sb_kv8(a, row, 2, h, c8);
+        }
+        *reinterpret_cast<sb_bf8 *>(Ks + t * kSbRow + c8) = kv;
+        *reinterpret_cast<sb_bf8 *>(Vs + t * kSbRow + c8) = vv;
+    }
+}
+
+// the 8 infos of tokens 32T + 8r .. + 7
+__device__ __forceinline__ void sb_info8(const int *inf, int T, int r, int (&v)[8])
+{
+    const int4 x = *reinterpret_cast<const int4 *>(inf + 32 * T + 8 * r), y = *reinterpret_cast<const int4 *>(inf + 32 * T + 8 * r + 4);
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
+}
+
+__global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_bf16_kernel(const SbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sw_smem[];
+    const SwArgs &g = a.g;
+    const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5;
+    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kSbRow;
+    float *tbl = reinterpret_cast<float *>(Vs + Np * kSbRow);
+    int *kinf = reinterpret_cast<int *>(tbl + Ep), *rows = kinf + Np;
+    int b, w, h;
+    sw_pair(g, b, w, h);
+    sb_fill_kv(a, b, w, h, Np, Ks, Vs, kinf, rows);
+    sw_load_table(g, h, tbl);
+    __syncthreads();
+    const int tq = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = tq * 16 + c;
+    const int qrow = qi < g.N ? rows[qi] : -1;
+    if (!__any(qrow >= 0)) return;                                      // a tile of padded tokens only: nothing to write
+    const SwTok qt = sw_token(g, b, w, qi < g.N ? qi : 0, false);
+    sb_bf8 qf = sb_zero8();
+    if (qrow >= 0) qf = sb_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
+    // s[2T + b][v] = score (base 2) of key 32T + 8r + 4b + v for query qi
+    sw_f4 s[2 * kSbMaxPairs];
+    float m = -INFINITY;
+#pragma unroll
+    for (int T = 0; T < kSbMaxPairs; ++T) {
+        if (T < npair) {
+            sb_pair(Ks, T, r, c, qf, s[2 * T], s[2 * T + 1]);
+            int kv[8];
+            sb_info8(kinf, T, r, kv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x = sw_score2(s[2 * T + (j >> 2)][j & 3] * g.scale, tbl, qt.rel, qt.reg, kv[j], 32 * T + 8 * r + j < g.N);
+                s[2 * T + (j >> 2)][j & 3] = x;
+                m = fmaxf(m, x);
+            }
+        }
+    }
+    m = sw_rmax(m);
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2 * kSbMaxPairs; ++t) {
+        if (t < 2 * npair) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) { s[t][v] = __builtin_amdgcn_exp2f(s[t][v] - m); sum += s[t][v]; }
+        }
+    }
+    sum = sw_rsum(sum);
+    const long long pair = blockIdx.x;
+    if (qrow >= 0 && r == 0) g.lse[pair * g.N + qi] = (m + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f;
+    const float inv = 1.f / sum;
+    sw_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+#pragma unroll
+    for (int T = 0; T < kSbMaxPairs; ++T) {
+        if (T < npair) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) { s[2 * T][v] *= inv; s[2 * T + 1][v] *= inv; }
+            const sb_bf8 pb = sb_pack(s[2 * T], s[2 * T + 1]);          // P^T[key 32T + 8r + j][query qi]
+            o0 = SB_MFMA(sb_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
+            o1 = SB_MFMA(sb_tr(Vs, T, 1, r, c), pb, o1);
+        }
+    }
+    if (qrow >= 0) {
+        uint16_t *op = a.o + (long long)qrow * g.C + h * 32 + 4 * r;
+        sb_st4(op, o0, 1.f);
+        sb_st4(op + 16, o1, 1.f);
+    }
+}
+
+// dK, dV: wavefront tk owns keys 16 tk .. 16 tk + 15 and walks the query pairs (S tiles: rows = queries)
+__global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_bf16_kernel(const SbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sw_smem[];
+    const SwArgs &g = a.g;
+    const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5, nwave = blockDim.x >> 6;
+    uint16_t *Qs = reinterpret_cast<uint16_t *>(sw_smem), *Gs = Qs + Np * kSbRow;
+    float *tbl = reinterpret_cast<float *>(Gs + Np * kSbRow), *lse_s = tbl + Ep, *del_s = lse_s + Np;
+    float *part = del_s + Np;                                           // [waves][64]
+    int *qinf = reinterpret_cast<int *>(part + nwave * 64), *rows = qinf + Np, *pany = rows + Np;
+    int b, w, h;
+    sw_pair(g, b, w, h);
+    const long long pair = blockIdx.x;
+    for (int t = threadIdx.x; t < Np; t += blockDim.x) {
+        SwTok q = {-1, 0, 0};
+        if (t < g.N) q = sw_token(g, b, w, t, false);
+        qinf[t] = q.rel | (q.reg << 16);
+        rows[t] = q.row;
+    }
+    sw_load_table(g, h, tbl);
+    for (int i = threadIdx.x; i < Np * 4; i += blockDim.x) {
+        const int t = i >> 2, c8 = (i & 3) * 8;
+        const int row = t < g.N ? sw_token(g, b, w, t, false).row : -1;
+        sb_bf8 qv = sb_zero8(), gv = sb_zero8();
+        if (row >= 0) {
+            qv = sb_ld8(a.qkv + (long long)row * 3 * g.C + h * 32 + c8);
+            gv = sb_ld8(a.gout + (long long)row * g.C + h * 32 + c8);
+        }
+        *reinterpret_cast<sb_bf8 *>(Qs + t * kSbRow + c8) = qv;
+        *reinterpret_cast<sb_bf8 *>(Gs + t * kSbRow + c8) = gv;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < Np; t += blockDim.x) {
+        const int row = rows[t];
+        float d = 0.f;
+        if (row >= 0) {
+            const uint16_t *orow = a.out + (long long)row * g.C + h * 32, *grow = Gs + t * kSbRow;
+#pragma unroll
+            for (int k8 = 0; k8 < 4; ++k8) {
+                const sb_bf8 ov = sb_ld8(orow + 8 * k8), gv = sb_ld8(grow + 8 * k8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d += sb_f(ov[j]) * sb_f(gv[j]);
+            }
+        }
+        del_s[t] = d;
+        lse_s[t] = row >= 0 ? g.lse[pair * g.N + t] * kLog2e : INFINITY;    // padded queries: probabilities 0
+    }
+    for (int t = threadIdx.x; t < npair; t += blockDim.x) {
+        int any = 0;
+        for (int u = 0; u < 32; ++u) any |= rows[32 * t + u] >= 0;
+        pany[t] = any;
+    }
+    __syncthreads();
+    const int tk = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int key = tk * 16 + c;
+    const bool kok = key < g.N;
+    const SwTok kt = sw_token(g, b, w, kok ? key : 0, true);
+    const int krow = kok ? kt.row : -1;
+    sb_bf8 kf = sb_zero8(), vf = sb_zero8();
+    if (kok) {
+        kf = sb_kv8(a, krow, 1, h, 8 * r);
+        vf = sb_kv8(a, krow, 2, h, 8 * r);
+    }
+    const int kinfo = (kt.rel & 0xffff) | (kt.reg << 16);
+    sw_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+#pragma unroll 1
+    for (int T = 0; T < npair; ++T) {
+        if (!pany[T]) continue;                                         // (the same for every lane of the workgroup)
+        // S and dP tiles of the pair: entry (b, v) = (query 32T + 8r + 4b + v, key)
+        sw_f4 s[2], dp[2];
+        sb_pair(Qs, T, r, c, kf, s[0], s[1]);
+        sb_pair(Gs, T, r, c, vf, dp[0], dp[1]);
+        const float *lq = lse_s + 32 * T + 8 * r, *dq = del_s + 32 * T + 8 * r;
+        const float4 l0 = sw_ld4(lq), l1 = sw_ld4(lq + 4), d0 = sw_ld4(dq), d1 = sw_ld4(dq + 4);
+        const float lsv[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w}, dlv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+        int qv[8];
+        sb_info8(qinf, T, r, qv);
+        sw_f4 pd[2], ds[2];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int bb = j >> 2, v = j & 3;
+            // (query info and key info swap roles: the table index is the sum of the two parts either way)
+            const float sc = sw_score2(s[bb][v] * g.scale, tbl, qv[j] & 0xffff, qv[j] >> 16, kinfo, true);
+            const float p = __builtin_amdgcn_exp2f(sc - lsv[j]);
+            pd[bb][v] = p;
+            ds[bb][v] = p * (dp[bb][v] - dlv[j]);
+        }
+        const sb_bf8 pb = sb_pack(pd[0], pd[1]), sb = sb_pack(ds[0], ds[1]);
+        dv0 = SB_MFMA(sb_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P
+        dv1 = SB_MFMA(sb_tr(Gs, T, 1, r, c), pb, dv1);
+        dk0 = SB_MFMA(sb_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
+        dk1 = SB_MFMA(sb_tr(Qs, T, 1, r, c), sb, dk1);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { dk0[v] *= g.scale; dk1[v] *= g.scale; }
+    if (krow >= 0) {
+        uint16_t *gk = a.gqkv + (long long)krow * 3 * g.C + g.C + h * 32 + 4 * r, *gv = gk + g.C;
+        sb_st4(gk, dk0, 1.f); sb_st4(gk + 16, dk1, 1.f);
+        sb_st4(gv, dv0, 1.f); sb_st4(gv + 16, dv1, 1.f);
+    }
+    // padded keys of this tile: their k / v gradients summed (a butterfly over the 16 keys), then over the wavefronts in order
+    const bool kpad = kok && krow < 0;
+    float acc[16];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        acc[v] = kpad ? dk0[v] : 0.f; acc[4 + v] = kpad ? dk1[v] : 0.f;
+        acc[8 + v] = kpad ? dv0[v] : 0.f; acc[12 + v] = kpad ? dv1[v] : 0.f;
+    }
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc[u] += __shfl_xor(acc[u], m);
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            part[tk * 64 + 4 * r + v] = acc[v];
+            part[tk * 64 + 16 + 4 * r + v] = acc[4 + v];
+            part[tk * 64 + 32 + 4 * r + v] = acc[8 + v];
+            part[tk * 64 + 48 + 4 * r + v] = acc[12 + v];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float sum = 0.f;
+        for (int u = 0; u < nwave; ++u) sum += part[u * 64 + threadIdx.x];
+        g.pb[pair * 64 + threadIdx.x] = sum;
+    }
+}
+
+// dQ: wavefront tq owns queries 16 tq .. 16 tq + 15 and walks the key pairs (S^T tiles, as the forward); fp32 dS rows into LDS,
+// then the per-pair table partial
+__global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_bf16_kernel(const SbArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float sw_smem[];
+    const SwArgs &g = a.g;
+    const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5, dss = Np + 4, nq = (blockDim.x >> 6) * 16;
+    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kSbRow;
+    float *tbl = reinterpret_cast<float *>(Vs + Np * kSbRow), *dS = tbl + Ep;       // dS [nq][dss]
+    int *kinf = reinterpret_cast<int *>(dS + nq * dss), *rows = kinf + Np;
+    int b, w, h;
+    sw_pair(g, b, w, h);
+    const long long pair = blockIdx.x;
+    sb_fill_kv(a, b, w, h, Np, Ks, Vs, kinf, rows);
+    sw_load_table(g, h, tbl);
+    __syncthreads();
+    const int tq = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = tq * 16 + c;
+    const int qrow = qi < g.N ? rows[qi] : -1;
+    float *dsrow = dS + qi * dss;
+    if (__any(qrow >= 0)) {
+        const SwTok qt = sw_token(g, b, w, qi < g.N ? qi : 0, false);
+        sb_bf8 qf = sb_zero8(), gf = sb_zero8(), of = sb_zero8();
+        float lse = INFINITY;
+        if (qrow >= 0) {
+            qf = sb_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
+            gf = sb_ld8(a.gout + (long long)qrow * g.C + h * 32 + 8 * r);
+            of = sb_ld8(a.out + (long long)qrow * g.C + h * 32 + 8 * r);
+            lse = g.lse[pair * g.N + qi] * kLog2e;
+        }
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += sb_f(gf[j]) * sb_f(of[j]);
+        const float delta = sw_rsum(d);
+        sw_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+#pragma unroll 1
+        for (int T = 0; T < npair; ++T) {
+            // S^T and dP^T tiles of the pair: entry (b, v) = (key 32T + 8r + 4b + v, query qi)
+            sw_f4 s[2], dp[2], ds[2];
+            sb_pair(Ks, T, r, c, qf, s[0], s[1]);
+            sb_pair(Vs, T, r, c, gf, dp[0], dp[1]);
+            int kv[8];
+            sb_info8(kinf, T, r, kv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int bb = j >> 2, v = j & 3;
+                const float sc = sw_score2(s[bb][v] * g.scale, tbl, qt.rel, qt.reg, kv[j], 32 * T + 8 * r + j < g.N);
+                const float p = __builtin_amdgcn_exp2f(sc - lse);
+                ds[bb][v] = p * (dp[bb][v] - delta);
+            }
+            const sb_bf8 sb = sb_pack(ds[0], ds[1]);
+            dq0 = SB_MFMA(sb_tr(Ks, T, 0, r, c), sb, dq0);              // dQ^T[channel][query] += K^T . dS^T
+            dq1 = SB_MFMA(sb_tr(Ks, T, 1, r, c), sb, dq1);
+            sw_st4(dsrow + 32 * T + 8 * r, ds[0]);
+            sw_st4(dsrow + 32 * T + 8 * r + 4, ds[1]);
+        }
+        if (qrow >= 0) {
+            uint16_t *gq = a.gqkv + (long long)qrow * 3 * g.C + h * 32 + 4 * r;
+            sb_st4(gq, dq0, g.scale);
+            sb_st4(gq + 16, dq1, g.scale);
+        }
+    } else {
+        for (int T = 0; T < npair; ++T) {
+            sw_st4(dsrow + 32 * T + 8 * r, sw_f4{0.f, 0.f, 0.f, 0.f});
+            sw_st4(dsrow + 32 * T + 8 * r + 4, sw_f4{0.f, 0.f, 0.f, 0.f});
+        }
+    }
+    __syncthreads();
+    // (the table pass of swin_bwd_q_kernel)
+    const int w2 = 2 * g.ws - 1;
+    for (int e = threadIdx.x; e < g.E; e += blockDim.x) {
+        const int dy = e / w2 - (g.ws - 1), dx = e % w2 - (g.ws - 1), off = dy * g.ws + dx;
+        const int y0 = max(0, dy), y1 = min(g.ws, g.ws + dy), x0 = max(0, dx), x1 = min(g.ws, g.ws + dx);
+        float acc = 0.f;
+        for (int yi = y0; yi < y1; ++yi)
+            for (int xi = x0; xi < x1; ++xi) {
+                const int i = yi * g.ws + xi;
+                acc += dS[i * dss + i - off];
+            }
+        g.pt[pair * g.E + e] = acc;
+    }
+}
+
+size_t sb_lds_fwd(int N, int E) { const int Np = (N + 31) & ~31; return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np) * 4; }
+size_t sb_lds_kv(int N, int E)
+{
+    const int Np = (N + 31) & ~31, nwave = (N + 15) / 16;
+    return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np + nwave * 64 + 2 * Np + (Np >> 5)) * 4;
+}
+size_t sb_lds_q(int N, int E)
+{
+    const int Np = (N + 31) & ~31, nq = (N + 15) / 16 * 16;
+    return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + nq * (Np + 4) + 2 * Np) * 4;
+}
+
 }  // namespace
 
 bool swin_supported(int B, int H, int W, int C, int nH, int ws, int shift)
@@ -555,6 +945,67 @@ int swin_backward(int B, int H, int W, int C, int nH, int ws, int shift, const f
     const long long outs = (long long)a.E * nH + 3LL * C;
     const unsigned blocks = (unsigned)((outs + kSwRedBlock / 64 - 1) / (kSwRedBlock / 64));
     hipLaunchKernelGGL(swin_bwd_reduce_kernel, dim3(blocks), dim3(kSwRedBlock), 0, stream, a);
+    return check_launch("swin_bwd_reduce_kernel");
+}
+
+int swin_forward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *bias,
+                      const float *table, uint16_t *out, float *lse, unsigned long long lse_bytes, hipStream_t stream)
+{
+    if (!swin_supported(B, H, W, C, nH, ws, shift))
+        return serr("msda_swin_attn: need B, H, W, nH >= 1, C == 32 nH, 1 <= ws <= 12, 0 <= shift < ws, tensors below 2^31 elements");
+    if (qkv == nullptr || table == nullptr || out == nullptr || lse == nullptr) return serr("msda_swin_attn: null pointer");
+    if (!aligned16(qkv) || !aligned16(out) || (bias != nullptr && !aligned16(bias)))
+        return serr("msda_swin_attn: qkv, qkv_bias and out must be 16-byte aligned");
+    if (lse_bytes < swin_workspace_bytes(B, H, W, C, nH, ws, shift, 0))
+        return serr("msda_swin_attn: lse buffer smaller than msda_swin_attn_workspace_bytes(..., 0)");
+    SbArgs a = {};
+    a.g = sw_args(B, H, W, C, nH, ws, shift);
+    a.g.bias = bias; a.g.table = table; a.g.lse = lse; a.qkv = qkv; a.o = out;
+    const int pairs = B * a.g.nW * nH, threads = 64 * ((a.g.N + 15) / 16);
+    const size_t lds = sb_lds_fwd(a.g.N, a.g.E);
+    int rc = sw_allow_lds(reinterpret_cast<const void *>(swin_fwd_bf16_kernel), lds);
+    if (rc != MSDA_OK) return rc;
+    hipLaunchKernelGGL(swin_fwd_bf16_kernel, dim3((unsigned)pairs), dim3((unsigned)threads), lds, stream, a);
+    return check_launch("swin_fwd_bf16_kernel");
+}
+
+int swin_backward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, const uint16_t *qkv, const float *bias,
+                       const float *table, const uint16_t *out, const float *lse, unsigned long long lse_bytes,
+                       const uint16_t *grad_out, uint16_t *grad_qkv, float *grad_table, float *grad_bias, void *workspace,
+                       unsigned long long workspace_bytes, hipStream_t stream)
+{
+    if (!swin_supported(B, H, W, C, nH, ws, shift))
+        return serr("msda_swin_attn: need B, H, W, nH >= 1, C == 32 nH, 1 <= ws <= 12, 0 <= shift < ws, tensors below 2^31 elements");
+    if (qkv == nullptr || table == nullptr || out == nullptr || lse == nullptr || grad_out == nullptr || grad_qkv == nullptr
+        || grad_table == nullptr || workspace == nullptr)
+        return serr("msda_swin_attn: null pointer");
+    if (!aligned16(qkv) || !aligned16(out) || !aligned16(grad_out) || !aligned16(grad_qkv) || !aligned16(workspace)
+        || (bias != nullptr && !aligned16(bias)))
+        return serr("msda_swin_attn: qkv, qkv_bias, out, grad_out, grad_qkv and the workspace must be 16-byte aligned");
+    if (lse_bytes < swin_workspace_bytes(B, H, W, C, nH, ws, shift, 0))
+        return serr("msda_swin_attn: lse buffer smaller than msda_swin_attn_workspace_bytes(..., 0)");
+    if (workspace_bytes < swin_workspace_bytes(B, H, W, C, nH, ws, shift, 1))
+        return serr("msda_swin_attn: workspace smaller than msda_swin_attn_workspace_bytes(..., 1)");
+    SbArgs a = {};
+    a.g = sw_args(B, H, W, C, nH, ws, shift);
+    a.g.bias = bias; a.g.table = table; a.g.lse = const_cast<float *>(lse); a.g.gtable = grad_table; a.g.gbias = grad_bias;
+    a.qkv = qkv; a.out = out; a.gout = grad_out; a.gqkv = grad_qkv;
+    const int pairs = B * a.g.nW * nH, threads = 64 * ((a.g.N + 15) / 16);
+    a.g.pt = static_cast<float *>(workspace);
+    a.g.pb = a.g.pt + (long long)pairs * a.g.E;
+    const size_t lkv = sb_lds_kv(a.g.N, a.g.E), lq = sb_lds_q(a.g.N, a.g.E);
+    int rc = sw_allow_lds(reinterpret_cast<const void *>(swin_bwd_kv_bf16_kernel), lkv);
+    if (rc == MSDA_OK) rc = sw_allow_lds(reinterpret_cast<const void *>(swin_bwd_q_bf16_kernel), lq);
+    if (rc != MSDA_OK) return rc;
+    hipLaunchKernelGGL(swin_bwd_kv_bf16_kernel, dim3((unsigned)pairs), dim3((unsigned)threads), lkv, stream, a);
+    rc = check_launch("swin_bwd_kv_bf16_kernel");
+    if (rc != MSDA_OK) return rc;
+    hipLaunchKernelGGL(swin_bwd_q_bf16_kernel, dim3((unsigned)pairs), dim3((unsigned)threads), lq, stream, a);
+    rc = check_launch("swin_bwd_q_bf16_kernel");
+    if (rc != MSDA_OK) return rc;
+    const long long outs = (long long)a.g.E * nH + 3LL * C;             // the fp32 form's reduce: every partial is fp32
+    const unsigned blocks = (unsigned)((outs + kSwRedBlock / 64 - 1) / (kSwRedBlock / 64));
+    hipLaunchKernelGGL(swin_bwd_reduce_kernel, dim3(blocks), dim3(kSwRedBlock), 0, stream, a.g);
     return check_launch("swin_bwd_reduce_kernel");
 }
 

@@ -10,13 +10,18 @@ qkv_bias (autograd adds it to the Linear's own bias gradient).
 On CUDA fp32 with head_dim 32 and windows up to 12 it is ``_SwinAttnFunction``: one HIP launch forward, three backward
 (``csrc/msda_swin.hip``), no host synchronisation, bitwise reproducible.  Everything else runs ``window_attention_reference``,
 a torch restatement of the reference's path: CPU tensors, autocast, other dtypes, head_dim != 32 and ``MSDA_SWIN_FUSED=0``
-(A/B knob)."""
+(A/B knob).
+
+``MSDA_SWIN_BF16=1`` (opt-in, read at call time, default off) adds the bf16 form: under bf16 autocast the qkv Linear's bf16 rows
+go through the same node on the bf16 MFMA kernels (out and grad_qkv bf16; table, bias, log-sum-exp and their gradients fp32),
+and so do bf16 rows outside autocast.  fp16 autocast keeps the restatement."""
 import os
 
 import torch
 import torch.nn.functional as F
 
 from .. import _native
+from .linear_func import _autocast_dtype
 
 HEAD_DIM = 32
 
@@ -106,13 +111,23 @@ def _fused_enabled():
     return os.environ.get("MSDA_SWIN_FUSED", "1") != "0"        # A/B knob: 0 = the torch restatement
 
 
+def _bf16_enabled():
+    return os.environ.get("MSDA_SWIN_BF16", "0") not in ("", "0")      # opt-in: the bf16 form of the node (default off)
+
+
 def fused_route(device, dtype, C, nH, ws):
-    """True when a block of this kind takes the HIP node: CUDA fp32, head_dim 32, ws <= 12, no autocast, knob on."""
-    return (_fused_enabled() and device.type == "cuda" and dtype == torch.float32 and not torch.is_autocast_enabled()
-            and nH > 0 and C == HEAD_DIM * nH and 1 <= ws <= _native.SWIN_MAX_WINDOW)
+    """True when a block of this kind takes the HIP node: CUDA, head_dim 32, ws <= 12, knob on, and fp32 outside autocast.
+    With MSDA_SWIN_BF16=1 also under bf16 autocast (dtype: the fp32 residual stream, or the qkv Linear's bf16 output) and for
+    bf16 rows outside autocast.  fp16 autocast always takes the composition."""
+    if not (_fused_enabled() and device.type == "cuda" and nH > 0 and C == HEAD_DIM * nH and 1 <= ws <= _native.SWIN_MAX_WINDOW):
+        return False
+    if torch.is_autocast_enabled():
+        return _bf16_enabled() and _autocast_dtype() == torch.bfloat16 and dtype in (torch.float32, torch.bfloat16)
+    return dtype == torch.float32 or (dtype == torch.bfloat16 and _bf16_enabled())
 
 
 def _fused_ok(qkv_rows, qkv_bias, table, geometry):
+    """The node takes qkv_rows as they are: fp32 rows run the fp32 kernels, bf16 rows the bf16 ones."""
     B, H, W, C, nH, ws, _ = geometry
     if not fused_route(qkv_rows.device, qkv_rows.dtype, C, nH, ws):
         return False
@@ -137,6 +152,8 @@ class _SwinAttnFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         qkv_rows, qkv_bias, table, out, lse = ctx.saved_tensors
+        if grad_out.dtype != out.dtype:                  # (the node's output type: fp32, or bf16 under autocast)
+            grad_out = grad_out.to(out.dtype)
         gq, gt, gb = _native.swin_attn_backward(ctx.geometry, qkv_rows, qkv_bias, table, out, lse, grad_out.contiguous())
         return None, gq, gb, gt
 

@@ -704,6 +704,78 @@ int msda_swin_attn_backward_bf16(int B, int H, int W, int C, int nH, int ws, int
                                  unsigned long long lse_bytes, const uint16_t *grad_out, uint16_t *grad_qkv, float *grad_table,
                                  float *grad_qkv_bias, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- The Swin blocks' residual, drop-path and LayerNorm glue, and PatchMerging's gather + norm (models/swin_transformer.py:
+ * 209-245 SwinTransformerBlock.forward's norm1 / shortcut + drop_path / norm2 / x + drop_path, :263-287 PatchMerging.forward) ----
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Rows x and y [rows, C] are fp32 (the residual stream).  T, the suffix, is the type of the branch a [rows, C], of the drop-path
+ * scale keep [ceil(rows / rows_per_sample)] (NULL: 1), of the normalised rows z and of their gradients: float (_f32) or bf16 bit
+ * patterns (_bf16).  Widths: C % 4 == 0 and 0 < C <= 3072 (msda_swin_glue_supported); fp32 rows and parameters 16-byte aligned,
+ * bf16 rows 8-byte; rows_per_sample > 0; 0 <= rows <= 2^32.  rnd_T rounds to bf16 (nearest even) for _bf16 and is the identity
+ * for _f32; no product is contracted with the add that follows it, so y is what torch's x + a * keep gives, bit for bit.
+ *   norm        forward   z = LN(x) gamma + beta; mean, rstd [rows] saved.
+ *               backward  grad_x from grad_z; grad_gamma, grad_beta.
+ *   add_norm    forward   y = x + rnd_T(a keep[row / rows_per_sample]), z = LN(y) gamma + beta, in one launch.
+ *               backward  grad_x = grad_y + LN'(grad_z), grad_a = rnd_T(rnd_T(grad_x) keep[..]) (keep NULL: rnd_T(grad_x)) in the
+ *                         same pass, from the saved y; grad_a may be NULL for _f32 without keep (it equals grad_x).
+ *   add         forward   y = x + rnd_T(a keep[..]).   backward  grad_a as above from grad_y (grad_x is grad_y itself).
+ *   merge_norm  x [B, H, W, C] -> z [B, ceil(H/2) ceil(W/2), 4 C] = LN over the channels of tokens (2i, 2j), (2i+1, 2j),
+ *               (2i, 2j+1), (2i+1, 2j+1) in this order, zeros where an odd H or W is padded; 4 C <= 3072; gamma, beta [4 C].
+ *               backward  grad_x [B, H, W, C]: every element written once.
+ * Each forward is one launch; each backward with parameter gradients is two (the rows' pass, which leaves per-workgroup partial
+ * column sums in the workspace, and one fixed-order reduction): no float atomics, bitwise reproducible.  add's backward is one.
+ * msda_swin_glue_workspace_bytes(rows, C) = min(1024, max(1, ceil(rows / 16))) * 2 * C * 4 (0 for an unsupported width); for
+ * merge_norm with rows = B ceil(H/2) ceil(W/2) and the width 4 C.  The workspace is 16-byte aligned.  No allocation, no
+ * synchronisation; argument errors before any launch. */
+int msda_swin_glue_supported(int C);
+unsigned long long msda_swin_glue_workspace_bytes(long long rows, int C);
+int msda_swin_glue_norm_forward_f32(const float *x, const float *gamma, const float *beta, long long rows, int C, float eps,
+                                    float *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_norm_forward_bf16(const float *x, const float *gamma, const float *beta, long long rows, int C, float eps,
+                                     uint16_t *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_norm_backward_f32(const float *grad_z, const float *x, const float *gamma, const float *mean,
+                                     const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma,
+                                     float *grad_beta, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+int msda_swin_glue_norm_backward_bf16(const uint16_t *grad_z, const float *x, const float *gamma, const float *mean,
+                                      const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma,
+                                      float *grad_beta, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+int msda_swin_glue_add_norm_forward_f32(const float *x, const float *a, const float *keep, long long rows,
+                                        long long rows_per_sample, int C, const float *gamma, const float *beta, float eps,
+                                        float *y, float *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_add_norm_forward_bf16(const float *x, const uint16_t *a, const uint16_t *keep, long long rows,
+                                         long long rows_per_sample, int C, const float *gamma, const float *beta, float eps,
+                                         float *y, uint16_t *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_add_norm_backward_f32(const float *grad_y, const float *grad_z, const float *y, const float *keep,
+                                         const float *gamma, const float *mean, const float *rstd, long long rows,
+                                         long long rows_per_sample, int C, float *grad_x, float *grad_a, float *grad_gamma,
+                                         float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                         msda_stream_t stream);
+int msda_swin_glue_add_norm_backward_bf16(const float *grad_y, const uint16_t *grad_z, const float *y, const uint16_t *keep,
+                                          const float *gamma, const float *mean, const float *rstd, long long rows,
+                                          long long rows_per_sample, int C, float *grad_x, uint16_t *grad_a, float *grad_gamma,
+                                          float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                          msda_stream_t stream);
+int msda_swin_glue_add_forward_f32(const float *x, const float *a, const float *keep, long long rows, long long rows_per_sample,
+                                   int C, float *y, msda_stream_t stream);
+int msda_swin_glue_add_forward_bf16(const float *x, const uint16_t *a, const uint16_t *keep, long long rows,
+                                    long long rows_per_sample, int C, float *y, msda_stream_t stream);
+int msda_swin_glue_add_backward_f32(const float *grad_y, const float *keep, long long rows, long long rows_per_sample, int C,
+                                    float *grad_a, msda_stream_t stream);
+int msda_swin_glue_add_backward_bf16(const float *grad_y, const uint16_t *keep, long long rows, long long rows_per_sample, int C,
+                                     uint16_t *grad_a, msda_stream_t stream);
+int msda_swin_glue_merge_norm_forward_f32(const float *x, int B, int H, int W, int C, const float *gamma, const float *beta,
+                                          float eps, float *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_merge_norm_forward_bf16(const float *x, int B, int H, int W, int C, const float *gamma, const float *beta,
+                                           float eps, uint16_t *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_merge_norm_backward_f32(const float *grad_z, const float *x, const float *gamma, const float *mean,
+                                           const float *rstd, int B, int H, int W, int C, float *grad_x, float *grad_gamma,
+                                           float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                           msda_stream_t stream);
+int msda_swin_glue_merge_norm_backward_bf16(const uint16_t *grad_z, const float *x, const float *gamma, const float *mean,
+                                            const float *rstd, int B, int H, int W, int C, float *grad_x, float *grad_gamma,
+                                            float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                            msda_stream_t stream);
+
 /* ---- MANO hand layer (smplx MANO with use_pca=False: lbs = Rodrigues, shape and pose blend shapes, kinematic chain, linear
  * blend skinning) over several groups of hands -------------------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

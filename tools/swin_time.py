@@ -15,7 +15,11 @@ stdout and appended to --out (default profiles/swin_time.jsonl).
 `autocast_composition` (what every block takes under autocast by default) and `autocast_bf16` (MSDA_SWIN_BF16=1: the opt-in bf16
 form of the node); the attention-only rows then take bf16 qkv rows.  The default remains the fp32 A/B.
 
-    python tools/swin_time.py [--autocast] [--steps K] [--warmup W] [--only ROUTE] [--no-attn] [--no-backbone] [--out FILE]"""
+--glue times the kernel route without and with MSDA_SWIN_GLUE=1 (the blocks' norms, residual adds and drop-path products and the
+patch mergings on HIP) in one process: `dropin` against `dropin_glue`, or with --autocast `autocast_bf16` against
+`autocast_bf16_glue`.  The glue does not touch the attention node, so --glue writes no attention-only rows.
+
+    python tools/swin_time.py [--autocast] [--glue] [--steps K] [--warmup W] [--only ROUTE] [--no-attn] [--no-backbone] [--out FILE]"""
 import argparse
 import contextlib
 import json
@@ -88,12 +92,14 @@ def emit(args, rec):
 def set_route(route):
     """The environment a route reads at call time."""
     os.environ["MSDA_SWIN_FUSED"] = "0" if route.endswith("composition") else "1"
-    os.environ["MSDA_SWIN_BF16"] = "1" if route == "autocast_bf16" else "0"
+    os.environ["MSDA_SWIN_BF16"] = "1" if route.startswith("autocast_bf16") else "0"
+    os.environ["MSDA_SWIN_GLUE"] = "1" if route.endswith("_glue") else "0"
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--autocast", action="store_true", help="bf16 autocast: the composition against MSDA_SWIN_BF16=1")
+    ap.add_argument("--glue", action="store_true", help="the kernel route without and with MSDA_SWIN_GLUE=1")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default=None)
@@ -103,6 +109,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "swin_time.jsonl"))
     args = ap.parse_args()
     routes = ("autocast_composition", "autocast_bf16") if args.autocast else ("composition", "dropin")
+    if args.glue:
+        routes = (routes[1], routes[1] + "_glue")
+        args.no_attn = True
     amp = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.autocast else contextlib.nullcontext
     torch.manual_seed(0)
     body = build_swin_transformer("swin_L_384_22k", pretrain_img_size=384, out_indices=(1, 2, 3), dilation=False,
@@ -131,7 +140,8 @@ def main():
         ms = gpu_ms(step, args.steps, args.warmup)
         rec = {"tool": "swin_time", "what": "backbone_fwd_bwd", "route": route, "backbone": "swin_L_384_22k", "frames": FRAMES,
                "img": IMG, "checkpoint": True, "drop_path_rate": 0.2, "gpu_event_ms_per_step": round(ms, 3),
-               "steps": args.steps, "warmup": args.warmup, "autocast": "bf16" if args.autocast else None}
+               "steps": args.steps, "warmup": args.warmup, "autocast": "bf16" if args.autocast else None,
+               "glue": route.endswith("_glue")}
         if not args.no_counts:
             rec.update(kernels_per_step=count_kernels(step), host_syncs_per_step=count_syncs(step),
                        max_memory_allocated_mb=round(peak_mb(step), 1))
@@ -165,6 +175,7 @@ def main():
                 emit(args, rec)
     os.environ.pop("MSDA_SWIN_FUSED", None)
     os.environ.pop("MSDA_SWIN_BF16", None)
+    os.environ.pop("MSDA_SWIN_GLUE", None)
 
 
 if __name__ == "__main__":

@@ -122,6 +122,25 @@ SIGNATURES = {
     "msda_swin_attn_backward_f32": "i iiiiiii ppppp U ppppp U p",
     "msda_swin_attn_forward_bf16": "i iiiiiii ppppp U p",
     "msda_swin_attn_backward_bf16": "i iiiiiii ppppp U ppppp U p",
+    # the Swin blocks' residual / drop-path / LayerNorm glue and PatchMerging's gather + norm
+    "msda_swin_glue_supported": "i i",
+    "msda_swin_glue_workspace_bytes": "U l i",
+    "msda_swin_glue_norm_forward_f32": "i ppp l i f ppp p",
+    "msda_swin_glue_norm_forward_bf16": "i ppp l i f ppp p",
+    "msda_swin_glue_norm_backward_f32": "i ppppp l i pppp U p",
+    "msda_swin_glue_norm_backward_bf16": "i ppppp l i pppp U p",
+    "msda_swin_glue_add_norm_forward_f32": "i ppp ll i pp f pppp p",
+    "msda_swin_glue_add_norm_forward_bf16": "i ppp ll i pp f pppp p",
+    "msda_swin_glue_add_norm_backward_f32": "i ppppppp ll i ppppp U p",
+    "msda_swin_glue_add_norm_backward_bf16": "i ppppppp ll i ppppp U p",
+    "msda_swin_glue_add_forward_f32": "i ppp ll i p p",
+    "msda_swin_glue_add_forward_bf16": "i ppp ll i p p",
+    "msda_swin_glue_add_backward_f32": "i pp ll i p p",
+    "msda_swin_glue_add_backward_bf16": "i pp ll i p p",
+    "msda_swin_glue_merge_norm_forward_f32": "i p iiii pp f ppp p",
+    "msda_swin_glue_merge_norm_forward_bf16": "i p iiii pp f ppp p",
+    "msda_swin_glue_merge_norm_backward_f32": "i ppppp iiii pppp U p",
+    "msda_swin_glue_merge_norm_backward_bf16": "i ppppp iiii pppp U p",
     # MANO hand layer
     "msda_mano_supported": "i iii",
     "msda_mano_workspace_bytes": "U iiii p",
@@ -1554,6 +1573,194 @@ def swin_attn_backward(geo, qkv, bias, table, out, lse, grad_out):
             out.data_ptr(), lse.data_ptr(), lse.numel() * 4, grad_out.data_ptr(), gq.data_ptr(), gt.data_ptr(), _vp(gb),
             ws.data_ptr(), ws.numel() * 4)
     return gq, gt, gb
+
+
+# ---- the Swin blocks' residual / drop-path / LayerNorm glue, PatchMerging's gather + norm (msda_swin_glue.hip) -----------------
+SWIN_GLUE_MAX_WIDTH = 3072
+
+
+def swin_glue_supported(C):
+    """msda_swin_glue_supported: C % 4 == 0 and 0 < C <= 3072."""
+    return bool((_lib or load()).msda_swin_glue_supported(int(C)))
+
+
+def swin_glue_workspace_bytes(rows, C):
+    """msda_swin_glue_workspace_bytes: the backward's partial column sums, min(1024, max(1, ceil(rows / 16))) * 2 * C * 4."""
+    return int((_lib or load()).msda_swin_glue_workspace_bytes(int(rows), int(C)))
+
+
+def _glue_suffix(what, dtype):
+    if dtype == torch.float32:
+        return "f32"
+    if dtype == torch.bfloat16:
+        return "bf16"
+    raise RuntimeError("%s: the branch / output type is float32 or bfloat16, got %s" % (what, dtype))
+
+
+def _glue_check(what, dev, f32, typed=(), dtype=torch.float32):
+    """Every tensor of `f32` contiguous fp32 on dev, every tensor of `typed` contiguous `dtype` there (None entries skipped)."""
+    _check_f32(what, dev, f32)
+    if not all(t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.device == dev) for t in typed):
+        raise RuntimeError("%s: expected contiguous %s CUDA tensors on the rows' device" % (what, dtype))
+
+
+def _glue_rows(what, x, others=()):
+    """(rows, C) of x [..., C]; every tensor of `others` has x's shape."""
+    if x.dim() < 1 or any(t is not None and t.shape != x.shape for t in others):
+        raise RuntimeError("%s: expected tensors of one shape [..., C]" % what)
+    C = x.shape[-1]
+    return (x.numel() // C if C else 0), C
+
+
+def _glue_keep(what, keep, rows, rows_per_sample):
+    rows_per_sample = int(rows_per_sample)
+    if keep is not None and (rows_per_sample <= 0 or keep.numel() * rows_per_sample < rows):
+        raise RuntimeError("%s: keep holds %d samples of %d rows, the tensor has %d rows"
+                           % (what, keep.numel(), rows_per_sample, rows))
+    return rows_per_sample if keep is not None else max(1, rows)
+
+
+def _glue_params(what, C, *params):
+    if any(tuple(p.shape) != (C,) for p in params):
+        raise RuntimeError("%s: expected LayerNorm parameters of shape [%d]" % (what, C))
+
+
+def _glue_workspace(rows, C, dev):
+    nbytes = max(16, swin_glue_workspace_bytes(rows, C))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
+def swin_glue_norm_forward(x, weight, bias, eps, out_dtype):
+    """msda_swin_glue_norm_forward_*: (z of out_dtype, mean, rstd) = LayerNorm over the last dimension of fp32 x.  One launch."""
+    what = "swin_glue_norm_forward"
+    suf = _glue_suffix(what, out_dtype)
+    _glue_check(what, x.device, [x, weight, bias])
+    rows, C = _glue_rows(what, x)
+    _glue_params(what, C, weight, bias)
+    z = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _launch(x.device, "msda_swin_glue_norm_forward_" + suf, what, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), rows, C,
+            float(eps), z.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    return z, mean, rstd
+
+
+def swin_glue_norm_backward(grad_z, x, weight, mean, rstd):
+    """msda_swin_glue_norm_backward_* by grad_z's dtype: (grad_x fp32, grad_weight, grad_bias).  Two launches."""
+    what = "swin_glue_norm_backward"
+    suf = _glue_suffix(what, grad_z.dtype)
+    _glue_check(what, x.device, [x, weight, mean, rstd], [grad_z], grad_z.dtype)
+    rows, C = _glue_rows(what, x, [grad_z])
+    _glue_params(what, C, weight)
+    gx = torch.empty_like(x)
+    gw, gb = torch.empty_like(weight), torch.empty_like(weight)
+    ws, nbytes = _glue_workspace(rows, C, x.device)
+    _launch(x.device, "msda_swin_glue_norm_backward_" + suf, what, grad_z.data_ptr(), x.data_ptr(), weight.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), rows, C, gx.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), nbytes)
+    return gx, gw, gb
+
+
+def swin_glue_add_norm_forward(x, a, keep, rows_per_sample, weight, bias, eps):
+    """msda_swin_glue_add_norm_forward_* by a's dtype T: (y fp32 = x + rnd_T(a * keep[row // rows_per_sample]), z = LN(y) as T,
+    mean, rstd); keep [samples] of T or None.  One launch."""
+    what = "swin_glue_add_norm_forward"
+    suf = _glue_suffix(what, a.dtype)
+    _glue_check(what, x.device, [x, weight, bias], [a, keep], a.dtype)
+    rows, C = _glue_rows(what, x, [a])
+    _glue_params(what, C, weight, bias)
+    rps = _glue_keep(what, keep, rows, rows_per_sample)
+    y = torch.empty_like(x)
+    z = torch.empty_like(a)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _launch(x.device, "msda_swin_glue_add_norm_forward_" + suf, what, x.data_ptr(), a.data_ptr(), _vp(keep), rows, rps, C,
+            weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    return y, z, mean, rstd
+
+
+def swin_glue_add_norm_backward(grad_y, grad_z, y, keep, rows_per_sample, weight, mean, rstd):
+    """msda_swin_glue_add_norm_backward_* by grad_z's dtype T: (grad_x fp32 = grad_y + LN'(grad_z), grad_a of T = rnd_T(rnd_T(
+    grad_x) * keep), grad_weight, grad_bias).  For fp32 without keep grad_a IS grad_x (the same tensor).  Two launches."""
+    what = "swin_glue_add_norm_backward"
+    suf = _glue_suffix(what, grad_z.dtype)
+    _glue_check(what, y.device, [grad_y, y, weight, mean, rstd], [grad_z, keep], grad_z.dtype)
+    rows, C = _glue_rows(what, y, [grad_y, grad_z])
+    _glue_params(what, C, weight)
+    rps = _glue_keep(what, keep, rows, rows_per_sample)
+    gx = torch.empty_like(y)
+    ga = gx if (suf == "f32" and keep is None) else torch.empty_like(grad_z)
+    gw, gb = torch.empty_like(weight), torch.empty_like(weight)
+    ws, nbytes = _glue_workspace(rows, C, y.device)
+    _launch(y.device, "msda_swin_glue_add_norm_backward_" + suf, what, grad_y.data_ptr(), grad_z.data_ptr(), y.data_ptr(),
+            _vp(keep), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, rps, C, gx.data_ptr(),
+            ga.data_ptr() if ga is not gx else None, gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), nbytes)
+    return gx, ga, gw, gb
+
+
+def swin_glue_add_forward(x, a, keep, rows_per_sample):
+    """msda_swin_glue_add_forward_* by a's dtype T: y fp32 = x + rnd_T(a * keep[row // rows_per_sample]).  One launch."""
+    what = "swin_glue_add_forward"
+    suf = _glue_suffix(what, a.dtype)
+    _glue_check(what, x.device, [x], [a, keep], a.dtype)
+    rows, C = _glue_rows(what, x, [a])
+    rps = _glue_keep(what, keep, rows, rows_per_sample)
+    y = torch.empty_like(x)
+    _launch(x.device, "msda_swin_glue_add_forward_" + suf, what, x.data_ptr(), a.data_ptr(), _vp(keep), rows, rps, C, y.data_ptr())
+    return y
+
+
+def swin_glue_add_backward(grad_y, keep, rows_per_sample, dtype):
+    """msda_swin_glue_add_backward_*: grad_a of `dtype` T = rnd_T(rnd_T(grad_y) * keep).  One launch; fp32 without keep: grad_y
+    itself, no launch."""
+    what = "swin_glue_add_backward"
+    suf = _glue_suffix(what, dtype)
+    if suf == "f32" and keep is None:
+        return grad_y
+    _glue_check(what, grad_y.device, [grad_y], [keep], dtype)
+    rows, C = _glue_rows(what, grad_y)
+    rps = _glue_keep(what, keep, rows, rows_per_sample)
+    ga = torch.empty(grad_y.shape, dtype=dtype, device=grad_y.device)
+    _launch(grad_y.device, "msda_swin_glue_add_backward_" + suf, what, grad_y.data_ptr(), _vp(keep), rows, rps, C, ga.data_ptr())
+    return ga
+
+
+def _glue_merge_dims(what, x, weight):
+    if x.dim() != 4 or tuple(weight.shape) != (4 * x.shape[3],):
+        raise RuntimeError("%s: expected x [B, H, W, C] and LayerNorm parameters [4C]" % what)
+    B, H, W, C = x.shape
+    return B, H, W, C, (H + 1) // 2 * ((W + 1) // 2)
+
+
+def swin_glue_merge_norm_forward(x, weight, bias, eps, out_dtype):
+    """msda_swin_glue_merge_norm_forward_*: x [B, H, W, C] fp32 -> (z [B, ceil(H/2) ceil(W/2), 4C] of out_dtype, mean, rstd):
+    PatchMerging's pad, 2 x 2 gather, concatenation and LayerNorm.  One launch."""
+    what = "swin_glue_merge_norm_forward"
+    suf = _glue_suffix(what, out_dtype)
+    _glue_check(what, x.device, [x, weight, bias])
+    B, H, W, C, L2 = _glue_merge_dims(what, x, weight)
+    _glue_params(what, 4 * C, bias)
+    z = torch.empty((B, L2, 4 * C), dtype=out_dtype, device=x.device)
+    mean = torch.empty((B * L2,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((B * L2,), dtype=torch.float32, device=x.device)
+    _launch(x.device, "msda_swin_glue_merge_norm_forward_" + suf, what, x.data_ptr(), B, H, W, C, weight.data_ptr(),
+            bias.data_ptr(), float(eps), z.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    return z, mean, rstd
+
+
+def swin_glue_merge_norm_backward(grad_z, x, weight, mean, rstd):
+    """msda_swin_glue_merge_norm_backward_* by grad_z's dtype: (grad_x [B, H, W, C] fp32, grad_weight, grad_bias).  Two launches."""
+    what = "swin_glue_merge_norm_backward"
+    suf = _glue_suffix(what, grad_z.dtype)
+    _glue_check(what, x.device, [x, weight, mean, rstd], [grad_z], grad_z.dtype)
+    B, H, W, C, L2 = _glue_merge_dims(what, x, weight)
+    if tuple(grad_z.shape) != (B, L2, 4 * C):
+        raise RuntimeError("%s: expected grad_z [B, ceil(H/2) ceil(W/2), 4C]" % what)
+    gx = torch.empty_like(x)
+    gw, gb = torch.empty_like(weight), torch.empty_like(weight)
+    ws, nbytes = _glue_workspace(B * L2, 4 * C, x.device)
+    _launch(x.device, "msda_swin_glue_merge_norm_backward_" + suf, what, grad_z.data_ptr(), x.data_ptr(), weight.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), B, H, W, C, gx.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), nbytes)
+    return gx, gw, gb
 
 
 # ---- MANO hand layer: grouped lbs (msda_mano.hip) -----------------------------------------------------------------------------

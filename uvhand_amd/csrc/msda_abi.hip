@@ -1268,4 +1268,76 @@ int msda_swin_attn_backward_bf16(int B, int H, int W, int C, int nH, int ws, int
                                     grad_table, grad_qkv_bias, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// ---- the Swin blocks' glue (msda_swin_glue.hip): every check is the launcher's, before its first launch ----
+int msda_swin_glue_supported(int C) { return msda::swin_glue_supported(C) ? 1 : 0; }
+
+unsigned long long msda_swin_glue_workspace_bytes(long long rows, int C) { return msda::swin_glue_workspace_bytes(rows, C); }
+
+#define MSDA_SWIN_GLUE_ENTRIES(T, SUF, BF)                                                                                       \
+    int msda_swin_glue_norm_forward_##SUF(const float *x, const float *gamma, const float *beta, long long rows, int C,          \
+                                          float eps, T *z, float *mean, float *rstd, msda_stream_t stream)                      \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_norm_forward(BF, x, gamma, beta, rows, C, eps, z, mean, rstd, (hipStream_t)stream);               \
+    }                                                                                                                            \
+    int msda_swin_glue_norm_backward_##SUF(const T *grad_z, const float *x, const float *gamma, const float *mean,               \
+                                           const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma,          \
+                                           float *grad_beta, void *workspace, unsigned long long workspace_bytes,               \
+                                           msda_stream_t stream)                                                                \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_norm_backward(BF, grad_z, x, gamma, mean, rstd, rows, C, grad_x, grad_gamma, grad_beta,           \
+                                             workspace, workspace_bytes, (hipStream_t)stream);                                  \
+    }                                                                                                                            \
+    int msda_swin_glue_add_norm_forward_##SUF(const float *x, const T *a, const T *keep, long long rows,                         \
+                                              long long rows_per_sample, int C, const float *gamma, const float *beta,          \
+                                              float eps, float *y, T *z, float *mean, float *rstd, msda_stream_t stream)        \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_norm_forward(BF, x, a, keep, rows, rows_per_sample, C, gamma, beta, eps, y, z, mean, rstd,    \
+                                                (hipStream_t)stream);                                                           \
+    }                                                                                                                            \
+    int msda_swin_glue_add_norm_backward_##SUF(const float *grad_y, const T *grad_z, const float *y, const T *keep,              \
+                                               const float *gamma, const float *mean, const float *rstd, long long rows,        \
+                                               long long rows_per_sample, int C, float *grad_x, T *grad_a, float *grad_gamma,   \
+                                               float *grad_beta, void *workspace, unsigned long long workspace_bytes,           \
+                                               msda_stream_t stream)                                                            \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_norm_backward(BF, grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C,       \
+                                                 grad_x, grad_a, grad_gamma, grad_beta, workspace, workspace_bytes,             \
+                                                 (hipStream_t)stream);                                                          \
+    }                                                                                                                            \
+    int msda_swin_glue_add_forward_##SUF(const float *x, const T *a, const T *keep, long long rows, long long rows_per_sample,   \
+                                         int C, float *y, msda_stream_t stream)                                                 \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_forward(BF, x, a, keep, rows, rows_per_sample, C, y, (hipStream_t)stream);                    \
+    }                                                                                                                            \
+    int msda_swin_glue_add_backward_##SUF(const float *grad_y, const T *keep, long long rows, long long rows_per_sample, int C,  \
+                                          T *grad_a, msda_stream_t stream)                                                      \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_backward(BF, grad_y, keep, rows, rows_per_sample, C, grad_a, (hipStream_t)stream);            \
+    }                                                                                                                            \
+    int msda_swin_glue_merge_norm_forward_##SUF(const float *x, int B, int H, int W, int C, const float *gamma,                  \
+                                                const float *beta, float eps, T *z, float *mean, float *rstd,                   \
+                                                msda_stream_t stream)                                                           \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_merge_norm_forward(BF, x, B, H, W, C, gamma, beta, eps, z, mean, rstd, (hipStream_t)stream);      \
+    }                                                                                                                            \
+    int msda_swin_glue_merge_norm_backward_##SUF(const T *grad_z, const float *x, const float *gamma, const float *mean,         \
+                                                 const float *rstd, int B, int H, int W, int C, float *grad_x,                  \
+                                                 float *grad_gamma, float *grad_beta, void *workspace,                          \
+                                                 unsigned long long workspace_bytes, msda_stream_t stream)                      \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_merge_norm_backward(BF, grad_z, x, gamma, mean, rstd, B, H, W, C, grad_x, grad_gamma, grad_beta,  \
+                                                   workspace, workspace_bytes, (hipStream_t)stream);                            \
+    }
+MSDA_SWIN_GLUE_ENTRIES(float, f32, false)
+MSDA_SWIN_GLUE_ENTRIES(uint16_t, bf16, true)
+#undef MSDA_SWIN_GLUE_ENTRIES
+
 }  // extern "C"

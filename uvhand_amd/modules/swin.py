@@ -10,7 +10,11 @@ HIP launch, ``functions/swin_func.py``) -> proj on the real rows: no pad, roll, 
 tensor, and the Linears skip the padded rows (a padded token's qkv is exactly qkv.bias).  ``BasicLayer`` then passes its blocks
 ``OWN_SHIFT_MASK`` instead of the mask tensor and builds the reference's mask only when a block takes the composition (CPU,
 autocast, other dtypes, head_dim != 32, attention dropout in training, a qk_scale override, ``MSDA_SWIN_FUSED=0``).  A block
-handed a mask tensor of its caller's takes the composition with that mask.  The MLP, LayerNorms and GEMMs stay on torch."""
+handed a mask tensor of its caller's takes the composition with that mask.  The MLP, LayerNorms and GEMMs stay on torch.
+
+``MSDA_SWIN_GLUE=1`` (opt-in, read at call time, default off; ``functions/swin_glue_func.py``) moves the memory-bound glue of
+such a block to HIP as well: norm1, shortcut + drop_path with norm2 in one launch, and the closing x + drop_path; PatchMerging's
+pad / gather / concatenation / norm in one launch; the per-stage output norms.  The drop-path tensor stays torch's own draw."""
 import math
 from typing import List
 
@@ -21,6 +25,8 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
 from ..functions.swin_func import fused_route, shift_mask, window_attention, window_partition, window_reverse
+from ..functions.swin_glue_func import (add_norm_rows, add_rows, affine_layernorm, draw_keep, glue_route, merge_norm,
+                                        norm_rows)
 from .detr import NestedTensor
 
 __all__ = ["Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
@@ -194,6 +200,8 @@ class SwinTransformerBlock(nn.Module):
         H, W = self.H, self.W
         assert L == H * W, "input feature has wrong size"
         own_mask = mask_matrix is OWN_SHIFT_MASK
+        if own_mask and self.fused_for(x) and self.glue_for(x):
+            return self._forward_glue(x)
         if own_mask and self.fused_for(x):
             shortcut = x
             x = self.norm1(x)
@@ -207,6 +215,29 @@ class SwinTransformerBlock(nn.Module):
         x = shortcut + self.drop_path(x)
         x = x + self.drop_path(self.mlp(self.norm2(x)))
         return x
+
+    def glue_for(self, x):
+        """True when this block's norms, residual adds and drop-path products take the HIP glue for input x (MSDA_SWIN_GLUE=1)."""
+        C = x.shape[-1]
+        return (glue_route(x.device, x.dtype, C) and affine_layernorm(self.norm1, C, x.device)
+                and affine_layernorm(self.norm2, C, x.device) and isinstance(self.drop_path, (DropPath, nn.Identity)))
+
+    def _keep(self, branch):
+        """drop_path's per-sample tensor for this branch, drawn where and as ``self.drop_path(branch)`` draws it (None: identity)."""
+        dp = self.drop_path
+        if not isinstance(dp, DropPath):
+            return None
+        return draw_keep(branch, dp.drop_prob, dp.training, dp.scale_by_keep)
+
+    def _forward_glue(self, x):
+        """The fused branch of forward with the glue on HIP: norm -> attention -> add + norm -> MLP -> add."""
+        B, L, C = x.shape
+        geometry = (B, self.H, self.W, C, self.num_heads, self.window_size, self.shift_size)
+        z = norm_rows(x, self.norm1)
+        branch = self.attn.attend_rows(z.reshape(B * L, C), geometry).view(B, L, C)
+        x, z = add_norm_rows(x, branch, self._keep(branch), self.norm2)
+        branch = self.mlp(z)
+        return add_rows(x, branch, self._keep(branch))
 
     def _attention_composition(self, x, mask_matrix):
         """models/swin_transformer.py:209-243: norm1, pad, roll, partition, W-MSA / SW-MSA, reverse, roll back, crop."""
@@ -251,6 +282,8 @@ class PatchMerging(nn.Module):
     def forward(self, x, H, W):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
+        if glue_route(x.device, x.dtype, 4 * C) and affine_layernorm(self.norm, 4 * C, x.device):
+            return self.reduction(merge_norm(x, H, W, self.norm))
         x = x.view(B, H, W, C)
         pad_input = (H % 2 == 1) or (W % 2 == 1)
         if pad_input:
@@ -449,7 +482,7 @@ class SwinTransformer(nn.Module):
             x_out, H, W, x, Wh, Ww = layer(x, Wh, Ww)
             if i in self.out_indices:
                 norm_layer = getattr(self, f'norm{i}')
-                x_out = norm_layer(x_out)
+                x_out = norm_rows(x_out, norm_layer, fp32_out=True)      # (norm_layer(x_out) unless MSDA_SWIN_GLUE=1)
                 out = x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous()
                 outs.append(out)
         return tuple(outs)

@@ -137,22 +137,7 @@ struct EvArgs {
     int B, J, NV, Lp, Lg, Lparts;   // rows of pred object.v.cam, gt object.v.cam and part_ids per frame
 };
 
-// fixed-order tree reduction of N values per thread; the sums end in red[k][0]
-template <int N>
-__device__ __forceinline__ void block_reduce(float (*red)[kBlock], const float (&v)[N])
-{
-    const int tid = threadIdx.x;
-    for (int k = 0; k < N; ++k) red[k][tid] = v[k];
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if (tid < w)
-            for (int k = 0; k < N; ++k) red[k][tid] += red[k][tid + w];
-        __syncthreads();
-    }
-}
-
 __device__ __forceinline__ bool invalid_long(float v) { return (long long)(1.f - v) != 0; }   // (1 - v).long() != 0
-__device__ __forceinline__ float sq(float x) { return x * x; }
 
 // nanmean of two values (torch_utils.nanmean over dim 1 of a [B, 2] stack): 0 / 0 = NaN when both are NaN
 __device__ __forceinline__ float nanmean2(float a, float b)

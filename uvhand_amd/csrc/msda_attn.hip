@@ -8,21 +8,15 @@
 // each at 300 rows (two workgroups per pair re-load the pair's operands and measured 8 % slower: MSDA_ATTN_HALVES);
 // the pair's other operand(s) sit in LDS row-major ([rows][36 floats]: 16-byte aligned rows, the 16 lanes of a ds_read_b128 on
 // different bank groups).  Every product runs on v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate: the arithmetic of an fmaf
-// chain), and the score tile never changes layout between the two products it takes part in:
-//   * forward and dQ work on S^T tiles (rows = keys, columns = queries).  The accumulator of a 16 x 16 tile gives lane
-//     (c = lane & 15, r = lane >> 4) the entries [4r .. 4r+3][c]; the following product sums over KEYS, and a sum does not care
-//     in which order its terms arrive: MFMA step v of a tile takes "k index r" to mean key 4r + v, so the B operand is the
-//     accumulator register v as it stands and the A operand is row 4r + v of V (or K) in LDS.  No transposition through LDS,
-//     no shuffles.
-//   * dK / dV work on S tiles (rows = queries, columns = keys) and sum over QUERIES the same way.
-//   * the head dimension is relabelled likewise (step (half, v): k index r = channel 16 half + 4r + v), so the operand whose
-//     row index is the lane's column reads four steps with one ds_read_b128 / one float4 global load.
+// chain), and the score tile never changes layout between the two products it takes part in (msda_attn_tile.h: the fragment
+// helpers and the relabelling that makes it so).
 // Softmax statistics: the forward keeps log-sum-exp per (pair, query); the backward recomputes the probabilities from it.
 // Dropout: keep(seed, pair, query, key) is a 32-bit integer hash (at_hash) compared with p * 2^32 — recomputed in the backward, no mask
 // tensor; the seed is READ FROM DEVICE MEMORY (the caller draws it with torch's generator: reproducible under manual_seed,
 // safe under HIP-graph capture).  This is the kernel's own random stream, not nn.functional.dropout's.
 #include <math.h>
 
+#include "msda_attn_tile.h"
 #include "msda_common.h"
 #include "msda_launch.h"
 
@@ -31,8 +25,7 @@ namespace msda {
 #ifndef MSDA_AT_WAVES
 #define MSDA_AT_WAVES 12
 #endif
-constexpr int kAtRow = 36, kAtWaves = MSDA_AT_WAVES, kAtBlock = kAtWaves * 64, kAtMaxTiles = 20, kAtMaxLen = 16 * kAtMaxTiles;
-using at_f4 = __attribute__((ext_vector_type(4))) float;
+constexpr int kAtWaves = MSDA_AT_WAVES, kAtBlock = kAtWaves * 64, kAtMaxTiles = 20, kAtMaxLen = 16 * kAtMaxTiles;
 
 struct AtView { float *p; long long sn, sl; };          // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
 
@@ -52,9 +45,6 @@ __device__ __forceinline__ unsigned at_hash(unsigned counter)
     return x;
 }
 
-__device__ __forceinline__ float4 at_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 at_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
 // rows [0, L) of two [L][32] slices (row strides sl0 / sl1) -> dst0 / dst1 [Lp][kAtRow]; rows [L, Lp) zero.  Lp * 8 float4 per
 // slice on 640 threads: at most four rounds (Lp <= 320); all the loads of a thread are issued before its first LDS store.
 __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, long long sl0, float *dst1, const float *src1,
@@ -66,8 +56,8 @@ __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, lo
     for (int k = 0; k < R; ++k) {
         const int i = threadIdx.x + k * kAtBlock, row = i >> 3, c = (i & 7) * 4;
         const bool live = row < L;
-        v0[k] = live ? at_ld4(src0 + (long long)row * sl0 + c) : at_zero4();
-        v1[k] = live ? at_ld4(src1 + (long long)row * sl1 + c) : at_zero4();
+        v0[k] = live ? ld4(src0 + (long long)row * sl0 + c) : at_zero4();
+        v1[k] = live ? ld4(src1 + (long long)row * sl1 + c) : at_zero4();
     }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -77,54 +67,6 @@ __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, lo
             *reinterpret_cast<float4 *>(dst1 + row * kAtRow + c) = v1[k];
         }
     }
-}
-
-#define AT_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-// acc += A-rows(tile) . breg over the 32 channels: `arow` = LDS row of this lane's A row (channels 4r.. of each half at +0, +16)
-__device__ __forceinline__ at_f4 at_dot32(const float *arow, const float4 &b0, const float4 &b1)
-{
-    const float4 a0 = at_ld4(arow), a1 = at_ld4(arow + 16);
-    at_f4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = AT_MFMA(a0.x, b0.x, acc); acc = AT_MFMA(a0.y, b0.y, acc); acc = AT_MFMA(a0.z, b0.z, acc); acc = AT_MFMA(a0.w, b0.w, acc);
-    acc = AT_MFMA(a1.x, b1.x, acc); acc = AT_MFMA(a1.y, b1.y, acc); acc = AT_MFMA(a1.z, b1.z, acc); acc = AT_MFMA(a1.w, b1.w, acc);
-    return acc;                                      // (one chain: the sum's association is the channel order)
-}
-
-// the same for this tile and the next one (16 rows further), the two accumulators' chains interleaved
-__device__ __forceinline__ void at_dot32x2(const float *arow, const float4 &b0, const float4 &b1, at_f4 &acc0, at_f4 &acc1)
-{
-    const float4 a0 = at_ld4(arow), a1 = at_ld4(arow + 16), c0 = at_ld4(arow + 16 * kAtRow), c1 = at_ld4(arow + 16 * kAtRow + 16);
-    at_f4 x = {0.f, 0.f, 0.f, 0.f}, y = x;
-    x = AT_MFMA(a0.x, b0.x, x); y = AT_MFMA(c0.x, b0.x, y); x = AT_MFMA(a0.y, b0.y, x); y = AT_MFMA(c0.y, b0.y, y);
-    x = AT_MFMA(a0.z, b0.z, x); y = AT_MFMA(c0.z, b0.z, y); x = AT_MFMA(a0.w, b0.w, x); y = AT_MFMA(c0.w, b0.w, y);
-    x = AT_MFMA(a1.x, b1.x, x); y = AT_MFMA(c1.x, b1.x, y); x = AT_MFMA(a1.y, b1.y, x); y = AT_MFMA(c1.y, b1.y, y);
-    x = AT_MFMA(a1.z, b1.z, x); y = AT_MFMA(c1.z, b1.z, y); x = AT_MFMA(a1.w, b1.w, x); y = AT_MFMA(c1.w, b1.w, y);
-    acc0 = x; acc1 = y;
-}
-
-// o[half] += X^T-rows . w over the tile's 16 rows: X = LDS tile base (row 16t), w = accumulator-layout weights of this lane
-__device__ __forceinline__ void at_accum_t(const float *xt, int r, int c, const at_f4 &w, at_f4 &o0, at_f4 &o1)
-{
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const float *row = xt + (4 * r + v) * kAtRow + c;
-        o0 = AT_MFMA(row[0], w[v], o0);
-        o1 = AT_MFMA(row[16], w[v], o1);
-    }
-}
-
-__device__ __forceinline__ float at_rsum(float x)               // over the four lanes c, c + 16, c + 32, c + 48
-{
-    x += __shfl_xor(x, 16);
-    x += __shfl_xor(x, 32);
-    return x;
-}
-__device__ __forceinline__ float at_rmax(float x)
-{
-    x = fmaxf(x, __shfl_xor(x, 16));
-    x = fmaxf(x, __shfl_xor(x, 32));
-    return x;
 }
 
 struct AtArgs {
@@ -153,7 +95,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AtArgs a)
         const int qi = tq * 16 + c;
         const bool qok = qi < a.Lq;
         float4 q0 = at_zero4(), q1 = at_zero4();
-        if (qok) { q0 = at_ld4(qp + (long long)qi * a.q.sl + 4 * r); q1 = at_ld4(qp + (long long)qi * a.q.sl + 16 + 4 * r); }
+        if (qok) { q0 = ld4(qp + (long long)qi * a.q.sl + 4 * r); q1 = ld4(qp + (long long)qi * a.q.sl + 16 + 4 * r); }
         q0.x *= a.scale2; q0.y *= a.scale2; q0.z *= a.scale2; q0.w *= a.scale2;
         q1.x *= a.scale2; q1.y *= a.scale2; q1.z *= a.scale2; q1.w *= a.scale2;
         // S^T tiles: s[t][v] = score (times log2 e) of key 16 t + 4 r + v for query qi
@@ -225,7 +167,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
             const float *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl, *grow = Gs + qi * kAtRow;
 #pragma unroll
             for (int k4 = 0; k4 < 8; ++k4) {
-                const float4 ov = at_ld4(orow + 4 * k4), gv = at_ld4(grow + 4 * k4);
+                const float4 ov = ld4(orow + 4 * k4), gv = ld4(grow + 4 * k4);
                 d += ov.x * gv.x + ov.y * gv.y + ov.z * gv.z + ov.w * gv.w;
             }
         }
@@ -242,7 +184,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
         if (kok) {
             const float *kr = a.k.p + n * a.k.sn + h * 32 + (long long)key * a.k.sl + 4 * r;
             const float *vr = a.v.p + n * a.v.sn + h * 32 + (long long)key * a.v.sl + 4 * r;
-            k0 = at_ld4(kr); k1 = at_ld4(kr + 16); v0 = at_ld4(vr); v1 = at_ld4(vr + 16);
+            k0 = ld4(kr); k1 = ld4(kr + 16); v0 = ld4(vr); v1 = ld4(vr + 16);
         }
         k0.x *= a.scale2; k0.y *= a.scale2; k0.z *= a.scale2; k0.w *= a.scale2;
         k1.x *= a.scale2; k1.y *= a.scale2; k1.z *= a.scale2; k1.w *= a.scale2;
@@ -257,7 +199,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
             const at_f4 s_next = at_dot32(Qs + (16 * tn + c) * kAtRow + 4 * r, k0, k1);
             const at_f4 dp_next = at_dot32(Gs + (16 * tn + c) * kAtRow + 4 * r, v0, v1);
             __builtin_amdgcn_sched_barrier(0);
-            const float4 ls = at_ld4(lse_s + 16 * t + 4 * r), dl = at_ld4(del_s + 16 * t + 4 * r);
+            const float4 ls = ld4(lse_s + 16 * t + 4 * r), dl = ld4(del_s + 16 * t + 4 * r);
             const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
             at_f4 pd, ds;
 #pragma unroll
@@ -303,7 +245,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_kernel(const AtArgs a)
             const float *qr = a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 4 * r;
             const float *gr = a.go.p + n * a.go.sn + h * 32 + (long long)qi * a.go.sl + 4 * r;
             const float *orw = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
-            q0 = at_ld4(qr); q1 = at_ld4(qr + 16); g0 = at_ld4(gr); g1 = at_ld4(gr + 16); o0 = at_ld4(orw); o1 = at_ld4(orw + 16);
+            q0 = ld4(qr); q1 = ld4(qr + 16); g0 = ld4(gr); g1 = ld4(gr + 16); o0 = ld4(orw); o1 = ld4(orw + 16);
             lse = a.lse[(long long)pair * a.Lq + qi] * 1.4426950408889634f;
         }
         q0.x *= a.scale2; q0.y *= a.scale2; q0.z *= a.scale2; q0.w *= a.scale2;
@@ -361,21 +303,9 @@ static bool at_view_ok(const AtView &v)
 // ds_read_b128 as the operand of the products over channels, and transposed (4 keys / queries of one channel) with
 // ds_read_b64_tr_b16 as the operand of the products over keys / queries.  Every kernel keeps its loops wave-uniform: the
 // transposed read needs all 64 lanes active.  LDS <= 2 * 320 * 80 B + 2 * 320 * 4 B = 53.8 KB: no opt-in.
-//
-// Relabelling.  A bf16 operand holds 8 consecutive k per lane (k = 8 (lane >> 4) + j), an accumulator 4 rows per lane (4 (lane >> 4)
-// + v).  The score tiles come in pairs b = 0, 1 covering 32 keys (or queries) 32T .. 32T + 31, and tile b's row i is taken to
-// be key 32T + 8 (i >> 2) + 4b + (i & 3): the row operand of the first product is read for that key, so the accumulators of the
-// pair give lane (c, r) keys 32T + 8r + j in natural order (j = 4b + v) — exactly the 8 k of the next product's operand.
+// The row and transposed reads and the relabelling of the score-tile pairs: msda_attn_tile.h.
 // Padding: rows up to a multiple of 32 are zero in LDS; padding keys get -inf scores / zero probabilities, padding queries
 // an lse of +inf.  The dropout hash takes the real (query, key) indices: the mask is the fp32 kernels' bit for bit.
-constexpr int kAbRow = 40;
-using at_bf8 = __attribute__((ext_vector_type(8))) __bf16;
-using at_bf4 = __attribute__((ext_vector_type(4))) __bf16;
-typedef __attribute__((address_space(3))) at_bf4 at_lds_bf4;
-
-__device__ __forceinline__ at_bf8 ab_ld8(const uint16_t *p) { return *reinterpret_cast<const at_bf8 *>(p); }
-__device__ __forceinline__ at_bf8 ab_zero8() { return at_bf8{}; }
-__device__ __forceinline__ float ab_f(__bf16 x) { return (float)x; }
 
 // rows [0, L) of two [L][32] bf16 slices -> dst0 / dst1 [Lp][kAbRow]; rows [L, Lp) zero (Lp * 4 16-byte chunks per slice)
 __device__ __forceinline__ void ab_load_rows2(uint16_t *dst0, const uint16_t *src0, long long sl0, uint16_t *dst1,
@@ -398,38 +328,6 @@ __device__ __forceinline__ void ab_load_rows2(uint16_t *dst0, const uint16_t *sr
             *reinterpret_cast<at_bf8 *>(dst1 + row * kAbRow + c) = v1[k];
         }
     }
-}
-
-#define AB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-// the score-tile pair T: acc[b] = rows(X) . bop over the 32 channels, X = LDS slice, rows relabelled as above
-__device__ __forceinline__ void ab_pair(const uint16_t *xs, int T, int r, int c, const at_bf8 &bop, at_f4 &acc0, at_f4 &acc1)
-{
-    const uint16_t *row = xs + (32 * T + 8 * (c >> 2) + (c & 3)) * kAbRow + 8 * r;
-    const at_bf8 a0 = ab_ld8(row), a1 = ab_ld8(row + 4 * kAbRow);
-    const at_f4 z = {0.f, 0.f, 0.f, 0.f};
-    acc0 = AB_MFMA(a0, bop, z);
-    acc1 = AB_MFMA(a1, bop, z);
-}
-
-// the transposed operand: lane (c, r) gets X[32T + 8r + j][16 half + c], j = 0..7 (X = LDS slice, rows = keys / queries)
-__device__ __forceinline__ at_bf8 ab_tr(const uint16_t *xs, int T, int half, int r, int c)
-{
-    const uint16_t *p = xs + (32 * T + 8 * r + (c >> 2)) * kAbRow + 16 * half + 4 * (c & 3);
-    const at_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((at_lds_bf4 *)p);
-    const at_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((at_lds_bf4 *)(p + 4 * kAbRow));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ at_bf8 ab_pack(const at_f4 &x0, const at_f4 &x1)
-{
-    return at_bf8{(__bf16)x0[0], (__bf16)x0[1], (__bf16)x0[2], (__bf16)x0[3], (__bf16)x1[0], (__bf16)x1[1], (__bf16)x1[2], (__bf16)x1[3]};
-}
-
-// 4 accumulator values (scaled) -> 4 bf16 at p (8 bytes)
-__device__ __forceinline__ void ab_st4(uint16_t *p, const at_f4 &x, float s)
-{
-    *reinterpret_cast<at_bf4 *>(p) = at_bf4{(__bf16)(x[0] * s), (__bf16)(x[1] * s), (__bf16)(x[2] * s), (__bf16)(x[3] * s)};
 }
 
 struct AbView { uint16_t *p; long long sn, sl; };
@@ -500,8 +398,8 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_bf16_kernel(const AbArgs 
                     s[2 * T + (j >> 2)][j & 3] = keep ? s[2 * T + (j >> 2)][j & 3] * inv : 0.f;
                 }
                 const at_bf8 pb = ab_pack(s[2 * T], s[2 * T + 1]);          // P^T[key 32T + 8r + j][query qi]
-                o0 = AB_MFMA(ab_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
-                o1 = AB_MFMA(ab_tr(Vs, T, 1, r, c), pb, o1);
+                o0 = ab_mfma(ab_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
+                o1 = ab_mfma(ab_tr(Vs, T, 1, r, c), pb, o1);
             }
         }
         if (qok) {
@@ -569,10 +467,10 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_bf16_kernel(const AbAr
                 ds[b][v] = p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - dlv[j]);
             }
             const at_bf8 pb = ab_pack(pd[0], pd[1]), sb = ab_pack(ds[0], ds[1]);
-            dv0 = AB_MFMA(ab_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P_drop
-            dv1 = AB_MFMA(ab_tr(Gs, T, 1, r, c), pb, dv1);
-            dk0 = AB_MFMA(ab_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
-            dk1 = AB_MFMA(ab_tr(Qs, T, 1, r, c), sb, dk1);
+            dv0 = ab_mfma(ab_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P_drop
+            dv1 = ab_mfma(ab_tr(Gs, T, 1, r, c), pb, dv1);
+            dk0 = ab_mfma(ab_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
+            dk1 = ab_mfma(ab_tr(Qs, T, 1, r, c), sb, dk1);
         }
         if (kok) {
             uint16_t *gvr = a.gv.p + n * a.gv.sn + h * 32 + (long long)key * a.gv.sl + 4 * r;
@@ -627,8 +525,8 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_bf16_kernel(const AbArg
                 ds[b][v] = p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - delta);
             }
             const at_bf8 sb = ab_pack(ds[0], ds[1]);
-            dq0 = AB_MFMA(ab_tr(Ks, T, 0, r, c), sb, dq0);                  // dQ^T[channel][query] += K^T . dS^T
-            dq1 = AB_MFMA(ab_tr(Ks, T, 1, r, c), sb, dq1);
+            dq0 = ab_mfma(ab_tr(Ks, T, 0, r, c), sb, dq0);                  // dQ^T[channel][query] += K^T . dS^T
+            dq1 = ab_mfma(ab_tr(Ks, T, 1, r, c), sb, dq1);
         }
         if (qok) {
             uint16_t *gq = a.gq.p + n * a.gq.sn + h * 32 + (long long)qi * a.gq.sl + 4 * r;

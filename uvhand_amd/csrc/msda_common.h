@@ -68,4 +68,30 @@ __device__ __forceinline__ F wave_sum(F x)
     return x;
 }
 
+// Fixed-order tree reduction of K values per thread of a workgroup of BS threads (red: [K][BS] in LDS); the sums end in
+// red[k][0].  K and BS are deduced from the arguments.
+template <int K, int BS>
+__device__ __forceinline__ void block_reduce(float (*red)[BS], const float (&v)[K])
+{
+    const int tid = threadIdx.x;
+    for (int k = 0; k < K; ++k) red[k][tid] = v[k];
+    __syncthreads();
+    for (int w = BS / 2; w > 0; w >>= 1) {
+        if (tid < w)
+            for (int k = 0; k < K; ++k) red[k][tid] += red[k][tid + w];
+        __syncthreads();
+    }
+}
+
+// Four consecutive values of a 16-byte aligned fp32 row, or of an 8-byte aligned bf16 row widened exactly.
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 ld4(const uint16_t *p)
+{
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+}
+
+__device__ __forceinline__ float sq(float x) { return x * x; }
+
 }  // namespace msda

@@ -120,7 +120,6 @@ __device__ __forceinline__ PointEntry point_entry(float x, float y, float a, int
 {
     return entry_of(point_geom<float>(x, y, H, Wd), a, Wd, level_ok);
 }
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 // Storage type of the value-like tensors (value, out, grad_out, grad_value): float, or bfloat16
 // bits (uint16_t) with all arithmetic and accumulation in fp32 and ONE rounding at the final store.

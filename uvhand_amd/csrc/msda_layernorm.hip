@@ -25,14 +25,8 @@ constexpr int kLnBlock = 256;                     // 4 wavefronts = 4 rows in fl
 constexpr int kLnWaves = kLnBlock / kWave;
 constexpr int kLnMaxVec = 4;                      // float4 per lane: d <= 1024
 
-__device__ __forceinline__ float4 ld_f4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-// residual rows: fp32, or bf16 widened exactly (msda_add_layernorm_*_f32_bf16res: the bf16 output of a projection under autocast)
-__device__ __forceinline__ float4 ld_f4(const uint16_t *p)
-{
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                       __uint_as_float(u.y & 0xffff0000u));
-}
+// residual rows: fp32, or bf16 widened exactly by ld4 (msda_add_layernorm_*_f32_bf16res: the bf16 output of a projection under
+// autocast)
 
 template <int NV, typename R>
 __global__ __launch_bounds__(kLnBlock) void add_layernorm_fwd_kernel(
@@ -52,8 +46,8 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_fwd_kernel(
         const int c = (k * kWave + lane) * 4;
         v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < d) {
-            v[k] = ld_f4(xr + c);
-            if (rr) { const float4 t = ld_f4(rr + c); v[k].x += t.x; v[k].y += t.y; v[k].z += t.z; v[k].w += t.w; }
+            v[k] = ld4(xr + c);
+            if (rr) { const float4 t = ld4(rr + c); v[k].x += t.x; v[k].y += t.y; v[k].z += t.z; v[k].w += t.w; }
             sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
         }
     }
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_fwd_kernel(
     for (int k = 0; k < NV; ++k) {
         const int c = (k * kWave + lane) * 4;
         if (c < d) {
-            const float4 g = ld_f4(gamma + c), b = ld_f4(beta + c);
+            const float4 g = ld4(gamma + c), b = ld4(beta + c);
             float4 o;
             o.x = (v[k].x - mean) * rstd * g.x + b.x; o.y = (v[k].y - mean) * rstd * g.y + b.y;
             o.z = (v[k].z - mean) * rstd * g.z + b.z; o.w = (v[k].w - mean) * rstd * g.w + b.w;
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_bwd_kernel(
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int c = (k * kWave + lane) * 4;
-        gm[k] = c < d ? ld_f4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        gm[k] = c < d ? ld4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         dg[k] = db[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (long long row = r0 + wave; row < r1; row += kLnWaves) {
@@ -113,9 +107,9 @@ __global__ __launch_bounds__(kLnBlock) void add_layernorm_bwd_kernel(
             const int c = (k * kWave + lane) * 4;
             xh[k] = g[k] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (c < d) {
-                float4 v = ld_f4(xr + c);
-                if (rr) { const float4 t = ld_f4(rr + c); v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
-                const float4 o = ld_f4(gr + c);
+                float4 v = ld4(xr + c);
+                if (rr) { const float4 t = ld4(rr + c); v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
+                const float4 o = ld4(gr + c);
                 xh[k] = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
                 g[k] = make_float4(o.x * gm[k].x, o.y * gm[k].y, o.z * gm[k].z, o.w * gm[k].w);
                 s1 += (g[k].x + g[k].y) + (g[k].z + g[k].w);

@@ -297,6 +297,7 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using i16x4 = __attribute__((ext_vector_type(4))) short;
 using i16x8 = __attribute__((ext_vector_type(8))) short;
 
+// (not msda_attn_tile.h's ab_tr: one bare read at a byte address of the blocked layout above, not the [rows][40] relabelling)
 __device__ __forceinline__ i16x4 lds_read_tr16(const unsigned char *p)
 {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((i16x4 __attribute__((address_space(3))) *)p);

@@ -60,20 +60,6 @@ struct SMArgs {
     float *err, *cds, *cdn, *wt, *coef;
 };
 
-// fixed-order tree reduction of n values per thread of a workgroup of BS threads (red: [n][BS] in LDS); the sums end in red[k][0]
-template <int K, int BS>
-__device__ __forceinline__ void block_reduce(float (*red)[BS], const float (&v)[K])
-{
-    const int tid = threadIdx.x;
-    for (int k = 0; k < K; ++k) red[k][tid] = v[k];
-    __syncthreads();
-    for (int w = BS / 2; w > 0; w >>= 1) {
-        if (tid < w)
-            for (int k = 0; k < K; ++k) red[k][tid] += red[k][tid + w];
-        __syncthreads();
-    }
-}
-
 // body 0 = r, 1 = l, 2 = o: vertices, rows per frame and the per-frame roots of the prediction (which = 0) or the gt (1)
 struct Body {
     const float *v, *root;          // root: a hand's joints (row 0 of a frame), null for the object

@@ -11,7 +11,7 @@
 // reference's relative_position_index) + (-100 where the shift regions 3 r(Y) + r(X) of query and key differ, s > 0).
 //
 // A workgroup owns one (image, window, head) pair and has one wavefront per 16-token tile of the window.  The products run on
-// v_mfma_f32_16x16x4_f32 with the conventions of msda_attn.hip (S^T tiles in the forward and dQ, S tiles in dK / dV, operands
+// v_mfma_f32_16x16x4_f32 with the helpers and conventions of msda_attn_tile.h (S^T tiles in the forward and dQ, S tiles in dK / dV, operands
 // in LDS as [rows][36]).
 //   forward   one launch: out for real queries, the log-sum-exp (natural log) of every real query, lse [pairs][N].
 //   backward  three launches.  kv: a wavefront owns 16 keys and walks the query tiles: dK, dV of real keys into grad_qkv, and
@@ -24,6 +24,7 @@
 // No atomics, fixed summation order: bitwise reproducible.  No allocation, no host synchronisation.
 #include <math.h>
 
+#include "msda_attn_tile.h"
 #include "msda_common.h"
 #include "msda_launch.h"
 
@@ -31,41 +32,12 @@ namespace msda {
 
 namespace {
 
-constexpr int kSwRow = 36, kSwMaxWs = 12, kSwMaxN = kSwMaxWs * kSwMaxWs, kSwMaxTiles = (kSwMaxN + 15) / 16;
+constexpr int kSwMaxWs = 12, kSwMaxN = kSwMaxWs * kSwMaxWs, kSwMaxTiles = (kSwMaxN + 15) / 16;
 constexpr int kSwMaxBlock = kSwMaxTiles * 64, kSwRedBlock = 256;
 constexpr float kLog2e = 1.4426950408889634f;
-using sw_f4 = __attribute__((ext_vector_type(4))) float;
 
-#define SW_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ float4 sw_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 sw_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void sw_st4(float *p, const sw_f4 &v) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void sw_st4(float *p, const at_f4 &v) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 __device__ __forceinline__ float4 sw_scale4(float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
-
-// acc = A-rows(tile) . b over the 32 channels (A row = this lane's LDS row, channel 4r.. at +0 and +16): one chain
-__device__ __forceinline__ sw_f4 sw_dot32(const float *arow, const float4 &b0, const float4 &b1)
-{
-    const float4 a0 = sw_ld4(arow), a1 = sw_ld4(arow + 16);
-    sw_f4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = SW_MFMA(a0.x, b0.x, acc); acc = SW_MFMA(a0.y, b0.y, acc); acc = SW_MFMA(a0.z, b0.z, acc); acc = SW_MFMA(a0.w, b0.w, acc);
-    acc = SW_MFMA(a1.x, b1.x, acc); acc = SW_MFMA(a1.y, b1.y, acc); acc = SW_MFMA(a1.z, b1.z, acc); acc = SW_MFMA(a1.w, b1.w, acc);
-    return acc;
-}
-
-// o[half] += X^T-rows . w over the tile's 16 rows (X = LDS tile base, w = accumulator-layout weights of this lane)
-__device__ __forceinline__ void sw_accum_t(const float *xt, int r, int c, const sw_f4 &w, sw_f4 &o0, sw_f4 &o1)
-{
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const float *row = xt + (4 * r + v) * kSwRow + c;
-        o0 = SW_MFMA(row[0], w[v], o0);
-        o1 = SW_MFMA(row[16], w[v], o1);
-    }
-}
-
-__device__ __forceinline__ float sw_rsum(float x) { x += __shfl_xor(x, 16); return x + __shfl_xor(x, 32); }
-__device__ __forceinline__ float sw_rmax(float x) { x = fmaxf(x, __shfl_xor(x, 16)); return fmaxf(x, __shfl_xor(x, 32)); }
 
 struct SwArgs {
     int B, H, W, C, nH, ws, s, Hp, Wp, nWx, nW, N, E;
@@ -97,8 +69,8 @@ __device__ __forceinline__ SwTok sw_token(const SwArgs &a, int b, int w, int t, 
 // the k (part 1) or v (part 2) channels c4 .. c4 + 3 of token `row` (padded: the bias's, or zero), head h
 __device__ __forceinline__ float4 sw_kv4(const SwArgs &a, int row, int part, int h, int c4)
 {
-    if (row >= 0) return sw_ld4(a.qkv + (long long)row * 3 * a.C + part * a.C + h * 32 + c4);
-    return a.bias != nullptr ? sw_ld4(a.bias + part * a.C + h * 32 + c4) : sw_zero4();
+    if (row >= 0) return ld4(a.qkv + (long long)row * 3 * a.C + part * a.C + h * 32 + c4);
+    return a.bias != nullptr ? ld4(a.bias + part * a.C + h * 32 + c4) : at_zero4();
 }
 
 __device__ __forceinline__ void sw_pair(const SwArgs &a, int &b, int &w, int &h)
@@ -109,7 +81,7 @@ __device__ __forceinline__ void sw_pair(const SwArgs &a, int &b, int &w, int &h)
     b = pair / (a.nH * a.nW);
 }
 
-// LDS: rows [Np][kSwRow] of k and v (part 1, 2) or q (scaled) and dO; the head's table slice; per token info (int)
+// LDS: rows [Np][kAtRow] of k and v (part 1, 2) or q (scaled) and dO; the head's table slice; per token info (int)
 __device__ __forceinline__ void sw_load_table(const SwArgs &a, int h, float *tbl)
 {
     for (int e = threadIdx.x; e < a.E; e += blockDim.x) tbl[e] = a.table[(long long)e * a.nH + h];
@@ -127,7 +99,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_kernel(const SwArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const int Np = (a.N + 15) & ~15, Ep = (a.E + 3) & ~3;
-    float *Ks = sw_smem, *Vs = Ks + Np * kSwRow, *tbl = Vs + Np * kSwRow;
+    float *Ks = sw_smem, *Vs = Ks + Np * kAtRow, *tbl = Vs + Np * kAtRow;
     int *kinf = reinterpret_cast<int *>(tbl + Ep), *rows = kinf + Np;
     int b, w, h;
     sw_pair(a, b, w, h);
@@ -140,14 +112,14 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_kernel(const SwArgs a)
     sw_load_table(a, h, tbl);
     for (int i = threadIdx.x; i < Np * 8; i += blockDim.x) {
         const int t = i >> 3, c4 = (i & 7) * 4;
-        float4 kv = sw_zero4(), vv = sw_zero4();
+        float4 kv = at_zero4(), vv = at_zero4();
         if (t < a.N) {
             const int row = sw_token(a, b, w, t, true).row;
             kv = sw_kv4(a, row, 1, h, c4);
             vv = sw_kv4(a, row, 2, h, c4);
         }
-        *reinterpret_cast<float4 *>(Ks + t * kSwRow + c4) = kv;
-        *reinterpret_cast<float4 *>(Vs + t * kSwRow + c4) = vv;
+        *reinterpret_cast<float4 *>(Ks + t * kAtRow + c4) = kv;
+        *reinterpret_cast<float4 *>(Vs + t * kAtRow + c4) = vv;
     }
     __syncthreads();
     const int ntk = Np >> 4, tq = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
@@ -155,18 +127,18 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_kernel(const SwArgs a)
     const int qrow = qi < a.N ? rows[qi] : -1;
     if (!__any(qrow >= 0)) return;                                      // a tile of padded tokens only: nothing to write
     const SwTok qt = sw_token(a, b, w, qi < a.N ? qi : 0, false);
-    float4 q0 = sw_zero4(), q1 = sw_zero4();
+    float4 q0 = at_zero4(), q1 = at_zero4();
     if (qrow >= 0) {
         const float *qp = a.qkv + (long long)qrow * 3 * a.C + h * 32 + 4 * r;
-        q0 = sw_scale4(sw_ld4(qp), a.scale);
-        q1 = sw_scale4(sw_ld4(qp + 16), a.scale);
+        q0 = sw_scale4(ld4(qp), a.scale);
+        q1 = sw_scale4(ld4(qp + 16), a.scale);
     }
-    sw_f4 s[kSwMaxTiles];
+    at_f4 s[kSwMaxTiles];
     float m = -INFINITY;
 #pragma unroll
     for (int t = 0; t < kSwMaxTiles; ++t) {
         if (t < ntk) {
-            s[t] = sw_dot32(Ks + (16 * t + c) * kSwRow + 4 * r, q0, q1);
+            s[t] = at_dot32(Ks + (16 * t + c) * kAtRow + 4 * r, q0, q1);
             const int4 ki = *reinterpret_cast<const int4 *>(kinf + 16 * t + 4 * r);
             const int kv[4] = {ki.x, ki.y, ki.z, ki.w};
 #pragma unroll
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_kernel(const SwArgs a)
             }
         }
     }
-    m = sw_rmax(m);
+    m = at_rmax(m);
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < kSwMaxTiles; ++t) {
@@ -185,17 +157,17 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_kernel(const SwArgs a)
             for (int v = 0; v < 4; ++v) { s[t][v] = __builtin_amdgcn_exp2f(s[t][v] - m); sum += s[t][v]; }
         }
     }
-    sum = sw_rsum(sum);
+    sum = at_rsum(sum);
     const long long pair = blockIdx.x;
     if (qrow >= 0 && r == 0) a.lse[pair * a.N + qi] = (m + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f;
     const float inv = 1.f / sum;
-    sw_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+    at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
 #pragma unroll
     for (int t = 0; t < kSwMaxTiles; ++t) {
         if (t < ntk) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) s[t][v] *= inv;
-            sw_accum_t(Vs + 16 * t * kSwRow, r, c, s[t], o0, o1);
+            at_accum_t(Vs + 16 * t * kAtRow, r, c, s[t], o0, o1);
         }
     }
     if (qrow >= 0) {
@@ -210,7 +182,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_kernel(const SwArgs a
 {
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const int Np = (a.N + 15) & ~15, Ep = (a.E + 3) & ~3, ntq = Np >> 4;
-    float *Qs = sw_smem, *Gs = Qs + Np * kSwRow, *tbl = Gs + Np * kSwRow, *lse_s = tbl + Ep, *del_s = lse_s + Np;
+    float *Qs = sw_smem, *Gs = Qs + Np * kAtRow, *tbl = Gs + Np * kAtRow, *lse_s = tbl + Ep, *del_s = lse_s + Np;
     float *part = del_s + Np;                                           // [waves][64]
     int *qinf = reinterpret_cast<int *>(part + ntq * 64), *rows = qinf + Np, *tany = rows + Np;
     int b, w, h;
@@ -226,23 +198,23 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_kernel(const SwArgs a
     for (int i = threadIdx.x; i < Np * 8; i += blockDim.x) {
         const int t = i >> 3, c4 = (i & 7) * 4;
         const int row = t < a.N ? sw_token(a, b, w, t, false).row : -1;
-        float4 qv = sw_zero4(), gv = sw_zero4();
+        float4 qv = at_zero4(), gv = at_zero4();
         if (row >= 0) {
-            qv = sw_scale4(sw_ld4(a.qkv + (long long)row * 3 * a.C + h * 32 + c4), a.scale);
-            gv = sw_ld4(a.gout + (long long)row * a.C + h * 32 + c4);
+            qv = sw_scale4(ld4(a.qkv + (long long)row * 3 * a.C + h * 32 + c4), a.scale);
+            gv = ld4(a.gout + (long long)row * a.C + h * 32 + c4);
         }
-        *reinterpret_cast<float4 *>(Qs + t * kSwRow + c4) = qv;
-        *reinterpret_cast<float4 *>(Gs + t * kSwRow + c4) = gv;
+        *reinterpret_cast<float4 *>(Qs + t * kAtRow + c4) = qv;
+        *reinterpret_cast<float4 *>(Gs + t * kAtRow + c4) = gv;
     }
     __syncthreads();
     for (int t = threadIdx.x; t < Np; t += blockDim.x) {
         const int row = rows[t];
         float d = 0.f;
         if (row >= 0) {
-            const float *orow = a.o + (long long)row * a.C + h * 32, *grow = Gs + t * kSwRow;
+            const float *orow = a.o + (long long)row * a.C + h * 32, *grow = Gs + t * kAtRow;
 #pragma unroll
             for (int k4 = 0; k4 < 8; ++k4) {
-                const float4 ov = sw_ld4(orow + 4 * k4), gv = sw_ld4(grow + 4 * k4);
+                const float4 ov = ld4(orow + 4 * k4), gv = ld4(grow + 4 * k4);
                 d += ov.x * gv.x + ov.y * gv.y + ov.z * gv.z + ov.w * gv.w;
             }
         }
@@ -260,22 +232,22 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_kernel(const SwArgs a
     const bool kok = key < a.N;
     const SwTok kt = sw_token(a, b, w, kok ? key : 0, true);
     const int krow = kok ? kt.row : -1;
-    float4 k0 = sw_zero4(), k1 = sw_zero4(), v0 = sw_zero4(), v1 = sw_zero4();
+    float4 k0 = at_zero4(), k1 = at_zero4(), v0 = at_zero4(), v1 = at_zero4();
     if (kok) {
         k0 = sw_kv4(a, krow, 1, h, 4 * r); k1 = sw_kv4(a, krow, 1, h, 16 + 4 * r);
         v0 = sw_kv4(a, krow, 2, h, 4 * r); v1 = sw_kv4(a, krow, 2, h, 16 + 4 * r);
     }
-    sw_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+    at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
 #pragma unroll 1
     for (int t = 0; t < ntq; ++t) {
         if (!tany[t]) continue;
-        const sw_f4 s = sw_dot32(Qs + (16 * t + c) * kSwRow + 4 * r, k0, k1);
-        const sw_f4 dp = sw_dot32(Gs + (16 * t + c) * kSwRow + 4 * r, v0, v1);
-        const float4 ls = sw_ld4(lse_s + 16 * t + 4 * r), dl = sw_ld4(del_s + 16 * t + 4 * r);
+        const at_f4 s = at_dot32(Qs + (16 * t + c) * kAtRow + 4 * r, k0, k1);
+        const at_f4 dp = at_dot32(Gs + (16 * t + c) * kAtRow + 4 * r, v0, v1);
+        const float4 ls = ld4(lse_s + 16 * t + 4 * r), dl = ld4(del_s + 16 * t + 4 * r);
         const int4 qi4 = *reinterpret_cast<const int4 *>(qinf + 16 * t + 4 * r);
         const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
         const int qv[4] = {qi4.x, qi4.y, qi4.z, qi4.w};
-        sw_f4 pd, ds;
+        at_f4 pd, ds;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             // (query info and key info swap roles: the table index is the sum of the two parts either way)
@@ -284,8 +256,8 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_kernel(const SwArgs a
             pd[v] = p;
             ds[v] = p * (dp[v] - dlv[v]);
         }
-        sw_accum_t(Gs + 16 * t * kSwRow, r, c, pd, dv0, dv1);           // dV^T[channel][key] += dO^T . P
-        sw_accum_t(Qs + 16 * t * kSwRow, r, c, ds, dk0, dk1);           // dK^T[channel][key] += (q scale)^T . dS
+        at_accum_t(Gs + 16 * t * kAtRow, r, c, pd, dv0, dv1);           // dV^T[channel][key] += dO^T . P
+        at_accum_t(Qs + 16 * t * kAtRow, r, c, ds, dk0, dk1);           // dK^T[channel][key] += (q scale)^T . dS
     }
     if (krow >= 0) {
         float *gk = a.gqkv + (long long)krow * 3 * a.C + a.C + h * 32 + 4 * r, *gv = gk + a.C;
@@ -328,7 +300,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_kernel(const SwArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const int Np = (a.N + 15) & ~15, Ep = (a.E + 3) & ~3, ntk = Np >> 4, dss = Np + 4;
-    float *Ks = sw_smem, *Vs = Ks + Np * kSwRow, *tbl = Vs + Np * kSwRow, *dS = tbl + Ep;
+    float *Ks = sw_smem, *Vs = Ks + Np * kAtRow, *tbl = Vs + Np * kAtRow, *dS = tbl + Ep;
     int *kinf = reinterpret_cast<int *>(dS + Np * dss), *rows = kinf + Np;
     int b, w, h;
     sw_pair(a, b, w, h);
@@ -342,14 +314,14 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_kernel(const SwArgs a)
     sw_load_table(a, h, tbl);
     for (int i = threadIdx.x; i < Np * 8; i += blockDim.x) {
         const int t = i >> 3, c4 = (i & 7) * 4;
-        float4 kv = sw_zero4(), vv = sw_zero4();
+        float4 kv = at_zero4(), vv = at_zero4();
         if (t < a.N) {
             const int row = sw_token(a, b, w, t, true).row;
             kv = sw_kv4(a, row, 1, h, c4);
             vv = sw_kv4(a, row, 2, h, c4);
         }
-        *reinterpret_cast<float4 *>(Ks + t * kSwRow + c4) = kv;
-        *reinterpret_cast<float4 *>(Vs + t * kSwRow + c4) = vv;
+        *reinterpret_cast<float4 *>(Ks + t * kAtRow + c4) = kv;
+        *reinterpret_cast<float4 *>(Vs + t * kAtRow + c4) = vv;
     }
     __syncthreads();
     const int tq = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
@@ -358,32 +330,32 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_kernel(const SwArgs a)
     float *dsrow = dS + qi * dss;
     if (__any(qrow >= 0)) {
         const SwTok qt = sw_token(a, b, w, qi < a.N ? qi : 0, false);
-        float4 q0 = sw_zero4(), q1 = sw_zero4(), g0 = sw_zero4(), g1 = sw_zero4(), o0 = sw_zero4(), o1 = sw_zero4();
+        float4 q0 = at_zero4(), q1 = at_zero4(), g0 = at_zero4(), g1 = at_zero4(), o0 = at_zero4(), o1 = at_zero4();
         float lse = INFINITY;
         if (qrow >= 0) {
             const float *qp = a.qkv + (long long)qrow * 3 * a.C + h * 32 + 4 * r;
             const float *gp = a.gout + (long long)qrow * a.C + h * 32 + 4 * r, *opp = a.o + (long long)qrow * a.C + h * 32 + 4 * r;
-            q0 = sw_scale4(sw_ld4(qp), a.scale); q1 = sw_scale4(sw_ld4(qp + 16), a.scale);
-            g0 = sw_ld4(gp); g1 = sw_ld4(gp + 16); o0 = sw_ld4(opp); o1 = sw_ld4(opp + 16);
+            q0 = sw_scale4(ld4(qp), a.scale); q1 = sw_scale4(ld4(qp + 16), a.scale);
+            g0 = ld4(gp); g1 = ld4(gp + 16); o0 = ld4(opp); o1 = ld4(opp + 16);
             lse = a.lse[pair * a.N + qi] * kLog2e;
         }
-        const float delta = sw_rsum(g0.x * o0.x + g0.y * o0.y + g0.z * o0.z + g0.w * o0.w + g1.x * o1.x + g1.y * o1.y + g1.z * o1.z +
+        const float delta = at_rsum(g0.x * o0.x + g0.y * o0.y + g0.z * o0.z + g0.w * o0.w + g1.x * o1.x + g1.y * o1.y + g1.z * o1.z +
                                     g1.w * o1.w);
-        sw_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+        at_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
 #pragma unroll 1
         for (int t = 0; t < ntk; ++t) {
-            const sw_f4 s = sw_dot32(Ks + (16 * t + c) * kSwRow + 4 * r, q0, q1);
-            const sw_f4 dp = sw_dot32(Vs + (16 * t + c) * kSwRow + 4 * r, g0, g1);
+            const at_f4 s = at_dot32(Ks + (16 * t + c) * kAtRow + 4 * r, q0, q1);
+            const at_f4 dp = at_dot32(Vs + (16 * t + c) * kAtRow + 4 * r, g0, g1);
             const int4 ki = *reinterpret_cast<const int4 *>(kinf + 16 * t + 4 * r);
             const int kv[4] = {ki.x, ki.y, ki.z, ki.w};
-            sw_f4 ds;
+            at_f4 ds;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const float sc = sw_score2(s[v], tbl, qt.rel, qt.reg, kv[v], 16 * t + 4 * r + v < a.N);
                 const float p = __builtin_amdgcn_exp2f(sc - lse);
                 ds[v] = p * (dp[v] - delta);
             }
-            sw_accum_t(Ks + 16 * t * kSwRow, r, c, ds, dq0, dq1);       // dQ^T[channel][query] += K^T . dS^T
+            at_accum_t(Ks + 16 * t * kAtRow, r, c, ds, dq0, dq1);       // dQ^T[channel][query] += K^T . dS^T
             sw_st4(dsrow + 16 * t + 4 * r, ds);
         }
         if (qrow >= 0) {
@@ -393,7 +365,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_kernel(const SwArgs a)
             sw_st4(gq + 16, dq1);
         }
     } else {
-        for (int t = 0; t < ntk; ++t) sw_st4(dsrow + 16 * t + 4 * r, sw_f4{0.f, 0.f, 0.f, 0.f});
+        for (int t = 0; t < ntk; ++t) sw_st4(dsrow + 16 * t + 4 * r, at_f4{0.f, 0.f, 0.f, 0.f});
     }
     __syncthreads();
     // table entry e = (dy + ws - 1) (2 ws - 1) + dx + ws - 1: the queries (yi, xi) whose key (yi - dy, xi - dx) lies in the
@@ -446,16 +418,16 @@ __global__ __launch_bounds__(kSwRedBlock) void swin_bwd_reduce_kernel(const SwAr
 
 int serr(const char *msg) { return set_error(MSDA_ERR_ARGUMENT, msg); }
 
-size_t sw_lds_fwd(int N, int E) { const int Np = (N + 15) & ~15; return (size_t)(2 * Np * kSwRow + ((E + 3) & ~3) + 2 * Np) * 4; }
+size_t sw_lds_fwd(int N, int E) { const int Np = (N + 15) & ~15; return (size_t)(2 * Np * kAtRow + ((E + 3) & ~3) + 2 * Np) * 4; }
 size_t sw_lds_kv(int N, int E)
 {
     const int Np = (N + 15) & ~15;
-    return (size_t)(2 * Np * kSwRow + ((E + 3) & ~3) + 2 * Np + (Np >> 4) * 64 + 2 * Np + (Np >> 4)) * 4;
+    return (size_t)(2 * Np * kAtRow + ((E + 3) & ~3) + 2 * Np + (Np >> 4) * 64 + 2 * Np + (Np >> 4)) * 4;
 }
 size_t sw_lds_q(int N, int E)
 {
     const int Np = (N + 15) & ~15;
-    return (size_t)(2 * Np * kSwRow + ((E + 3) & ~3) + Np * (Np + 4) + 2 * Np) * 4;
+    return (size_t)(2 * Np * kAtRow + ((E + 3) & ~3) + Np * (Np + 4) + 2 * Np) * 4;
 }
 
 int sw_allow_lds(const void *fn, size_t bytes)
@@ -469,7 +441,7 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 // ---- bf16 operands (msda_swin_attn_*_bf16) ---------------------------------------------------------------------------------------
 // The same four launches and the same work split with qkv, out, dO and grad_qkv in bf16 and every product on
-// v_mfma_f32_16x16x32_bf16 (fp32 accumulate), following the bf16 block of msda_attn.hip: the pair's operands sit in LDS as bf16
+// v_mfma_f32_16x16x32_bf16 (fp32 accumulate), following the bf16 block of msda_attn_tile.h: the pair's operands sit in LDS as bf16
 // rows [Np][40] (N padded to a multiple of 32, padding rows zero), read as a row (ds_read_b128) for the products over channels and
 // transposed (ds_read_b64_tr_b16) for the products over keys / queries; score tiles come in pairs covering 32 keys (queries), tile
 // b's row i being key 32T + 8 (i >> 2) + 4b + (i & 3), so that the accumulators of a pair are the next product's 8-wide operand.
@@ -477,46 +449,7 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 // pass sums (LDS) and every partial.  bf16: P and dS as MFMA operands only; out and grad_qkv, rounded once.  A padded token's k and
 // v are the bias's parts rounded to bf16 (a bf16 Linear on a zero row).  Every loop around a transposed read is wave-uniform.
 // LDS of the q kernel at ws 12: 2 * 160 * 80 + 532 * 4 + 144 * 164 * 4 + 2 * 160 * 4 = 123472 B (the fp32 one: 130000 B).
-constexpr int kSbRow = 40, kSbMaxPairs = (kSwMaxN + 31) / 32;
-using sb_bf8 = __attribute__((ext_vector_type(8))) __bf16;
-using sb_bf4 = __attribute__((ext_vector_type(4))) __bf16;
-typedef __attribute__((address_space(3))) sb_bf4 sb_lds_bf4;
-
-#define SB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ sb_bf8 sb_ld8(const uint16_t *p) { return *reinterpret_cast<const sb_bf8 *>(p); }
-__device__ __forceinline__ sb_bf8 sb_zero8() { return sb_bf8{}; }
-__device__ __forceinline__ float sb_f(__bf16 x) { return (float)x; }
-
-// the score-tile pair T: acc[b] = rows(X) . bop over the 32 channels, X = LDS slice, rows relabelled as above
-__device__ __forceinline__ void sb_pair(const uint16_t *xs, int T, int r, int c, const sb_bf8 &bop, sw_f4 &acc0, sw_f4 &acc1)
-{
-    const uint16_t *row = xs + (32 * T + 8 * (c >> 2) + (c & 3)) * kSbRow + 8 * r;
-    const sb_bf8 a0 = sb_ld8(row), a1 = sb_ld8(row + 4 * kSbRow);
-    const sw_f4 z = {0.f, 0.f, 0.f, 0.f};
-    acc0 = SB_MFMA(a0, bop, z);
-    acc1 = SB_MFMA(a1, bop, z);
-}
-
-// the transposed operand: lane (c, r) gets X[32T + 8r + j][16 half + c], j = 0..7 (X = LDS slice, rows = keys / queries)
-__device__ __forceinline__ sb_bf8 sb_tr(const uint16_t *xs, int T, int half, int r, int c)
-{
-    const uint16_t *p = xs + (32 * T + 8 * r + (c >> 2)) * kSbRow + 16 * half + 4 * (c & 3);
-    const sb_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sb_lds_bf4 *)p);
-    const sb_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sb_lds_bf4 *)(p + 4 * kSbRow));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ sb_bf8 sb_pack(const sw_f4 &x0, const sw_f4 &x1)
-{
-    return sb_bf8{(__bf16)x0[0], (__bf16)x0[1], (__bf16)x0[2], (__bf16)x0[3], (__bf16)x1[0], (__bf16)x1[1], (__bf16)x1[2], (__bf16)x1[3]};
-}
-
-// 4 accumulator values (scaled) -> 4 bf16 at p (8 bytes)
-__device__ __forceinline__ void sb_st4(uint16_t *p, const sw_f4 &x, float s)
-{
-    *reinterpret_cast<sb_bf4 *>(p) = sb_bf4{(__bf16)(x[0] * s), (__bf16)(x[1] * s), (__bf16)(x[2] * s), (__bf16)(x[3] * s)};
-}
+constexpr int kSbMaxPairs = (kSwMaxN + 31) / 32;
 
 // g: geometry, bias, table, lse, gtable, gbias, pt, pb (its fp32 tensor pointers stay null); the bf16 tensors
 struct SbArgs {
@@ -526,13 +459,13 @@ struct SbArgs {
 };
 
 // the k (part 1) or v (part 2) channels c8 .. c8 + 7 of token `row` (padded: the bias's rounded to bf16, or zero), head h
-__device__ __forceinline__ sb_bf8 sb_kv8(const SbArgs &a, int row, int part, int h, int c8)
+__device__ __forceinline__ at_bf8 sb_kv8(const SbArgs &a, int row, int part, int h, int c8)
 {
-    if (row >= 0) return sb_ld8(a.qkv + (long long)row * 3 * a.g.C + part * a.g.C + h * 32 + c8);
-    if (a.g.bias == nullptr) return sb_zero8();
+    if (row >= 0) return ab_ld8(a.qkv + (long long)row * 3 * a.g.C + part * a.g.C + h * 32 + c8);
+    if (a.g.bias == nullptr) return ab_zero8();
     const float *bp = a.g.bias + part * a.g.C + h * 32 + c8;
-    const float4 b0 = sw_ld4(bp), b1 = sw_ld4(bp + 4);
-    return sb_bf8{(__bf16)b0.x, (__bf16)b0.y, (__bf16)b0.z, (__bf16)b0.w, (__bf16)b1.x, (__bf16)b1.y, (__bf16)b1.z, (__bf16)b1.w};
+    const float4 b0 = ld4(bp), b1 = ld4(bp + 4);
+    return at_bf8{(__bf16)b0.x, (__bf16)b0.y, (__bf16)b0.z, (__bf16)b0.w, (__bf16)b1.x, (__bf16)b1.y, (__bf16)b1.z, (__bf16)b1.w};
 }
 
 // the window's keys: info and qkv row per token, k and v rows into LDS (rows N .. Np - 1 zero)
@@ -546,14 +479,14 @@ __device__ __forceinline__ void sb_fill_kv(const SbArgs &a, int b, int w, int h,
     }
     for (int i = threadIdx.x; i < Np * 4; i += blockDim.x) {
         const int t = i >> 2, c8 = (i & 3) * 8;
-        sb_bf8 kv = sb_zero8(), vv = sb_zero8();
+        at_bf8 kv = ab_zero8(), vv = ab_zero8();
         if (t < a.g.N) {
             const int row = sw_token(a.g, b, w, t, true).row;
             kv = sb_kv8(a, row, 1, h, c8);
             vv = sb_kv8(a, row, 2, h, c8);
         }
-        *reinterpret_cast<sb_bf8 *>(Ks + t * kSbRow + c8) = kv;
-        *reinterpret_cast<sb_bf8 *>(Vs + t * kSbRow + c8) = vv;
+        *reinterpret_cast<at_bf8 *>(Ks + t * kAbRow + c8) = kv;
+        *reinterpret_cast<at_bf8 *>(Vs + t * kAbRow + c8) = vv;
     }
 }
 
@@ -569,8 +502,8 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_bf16_kernel(const SbArgs
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const SwArgs &g = a.g;
     const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5;
-    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kSbRow;
-    float *tbl = reinterpret_cast<float *>(Vs + Np * kSbRow);
+    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kAbRow;
+    float *tbl = reinterpret_cast<float *>(Vs + Np * kAbRow);
     int *kinf = reinterpret_cast<int *>(tbl + Ep), *rows = kinf + Np;
     int b, w, h;
     sw_pair(g, b, w, h);
@@ -582,15 +515,15 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_bf16_kernel(const SbArgs
     const int qrow = qi < g.N ? rows[qi] : -1;
     if (!__any(qrow >= 0)) return;                                      // a tile of padded tokens only: nothing to write
     const SwTok qt = sw_token(g, b, w, qi < g.N ? qi : 0, false);
-    sb_bf8 qf = sb_zero8();
-    if (qrow >= 0) qf = sb_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
+    at_bf8 qf = ab_zero8();
+    if (qrow >= 0) qf = ab_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
     // s[2T + b][v] = score (base 2) of key 32T + 8r + 4b + v for query qi
-    sw_f4 s[2 * kSbMaxPairs];
+    at_f4 s[2 * kSbMaxPairs];
     float m = -INFINITY;
 #pragma unroll
     for (int T = 0; T < kSbMaxPairs; ++T) {
         if (T < npair) {
-            sb_pair(Ks, T, r, c, qf, s[2 * T], s[2 * T + 1]);
+            ab_pair(Ks, T, r, c, qf, s[2 * T], s[2 * T + 1]);
             int kv[8];
             sb_info8(kinf, T, r, kv);
 #pragma unroll
@@ -601,7 +534,7 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_bf16_kernel(const SbArgs
             }
         }
     }
-    m = sw_rmax(m);
+    m = at_rmax(m);
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < 2 * kSbMaxPairs; ++t) {
@@ -610,25 +543,25 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_fwd_bf16_kernel(const SbArgs
             for (int v = 0; v < 4; ++v) { s[t][v] = __builtin_amdgcn_exp2f(s[t][v] - m); sum += s[t][v]; }
         }
     }
-    sum = sw_rsum(sum);
+    sum = at_rsum(sum);
     const long long pair = blockIdx.x;
     if (qrow >= 0 && r == 0) g.lse[pair * g.N + qi] = (m + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f;
     const float inv = 1.f / sum;
-    sw_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+    at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
 #pragma unroll
     for (int T = 0; T < kSbMaxPairs; ++T) {
         if (T < npair) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) { s[2 * T][v] *= inv; s[2 * T + 1][v] *= inv; }
-            const sb_bf8 pb = sb_pack(s[2 * T], s[2 * T + 1]);          // P^T[key 32T + 8r + j][query qi]
-            o0 = SB_MFMA(sb_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
-            o1 = SB_MFMA(sb_tr(Vs, T, 1, r, c), pb, o1);
+            const at_bf8 pb = ab_pack(s[2 * T], s[2 * T + 1]);          // P^T[key 32T + 8r + j][query qi]
+            o0 = ab_mfma(ab_tr(Vs, T, 0, r, c), pb, o0);                // O^T[channel][query] += V^T . P^T
+            o1 = ab_mfma(ab_tr(Vs, T, 1, r, c), pb, o1);
         }
     }
     if (qrow >= 0) {
         uint16_t *op = a.o + (long long)qrow * g.C + h * 32 + 4 * r;
-        sb_st4(op, o0, 1.f);
-        sb_st4(op + 16, o1, 1.f);
+        ab_st4(op, o0, 1.f);
+        ab_st4(op + 16, o1, 1.f);
     }
 }
 
@@ -638,8 +571,8 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_bf16_kernel(const SbA
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const SwArgs &g = a.g;
     const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5, nwave = blockDim.x >> 6;
-    uint16_t *Qs = reinterpret_cast<uint16_t *>(sw_smem), *Gs = Qs + Np * kSbRow;
-    float *tbl = reinterpret_cast<float *>(Gs + Np * kSbRow), *lse_s = tbl + Ep, *del_s = lse_s + Np;
+    uint16_t *Qs = reinterpret_cast<uint16_t *>(sw_smem), *Gs = Qs + Np * kAbRow;
+    float *tbl = reinterpret_cast<float *>(Gs + Np * kAbRow), *lse_s = tbl + Ep, *del_s = lse_s + Np;
     float *part = del_s + Np;                                           // [waves][64]
     int *qinf = reinterpret_cast<int *>(part + nwave * 64), *rows = qinf + Np, *pany = rows + Np;
     int b, w, h;
@@ -655,25 +588,25 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_bf16_kernel(const SbA
     for (int i = threadIdx.x; i < Np * 4; i += blockDim.x) {
         const int t = i >> 2, c8 = (i & 3) * 8;
         const int row = t < g.N ? sw_token(g, b, w, t, false).row : -1;
-        sb_bf8 qv = sb_zero8(), gv = sb_zero8();
+        at_bf8 qv = ab_zero8(), gv = ab_zero8();
         if (row >= 0) {
-            qv = sb_ld8(a.qkv + (long long)row * 3 * g.C + h * 32 + c8);
-            gv = sb_ld8(a.gout + (long long)row * g.C + h * 32 + c8);
+            qv = ab_ld8(a.qkv + (long long)row * 3 * g.C + h * 32 + c8);
+            gv = ab_ld8(a.gout + (long long)row * g.C + h * 32 + c8);
         }
-        *reinterpret_cast<sb_bf8 *>(Qs + t * kSbRow + c8) = qv;
-        *reinterpret_cast<sb_bf8 *>(Gs + t * kSbRow + c8) = gv;
+        *reinterpret_cast<at_bf8 *>(Qs + t * kAbRow + c8) = qv;
+        *reinterpret_cast<at_bf8 *>(Gs + t * kAbRow + c8) = gv;
     }
     __syncthreads();
     for (int t = threadIdx.x; t < Np; t += blockDim.x) {
         const int row = rows[t];
         float d = 0.f;
         if (row >= 0) {
-            const uint16_t *orow = a.out + (long long)row * g.C + h * 32, *grow = Gs + t * kSbRow;
+            const uint16_t *orow = a.out + (long long)row * g.C + h * 32, *grow = Gs + t * kAbRow;
 #pragma unroll
             for (int k8 = 0; k8 < 4; ++k8) {
-                const sb_bf8 ov = sb_ld8(orow + 8 * k8), gv = sb_ld8(grow + 8 * k8);
+                const at_bf8 ov = ab_ld8(orow + 8 * k8), gv = ab_ld8(grow + 8 * k8);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) d += sb_f(ov[j]) * sb_f(gv[j]);
+                for (int j = 0; j < 8; ++j) d += ab_f(ov[j]) * ab_f(gv[j]);
             }
         }
         del_s[t] = d;
@@ -690,26 +623,26 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_bf16_kernel(const SbA
     const bool kok = key < g.N;
     const SwTok kt = sw_token(g, b, w, kok ? key : 0, true);
     const int krow = kok ? kt.row : -1;
-    sb_bf8 kf = sb_zero8(), vf = sb_zero8();
+    at_bf8 kf = ab_zero8(), vf = ab_zero8();
     if (kok) {
         kf = sb_kv8(a, krow, 1, h, 8 * r);
         vf = sb_kv8(a, krow, 2, h, 8 * r);
     }
     const int kinfo = (kt.rel & 0xffff) | (kt.reg << 16);
-    sw_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+    at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
 #pragma unroll 1
     for (int T = 0; T < npair; ++T) {
         if (!pany[T]) continue;                                         // (the same for every lane of the workgroup)
         // S and dP tiles of the pair: entry (b, v) = (query 32T + 8r + 4b + v, key)
-        sw_f4 s[2], dp[2];
-        sb_pair(Qs, T, r, c, kf, s[0], s[1]);
-        sb_pair(Gs, T, r, c, vf, dp[0], dp[1]);
+        at_f4 s[2], dp[2];
+        ab_pair(Qs, T, r, c, kf, s[0], s[1]);
+        ab_pair(Gs, T, r, c, vf, dp[0], dp[1]);
         const float *lq = lse_s + 32 * T + 8 * r, *dq = del_s + 32 * T + 8 * r;
-        const float4 l0 = sw_ld4(lq), l1 = sw_ld4(lq + 4), d0 = sw_ld4(dq), d1 = sw_ld4(dq + 4);
+        const float4 l0 = ld4(lq), l1 = ld4(lq + 4), d0 = ld4(dq), d1 = ld4(dq + 4);
         const float lsv[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w}, dlv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
         int qv[8];
         sb_info8(qinf, T, r, qv);
-        sw_f4 pd[2], ds[2];
+        at_f4 pd[2], ds[2];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int bb = j >> 2, v = j & 3;
@@ -719,18 +652,18 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_kv_bf16_kernel(const SbA
             pd[bb][v] = p;
             ds[bb][v] = p * (dp[bb][v] - dlv[j]);
         }
-        const sb_bf8 pb = sb_pack(pd[0], pd[1]), sb = sb_pack(ds[0], ds[1]);
-        dv0 = SB_MFMA(sb_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P
-        dv1 = SB_MFMA(sb_tr(Gs, T, 1, r, c), pb, dv1);
-        dk0 = SB_MFMA(sb_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
-        dk1 = SB_MFMA(sb_tr(Qs, T, 1, r, c), sb, dk1);
+        const at_bf8 pb = ab_pack(pd[0], pd[1]), sb = ab_pack(ds[0], ds[1]);
+        dv0 = ab_mfma(ab_tr(Gs, T, 0, r, c), pb, dv0);                  // dV^T[channel][key] += dO^T . P
+        dv1 = ab_mfma(ab_tr(Gs, T, 1, r, c), pb, dv1);
+        dk0 = ab_mfma(ab_tr(Qs, T, 0, r, c), sb, dk0);                  // dK^T[channel][key] += Q^T . dS
+        dk1 = ab_mfma(ab_tr(Qs, T, 1, r, c), sb, dk1);
     }
 #pragma unroll
     for (int v = 0; v < 4; ++v) { dk0[v] *= g.scale; dk1[v] *= g.scale; }
     if (krow >= 0) {
         uint16_t *gk = a.gqkv + (long long)krow * 3 * g.C + g.C + h * 32 + 4 * r, *gv = gk + g.C;
-        sb_st4(gk, dk0, 1.f); sb_st4(gk + 16, dk1, 1.f);
-        sb_st4(gv, dv0, 1.f); sb_st4(gv + 16, dv1, 1.f);
+        ab_st4(gk, dk0, 1.f); ab_st4(gk + 16, dk1, 1.f);
+        ab_st4(gv, dv0, 1.f); ab_st4(gv + 16, dv1, 1.f);
     }
     // padded keys of this tile: their k / v gradients summed (a butterfly over the 16 keys), then over the wavefronts in order
     const bool kpad = kok && krow < 0;
@@ -769,8 +702,8 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_bf16_kernel(const SbAr
     extern __shared__ __attribute__((aligned(16))) float sw_smem[];
     const SwArgs &g = a.g;
     const int Np = (g.N + 31) & ~31, Ep = (g.E + 3) & ~3, npair = Np >> 5, dss = Np + 4, nq = (blockDim.x >> 6) * 16;
-    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kSbRow;
-    float *tbl = reinterpret_cast<float *>(Vs + Np * kSbRow), *dS = tbl + Ep;       // dS [nq][dss]
+    uint16_t *Ks = reinterpret_cast<uint16_t *>(sw_smem), *Vs = Ks + Np * kAbRow;
+    float *tbl = reinterpret_cast<float *>(Vs + Np * kAbRow), *dS = tbl + Ep;       // dS [nq][dss]
     int *kinf = reinterpret_cast<int *>(dS + nq * dss), *rows = kinf + Np;
     int b, w, h;
     sw_pair(g, b, w, h);
@@ -784,25 +717,25 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_bf16_kernel(const SbAr
     float *dsrow = dS + qi * dss;
     if (__any(qrow >= 0)) {
         const SwTok qt = sw_token(g, b, w, qi < g.N ? qi : 0, false);
-        sb_bf8 qf = sb_zero8(), gf = sb_zero8(), of = sb_zero8();
+        at_bf8 qf = ab_zero8(), gf = ab_zero8(), of = ab_zero8();
         float lse = INFINITY;
         if (qrow >= 0) {
-            qf = sb_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
-            gf = sb_ld8(a.gout + (long long)qrow * g.C + h * 32 + 8 * r);
-            of = sb_ld8(a.out + (long long)qrow * g.C + h * 32 + 8 * r);
+            qf = ab_ld8(a.qkv + (long long)qrow * 3 * g.C + h * 32 + 8 * r);
+            gf = ab_ld8(a.gout + (long long)qrow * g.C + h * 32 + 8 * r);
+            of = ab_ld8(a.out + (long long)qrow * g.C + h * 32 + 8 * r);
             lse = g.lse[pair * g.N + qi] * kLog2e;
         }
         float d = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) d += sb_f(gf[j]) * sb_f(of[j]);
-        const float delta = sw_rsum(d);
-        sw_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+        for (int j = 0; j < 8; ++j) d += ab_f(gf[j]) * ab_f(of[j]);
+        const float delta = at_rsum(d);
+        at_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
 #pragma unroll 1
         for (int T = 0; T < npair; ++T) {
             // S^T and dP^T tiles of the pair: entry (b, v) = (key 32T + 8r + 4b + v, query qi)
-            sw_f4 s[2], dp[2], ds[2];
-            sb_pair(Ks, T, r, c, qf, s[0], s[1]);
-            sb_pair(Vs, T, r, c, gf, dp[0], dp[1]);
+            at_f4 s[2], dp[2], ds[2];
+            ab_pair(Ks, T, r, c, qf, s[0], s[1]);
+            ab_pair(Vs, T, r, c, gf, dp[0], dp[1]);
             int kv[8];
             sb_info8(kinf, T, r, kv);
 #pragma unroll
@@ -812,21 +745,21 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_bf16_kernel(const SbAr
                 const float p = __builtin_amdgcn_exp2f(sc - lse);
                 ds[bb][v] = p * (dp[bb][v] - delta);
             }
-            const sb_bf8 sb = sb_pack(ds[0], ds[1]);
-            dq0 = SB_MFMA(sb_tr(Ks, T, 0, r, c), sb, dq0);              // dQ^T[channel][query] += K^T . dS^T
-            dq1 = SB_MFMA(sb_tr(Ks, T, 1, r, c), sb, dq1);
+            const at_bf8 sb = ab_pack(ds[0], ds[1]);
+            dq0 = ab_mfma(ab_tr(Ks, T, 0, r, c), sb, dq0);              // dQ^T[channel][query] += K^T . dS^T
+            dq1 = ab_mfma(ab_tr(Ks, T, 1, r, c), sb, dq1);
             sw_st4(dsrow + 32 * T + 8 * r, ds[0]);
             sw_st4(dsrow + 32 * T + 8 * r + 4, ds[1]);
         }
         if (qrow >= 0) {
             uint16_t *gq = a.gqkv + (long long)qrow * 3 * g.C + h * 32 + 4 * r;
-            sb_st4(gq, dq0, g.scale);
-            sb_st4(gq + 16, dq1, g.scale);
+            ab_st4(gq, dq0, g.scale);
+            ab_st4(gq + 16, dq1, g.scale);
         }
     } else {
         for (int T = 0; T < npair; ++T) {
-            sw_st4(dsrow + 32 * T + 8 * r, sw_f4{0.f, 0.f, 0.f, 0.f});
-            sw_st4(dsrow + 32 * T + 8 * r + 4, sw_f4{0.f, 0.f, 0.f, 0.f});
+            sw_st4(dsrow + 32 * T + 8 * r, at_f4{0.f, 0.f, 0.f, 0.f});
+            sw_st4(dsrow + 32 * T + 8 * r + 4, at_f4{0.f, 0.f, 0.f, 0.f});
         }
     }
     __syncthreads();
@@ -845,16 +778,16 @@ __global__ __launch_bounds__(kSwMaxBlock) void swin_bwd_q_bf16_kernel(const SbAr
     }
 }
 
-size_t sb_lds_fwd(int N, int E) { const int Np = (N + 31) & ~31; return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np) * 4; }
+size_t sb_lds_fwd(int N, int E) { const int Np = (N + 31) & ~31; return (size_t)2 * Np * kAbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np) * 4; }
 size_t sb_lds_kv(int N, int E)
 {
     const int Np = (N + 31) & ~31, nwave = (N + 15) / 16;
-    return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np + nwave * 64 + 2 * Np + (Np >> 5)) * 4;
+    return (size_t)2 * Np * kAbRow * 2 + (size_t)(((E + 3) & ~3) + 2 * Np + nwave * 64 + 2 * Np + (Np >> 5)) * 4;
 }
 size_t sb_lds_q(int N, int E)
 {
     const int Np = (N + 31) & ~31, nq = (N + 15) / 16 * 16;
-    return (size_t)2 * Np * kSbRow * 2 + (size_t)(((E + 3) & ~3) + nq * (Np + 4) + 2 * Np) * 4;
+    return (size_t)2 * Np * kAbRow * 2 + (size_t)(((E + 3) & ~3) + nq * (Np + 4) + 2 * Np) * 4;
 }
 
 }  // namespace

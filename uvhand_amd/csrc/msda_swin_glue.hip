@@ -38,13 +38,6 @@ constexpr int kNorm = 0, kAddNorm = 1, kMerge = 2;
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf4;
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 ld4(const uint16_t *p)
-{
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                       __uint_as_float(u.y & 0xffff0000u));
-}
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 __device__ __forceinline__ void st4(uint16_t *p, float4 v)
 {

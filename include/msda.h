@@ -776,6 +776,61 @@ int msda_swin_glue_merge_norm_backward_bf16(const uint16_t *grad_z, const float 
                                             float *grad_beta, void *workspace, unsigned long long workspace_bytes,
                                             msda_stream_t stream);
 
+/* ---- The same glue over a bf16 residual stream (suffix <T>_sbf16, s = stream) ------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Under bf16 autocast PatchMerging's reduction returns bf16, so from the second stage on the residual stream x, y and their
+ * gradients are bf16 bit patterns [rows, C], 8-byte aligned.  T is bf16 for all four operations and float for norm alone (the
+ * per-stage output norms).  Argument order, widths, workspace formula, launch counts and argument checks are those of the
+ * fp32-stream entries above.  rnd rounds to bf16 (nearest even), LN is the fp32 LayerNorm of float(rows), LN' its backward;
+ * the rounding points are those of torch's bf16 arithmetic under autocast:
+ *
+ *   op          forward                                               backward
+ *   norm        z = rnd(LN(x))  (_f32_sbf16: z = LN(x), fp32);        grad_x = rnd(LN'(grad_z)), bf16 (the caller's autograd adds the
+ *               mean, rstd fp32                                       shortcut's gradient); grad_gamma, grad_beta fp32 as above
+ *   add_norm    y = rnd(float(x) + float(rnd(a keep))), bf16;         grad_x = rnd(float(grad_y) + float(rnd(LN'(grad_z)))): the cast's
+ *               z = rnd(LN(y)) over the ROUNDED y, not over the       backward, then the bf16 accumulation.  grad_a = rnd(grad_x keep);
+ *               fp32 sum                                              keep NULL: grad_a is grad_x, pass grad_a NULL
+ *   add         y = rnd(float(x) + float(rnd(a keep)))                grad_x is grad_y itself.  grad_a = rnd(grad_y keep): one launch;
+ *                                                                     keep NULL is refused (grad_a would be grad_y: nothing to compute)
+ *   merge_norm  bf16 x [B, H, W, C] -> z = rnd(LN(cat)), padded       grad_x bf16 [B, H, W, C]: every real token written once
+ *               positions read zero
+ *
+ * keep stays the caller's draw, of type T; no kernel generates random numbers; nothing is contracted into an fma; no float
+ * atomics, bitwise reproducible, no allocation, no synchronisation; argument errors before any launch. */
+int msda_swin_glue_norm_forward_f32_sbf16(const uint16_t *x, const float *gamma, const float *beta, long long rows, int C,
+                                          float eps, float *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_norm_forward_bf16_sbf16(const uint16_t *x, const float *gamma, const float *beta, long long rows, int C,
+                                           float eps, uint16_t *z, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_glue_norm_backward_f32_sbf16(const float *grad_z, const uint16_t *x, const float *gamma, const float *mean,
+                                           const float *rstd, long long rows, int C, uint16_t *grad_x, float *grad_gamma,
+                                           float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                           msda_stream_t stream);
+int msda_swin_glue_norm_backward_bf16_sbf16(const uint16_t *grad_z, const uint16_t *x, const float *gamma, const float *mean,
+                                            const float *rstd, long long rows, int C, uint16_t *grad_x, float *grad_gamma,
+                                            float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                            msda_stream_t stream);
+int msda_swin_glue_add_norm_forward_bf16_sbf16(const uint16_t *x, const uint16_t *a, const uint16_t *keep, long long rows,
+                                               long long rows_per_sample, int C, const float *gamma, const float *beta,
+                                               float eps, uint16_t *y, uint16_t *z, float *mean, float *rstd,
+                                               msda_stream_t stream);
+int msda_swin_glue_add_norm_backward_bf16_sbf16(const uint16_t *grad_y, const uint16_t *grad_z, const uint16_t *y,
+                                                const uint16_t *keep, const float *gamma, const float *mean, const float *rstd,
+                                                long long rows, long long rows_per_sample, int C, uint16_t *grad_x,
+                                                uint16_t *grad_a, float *grad_gamma, float *grad_beta, void *workspace,
+                                                unsigned long long workspace_bytes, msda_stream_t stream);
+int msda_swin_glue_add_forward_bf16_sbf16(const uint16_t *x, const uint16_t *a, const uint16_t *keep, long long rows,
+                                          long long rows_per_sample, int C, uint16_t *y, msda_stream_t stream);
+int msda_swin_glue_add_backward_bf16_sbf16(const uint16_t *grad_y, const uint16_t *keep, long long rows,
+                                           long long rows_per_sample, int C, uint16_t *grad_a, msda_stream_t stream);
+int msda_swin_glue_merge_norm_forward_bf16_sbf16(const uint16_t *x, int B, int H, int W, int C, const float *gamma,
+                                                 const float *beta, float eps, uint16_t *z, float *mean, float *rstd,
+                                                 msda_stream_t stream);
+int msda_swin_glue_merge_norm_backward_bf16_sbf16(const uint16_t *grad_z, const uint16_t *x, const float *gamma,
+                                                  const float *mean, const float *rstd, int B, int H, int W, int C,
+                                                  uint16_t *grad_x, float *grad_gamma, float *grad_beta, void *workspace,
+                                                  unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* ---- MANO hand layer (smplx MANO with use_pca=False: lbs = Rodrigues, shape and pose blend shapes, kinematic chain, linear
  * blend skinning) over several groups of hands -------------------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

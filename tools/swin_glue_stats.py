@@ -8,12 +8,16 @@ measured HBM rate that gives; then the Swin attention kernels and every other ke
         --only autocast_bf16_glue --steps 2 --warmup 1 --no-counts --out ""
     python tools/swin_glue_stats.py DIR/glue_kernel_stats.csv --steps 3 > profiles/swin_glue_kernel_stats.csv
 
-(--glue-stages 4 for a profile of the fp32 route `--glue --only dropin_glue`.)
+(--glue-stages 4 for a profile of the fp32 route `--glue --only dropin_glue`.)  A profile of `--glue-stream --only
+autocast_bf16_glue_stream` (MSDA_SWIN_GLUE_BF16=1 as well) needs no option: the kernels of a bf16 residual stream are other
+instantiations (X = unsigned short), counted with 2-byte rows over stages 1 to 3.
 
-Bytes a kernel must move per row element (x, y and their gradients fp32 = 4, T = bf16 = 2; statistics and parameters left out):
-norm forward x + z = 6, backward grad_z + x + grad_x = 10; add + norm forward x + a + y + z = 12, backward grad_y + grad_z + y +
-grad_x + grad_a = 16; add forward x + a + y = 10, backward grad_y + grad_a = 6; merge + norm forward (per element of the 4C-wide
-row) x + z = 6, backward 10; with T = fp32 each T term is 4 instead of 2.  A kernel's bytes per step are its calls per step
+Bytes a kernel must move per row element (x, y and their gradients: X = fp32 = 4 or bf16 = 2; T = bf16 = 2; statistics and
+parameters left out), for X = fp32: norm forward x + z = 6, backward grad_z + x + grad_x = 10; add + norm forward x + a + y + z =
+12, backward grad_y + grad_z + y + grad_x + grad_a = 16; add forward x + a + y = 10, backward grad_y + grad_a = 6; merge + norm
+forward (per element of the 4C-wide row) x + z = 6, backward 10; with T = fp32 each T term is 4 instead of 2, with X = bf16 each
+X term is 2 instead of 4, and add + norm's backward without a keep vector writes no grad_a (it is grad_x; counted as written, so
+the share of the HBM rate is an upper bound there).  A kernel's bytes per step are its calls per step
 times the bytes of its stage's rows, so checkpoint recomputation and the per-stage output norms are counted as they ran."""
 import argparse
 import csv
@@ -49,34 +53,40 @@ def must_move(name, calls_per_step, glue_stages):
     """(label, bytes per step) of a glue kernel from its template arguments and its calls per step, or None.  A kernel whose
     width is a template argument serves one stage, so its calls all move the same bytes; the add kernels serve every stage
     that takes the glue (`glue_stages`: 4 in fp32, 1 under autocast, where the stream is fp32 in stage 0 only)."""
-    m = re.search(r"glue_(fwd|bwd)_kernel<(\d+), *(unsigned short|float), *(\d)>", name)
+    m = re.search(r"glue_(fwd|bwd)_kernel<(\d+), *(unsigned short|float), *(unsigned short|float), *(\d)>", name)
     if m:
-        direction, nv, typ, mode = m.group(1), int(m.group(2)), m.group(3), int(m.group(4))
+        direction, nv, stream, typ, mode = m.group(1), int(m.group(2)), m.group(3), m.group(4), int(m.group(5))
         t = 2 if typ == "unsigned short" else 4
+        xb = 2 if stream == "unsigned short" else 4
         merged = mode == 2
         width = width_of(nv, merged)
         rows, _ = stage_of_width(width, merged)
         if rows is None:
             return None
         op = ("norm", "add_norm", "merge_norm")[mode]
-        per_elem = {("norm", "fwd"): 4 + t, ("norm", "bwd"): t + 8, ("add_norm", "fwd"): 8 + 2 * t, ("add_norm", "bwd"): 12 + 2 * t,
-                    ("merge_norm", "fwd"): 4 + t, ("merge_norm", "bwd"): t + 8}[(op, direction)]
-        label = "glue %s %s width %d %s" % (op, "forward" if direction == "fwd" else "backward", width,
-                                            "bf16" if t == 2 else "fp32")
+        per_elem = {("norm", "fwd"): xb + t, ("norm", "bwd"): t + 2 * xb, ("add_norm", "fwd"): 2 * xb + 2 * t,
+                    ("add_norm", "bwd"): 3 * xb + 2 * t, ("merge_norm", "fwd"): xb + t,
+                    ("merge_norm", "bwd"): t + 2 * xb}[(op, direction)]
+        label = "glue %s %s width %d %s%s" % (op, "forward" if direction == "fwd" else "backward", width,
+                                              "bf16" if t == 2 else "fp32", " (bf16 stream)" if xb == 2 else "")
         return label, calls_per_step * rows * width * per_elem
-    m = re.search(r"glue_add_(fwd|bwd)_kernel<(unsigned short|float)>", name)
+    m = re.search(r"glue_add_(fwd|bwd)_kernel<(unsigned short|float), *(unsigned short|float)>", name)
     if m:
         # The first block of the network has no drop-path: its closing add saves nothing, so checkpoint recomputation stops
         # before it (forward: once instead of twice), and in fp32 its grad_a is grad_y itself (no launch).
-        direction, t = m.group(1), 2 if m.group(2) == "unsigned short" else 4
-        per_elem = 8 + t if direction == "fwd" else 4 + t
+        direction, t = m.group(1), 2 if m.group(3) == "unsigned short" else 4
+        xb = 2 if m.group(2) == "unsigned short" else 4
+        per_elem = 2 * xb + t if direction == "fwd" else xb + t
         calls, total = 0, 0
-        for i, (H, W, C, depth) in enumerate(STAGES[:glue_stages]):
+        # a bf16 stream: stages 1 to 3 (every block there has drop-path), whatever glue_stages says of the fp32 stream
+        first, stages = (1, STAGES[1:]) if xb == 2 else (0, STAGES[:glue_stages])
+        for i, (H, W, C, depth) in enumerate(stages, first):
             n = 2 * depth - (i == 0) if direction == "fwd" else depth - (i == 0 and t == 4)
             calls += n
             total += n * FRAMES * H * W * C * per_elem
-        label = "glue add %s (%d stage%s) %s" % ("forward" if direction == "fwd" else "backward", glue_stages,
-                                                 "" if glue_stages == 1 else "s", "bf16" if t == 2 else "fp32")
+        label = "glue add %s (%d stage%s) %s%s" % ("forward" if direction == "fwd" else "backward", len(stages),
+                                                   "" if len(stages) == 1 else "s", "bf16" if t == 2 else "fp32",
+                                                   " (bf16 stream)" if xb == 2 else "")
         if abs(calls - calls_per_step) > 1e-9:
             label += " (%g calls per step, %d expected: bytes not comparable)" % (calls_per_step, calls)
         return label, total

@@ -19,7 +19,10 @@ form of the node); the attention-only rows then take bf16 qkv rows.  The default
 patch mergings on HIP) in one process: `dropin` against `dropin_glue`, or with --autocast `autocast_bf16` against
 `autocast_bf16_glue`.  The glue does not touch the attention node, so --glue writes no attention-only rows.
 
-    python tools/swin_time.py [--autocast] [--glue] [--steps K] [--warmup W] [--only ROUTE] [--no-attn] [--no-backbone] [--out FILE]"""
+--glue-stream (with --autocast --glue) adds the route `autocast_bf16_glue_stream`: MSDA_SWIN_BF16=1, MSDA_SWIN_GLUE=1 and
+MSDA_SWIN_GLUE_BF16=1, the glue over the bf16 residual stream of stages 1 to 3 as well.
+
+    python tools/swin_time.py [--autocast] [--glue] [--glue-stream] [--steps K] [--warmup W] [--only ROUTE] [--no-attn] [--no-backbone] [--out FILE]"""
 import argparse
 import contextlib
 import json
@@ -93,13 +96,16 @@ def set_route(route):
     """The environment a route reads at call time."""
     os.environ["MSDA_SWIN_FUSED"] = "0" if route.endswith("composition") else "1"
     os.environ["MSDA_SWIN_BF16"] = "1" if route.startswith("autocast_bf16") else "0"
-    os.environ["MSDA_SWIN_GLUE"] = "1" if route.endswith("_glue") else "0"
+    os.environ["MSDA_SWIN_GLUE"] = "1" if route.endswith(("_glue", "_glue_stream")) else "0"
+    os.environ["MSDA_SWIN_GLUE_BF16"] = "1" if route.endswith("_glue_stream") else "0"
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--autocast", action="store_true", help="bf16 autocast: the composition against MSDA_SWIN_BF16=1")
     ap.add_argument("--glue", action="store_true", help="the kernel route without and with MSDA_SWIN_GLUE=1")
+    ap.add_argument("--glue-stream", action="store_true",
+                    help="with --autocast --glue: also the route with MSDA_SWIN_GLUE_BF16=1 (the glue over the bf16 stream)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default=None)
@@ -109,8 +115,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "swin_time.jsonl"))
     args = ap.parse_args()
     routes = ("autocast_composition", "autocast_bf16") if args.autocast else ("composition", "dropin")
+    if args.glue_stream and not (args.glue and args.autocast):
+        ap.error("--glue-stream needs --autocast --glue: outside autocast the residual stream is fp32")
     if args.glue:
-        routes = (routes[1], routes[1] + "_glue")
+        routes = (routes[1], routes[1] + "_glue") + ((routes[1] + "_glue_stream",) if args.glue_stream else ())
         args.no_attn = True
     amp = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.autocast else contextlib.nullcontext
     torch.manual_seed(0)
@@ -141,7 +149,7 @@ def main():
         rec = {"tool": "swin_time", "what": "backbone_fwd_bwd", "route": route, "backbone": "swin_L_384_22k", "frames": FRAMES,
                "img": IMG, "checkpoint": True, "drop_path_rate": 0.2, "gpu_event_ms_per_step": round(ms, 3),
                "steps": args.steps, "warmup": args.warmup, "autocast": "bf16" if args.autocast else None,
-               "glue": route.endswith("_glue")}
+               "glue": route.endswith(("_glue", "_glue_stream")), "glue_stream": route.endswith("_glue_stream")}
         if not args.no_counts:
             rec.update(kernels_per_step=count_kernels(step), host_syncs_per_step=count_syncs(step),
                        max_memory_allocated_mb=round(peak_mb(step), 1))
@@ -176,6 +184,7 @@ def main():
     os.environ.pop("MSDA_SWIN_FUSED", None)
     os.environ.pop("MSDA_SWIN_BF16", None)
     os.environ.pop("MSDA_SWIN_GLUE", None)
+    os.environ.pop("MSDA_SWIN_GLUE_BF16", None)
 
 
 if __name__ == "__main__":

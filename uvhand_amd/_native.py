@@ -141,6 +141,16 @@ SIGNATURES = {
     "msda_swin_glue_merge_norm_forward_bf16": "i p iiii pp f ppp p",
     "msda_swin_glue_merge_norm_backward_f32": "i ppppp iiii pppp U p",
     "msda_swin_glue_merge_norm_backward_bf16": "i ppppp iiii pppp U p",
+    "msda_swin_glue_norm_forward_f32_sbf16": "i ppp l i f ppp p",
+    "msda_swin_glue_norm_forward_bf16_sbf16": "i ppp l i f ppp p",
+    "msda_swin_glue_norm_backward_f32_sbf16": "i ppppp l i pppp U p",
+    "msda_swin_glue_norm_backward_bf16_sbf16": "i ppppp l i pppp U p",
+    "msda_swin_glue_add_norm_forward_bf16_sbf16": "i ppp ll i pp f pppp p",
+    "msda_swin_glue_add_norm_backward_bf16_sbf16": "i ppppppp ll i ppppp U p",
+    "msda_swin_glue_add_forward_bf16_sbf16": "i ppp ll i p p",
+    "msda_swin_glue_add_backward_bf16_sbf16": "i pp ll i p p",
+    "msda_swin_glue_merge_norm_forward_bf16_sbf16": "i p iiii pp f ppp p",
+    "msda_swin_glue_merge_norm_backward_bf16_sbf16": "i ppppp iiii pppp U p",
     # MANO hand layer
     "msda_mano_supported": "i iii",
     "msda_mano_workspace_bytes": "U iiii p",
@@ -1589,19 +1599,27 @@ def swin_glue_workspace_bytes(rows, C):
     return int((_lib or load()).msda_swin_glue_workspace_bytes(int(rows), int(C)))
 
 
-def _glue_suffix(what, dtype):
-    if dtype == torch.float32:
-        return "f32"
+def _glue_suffix(what, dtype, stream=torch.float32):
+    """The entry's suffix: <T> for an fp32 residual stream, <T>_sbf16 for a bf16 one (bf16 T; fp32 T for norm alone)."""
+    if stream not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("%s: the residual stream is float32 or bfloat16, got %s" % (what, stream))
+    tail = "_sbf16" if stream == torch.bfloat16 else ""
+    if dtype == torch.float32 and (not tail or what.startswith("swin_glue_norm_")):
+        return "f32" + tail
     if dtype == torch.bfloat16:
-        return "bf16"
+        return "bf16" + tail
+    if tail:
+        raise RuntimeError("%s: a bfloat16 residual stream takes a bfloat16 branch, got %s" % (what, dtype))
     raise RuntimeError("%s: the branch / output type is float32 or bfloat16, got %s" % (what, dtype))
 
 
-def _glue_check(what, dev, f32, typed=(), dtype=torch.float32):
-    """Every tensor of `f32` contiguous fp32 on dev, every tensor of `typed` contiguous `dtype` there (None entries skipped)."""
+def _glue_check(what, dev, f32, typed=(), dtype=torch.float32, stream=(), stream_dtype=torch.float32):
+    """Every tensor of `f32` contiguous fp32 on dev, every tensor of `typed` contiguous `dtype` there and every tensor of
+    `stream` (the residual stream's rows) contiguous `stream_dtype` there (None entries skipped)."""
     _check_f32(what, dev, f32)
-    if not all(t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.device == dev) for t in typed):
-        raise RuntimeError("%s: expected contiguous %s CUDA tensors on the rows' device" % (what, dtype))
+    for group, want in ((typed, dtype), (stream, stream_dtype)):
+        if not all(t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and t.device == dev) for t in group):
+            raise RuntimeError("%s: expected contiguous %s CUDA tensors on the rows' device" % (what, want))
 
 
 def _glue_rows(what, x, others=()):
@@ -1631,10 +1649,11 @@ def _glue_workspace(rows, C, dev):
 
 
 def swin_glue_norm_forward(x, weight, bias, eps, out_dtype):
-    """msda_swin_glue_norm_forward_*: (z of out_dtype, mean, rstd) = LayerNorm over the last dimension of fp32 x.  One launch."""
+    """msda_swin_glue_norm_forward_*: (z of out_dtype, mean, rstd) = LayerNorm over the last dimension of x (fp32, or bf16: the
+    _sbf16 entries).  One launch."""
     what = "swin_glue_norm_forward"
-    suf = _glue_suffix(what, out_dtype)
-    _glue_check(what, x.device, [x, weight, bias])
+    suf = _glue_suffix(what, out_dtype, x.dtype)
+    _glue_check(what, x.device, [weight, bias], stream=[x], stream_dtype=x.dtype)
     rows, C = _glue_rows(what, x)
     _glue_params(what, C, weight, bias)
     z = torch.empty(x.shape, dtype=out_dtype, device=x.device)
@@ -1646,10 +1665,10 @@ def swin_glue_norm_forward(x, weight, bias, eps, out_dtype):
 
 
 def swin_glue_norm_backward(grad_z, x, weight, mean, rstd):
-    """msda_swin_glue_norm_backward_* by grad_z's dtype: (grad_x fp32, grad_weight, grad_bias).  Two launches."""
+    """msda_swin_glue_norm_backward_* by grad_z's and x's dtypes: (grad_x of x's type, grad_weight, grad_bias).  Two launches."""
     what = "swin_glue_norm_backward"
-    suf = _glue_suffix(what, grad_z.dtype)
-    _glue_check(what, x.device, [x, weight, mean, rstd], [grad_z], grad_z.dtype)
+    suf = _glue_suffix(what, grad_z.dtype, x.dtype)
+    _glue_check(what, x.device, [weight, mean, rstd], [grad_z], grad_z.dtype, [x], x.dtype)
     rows, C = _glue_rows(what, x, [grad_z])
     _glue_params(what, C, weight)
     gx = torch.empty_like(x)
@@ -1661,11 +1680,11 @@ def swin_glue_norm_backward(grad_z, x, weight, mean, rstd):
 
 
 def swin_glue_add_norm_forward(x, a, keep, rows_per_sample, weight, bias, eps):
-    """msda_swin_glue_add_norm_forward_* by a's dtype T: (y fp32 = x + rnd_T(a * keep[row // rows_per_sample]), z = LN(y) as T,
-    mean, rstd); keep [samples] of T or None.  One launch."""
+    """msda_swin_glue_add_norm_forward_* by a's dtype T and x's: (y of x's type = x + rnd_T(a * keep[row // rows_per_sample]),
+    rounded once more where x is bf16; z = LN(y) as T, mean, rstd); keep [samples] of T or None.  One launch."""
     what = "swin_glue_add_norm_forward"
-    suf = _glue_suffix(what, a.dtype)
-    _glue_check(what, x.device, [x, weight, bias], [a, keep], a.dtype)
+    suf = _glue_suffix(what, a.dtype, x.dtype)
+    _glue_check(what, x.device, [weight, bias], [a, keep], a.dtype, [x], x.dtype)
     rows, C = _glue_rows(what, x, [a])
     _glue_params(what, C, weight, bias)
     rps = _glue_keep(what, keep, rows, rows_per_sample)
@@ -1679,16 +1698,17 @@ def swin_glue_add_norm_forward(x, a, keep, rows_per_sample, weight, bias, eps):
 
 
 def swin_glue_add_norm_backward(grad_y, grad_z, y, keep, rows_per_sample, weight, mean, rstd):
-    """msda_swin_glue_add_norm_backward_* by grad_z's dtype T: (grad_x fp32 = grad_y + LN'(grad_z), grad_a of T = rnd_T(rnd_T(
-    grad_x) * keep), grad_weight, grad_bias).  For fp32 without keep grad_a IS grad_x (the same tensor).  Two launches."""
+    """msda_swin_glue_add_norm_backward_* by grad_z's dtype T and y's: (grad_x of y's type = grad_y + LN'(grad_z), grad_a of T =
+    rnd_T(rnd_T(grad_x) * keep), grad_weight, grad_bias); a bf16 y rounds LN'(grad_z) and the sum (msda.h).  Where T is y's type
+    and there is no keep, grad_a IS grad_x (the same tensor).  Two launches."""
     what = "swin_glue_add_norm_backward"
-    suf = _glue_suffix(what, grad_z.dtype)
-    _glue_check(what, y.device, [grad_y, y, weight, mean, rstd], [grad_z, keep], grad_z.dtype)
+    suf = _glue_suffix(what, grad_z.dtype, y.dtype)
+    _glue_check(what, y.device, [weight, mean, rstd], [grad_z, keep], grad_z.dtype, [grad_y, y], y.dtype)
     rows, C = _glue_rows(what, y, [grad_y, grad_z])
     _glue_params(what, C, weight)
     rps = _glue_keep(what, keep, rows, rows_per_sample)
     gx = torch.empty_like(y)
-    ga = gx if (suf == "f32" and keep is None) else torch.empty_like(grad_z)
+    ga = gx if (grad_z.dtype == y.dtype and keep is None) else torch.empty_like(grad_z)
     gw, gb = torch.empty_like(weight), torch.empty_like(weight)
     ws, nbytes = _glue_workspace(rows, C, y.device)
     _launch(y.device, "msda_swin_glue_add_norm_backward_" + suf, what, grad_y.data_ptr(), grad_z.data_ptr(), y.data_ptr(),
@@ -1698,10 +1718,11 @@ def swin_glue_add_norm_backward(grad_y, grad_z, y, keep, rows_per_sample, weight
 
 
 def swin_glue_add_forward(x, a, keep, rows_per_sample):
-    """msda_swin_glue_add_forward_* by a's dtype T: y fp32 = x + rnd_T(a * keep[row // rows_per_sample]).  One launch."""
+    """msda_swin_glue_add_forward_* by a's dtype T and x's: y of x's type = x + rnd_T(a * keep[row // rows_per_sample]).  One
+    launch."""
     what = "swin_glue_add_forward"
-    suf = _glue_suffix(what, a.dtype)
-    _glue_check(what, x.device, [x], [a, keep], a.dtype)
+    suf = _glue_suffix(what, a.dtype, x.dtype)
+    _glue_check(what, x.device, [], [a, keep], a.dtype, [x], x.dtype)
     rows, C = _glue_rows(what, x, [a])
     rps = _glue_keep(what, keep, rows, rows_per_sample)
     y = torch.empty_like(x)
@@ -1710,13 +1731,13 @@ def swin_glue_add_forward(x, a, keep, rows_per_sample):
 
 
 def swin_glue_add_backward(grad_y, keep, rows_per_sample, dtype):
-    """msda_swin_glue_add_backward_*: grad_a of `dtype` T = rnd_T(rnd_T(grad_y) * keep).  One launch; fp32 without keep: grad_y
-    itself, no launch."""
+    """msda_swin_glue_add_backward_*: grad_a of `dtype` T = rnd_T(rnd_T(grad_y) * keep).  One launch; grad_y of type T without
+    keep: grad_y itself, no launch."""
     what = "swin_glue_add_backward"
-    suf = _glue_suffix(what, dtype)
-    if suf == "f32" and keep is None:
+    suf = _glue_suffix(what, dtype, grad_y.dtype)
+    if grad_y.dtype == dtype and keep is None:
         return grad_y
-    _glue_check(what, grad_y.device, [grad_y], [keep], dtype)
+    _glue_check(what, grad_y.device, [], [keep], dtype, [grad_y], grad_y.dtype)
     rows, C = _glue_rows(what, grad_y)
     rps = _glue_keep(what, keep, rows, rows_per_sample)
     ga = torch.empty(grad_y.shape, dtype=dtype, device=grad_y.device)
@@ -1732,11 +1753,11 @@ def _glue_merge_dims(what, x, weight):
 
 
 def swin_glue_merge_norm_forward(x, weight, bias, eps, out_dtype):
-    """msda_swin_glue_merge_norm_forward_*: x [B, H, W, C] fp32 -> (z [B, ceil(H/2) ceil(W/2), 4C] of out_dtype, mean, rstd):
-    PatchMerging's pad, 2 x 2 gather, concatenation and LayerNorm.  One launch."""
+    """msda_swin_glue_merge_norm_forward_*: x [B, H, W, C] fp32 or bf16 -> (z [B, ceil(H/2) ceil(W/2), 4C] of out_dtype, mean,
+    rstd): PatchMerging's pad, 2 x 2 gather, concatenation and LayerNorm.  One launch."""
     what = "swin_glue_merge_norm_forward"
-    suf = _glue_suffix(what, out_dtype)
-    _glue_check(what, x.device, [x, weight, bias])
+    suf = _glue_suffix(what, out_dtype, x.dtype)
+    _glue_check(what, x.device, [weight, bias], stream=[x], stream_dtype=x.dtype)
     B, H, W, C, L2 = _glue_merge_dims(what, x, weight)
     _glue_params(what, 4 * C, bias)
     z = torch.empty((B, L2, 4 * C), dtype=out_dtype, device=x.device)
@@ -1748,10 +1769,11 @@ def swin_glue_merge_norm_forward(x, weight, bias, eps, out_dtype):
 
 
 def swin_glue_merge_norm_backward(grad_z, x, weight, mean, rstd):
-    """msda_swin_glue_merge_norm_backward_* by grad_z's dtype: (grad_x [B, H, W, C] fp32, grad_weight, grad_bias).  Two launches."""
+    """msda_swin_glue_merge_norm_backward_* by grad_z's and x's dtypes: (grad_x [B, H, W, C] of x's type, grad_weight, grad_bias).
+    Two launches."""
     what = "swin_glue_merge_norm_backward"
-    suf = _glue_suffix(what, grad_z.dtype)
-    _glue_check(what, x.device, [x, weight, mean, rstd], [grad_z], grad_z.dtype)
+    suf = _glue_suffix(what, grad_z.dtype, x.dtype)
+    _glue_check(what, x.device, [weight, mean, rstd], [grad_z], grad_z.dtype, [x], x.dtype)
     B, H, W, C, L2 = _glue_merge_dims(what, x, weight)
     if tuple(grad_z.shape) != (B, L2, 4 * C):
         raise RuntimeError("%s: expected grad_z [B, ceil(H/2) ceil(W/2), 4C]" % what)

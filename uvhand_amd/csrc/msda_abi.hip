@@ -1273,71 +1273,78 @@ int msda_swin_glue_supported(int C) { return msda::swin_glue_supported(C) ? 1 : 
 
 unsigned long long msda_swin_glue_workspace_bytes(long long rows, int C) { return msda::swin_glue_workspace_bytes(rows, C); }
 
-#define MSDA_SWIN_GLUE_ENTRIES(T, SUF, BF)                                                                                       \
-    int msda_swin_glue_norm_forward_##SUF(const float *x, const float *gamma, const float *beta, long long rows, int C,          \
-                                          float eps, T *z, float *mean, float *rstd, msda_stream_t stream)                      \
+// X: the residual stream's type (x, y and their gradients), T: the branch's and the normalised rows'; SUF <T> or <T>_sbf16
+#define MSDA_SWIN_GLUE_NORM_ENTRIES(X, T, SUF, SBF, BF)                                                                          \
+    int msda_swin_glue_norm_forward_##SUF(const X *x, const float *gamma, const float *beta, long long rows, int C, float eps,   \
+                                          T *z, float *mean, float *rstd, msda_stream_t stream)                                  \
     {                                                                                                                            \
         msda::begin_call();                                                                                                      \
-        return msda::swin_glue_norm_forward(BF, x, gamma, beta, rows, C, eps, z, mean, rstd, (hipStream_t)stream);               \
+        return msda::swin_glue_norm_forward(SBF, BF, x, gamma, beta, rows, C, eps, z, mean, rstd, (hipStream_t)stream);          \
     }                                                                                                                            \
-    int msda_swin_glue_norm_backward_##SUF(const T *grad_z, const float *x, const float *gamma, const float *mean,               \
-                                           const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma,          \
-                                           float *grad_beta, void *workspace, unsigned long long workspace_bytes,               \
-                                           msda_stream_t stream)                                                                \
+    int msda_swin_glue_norm_backward_##SUF(const T *grad_z, const X *x, const float *gamma, const float *mean,                   \
+                                           const float *rstd, long long rows, int C, X *grad_x, float *grad_gamma,               \
+                                           float *grad_beta, void *workspace, unsigned long long workspace_bytes,                \
+                                           msda_stream_t stream)                                                                 \
     {                                                                                                                            \
         msda::begin_call();                                                                                                      \
-        return msda::swin_glue_norm_backward(BF, grad_z, x, gamma, mean, rstd, rows, C, grad_x, grad_gamma, grad_beta,           \
-                                             workspace, workspace_bytes, (hipStream_t)stream);                                  \
-    }                                                                                                                            \
-    int msda_swin_glue_add_norm_forward_##SUF(const float *x, const T *a, const T *keep, long long rows,                         \
-                                              long long rows_per_sample, int C, const float *gamma, const float *beta,          \
-                                              float eps, float *y, T *z, float *mean, float *rstd, msda_stream_t stream)        \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_add_norm_forward(BF, x, a, keep, rows, rows_per_sample, C, gamma, beta, eps, y, z, mean, rstd,    \
-                                                (hipStream_t)stream);                                                           \
-    }                                                                                                                            \
-    int msda_swin_glue_add_norm_backward_##SUF(const float *grad_y, const T *grad_z, const float *y, const T *keep,              \
-                                               const float *gamma, const float *mean, const float *rstd, long long rows,        \
-                                               long long rows_per_sample, int C, float *grad_x, T *grad_a, float *grad_gamma,   \
-                                               float *grad_beta, void *workspace, unsigned long long workspace_bytes,           \
-                                               msda_stream_t stream)                                                            \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_add_norm_backward(BF, grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C,       \
-                                                 grad_x, grad_a, grad_gamma, grad_beta, workspace, workspace_bytes,             \
-                                                 (hipStream_t)stream);                                                          \
-    }                                                                                                                            \
-    int msda_swin_glue_add_forward_##SUF(const float *x, const T *a, const T *keep, long long rows, long long rows_per_sample,   \
-                                         int C, float *y, msda_stream_t stream)                                                 \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_add_forward(BF, x, a, keep, rows, rows_per_sample, C, y, (hipStream_t)stream);                    \
-    }                                                                                                                            \
-    int msda_swin_glue_add_backward_##SUF(const float *grad_y, const T *keep, long long rows, long long rows_per_sample, int C,  \
-                                          T *grad_a, msda_stream_t stream)                                                      \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_add_backward(BF, grad_y, keep, rows, rows_per_sample, C, grad_a, (hipStream_t)stream);            \
-    }                                                                                                                            \
-    int msda_swin_glue_merge_norm_forward_##SUF(const float *x, int B, int H, int W, int C, const float *gamma,                  \
-                                                const float *beta, float eps, T *z, float *mean, float *rstd,                   \
-                                                msda_stream_t stream)                                                           \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_merge_norm_forward(BF, x, B, H, W, C, gamma, beta, eps, z, mean, rstd, (hipStream_t)stream);      \
-    }                                                                                                                            \
-    int msda_swin_glue_merge_norm_backward_##SUF(const T *grad_z, const float *x, const float *gamma, const float *mean,         \
-                                                 const float *rstd, int B, int H, int W, int C, float *grad_x,                  \
-                                                 float *grad_gamma, float *grad_beta, void *workspace,                          \
-                                                 unsigned long long workspace_bytes, msda_stream_t stream)                      \
-    {                                                                                                                            \
-        msda::begin_call();                                                                                                      \
-        return msda::swin_glue_merge_norm_backward(BF, grad_z, x, gamma, mean, rstd, B, H, W, C, grad_x, grad_gamma, grad_beta,  \
-                                                   workspace, workspace_bytes, (hipStream_t)stream);                            \
+        return msda::swin_glue_norm_backward(SBF, BF, grad_z, x, gamma, mean, rstd, rows, C, grad_x, grad_gamma, grad_beta,      \
+                                             workspace, workspace_bytes, (hipStream_t)stream);                                   \
     }
-MSDA_SWIN_GLUE_ENTRIES(float, f32, false)
-MSDA_SWIN_GLUE_ENTRIES(uint16_t, bf16, true)
+#define MSDA_SWIN_GLUE_ENTRIES(X, T, SUF, SBF, BF)                                                                               \
+    MSDA_SWIN_GLUE_NORM_ENTRIES(X, T, SUF, SBF, BF)                                                                              \
+    int msda_swin_glue_add_norm_forward_##SUF(const X *x, const T *a, const T *keep, long long rows,                             \
+                                              long long rows_per_sample, int C, const float *gamma, const float *beta,           \
+                                              float eps, X *y, T *z, float *mean, float *rstd, msda_stream_t stream)             \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_norm_forward(SBF, BF, x, a, keep, rows, rows_per_sample, C, gamma, beta, eps, y, z, mean,     \
+                                                rstd, (hipStream_t)stream);                                                      \
+    }                                                                                                                            \
+    int msda_swin_glue_add_norm_backward_##SUF(const X *grad_y, const T *grad_z, const X *y, const T *keep,                      \
+                                               const float *gamma, const float *mean, const float *rstd, long long rows,         \
+                                               long long rows_per_sample, int C, X *grad_x, T *grad_a, float *grad_gamma,        \
+                                               float *grad_beta, void *workspace, unsigned long long workspace_bytes,            \
+                                               msda_stream_t stream)                                                             \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_norm_backward(SBF, BF, grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C,  \
+                                                 grad_x, grad_a, grad_gamma, grad_beta, workspace, workspace_bytes,              \
+                                                 (hipStream_t)stream);                                                           \
+    }                                                                                                                            \
+    int msda_swin_glue_add_forward_##SUF(const X *x, const T *a, const T *keep, long long rows, long long rows_per_sample,       \
+                                         int C, X *y, msda_stream_t stream)                                                      \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_forward(SBF, BF, x, a, keep, rows, rows_per_sample, C, y, (hipStream_t)stream);               \
+    }                                                                                                                            \
+    int msda_swin_glue_add_backward_##SUF(const X *grad_y, const T *keep, long long rows, long long rows_per_sample, int C,      \
+                                          T *grad_a, msda_stream_t stream)                                                       \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_add_backward(SBF, BF, grad_y, keep, rows, rows_per_sample, C, grad_a, (hipStream_t)stream);       \
+    }                                                                                                                            \
+    int msda_swin_glue_merge_norm_forward_##SUF(const X *x, int B, int H, int W, int C, const float *gamma,                      \
+                                                const float *beta, float eps, T *z, float *mean, float *rstd,                    \
+                                                msda_stream_t stream)                                                            \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_merge_norm_forward(SBF, BF, x, B, H, W, C, gamma, beta, eps, z, mean, rstd,                       \
+                                                  (hipStream_t)stream);                                                          \
+    }                                                                                                                            \
+    int msda_swin_glue_merge_norm_backward_##SUF(const T *grad_z, const X *x, const float *gamma, const float *mean,             \
+                                                 const float *rstd, int B, int H, int W, int C, X *grad_x,                       \
+                                                 float *grad_gamma, float *grad_beta, void *workspace,                           \
+                                                 unsigned long long workspace_bytes, msda_stream_t stream)                       \
+    {                                                                                                                            \
+        msda::begin_call();                                                                                                      \
+        return msda::swin_glue_merge_norm_backward(SBF, BF, grad_z, x, gamma, mean, rstd, B, H, W, C, grad_x, grad_gamma,        \
+                                                   grad_beta, workspace, workspace_bytes, (hipStream_t)stream);                  \
+    }
+MSDA_SWIN_GLUE_ENTRIES(float, float, f32, false, false)
+MSDA_SWIN_GLUE_ENTRIES(float, uint16_t, bf16, false, true)
+MSDA_SWIN_GLUE_ENTRIES(uint16_t, uint16_t, bf16_sbf16, true, true)
+MSDA_SWIN_GLUE_NORM_ENTRIES(uint16_t, float, f32_sbf16, true, false)       // the per-stage output norms of a bf16 stream
 #undef MSDA_SWIN_GLUE_ENTRIES
+#undef MSDA_SWIN_GLUE_NORM_ENTRIES
 
 }  // extern "C"

@@ -335,30 +335,32 @@ int swin_backward_bf16(int B, int H, int W, int C, int nH, int ws, int shift, co
                        unsigned long long workspace_bytes, hipStream_t stream);
 
 // ---- the Swin blocks' residual / drop-path / LayerNorm glue and PatchMerging's gather + norm (msda_swin_glue.hip; C entries
-// msda_swin_glue_*).  bf16: a, keep, z and their gradients are bf16 bits (uint16_t), else float; x, y and the statistics fp32.
+// msda_swin_glue_*).  bf16: a, keep, z and their gradients are bf16 bits (uint16_t), else float.  sbf16: the residual stream (x,
+// y and their gradients) is bf16 bits, else float; a bf16 stream has a bf16 branch, and fp32 z for norm alone.  Statistics fp32.
 bool swin_glue_supported(int C);
 unsigned long long swin_glue_workspace_bytes(long long rows, int C);
-int swin_glue_norm_forward(bool bf16, const float *x, const float *gamma, const float *beta, long long rows, int C, float eps,
-                           void *z, float *mean, float *rstd, hipStream_t stream);
-int swin_glue_norm_backward(bool bf16, const void *grad_z, const float *x, const float *gamma, const float *mean,
-                            const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma, float *grad_beta,
+int swin_glue_norm_forward(bool sbf16, bool bf16, const void *x, const float *gamma, const float *beta, long long rows, int C,
+                           float eps, void *z, float *mean, float *rstd, hipStream_t stream);
+int swin_glue_norm_backward(bool sbf16, bool bf16, const void *grad_z, const void *x, const float *gamma, const float *mean,
+                            const float *rstd, long long rows, int C, void *grad_x, float *grad_gamma, float *grad_beta,
                             void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
-int swin_glue_add_norm_forward(bool bf16, const float *x, const void *a, const void *keep, long long rows,
-                               long long rows_per_sample, int C, const float *gamma, const float *beta, float eps, float *y,
+int swin_glue_add_norm_forward(bool sbf16, bool bf16, const void *x, const void *a, const void *keep, long long rows,
+                               long long rows_per_sample, int C, const float *gamma, const float *beta, float eps, void *y,
                                void *z, float *mean, float *rstd, hipStream_t stream);
-int swin_glue_add_norm_backward(bool bf16, const float *grad_y, const void *grad_z, const float *y, const void *keep,
+int swin_glue_add_norm_backward(bool sbf16, bool bf16, const void *grad_y, const void *grad_z, const void *y, const void *keep,
                                 const float *gamma, const float *mean, const float *rstd, long long rows,
-                                long long rows_per_sample, int C, float *grad_x, void *grad_a, float *grad_gamma,
+                                long long rows_per_sample, int C, void *grad_x, void *grad_a, float *grad_gamma,
                                 float *grad_beta, void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
-int swin_glue_add_forward(bool bf16, const float *x, const void *a, const void *keep, long long rows, long long rows_per_sample,
-                          int C, float *y, hipStream_t stream);
-int swin_glue_add_backward(bool bf16, const float *grad_y, const void *keep, long long rows, long long rows_per_sample, int C,
-                           void *grad_a, hipStream_t stream);
-int swin_glue_merge_norm_forward(bool bf16, const float *x, int B, int H, int W, int C, const float *gamma, const float *beta,
-                                 float eps, void *z, float *mean, float *rstd, hipStream_t stream);
-int swin_glue_merge_norm_backward(bool bf16, const void *grad_z, const float *x, const float *gamma, const float *mean,
-                                  const float *rstd, int B, int H, int W, int C, float *grad_x, float *grad_gamma,
-                                  float *grad_beta, void *workspace, unsigned long long workspace_bytes, hipStream_t stream);
+int swin_glue_add_forward(bool sbf16, bool bf16, const void *x, const void *a, const void *keep, long long rows,
+                          long long rows_per_sample, int C, void *y, hipStream_t stream);
+int swin_glue_add_backward(bool sbf16, bool bf16, const void *grad_y, const void *keep, long long rows,
+                           long long rows_per_sample, int C, void *grad_a, hipStream_t stream);
+int swin_glue_merge_norm_forward(bool sbf16, bool bf16, const void *x, int B, int H, int W, int C, const float *gamma,
+                                 const float *beta, float eps, void *z, float *mean, float *rstd, hipStream_t stream);
+int swin_glue_merge_norm_backward(bool sbf16, bool bf16, const void *grad_z, const void *x, const float *gamma,
+                                  const float *mean, const float *rstd, int B, int H, int W, int C, void *grad_x,
+                                  float *grad_gamma, float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                  hipStream_t stream);
 
 // ---- the input-projection neck: bias + GroupNorm + feature mask of every level (msda_neck.hip; C entries msda_neck_*) ----
 // Both level tables travel by value in the kernel arguments, as FlattenPlan does.

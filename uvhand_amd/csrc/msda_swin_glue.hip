@@ -2,8 +2,10 @@
 // norm1 / residual + drop_path / norm2 / residual + drop_path, :263-287 PatchMerging's pad, 2x2 gather, concatenation and norm),
 // for MI355X (gfx950).  Opt-in from Python (MSDA_SWIN_GLUE=1); C entries msda_swin_glue_*.
 //
-// The residual stream x is always fp32.  T is the type of the branch a, of the per-sample drop-path scale keep, of the
-// normalised output z and of their gradients: float, or uint16_t holding bf16 bits (the bf16-autocast route).
+// X is the type of the residual stream (x, y, their gradients and the rows the backward re-reads), T the type of the branch a,
+// of the per-sample drop-path scale keep, of the normalised output z and of their gradients: float, or uint16_t holding bf16
+// bits.  X = float is the stream outside autocast and of stage 0 under bf16 autocast; X = bf16 (the _sbf16 entries) is the
+// stream from the first PatchMerging on under bf16 autocast, with T = bf16, or T = float for the per-stage output norms.
 //
 //   norm        z = LN(x) gamma + beta                                            -> z (T), mean, rstd
 //   add_norm    y = x + rnd_T(a keep[row / rows_per_sample]);  z = LN(y) ...      -> y (fp32), z (T), mean, rstd   one launch
@@ -13,6 +15,12 @@
 // rnd_T rounds to bf16 (nearest even) for bf16 and is the identity for fp32: the product a * keep is a tensor of type T in
 // torch before type promotion widens it for the add, so y is bit for bit torch's.  keep null means 1 (no product, no rounding).
 // Nothing here is contracted into an fma (the pragma below): torch runs the product and the add as separate kernels.
+//
+// A bf16 stream rounds (rnd_X, nearest even) wherever torch's bf16 arithmetic under autocast materialises a bf16 tensor:
+//   forward   y = rnd_X(x + rnd_T(a keep)), and z normalises that ROUNDED y (the LayerNorm reads the stored tensor);
+//   backward  grad_x = rnd_X(grad_y + rnd_X(LN'(grad_z))): the cast's backward rounds, then autograd's accumulation rounds;
+//             grad_a = rnd_T(grad_x keep) from the rounded grad_x; without keep grad_a is grad_x and is not written.
+// rnd_X is the identity for X = float, so the fp32-stream instantiations compute what they computed before X existed.
 //
 // Conventions of msda_layernorm.hip: one wavefront per row, 4 rows in flight per workgroup, lane i holds channels 4i..4i+3
 // (+256k) as float4 (16-byte fp32 / 8-byte bf16 accesses), two-pass moments in fp32 over registers; the backward's gamma / beta
@@ -79,10 +87,10 @@ __device__ __forceinline__ long long merge_off(const MergeGeo &g, const MergeRow
     return (r.base + (long long)h * g.W + w) * g.C + cc;
 }
 
-template <int NV, typename T, int MODE>
+template <int NV, typename X, typename T, int MODE>
 __global__ __launch_bounds__(kGlBlock) void glue_fwd_kernel(
-    const float *__restrict__ x, const T *__restrict__ a, const T *__restrict__ keep, long long rows, long long rows_per_sample,
-    int d, MergeGeo geo, const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float *__restrict__ y,
+    const X *__restrict__ x, const T *__restrict__ a, const T *__restrict__ keep, long long rows, long long rows_per_sample,
+    int d, MergeGeo geo, const float *__restrict__ gamma, const float *__restrict__ beta, float eps, X *__restrict__ y,
     T *__restrict__ z, float *__restrict__ mean_out, float *__restrict__ rstd_out)
 {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -109,6 +117,7 @@ __global__ __launch_bounds__(kGlBlock) void glue_fwd_kernel(
                 float4 t = ld4(a + row * d + c);
                 if (scaled) t = scale4<T>(t, kp);
                 v[k].x += t.x; v[k].y += t.y; v[k].z += t.z; v[k].w += t.w;
+                v[k] = rnd4<X>(v[k]);                                    // the LayerNorm reads the stored y
                 st4(y + row * d + c, v[k]);
             }
             sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
@@ -142,12 +151,13 @@ __global__ __launch_bounds__(kGlBlock) void glue_fwd_kernel(
 // Workgroup w owns the rows [w * rows_per_wg, (w+1) * rows_per_wg); its 4 wavefronts take them round-robin.  src: the rows the
 // forward normalised (norm, merge_norm: x; add_norm: the saved y).  add_norm adds grad_y and writes the sum as grad_x, and
 // grad_a = rnd_T(rnd_T(grad_x) keep) (the two roundings of torch's autograd; one product for fp32) unless ga is null.
+// A bf16 stream rounds LN'(grad_z) before the sum and the sum again (the file comment); grad_a then starts from that grad_x.
 // partial[w][2][d]: the workgroup's dgamma / dbeta column sums.
-template <int NV, typename T, int MODE>
+template <int NV, typename X, typename T, int MODE>
 __global__ __launch_bounds__(kGlBlock) void glue_bwd_kernel(
-    const float *__restrict__ gy, const T *__restrict__ gz, const float *__restrict__ src, const T *__restrict__ keep,
+    const X *__restrict__ gy, const T *__restrict__ gz, const X *__restrict__ src, const T *__restrict__ keep,
     const float *__restrict__ gamma, const float *__restrict__ mean_in, const float *__restrict__ rstd_in, long long rows,
-    long long rows_per_sample, int d, MergeGeo geo, int rows_per_wg, float *__restrict__ gx, T *__restrict__ ga,
+    long long rows_per_sample, int d, MergeGeo geo, int rows_per_wg, X *__restrict__ gx, T *__restrict__ ga,
     float *__restrict__ partial)
 {
     constexpr bool kLds = NV > kGlRegVec;                                // column sums in LDS instead of registers
@@ -221,7 +231,9 @@ __global__ __launch_bounds__(kGlBlock) void glue_bwd_kernel(
                 } else {
                     if (MODE == kAddNorm) {
                         const float4 t = ld4(gy + row * d + c);
+                        o = rnd4<X>(o);
                         o.x += t.x; o.y += t.y; o.z += t.z; o.w += t.w;
+                        o = rnd4<X>(o);
                     }
                     st4(gx + row * d + c, o);
                     if (MODE == kAddNorm && ga) {
@@ -251,11 +263,12 @@ __global__ __launch_bounds__(kGlBlock) void glue_bwd_kernel(
     }
 }
 
-// y = x + rnd_T(a keep[row / rows_per_sample]): one wavefront per row, so the sample index is found once per row
-template <typename T>
-__global__ __launch_bounds__(kGlBlock) void glue_add_fwd_kernel(const float *__restrict__ x, const T *__restrict__ a,
+// y = rnd_X(x + rnd_T(a keep[row / rows_per_sample])) (the store rounds): one wavefront per row, so the sample index is found
+// once per row
+template <typename X, typename T>
+__global__ __launch_bounds__(kGlBlock) void glue_add_fwd_kernel(const X *__restrict__ x, const T *__restrict__ a,
                                                                 const T *__restrict__ keep, long long rows,
-                                                                long long rows_per_sample, int d, float *__restrict__ y)
+                                                                long long rows_per_sample, int d, X *__restrict__ y)
 {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * kGlWaves + wave;
@@ -270,8 +283,8 @@ __global__ __launch_bounds__(kGlBlock) void glue_add_fwd_kernel(const float *__r
 }
 
 // grad_a = rnd_T(rnd_T(grad_y) keep[..]) (keep null: rnd_T(grad_y)); grad_x is grad_y itself
-template <typename T>
-__global__ __launch_bounds__(kGlBlock) void glue_add_bwd_kernel(const float *__restrict__ gy, const T *__restrict__ keep,
+template <typename X, typename T>
+__global__ __launch_bounds__(kGlBlock) void glue_add_bwd_kernel(const X *__restrict__ gy, const T *__restrict__ keep,
                                                                 long long rows, long long rows_per_sample, int d,
                                                                 T *__restrict__ ga)
 {
@@ -386,31 +399,32 @@ MergeGeo merge_geo(int H, int W, int C) { return MergeGeo{H, W, (H + 1) / 2, (W 
         else if (d <= 1536) F(6); else if (d <= 2048) F(8); else F(12);                                                          \
     } while (0)
 
-template <typename T, int MODE>
-int glue_fwd(const float *x, const void *a, const void *keep, long long rows, long long rps, int d, MergeGeo geo,
-             const float *gamma, const float *beta, float eps, float *y, void *z, float *mean, float *rstd, hipStream_t stream)
+template <typename X, typename T, int MODE>
+int glue_fwd(const void *x, const void *a, const void *keep, long long rows, long long rps, int d, MergeGeo geo,
+             const float *gamma, const float *beta, float eps, void *y, void *z, float *mean, float *rstd, hipStream_t stream)
 {
     if (rows == 0) return MSDA_OK;
     const dim3 grid((unsigned)((rows + kGlWaves - 1) / kGlWaves)), block(kGlBlock);
 #define MSDA_GLUE_F(NV)                                                                                                          \
-    hipLaunchKernelGGL((glue_fwd_kernel<NV, T, MODE>), grid, block, 0, stream, x, (const T *)a, (const T *)keep, rows, rps, d,   \
-                       geo, gamma, beta, eps, y, (T *)z, mean, rstd)
+    hipLaunchKernelGGL((glue_fwd_kernel<NV, X, T, MODE>), grid, block, 0, stream, (const X *)x, (const T *)a, (const T *)keep,   \
+                       rows, rps, d, geo, gamma, beta, eps, (X *)y, (T *)z, mean, rstd)
     MSDA_GLUE_NV(d, MSDA_GLUE_F);
 #undef MSDA_GLUE_F
     return check_launch("msda swin glue forward");
 }
 
-template <typename T, int MODE>
-int glue_bwd(const float *gy, const void *gz, const float *src, const void *keep, const float *gamma, const float *mean,
-             const float *rstd, long long rows, long long rps, int d, MergeGeo geo, float *gx, void *ga, float *dgamma,
+template <typename X, typename T, int MODE>
+int glue_bwd(const void *gy, const void *gz, const void *src, const void *keep, const float *gamma, const float *mean,
+             const float *rstd, long long rows, long long rps, int d, MergeGeo geo, void *gx, void *ga, float *dgamma,
              float *dbeta, float *workspace, hipStream_t stream)
 {
     // rows == 0: no partials; the reduce below then writes zeros from one empty workgroup's sums
     const int nwg = glue_wgs(rows);
     const int rows_per_wg = (int)((rows + nwg - 1) / nwg);
 #define MSDA_GLUE_B(NV)                                                                                                          \
-    hipLaunchKernelGGL((glue_bwd_kernel<NV, T, MODE>), dim3(nwg), dim3(kGlBlock), 0, stream, gy, (const T *)gz, src,             \
-                       (const T *)keep, gamma, mean, rstd, rows, rps, d, geo, rows_per_wg, gx, (T *)ga, workspace)
+    hipLaunchKernelGGL((glue_bwd_kernel<NV, X, T, MODE>), dim3(nwg), dim3(kGlBlock), 0, stream, (const X *)gy, (const T *)gz,    \
+                       (const X *)src, (const T *)keep, gamma, mean, rstd, rows, rps, d, geo, rows_per_wg, (X *)gx, (T *)ga,    \
+                       workspace)
     MSDA_GLUE_NV(d, MSDA_GLUE_B);
 #undef MSDA_GLUE_B
     if (int rc = check_launch("msda swin glue backward")) return rc;
@@ -418,8 +432,18 @@ int glue_bwd(const float *gy, const void *gz, const float *src, const void *keep
     return check_launch("msda swin glue parameter gradients");
 }
 
+// The instantiations: a bf16 stream has a bf16 branch, and fp32 normalised rows for norm alone (the per-stage output norms).
+#define MSDA_GLUE_PICK(sbf16, bf16, CALL) ((sbf16) ? CALL(uint16_t, uint16_t) : (bf16) ? CALL(float, uint16_t) : CALL(float, float))
+#define MSDA_GLUE_PICK_NORM(sbf16, bf16, CALL) ((sbf16) && !(bf16) ? CALL(uint16_t, float) : MSDA_GLUE_PICK(sbf16, bf16, CALL))
+
 inline size_t row_align(bool bf16) { return bf16 ? 8 : 16; }
 inline size_t elem_align(bool bf16) { return bf16 ? 2 : 4; }
+
+// "msda_swin_glue_<op>_<T>[_sbf16]"
+const char *entry_name(bool sbf16, bool bf16, const char *const (&names)[4]) { return names[(sbf16 ? 2 : 0) + (bf16 ? 1 : 0)]; }
+#define MSDA_GLUE_NAMES(op)                                                                                                      \
+    {"msda_swin_glue_" op "_f32", "msda_swin_glue_" op "_bf16", "msda_swin_glue_" op "_f32_sbf16",                               \
+     "msda_swin_glue_" op "_bf16_sbf16"}
 
 }  // namespace
 
@@ -431,137 +455,147 @@ unsigned long long swin_glue_workspace_bytes(long long rows, int C)
     return (unsigned long long)glue_wgs(rows) * 2 * C * sizeof(float);
 }
 
-int swin_glue_norm_forward(bool bf16, const float *x, const float *gamma, const float *beta, long long rows, int C, float eps,
-                           void *z, float *mean, float *rstd, hipStream_t stream)
+int swin_glue_norm_forward(bool sbf16, bool bf16, const void *x, const float *gamma, const float *beta, long long rows, int C,
+                           float eps, void *z, float *mean, float *rstd, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_norm_forward_bf16" : "msda_swin_glue_norm_forward_f32";
-    if (int rc = glue_check(who, rows, 1, C, {{x, 16, false}, {gamma, 16, false}, {beta, 16, false}, {z, row_align(bf16), false},
-                                             {mean, 4, false}, {rstd, 4, false}}))
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("norm_forward"));
+    if (int rc = glue_check(who, rows, 1, C, {{x, row_align(sbf16), false}, {gamma, 16, false}, {beta, 16, false},
+                                             {z, row_align(bf16), false}, {mean, 4, false}, {rstd, 4, false}}))
         return rc;
     const MergeGeo geo{};
-    return bf16 ? glue_fwd<uint16_t, kNorm>(x, nullptr, nullptr, rows, 1, C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream)
-                : glue_fwd<float, kNorm>(x, nullptr, nullptr, rows, 1, C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream);
+#define MSDA_GLUE_CALL(X, T) glue_fwd<X, T, kNorm>(x, nullptr, nullptr, rows, 1, C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream)
+    return MSDA_GLUE_PICK_NORM(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
-int swin_glue_norm_backward(bool bf16, const void *grad_z, const float *x, const float *gamma, const float *mean,
-                            const float *rstd, long long rows, int C, float *grad_x, float *grad_gamma, float *grad_beta,
+int swin_glue_norm_backward(bool sbf16, bool bf16, const void *grad_z, const void *x, const float *gamma, const float *mean,
+                            const float *rstd, long long rows, int C, void *grad_x, float *grad_gamma, float *grad_beta,
                             void *workspace, unsigned long long workspace_bytes, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_norm_backward_bf16" : "msda_swin_glue_norm_backward_f32";
-    if (int rc = glue_check(who, rows, 1, C, {{grad_z, row_align(bf16), false}, {x, 16, false}, {gamma, 16, false},
-                                             {mean, 4, false}, {rstd, 4, false}, {grad_x, 16, false}, {grad_gamma, 4, false},
-                                             {grad_beta, 4, false}}))
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("norm_backward"));
+    if (int rc = glue_check(who, rows, 1, C, {{grad_z, row_align(bf16), false}, {x, row_align(sbf16), false},
+                                             {gamma, 16, false}, {mean, 4, false}, {rstd, 4, false},
+                                             {grad_x, row_align(sbf16), false}, {grad_gamma, 4, false}, {grad_beta, 4, false}}))
         return rc;
     if (int rc = glue_check_workspace(who, rows, C, workspace, workspace_bytes)) return rc;
     const MergeGeo geo{};
-    return bf16 ? glue_bwd<uint16_t, kNorm>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, C, geo, grad_x, nullptr,
-                                            grad_gamma, grad_beta, (float *)workspace, stream)
-                : glue_bwd<float, kNorm>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, C, geo, grad_x, nullptr,
-                                         grad_gamma, grad_beta, (float *)workspace, stream);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    glue_bwd<X, T, kNorm>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, C, geo, grad_x, nullptr, grad_gamma,          \
+                          grad_beta, (float *)workspace, stream)
+    return MSDA_GLUE_PICK_NORM(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
-int swin_glue_add_norm_forward(bool bf16, const float *x, const void *a, const void *keep, long long rows,
-                               long long rows_per_sample, int C, const float *gamma, const float *beta, float eps, float *y,
+int swin_glue_add_norm_forward(bool sbf16, bool bf16, const void *x, const void *a, const void *keep, long long rows,
+                               long long rows_per_sample, int C, const float *gamma, const float *beta, float eps, void *y,
                                void *z, float *mean, float *rstd, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_add_norm_forward_bf16" : "msda_swin_glue_add_norm_forward_f32";
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("add_norm_forward"));
     if (int rc = glue_check(who, rows, rows_per_sample, C,
-                            {{x, 16, false}, {a, row_align(bf16), false}, {keep, elem_align(bf16), true}, {gamma, 16, false},
-                             {beta, 16, false}, {y, 16, false}, {z, row_align(bf16), false}, {mean, 4, false}, {rstd, 4, false}}))
+                            {{x, row_align(sbf16), false}, {a, row_align(bf16), false}, {keep, elem_align(bf16), true},
+                             {gamma, 16, false}, {beta, 16, false}, {y, row_align(sbf16), false}, {z, row_align(bf16), false},
+                             {mean, 4, false}, {rstd, 4, false}}))
         return rc;
     const MergeGeo geo{};
-    return bf16 ? glue_fwd<uint16_t, kAddNorm>(x, a, keep, rows, rows_per_sample, C, geo, gamma, beta, eps, y, z, mean, rstd, stream)
-                : glue_fwd<float, kAddNorm>(x, a, keep, rows, rows_per_sample, C, geo, gamma, beta, eps, y, z, mean, rstd, stream);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    glue_fwd<X, T, kAddNorm>(x, a, keep, rows, rows_per_sample, C, geo, gamma, beta, eps, y, z, mean, rstd, stream)
+    return MSDA_GLUE_PICK(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
-int swin_glue_add_norm_backward(bool bf16, const float *grad_y, const void *grad_z, const float *y, const void *keep,
+int swin_glue_add_norm_backward(bool sbf16, bool bf16, const void *grad_y, const void *grad_z, const void *y, const void *keep,
                                 const float *gamma, const float *mean, const float *rstd, long long rows,
-                                long long rows_per_sample, int C, float *grad_x, void *grad_a, float *grad_gamma,
+                                long long rows_per_sample, int C, void *grad_x, void *grad_a, float *grad_gamma,
                                 float *grad_beta, void *workspace, unsigned long long workspace_bytes, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_add_norm_backward_bf16" : "msda_swin_glue_add_norm_backward_f32";
-    // grad_a may be null only where it would equal grad_x bit for bit: fp32 without a keep vector
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("add_norm_backward"));
+    // grad_a may be null only where it would equal grad_x bit for bit: a branch of the stream's type without a keep vector
     if (int rc = glue_check(who, rows, rows_per_sample, C,
-                            {{grad_y, 16, false}, {grad_z, row_align(bf16), false}, {y, 16, false},
+                            {{grad_y, row_align(sbf16), false}, {grad_z, row_align(bf16), false}, {y, row_align(sbf16), false},
                              {keep, elem_align(bf16), true}, {gamma, 16, false}, {mean, 4, false}, {rstd, 4, false},
-                             {grad_x, 16, false}, {grad_a, row_align(bf16), !bf16 && !keep}, {grad_gamma, 4, false},
-                             {grad_beta, 4, false}}))
+                             {grad_x, row_align(sbf16), false}, {grad_a, row_align(bf16), sbf16 == bf16 && !keep},
+                             {grad_gamma, 4, false}, {grad_beta, 4, false}}))
         return rc;
     if (int rc = glue_check_workspace(who, rows, C, workspace, workspace_bytes)) return rc;
     const MergeGeo geo{};
-    return bf16 ? glue_bwd<uint16_t, kAddNorm>(grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C, geo, grad_x,
-                                               grad_a, grad_gamma, grad_beta, (float *)workspace, stream)
-                : glue_bwd<float, kAddNorm>(grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C, geo, grad_x,
-                                            grad_a, grad_gamma, grad_beta, (float *)workspace, stream);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    glue_bwd<X, T, kAddNorm>(grad_y, grad_z, y, keep, gamma, mean, rstd, rows, rows_per_sample, C, geo, grad_x, grad_a,          \
+                             grad_gamma, grad_beta, (float *)workspace, stream)
+    return MSDA_GLUE_PICK(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
-int swin_glue_add_forward(bool bf16, const float *x, const void *a, const void *keep, long long rows, long long rows_per_sample,
-                          int C, float *y, hipStream_t stream)
+int swin_glue_add_forward(bool sbf16, bool bf16, const void *x, const void *a, const void *keep, long long rows,
+                          long long rows_per_sample, int C, void *y, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_add_forward_bf16" : "msda_swin_glue_add_forward_f32";
-    if (int rc = glue_check(who, rows, rows_per_sample, C,
-                            {{x, 16, false}, {a, row_align(bf16), false}, {keep, elem_align(bf16), true}, {y, 16, false}}))
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("add_forward"));
+    if (int rc = glue_check(who, rows, rows_per_sample, C, {{x, row_align(sbf16), false}, {a, row_align(bf16), false},
+                                                           {keep, elem_align(bf16), true}, {y, row_align(sbf16), false}}))
         return rc;
     if (rows == 0) return MSDA_OK;
     const dim3 grid((unsigned)((rows + kGlWaves - 1) / kGlWaves)), block(kGlBlock);
-    if (bf16)
-        hipLaunchKernelGGL(glue_add_fwd_kernel<uint16_t>, grid, block, 0, stream, x, (const uint16_t *)a, (const uint16_t *)keep,
-                           rows, rows_per_sample, C, y);
-    else
-        hipLaunchKernelGGL(glue_add_fwd_kernel<float>, grid, block, 0, stream, x, (const float *)a, (const float *)keep, rows,
-                           rows_per_sample, C, y);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    hipLaunchKernelGGL((glue_add_fwd_kernel<X, T>), grid, block, 0, stream, (const X *)x, (const T *)a, (const T *)keep, rows,   \
+                       rows_per_sample, C, (X *)y)
+    if (sbf16) MSDA_GLUE_CALL(uint16_t, uint16_t); else if (bf16) MSDA_GLUE_CALL(float, uint16_t); else MSDA_GLUE_CALL(float, float);
+#undef MSDA_GLUE_CALL
     return check_launch("msda swin glue add forward");
 }
 
-int swin_glue_add_backward(bool bf16, const float *grad_y, const void *keep, long long rows, long long rows_per_sample, int C,
-                           void *grad_a, hipStream_t stream)
+int swin_glue_add_backward(bool sbf16, bool bf16, const void *grad_y, const void *keep, long long rows,
+                           long long rows_per_sample, int C, void *grad_a, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_add_backward_bf16" : "msda_swin_glue_add_backward_f32";
-    if (int rc = glue_check(who, rows, rows_per_sample, C,
-                            {{grad_y, 16, false}, {keep, elem_align(bf16), true}, {grad_a, row_align(bf16), false}}))
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("add_backward"));
+    // a bf16 stream without keep: grad_a is grad_y itself, there is nothing to compute
+    if (int rc = glue_check(who, rows, rows_per_sample, C, {{grad_y, row_align(sbf16), false}, {keep, elem_align(bf16), !sbf16},
+                                                           {grad_a, row_align(bf16), false}}))
         return rc;
     if (rows == 0) return MSDA_OK;
     const dim3 grid((unsigned)((rows + kGlWaves - 1) / kGlWaves)), block(kGlBlock);
-    if (bf16)
-        hipLaunchKernelGGL(glue_add_bwd_kernel<uint16_t>, grid, block, 0, stream, grad_y, (const uint16_t *)keep, rows,
-                           rows_per_sample, C, (uint16_t *)grad_a);
-    else
-        hipLaunchKernelGGL(glue_add_bwd_kernel<float>, grid, block, 0, stream, grad_y, (const float *)keep, rows, rows_per_sample,
-                           C, (float *)grad_a);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    hipLaunchKernelGGL((glue_add_bwd_kernel<X, T>), grid, block, 0, stream, (const X *)grad_y, (const T *)keep, rows,            \
+                       rows_per_sample, C, (T *)grad_a)
+    if (sbf16) MSDA_GLUE_CALL(uint16_t, uint16_t); else if (bf16) MSDA_GLUE_CALL(float, uint16_t); else MSDA_GLUE_CALL(float, float);
+#undef MSDA_GLUE_CALL
     return check_launch("msda swin glue add backward");
 }
 
-int swin_glue_merge_norm_forward(bool bf16, const float *x, int B, int H, int W, int C, const float *gamma, const float *beta,
-                                 float eps, void *z, float *mean, float *rstd, hipStream_t stream)
+int swin_glue_merge_norm_forward(bool sbf16, bool bf16, const void *x, int B, int H, int W, int C, const float *gamma,
+                                 const float *beta, float eps, void *z, float *mean, float *rstd, hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_merge_norm_forward_bf16" : "msda_swin_glue_merge_norm_forward_f32";
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("merge_norm_forward"));
     if (int rc = merge_check(who, B, H, W, C)) return rc;
     const MergeGeo geo = merge_geo(H, W, C);
     const long long rows = (long long)B * geo.H2 * geo.W2;
-    if (int rc = glue_check(who, rows, 1, 4 * C, {{x, 16, false}, {gamma, 16, false}, {beta, 16, false},
+    if (int rc = glue_check(who, rows, 1, 4 * C, {{x, row_align(sbf16), false}, {gamma, 16, false}, {beta, 16, false},
                                                  {z, row_align(bf16), false}, {mean, 4, false}, {rstd, 4, false}}))
         return rc;
-    return bf16 ? glue_fwd<uint16_t, kMerge>(x, nullptr, nullptr, rows, 1, 4 * C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream)
-                : glue_fwd<float, kMerge>(x, nullptr, nullptr, rows, 1, 4 * C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    glue_fwd<X, T, kMerge>(x, nullptr, nullptr, rows, 1, 4 * C, geo, gamma, beta, eps, nullptr, z, mean, rstd, stream)
+    return MSDA_GLUE_PICK(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
-int swin_glue_merge_norm_backward(bool bf16, const void *grad_z, const float *x, const float *gamma, const float *mean,
-                                  const float *rstd, int B, int H, int W, int C, float *grad_x, float *grad_gamma,
-                                  float *grad_beta, void *workspace, unsigned long long workspace_bytes, hipStream_t stream)
+int swin_glue_merge_norm_backward(bool sbf16, bool bf16, const void *grad_z, const void *x, const float *gamma,
+                                  const float *mean, const float *rstd, int B, int H, int W, int C, void *grad_x,
+                                  float *grad_gamma, float *grad_beta, void *workspace, unsigned long long workspace_bytes,
+                                  hipStream_t stream)
 {
-    const char *who = bf16 ? "msda_swin_glue_merge_norm_backward_bf16" : "msda_swin_glue_merge_norm_backward_f32";
+    const char *who = entry_name(sbf16, bf16, MSDA_GLUE_NAMES("merge_norm_backward"));
     if (int rc = merge_check(who, B, H, W, C)) return rc;
     const MergeGeo geo = merge_geo(H, W, C);
     const long long rows = (long long)B * geo.H2 * geo.W2;
-    if (int rc = glue_check(who, rows, 1, 4 * C, {{grad_z, row_align(bf16), false}, {x, 16, false}, {gamma, 16, false},
-                                                 {mean, 4, false}, {rstd, 4, false}, {grad_x, 16, false},
-                                                 {grad_gamma, 4, false}, {grad_beta, 4, false}}))
+    if (int rc = glue_check(who, rows, 1, 4 * C, {{grad_z, row_align(bf16), false}, {x, row_align(sbf16), false},
+                                                 {gamma, 16, false}, {mean, 4, false}, {rstd, 4, false},
+                                                 {grad_x, row_align(sbf16), false}, {grad_gamma, 4, false},
+                                                 {grad_beta, 4, false}}))
         return rc;
     if (int rc = glue_check_workspace(who, rows, 4 * C, workspace, workspace_bytes)) return rc;
-    return bf16 ? glue_bwd<uint16_t, kMerge>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, 4 * C, geo, grad_x, nullptr,
-                                             grad_gamma, grad_beta, (float *)workspace, stream)
-                : glue_bwd<float, kMerge>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, 4 * C, geo, grad_x, nullptr,
-                                          grad_gamma, grad_beta, (float *)workspace, stream);
+#define MSDA_GLUE_CALL(X, T)                                                                                                     \
+    glue_bwd<X, T, kMerge>(nullptr, grad_z, x, nullptr, gamma, mean, rstd, rows, 1, 4 * C, geo, grad_x, nullptr, grad_gamma,     \
+                           grad_beta, (float *)workspace, stream)
+    return MSDA_GLUE_PICK(sbf16, bf16, MSDA_GLUE_CALL);
+#undef MSDA_GLUE_CALL
 }
 
 }  // namespace msda

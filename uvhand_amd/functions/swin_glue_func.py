@@ -4,6 +4,11 @@ and of PatchMerging (:263-287: pad, 2 x 2 gather, concatenation, norm) as four a
 ``MSDA_SWIN_GLUE=1`` switches them on (opt-in, read at call time; unset, ``""`` and ``"0"`` mean off).  The residual stream is
 fp32; T, the type of the normalised rows and of the branch, is bfloat16 under bf16 autocast and float32 outside autocast.
 
+``MSDA_SWIN_GLUE_BF16=1`` (opt-in as well, read at call time, only with ``MSDA_SWIN_GLUE`` on) lets a bfloat16 residual stream
+under bf16 autocast take the same four nodes: from the first PatchMerging on, whose reduction Linear returns bfloat16 there.
+y, grad_x and the rows the nodes save are then bfloat16, rounded where torch's bf16 arithmetic rounds (include/msda.h: y is
+rounded before it is normalised; grad_x is rounded twice, by the cast's backward and by autograd's accumulation).
+
   ``norm_rows(x, norm)``                        LN(x) as T (``fp32_out=True``: float32 under autocast too, what F.layer_norm gives)
   ``add_norm_rows(x, branch, keep, norm)``      (y, z): y = x + branch * keep in one launch with z = LN(y) as T
   ``add_rows(x, branch, keep)``                 y = x + branch * keep
@@ -14,8 +19,9 @@ the Philox stream is consumed as in the composition and checkpoint recomputation
 the branch's type before the fp32 add, as torch does, so y is bit for bit ``x + drop_path(branch)``; the backward rounds
 where torch's autograd rounds.  No kernel generates random numbers.
 
-Everything else runs exactly the torch expressions: CPU tensors, fp16 autocast, a non-fp32 x, a width the kernels do not take
-(C % 4 != 0 or C > 3072), a norm that is not an affine 1-d nn.LayerNorm, a branch of another type, and the knob off."""
+Everything else runs exactly the torch expressions: CPU tensors, fp16 autocast, an x that is neither fp32 nor (second knob, bf16
+autocast) bfloat16, bfloat16 rows outside autocast, a width the kernels do not take (C % 4 != 0 or C > 3072), a norm that is not
+an affine 1-d nn.LayerNorm, a branch of another type, and the knob off."""
 import os
 
 import torch
@@ -32,13 +38,19 @@ def _glue_enabled():
     return os.environ.get("MSDA_SWIN_GLUE", "0") not in ("", "0")       # opt-in (default off)
 
 
+def _glue_bf16_stream_enabled():
+    return os.environ.get("MSDA_SWIN_GLUE_BF16", "0") not in ("", "0")  # opt-in (default off)
+
+
 def glue_route(device, dtype, C):
-    """True when rows of this device, type and width take the HIP glue: the knob on, CUDA, fp32 rows, C % 4 == 0 and C <= 3072,
-    and either no autocast or bf16 autocast."""
-    if not (_glue_enabled() and device.type == "cuda" and dtype == torch.float32
-            and C % 4 == 0 and 0 < C <= _native.SWIN_GLUE_MAX_WIDTH):
+    """True when rows of this device, type and width take the HIP glue: the knob on, CUDA, C % 4 == 0 and C <= 3072, and either
+    fp32 rows with no autocast or bf16 autocast, or bfloat16 rows under bf16 autocast with MSDA_SWIN_GLUE_BF16 on as well."""
+    if not (_glue_enabled() and device.type == "cuda" and C % 4 == 0 and 0 < C <= _native.SWIN_GLUE_MAX_WIDTH):
         return False
-    return not torch.is_autocast_enabled() or _autocast_dtype() == torch.bfloat16
+    bf16_autocast = torch.is_autocast_enabled() and _autocast_dtype() == torch.bfloat16
+    if dtype == torch.float32:
+        return not torch.is_autocast_enabled() or bf16_autocast
+    return dtype == torch.bfloat16 and bf16_autocast and _glue_bf16_stream_enabled()
 
 
 def _branch_dtype():
@@ -113,14 +125,14 @@ class _AddNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, keep, rows_per_sample, weight, bias, eps):
         y, z, mean, rstd = _native.swin_glue_add_norm_forward(x, a, keep, rows_per_sample, weight, bias, eps)
-        ctx.rows_per_sample, ctx.branch_dtype = rows_per_sample, a.dtype
+        ctx.rows_per_sample, ctx.branch_dtype, ctx.stream_dtype = rows_per_sample, a.dtype, x.dtype
         ctx.save_for_backward(y, keep, weight, mean, rstd)
         return y, z
 
     @staticmethod
     def backward(ctx, grad_y, grad_z):
         y, keep, weight, mean, rstd = ctx.saved_tensors
-        gx, ga, gw, gb = _native.swin_glue_add_norm_backward(_grad(grad_y, torch.float32), _grad(grad_z, ctx.branch_dtype), y,
+        gx, ga, gw, gb = _native.swin_glue_add_norm_backward(_grad(grad_y, ctx.stream_dtype), _grad(grad_z, ctx.branch_dtype), y,
                                                              keep, ctx.rows_per_sample, weight, mean, rstd)
         return gx, ga, None, None, gw, gb, None
 
@@ -128,14 +140,14 @@ class _AddNormFunction(torch.autograd.Function):
 class _AddFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, keep, rows_per_sample):
-        ctx.rows_per_sample, ctx.branch_dtype = rows_per_sample, a.dtype
+        ctx.rows_per_sample, ctx.branch_dtype, ctx.stream_dtype = rows_per_sample, a.dtype, x.dtype
         ctx.save_for_backward(keep)
         return _native.swin_glue_add_forward(x, a, keep, rows_per_sample)
 
     @staticmethod
     def backward(ctx, grad_y):
         keep, = ctx.saved_tensors
-        grad_y = _grad(grad_y, torch.float32)
+        grad_y = _grad(grad_y, ctx.stream_dtype)
         return grad_y, _native.swin_glue_add_backward(grad_y, keep, ctx.rows_per_sample, ctx.branch_dtype), None, None
 
 
@@ -155,12 +167,13 @@ class _MergeNormFunction(torch.autograd.Function):
 
 
 def norm_rows(x, norm, fp32_out=False):
-    """norm(x) over the last dimension: one launch, as T (fp32_out: float32 whatever the autocast state)."""
+    """norm(x) over the last dimension of fp32 or (glue_route) bfloat16 rows: one launch, as T (fp32_out: float32 whatever the
+    autocast state)."""
     C = x.shape[-1] if x.dim() else 0
     if not (glue_route(x.device, x.dtype, C) and affine_layernorm(norm, C, x.device)):
         return norm(x)
     out_dtype = torch.float32 if fp32_out else _branch_dtype()
-    x = _rows(x, 16)
+    x = _rows(x, _align(x.dtype))
     if not _needs_grad(x, norm.weight, norm.bias):
         return _native.swin_glue_norm_forward(x, norm.weight, norm.bias, norm.eps, out_dtype)[0]
     return _NormFunction.apply(x, norm.weight, norm.bias, norm.eps, out_dtype)
@@ -177,11 +190,11 @@ def _add_route(x, branch, keep):
 
 
 def add_norm_rows(x, branch, keep, norm):
-    """(y, z) = (x + branch * keep, norm(y)): one launch; y float32, z as T."""
+    """(y, z) = (x + branch * keep, norm(y)): one launch; y of x's type, z as T."""
     if not (_add_route(x, branch, keep) and affine_layernorm(norm, x.shape[-1], x.device)):
         y = _composition(x, branch, keep)
         return y, norm(y)
-    x, branch = _rows(x, 16), _rows(branch, _align(branch.dtype))
+    x, branch = _rows(x, _align(x.dtype)), _rows(branch, _align(branch.dtype))
     keep = keep.reshape(-1) if keep is not None else None
     rps = _rows_per_sample(branch)
     if not _needs_grad(x, branch, norm.weight, norm.bias):
@@ -190,10 +203,10 @@ def add_norm_rows(x, branch, keep, norm):
 
 
 def add_rows(x, branch, keep):
-    """y = x + branch * keep: one launch, float32."""
+    """y = x + branch * keep: one launch, of x's type."""
     if not _add_route(x, branch, keep):
         return _composition(x, branch, keep)
-    x, branch = _rows(x, 16), _rows(branch, _align(branch.dtype))
+    x, branch = _rows(x, _align(x.dtype)), _rows(branch, _align(branch.dtype))
     keep = keep.reshape(-1) if keep is not None else None
     rps = _rows_per_sample(branch)
     if not _needs_grad(x, branch):
@@ -221,7 +234,7 @@ def merge_norm(x, H, W, norm):
     B, L, C = x.shape
     if not (L == H * W and glue_route(x.device, x.dtype, 4 * C) and affine_layernorm(norm, 4 * C, x.device)):
         return _merge_composition(x, H, W, norm)
-    x = _rows(x, 16).view(B, H, W, C)
+    x = _rows(x, _align(x.dtype)).view(B, H, W, C)
     out_dtype = _branch_dtype()
     if not _needs_grad(x, norm.weight, norm.bias):
         return _native.swin_glue_merge_norm_forward(x, norm.weight, norm.bias, norm.eps, out_dtype)[0]

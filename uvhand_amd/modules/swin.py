@@ -14,7 +14,8 @@ handed a mask tensor of its caller's takes the composition with that mask.  The 
 
 ``MSDA_SWIN_GLUE=1`` (opt-in, read at call time, default off; ``functions/swin_glue_func.py``) moves the memory-bound glue of
 such a block to HIP as well: norm1, shortcut + drop_path with norm2 in one launch, and the closing x + drop_path; PatchMerging's
-pad / gather / concatenation / norm in one launch; the per-stage output norms.  The drop-path tensor stays torch's own draw."""
+pad / gather / concatenation / norm in one launch; the per-stage output norms.  The drop-path tensor stays torch's own draw.
+With ``MSDA_SWIN_GLUE_BF16=1`` as well, the bfloat16 residual stream of stages 1 to 3 under bf16 autocast takes the same nodes."""
 import math
 from typing import List
 

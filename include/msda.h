@@ -1064,6 +1064,43 @@ int msda_smooth_loss_backward_f32(const int *dims, float fps, const float *const
                                   const float *grad_losses, int acc_grad, float *const *grads, const void *workspace,
                                   unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- ARCTIC target preparation: rigid fit, camera translation and distance fields (csrc/msda_pre_process.hip) -----------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * Target fit: what arctic_tools/src/callbacks/process/process_arctic.py process_data (38-124) computes between its object and
+ * MANO forwards and its vertex sums: common/transforms.py batch_solve_rigid_tf and rigid_tf_torch_batch (both hands), the
+ * Tr0 / Tl0 means, common/data_utils.py unormalize_kp2d, common/camera.py estimate_translation_k (use_all_joints, pad_2d:
+ * unit weights) over estimate_translation_k_np, and the three perspective_to_weak_perspective_torch.  B frames (>= 0), NK
+ * keypoints (3 .. 64), J hand joints (1 .. 32).  inputs: HOST array of 8 device pointers, fp32 contiguous: object.kp3d.full.b
+ * [B, NK, 3], the posed object's bottom kp3d without translation [B, NK, 3], object.kp2d.norm.b [B, NK, 2], intrinsics
+ * [B, 3, 3], mano.j3d.full.r, .l [B, J, 3], the MANO joints r, l without translation [B, J, 3].  img_res: process_data's 224.
+ * outputs: HOST array of 12 device pointers: R0 [B, 3, 3], T0 [B, 3], transl [B, 3], mano.j3d.cam.r, .l [B, J, 3], mano.cam_t.r,
+ * .l [B, 3], mano.cam_t.wp.r, .l and object.cam_t.wp [B, 3], and the vertex offsets Tr0 + transl, Tl0 + transl [B, 3].
+ * status [B] int32, bits: 1 the fit had a negative determinant (the reference raises; the corrected rotation of Arun's
+ * method is returned), 2 the rotation is not unique (second singular value of H below 1e-6 of the first), 4 a non-finite
+ * input (the frame's outputs are NaN, no other bit), 8 a singular normal matrix (transl and what depends on it are NaN).  A
+ * rank-deficient H (third singular value below 1e-12 of the first: planar keypoints) has no orientation and never sets bit 1.
+ * The 3 x 3 algebra runs in fp64 in a fixed order and every output is rounded to fp32 once; no frame influences another.
+ *   msda_pre_fit_supported  1 when the kernel takes this geometry.
+ *   msda_pre_fit_f32        one launch, one wavefront per frame (none for B = 0).
+ *
+ * Distance fields: arctic_tools/src/utils/interfield.py compute_dist_mano_to_obj and compute_dist_obj_to_mano as
+ * src/callbacks/process/process_generic.py prepare_interfield (97-138) calls them, i.e. pytorch3d knn_points with K = 1 and
+ * lengths on the object.  hand_r, hand_l [B, NV, 3], obj [B, L, 3] fp32, v_len [B] int64 (device, clamped to 0 .. L).  dists,
+ * idx: HOST arrays of 4 device pointers in the order ro, lo [B, NV], or, ol [B, L]; fp32 and int64.  d = dx dx + dy dy + dz dz
+ * summed in that order; the minimum moves on strict < only (lowest index on a tie, a NaN distance never wins; no finite
+ * candidate: +inf, index 0); the value is clamp(sqrt(d), dist_min, dist_max).  Object rows at or beyond v_len are never
+ * candidates; as sources they get 0 before the clamp and index 0, and so does every hand vertex of a frame with v_len = 0.
+ *   msda_dist_fields_supported  1 when the kernel takes this geometry: B >= 0, NV 1 .. 1024, L 1 .. 65536.
+ *   msda_dist_fields_f32        one launch for the four fields (none for B = 0).
+ * Forward only.  No atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+int msda_pre_fit_supported(int B, int NK, int J);
+int msda_pre_fit_f32(int B, int NK, int J, float img_res, const float *const *inputs, float *const *outputs, int *status,
+                     msda_stream_t stream);
+int msda_dist_fields_supported(int B, int NV, int L);
+int msda_dist_fields_f32(int B, int NV, int L, const float *hand_r, const float *hand_l, const float *obj, const long long *v_len,
+                         float dist_min, float dist_max, float *const *dists, long long *const *idx, msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -19,8 +19,10 @@ _ARCTIC_EVAL = ("get_NN", "nn_many", "make_output", "post_process_arctic_output"
                 "arctic_metrics", "ArcticEvaluator")
 # the SmoothNet criterion's losses (uvhand_amd/smooth_loss.py), resolved the same way
 _SMOOTH_LOSS = ("compute_smoothnet_loss", "smooth_loss_reference", "eval_acc_pose", "compute_error_accel")
+# the step's first call, arctic_pre_process (uvhand_amd/pre_process.py), resolved the same way
+_PRE_PROCESS = ("arctic_pre_process", "fit_targets", "distance_fields")
 __all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"] + list(_ARCTIC_EVAL) + list(_SMOOTH_LOSS) \
-    + ["SmoothCriterion"]
+    + ["SmoothCriterion"] + list(_PRE_PROCESS)
 
 
 def __getattr__(name):
@@ -30,6 +32,9 @@ def __getattr__(name):
     if name in _SMOOTH_LOSS:
         from . import smooth_loss
         return getattr(smooth_loss, name)
+    if name in _PRE_PROCESS:
+        from . import pre_process
+        return getattr(pre_process, name)
     if name == "SmoothCriterion":
         from .modules import SmoothCriterion
         return SmoothCriterion

@@ -190,6 +190,11 @@ SIGNATURES = {
     "msda_smooth_loss_workspace_bytes": "U iiii",
     "msda_smooth_loss_forward_f32": "i p f pp pp p U p",
     "msda_smooth_loss_backward_f32": "i p f pp p i p p U p",
+    # ARCTIC target preparation: rigid fit, camera translation and distance fields
+    "msda_pre_fit_supported": "i iii",
+    "msda_pre_fit_f32": "i iii f pp p p",
+    "msda_dist_fields_supported": "i iii",
+    "msda_dist_fields_f32": "i iii pppp ff pp p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -2141,3 +2146,51 @@ def smooth_loss_backward(dims, fps, floats, longs, grad_losses, ws, acc_grad):
     _launch(dev, "msda_smooth_loss_backward_f32", "smooth_loss_backward", _int_array(dims), float(fps), _ptr_array(floats),
             _ptr_array(longs), grad_losses.data_ptr(), 1 if acc_grad else 0, _opt_ptr_array(grads), ws.data_ptr(), ws.numel() * 4)
     return grads
+
+
+# ---- ARCTIC target preparation (msda_pre_process.hip) ---------------------------------------------------------------------------
+PRE_FIT_OUTPUTS = ("R0", "T0", "transl", "j3d_cam_r", "j3d_cam_l", "cam_t_r", "cam_t_l", "cam_t_wp_r", "cam_t_wp_l", "cam_t_wp_o",
+                   "off_r", "off_l")
+
+
+def pre_fit_supported(B, NK, J):
+    return bool((_lib or load()).msda_pre_fit_supported(int(B), int(NK), int(J)))
+
+
+def dist_fields_supported(B, NV, L):
+    return bool((_lib or load()).msda_dist_fields_supported(int(B), int(NV), int(L)))
+
+
+def pre_fit(kp_full, kp_cano, kp2d_norm, K, j_full_r, j_full_l, j_cano_r, j_cano_l, img_res):
+    """msda_pre_fit_f32.  Returns ({name: tensor} in PRE_FIT_OUTPUTS' order, status [B] int32).  One launch, no host sync."""
+    ins = [kp_full, kp_cano, kp2d_norm, K, j_full_r, j_full_l, j_cano_r, j_cano_l]
+    dev = kp_full.device
+    _nn_check("pre_fit", dev, ins)
+    if any(t.dtype != torch.float32 for t in ins):
+        raise RuntimeError("pre_fit: expected contiguous fp32 CUDA tensors on one device")
+    B, NK, _ = kp_full.shape
+    J = j_full_r.shape[1]
+    want = [(B, NK, 3), (B, NK, 3), (B, NK, 2), (B, 3, 3)] + [(B, J, 3)] * 4
+    if any(tuple(t.shape) != s for t, s in zip(ins, want)):
+        raise RuntimeError("pre_fit: expected kp [B, NK, 3], kp2d [B, NK, 2], K [B, 3, 3] and joints [B, J, 3]")
+    shapes = [(B, 3, 3), (B, 3), (B, 3), (B, J, 3), (B, J, 3)] + [(B, 3)] * 7
+    outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    _launch(dev, "msda_pre_fit_f32", "pre_fit", B, NK, J, float(img_res), _ptr_array(ins), _ptr_array(outs), status.data_ptr())
+    return dict(zip(PRE_FIT_OUTPUTS, outs)), status
+
+
+def dist_fields(hand_r, hand_l, obj, v_len, dist_min, dist_max):
+    """msda_dist_fields_f32.  Returns (dists, idx): four tensors each, in the order ro, lo [B, NV], or, ol [B, L].  One launch."""
+    dev = hand_r.device
+    _nn_check("dist_fields", dev, [hand_r, hand_l, obj, v_len])
+    B, NV, _ = hand_r.shape
+    L = obj.shape[1]
+    if any(t.dtype != torch.float32 for t in (hand_r, hand_l, obj)) or v_len.dtype != torch.int64 \
+            or tuple(hand_l.shape) != (B, NV, 3) or tuple(obj.shape) != (B, L, 3) or tuple(v_len.shape) != (B,):
+        raise RuntimeError("dist_fields: expected fp32 hands [B, NV, 3], obj [B, L, 3] and int64 v_len [B]")
+    dists = [torch.empty(B, n, dtype=torch.float32, device=dev) for n in (NV, NV, L, L)]
+    idx = [torch.empty(B, n, dtype=torch.int64, device=dev) for n in (NV, NV, L, L)]
+    _launch(dev, "msda_dist_fields_f32", "dist_fields", B, NV, L, hand_r.data_ptr(), hand_l.data_ptr(), obj.data_ptr(),
+            v_len.data_ptr(), float(dist_min), float(dist_max), _ptr_array(dists), _ptr_array(idx))
+    return dists, idx

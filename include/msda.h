@@ -1101,6 +1101,59 @@ int msda_dist_fields_supported(int B, int NV, int L);
 int msda_dist_fields_f32(int B, int NV, int L, const float *hand_r, const float *hand_l, const float *obj, const long long *v_len,
                          float dist_min, float dist_max, float *const *dists, long long *const *idx, msda_stream_t stream);
 
+/* ---- The tail of the training step: gradient norm, clip and AdamW as multi-tensor launches (csrc/msda_optim.hip) ---------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * What engine.py:644-648 runs after losses.backward(): torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) (or, for
+ * max_norm <= 0, util/misc.py's get_total_grad_norm: the norm alone) and optimizer.step() of util/settings.py:434's
+ * torch.optim.AdamW over three parameter groups.  fp32 only.  The number of launches does not grow with the number of tensors:
+ * every tensor is cut into chunks of msda_optim_chunk_elems() elements, one workgroup per chunk, a chunk never spans two
+ * tensors.  The tensors are described by DEVICE arrays that the caller owns, one entry per tensor: g, p, exp_avg, exp_avg_sq
+ * (device pointers to contiguous fp32 data that need only be 4-byte aligned: a chunk moves 16-byte vectors when all its bases
+ * are 16-byte aligned and single elements otherwise, with the same element-to-thread assignment, so no result depends on the
+ * alignment), numel (int64), chunk_start (int64, n_tensors + 1 entries, as msda_optim_chunks lays them out), group (int32, the
+ * tensor's parameter group, clamped to 0 .. n_groups - 1) and step_offset (int64).  An empty tensor owns no chunk.
+ *   msda_optim_supported       1 for 0 .. 2^20 tensors in 1 .. 8 groups.
+ *   msda_optim_chunk_elems     elements of a chunk.
+ *   msda_optim_chunks          host logic: fills the HOST array chunk_start [n_tensors + 1] from the HOST array numel
+ *       (chunk_start[i + 1] - chunk_start[i] = ceil(numel[i] / chunk)) and returns chunk_start[n_tensors], the grid size of the
+ *       three chunked launches; -1 (message in msda_last_error) for a null pointer, a negative count or numel, a numel beyond
+ *       2^46 or more than 2^31 - 1 chunks.
+ *   msda_grad_sumsq_f32        one launch: partials [n_chunks] fp32, the sum of squares of each chunk; a thread adds its
+ *       elements in index order, the workgroup its threads in a fixed tree order.
+ *   msda_grad_norm_finish_f32  one launch, one workgroup: adds the partials in a fixed order (fp64, rounded once) and writes
+ *       out[0] = total_norm = sqrt of the sum and out[1] = the clip coefficient exactly as torch forms it in fp32,
+ *       clamp(reciprocal(total_norm + 1e-6) * max_norm, max = 1): an infinite norm gives 0, a NaN norm gives NaN.
+ *       max_norm <= 0 writes the coefficient 1 (get_total_grad_norm's branch).  n_chunks = 0 launches nothing and leaves out
+ *       alone (the norm of nothing is 0).
+ *   msda_grad_scale_f32        one launch: g *= *coef in place (coef: device, e.g. out + 1): clip_grad_norm_ on its own.
+ *   msda_adamw_step_f32        one launch.  Per element, in torch's operation order (torch/optim/adamw.py, the single-tensor
+ *       form): g' = g * *coef (coef: device pointer; NULL: no clipping; g itself is never written), p *= 1 - lr wd,
+ *       m += (g' - m) (1 - b1), v = v b2 + g' g' (1 - b2), p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), with
+ *       bc = 1 - beta^t evaluated in fp64 (fp32 pow loses four digits of 1 - 0.999^1) and lr / bc1, sqrt(bc2), 1 - lr wd,
+ *       1 - beta rounded to fp32 once, as torch's Python scalars are.  t = global_step - step_offset[tensor] (at least 1):
+ *       torch skips a parameter whose .grad is None and its step does not advance, so t is per tensor.  lr, weight_decay,
+ *       beta1, beta2, eps: HOST arrays of n_groups doubles, carried by value in the kernel arguments.  Correctly rounded
+ *       sqrt and division, no fast intrinsic.
+ * A clipped step is sumsq + finish + step = 3 launches, an unclipped step 1; n_tensors = 0 or n_chunks = 0 launches nothing.
+ * No float atomics, fixed summation order: bitwise reproducible.  No allocation, no synchronisation.  Argument errors
+ * (MSDA_ERR_ARGUMENT before any launch, msda_launch_count unchanged): a null table with something to launch, a negative or
+ * too large count, n_groups outside 1 .. 8, a beta outside [0, 1), a non-finite lr, eps or weight_decay, a NaN max_norm,
+ * global_step < 1. */
+int msda_optim_supported(long long n_tensors, int n_groups);
+int msda_optim_chunk_elems(void);
+long long msda_optim_chunks(int n_tensors, const long long *numel, long long *chunk_start);
+int msda_grad_sumsq_f32(int n_tensors, long long n_chunks, const float *const *g, const long long *numel,
+                        const long long *chunk_start, float *partials, msda_stream_t stream);
+int msda_grad_norm_finish_f32(long long n_chunks, const float *partials, float max_norm, float *out, msda_stream_t stream);
+int msda_grad_scale_f32(int n_tensors, long long n_chunks, float *const *g, const long long *numel, const long long *chunk_start,
+                        const float *coef, msda_stream_t stream);
+int msda_adamw_step_f32(int n_tensors, long long n_chunks, float *const *p, const float *const *g, float *const *exp_avg,
+                        float *const *exp_avg_sq, const long long *numel, const long long *chunk_start, const int *group,
+                        const long long *step_offset, int n_groups, const double *lr, const double *weight_decay,
+                        const double *beta1, const double *beta2, const double *eps, long long global_step, const float *coef,
+                        msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -21,8 +21,10 @@ _ARCTIC_EVAL = ("get_NN", "nn_many", "make_output", "post_process_arctic_output"
 _SMOOTH_LOSS = ("compute_smoothnet_loss", "smooth_loss_reference", "eval_acc_pose", "compute_error_accel")
 # the step's first call, arctic_pre_process (uvhand_amd/pre_process.py), resolved the same way
 _PRE_PROCESS = ("arctic_pre_process", "fit_targets", "distance_fields")
+# the tail of the step, clip_grad_norm_ and AdamW (uvhand_amd/optim.py), resolved the same way
+_OPTIM = ("AdamW", "clip_grad_norm_", "grad_norm")
 __all__ = ["MSDeformAttn", "MSDeformAttnFunction", "graphed", "set_exact_nonfinite"] + list(_ARCTIC_EVAL) + list(_SMOOTH_LOSS) \
-    + ["SmoothCriterion"] + list(_PRE_PROCESS)
+    + ["SmoothCriterion"] + list(_PRE_PROCESS) + list(_OPTIM)
 
 
 def __getattr__(name):
@@ -35,6 +37,9 @@ def __getattr__(name):
     if name in _PRE_PROCESS:
         from . import pre_process
         return getattr(pre_process, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     if name == "SmoothCriterion":
         from .modules import SmoothCriterion
         return SmoothCriterion

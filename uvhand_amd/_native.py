@@ -195,6 +195,14 @@ SIGNATURES = {
     "msda_pre_fit_f32": "i iii f pp p p",
     "msda_dist_fields_supported": "i iii",
     "msda_dist_fields_f32": "i iii pppp ff pp p",
+    # the tail of the step: gradient norm, clip and AdamW as multi-tensor launches
+    "msda_optim_supported": "i li",
+    "msda_optim_chunk_elems": "i",
+    "msda_optim_chunks": "l ipp",
+    "msda_grad_sumsq_f32": "i il ppp p p",
+    "msda_grad_norm_finish_f32": "i l p f p p",
+    "msda_grad_scale_f32": "i il ppp p p",
+    "msda_adamw_step_f32": "i il pppp pp pp i ppppp l p p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -2194,3 +2202,51 @@ def dist_fields(hand_r, hand_l, obj, v_len, dist_min, dist_max):
     _launch(dev, "msda_dist_fields_f32", "dist_fields", B, NV, L, hand_r.data_ptr(), hand_l.data_ptr(), obj.data_ptr(),
             v_len.data_ptr(), float(dist_min), float(dist_max), _ptr_array(dists), _ptr_array(idx))
     return dists, idx
+
+
+# ---- the tail of the step: gradient norm, clip and AdamW as multi-tensor launches (csrc/msda_optim.hip) ----
+OPTIM_MAX_GROUPS = 8
+
+
+def optim_supported(n_tensors, n_groups):
+    return bool((_lib or load()).msda_optim_supported(int(n_tensors), int(n_groups)))
+
+
+def optim_chunk_elems():
+    return int((_lib or load()).msda_optim_chunk_elems())
+
+
+def optim_chunks(numels):
+    """msda_optim_chunks: (chunk_start as a list of len(numels) + 1 ints, the chunk count).  Host logic, nothing is launched."""
+    lib = _lib or load()
+    n = len(numels)
+    numel = (ctypes.c_longlong * max(1, n))(*numels)
+    start = (ctypes.c_longlong * (n + 1))()
+    total = int(lib.msda_optim_chunks(n, ctypes.cast(numel, _VP), ctypes.cast(start, _VP)))
+    if total < 0:
+        _raise(lib, 1, "optim_chunks")
+    return list(start), total
+
+
+def grad_sumsq(dev, n, n_chunks, g, numel, chunk_start, partials):
+    """msda_grad_sumsq_f32 over device tables given as addresses; partials: fp32 [n_chunks].  One launch."""
+    _launch(dev, "msda_grad_sumsq_f32", "grad_sumsq", n, n_chunks, g, numel, chunk_start, partials.data_ptr())
+
+
+def grad_norm_finish(dev, n_chunks, partials, max_norm, out):
+    """msda_grad_norm_finish_f32: out (fp32 [2]) = total norm, clip coefficient.  One launch."""
+    _launch(dev, "msda_grad_norm_finish_f32", "grad_norm_finish", n_chunks, partials.data_ptr(), float(max_norm), out.data_ptr())
+
+
+def grad_scale(dev, n, n_chunks, g, numel, chunk_start, coef):
+    """msda_grad_scale_f32: every gradient of the table *= the device scalar at address `coef`.  One launch."""
+    _launch(dev, "msda_grad_scale_f32", "grad_scale", n, n_chunks, g, numel, chunk_start, coef)
+
+
+def adamw_step(dev, n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, group, step_offset, hyper, global_step, coef):
+    """msda_adamw_step_f32.  Tables as device addresses; hyper: per group (lr, weight_decay, beta1, beta2, eps); coef: the
+    address of the device clip coefficient or None.  One launch."""
+    ng = len(hyper)
+    cols = [(ctypes.c_double * ng)(*[float(h[k]) for h in hyper]) for k in range(5)]
+    _launch(dev, "msda_adamw_step_f32", "adamw_step", n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, group,
+            step_offset, ng, *[ctypes.cast(c, _VP) for c in cols], int(global_step), coef)

@@ -1347,4 +1347,48 @@ MSDA_SWIN_GLUE_NORM_ENTRIES(uint16_t, float, f32_sbf16, true, false)       // th
 #undef MSDA_SWIN_GLUE_ENTRIES
 #undef MSDA_SWIN_GLUE_NORM_ENTRIES
 
+// ---- the tail of the step (msda_optim.hip): engine.py:644-648's clip_grad_norm_ and optimizer.step(), util/settings.py:434's
+// AdamW and util/misc.py's get_total_grad_norm; every check is the launcher's, before its launch ----
+int msda_optim_supported(long long n_tensors, int n_groups) { return msda::optim_supported(n_tensors, n_groups) ? 1 : 0; }
+
+int msda_optim_chunk_elems(void) { return msda::kOptimChunk; }
+
+long long msda_optim_chunks(int n_tensors, const long long *numel, long long *chunk_start)
+{
+    return msda::optim_chunks(n_tensors, numel, chunk_start);
+}
+
+int msda_grad_sumsq_f32(int n_tensors, long long n_chunks, const float *const *g, const long long *numel,
+                        const long long *chunk_start, float *partials, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::launch_grad_sumsq(n_tensors, n_chunks, g, numel, chunk_start, partials, (hipStream_t)stream);
+}
+
+int msda_grad_norm_finish_f32(long long n_chunks, const float *partials, float max_norm, float *out, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::launch_grad_norm_finish(n_chunks, partials, max_norm, out, (hipStream_t)stream);
+}
+
+int msda_grad_scale_f32(int n_tensors, long long n_chunks, float *const *g, const long long *numel, const long long *chunk_start,
+                        const float *coef, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::launch_grad_scale(n_tensors, n_chunks, g, numel, chunk_start, coef, (hipStream_t)stream);
+}
+
+int msda_adamw_step_f32(int n_tensors, long long n_chunks, float *const *p, const float *const *g, float *const *exp_avg,
+                        float *const *exp_avg_sq, const long long *numel, const long long *chunk_start, const int *group,
+                        const long long *step_offset, int n_groups, const double *lr, const double *weight_decay,
+                        const double *beta1, const double *beta2, const double *eps, long long global_step, const float *coef,
+                        msda_stream_t stream)
+{
+    msda::begin_call();
+    msda::OptimTables t;
+    t.n = n_tensors; t.n_chunks = n_chunks; t.p = p; t.g = g; t.exp_avg = exp_avg; t.exp_avg_sq = exp_avg_sq;
+    t.numel = numel; t.chunk_start = chunk_start; t.group = group; t.step_offset = step_offset;
+    return msda::launch_adamw_step(t, n_groups, lr, weight_decay, beta1, beta2, eps, global_step, coef, (hipStream_t)stream);
+}
+
 }  // extern "C"

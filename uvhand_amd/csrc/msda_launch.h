@@ -387,4 +387,29 @@ size_t neck_workspace_bytes(int L, int N, int C);
 int launch_neck_forward(const NeckFwdPlan &plan, int N, int C, int groups, float eps, hipStream_t stream);
 int launch_neck_backward(const NeckBwdPlan &plan, int N, int C, int groups, hipStream_t stream);
 
+// ---- the tail of the step: gradient norm, clip and AdamW as multi-tensor launches (msda_optim.hip; C entries msda_optim_*,
+// msda_grad_*, msda_adamw_step_f32).  Every table is a DEVICE array the caller owns, one entry per tensor (chunk_start: n + 1);
+// the per-group hyperparameters are host arrays and travel by value in the kernel arguments.  Every check is the launcher's.
+constexpr int kOptimChunk = 8192;     // elements of a chunk: one workgroup
+constexpr int kOptimMaxGroups = 8;
+struct OptimTables {
+    int n;
+    long long n_chunks;
+    float *const *p;
+    const float *const *g;
+    float *const *exp_avg, *const *exp_avg_sq;
+    const long long *numel, *chunk_start;
+    const int *group;
+    const long long *step_offset;
+};
+bool optim_supported(long long n_tensors, int n_groups);
+long long optim_chunks(int n, const long long *numel, long long *chunk_start);      // host arrays; -1: argument error
+int launch_grad_sumsq(int n, long long n_chunks, const float *const *g, const long long *numel, const long long *chunk_start,
+                      float *partials, hipStream_t stream);
+int launch_grad_norm_finish(long long n_chunks, const float *partials, float max_norm, float *out, hipStream_t stream);
+int launch_grad_scale(int n, long long n_chunks, float *const *g, const long long *numel, const long long *chunk_start,
+                      const float *coef, hipStream_t stream);
+int launch_adamw_step(const OptimTables &t, int n_groups, const double *lr, const double *weight_decay, const double *beta1,
+                      const double *beta2, const double *eps, long long global_step, const float *coef, hipStream_t stream);
+
 }  // namespace msda

@@ -1154,6 +1154,36 @@ int msda_adamw_step_f32(int n_tensors, long long n_chunks, float *const *p, cons
                         const double *beta1, const double *beta2, const double *eps, long long global_step, const float *coef,
                         msda_stream_t stream);
 
+/* The device-state forms of the same tail (engine.py:644-648: clip_grad_norm_ then optimizer.step(); util/settings.py:434-440:
+ * AdamW under OneCycleLR, whose default cycle_momentum moves lr and beta1 after every step).  Added without a version bump: purely
+ * additive.  They are what torch.optim.AdamW(capturable=True) needs to run inside a HIP graph: nothing that changes from step to
+ * step is a kernel argument, so a captured launch replays with the values of the replay.
+ *   step    DEVICE table [n_tensors] of pointers to 0-d fp32 DEVICE tensors, the state capturable=True keeps per parameter.
+ *   hyper   DEVICE table [n_groups][5] of doubles: lr, weight_decay, beta1, beta2, eps of each group.  The caller validates the
+ *           values (the library cannot read them without a synchronisation).
+ *   msda_optim_advance_f32 (engine.py:644-648, util/settings.py:434-440)  one launch: *step[i] += 1 for every i < n_tensors; the
+ *       first launch of an unclipped step.
+ *   msda_grad_norm_finish_dev_f32 (engine.py:644-648, util/settings.py:434-440)  msda_grad_norm_finish_f32, then status[0] =
+ *       skipped = skip_nonfinite && !isfinite(total_norm), status[1] += skipped (status: DEVICE int32 [2]; may be NULL when
+ *       skip_nonfinite is 0) and, unless skipped, *step[i] += 1 for every i < n_tensors.  One launch, one workgroup.  n_tensors = 0
+ *       or n_chunks = 0 launches nothing (advance the steps of tensors that are all empty with msda_optim_advance_f32).
+ *   msda_adamw_step_dev_f32 (engine.py:644-648, util/settings.py:434-440)  msda_adamw_step_f32 with t = (long long)*step[tensor]
+ *       (already advanced for this launch; at least 1) and decay, 1 - beta1, beta2, 1 - beta2, eps, lr / bc1, sqrt(bc2) formed on
+ *       the device by the same fp64 expressions, each rounded to fp32 once: with the same values the result is bit for bit that of
+ *       msda_adamw_step_f32.  coef: as there.  skip: DEVICE int32 or NULL; when *skip != 0 every workgroup returns before it reads
+ *       or writes anything (pass status of the finish launch).
+ * A clipped step is sumsq + finish_dev + step_dev = 3 launches, an unclipped one advance + step_dev = 2.  No float atomics, no
+ * allocation, no synchronisation.  Argument errors (MSDA_ERR_ARGUMENT before any launch, msda_launch_count unchanged): counts
+ * outside msda_optim_supported, a null table with something to launch, a null hyper or step table, a NaN max_norm, and a null
+ * status with skip_nonfinite set. */
+int msda_optim_advance_f32(int n_tensors, float *const *step, msda_stream_t stream);
+int msda_grad_norm_finish_dev_f32(long long n_chunks, const float *partials, float max_norm, float *out, int n_tensors,
+                                  float *const *step, int skip_nonfinite, int *status, msda_stream_t stream);
+int msda_adamw_step_dev_f32(int n_tensors, long long n_chunks, float *const *p, const float *const *g, float *const *exp_avg,
+                            float *const *exp_avg_sq, const long long *numel, const long long *chunk_start, const int *group,
+                            const float *const *step, int n_groups, const double *hyper, const float *coef, const int *skip,
+                            msda_stream_t stream);
+
 /* Library/ABI version (major*100 + minor) and the kernel family a geometry maps to.  MSDA_ABI_VERSION is what a binding
  * compiled against THIS header expects msda_version() to return at run time (uvhand_amd/_ext.py compares the two);
  * it changes whenever a declaration in this file does.  116: msda_attn32_forward_bf16 / msda_attn32_backward_bf16 and

@@ -203,6 +203,9 @@ SIGNATURES = {
     "msda_grad_norm_finish_f32": "i l p f p p",
     "msda_grad_scale_f32": "i il ppp p p",
     "msda_adamw_step_f32": "i il pppp pp pp i ppppp l p p",
+    "msda_optim_advance_f32": "i ip p",
+    "msda_grad_norm_finish_dev_f32": "i l p f p ip ip p",
+    "msda_adamw_step_dev_f32": "i il pppp pp pp i p pp p",
     # introspection and test hooks
     "msda_version": "i",
     "msda_path_for": "i iiiii",
@@ -2250,3 +2253,22 @@ def adamw_step(dev, n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, 
     cols = [(ctypes.c_double * ng)(*[float(h[k]) for h in hyper]) for k in range(5)]
     _launch(dev, "msda_adamw_step_f32", "adamw_step", n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, group,
             step_offset, ng, *[ctypes.cast(c, _VP) for c in cols], int(global_step), coef)
+
+
+def optim_advance(dev, n, step):
+    """msda_optim_advance_f32: every 0-d fp32 device step of the pointer table at address `step` += 1.  One launch."""
+    _launch(dev, "msda_optim_advance_f32", "optim_advance", n, step)
+
+
+def grad_norm_finish_dev(dev, n_chunks, partials, max_norm, out, n, step, skip_nonfinite, status):
+    """msda_grad_norm_finish_dev_f32: grad_norm_finish, then status (address of int32 [2] or None) = (skipped, += skipped) and,
+    unless skipped, every step of the table += 1.  One launch."""
+    _launch(dev, "msda_grad_norm_finish_dev_f32", "grad_norm_finish_dev", n_chunks, partials.data_ptr(), float(max_norm),
+            out.data_ptr(), n, step, int(bool(skip_nonfinite)), status)
+
+
+def adamw_step_dev(dev, n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, group, step, n_groups, hyper, coef, skip):
+    """msda_adamw_step_dev_f32.  Every table a device address; hyper: fp64 [n_groups][5] on the device; coef, skip: the addresses
+    of the device clip coefficient and skip flag, or None.  One launch."""
+    _launch(dev, "msda_adamw_step_dev_f32", "adamw_step_dev", n, n_chunks, p, g, exp_avg, exp_avg_sq, numel, chunk_start, group,
+            step, n_groups, hyper, coef, skip)

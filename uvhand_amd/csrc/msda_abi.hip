@@ -1391,4 +1391,31 @@ int msda_adamw_step_f32(int n_tensors, long long n_chunks, float *const *p, cons
     return msda::launch_adamw_step(t, n_groups, lr, weight_decay, beta1, beta2, eps, global_step, coef, (hipStream_t)stream);
 }
 
+// the device-state forms of the same tail (engine.py:644-648, util/settings.py:434-440): steps and hyperparameters live on the device
+int msda_optim_advance_f32(int n_tensors, float *const *step, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::launch_optim_advance(n_tensors, step, (hipStream_t)stream);
+}
+
+int msda_grad_norm_finish_dev_f32(long long n_chunks, const float *partials, float max_norm, float *out, int n_tensors,
+                                  float *const *step, int skip_nonfinite, int *status, msda_stream_t stream)
+{
+    msda::begin_call();
+    return msda::launch_grad_norm_finish_dev(n_chunks, partials, max_norm, out, n_tensors, step, skip_nonfinite, status,
+                                             (hipStream_t)stream);
+}
+
+int msda_adamw_step_dev_f32(int n_tensors, long long n_chunks, float *const *p, const float *const *g, float *const *exp_avg,
+                            float *const *exp_avg_sq, const long long *numel, const long long *chunk_start, const int *group,
+                            const float *const *step, int n_groups, const double *hyper, const float *coef, const int *skip,
+                            msda_stream_t stream)
+{
+    msda::begin_call();
+    msda::OptimTables t;
+    t.n = n_tensors; t.n_chunks = n_chunks; t.p = p; t.g = g; t.exp_avg = exp_avg; t.exp_avg_sq = exp_avg_sq;
+    t.numel = numel; t.chunk_start = chunk_start; t.group = group; t.step_offset = nullptr;
+    return msda::launch_adamw_step_dev(t, step, n_groups, hyper, coef, skip, (hipStream_t)stream);
+}
+
 }  // extern "C"

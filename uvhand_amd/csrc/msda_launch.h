@@ -411,5 +411,13 @@ int launch_grad_scale(int n, long long n_chunks, float *const *g, const long lon
                       const float *coef, hipStream_t stream);
 int launch_adamw_step(const OptimTables &t, int n_groups, const double *lr, const double *weight_decay, const double *beta1,
                       const double *beta2, const double *eps, long long global_step, const float *coef, hipStream_t stream);
+// the device-state forms (msda_optim_advance_f32, msda_grad_norm_finish_dev_f32, msda_adamw_step_dev_f32): step is a DEVICE table
+// of pointers to 0-d fp32 device steps, hyper a DEVICE table [n_groups][5] of lr, weight_decay, beta1, beta2, eps; t.step_offset
+// is not read
+int launch_optim_advance(int n, float *const *step, hipStream_t stream);
+int launch_grad_norm_finish_dev(long long n_chunks, const float *partials, float max_norm, float *out, int n, float *const *step,
+                                int skip_nonfinite, int *status, hipStream_t stream);
+int launch_adamw_step_dev(const OptimTables &t, const float *const *step, int n_groups, const double *hyper, const float *coef,
+                          const int *skip, hipStream_t stream);
 
 }  // namespace msda

@@ -24,6 +24,17 @@
 //                     products, an error below 1e-14 of beta^t), lr / bc1 and sqrt(bc2) are fp64 rounded to fp32 once, as
 //                     torch's Python scalars are.  sqrtf and the divisions are correctly rounded, no fast intrinsic; every
 //                     fused multiply-add is written out and contraction is off, so the arithmetic is the text below.
+//
+// The device-state forms (torch.optim.AdamW(capturable=True): every tensor's step is a 0-d fp32 DEVICE tensor, reached through a
+// table of pointers; the groups' lr, weight_decay, beta1, beta2, eps are a DEVICE table of doubles) take nothing from the host
+// that changes from step to step, so a captured launch replays with the values of the replay (util/settings.py:434-440: OneCycleLR
+// moves lr and beta1 after every step):
+// optim_advance_kernel    *step[i] += 1 for every tensor: the unclipped step's first launch.
+// norm_finish_dev_kernel  norm_finish_kernel, then status[0] = skipped = skip_nonfinite && !isfinite(norm), status[1] += skipped
+//                         and, unless skipped, *step[i] += 1 for every tensor (its threads loop over i).
+// adamw_step_dev_kernel   adamw_step_kernel with t = *step[tensor] (already advanced) and the per-group scalars formed on the
+//                         device by the fp64 expressions of launch_adamw_step, each rounded to fp32 once: the same bits.  A
+//                         non-zero *skip ends the workgroup before it touches anything.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -252,6 +263,106 @@ __global__ void __launch_bounds__(kBlock) adamw_step_kernel(float *const *p, con
     else adamw_chunk<false>(pp, gg, mm, vv, c.count, s);
 }
 
+__global__ void __launch_bounds__(kBlock) optim_advance_kernel(float *const *step, int n)
+{
+    const int i = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+    if (i < n) *step[i] += 1.f;                            // every tensor has a step of its own: no two threads meet
+}
+
+// What the device-state kernels share with their host-state twins above (norm_finish_kernel, adamw_step_kernel), one copy each.
+// The twins keep their own text for now; they are to call these too, so that a fix reaches both.
+
+// The total norm and the clip coefficient out of the chunks' sums of squares, by one workgroup of kFinishBlock threads: the
+// reduction and the expressions of norm_finish_kernel.  Writes out[0] = norm, out[1] = coef; the norm is returned to thread 0 only.
+__device__ __forceinline__ float finish_norm_and_coef(const float *partials, long long n_chunks, float max_norm, float *out,
+                                                      double *red)
+{
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (long long i = tid; i < n_chunks; i += kFinishBlock) s += (double)partials[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = kFinishBlock / 2; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid != 0) return 0.f;
+    const float norm = (float)sqrt(red[0]);
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+        // torch: clamp(max_norm / (total_norm + 1e-6), max = 1), where float / Tensor is reciprocal() * float
+        const float c = (1.f / (norm + 1e-6f)) * max_norm;
+        coef = c > 1.f ? 1.f : c;                          // a NaN stays a NaN, as in torch.clamp
+    }
+    out[0] = norm;
+    out[1] = coef;
+    return norm;
+}
+
+// step_size = lr / bc1 and sqrt(bc2) of a tensor at step t >= 1: fp64, each rounded to fp32 once
+__device__ __forceinline__ void set_bias_corrections(AdamScalars &s, double lr, double beta1, double beta2, long long t)
+{
+    const double bc1 = 1.0 - powi(beta1, t), bc2 = 1.0 - powi(beta2, t);
+    s.step_size = (float)(lr / bc1);
+    s.bc2_sqrt = (float)sqrt(bc2);
+}
+
+// the update of chunk c of its tensor: vector accesses when all four addresses are 16-byte aligned, else element by element
+__device__ __forceinline__ void adamw_update_chunk(float *const *p, const float *const *g, float *const *m, float *const *v,
+                                                   const ChunkRef &c, const AdamScalars &s)
+{
+    gfloat *pp = as_global(p[c.tensor]) + c.base, *mm = as_global(m[c.tensor]) + c.base, *vv = as_global(v[c.tensor]) + c.base;
+    const gfloat *gg = as_global(g[c.tensor]) + c.base;
+    if (aligned16(pp) && aligned16(gg) && aligned16(mm) && aligned16(vv)) adamw_chunk<true>(pp, gg, mm, vv, c.count, s);
+    else adamw_chunk<false>(pp, gg, mm, vv, c.count, s);
+}
+
+__global__ void __launch_bounds__(kFinishBlock) norm_finish_dev_kernel(const float *partials, long long n_chunks, float max_norm,
+                                                                       float *out, float *const *step, int n_tensors,
+                                                                       int skip_nonfinite, int *status)
+{
+    __shared__ double red[kFinishBlock];
+    __shared__ int skip_all;
+    const int tid = threadIdx.x;
+    const float norm = finish_norm_and_coef(partials, n_chunks, max_norm, out, red);
+    if (tid == 0) {
+        const int skipped = (skip_nonfinite && !std::isfinite(norm)) ? 1 : 0;
+        if (status) {
+            status[0] = skipped;
+            status[1] += skipped;
+        }
+        skip_all = skipped;
+    }
+    __syncthreads();
+    if (skip_all) return;
+    for (int i = tid; i < n_tensors; i += kFinishBlock) *step[i] += 1.f;
+}
+
+__global__ void __launch_bounds__(kBlock) adamw_step_dev_kernel(float *const *p, const float *const *g, float *const *m,
+                                                                float *const *v, const long long *numel,
+                                                                const long long *chunk_start, const int *group,
+                                                                const float *const *step, int n, const double *hyper, int n_groups,
+                                                                const float *coef, const int *skip)
+{
+    if (skip && *skip != 0) return;                        // a skipped step: nothing is read or written
+    const ChunkRef c = find_chunk(chunk_start, numel, n);
+    int gi = group[c.tensor];
+    gi = gi < 0 ? 0 : (gi >= n_groups ? n_groups - 1 : gi);   // a bad table entry never indexes past the hyper table
+    long long t = (long long)*step[c.tensor];              // advanced by this step's earlier launch
+    if (t < 1) t = 1;
+    const double *h = hyper + 5 * gi;
+    const double lr = h[0], weight_decay = h[1], beta1 = h[2], beta2 = h[3], eps = h[4];
+    AdamScalars s;                                         // launch_adamw_step's expressions, on the device
+    s.decay = (float)(1.0 - lr * weight_decay);
+    s.w1 = (float)(1.0 - beta1);
+    s.b2 = (float)beta2;
+    s.w2 = (float)(1.0 - beta2);
+    s.eps = (float)eps;
+    set_bias_corrections(s, lr, beta1, beta2, t);
+    s.coef = coef ? *coef : 1.f;
+    adamw_update_chunk(p, g, m, v, c, s);
+}
+
 int perr(const char *msg) { return set_error(MSDA_ERR_ARGUMENT, msg); }
 
 // the checks every entry shares; *launch: whether there is anything to launch
@@ -357,6 +468,45 @@ int launch_adamw_step(const OptimTables &t, int n_groups, const double *lr, cons
     hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)t.n_chunks), dim3(kBlock), 0, stream, t.p, t.g, t.exp_avg, t.exp_avg_sq,
                        t.numel, t.chunk_start, t.group, t.step_offset, t.n, hp, global_step, coef);
     return check_launch("adamw_step_kernel");
+}
+
+int launch_optim_advance(int n, float *const *step, hipStream_t stream)
+{
+    if (n < 0 || n > kMaxTensors) return perr("msda_optim_advance: tensor count 0 .. 2^20 (msda_optim_supported)");
+    if (n == 0) return MSDA_OK;
+    if (step == nullptr) return perr("msda_optim_advance: null step table");
+    hipLaunchKernelGGL(optim_advance_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, step, n);
+    return check_launch("optim_advance_kernel");
+}
+
+int launch_grad_norm_finish_dev(long long n_chunks, const float *partials, float max_norm, float *out, int n, float *const *step,
+                                int skip_nonfinite, int *status, hipStream_t stream)
+{
+    if (n < 0 || n > kMaxTensors || n_chunks < 0 || n_chunks > 0x7fffffffLL)
+        return perr("msda_grad_norm_finish_dev: tensor count 0 .. 2^20 and chunk count 0 .. 2^31 - 1 (msda_optim_supported)");
+    if (std::isnan(max_norm)) return perr("msda_grad_norm_finish_dev: max_norm is NaN");
+    if (skip_nonfinite && status == nullptr) return perr("msda_grad_norm_finish_dev: skip_nonfinite needs a status array");
+    if (n == 0 || n_chunks == 0) return MSDA_OK;
+    if (partials == nullptr || out == nullptr) return perr("msda_grad_norm_finish_dev: null pointer");
+    if (step == nullptr) return perr("msda_grad_norm_finish_dev: null step table");
+    hipLaunchKernelGGL(norm_finish_dev_kernel, dim3(1), dim3(kFinishBlock), 0, stream, partials, n_chunks, max_norm, out, step, n,
+                       skip_nonfinite ? 1 : 0, status);
+    return check_launch("norm_finish_dev_kernel");
+}
+
+int launch_adamw_step_dev(const OptimTables &t, const float *const *step, int n_groups, const double *hyper, const float *coef,
+                          const int *skip, hipStream_t stream)
+{
+    if (!optim_supported(t.n, n_groups)) return perr("msda_adamw_step_dev: 0 .. 2^20 tensors in 1 .. 8 groups (msda_optim_supported)");
+    if (hyper == nullptr) return perr("msda_adamw_step_dev: null hyper table");
+    bool launch;
+    const bool ok = t.p && t.g && t.exp_avg && t.exp_avg_sq && t.numel && t.chunk_start && t.group;
+    if (int rc = check_tables("msda_adamw_step_dev", t.n, t.n_chunks, ok, &launch)) return rc;
+    if (!launch) return MSDA_OK;
+    if (step == nullptr) return perr("msda_adamw_step_dev: null step table");
+    hipLaunchKernelGGL(adamw_step_dev_kernel, dim3((unsigned)t.n_chunks), dim3(kBlock), 0, stream, t.p, t.g, t.exp_avg, t.exp_avg_sq,
+                       t.numel, t.chunk_start, t.group, step, t.n, hyper, n_groups, coef, skip);
+    return check_launch("adamw_step_dev_kernel");
 }
 
 }  // namespace msda

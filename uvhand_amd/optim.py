@@ -15,6 +15,13 @@ offsets).  They are uploaded when the set of parameters with a gradient changes;
 step (``zero_grad(set_to_none=True)``), so their list is compared on the host and that one table is re-sent when it differs.
 Every upload is a non-blocking copy out of a pinned buffer that is not rewritten while that copy may be pending: a ring of
 buffers, each with an event that is polled with ``query()``; the ring grows rather than waits.
+
+The device-state form.  ``AdamW(..., capturable=True)`` (torch's own flag, on every group) keeps what changes from step to step on
+the device: each parameter's ``step`` is the 0-d fp32 device tensor ``torch.optim.AdamW(capturable=True)`` keeps, and the groups'
+hyperparameters are a device table with a host shadow (``AdamW.refresh_hyper``).  The same arithmetic then runs eagerly or
+inside a stream capture, so that forward + loss + backward + clip + update replay as one HIP graph::
+
+    graph.replay(); lr_scheduler.step(); optimizer.refresh_hyper()
 """
 import os
 
@@ -174,24 +181,24 @@ def grad_norm(parameters):
 class _Plan:
     """The device tables of one set of parameters with a gradient, in param_groups order."""
 
-    def __init__(self, dev, params, states, gidx, pptrs, global_step):
+    def __init__(self, dev, params, states, gidx, pptrs, per_tensor):
+        """per_tensor: what the update reads for each tensor besides its addresses: the step offset (host steps: t of a tensor in
+        the next launch = (global_step + 1) - offset = its own step + 1) or the address of its device step (_DevPlan)."""
         n = self.n = len(params)
         self.dev, self.gidx, self.pptrs = dev, gidx, pptrs
-        self.steps = [s["step"] for s in states]
+        self.steps = [s["step"] for s in states]             # host steps: advanced through this list; device steps: kept alive
         self.state_ids = [id(s["exp_avg"]) for s in states]
         numels = [p.numel() for p in params]
         chunk_start, self.n_chunks = _native.optim_chunks(numels)
-        # t of a tensor in the next launch = (global_step + 1) - offset = its own step + 1
-        offsets = [global_step - int(s.item()) for s in self.steps]
         rows = pptrs + [s["exp_avg"].data_ptr() for s in states] + [s["exp_avg_sq"].data_ptr() for s in states] + numels \
-            + offsets + chunk_start
+            + list(per_tensor) + chunk_start
         groups = torch.zeros(2 * ((n + 1) // 2), dtype=torch.int32)
         groups[:n] = torch.tensor(gidx, dtype=torch.int32)
         host = torch.cat([torch.tensor(rows, dtype=torch.int64), groups.view(torch.int64)])
         self.table = torch.empty(host.numel(), dtype=torch.int64, device=dev)
         _uploader(dev).send(host, self.table)
         base = self.table.data_ptr()
-        self.p, self.m, self.v, self.numel, self.offset = (base + 8 * n * k for k in range(5))
+        self.p, self.m, self.v, self.numel, self.per_tensor = (base + 8 * n * k for k in range(5))
         self.start = base + 8 * 5 * n
         self.group = self.start + 8 * (n + 1)
         self.gtable = torch.empty(n, dtype=torch.int64, device=dev)
@@ -199,9 +206,60 @@ class _Plan:
         self.partials = torch.empty(max(1, self.n_chunks), dtype=torch.float32, device=dev)
 
     def bind(self, gptrs):
+        """The gradients' table, re-sent through the ring when the addresses changed.  Returns the table's address."""
         if gptrs != self.gptrs:
             _uploader(self.dev).send(torch.tensor(gptrs, dtype=torch.int64), self.gtable)
             self.gptrs = gptrs
+        return self.gtable.data_ptr()
+
+
+class _DevPlan(_Plan):
+    """The plan of the device-state form: per tensor the address of its 0-d device step.  Nothing in its tables changes from
+    step to step, and under a capture the gradients' table is the capture's own."""
+
+    def __init__(self, dev, params, states, gidx, pptrs):
+        super().__init__(dev, params, states, gidx, pptrs, [s["step"].data_ptr() for s in states])
+        # a capture may not allocate pinned memory (that is no stream operation, and the runtime can refuse it while a stream
+        # captures), so the buffer its table is copied from exists beforehand; an eager step after a capture makes the next one
+        self.spare = self._pinned()
+        self.captured = []                                   # (addresses, pinned copy, device table) of every capture
+
+    def _pinned(self):
+        return torch.empty(max(1, self.n), dtype=torch.int64, pin_memory=True)
+
+    def bind(self, gptrs):
+        if self.spare is None:
+            self.spare = self._pinned()
+        return super().bind(gptrs)
+
+    def bind_captured(self, gptrs):
+        """Under a capture: a table of the capture's own, filled by ONE captured copy out of a pinned buffer that is written
+        here, once, and then kept unchanged for the plan's life, so that every replay copies the same addresses again.  The
+        eager table and the ring are left alone: a later eager step may rewrite both."""
+        for ptrs, pinned, table in self.captured:
+            if ptrs == gptrs:
+                break
+        else:
+            if self.spare is None:
+                raise RuntimeError("AdamW(capturable=True): a second capture with gradients at other addresses needs an eager "
+                                   "step() in between (it prepares the pinned buffer the capture copies their table from)")
+            pinned, self.spare = self.spare, None
+            pinned[:self.n] = torch.tensor(gptrs, dtype=torch.int64)
+            table = torch.empty(max(1, self.n), dtype=torch.int64, device=self.dev)
+            self.captured.append((gptrs, pinned, table))
+        table.copy_(pinned, non_blocking=True)
+        return table.data_ptr()
+
+
+def _hyper_rows(groups):
+    """[(lr, weight_decay, beta1, beta2, eps)] of the groups as Python floats, checked as msda_adamw_step_f32 checks them."""
+    rows = [(float(g["lr"]), float(g["weight_decay"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) for g in groups]
+    for lr, wd, b1, b2, eps in rows:
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise RuntimeError("AdamW(capturable=True): betas must be in [0, 1)")
+        if not all(x == x and abs(x) != float("inf") for x in (lr, wd, eps)):
+            raise RuntimeError("AdamW(capturable=True): lr, eps and weight_decay must be finite")
+    return rows
 
 
 class AdamW(torch.optim.AdamW):
@@ -210,6 +268,18 @@ class AdamW(torch.optim.AdamW):
     A subclass with the same constructor: ``param_groups``, ``state_dict``, ``load_state_dict``, ``add_param_group`` and every
     ``lr_scheduler`` work unchanged, and the state is exactly torch's (``step`` as torch creates it, ``exp_avg``,
     ``exp_avg_sq``), so checkpoints move between this class and ``torch.optim.AdamW`` in both directions.
+
+    ``capturable=True`` on every group selects the device-state form (see the module's head): two launches for a plain step,
+    three with the clip, eagerly or inside a stream capture, with the state of ``torch.optim.AdamW(capturable=True)``.  A
+    capture needs what torch's graph recipe needs, warm-up steps: the tables and every state must exist from an earlier eager
+    step, and the device hyperparameters must equal ``param_groups`` (``refresh_hyper``).  The gradients may live anywhere:
+    ``zero_grad(set_to_none=True)`` before the capture and a backward inside it is fine.  ``last_grad_norm`` of a captured
+    step is static memory of the graph that every replay refreshes; read or clone it before the next replay.
+
+    A graph holds the addresses it was captured with.  The optimizer keeps the tables and step counts of every captured plan
+    alive, but not ``exp_avg`` and ``exp_avg_sq``, and a change of device replaces the hyperparameter table and the skip
+    counter: capture again after ``load_state_dict``, ``add_param_group`` or a move to another device, as torch's capturable
+    optimizer requires.  A replay of the older graph would write moments the allocator may already have handed out again.
     """
 
     def __init__(self, *args, **kwargs):
@@ -217,6 +287,38 @@ class AdamW(torch.optim.AdamW):
         self._plan = None
         self._global_step = 0
         self.last_grad_norm = None
+        self._hyper = None                                   # device-state form: (device, fp64 [8, 5] table, host shadow)
+        self._status = None                                  # int32 [2] on the device: (the last step was skipped, skipped steps)
+        self._kept = []                                      # plans a capture has read: their tables outlive a rebuild
+
+    @property
+    def skipped_steps(self):
+        """0-d int32 device tensor: the ``step(..., skip_nonfinite=True)`` calls (replays included) whose norm was not finite.
+        None before the first step of the device-state form."""
+        return None if self._status is None else self._status[1]
+
+    def refresh_hyper(self):
+        """Device-state form: compare ``param_groups`` with the host shadow of the device hyperparameter table and, when they
+        differ, send the table (a non-blocking copy on the current stream, no synchronisation).  Returns whether it sent
+        anything.  Call it after ``lr_scheduler.step()`` between two replays of a captured step; an eager ``step`` does it by
+        itself.  False and nothing done on the other routes and before the first step.
+
+        The copy is ordered against ``graph.replay()`` only when both are issued on the same stream: with the replay on a side
+        stream, call this under that stream too, otherwise the copy races with the replay's reads of the table."""
+        if self._hyper is None or not _enabled() or not all(g["capturable"] for g in self.param_groups):
+            return False
+        dev, table, shadow = self._hyper
+        rows = _hyper_rows(self.param_groups)
+        if rows == shadow or len(rows) > _native.OPTIM_MAX_GROUPS:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("AdamW.refresh_hyper() inside a stream capture: the copy would replay a buffer that is rewritten "
+                               "later; call it between replays")
+        with torch.cuda.device(dev):
+            flat = torch.tensor([x for row in rows for x in row], dtype=torch.float64)
+            _uploader(dev).send(flat.view(torch.int64), table.view(-1)[:flat.numel()].view(torch.int64))
+        self._hyper = (dev, table, rows)
+        return True
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -228,12 +330,13 @@ class AdamW(torch.optim.AdamW):
 
     def _collect(self):
         """(device, params, group indices, param addresses, grad addresses) of the parameters with a gradient when the kernels
-        take all of them, else None."""
+        take all of them, else None.  Groups that all have ``capturable=True`` are the device-state form; mixed ones are torch's."""
         groups = self.param_groups
         if not _enabled() or not 1 <= len(groups) <= _native.OPTIM_MAX_GROUPS:
             return None
+        capturable = groups[0]["capturable"]
         for g in groups:
-            if g["amsgrad"] or g["maximize"] or g["capturable"] or g["differentiable"] or g.get("fused"):
+            if g["amsgrad"] or g["maximize"] or g["capturable"] != capturable or g["differentiable"] or g.get("fused"):
                 return None
             scalars = (g["lr"], g["eps"], g["weight_decay"]) + tuple(g["betas"])
             if any(isinstance(x, torch.Tensor) for x in scalars):
@@ -256,7 +359,7 @@ class AdamW(torch.optim.AdamW):
                 gidx.append(gi)
                 pptrs.append(p.data_ptr())
                 gptrs.append(grad.data_ptr())
-        if dev is not None and torch.cuda.is_current_stream_capturing():
+        if dev is not None and not capturable and torch.cuda.is_current_stream_capturing():
             return None
         return dev, params, gidx, pptrs, gptrs
 
@@ -273,7 +376,69 @@ class AdamW(torch.optim.AdamW):
                     and m.numel() == p.numel() and v.numel() == p.numel() and not step.is_cuda):
                 return None
             states.append(state)
-        return _Plan(dev, params, states, gidx, pptrs, self._global_step)
+        return _Plan(dev, params, states, gidx, pptrs, [self._global_step - int(s["step"].item()) for s in states])
+
+    def _make_dev_plan(self, dev, params, gidx, pptrs):
+        states = []
+        for p in params:
+            state = self.state[p]
+            if len(state) == 0:                              # as torch's capturable route creates it (Adam._init_group)
+                state["step"] = torch.zeros((), dtype=_get_scalar_dtype(), device=p.device)
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            m, v, step = state["exp_avg"], state["exp_avg_sq"], state["step"]
+            if not (_dense_f32_cuda(m) and _dense_f32_cuda(v) and m.device == dev and v.device == dev
+                    and m.numel() == p.numel() and v.numel() == p.numel()
+                    and _dense_f32_cuda(step) and step.device == dev and step.dim() == 0):
+                return None
+            states.append(state)
+        return _DevPlan(dev, params, states, gidx, pptrs)
+
+    def _dev_step(self, dev, params, gidx, pptrs, gptrs, max_norm, skip_nonfinite):
+        """The device-state form.  Returns False when a state is not what the kernels take (torch's route then runs)."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        plan = self._plan
+        if type(plan) is not _DevPlan or plan.pptrs != pptrs or plan.gidx != gidx or plan.dev != dev \
+                or plan.state_ids != [id(self.state[p].get("exp_avg")) for p in params] \
+                or self._hyper is None or self._hyper[0] != dev:
+            if capturing:
+                raise RuntimeError("AdamW(capturable=True).step() inside a stream capture before its tables and states exist "
+                                   "for this set of parameters: warm-up steps are needed, run an eager step() with the same "
+                                   "parameters having gradients first (torch's CUDA graph recipe does the same)")
+            plan = self._make_dev_plan(dev, params, gidx, pptrs)
+            if plan is None:
+                return False
+            self._plan = plan
+            if self._hyper is None or self._hyper[0] != dev:
+                self._hyper = (dev, torch.zeros(_native.OPTIM_MAX_GROUPS, 5, dtype=torch.float64, device=dev), None)
+                self._status = torch.zeros(2, dtype=torch.int32, device=dev)
+        if capturing:
+            if _hyper_rows(self.param_groups) != self._hyper[2]:
+                raise RuntimeError("AdamW(capturable=True).step() inside a stream capture: param_groups' hyperparameters differ "
+                                   "from the device table; call refresh_hyper() before the capture")
+            g = plan.bind_captured(gptrs)
+            if plan not in self._kept:
+                self._kept.append(plan)
+        else:
+            g = plan.bind(gptrs)
+            self.refresh_hyper()
+        hyper, status = self._hyper[1].data_ptr(), self._status.data_ptr()
+        coef = skip = None
+        if max_norm is not None and plan.n_chunks > 0:
+            out = torch.empty(2, dtype=torch.float32, device=dev)      # under a capture: the graph's own memory
+            _native.grad_sumsq(dev, plan.n, plan.n_chunks, g, plan.numel, plan.start, plan.partials)
+            _native.grad_norm_finish_dev(dev, plan.n_chunks, plan.partials, max_norm, out, plan.n, plan.per_tensor, skip_nonfinite,
+                                         status)
+            self.last_grad_norm = out[0]
+            coef = out.data_ptr() + 4
+            skip = status if skip_nonfinite else None
+        else:
+            if max_norm is not None:                         # nothing but empty tensors: their norm is 0, their steps advance
+                self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            _native.optim_advance(dev, plan.n, plan.per_tensor)
+        _native.adamw_step_dev(dev, plan.n, plan.n_chunks, plan.p, g, plan.m, plan.v, plan.numel, plan.start, plan.group,
+                               plan.per_tensor, len(self.param_groups), hyper, coef, skip)
+        return True
 
     def _torch_step(self, max_norm):
         self._plan = None
@@ -289,7 +454,7 @@ class AdamW(torch.optim.AdamW):
         step(self)
 
     @torch.no_grad()
-    def step(self, closure=None, *, max_norm=None):
+    def step(self, closure=None, *, max_norm=None, skip_nonfinite=False):
         """One optimisation step.  ``max_norm`` given: the fused form of ``clip_grad_norm_(parameters, max_norm)`` followed by
         the step.  The clipped gradient exists in registers only: **``.grad`` is left unscaled**, unlike after torch's
         ``clip_grad_norm_``.  ``self.last_grad_norm`` is then the 0-d device tensor of the total norm before clipping (what
@@ -297,25 +462,44 @@ class AdamW(torch.optim.AdamW):
         ``get_total_grad_norm`` branch).
 
         torch's own ``clip_grad_norm_`` and ``AdamW.step`` run instead, and the library launches nothing, for ``amsgrad``,
-        ``maximize``, ``capturable``, ``differentiable`` or ``fused`` groups, tensor hyperparameters, any parameter with a
+        ``maximize``, ``differentiable`` or ``fused`` groups, tensor hyperparameters, any parameter with a
         gradient (or gradient, or state) that is not a dense contiguous fp32 CUDA tensor, parameters on more than one device,
-        more than 8 groups, an active stream capture and ``MSDA_OPTIM_FUSED=0``."""
+        more than 8 groups, ``MSDA_OPTIM_FUSED=0``, groups of which only some are ``capturable`` and, unless every group is
+        ``capturable``, an active stream capture.
+
+        ``skip_nonfinite=True`` (device-state form with ``max_norm``, else an error): a step whose total norm is not finite
+        leaves every parameter, moment and step count untouched and adds one to ``self.skipped_steps``; inside a graph this
+        stands where engine.py:626 leaves the loop on a non-finite loss.  The default lets such a step poison what torch's
+        route poisons."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         got = self._collect()
+        nothing = got is not None and got[0] is None         # no parameter has a gradient
+        device_state = got is not None and not nothing and self.param_groups[0]["capturable"]
+        if skip_nonfinite and not nothing and (max_norm is None or not device_state):
+            raise RuntimeError("AdamW.step(skip_nonfinite=True) needs max_norm and the device-state form (capturable=True on "
+                               "every group, on the kernels' route): no other route can skip without a host synchronisation")
         if got is None:
             self._torch_step(max_norm)
             return loss
         dev, params, gidx, pptrs, gptrs = got
-        if dev is None:                                      # no parameter has a gradient: torch's step does nothing
+        if nothing:                                          # torch's step does nothing
             if max_norm is not None:
                 self.last_grad_norm = torch.tensor(0.0)
             return loss
+        if device_state:
+            with torch.cuda.device(dev):
+                if self._dev_step(dev, params, gidx, pptrs, gptrs, max_norm, skip_nonfinite):
+                    return loss
+            if skip_nonfinite:
+                raise RuntimeError("AdamW.step(skip_nonfinite=True): a state is not what the device-state kernels take")
+            self._torch_step(max_norm)
+            return loss
         with torch.cuda.device(dev):
             plan = self._plan
-            if plan is None or plan.pptrs != pptrs or plan.gidx != gidx or plan.dev != dev \
+            if type(plan) is not _Plan or plan.pptrs != pptrs or plan.gidx != gidx or plan.dev != dev \
                     or plan.state_ids != [id(self.state[p].get("exp_avg")) for p in params]:
                 plan = self._make_plan(dev, params, gidx, pptrs)
                 if plan is None:
@@ -337,5 +521,5 @@ class AdamW(torch.optim.AdamW):
                     self.last_grad_norm = out[0]
                     coef = out.data_ptr() + 4
             _native.adamw_step(dev, plan.n, plan.n_chunks, plan.p, plan.gtable.data_ptr(), plan.m, plan.v, plan.numel, plan.start,
-                               plan.group, plan.offset, hyper, self._global_step, coef)
+                               plan.group, plan.per_tensor, hyper, self._global_step, coef)
         return loss

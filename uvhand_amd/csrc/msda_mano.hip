@@ -121,9 +121,9 @@ __device__ void mano_prelude(const ManoArgs &P, const ManoLayer &L, const ManoGr
     }
     for (int i = tid; i < nh * kJ * 3; i += kBlock) {
         const int h = i / (kJ * 3), jc = i % (kJ * 3);
-        float v = L.j_template[jc];
+        float v = 0.f;                              // the shape blend from zero, as mano_vposed sums it
         for (int k = 0; k < nb; ++k) v += L.j_shapedirs[jc * nb + k] * S.beta[h][k];
-        S.J[h][jc / 3][jc % 3] = v;
+        S.J[h][jc / 3][jc % 3] = L.j_template[jc] + v;
     }
     __syncthreads();
     for (int lvl = 0; lvl <= L.max_depth; ++lvl) {
@@ -168,9 +168,11 @@ __device__ void mano_vposed(const ManoArgs &P, const ManoLayer &L, int v0, int n
     const int col = tid;
     if (col < 3 * nv) {
         const long long gc = (long long)v0 * 3 + col;
-        float acc[kHT];
+        // each blend is summed from zero and added to the template once: summed onto the template, its 135 (or nb) small
+        // terms would each round at the template's magnitude, which is as large as a whole pose offset at small angles
+        float acc[kHT], off[kHT];
         const float tmpl = L.v_template[gc];
-        for (int h = 0; h < kHT; ++h) acc[h] = tmpl;
+        for (int h = 0; h < kHT; ++h) acc[h] = off[h] = 0.f;
         for (int k = 0; k < nb; ++k) {
             const float sd = L.shapedirs[gc * nb + k];
             for (int h = 0; h < kHT; ++h)
@@ -180,10 +182,10 @@ __device__ void mano_vposed(const ManoArgs &P, const ManoLayer &L, int v0, int n
         for (int p = 0; p < kPF; ++p) {
             const float d = pd[(long long)p * 3 * V];
             for (int h = 0; h < kHT; ++h)
-                if (h < nh) acc[h] += S.pf[h][p] * d;
+                if (h < nh) off[h] += S.pf[h][p] * d;
         }
         for (int h = 0; h < kHT; ++h)
-            if (h < nh) Q.VP[h][col] = acc[h];
+            if (h < nh) Q.VP[h][col] = (tmpl + acc[h]) + off[h];
     }
     __syncthreads();
 }
@@ -272,15 +274,17 @@ __global__ __launch_bounds__(kBlock) void mano_bwd_slice_kernel(ManoArgs P)
     __syncthreads();
     float *part = P.ws + g.ws + ((long long)h0 * P.nslices + slice) * kPart;
     const long long hstride = (long long)P.nslices * kPart;
-    // dA[j][r][c] = sum_v W[v][j] gv[v][r] [v_posed, 1][v][c]
+    // dA[j][r][c] = sum_v W[v][j] gv[v][r] [v_posed - J_j, 1][v][c]: the rotation part is taken about the rest joint, which
+    // is what the gradient of R^G_j comes to (dA[c] - dA[3] J_j[c]); formed per vertex, the two products do not have to cancel
     for (int i = tid; i < nh * kJ * 3; i += kBlock) {
         const int h = i / (kJ * 3), j = (i / 3) % kJ, r = i % 3;
+        const float jx = S.J[h][j][0], jy = S.J[h][j][1], jz = S.J[h][j][2];
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
         for (int v = 0; v < nv; ++v) {
             const float wg = Q.W[v][j] * Q.GV[h][3 * v + r];
-            a0 += wg * Q.VP[h][3 * v];
-            a1 += wg * Q.VP[h][3 * v + 1];
-            a2 += wg * Q.VP[h][3 * v + 2];
+            a0 += wg * (Q.VP[h][3 * v] - jx);
+            a1 += wg * (Q.VP[h][3 * v + 1] - jy);
+            a2 += wg * (Q.VP[h][3 * v + 2] - jz);
             a3 += wg;
         }
         float *d = part + h * hstride + j * 12 + r * 4;
@@ -333,13 +337,14 @@ __global__ __launch_bounds__(kBlock) void mano_bwd_chain_kernel(ManoArgs P)
         C.par[h][q] = acc;
     }
     __syncthreads();
-    // A_j = [R^G | t - R^G J]: gradients of R^G_j, t_j (posed joints included) and the direct part of J_j
+    // A_j = [R^G | t - R^G J]: gradients of R^G_j (the partials' rotation part, already about J_j), t_j (posed joints
+    // included) and the direct part of J_j
     for (int i = tid; i < nh * kJ; i += kBlock) {
         const int h = i / kJ, j = i % kJ, b = h0 + h;
         const float *dA = C.par[h] + j * 12;
         const float *RG = S.G[h][j];
         for (int r = 0; r < 3; ++r) {
-            for (int m = 0; m < 3; ++m) C.dRG[h][j][r * 3 + m] = dA[r * 4 + m] - dA[r * 4 + 3] * S.J[h][j][m];
+            for (int m = 0; m < 3; ++m) C.dRG[h][j][r * 3 + m] = dA[r * 4 + m];
             C.dt[h][j][r] = dA[r * 4 + 3] + (g.gjoints ? g.gjoints[((long long)b * NJ + j) * 3 + r] : 0.f);
         }
         for (int m = 0; m < 3; ++m)

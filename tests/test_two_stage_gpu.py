@@ -1,6 +1,8 @@
 """The two-stage kernels (csrc/msda_two_stage.hip) on the GPU: proposals against the reference formula in fp64, the query
 selection against the torch.topk composition (bitwise: gathers plus sigmoid), no host synchronisation and graph capture,
-the proposal embedding against fp64, and the fused pos_trans[0] node against fp64 at the cfg-2 / cfg-4 row counts."""
+the proposal embedding against fp64, and the fused pos_trans[0] node against fp64 at the cfg-2 / cfg-4 row counts.
+The true fp64 comparison of the proposals (proposals_composition builds its grid in fp32 whatever it is given) and the edge
+shapes of all four kernels live in tests/test_two_stage_envelope_gpu.py."""
 import math
 
 import pytest

@@ -242,10 +242,13 @@ int launch_pe(const float *r, const float *dim_t, long long M, float *pe, hipStr
 // B operand (W1, [out, 5376] K-major) is staged from memory as msda_gemm.hip's linear_rows_kernel stages it; the A operand
 // is generated: each thread computes its 2 x 4 PE values of the stage (4 sincosf) two stages ahead, while the MFMAs of the
 // current stage run, and stores them to LDS where the global loads would have landed.  Every PE element is generated
-// Nc / 128 times (8 at Nc = 1024).  Fixed summation order: bitwise reproducible.
+// Nc / 128 times (8 at Nc = 1024).  The sum of an output is two-level: MFMA chains of kPlFlush = 256 columns, added into a
+// total in order.  Fixed summation order: bitwise reproducible.
 constexpr int kPlM = 64, kPlN = 128, kPlStage = 32, kPlRow = kPlStage + 4;
+constexpr int kPlFlush = 256;                  // columns per MFMA chain
+static_assert(kPeWidth % kPlFlush == 0 && (kPlFlush & (kPlFlush - 1)) == 0 && kPlFlush % kPlStage == 0, "chains tile the reduction");
 
-__global__ __launch_bounds__(kTsBlock) void pe_linear_relu_kernel(
+__global__ __launch_bounds__(kTsBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void pe_linear_relu_kernel(
     const float *__restrict__ R, const float *__restrict__ dim_t, const float *__restrict__ B, const float *__restrict__ bias,
     float *__restrict__ C, long long M, int Nc, int tiles_n, long long tiles)
 {
@@ -320,9 +323,12 @@ __global__ __launch_bounds__(kTsBlock) void pe_linear_relu_kernel(
         }                                                                                                               \
     } while (0)
     float4 av[NI], bv0[NI], bv1[NI], avn[NI], bvn0[NI], bvn1[NI];
-    Acc acc0, acc1;
+    // two-level sum: the MFMA chain runs over kPlFlush columns (two coordinates, 128 MFMAs), then goes into the total.  One
+    // chain over all 5376 columns rounds 2688 times at the magnitude of the whole sum: 2.1e-6 of max |y| against 4e-7 for
+    // torch's blocked fp32 GEMM (tests/test_two_stage_envelope_gpu.py); 128 + 21 roundings leave a third of that.
+    Acc acc0, acc1, tot0, tot1;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; tot0[r] = 0.f; tot1[r] = 0.f; }
     TS_GEN(0);
     TS_LOAD_B(0);
     TS_STORE(0);
@@ -352,6 +358,15 @@ __global__ __launch_bounds__(kTsBlock) void pe_linear_relu_kernel(
 #pragma unroll
             for (int i = 0; i < NI; ++i) { av[i] = avn[i]; bv0[i] = bvn0[i]; bv1[i] = bvn1[i]; }
         }
+        if ((k0 & (kPlFlush - 1)) == kPlFlush - kPlStage) {     // the last stage of a chain (and of the loop)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                tot0[r] += acc0[r];
+                tot1[r] += acc1[r];
+                acc0[r] = 0.f;
+                acc1[r] = 0.f;
+            }
+        }
         cur ^= 1;
     }
 #undef TS_GEN
@@ -369,7 +384,7 @@ __global__ __launch_bounds__(kTsBlock) void pe_linear_relu_kernel(
         for (int r = 0; r < 16; ++r) {
             const long long i = m0 + i0 + (r & 3) + 8 * (r >> 2) + 4 * g;
             if (i < M) {
-                const float v = (half ? acc1[r] : acc0[r]) + bj;
+                const float v = (half ? tot1[r] : tot0[r]) + bj;
                 C[i * Nc + j] = v < 0.f ? 0.f : v;
             }
         }

@@ -614,6 +614,40 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
                             float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                             unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* The bf16-autocast form of the same node.  Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ * Same problems, host pointer arrays, launch budget (3 forward, 5 backward) and flags as the fp32 entries; every product runs
+ * on the bf16 MFMA with fp32 accumulation, and the dtypes and roundings are those of torch's bf16 autocast over the
+ * reference's composition.  bf16 tensors are uint16_t bit patterns; a `void *` is float for MSDA_HEADS_ARCTIC and bf16 for
+ * MSDA_HEADS_ASSEMBLY.
+ *   fp32: hs, every weight and bias, init_ref, inter_ref, sig, grad_hs and every weight / bias gradient.  hs and the weights
+ *         are rounded to bf16 (nearest even) in the load that stages them; nothing else reads them.
+ *   bf16: hidden [n_mlp, 2, L, M, C], shared_out[g] and grad_shared[g], the hidden gradients in the workspace.
+ *   kind: logits / grad_logits, kp_out[h] / grad_kp[h].  ARCTIC: logits are bf16-rounded values stored as float (the
+ *         reference's .to(float32)); keypoints are sigmoid(float(rnd(y)) + inverse_sigmoid(ref)) * 2 - 1 in fp32.
+ *         AssemblyHands: rnd(rnd(rnd(s) * 2) - 0.5), s = sigmoid of the bf16 pre-activation after rnd(y + offset) on x and y.
+ *   Every Linear output is rounded once to bf16, bias included; ReLU acts on bf16.  Backward: dy o mode is formed in fp32 and
+ *   rounded to bf16 as a matrix operand; hidden gradients are stored bf16; grad_hs and the weight / bias gradients are
+ *   accumulated and written in fp32 without a bf16 rounding.
+ * C % 8 == 0, 8 <= C <= 4096 (msda_heads_bf16_supported); hs, hidden, the weights and the workspace 16-byte aligned; the other
+ * limits of the fp32 entries.  workspace: at least msda_heads_bf16_workspace_bytes(...) bytes.
+ * Fixed summation order: bitwise reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+int msda_heads_bf16_supported(int C);
+unsigned long long msda_heads_bf16_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
+int msda_heads_forward_bf16(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
+                            const float *init_ref, const float *inter_ref, const float *const *cls_w,
+                            const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,
+                            const float *const *shared_w, const float *const *shared_b, void *logits, void *const *kp_out,
+                            uint16_t *const *shared_out, uint16_t *hidden, float *sig, msda_stream_t stream);
+int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
+                             const float *init_ref, const float *inter_ref, const float *const *cls_w,
+                             const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,
+                             const float *const *shared_w, const float *const *shared_b, const uint16_t *hidden,
+                             const float *sig, const void *grad_logits, const void *const *grad_kp,
+                             const uint16_t *const *grad_shared, float *grad_hs, float *const *grad_cls_w,
+                             float *const *grad_cls_b, float *const *grad_mlp_w, float *const *grad_mlp_b,
+                             float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
+                             unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* ---- SmoothNet (models/smoothnet.py:7-178): MotionSmoother modules as grouped fp32 GEMMs, and get_arctic_item's query
  * selection (arctic_tools/process.py:20-70) ---------------------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

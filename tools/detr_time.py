@@ -11,7 +11,12 @@ Routes: `composition` (MSDA_HEADS_FUSED=0: the reference's per-level Linears and
 device events, host syncs per step (torch.cuda.set_sync_debug_mode("warn")) and kernels per step (torch.profiler).  One JSON
 line per route and model, on stdout and appended to --out (default profiles/detr_time.jsonl).
 
-    python tools/detr_time.py [--iters N] [--only composition|dropin] [--out FILE]"""
+`--autocast` measures the same step under torch.autocast("cuda", dtype=torch.bfloat16) instead: `amp_composition` (what autocast
+gets by default: the torch composition) and `amp_bf16_node` (MSDA_HEADS_BF16=1: the node on the bf16 MFMA,
+csrc/msda_heads_bf16.hip), three runs of each, interleaved, in one session; these rows also carry the step's peak memory above
+what was allocated before it.
+
+    python tools/detr_time.py [--iters N] [--only ROUTE] [--autocast] [--out FILE]"""
 import argparse
 import json
 import os
@@ -77,10 +82,21 @@ def measure(fn, iters, warm=3):
     return wall, a.elapsed_time(b) / iters
 
 
+def peak_mib(fn):
+    """Peak allocated memory of one step above the level before it."""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated(DEV)
+    torch.cuda.reset_peak_memory_stats(DEV)
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated(DEV) - base) / 2 ** 20
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--autocast", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detr_time.jsonl"))
     args = ap.parse_args()
     for kind in (ARCTIC, ASSEMBLY):
@@ -88,24 +104,33 @@ def main():
         params = [p for m in [cls] + heads + (shared or []) for p in m.parameters()]
 
         def step():
-            logits, keys, outs = detr_heads(kind, hs, init, inter, cls, heads, shared)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.autocast):
+                logits, keys, outs = detr_heads(kind, hs, init, inter, cls, heads, shared)
             loss = sum(t.sum() for t in [logits] + keys + outs)
             torch.autograd.grad(loss, [hs] + params)
 
-        for route in ("composition", "dropin"):
+        routes = [("amp_composition", r) for r in range(3)] + [("amp_bf16_node", r) for r in range(3)] if args.autocast \
+            else [("composition", None), ("dropin", None)]
+        routes.sort(key=lambda x: (x[1] or 0))                       # autocast: the two routes interleaved, run by run
+        for route, run in routes:
             if args.only and route != args.only:
                 continue
             os.environ["MSDA_HEADS_FUSED"] = "0" if route == "composition" else "1"
+            os.environ["MSDA_HEADS_BF16"] = "1" if route == "amp_bf16_node" else "0"
             wall, gpu = measure(step, args.iters)
-            line = json.dumps({"tool": "detr_time", "model": kind, "route": route, "levels": L, "rows_per_level": B * Q,
-                               "hidden": C, "classes": K, "wall_ms_per_step": round(wall, 4),
-                               "gpu_event_ms_per_step": round(gpu, 4), "host_syncs_per_step": count_syncs(step),
-                               "kernels_per_step": count_kernels(step), "iters": args.iters,
-                               "device": torch.cuda.get_device_name(DEV)})
+            row = {"tool": "detr_time", "model": kind, "route": route, "levels": L, "rows_per_level": B * Q,
+                   "hidden": C, "classes": K, "wall_ms_per_step": round(wall, 4),
+                   "gpu_event_ms_per_step": round(gpu, 4), "host_syncs_per_step": count_syncs(step),
+                   "kernels_per_step": count_kernels(step), "iters": args.iters,
+                   "device": torch.cuda.get_device_name(DEV)}
+            if args.autocast:
+                row.update({"autocast": "bfloat16", "run": run, "peak_mib_per_step": round(peak_mib(step), 1)})
+            line = json.dumps(row)
             print(line, flush=True)
             with open(args.out, "a") as f:
                 f.write(line + "\n")
     os.environ.pop("MSDA_HEADS_FUSED", None)
+    os.environ.pop("MSDA_HEADS_BF16", None)
 
 
 if __name__ == "__main__":

@@ -107,6 +107,10 @@ SIGNATURES = {
     "msda_heads_workspace_bytes": "U ii l iii u",
     "msda_heads_forward_f32": "i ii l iiii u ppppppppp pppppp",
     "msda_heads_backward_f32": "i ii l iiii u ppppppppp ppppp pppppppp U p",
+    "msda_heads_bf16_supported": "i i",
+    "msda_heads_bf16_workspace_bytes": "U ii l iii u",
+    "msda_heads_forward_bf16": "i ii l iiii u ppppppppp pppppp",
+    "msda_heads_backward_bf16": "i ii l iiii u ppppppppp ppppp pppppppp U p",
     # SmoothNet and get_arctic_item's selection
     "msda_smoother_supported": "i iiiii",
     "msda_smoother_workspace_bytes": "U iiiiiii ppp i",
@@ -1413,6 +1417,58 @@ def heads_backward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidde
     g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
     g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
     _launch(dev, "msda_heads_backward_f32", "heads_backward", *args, hidden.data_ptr() if n_mlp else None,
+            sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(), _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared),
+            grad_hs.data_ptr(), _ptr_array(g_cls[0]), _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]),
+            _ptrs_or_none(g_sh[0]), _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4)
+    return grad_hs, g_cls, g_mlp, g_sh
+
+
+def heads_bf16_supported(C):
+    """msda_heads_bf16_supported (include/msda.h): 1 when the bf16-autocast heads kernels take hidden size C."""
+    return bool((_lib or load()).msda_heads_bf16_supported(int(C)))
+
+
+def heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
+    return int((_lib or load()).msda_heads_bf16_workspace_bytes(int(kind), int(L), int(M), int(C), int(K), int(n_mlp),
+                                                               int(flags)))
+
+
+def heads_forward_bf16(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
+    """msda_heads_forward_bf16: the heads under bf16 autocast from fp32 hs / parameters / references.  Returns (logits
+    [L, M, K], kp outputs [L, M, D] per MLP head, shared outputs [L, M, n_g], hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D])
+    with autocast's dtypes: logits and keypoints fp32 (ARCTIC) or bf16 (AssemblyHands), shared outputs and hidden bf16, sig
+    fp32.  At most 3 launches, no host synchronisation."""
+    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
+    D = 42 if kind == HEADS_ARCTIC else 63
+    dev, bf = hs.device, torch.bfloat16
+    out_dt = torch.float32 if kind == HEADS_ARCTIC else bf
+    logits = torch.empty(L, M, K, dtype=out_dt, device=dev)
+    kp = [torch.empty(L, M, D, dtype=out_dt, device=dev) for _ in range(n_mlp)]
+    sh = [torch.empty(L, M, n, dtype=bf, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
+    hidden = torch.empty(n_mlp, 2, L, M, C, dtype=bf, device=dev)
+    sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
+    _launch(dev, "msda_heads_forward_bf16", "heads_forward_bf16", *args, logits.data_ptr(), _ptrs_or_none(kp),
+            _ptrs_or_none(sh), hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None)
+    return logits, kp, sh, hidden, sig
+
+
+def heads_backward_bf16(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
+    """msda_heads_backward_bf16: (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases),
+    all fp32, every element written; the output gradients carry the outputs' dtypes.  At most 5 launches, no host
+    synchronisation."""
+    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
+    dev, bf = hs.device, torch.bfloat16
+    out_dt = torch.float32 if kind == HEADS_ARCTIC else bf
+    typed = [(grad_logits, out_dt)] + [(t, out_dt) for t in grad_kp] + [(t, bf) for t in grad_shared]
+    if not all(t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == dev for t, dt in typed + [(hidden, bf)]):
+        raise RuntimeError("detr_heads: expected contiguous CUDA output gradients of the outputs' dtypes")
+    ws = torch.empty(max(1, (heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags) + 3) // 4), dtype=torch.float32,
+                     device=dev)
+    grad_hs = torch.empty_like(hs)
+    g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
+    g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
+    g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
+    _launch(dev, "msda_heads_backward_bf16", "heads_backward_bf16", *args, hidden.data_ptr() if n_mlp else None,
             sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(), _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared),
             grad_hs.data_ptr(), _ptr_array(g_cls[0]), _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]),
             _ptrs_or_none(g_sh[0]), _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4)

@@ -30,6 +30,7 @@ namespace msda {
 namespace {
 
 #include "msda_tile.h"
+static_assert(kHBlock == kHeadsReduceBlock, "heads_reduce_kernel's block is what the bf16 form's plan counts with");
 
 // the reference's inverse_sigmoid (util/misc.py:614-618)
 __device__ __forceinline__ float inv_sigmoid(float x)

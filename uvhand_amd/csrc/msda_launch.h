@@ -318,6 +318,34 @@ int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan);
 int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream);
 int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream);
 
+// ---- the same heads under bf16 autocast, on the bf16 MFMA (msda_heads_bf16.hip; C entries msda_heads_*_bf16) ----
+// HeadsCall's operands with the dtypes of torch's bf16 autocast: hs, parameters, references, sig and every parameter gradient
+// fp32; hidden, the shared outputs and their gradients bf16; logits / keypoints and their gradients fp32 (ARCTIC) or bf16
+// (AssemblyHands).  plan_* checks the call and builds this thread's problem tables without launching, run_* launches them.
+constexpr int kHeadsReduceBlock = 256;                              // launch_heads_reduce's workgroup: elements per block
+struct HeadsBf16Call {
+    int kind, L, n_mlp, R, C, K;
+    long long M;
+    unsigned flags;
+    const float *hs, *init_ref, *inter_ref;
+    const float *const *cls_w, *const *cls_b, *const *mlp_w, *const *mlp_b, *const *shared_w, *const *shared_b;
+    void *logits, *const *kp_out;
+    uint16_t *const *shared_out, *hidden;
+    float *sig;
+    const void *grad_logits, *const *grad_kp;
+    const uint16_t *const *grad_shared;
+    float *grad_hs, *const *grad_cls_w, *const *grad_cls_b, *const *grad_mlp_w, *const *grad_mlp_b, *const *grad_shared_w,
+        *const *grad_shared_b;
+    void *ws;
+    unsigned long long ws_bytes;
+};
+bool heads_bf16_supported(int C);
+unsigned long long heads_bf16_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
+int heads_bf16_plan_forward(const HeadsBf16Call &c);
+int heads_bf16_plan_backward(const HeadsBf16Call &c);
+int heads_bf16_run_forward(hipStream_t stream);
+int heads_bf16_run_backward(hipStream_t stream);
+
 // ---- Swin window attention, head_dim 32, windows up to 12 x 12 (msda_swin.hip; C entries msda_swin_attn_*) ----
 bool swin_supported(int B, int H, int W, int C, int nH, int ws, int shift);
 unsigned long long swin_workspace_bytes(int B, int H, int W, int C, int nH, int ws, int shift, int which);

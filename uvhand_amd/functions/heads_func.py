@@ -4,14 +4,21 @@
 their reference epilogue and (ARCTIC) the six shared pose / shape / camera Linears, and returns the reference's
 ``torch.stack``-ed tensors.  On CUDA fp32 it is ``_DetrHeadsFunction``: three forward launches and five backward launches
 (``csrc/msda_heads.hip``) over every head of every level, with no host synchronisation.  Everything else runs
-``detr_heads_reference``, a torch restatement of the reference's composition: CPU tensors, bf16 autocast (the reference
+``detr_heads_reference``, a torch restatement of the reference's composition: CPU tensors, autocast (the reference
 under ``--amp``: logits go ``.to(float32)`` for ARCTIC, the rest stays bf16), hidden sizes the kernels do not take,
-references that require grad, heads whose levels share some modules but not all, and ``MSDA_HEADS_FUSED=0`` (A/B knob)."""
+references that require grad, heads whose levels share some modules but not all, and ``MSDA_HEADS_FUSED=0`` (A/B knob).
+
+``MSDA_HEADS_BF16=1`` (read at call time, off by default) sends bf16 autocast over fp32 ``hs``, parameters and references
+to the same node on the bf16 MFMA (``csrc/msda_heads_bf16.hip``): the same launch counts, the composition's output dtypes and
+forward roundings, hidden activations saved as bf16, ``hs`` and the weights rounded in the kernels' own loads (no cast
+kernels), and fp32 ``grad_hs`` / parameter gradients that are not rounded to bf16 on the way.  fp16 autocast, bf16 ``hs``
+and hidden sizes with ``C % 8 != 0`` keep the composition."""
 import os
 
 import torch
 
 from .. import _native
+from .linear_func import _autocast_dtype
 
 ARCTIC, ASSEMBLY = "arctic", "assembly"
 _KIND = {ARCTIC: _native.HEADS_ARCTIC, ASSEMBLY: _native.HEADS_ASSEMBLY}
@@ -76,6 +83,10 @@ def _fused_enabled():
     return os.environ.get("MSDA_HEADS_FUSED", "1") != "0"     # A/B knob: 0 = the torch restatement
 
 
+def _bf16_enabled():
+    return os.environ.get("MSDA_HEADS_BF16", "0") not in ("", "0")     # opt-in: the node under bf16 autocast
+
+
 def _levels(mods, L):
     """([modules], shared) for levels < L: one module repeated, or L distinct ones; None for anything in between."""
     mods = list(mods)[:L]
@@ -90,7 +101,10 @@ def _fused_plan(kind, hs, init_reference, inter_references, cls_embed, mlps, sha
     """The kernels' operands, or None where the composition runs."""
     if not (_fused_enabled() and hs.is_cuda and hs.dtype == torch.float32 and hs.dim() == 4):
         return None
-    if torch.is_autocast_enabled() or not _native.heads_supported(hs.shape[-1]):
+    bf16 = torch.is_autocast_enabled()
+    if bf16 and not (_bf16_enabled() and _autocast_dtype() == torch.bfloat16):
+        return None
+    if not (_native.heads_bf16_supported(hs.shape[-1]) if bf16 else _native.heads_supported(hs.shape[-1])):
         return None
     L = hs.shape[0]
     if not 1 <= L <= MAX_LEVELS or (kind == ARCTIC and len(mlps) not in (0, 2)) or (kind == ASSEMBLY and len(mlps) != 1):
@@ -130,20 +144,21 @@ def _fused_plan(kind, hs, init_reference, inter_references, cls_embed, mlps, sha
             return None
         if R not in ((42,) if kind == ARCTIC else (2, 42)):
             return None
-    meta = (_KIND[kind], flags, len(cls_w), len(mlp_w), len(sh_w))
+    meta = (_KIND[kind], flags, len(cls_w), len(mlp_w), len(sh_w), bf16)
     return meta, params
 
 
 class _DetrHeadsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, hs, init_ref, inter_ref, *params):
-        kind, flags, n_cls, n_mlp, n_sh = meta
+        kind, flags, n_cls, n_mlp, n_sh, bf16 = meta
         L, B, Q, C = hs.shape
         hs3 = hs.contiguous().view(L, B * Q, C)
         init3 = init_ref.contiguous() if init_ref is not None else None
         inter3 = inter_ref[:L - 1].contiguous() if inter_ref is not None and L > 1 else None
         groups = _split(params, n_cls, n_mlp, n_sh)
-        logits, kp, sh, hidden, sig = _native.heads_forward(kind, hs3, init3, inter3, *groups, flags)
+        run = _native.heads_forward_bf16 if bf16 else _native.heads_forward
+        logits, kp, sh, hidden, sig = run(kind, hs3, init3, inter3, *groups, flags)
         ctx.meta = meta
         ctx.save_for_backward(hs3, init3, inter3, hidden, sig, *params)
         ctx.shape = (L, B, Q)
@@ -153,14 +168,14 @@ class _DetrHeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        kind, flags, n_cls, n_mlp, n_sh = ctx.meta
+        kind, flags, n_cls, n_mlp, n_sh, bf16 = ctx.meta
         hs3, init3, inter3, hidden, sig, *params = ctx.saved_tensors
         L, B, Q = ctx.shape
         g = [x.contiguous().view(L, B * Q, x.shape[-1]) for x in grads]
         grad_logits, grad_kp, grad_sh = g[0], g[1:1 + ctx.n_kp], g[1 + ctx.n_kp:]
         groups = _split(params, n_cls, n_mlp, n_sh)
-        grad_hs, g_cls, g_mlp, g_sh = _native.heads_backward(kind, hs3, init3, inter3, *groups, flags, hidden, sig,
-                                                             grad_logits, grad_kp, grad_sh)
+        run = _native.heads_backward_bf16 if bf16 else _native.heads_backward
+        grad_hs, g_cls, g_mlp, g_sh = run(kind, hs3, init3, inter3, *groups, flags, hidden, sig, grad_logits, grad_kp, grad_sh)
         pgrads = g_cls[0] + g_cls[1] + g_mlp[0] + g_mlp[1] + g_sh[0] + g_sh[1]
         return (None, grad_hs.view(L, B, Q, -1), None, None) + tuple(pgrads)
 

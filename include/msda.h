@@ -675,6 +675,15 @@ int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_m
  * (left, right, object query).  The object rule runs over classes 1 .. obj_end - 1 (obj_end = cfg.hand_idx[0]).
  *   msda_arctic_item_forward_f32   one launch.  msda_arctic_item_backward_f32: one launch; writes every element of the six
  *       source gradients; grad_out entries may be NULL (no gradient).
+ * Grouped selection (arctic_tools/process.py:20-70 for n_sets prediction sets of one shape, 1 <= n_sets <= 8): logits a HOST
+ * array of n_sets fp32 [bs, Q, K]; sources a HOST array of n_sets * 6 (set-major, the order above), all fp32 (src_bf16 = 0) or
+ * all bf16 bits (src_bf16 = 1; rows need 2-byte alignment only); out a HOST array of n_sets * 9 fp32 tensors, for bf16 sources
+ * the gathered values widened exactly; idx [n_sets, bs, 3].
+ *   msda_arctic_item_many_forward  one launch, grid (bs, n_sets); the rule, and for fp32 sources the bits, of
+ *       msda_arctic_item_forward_f32 per set.
+ *   msda_arctic_item_many_backward one launch; grad_out a HOST array of n_sets * 9 fp32 tensors (entries may be NULL);
+ *       grad_sources a HOST array of n_sets * 6 tensors of the sources' dtype, every element written.  A row's gradients are
+ *       summed in fp32, left hand first, and a bf16 result is rounded once, to nearest even.
  * Fixed summation order, no atomics: bitwise reproducible.  No allocation, no synchronisation; argument errors before any
  * launch. */
 int msda_smoother_supported(int T, int O, int H, int R, int num_blocks);
@@ -696,6 +705,11 @@ int msda_arctic_item_forward_f32(int bs, int Q, int K, int obj_end, int hand_l, 
                                  const float *const *sources, float *const *out, int64_t *idx, msda_stream_t stream);
 int msda_arctic_item_backward_f32(int bs, int Q, const int64_t *idx, const float *const *grad_out, float *const *grad_sources,
                                   msda_stream_t stream);
+int msda_arctic_item_many_forward(int n_sets, int bs, int Q, int K, int obj_end, int hand_l, int hand_r, int src_bf16,
+                                  const float *const *logits, const void *const *sources, float *const *out, int64_t *idx,
+                                  msda_stream_t stream);
+int msda_arctic_item_many_backward(int n_sets, int bs, int Q, int src_bf16, const int64_t *idx, const float *const *grad_out,
+                                   void *const *grad_sources, msda_stream_t stream);
 
 /* ---- Swin window attention (models/swin_transformer.py:126-142 WindowAttention.forward, :210-240 SwinTransformerBlock's pad /
  * roll / partition / reverse / crop, :339-357 BasicLayer's shift mask) for head_dim 32 -----------------------------------------

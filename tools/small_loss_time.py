@@ -11,7 +11,14 @@ all sets: one mano_many, one objects_many, one loss node).  Per route: wall ms a
 move (read inputs, write outputs, from the shapes) with their time at the HBM rate.  One JSON line per route, on stdout and
 appended to --out (default profiles/small_loss_time.jsonl).
 
-    python tools/small_loss_time.py [--iters N] [--batch 32] [--obj-len 4000] [--only ROUTE] [--out FILE]"""
+    python tools/small_loss_time.py [--iters N] [--batch 32] [--obj-len 4000] [--only ROUTE] [--out FILE]
+
+`--autocast` times the amp step instead: the six sets as DETR outputs at Q = 300 (fp32 logits, bf16
+pred_cams / pred_mano_params / pred_obj_params), ArcticSmallLoss.many forward + backward under bf16 autocast with the selection
+inside the timed step.  Routes: `amp_knob_off` (MSDA_SMALL_LOSS_BF16 unset: the restatements), `amp_knob_on` (the grouped bf16
+selection and the fp32 nodes) and `fp32_many` (no autocast, `.float()` sources, per-set selection), --runs times each,
+interleaved.  A last line, `amp_distance`, gives per key the largest relative distance of the two amp routes from
+small_loss_reference in fp64 on the same bf16-valued inputs."""
 import argparse
 import json
 import os
@@ -28,7 +35,8 @@ import small_loss_inputs as SI  # noqa: E402
 from smoother_time import count_kernels, count_syncs, measure  # noqa: E402
 from uvhand_amd.mano import MANO  # noqa: E402
 from uvhand_amd.object_tensors import ObjectTensors  # noqa: E402
-from uvhand_amd.small_loss import KEYS, compute_small_loss, small_loss_many, small_loss_reference  # noqa: E402
+from uvhand_amd.arctic_item import get_arctic_item_reference  # noqa: E402
+from uvhand_amd.small_loss import KEYS, ArcticSmallLoss, compute_small_loss, small_loss_many, small_loss_reference  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 SETS = 6
@@ -44,12 +52,94 @@ def bytes_moved(B, L):
     return obj + loss
 
 
+def detr_sets(preds, Q, seed=33):
+    """Per set DETR outputs whose every query holds that frame's prediction plus a little noise, rounded to bf16: whichever
+    queries the random logits select, the small losses see inputs of the usual size."""
+    g = torch.Generator().manual_seed(seed)
+    sets = []
+    for p in preds:
+        (rl, rr, ro), (pl, pr), (bl, br), (rot, rad) = [[t.detach().cpu() for t in grp] for grp in p]
+        B = rl.shape[0]
+        spread = lambda a, b: (torch.where(torch.rand(B, Q, 1, generator=g) < 0.5, a[:, None, :], b[:, None, :])  # noqa: E731
+                               + 0.01 * torch.randn(B, Q, a.shape[1], generator=g))
+        srcs = [spread(rl, rr), spread(ro, ro), spread(pl, pr), spread(bl, br), spread(rad.reshape(B, 1), rad.reshape(B, 1)),
+                spread(rot.reshape(B, 3), rot.reshape(B, 3))]
+        leaf = lambda t: t.to(torch.bfloat16).to(DEV).requires_grad_(True)  # noqa: E731
+        hc, oc, mp, ms, orad, orot = [leaf(t) for t in srcs]
+        sets.append({"pred_logits": (torch.randn(B, Q, 14, generator=g) * 2).to(DEV), "pred_cams": [hc, oc],
+                     "pred_mano_params": [mp, ms], "pred_obj_params": [orad, orot]})
+    return sets
+
+
+def _sources(o):
+    return o["pred_cams"] + o["pred_mano_params"] + o["pred_obj_params"]
+
+
+def autocast_routes(args, m, preds, gt, meta):
+    import types
+    B, L, Q = args.batch, args.obj_len, 300
+    cfg = types.SimpleNamespace(hand_idx=[12, 13])
+    crit_args = types.SimpleNamespace(img_res=SI.IMG_RES, device=DEV)
+    small = ArcticSmallLoss(m, cfg)
+    suffixes = [""] + ["_%d" % i for i in range(SETS - 1)]
+    bf16_sets = detr_sets(preds, Q)
+    f32_sets = [dict(o, pred_cams=[t.detach().float().requires_grad_(True) for t in o["pred_cams"]],
+                     pred_mano_params=[t.detach().float().requires_grad_(True) for t in o["pred_mano_params"]],
+                     pred_obj_params=[t.detach().float().requires_grad_(True) for t in o["pred_obj_params"]]) for o in bf16_sets]
+
+    def run(route, backward=True):
+        sets = f32_sets if route == "fp32_many" else bf16_sets
+        if route == "amp_knob_on":
+            os.environ["MSDA_SMALL_LOSS_BF16"] = "1"
+        else:
+            os.environ.pop("MSDA_SMALL_LOSS_BF16", None)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=route != "fp32_many"):
+            ds = small.many(sets, gt, meta, crit_args, suffixes)
+            loss = sum(v.sum() for d in ds for v in d.values())
+        if backward:
+            torch.autograd.grad(loss, [t for o in sets for t in _sources(o)], allow_unused=True)
+        return ds
+
+    routes = ("amp_knob_off", "amp_knob_on", "fp32_many")
+    with open(args.out, "a") as f:
+        for rep in range(args.runs):
+            for route in routes:
+                if args.only and route != args.only:
+                    continue
+                step = lambda: run(route)  # noqa: E731
+                wall, gpu = measure(step, args.iters)
+                line = json.dumps({"tool": "small_loss_time", "mode": "autocast", "route": route, "run": rep, "sets": SETS,
+                                   "batch": B, "queries": Q, "obj_len": L, "wall_ms_per_step": round(wall, 4),
+                                   "gpu_event_ms_per_step": round(gpu, 4), "host_syncs_per_step": count_syncs(step),
+                                   "kernels_per_step": count_kernels(step), "iters": args.iters,
+                                   "device": torch.cuda.get_device_name(DEV)})
+                print(line, flush=True)
+                f.write(line + "\n")
+        # for the record: what the autocast composition's bf16 products cost, against fp64 on the same bf16-valued inputs
+        with torch.no_grad():
+            ref = [small_loss_reference(get_arctic_item_reference(o, cfg), gt, meta, m, SI.IMG_RES, dtype=torch.float64)
+                   for o in f32_sets]
+            dist = {}
+            for route in routes[:2]:
+                ds = run(route, backward=False)
+                dist[route] = {k: max(float(((d[k + sfx].double().reshape(-1) - r[k].reshape(-1)).abs()
+                                             / r[k].reshape(-1).abs().clamp_min(1e-30)).max())
+                                      for d, r, sfx in zip(ds, ref, suffixes)) for k in KEYS}
+        line = json.dumps({"tool": "small_loss_time", "mode": "autocast", "route": "amp_distance", "sets": SETS, "batch": B,
+                           "queries": Q, "obj_len": L, "max_rel_distance_from_fp64": dist})
+        print(line, flush=True)
+        f.write(line + "\n")
+    os.environ.pop("MSDA_SMALL_LOSS_BF16", None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--obj-len", type=int, default=4000)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--autocast", action="store_true", help="the amp step: knob off, knob on, and the fp32 many route")
+    ap.add_argument("--runs", type=int, default=3, help="--autocast: runs of each route, interleaved")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "small_loss_time.jsonl"))
     args = ap.parse_args()
     B, L = args.batch, args.obj_len
@@ -66,6 +156,8 @@ def main():
     for s in range(SETS):
         p = pred if s == 0 else SI.case_inputs("partial", B=B, seed=31 + 10 * s, objects=meta["query_names"])[0]
         preds.append(SI.unflat_pred([t.to(DEV).requires_grad_(True) for t in SI.flat_pred(p)]))
+    if args.autocast:
+        return autocast_routes(args, m, preds, gt, meta)
     leaves = [t for p in preds for t in SI.flat_pred(p)]
     nbytes = bytes_moved(B, L)
     for route in ("restatement", "dropin", "many"):

@@ -119,6 +119,8 @@ SIGNATURES = {
     "msda_smoother_dropout_mask_f32": "i p iiii f pp",
     "msda_arctic_item_forward_f32": "i iiiiii ppppp",
     "msda_arctic_item_backward_f32": "i ii pppp",
+    "msda_arctic_item_many_forward": "i iiiiiiii ppppp",
+    "msda_arctic_item_many_backward": "i iiii pppp",
     # Swin window attention
     "msda_swin_attn_supported": "i iiiiiii",
     "msda_swin_attn_workspace_bytes": "U iiiiiiii",
@@ -1587,6 +1589,55 @@ def arctic_item_backward(idx, Q, grad_outs):
     gsrc = [torch.empty(bs, Q, w, dtype=torch.float32, device=dev) for w in ARCTIC_ITEM_WIDTHS]
     garr = (_VP * len(grad_outs))(*[g.data_ptr() if g is not None else None for g in grad_outs])
     _launch(dev, "msda_arctic_item_backward_f32", "arctic_item_backward", bs, int(Q), idx.data_ptr(), garr, _ptr_array(gsrc))
+    return gsrc
+
+
+def _arctic_item_src_dtype(what, dev, tensors):
+    """The one dtype (fp32 or bf16) of contiguous CUDA tensors on `dev`."""
+    dtype = tensors[0].dtype
+    if dtype not in (torch.float32, torch.bfloat16) or not all(
+            t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() for t in tensors):
+        raise RuntimeError("%s: expected contiguous CUDA sources on one device, all fp32 or all bf16" % what)
+    return dtype
+
+
+def arctic_item_many_forward(logits, sources, obj_end, hand_l, hand_r):
+    """msda_arctic_item_many_forward for per-set lists: logits[s] fp32 [bs, Q, K] and sources[s] the six tensors, all fp32 or
+    all bf16.  Returns (per set the nine fp32 outputs, idx [n_sets, bs, 3] int64).  One launch."""
+    n = len(logits)
+    bs, Q, K = logits[0].shape
+    dev = logits[0].device
+    _check_f32("arctic_item_many", dev, logits)
+    flat = [t for grp in sources for t in grp]
+    dtype = _arctic_item_src_dtype("arctic_item_many", dev, flat)
+    if len(sources) != n or any(tuple(l.shape) != (bs, Q, K) for l in logits) or any(
+            len(grp) != 6 or any(tuple(s.shape) != (bs, Q, w) for s, w in zip(grp, ARCTIC_ITEM_WIDTHS)) for grp in sources):
+        raise RuntimeError("arctic_item_many: every set needs logits [bs, Q, K] and sources [bs, Q, w] with w = %s"
+                           % (ARCTIC_ITEM_WIDTHS,))
+    outs = [[torch.empty(bs, ARCTIC_ITEM_WIDTHS[s], dtype=torch.float32, device=dev) for s in ARCTIC_ITEM_OUT_SOURCES]
+            for _ in range(n)]
+    idx = torch.empty(n, bs, 3, dtype=torch.int64, device=dev)
+    _launch(dev, "msda_arctic_item_many_forward", "arctic_item_many_forward", n, bs, Q, K, int(obj_end), int(hand_l),
+            int(hand_r), int(dtype == torch.bfloat16), _ptr_array(logits), _ptr_array(flat),
+            _ptr_array([t for grp in outs for t in grp]), idx.data_ptr())
+    return outs, idx
+
+
+def arctic_item_many_backward(idx, Q, grad_outs, dtype):
+    """msda_arctic_item_many_backward: per set the six source gradients [bs, Q, w] of `dtype` (fp32 or bf16), every element
+    written, from the flat list of n_sets * 9 fp32 output gradients (None: no gradient).  One launch."""
+    dev = idx.device
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 3 and idx.shape[2] == 3
+            and len(grad_outs) == 9 * idx.shape[0] and dtype in (torch.float32, torch.bfloat16)):
+        raise RuntimeError("arctic_item_many_backward: idx must be a contiguous int64 CUDA tensor [n_sets, bs, 3] with nine "
+                           "output gradients per set")
+    n, bs = idx.shape[:2]
+    if not all(g is None or (_f32_cuda(g) and g.device == dev and tuple(g.shape) == (bs, ARCTIC_ITEM_WIDTHS[ARCTIC_ITEM_OUT_SOURCES[i % 9]]))
+               for i, g in enumerate(grad_outs)):
+        raise RuntimeError("arctic_item_many_backward: expected contiguous fp32 CUDA output gradients [bs, w]")
+    gsrc = [[torch.empty(bs, Q, w, dtype=dtype, device=dev) for w in ARCTIC_ITEM_WIDTHS] for _ in range(n)]
+    _launch(dev, "msda_arctic_item_many_backward", "arctic_item_many_backward", n, bs, int(Q), int(dtype == torch.bfloat16),
+            idx.data_ptr(), _ptr_table(grad_outs), _ptr_array([t for grp in gsrc for t in grp]))
     return gsrc
 
 

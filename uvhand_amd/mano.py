@@ -10,7 +10,9 @@ forward launch and two backward launches (``csrc/msda_mano.hip``) for all of the
 no host synchronisation; the node captures in a graph.  The kernels need fp32 CUDA tensors, model tensors that do not require
 grad, at most ``MANO_MAX_GROUPS`` calls over at most ``MANO_MAX_LAYERS`` layers.  Everything else runs ``mano_reference``, a
 torch restatement of smplx's MANO forward and ``lbs`` in any dtype: CPU tensors, non-fp32 inputs, autocast, model tensors
-that require grad, anything over the limits, and ``MSDA_MANO_FUSED=0`` (A/B knob)."""
+that require grad, anything over the limits, and ``MSDA_MANO_FUSED=0`` (A/B knob).  With ``MSDA_SMALL_LOSS_BF16=1`` (read at
+call time, off by default) bf16 autocast alone no longer does: the node calls the C ABI on its fp32 inputs, so it returns the
+bits it returns outside the region.  fp16 autocast keeps the restatement."""
 import os
 
 import numpy as np
@@ -18,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _native
+from ._autocast import autocast_refuses
 
 MANO_MAX_GROUPS = _native.MANO_MAX_GROUPS       # calls per mano_many node; more run the restatement
 MANO_MAX_LAYERS = _native.MANO_MAX_LAYERS       # distinct layers per node
@@ -120,7 +123,7 @@ def _layer_ok(layer, dev):
 
 def _fused_plan(calls):
     """(dims, layers, group_layer, group_bcast, inputs) for the kernels, or None where the restatement runs."""
-    if not (_fused_enabled() and calls) or torch.is_autocast_enabled() or len(calls) > MANO_MAX_GROUPS:
+    if not (_fused_enabled() and calls) or autocast_refuses() or len(calls) > MANO_MAX_GROUPS:
         return None
     layers = []
     for c in calls:

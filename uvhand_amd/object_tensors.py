@@ -15,7 +15,9 @@ and go up with a pinned ``non_blocking`` copy.  For graph capture, ``obj_idx=`` 
 ``kp3d`` of every call and one backward launch gives the ``angles``, ``global_orient`` (and ``transl``) gradients with
 fixed-order reductions (``csrc/msda_small_loss.hip``).  The kernels need fp32 CUDA inputs and model tensors that do not
 require grad, at most ``OBJECT_MAX_GROUPS`` calls and the model sizes of ``msda_object_supported``; everything else (CPU
-tensors, other dtypes, autocast, ``MSDA_OBJECT_FUSED=0``) runs ``object_tensors_reference``, a torch restatement.
+tensors, other dtypes, autocast, ``MSDA_OBJECT_FUSED=0``) runs ``object_tensors_reference``, a torch restatement.  With
+``MSDA_SMALL_LOSS_BF16=1`` (read at call time, off by default) bf16 autocast alone no longer does: the node calls the C ABI on
+its fp32 inputs and returns the bits it returns outside the region; fp16 autocast keeps the restatement.
 
 Kept from the reference: ``transl`` is added in metres (its ``*1000`` in ``_sanity_check`` changes only a local variable);
 articulation is ``q p q*`` about -z with ``q`` from pytorch3d's ``axis_angle_to_quaternion`` (the ``|theta| < 1e-6`` series),
@@ -29,6 +31,7 @@ import torch
 from torch import nn
 
 from . import _native
+from ._autocast import autocast_refuses
 
 OBJECT_MAX_GROUPS = _native.OBJECT_MAX_GROUPS
 OUTPUT_KEYS = ("diameter", "f", "f_len", "v_len", "v", "mask", "v_sub", "parts_ids", "parts_sub_ids", "bbox3d", "kp3d")
@@ -151,7 +154,7 @@ class _ObjectFunction(torch.autograd.Function):
 
 def _fused_plan(calls):
     """(dims, model, lens, inputs) for the kernels, or None where the restatement runs."""
-    if not (_fused_enabled() and calls) or torch.is_autocast_enabled() or len(calls) > OBJECT_MAX_GROUPS:
+    if not (_fused_enabled() and calls) or autocast_refuses() or len(calls) > OBJECT_MAX_GROUPS:
         return None
     layer = calls[0][0]
     if any(c[0] is not layer for c in calls):

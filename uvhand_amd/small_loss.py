@@ -23,6 +23,14 @@ orders: two runs, and grouped against per-set calls, are bitwise equal.
 pytorch3d, cv2 or loguru), in fp32 as the reference or in fp64 as the tests' yardstick.  It runs for CPU tensors, non-fp32
 inputs, autocast, geometries over the kernel limits, more than ``SMALL_LOSS_MAX_SETS`` sets and ``MSDA_SMALL_LOSS_FUSED=0``.
 
+``MSDA_SMALL_LOSS_BF16=1`` (read at call time, off by default) keeps an amp step on the kernels.  Under bf16 autocast ARCTIC's
+``pred_cams`` / ``pred_mano_params`` / ``pred_obj_params`` are bf16 and its logits fp32: ``ArcticSmallLoss.many`` then selects
+for every set with ``get_arctic_item_many`` (one launch instead of one per set; fp32 outputs, the bf16 values widened exactly),
+and bf16 autocast alone no longer sends ``mano_many``, ``objects_many`` and the loss node to their restatements.  They call the
+C ABI on fp32 tensors, and the Python glue between them runs with autocast disabled, so values are those of the same step
+outside autocast on ``.float()`` predictions, bit for bit, and the bf16 leaves' gradients are that step's rounded once.  fp16
+autocast and bf16 inputs to the MANO / object / loss nodes themselves keep the restatement.
+
 The first deviation: a skipped hand block (no frame with ``is_valid * hand_valid``) returns shape ``[1]`` zeros where the
 reference returns 0-d zeros, since a data-dependent shape would need a sync.  ``loss/cd`` and ``loss/object/v3d_smoothing``
 are 0-d as in the reference.  A second one: with a single frame the reference's ``obj_smt_loss`` raises (it reads ``v[1]``);
@@ -32,7 +40,8 @@ import os
 import torch
 
 from . import _native
-from .arctic_item import get_arctic_item
+from ._autocast import autocast_refuses, no_autocast, small_loss_bf16_enabled
+from .arctic_item import get_arctic_item, get_arctic_item_many
 from .mano import MANO, mano_many
 from .object_tensors import ObjectTensors, axis_angle_to_matrix, objects_many
 
@@ -244,7 +253,7 @@ def _flat_pred(pred):
 
 
 def _fused_ok(preds, gt, models):
-    if not (_fused_enabled() and preds) or torch.is_autocast_enabled() or len(preds) > SMALL_LOSS_MAX_SETS:
+    if not (_fused_enabled() and preds) or autocast_refuses() or len(preds) > SMALL_LOSS_MAX_SETS:
         return False
     ts = [t for p in preds for t in _flat_pred(p)]
     dev = ts[0].device
@@ -300,7 +309,8 @@ def _fused(preds, gt, meta_info, models, img_res):
 def small_loss_many(preds, gt, meta_info, pre_process_models, img_res):
     """One 19-key dict per set of ``preds`` (each in get_arctic_item's structure)."""
     if _fused_ok(preds, gt, pre_process_models):
-        out = _fused(preds, gt, meta_info, pre_process_models, img_res)
+        with no_autocast():          # the nodes call the C ABI; no torch op of the glue between them is autocast
+            out = _fused(preds, gt, meta_info, pre_process_models, img_res)
         if out is not None:
             return out
     return [small_loss_reference(p, gt, meta_info, pre_process_models, img_res) for p in preds]
@@ -323,6 +333,9 @@ class ArcticSmallLoss:
         return self.many([outputs], targets, meta_info, args, [suffix])[0]
 
     def many(self, sets, targets, meta_info, args, suffixes):
-        preds = [get_arctic_item(o, self.cfg, getattr(args, "device", None)) for o in sets]
+        if small_loss_bf16_enabled():
+            preds = get_arctic_item_many(sets, self.cfg, getattr(args, "device", None))
+        else:
+            preds = [get_arctic_item(o, self.cfg, getattr(args, "device", None)) for o in sets]
         dicts = small_loss_many(preds, targets, meta_info, self.pre_process_models, args.img_res)
         return [{k + sfx: v for k, v in d.items()} for d, sfx in zip(dicts, suffixes)]

@@ -1,4 +1,5 @@
-"""C ABI of the DETR heads entries (csrc/msda_heads.hip; added without an ABI version bump): the symbols are exported and
+"""C ABI of the DETR heads entries, fp32 and bf16 autocast (one planner and one argument check in csrc/msda_heads.hip serve
+both; added without an ABI version bump): the symbols are exported, the workspace sizes are what they have always been, and
 argument errors come back as codes from the host-side checks before anything is launched (msda_launch_count unchanged) — so
 no GPU is needed, and the fake device addresses below never reach a kernel."""
 import ctypes
@@ -34,15 +35,15 @@ def _args(kind=0, L=6, M=9600, C=256, K=14, n_mlp=2, R=42, flags=0, hs=P, init=P
     return [kind, L, M, C, K, n_mlp, R, flags, hs, init, inter, cls, cls, mlp, mlp, sh, sh]
 
 
-def _fwd(lib, logits=P, kp=None, sh_out=None, hidden=P, sig=P, **kw):
-    return lib.msda_heads_forward_f32(*_args(**kw), logits, kp if kp is not None else _ptrs(2),
-                                      sh_out if sh_out is not None else _ptrs(6), hidden, sig, None)
+def _fwd(lib, logits=P, kp=None, sh_out=None, hidden=P, sig=P, form="f32", **kw):
+    return getattr(lib, "msda_heads_forward_" + form)(*_args(**kw), logits, kp if kp is not None else _ptrs(2),
+                                                      sh_out if sh_out is not None else _ptrs(6), hidden, sig, None)
 
 
-def _bwd(lib, glog=P, gkp=None, ghs=P, gw=None, ws=P, ws_bytes=1 << 40, **kw):
+def _bwd(lib, glog=P, gkp=None, ghs=P, gw=None, ws=P, ws_bytes=1 << 40, hidden=P, form="f32", **kw):
     g = gw if gw is not None else _ptrs(48)
-    return lib.msda_heads_backward_f32(*_args(**kw), P, P, glog, gkp if gkp is not None else _ptrs(2), _ptrs(6), ghs,
-                                       g, g, g, g, g, g, ws, ws_bytes, None)
+    return getattr(lib, "msda_heads_backward_" + form)(*_args(**kw), hidden, P, glog, gkp if gkp is not None else _ptrs(2),
+                                                       _ptrs(6), ghs, g, g, g, g, g, g, ws, ws_bytes, None)
 
 
 def test_entries_exported_abi_unchanged(lib):
@@ -97,3 +98,100 @@ def test_backward_argument_errors(lib):
     assert _bwd(lib, L=0) == ERR_ARGUMENT
     assert _bwd(lib, kind=-1) == ERR_ARGUMENT
     assert lib.msda_launch_count() == n0
+
+
+# ---- the one argument check behind the fp32 and the bf16 entries ---------------------------------------------------------------
+FORMS = ("f32", "bf16")
+NULL = "msda_heads: null pointer"
+KIND = "msda_heads: kind must be 0 (ARCTIC) or 1 (AssemblyHands)"
+LEVELS = "msda_heads: need 1 <= L <= 8 levels"
+SIZES = "msda_heads: need M >= 1, K >= 1 and a hidden size C with C % 4 == 0, 4 <= C <= 4096"
+N_MLP = "msda_heads: n_mlp must be 0 or 2 (ARCTIC) or 1 (AssemblyHands)"
+REF = "msda_heads: reference width R must be 42 (ARCTIC) or 2 / 42 (AssemblyHands)"
+WIDTH_BF16 = "msda_heads_bf16: need a hidden size C with C % 8 == 0, 8 <= C <= 4096"
+ALIGN = "msda_heads_bf16: hs, hidden and the weights must be 16-byte aligned"
+WS_ALIGN = "msda_heads_bf16: the workspace must be 16-byte aligned"
+WS_SMALL = {"f32": "msda_heads: workspace smaller than msda_heads_workspace_bytes",
+            "bf16": "msda_heads_bf16: workspace smaller than msda_heads_bf16_workspace_bytes"}
+
+# what test_forward_argument_errors / test_backward_argument_errors assert of the fp32 entries, with the whole message: the
+# calls that both forms must refuse in the same words (a bad width and a short workspace name the form: tested apart)
+BAD_FORWARD = [
+    (dict(kind=2), KIND), (dict(L=0), LEVELS), (dict(L=9), LEVELS), (dict(M=0), SIZES), (dict(K=0), SIZES),
+    (dict(n_mlp=1), N_MLP), (dict(kind=1, n_mlp=2), N_MLP), (dict(R=2), REF), (dict(kind=1, n_mlp=1, R=3), REF),
+    (dict(flags=4), "msda_heads: unknown flags"), (dict(M=1 << 30), "msda_heads: tensors beyond 2^31 elements"),
+    (dict(hs=None), NULL), (dict(init=None), NULL), (dict(inter=None), NULL), (dict(cls=_ptrs(8, 0)), NULL),
+    (dict(mlp=_ptrs(48, 0)), NULL), (dict(sh=_ptrs(6, 0)), NULL), (dict(logits=None), NULL), (dict(kp=_ptrs(2, 0)), NULL),
+    (dict(hidden=None), NULL),
+]
+BAD_BACKWARD = [
+    (dict(glog=None), NULL), (dict(ghs=None), NULL), (dict(gkp=_ptrs(2, 0)), NULL), (dict(gw=_ptrs(48, 0)), NULL),
+    (dict(ws=None), NULL), (dict(L=0), LEVELS), (dict(kind=-1), KIND),
+]
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_both_forms_refuse_the_same_calls_in_the_same_words(lib, form):
+    n0 = lib.msda_launch_count()
+    for call, table in ((_fwd, BAD_FORWARD), (_bwd, BAD_BACKWARD)):
+        for kw, message in table:
+            assert call(lib, form=form, **kw) == ERR_ARGUMENT and _err(lib) == message, (form, kw)
+    assert lib.msda_launch_count() == n0
+
+
+def test_each_form_names_its_own_widths(lib):
+    n0 = lib.msda_launch_count()
+    for call in (_fwd, _bwd):
+        assert call(lib, C=30) == ERR_ARGUMENT and _err(lib) == SIZES
+        for C in (30, 36, 4, 4104):                                     # the bf16 form tests its width before anything else
+            assert call(lib, form="bf16", C=C, kind=7, hs=None) == ERR_ARGUMENT and _err(lib) == WIDTH_BF16
+    assert lib.msda_launch_count() == n0
+
+
+def test_bf16_alignment_and_workspace_errors(lib):
+    """The bf16 form's own checks come after the shared ones: 16-byte alignment of hs, hidden and every weight, then (backward)
+    a workspace that is there, aligned and large enough."""
+    n0 = lib.msda_launch_count()
+    need = lib.msda_heads_bf16_workspace_bytes(0, 6, 9600, 256, 14, 2, 0)
+    for call in (_fwd, _bwd):
+        for kw in (dict(hs=P + 4), dict(hidden=P + 8), dict(cls=_ptrs(8, P + 4)), dict(mlp=_ptrs(48, P + 8)),
+                   dict(sh=_ptrs(6, P + 2))):
+            assert call(lib, form="bf16", **kw) == ERR_ARGUMENT and _err(lib) == ALIGN, kw
+    assert _fwd(lib, form="bf16", hs=P + 4, logits=None) == ERR_ARGUMENT and _err(lib) == NULL    # the shared checks come first
+    assert _bwd(lib, form="bf16", hs=P + 4, glog=None) == ERR_ARGUMENT and _err(lib) == NULL
+    assert _bwd(lib, form="bf16", hs=P + 4, ws=P + 4, ws_bytes=0) == ERR_ARGUMENT and _err(lib) == ALIGN
+    assert _bwd(lib, form="bf16", ws=None, ws_bytes=0) == ERR_ARGUMENT and _err(lib) == NULL      # this form needs a workspace
+    assert _bwd(lib, form="bf16", ws=None, ws_bytes=need) == ERR_ARGUMENT and _err(lib) == NULL
+    assert _bwd(lib, form="bf16", ws=P + 4, ws_bytes=need) == ERR_ARGUMENT and _err(lib) == WS_ALIGN
+    assert _bwd(lib, form="bf16", ws=P + 4, ws_bytes=0) == ERR_ARGUMENT and _err(lib) == WS_ALIGN  # alignment before size
+    assert _bwd(lib, form="bf16", ws_bytes=need - 1) == ERR_ARGUMENT and _err(lib) == WS_SMALL["bf16"]
+    assert _bwd(lib, form="bf16", ws_bytes=0) == ERR_ARGUMENT and _err(lib) == WS_SMALL["bf16"]
+    assert lib.msda_launch_count() == n0
+
+
+def test_fp32_workspace_errors(lib):
+    n0 = lib.msda_launch_count()
+    need = lib.msda_heads_workspace_bytes(0, 6, 9600, 256, 14, 2, 0)
+    assert _bwd(lib, ws_bytes=need - 1) == ERR_ARGUMENT and _err(lib) == WS_SMALL["f32"]
+    assert _bwd(lib, ws=None, ws_bytes=need) == ERR_ARGUMENT and _err(lib) == NULL
+    assert _bwd(lib, ws=None, ws_bytes=0) == ERR_ARGUMENT and _err(lib) == WS_SMALL["f32"]         # an empty workspace may be null
+    assert _bwd(lib, ws=P + 4, ws_bytes=need - 1) == ERR_ARGUMENT and _err(lib) == WS_SMALL["f32"]  # no alignment asked of it
+    assert lib.msda_launch_count() == n0
+
+
+# (entry, (kind, L, M, C, K, n_mlp, flags)) -> bytes, as the library returned them before the two forms shared one planner
+WORKSPACE_BYTES = [
+    ("msda_heads_workspace_bytes", (0, 6, 9600, 256, 14, 2, 0), 272559296),
+    ("msda_heads_workspace_bytes", (0, 2, 2049, 64, 14, 2, 0), 4617552),          # M = 2049: two weight-gradient chunks
+    ("msda_heads_workspace_bytes", (0, 2, 2049, 64, 14, 2, 3), 4525512),          # shared class head and MLP weights
+    ("msda_heads_workspace_bytes", (1, 6, 63, 256, 65, 1, 2), 1766164),
+    ("msda_heads_workspace_bytes", (0, 1, 1, 8, 1, 0, 0), 2484),
+    ("msda_heads_bf16_workspace_bytes", (0, 6, 9600, 256, 14, 2, 0), 154594496),
+    ("msda_heads_bf16_workspace_bytes", (0, 2, 2049, 64, 14, 2, 3), 2427336),
+    ("msda_heads_bf16_workspace_bytes", (1, 8, 2049, 8, 65, 1, 1), 591108),
+]
+
+
+@pytest.mark.parametrize("entry,geom,want", WORKSPACE_BYTES)
+def test_workspace_sizes_are_pinned(lib, entry, geom, want):
+    assert getattr(lib, entry)(*geom) == want

@@ -1355,7 +1355,7 @@ def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
     return g_logits, g_hand, g_obj
 
 
-# ---- the DeformableDETR prediction heads (csrc/msda_heads.hip) ------------------------------------------------------------
+# ---- the DeformableDETR prediction heads, fp32 and bf16 autocast (csrc/msda_heads.hip, csrc/msda_heads_bf16.hip) ------------
 HEADS_ARCTIC, HEADS_ASSEMBLY = 0, 1
 HEADS_SHARED_CLS, HEADS_SHARED_MLP = 1, 2
 HEADS_SHARED_WIDTHS = (48, 10, 3, 3, 3, 1)
@@ -1366,8 +1366,25 @@ def heads_supported(C):
     return bool((_lib or load()).msda_heads_supported(int(C)))
 
 
-def heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
-    return int((_lib or load()).msda_heads_workspace_bytes(int(kind), int(L), int(M), int(C), int(K), int(n_mlp), int(flags)))
+def heads_bf16_supported(C):
+    """msda_heads_bf16_supported (include/msda.h): 1 when the bf16-autocast heads kernels take hidden size C."""
+    return bool((_lib or load()).msda_heads_bf16_supported(int(C)))
+
+
+# The two forms of the heads entries: the C names, and the dtypes of what differs between them (hidden and the shared outputs;
+# logits and keypoints by kind).  hs, the parameters, the references, sig and every parameter gradient are fp32 in both.
+_BF = torch.bfloat16
+_HEADS_FORMS = {
+    "f32": dict(suffix="_f32", label="", ws="msda_heads_workspace_bytes", hidden=torch.float32,
+                out=(torch.float32, torch.float32), grads="contiguous fp32 CUDA output gradients"),
+    "bf16": dict(suffix="_bf16", label="_bf16", ws="msda_heads_bf16_workspace_bytes", hidden=_BF, out=(torch.float32, _BF),
+                 grads="contiguous CUDA output gradients of the outputs' dtypes"),
+}
+
+
+def _heads_workspace_bytes(form, kind, L, M, C, K, n_mlp, flags):
+    entry = getattr(_lib or load(), _HEADS_FORMS[form]["ws"])
+    return int(entry(int(kind), int(L), int(M), int(C), int(K), int(n_mlp), int(flags)))
 
 
 def _ptrs_or_none(ts):
@@ -1389,92 +1406,73 @@ def _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
             _ptrs_or_none(shared[1])], (L, M, C, K, n_mlp)
 
 
-def heads_forward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
-    """msda_heads_forward_f32: (logits [L, M, K], kp outputs [L, M, D] per MLP head, shared outputs [L, M, n_g],
-    hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D]).  At most 3 launches, no host synchronisation."""
+def _heads_forward(form, kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
+    f = _HEADS_FORMS[form]
     args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
     D = 42 if kind == HEADS_ARCTIC else 63
-    dev = hs.device
-    logits = torch.empty(L, M, K, dtype=torch.float32, device=dev)
-    kp = [torch.empty(L, M, D, dtype=torch.float32, device=dev) for _ in range(n_mlp)]
-    sh = [torch.empty(L, M, n, dtype=torch.float32, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
-    hidden = torch.empty(n_mlp, 2, L, M, C, dtype=torch.float32, device=dev)
-    sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
-    _launch(dev, "msda_heads_forward_f32", "heads_forward", *args, logits.data_ptr(), _ptrs_or_none(kp), _ptrs_or_none(sh),
-            hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None)
-    return logits, kp, sh, hidden, sig
-
-
-def heads_backward(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
-    """msda_heads_backward_f32: (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases),
-    every element written.  At most 5 launches, no host synchronisation."""
-    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
-    grads = [grad_logits] + list(grad_kp) + list(grad_shared)
-    if not all(_f32_cuda(t) and t.device == hs.device for t in grads):
-        raise RuntimeError("detr_heads: expected contiguous fp32 CUDA output gradients")
-    dev = hs.device
-    ws = torch.empty(max(1, heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags) // 4), dtype=torch.float32, device=dev)
-    grad_hs = torch.empty_like(hs)
-    g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
-    g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
-    g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
-    _launch(dev, "msda_heads_backward_f32", "heads_backward", *args, hidden.data_ptr() if n_mlp else None,
-            sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(), _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared),
-            grad_hs.data_ptr(), _ptr_array(g_cls[0]), _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]),
-            _ptrs_or_none(g_sh[0]), _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4)
-    return grad_hs, g_cls, g_mlp, g_sh
-
-
-def heads_bf16_supported(C):
-    """msda_heads_bf16_supported (include/msda.h): 1 when the bf16-autocast heads kernels take hidden size C."""
-    return bool((_lib or load()).msda_heads_bf16_supported(int(C)))
-
-
-def heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
-    return int((_lib or load()).msda_heads_bf16_workspace_bytes(int(kind), int(L), int(M), int(C), int(K), int(n_mlp),
-                                                               int(flags)))
-
-
-def heads_forward_bf16(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags):
-    """msda_heads_forward_bf16: the heads under bf16 autocast from fp32 hs / parameters / references.  Returns (logits
-    [L, M, K], kp outputs [L, M, D] per MLP head, shared outputs [L, M, n_g], hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D])
-    with autocast's dtypes: logits and keypoints fp32 (ARCTIC) or bf16 (AssemblyHands), shared outputs and hidden bf16, sig
-    fp32.  At most 3 launches, no host synchronisation."""
-    args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
-    D = 42 if kind == HEADS_ARCTIC else 63
-    dev, bf = hs.device, torch.bfloat16
-    out_dt = torch.float32 if kind == HEADS_ARCTIC else bf
+    dev, out_dt = hs.device, f["out"][kind == HEADS_ASSEMBLY]
     logits = torch.empty(L, M, K, dtype=out_dt, device=dev)
     kp = [torch.empty(L, M, D, dtype=out_dt, device=dev) for _ in range(n_mlp)]
-    sh = [torch.empty(L, M, n, dtype=bf, device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
-    hidden = torch.empty(n_mlp, 2, L, M, C, dtype=bf, device=dev)
+    sh = [torch.empty(L, M, n, dtype=f["hidden"], device=dev) for n in HEADS_SHARED_WIDTHS] if shared[0] else []
+    hidden = torch.empty(n_mlp, 2, L, M, C, dtype=f["hidden"], device=dev)
     sig = torch.empty(n_mlp, L, M, D, dtype=torch.float32, device=dev)
-    _launch(dev, "msda_heads_forward_bf16", "heads_forward_bf16", *args, logits.data_ptr(), _ptrs_or_none(kp),
+    _launch(dev, "msda_heads_forward" + f["suffix"], "heads_forward" + f["label"], *args, logits.data_ptr(), _ptrs_or_none(kp),
             _ptrs_or_none(sh), hidden.data_ptr() if n_mlp else None, sig.data_ptr() if n_mlp else None)
     return logits, kp, sh, hidden, sig
 
 
-def heads_backward_bf16(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
-    """msda_heads_backward_bf16: (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases),
-    all fp32, every element written; the output gradients carry the outputs' dtypes.  At most 5 launches, no host
-    synchronisation."""
+def _heads_backward(form, kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp, grad_shared):
+    f = _HEADS_FORMS[form]
     args, (L, M, C, K, n_mlp) = _heads_common(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags)
-    dev, bf = hs.device, torch.bfloat16
-    out_dt = torch.float32 if kind == HEADS_ARCTIC else bf
-    typed = [(grad_logits, out_dt)] + [(t, out_dt) for t in grad_kp] + [(t, bf) for t in grad_shared]
-    if not all(t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == dev for t, dt in typed + [(hidden, bf)]):
-        raise RuntimeError("detr_heads: expected contiguous CUDA output gradients of the outputs' dtypes")
-    ws = torch.empty(max(1, (heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags) + 3) // 4), dtype=torch.float32,
-                     device=dev)
+    dev, out_dt = hs.device, f["out"][kind == HEADS_ASSEMBLY]
+    typed = [(grad_logits, out_dt)] + [(t, out_dt) for t in grad_kp] + [(t, f["hidden"]) for t in list(grad_shared) + [hidden]]
+    if not all(t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == dev for t, dt in typed):
+        raise RuntimeError("detr_heads: expected " + f["grads"])
+    ws_bytes = _heads_workspace_bytes(form, kind, L, M, C, K, n_mlp, flags)
+    ws = torch.empty(max(1, (ws_bytes + 3) // 4), dtype=torch.float32, device=dev)
     grad_hs = torch.empty_like(hs)
     g_cls = ([torch.empty_like(w) for w in cls[0]], [torch.empty_like(b) for b in cls[1]])
     g_mlp = ([torch.empty_like(w) for w in mlp[0]], [torch.empty_like(b) for b in mlp[1]])
     g_sh = ([torch.empty_like(w) for w in shared[0]], [torch.empty_like(b) for b in shared[1]])
-    _launch(dev, "msda_heads_backward_bf16", "heads_backward_bf16", *args, hidden.data_ptr() if n_mlp else None,
+    _launch(dev, "msda_heads_backward" + f["suffix"], "heads_backward" + f["label"], *args, hidden.data_ptr() if n_mlp else None,
             sig.data_ptr() if n_mlp else None, grad_logits.data_ptr(), _ptrs_or_none(grad_kp), _ptrs_or_none(grad_shared),
             grad_hs.data_ptr(), _ptr_array(g_cls[0]), _ptr_array(g_cls[1]), _ptrs_or_none(g_mlp[0]), _ptrs_or_none(g_mlp[1]),
             _ptrs_or_none(g_sh[0]), _ptrs_or_none(g_sh[1]), ws.data_ptr(), ws.numel() * 4)
     return grad_hs, g_cls, g_mlp, g_sh
+
+
+def heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
+    return _heads_workspace_bytes("f32", kind, L, M, C, K, n_mlp, flags)
+
+
+def heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags):
+    return _heads_workspace_bytes("bf16", kind, L, M, C, K, n_mlp, flags)
+
+
+def heads_forward(*args):
+    """msda_heads_forward_f32(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags): (logits [L, M, K], kp outputs [L, M, D]
+    per MLP head, shared outputs [L, M, n_g], hidden [n_mlp, 2, L, M, C], sig [n_mlp, L, M, D]), all fp32.  At most 3 launches,
+    no host synchronisation."""
+    return _heads_forward("f32", *args)
+
+
+def heads_backward(*args):
+    """msda_heads_backward_f32(kind, hs, init_ref, inter_ref, cls, mlp, shared, flags, hidden, sig, grad_logits, grad_kp,
+    grad_shared): (grad_hs, grad cls weights / biases, grad MLP weights / biases, grad shared weights / biases), every element
+    written.  At most 5 launches, no host synchronisation."""
+    return _heads_backward("f32", *args)
+
+
+def heads_forward_bf16(*args):
+    """msda_heads_forward_bf16: heads_forward under bf16 autocast from fp32 hs / parameters / references, with autocast's
+    dtypes: logits and keypoints fp32 (ARCTIC) or bf16 (AssemblyHands), shared outputs and hidden bf16, sig fp32."""
+    return _heads_forward("bf16", *args)
+
+
+def heads_backward_bf16(*args):
+    """msda_heads_backward_bf16: heads_backward for that form; the parameter gradients and grad_hs are fp32, the output
+    gradients carry the outputs' dtypes."""
+    return _heads_backward("bf16", *args)
 
 
 # ---- SmoothNet: MotionSmoother modules and get_arctic_item's selection (msda_smoother.hip, msda_arctic_item.hip) ----------

@@ -1161,25 +1161,66 @@ int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const floa
     return msda::launch_criterion_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
 }
 
-/* ---- the DETR prediction heads (msda_heads.hip) ---- */
-int msda_heads_supported(int C) { return C >= 4 && C <= 4096 && C % 4 == 0 ? 1 : 0; }
+/* ---- the DETR prediction heads, fp32 and under bf16 autocast (msda_heads.hip plans both; msda_heads_bf16.hip) ---- */
+int msda_heads_supported(int C) { return msda::heads_supported(msda::kHeadsF32, C) ? 1 : 0; }
+int msda_heads_bf16_supported(int C) { return msda::heads_supported(msda::kHeadsBf16, C) ? 1 : 0; }
+
+static unsigned long long heads_workspace(int form, int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
+{
+    if (L < 1 || L > msda::kHeadsMaxLevels || M < 1 || C < 1 || K < 1 || n_mlp < 0 || n_mlp > msda::kHeadsMaxMlp) return 0;
+    return msda::heads_workspace_bytes(form, kind, L, M, C, K, n_mlp, flags);
+}
 
 unsigned long long msda_heads_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
 {
-    if (L < 1 || L > msda::kHeadsMaxLevels || M < 1 || C < 1 || K < 1 || n_mlp < 0 || n_mlp > msda::kHeadsMaxMlp) return 0;
-    return msda::heads_workspace_bytes(kind, L, M, C, K, n_mlp, flags);
+    return heads_workspace(msda::kHeadsF32, kind, L, M, C, K, n_mlp, flags);
 }
 
-static msda::HeadsCall heads_call(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
-                                  const float *init_ref, const float *inter_ref, const float *const *cls_w,
+unsigned long long msda_heads_bf16_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
+{
+    return heads_workspace(msda::kHeadsBf16, kind, L, M, C, K, n_mlp, flags);
+}
+
+/* The operands every entry has; the forward entries add their outputs, the backward entries their gradients and workspace.
+ * An entry's typed pointer arrays (float *const *, uint16_t *const *) become the call's void *const *: arrays of addresses. */
+static msda::HeadsCall heads_call(int form, int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags,
+                                  const float *hs, const float *init_ref, const float *inter_ref, const float *const *cls_w,
                                   const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,
-                                  const float *const *shared_w, const float *const *shared_b)
+                                  const float *const *shared_w, const float *const *shared_b, const void *hidden, const float *sig)
 {
     msda::HeadsCall c = {};
-    c.kind = kind; c.L = L; c.M = M; c.C = C; c.K = K; c.n_mlp = n_mlp; c.R = R; c.flags = flags;
+    c.form = form; c.kind = kind; c.L = L; c.M = M; c.C = C; c.K = K; c.n_mlp = n_mlp; c.R = R; c.flags = flags;
     c.hs = hs; c.init_ref = init_ref; c.inter_ref = inter_ref;
     c.cls_w = cls_w; c.cls_b = cls_b; c.mlp_w = mlp_w; c.mlp_b = mlp_b; c.shared_w = shared_w; c.shared_b = shared_b;
+    c.hidden = const_cast<void *>(hidden); c.sig = const_cast<float *>(sig);
     return c;
+}
+
+/* the one plan of each direction that this thread's calls of either form build and launch */
+static int heads_forward(msda::HeadsCall &c, void *logits, const void *kp_out, const void *shared_out, msda_stream_t stream)
+{
+    c.logits = logits; c.kp_out = static_cast<void *const *>(kp_out); c.shared_out = static_cast<void *const *>(shared_out);
+    static thread_local msda::HeadsFwdPlan plan;
+    const int rc = msda::heads_plan_forward(c, plan);
+    if (rc != MSDA_OK) return rc;
+    msda::begin_call();
+    return msda::heads_run_forward(plan, (hipStream_t)stream);
+}
+
+static int heads_backward(msda::HeadsCall &c, const void *grad_logits, const void *grad_kp, const void *grad_shared,
+                          float *grad_hs, float *const *grad_cls_w, float *const *grad_cls_b, float *const *grad_mlp_w,
+                          float *const *grad_mlp_b, float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
+                          unsigned long long workspace_bytes, msda_stream_t stream)
+{
+    c.grad_logits = grad_logits; c.grad_kp = static_cast<const void *const *>(grad_kp);
+    c.grad_shared = static_cast<const void *const *>(grad_shared); c.grad_hs = grad_hs;
+    c.grad_cls_w = grad_cls_w; c.grad_cls_b = grad_cls_b; c.grad_mlp_w = grad_mlp_w; c.grad_mlp_b = grad_mlp_b;
+    c.grad_shared_w = grad_shared_w; c.grad_shared_b = grad_shared_b; c.ws = workspace; c.ws_bytes = workspace_bytes;
+    static thread_local msda::HeadsBwdPlan plan;
+    const int rc = msda::heads_plan_backward(c, plan);
+    if (rc != MSDA_OK) return rc;
+    msda::begin_call();
+    return msda::heads_run_backward(plan, (hipStream_t)stream);
 }
 
 int msda_heads_forward_f32(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
@@ -1188,14 +1229,9 @@ int msda_heads_forward_f32(int kind, int L, long long M, int C, int K, int n_mlp
                            const float *const *shared_w, const float *const *shared_b, float *logits, float *const *kp_out,
                            float *const *shared_out, float *hidden, float *sig, msda_stream_t stream)
 {
-    msda::HeadsCall c = heads_call(kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b, mlp_w, mlp_b,
-                                   shared_w, shared_b);
-    c.logits = logits; c.kp_out = kp_out; c.shared_out = shared_out; c.hidden = hidden; c.sig = sig;
-    static thread_local msda::HeadsFwdPlan plan;
-    const int rc = msda::heads_plan_forward(c, plan);
-    if (rc != MSDA_OK) return rc;
-    msda::begin_call();
-    return msda::heads_run_forward(plan, (hipStream_t)stream);
+    msda::HeadsCall c = heads_call(msda::kHeadsF32, kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b,
+                                   mlp_w, mlp_b, shared_w, shared_b, hidden, sig);
+    return heads_forward(c, logits, kp_out, shared_out, stream);
 }
 
 int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
@@ -1208,38 +1244,10 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
                             float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                             unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    msda::HeadsCall c = heads_call(kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b, mlp_w, mlp_b,
-                                   shared_w, shared_b);
-    c.hidden = const_cast<float *>(hidden); c.sig = const_cast<float *>(sig);
-    c.grad_logits = grad_logits; c.grad_kp = grad_kp; c.grad_shared = grad_shared; c.grad_hs = grad_hs;
-    c.grad_cls_w = grad_cls_w; c.grad_cls_b = grad_cls_b; c.grad_mlp_w = grad_mlp_w; c.grad_mlp_b = grad_mlp_b;
-    c.grad_shared_w = grad_shared_w; c.grad_shared_b = grad_shared_b; c.ws = workspace; c.ws_bytes = workspace_bytes;
-    static thread_local msda::HeadsBwdPlan plan;
-    const int rc = msda::heads_plan_backward(c, plan);
-    if (rc != MSDA_OK) return rc;
-    msda::begin_call();
-    return msda::heads_run_backward(plan, (hipStream_t)stream);
-}
-
-/* ---- the same heads under bf16 autocast (msda_heads_bf16.hip) ---- */
-int msda_heads_bf16_supported(int C) { return msda::heads_bf16_supported(C) ? 1 : 0; }
-
-unsigned long long msda_heads_bf16_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
-{
-    if (L < 1 || L > msda::kHeadsMaxLevels || M < 1 || C < 1 || K < 1 || n_mlp < 0 || n_mlp > msda::kHeadsMaxMlp) return 0;
-    return msda::heads_bf16_workspace_bytes(kind, L, M, C, K, n_mlp, flags);
-}
-
-static msda::HeadsBf16Call heads_bf16_call(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags,
-                                           const float *hs, const float *init_ref, const float *inter_ref,
-                                           const float *const *cls_w, const float *const *cls_b, const float *const *mlp_w,
-                                           const float *const *mlp_b, const float *const *shared_w, const float *const *shared_b)
-{
-    msda::HeadsBf16Call c = {};
-    c.kind = kind; c.L = L; c.M = M; c.C = C; c.K = K; c.n_mlp = n_mlp; c.R = R; c.flags = flags;
-    c.hs = hs; c.init_ref = init_ref; c.inter_ref = inter_ref;
-    c.cls_w = cls_w; c.cls_b = cls_b; c.mlp_w = mlp_w; c.mlp_b = mlp_b; c.shared_w = shared_w; c.shared_b = shared_b;
-    return c;
+    msda::HeadsCall c = heads_call(msda::kHeadsF32, kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b,
+                                   mlp_w, mlp_b, shared_w, shared_b, hidden, sig);
+    return heads_backward(c, grad_logits, grad_kp, grad_shared, grad_hs, grad_cls_w, grad_cls_b, grad_mlp_w, grad_mlp_b,
+                          grad_shared_w, grad_shared_b, workspace, workspace_bytes, stream);
 }
 
 int msda_heads_forward_bf16(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
@@ -1248,13 +1256,9 @@ int msda_heads_forward_bf16(int kind, int L, long long M, int C, int K, int n_ml
                             const float *const *shared_w, const float *const *shared_b, void *logits, void *const *kp_out,
                             uint16_t *const *shared_out, uint16_t *hidden, float *sig, msda_stream_t stream)
 {
-    msda::HeadsBf16Call c = heads_bf16_call(kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b, mlp_w,
-                                            mlp_b, shared_w, shared_b);
-    c.logits = logits; c.kp_out = kp_out; c.shared_out = shared_out; c.hidden = hidden; c.sig = sig;
-    const int rc = msda::heads_bf16_plan_forward(c);
-    if (rc != MSDA_OK) return rc;
-    msda::begin_call();
-    return msda::heads_bf16_run_forward((hipStream_t)stream);
+    msda::HeadsCall c = heads_call(msda::kHeadsBf16, kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b,
+                                   mlp_w, mlp_b, shared_w, shared_b, hidden, sig);
+    return heads_forward(c, logits, kp_out, shared_out, stream);
 }
 
 int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
@@ -1267,16 +1271,10 @@ int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_m
                              float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                              unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    msda::HeadsBf16Call c = heads_bf16_call(kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b, mlp_w,
-                                            mlp_b, shared_w, shared_b);
-    c.hidden = const_cast<uint16_t *>(hidden); c.sig = const_cast<float *>(sig);
-    c.grad_logits = grad_logits; c.grad_kp = grad_kp; c.grad_shared = grad_shared; c.grad_hs = grad_hs;
-    c.grad_cls_w = grad_cls_w; c.grad_cls_b = grad_cls_b; c.grad_mlp_w = grad_mlp_w; c.grad_mlp_b = grad_mlp_b;
-    c.grad_shared_w = grad_shared_w; c.grad_shared_b = grad_shared_b; c.ws = workspace; c.ws_bytes = workspace_bytes;
-    const int rc = msda::heads_bf16_plan_backward(c);
-    if (rc != MSDA_OK) return rc;
-    msda::begin_call();
-    return msda::heads_bf16_run_backward((hipStream_t)stream);
+    msda::HeadsCall c = heads_call(msda::kHeadsBf16, kind, L, M, C, K, n_mlp, R, flags, hs, init_ref, inter_ref, cls_w, cls_b,
+                                   mlp_w, mlp_b, shared_w, shared_b, hidden, sig);
+    return heads_backward(c, grad_logits, grad_kp, grad_shared, grad_hs, grad_cls_w, grad_cls_b, grad_mlp_w, grad_mlp_b,
+                          grad_shared_w, grad_shared_b, workspace, workspace_bytes, stream);
 }
 
 /* ---- Swin window attention (msda_swin.hip): replaces models/swin_transformer.py:126-142 (WindowAttention.forward's scores,

@@ -19,34 +19,34 @@
 // the MFMAs), the lane / register layout of msda_gemm.hip.  An operand is staged K-major ([64][32 + 4]) or MN-major
 // ([32][64 + 4]) as it lies in memory; 16-byte loads where rows are C floats long (C % 4 == 0), 4-byte loads where they are
 // a head's width (14, 42, 63 ...).  Fixed summation order everywhere: bitwise reproducible.
+//
+// The host side below is the planner of BOTH forms, this one and the bf16-autocast one (kernels: msda_heads_bf16.hip): one
+// argument check, one enumeration of the problems, one workspace layout, one set of tables (msda_launch.h) whose dtype flags
+// come from a form's description (Form); heads_run_* launch a plan on its form's kernels.  The fp32 kernels here read the
+// same tables and ignore the flags.
 #include <cstdio>
 #include <cstring>
 
-#include "msda_common.h"
-#include "msda_launch.h"
+#include "msda_heads_common.h"
 
 namespace msda {
 
 namespace {
 
 #include "msda_tile.h"
-static_assert(kHBlock == kHeadsReduceBlock, "heads_reduce_kernel's block is what the bf16 form's plan counts with");
+static_assert(kHBlock == kHeadsReduceBlock && kHT == kHeadsTile, "what the planner counts workgroups with");
 
-// the reference's inverse_sigmoid (util/misc.py:614-618)
-__device__ __forceinline__ float inv_sigmoid(float x)
-{
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    const float x1 = fmaxf(x, 1e-5f), x2 = fmaxf(1.f - x, 1e-5f);
-    return logf(x1 / x2);
-}
+// this form's operands are all fp32: the tables' dtype flags are not read
+__device__ __forceinline__ const float *f32(const void *p) { return static_cast<const float *>(p); }
+__device__ __forceinline__ float *f32(void *p) { return static_cast<float *>(p); }
 
-__device__ __forceinline__ float apply_mode(float a, const float *aux, long long e, int mode)
+__device__ __forceinline__ float apply_mode(float a, const void *aux, long long e, int mode)
 {
     if (mode == kHeadsModeSigmoid) {
-        const float s = aux[e];
+        const float s = f32(aux)[e];
         return (a * 2.f) * (1.f - s) * s;                   // MulBackward (out = 2 s - c), then sigmoid_backward
     }
-    if (mode == kHeadsModeRelu) return aux[e] > 0.f ? a : 0.f;
+    if (mode == kHeadsModeRelu) return f32(aux)[e] > 0.f ? a : 0.f;
     return a;
 }
 
@@ -56,15 +56,13 @@ __global__ __launch_bounds__(kHBlock) void heads_fwd_kernel(HeadsFwdArgs P)
     __shared__ __attribute__((aligned(16))) float As[2][kLds];
     __shared__ __attribute__((aligned(16))) float Bs[2][kLds];
     __shared__ float refoff[kHT][2];
-    int pi = 0;
-    while (pi + 1 < P.nprob && (int)blockIdx.x >= P.p[pi + 1].tile0) ++pi;
-    const HeadsFwdProb &p = P.p[pi];
+    const HeadsFwdProb &p = P.p[heads_problem(P)];
     const int tiles_n = (p.n + kHT - 1) / kHT;
     const int local = (int)blockIdx.x - p.tile0;
     if (local >= ((p.rows + kHT - 1) / kHT) * tiles_n) return;
     const int m0 = (local / tiles_n) * kHT, n0 = (local % tiles_n) * kHT;
     const int C = P.C, tid = threadIdx.x;
-    const float *A = p.a + (long long)p.row0 * C;
+    const float *A = f32(p.a) + (long long)p.row0 * C;
 
     auto load = [&](int s, float (&ra)[8], float (&rb)[8]) {
         const int k = s * kHS + (tid % 8) * 4;
@@ -74,9 +72,8 @@ __global__ __launch_bounds__(kHBlock) void heads_fwd_kernel(HeadsFwdArgs P)
             float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
             if (m < p.rows && k < C) va = *reinterpret_cast<const float4 *>(A + (long long)m * C + k);
             if (j < p.n && k < C) {
-                int gi = p.g0;
-                while (gi + 1 < p.g0 + p.ng && j >= P.g[gi + 1].off) ++gi;
-                vb = *reinterpret_cast<const float4 *>(P.g[gi].w + (long long)(j - P.g[gi].off) * C + k);
+                const HeadsFwdGroup &G = P.g[heads_group(P, p, j)];
+                vb = *reinterpret_cast<const float4 *>(G.w + (long long)(j - G.off) * C + k);
             }
             ra[4 * u] = va.x; ra[4 * u + 1] = va.y; ra[4 * u + 2] = va.z; ra[4 * u + 3] = va.w;
             rb[4 * u] = vb.x; rb[4 * u + 1] = vb.y; rb[4 * u + 2] = vb.z; rb[4 * u + 3] = vb.w;
@@ -84,38 +81,12 @@ __global__ __launch_bounds__(kHBlock) void heads_fwd_kernel(HeadsFwdArgs P)
     };
     const f32x16 acc = tile_loop<true, true, true, true>(As, Bs, (C + kHS - 1) / kHS, load, NoStage());
 
-    // AssemblyHands keypoints: the x / y offsets of each row of the tile (models/assembly_detr.py:172-199): the reference point
-    // (2-d) or the means of the 21 x and 21 y values (42-d), after inverse_sigmoid; levels >= 1 map r -> (r + 0.5) / 2 first
-    if (p.epi == kHeadsEpiAssembly) {
-        if (tid < 2 * kHT) {
-            const int row = tid >> 1, coord = tid & 1, gr = p.row0 + m0 + row;
-            float v = 0.f;
-            if (m0 + row < p.rows) {
-                const bool first = gr < P.M;
-                const float *ref = first ? P.init_ref + (long long)gr * P.R : P.inter_ref + (long long)(gr - P.M) * P.R;
-                if (P.R == 2) {
-                    const float r = ref[coord];
-                    v = inv_sigmoid(first ? r : (r + 0.5f) / 2.f);
-                } else {
-                    float sum = 0.f;
-                    for (int q = 0; q < P.R / 2; ++q) {
-                        const float r = ref[2 * q + coord];
-                        sum += inv_sigmoid(first ? r : (r + 0.5f) / 2.f);
-                    }
-                    v = sum / (float)(P.R / 2);
-                }
-            }
-            refoff[row][coord] = v;
-        }
-        __syncthreads();
-    }
+    if (p.epi == kHeadsEpiAssembly) heads_refoff(P, p, m0, refoff);
 
     const int wave = tid >> 6, lane = tid & 63;
     const int i0 = (wave >> 1) * 32, g = lane >> 5, j = n0 + (wave & 1) * 32 + (lane & 31);
     if (j >= p.n) return;
-    int gi = p.g0;
-    while (gi + 1 < p.g0 + p.ng && j >= P.g[gi + 1].off) ++gi;
-    const HeadsFwdGroup &G = P.g[gi];
+    const HeadsFwdGroup &G = P.g[heads_group(P, p, j)];
     const int jj = j - G.off;
     const float bj = G.b[jj];
 #pragma unroll
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(kHBlock) void heads_fwd_kernel(HeadsFwdArgs P)
             p.sig[gr * G.n + jj] = s;
             v = s * 2.f - 0.5f;
         }
-        G.out[gr * G.n + jj] = v;
+        f32(G.out)[gr * G.n + jj] = v;
     }
 }
 
@@ -148,9 +119,7 @@ __global__ __launch_bounds__(kHBlock) void heads_dgrad_kernel(HeadsDgradArgs P)
 {
     __shared__ __attribute__((aligned(16))) float As[2][kLds];
     __shared__ __attribute__((aligned(16))) float Bs[2][kLds];
-    int pi = 0;
-    while (pi + 1 < P.nprob && (int)blockIdx.x >= P.p[pi + 1].tile0) ++pi;
-    const HeadsDgradProb &p = P.p[pi];
+    const HeadsDgradProb &p = P.p[heads_problem(P)];
     const int C = P.C, tiles_n = (C + kHT - 1) / kHT;
     const int local = (int)blockIdx.x - p.tile0;
     if (local >= ((p.rows + kHT - 1) / kHT) * tiles_n) return;
@@ -173,7 +142,7 @@ __global__ __launch_bounds__(kHBlock) void heads_dgrad_kernel(HeadsDgradArgs P)
             float v = 0.f;
             if (m < p.rows && k < S.k) {
                 const long long e = ((long long)p.row0 + m) * S.k + k;
-                v = apply_mode(S.a[e], S.aux, e, S.mode);
+                v = apply_mode(f32(S.a)[e], S.aux, e, S.mode);
             }
             ra[u] = v;
         }
@@ -193,7 +162,7 @@ __global__ __launch_bounds__(kHBlock) void heads_dgrad_kernel(HeadsDgradArgs P)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + i0 + acc_row(r, g);
-        if (m < p.rows) p.out[((long long)p.row0 + m) * C + j] = acc[r];
+        if (m < p.rows) f32(p.out)[((long long)p.row0 + m) * C + j] = acc[r];
     }
 }
 
@@ -203,9 +172,7 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
     __shared__ __attribute__((aligned(16))) float As[2][kLds];
     __shared__ __attribute__((aligned(16))) float Bs[2][kLds];
     __shared__ float bred[4][kHT];
-    int pi = 0;
-    while (pi + 1 < P.nprob && (int)blockIdx.x >= P.p[pi + 1].tile0) ++pi;
-    const HeadsWgradProb &p = P.p[pi];
+    const HeadsWgradProb &p = P.p[heads_problem(P)];
     const int C = P.C, tiles_j = (C + kHT - 1) / kHT, tiles_i = (p.n + kHT - 1) / kHT;
     const int local = (int)blockIdx.x - p.tile0;
     if (local >= p.chunks * tiles_i * tiles_j) return;
@@ -222,7 +189,7 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
             float v = 0.f;
             if (m < nrows && i < p.n) {
                 const long long e = (base + m) * p.n + i;
-                v = apply_mode(p.dy[e], p.aux, e, p.mode);
+                v = apply_mode(f32(p.dy)[e], p.aux, e, p.mode);
             }
             ra[u] = v;
         }
@@ -231,7 +198,7 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
         for (int u = 0; u < 2; ++u) {
             const int m = s * kHS + tid / 16 + 16 * u, jn = j0t + (tid % 16) * 4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m < nrows && jn < C) v = *reinterpret_cast<const float4 *>(p.x + (base + m) * C + jn);
+            if (m < nrows && jn < C) v = *reinterpret_cast<const float4 *>(f32(p.x) + (base + m) * C + jn);
             rb[4 * u] = v.x; rb[4 * u + 1] = v.y; rb[4 * u + 2] = v.z; rb[4 * u + 3] = v.w;
         }
     };
@@ -267,11 +234,9 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
 // ---- dW = sum of the chunk partials in chunk order; db likewise ------------------------------------------------------------
 __global__ __launch_bounds__(kHBlock) void heads_reduce_kernel(HeadsReduceArgs P)
 {
-    int pi = 0;
-    while (pi + 1 < P.nprob && (int)blockIdx.x >= P.p[pi + 1].blk0) ++pi;
-    const HeadsReduceProb &p = P.p[pi];
+    const HeadsReduceProb &p = P.p[heads_problem(P)];
     const long long nw = (long long)p.n * P.C;
-    const long long e = (long long)((int)blockIdx.x - p.blk0) * kHBlock + threadIdx.x;
+    const long long e = (long long)((int)blockIdx.x - p.tile0) * kHBlock + threadIdx.x;
     if (e >= nw + p.n) return;
     const float *part = P.ws + p.part;
     float s = 0.f;
@@ -285,51 +250,59 @@ __global__ __launch_bounds__(kHBlock) void heads_reduce_kernel(HeadsReduceArgs P
     }
 }
 
-}  // namespace
+// ---- host side, both forms: argument checks, problem tables, workspace layout ----------------------------------------------
+const int kSharedN[kHeadsShared] = {48, 10, 3, 3, 3, 1};   // mano pose, mano beta, hand cam, obj cam, obj rot, obj rad
 
-int launch_heads_forward(const HeadsFwdArgs &a, int tiles, hipStream_t stream)
+// What a form is, beyond the operands that are fp32 in both (hs, weights, references, sig, parameter gradients): nothing else
+// may differ between the forms.
+struct Form {
+    int hidden_bf16;            // hidden, the hidden gradients, the six shared outputs and their gradients
+    int out_bf16[2];            // logits, keypoints and their gradients, by kind
+    int width;                  // C % width == 0, width <= C <= 4096
+    bool aligned;               // hs, hidden, every weight and the (required) workspace are 16-byte aligned
+    const char *width_msg;      // the form's own width test comes before every other check; null: the shared check's
+    const char *ws_msg;         // a workspace smaller than the form's entry asks for
+};
+const Form kForms[2] = {
+    {0, {0, 0}, 4, false, nullptr, "msda_heads: workspace smaller than msda_heads_workspace_bytes"},
+    {1, {0, 1}, 8, true, "msda_heads_bf16: need a hidden size C with C % 8 == 0, 8 <= C <= 4096",
+     "msda_heads_bf16: workspace smaller than msda_heads_bf16_workspace_bytes"},
+};
+
+int heads_D(int kind) { return kind == MSDA_HEADS_ARCTIC ? 42 : 63; }
+int tiles_of(long long rows, int n) { return (int)(((rows + kHT - 1) / kHT) * ((n + kHT - 1) / kHT)); }
+int chunks_of(long long rows) { return (int)((rows + kHeadsWgradChunk - 1) / kHeadsWgradChunk); }
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int herr(const char *msg) { return set_error(MSDA_ERR_ARGUMENT, msg); }
+// dy rows of width n can be staged 8 elements per load: whole groups, aligned rows (fp32 rows: two 16-byte loads each)
+int vec_ok(const void *dy, const void *aux, int n, int mode)
 {
-    if (tiles == 0) return MSDA_OK;
-    hipLaunchKernelGGL(heads_fwd_kernel, dim3((unsigned)tiles), dim3(kHBlock), 0, stream, a);
-    return check_launch("heads_fwd_kernel");
+    return n % 8 == 0 && mode != kHeadsModeSigmoid && aligned16(dy) && (mode != kHeadsModeRelu || aligned16(aux)) ? 1 : 0;
 }
 
-int launch_heads_dgrad(const HeadsDgradArgs &a, int tiles, hipStream_t stream)
-{
-    if (tiles == 0) return MSDA_OK;
-    hipLaunchKernelGGL(heads_dgrad_kernel, dim3((unsigned)tiles), dim3(kHBlock), 0, stream, a);
-    return check_launch("heads_dgrad_kernel");
-}
-
-int launch_heads_wgrad(const HeadsWgradArgs &a, int tiles, hipStream_t stream)
-{
-    if (tiles == 0) return MSDA_OK;
-    hipLaunchKernelGGL(heads_wgrad_kernel, dim3((unsigned)tiles), dim3(kHBlock), 0, stream, a);
-    return check_launch("heads_wgrad_kernel");
-}
-
-int launch_heads_reduce(const HeadsReduceArgs &a, int blocks, hipStream_t stream)
-{
-    if (blocks == 0) return MSDA_OK;
-    hipLaunchKernelGGL(heads_reduce_kernel, dim3((unsigned)blocks), dim3(kHBlock), 0, stream, a);
-    return check_launch("heads_reduce_kernel");
-}
-
-// ---- host side: argument checks and problem tables ----------------------------------------------------------------------
-static const int kSharedN[kHeadsShared] = {48, 10, 3, 3, 3, 1};   // mano pose, mano beta, hand cam, obj cam, obj rot, obj rad
-
-static int heads_D(int kind) { return kind == MSDA_HEADS_ARCTIC ? 42 : 63; }
-static int tiles_of(long long rows, int n) { return (int)(((rows + kHT - 1) / kHT) * ((n + kHT - 1) / kHT)); }
-static int chunks_of(long long rows) { return (int)((rows + kHeadsWgradChunk - 1) / kHeadsWgradChunk); }
-
-static int herr(const char *msg) { return set_error(MSDA_ERR_ARGUMENT, msg); }
+// Where the tensors stacked behind one pointer lie, in the form's element types: the saved hidden activations
+// [head][layer][L * M][C], the hidden gradients that open the workspace in the same layout, sig [head][L * M][D].  A null
+// base (heads_workspace_bytes has no operands) stays null.
+struct Stacked {
+    long long LM;
+    int C, D, es;               // es: bytes per hidden element
+    Stacked(const HeadsCall &c)
+        : LM((long long)c.L * c.M), C(c.C), D(heads_D(c.kind)), es(kForms[c.form].hidden_bf16 ? 2 : 4) {}
+    void *hidden(void *base, int h, int layer) const
+    {
+        return base ? static_cast<char *>(base) + ((long long)(h * 2 + layer) * LM * C) * es : nullptr;
+    }
+    float *sig(float *base, int h) const { return base ? base + (long long)h * LM * D : nullptr; }
+};
 
 int heads_check(const HeadsCall &c, bool backward)
 {
+    const Form &f = kForms[c.form];
+    if (f.width_msg != nullptr && !heads_supported(c.form, c.C)) return herr(f.width_msg);
     if (c.kind != MSDA_HEADS_ARCTIC && c.kind != MSDA_HEADS_ASSEMBLY)
         return herr("msda_heads: kind must be 0 (ARCTIC) or 1 (AssemblyHands)");
     if (c.L < 1 || c.L > kHeadsMaxLevels) return herr("msda_heads: need 1 <= L <= 8 levels");
-    if (c.M < 1 || c.K < 1 || c.C < 4 || c.C > 4096 || c.C % 4 != 0)
+    if (c.M < 1 || c.K < 1 || !heads_supported(kHeadsF32, c.C))
         return herr("msda_heads: need M >= 1, K >= 1 and a hidden size C with C % 4 == 0, 4 <= C <= 4096");
     if ((c.flags & ~(unsigned)(MSDA_HEADS_SHARED_CLS | MSDA_HEADS_SHARED_MLP)) != 0) return herr("msda_heads: unknown flags");
     if (c.kind == MSDA_HEADS_ARCTIC ? (c.n_mlp != 0 && c.n_mlp != 2) : c.n_mlp != 1)
@@ -341,92 +314,88 @@ int heads_check(const HeadsCall &c, bool backward)
     if (LM * widest >= (1LL << 31) || LM * (c.n_mlp > 0 ? c.R : 1) >= (1LL << 31))
         return herr("msda_heads: tensors beyond 2^31 elements");
     const int Lc = (c.flags & MSDA_HEADS_SHARED_CLS) ? 1 : c.L, Lw = (c.flags & MSDA_HEADS_SHARED_MLP) ? 1 : c.L;
-    const bool arctic_shared = c.kind == MSDA_HEADS_ARCTIC;
-    if (c.hs == nullptr || c.cls_w == nullptr || c.cls_b == nullptr) return herr("msda_heads: null pointer");
-    for (int l = 0; l < Lc; ++l)
-        if (c.cls_w[l] == nullptr || c.cls_b[l] == nullptr) return herr("msda_heads: null pointer");
-    if (c.n_mlp > 0) {
-        if (c.init_ref == nullptr || (c.L > 1 && c.inter_ref == nullptr) || c.mlp_w == nullptr || c.mlp_b == nullptr)
-            return herr("msda_heads: null pointer");
-        for (int i = 0; i < c.n_mlp * 3 * Lw; ++i)
-            if (c.mlp_w[i] == nullptr || c.mlp_b[i] == nullptr) return herr("msda_heads: null pointer");
+    const int n_shared = c.kind == MSDA_HEADS_ARCTIC ? kHeadsShared : 0, n_w = c.n_mlp * 3 * Lw;
+    // every array of n pointers that the call reads, and the single pointers beside them
+    auto all = [](auto a, int n) {
+        bool ok = n == 0 || a != nullptr;
+        for (int i = 0; ok && i < n; ++i) ok = a[i] != nullptr;
+        return ok;
+    };
+    bool ok = c.hs != nullptr && all(c.cls_w, Lc) && all(c.cls_b, Lc) && all(c.mlp_w, n_w) && all(c.mlp_b, n_w)
+              && all(c.shared_w, n_shared) && all(c.shared_b, n_shared);
+    if (c.n_mlp > 0)
+        ok = ok && c.init_ref != nullptr && (c.L == 1 || c.inter_ref != nullptr) && c.hidden != nullptr && c.sig != nullptr;
+    if (!backward)
+        ok = ok && c.logits != nullptr && all(c.kp_out, c.n_mlp) && all(c.shared_out, n_shared);
+    else
+        ok = ok && c.grad_logits != nullptr && c.grad_hs != nullptr && all(c.grad_cls_w, Lc) && all(c.grad_cls_b, Lc)
+             && all(c.grad_kp, c.n_mlp) && all(c.grad_mlp_w, n_w) && all(c.grad_mlp_b, n_w) && all(c.grad_shared, n_shared)
+             && all(c.grad_shared_w, n_shared) && all(c.grad_shared_b, n_shared)
+             && (c.ws != nullptr || (!f.aligned && c.ws_bytes == 0));           // the fp32 form's workspace may be empty
+    if (!ok) return herr("msda_heads: null pointer");
+    if (f.aligned) {
+        ok = aligned16(c.hs) && (c.n_mlp == 0 || aligned16(c.hidden));
+        for (int l = 0; l < Lc; ++l) ok = ok && aligned16(c.cls_w[l]);
+        for (int i = 0; i < n_w; ++i) ok = ok && aligned16(c.mlp_w[i]);
+        for (int g = 0; g < n_shared; ++g) ok = ok && aligned16(c.shared_w[g]);
+        if (!ok) return herr("msda_heads_bf16: hs, hidden and the weights must be 16-byte aligned");
+        if (backward && !aligned16(c.ws)) return herr("msda_heads_bf16: the workspace must be 16-byte aligned");
     }
-    if (arctic_shared) {
-        if (c.shared_w == nullptr || c.shared_b == nullptr) return herr("msda_heads: null pointer");
-        for (int g = 0; g < kHeadsShared; ++g)
-            if (c.shared_w[g] == nullptr || c.shared_b[g] == nullptr) return herr("msda_heads: null pointer");
-    }
-    if (c.n_mlp > 0 && (c.hidden == nullptr || c.sig == nullptr)) return herr("msda_heads: null pointer");
-    if (!backward) {
-        if (c.logits == nullptr || (c.n_mlp > 0 && c.kp_out == nullptr) || (arctic_shared && c.shared_out == nullptr))
-            return herr("msda_heads: null pointer");
-        for (int h = 0; h < c.n_mlp; ++h)
-            if (c.kp_out[h] == nullptr) return herr("msda_heads: null pointer");
-        for (int g = 0; arctic_shared && g < kHeadsShared; ++g)
-            if (c.shared_out[g] == nullptr) return herr("msda_heads: null pointer");
-        return MSDA_OK;
-    }
-    if (c.grad_logits == nullptr || c.grad_hs == nullptr || c.grad_cls_w == nullptr || c.grad_cls_b == nullptr
-        || (c.n_mlp > 0 && (c.grad_kp == nullptr || c.grad_mlp_w == nullptr || c.grad_mlp_b == nullptr))
-        || (arctic_shared && (c.grad_shared == nullptr || c.grad_shared_w == nullptr || c.grad_shared_b == nullptr)))
-        return herr("msda_heads: null pointer");
-    for (int l = 0; l < Lc; ++l)
-        if (c.grad_cls_w[l] == nullptr || c.grad_cls_b[l] == nullptr) return herr("msda_heads: null pointer");
-    for (int h = 0; h < c.n_mlp; ++h)
-        if (c.grad_kp[h] == nullptr) return herr("msda_heads: null pointer");
-    for (int i = 0; i < c.n_mlp * 3 * Lw; ++i)
-        if (c.grad_mlp_w[i] == nullptr || c.grad_mlp_b[i] == nullptr) return herr("msda_heads: null pointer");
-    for (int g = 0; arctic_shared && g < kHeadsShared; ++g)
-        if (c.grad_shared[g] == nullptr || c.grad_shared_w[g] == nullptr || c.grad_shared_b[g] == nullptr)
-            return herr("msda_heads: null pointer");
-    if (c.ws == nullptr && c.ws_bytes > 0) return herr("msda_heads: null pointer");
-    if (c.ws_bytes < heads_workspace_bytes(c.kind, c.L, c.M, c.C, c.K, c.n_mlp, c.flags))
-        return herr("msda_heads: workspace smaller than msda_heads_workspace_bytes");
+    if (backward && c.ws_bytes < heads_workspace_bytes(c.form, c.kind, c.L, c.M, c.C, c.K, c.n_mlp, c.flags)) return herr(f.ws_msg);
     return MSDA_OK;
 }
 
 // The weight problems of the backward, in one fixed order (the workspace layout follows it): class head(s), MLP layers
-// (head, layer, level), the six shared Linears.  `emit(dy, aux, x, row0, rows, n, mode, dw, db)`.
+// (head, layer, level), the six shared Linears.  Operands the call does not carry (heads_workspace_bytes) come out null.
+struct WeightProblem {
+    const void *dy, *aux, *x;
+    int dy_bf16, x_bf16, row0, rows, n, mode;
+    float *dw, *db;
+};
 template <class Emit>
-static void heads_weight_problems(const HeadsCall &c, Emit emit)
+void weight_problems(const HeadsCall &c, Emit emit)
 {
-    const long long LM = (long long)c.L * c.M;
-    const int M = (int)c.M, C = c.C, D = heads_D(c.kind);
+    const Form &f = kForms[c.form];
+    const Stacked at(c);
+    const int M = (int)c.M, LM = (int)at.LM, hb = f.hidden_bf16, ob = f.out_bf16[c.kind == MSDA_HEADS_ASSEMBLY];
     const bool shc = (c.flags & MSDA_HEADS_SHARED_CLS) != 0, shm = (c.flags & MSDA_HEADS_SHARED_MLP) != 0;
     const int Lc = shc ? 1 : c.L, Lw = shm ? 1 : c.L;
+    auto of = [](float *const *a, int i) { return a ? a[i] : nullptr; };
     for (int l = 0; l < Lc; ++l)
-        emit(c.grad_logits, (const float *)nullptr, c.hs, shc ? 0 : l * M, shc ? (int)LM : M, c.K, kHeadsModePlain,
-             c.grad_cls_w ? c.grad_cls_w[l] : nullptr, c.grad_cls_b ? c.grad_cls_b[l] : nullptr);
-    const float *dH = static_cast<const float *>(c.ws);                 // [n_mlp][2][LM][C]: dH1, dH2
+        emit(WeightProblem{c.grad_logits, nullptr, c.hs, ob, 0, shc ? 0 : l * M, shc ? LM : M, c.K, kHeadsModePlain,
+                           of(c.grad_cls_w, l), of(c.grad_cls_b, l)});
     for (int h = 0; h < c.n_mlp; ++h)
         for (int layer = 0; layer < 3; ++layer)
             for (int l = 0; l < Lw; ++l) {
                 const int wi = (h * 3 + layer) * Lw + l;
-                const float *H1 = c.hidden + (long long)(h * 2) * LM * C, *H2 = H1 + LM * C;
-                const float *dH1 = dH ? dH + (long long)(h * 2) * LM * C : nullptr, *dH2 = dH ? dH1 + LM * C : nullptr;
-                const float *dy = layer == 0 ? dH1 : layer == 1 ? dH2 : (c.grad_kp ? c.grad_kp[h] : nullptr);
-                const float *aux = layer == 0 ? H1 : layer == 1 ? H2 : c.sig + (long long)h * LM * D;
-                const float *x = layer == 0 ? c.hs : layer == 1 ? H1 : H2;
-                emit(dy, aux, x, shm ? 0 : l * M, shm ? (int)LM : M, layer == 2 ? D : C,
-                     layer == 2 ? kHeadsModeSigmoid : kHeadsModeRelu, c.grad_mlp_w ? c.grad_mlp_w[wi] : nullptr,
-                     c.grad_mlp_b ? c.grad_mlp_b[wi] : nullptr);
+                const void *dy = layer < 2 ? at.hidden(c.ws, h, layer) : c.grad_kp ? c.grad_kp[h] : nullptr;
+                const void *aux = layer < 2 ? at.hidden(c.hidden, h, layer) : at.sig(c.sig, h);
+                const void *x = layer == 0 ? c.hs : at.hidden(c.hidden, h, layer - 1);
+                emit(WeightProblem{dy, aux, x, layer < 2 ? hb : ob, layer == 0 ? 0 : hb, shm ? 0 : l * M, shm ? LM : M,
+                                   layer == 2 ? at.D : c.C, layer == 2 ? kHeadsModeSigmoid : kHeadsModeRelu, of(c.grad_mlp_w, wi),
+                                   of(c.grad_mlp_b, wi)});
             }
     if (c.kind == MSDA_HEADS_ARCTIC)
         for (int g = 0; g < kHeadsShared; ++g)
-            emit(c.grad_shared ? c.grad_shared[g] : nullptr, (const float *)nullptr, c.hs, 0, (int)LM, kSharedN[g],
-                 kHeadsModePlain, c.grad_shared_w ? c.grad_shared_w[g] : nullptr,
-                 c.grad_shared_b ? c.grad_shared_b[g] : nullptr);
+            emit(WeightProblem{c.grad_shared ? c.grad_shared[g] : nullptr, nullptr, c.hs, hb, 0, 0, LM, kSharedN[g], kHeadsModePlain,
+                               of(c.grad_shared_w, g), of(c.grad_shared_b, g)});
 }
 
-unsigned long long heads_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
+// the float offset of the first weight-gradient partial: behind the hidden gradients [n_mlp][2][L * M][C] (bf16: an even count)
+long long partials_offset(const HeadsCall &c) { return (long long)c.n_mlp * 2 * c.L * c.M * c.C * Stacked(c).es / 4; }
+
+}  // namespace
+
+bool heads_supported(int form, int C) { return C >= kForms[form].width && C <= 4096 && C % kForms[form].width == 0; }
+
+// The workspace: hidden gradients [n_mlp][2][L * M][C] in the form's hidden type, then per weight problem, in enumeration
+// order, fp32 partials [chunks][n][C] and [chunks][n].
+unsigned long long heads_workspace_bytes(int form, int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags)
 {
     HeadsCall c = {};
-    c.kind = kind; c.L = L; c.M = M; c.C = C; c.K = K; c.n_mlp = n_mlp; c.flags = flags;
-    const long long LM = (long long)L * M;
-    unsigned long long floats = (unsigned long long)n_mlp * 2 * LM * C;
-    heads_weight_problems(c, [&](const float *, const float *, const float *, int, int rows, int n, int, float *, float *) {
-        floats += (unsigned long long)chunks_of(rows) * n * (C + 1);
-    });
+    c.form = form; c.kind = kind; c.L = L; c.M = M; c.C = C; c.K = K; c.n_mlp = n_mlp; c.flags = flags;
+    unsigned long long floats = (unsigned long long)partials_offset(c);
+    weight_problems(c, [&](const WeightProblem &w) { floats += (unsigned long long)chunks_of(w.rows) * w.n * (C + 1); });
     return floats * sizeof(float);
 }
 
@@ -435,8 +404,10 @@ int heads_plan_forward(const HeadsCall &c, HeadsFwdPlan &plan)
     int rc = heads_check(c, false);
     if (rc != MSDA_OK) return rc;
     std::memset(&plan, 0, sizeof(plan));
-    const long long LM = (long long)c.L * c.M;
-    const int M = (int)c.M, C = c.C, D = heads_D(c.kind);
+    plan.form = c.form;
+    const Form &f = kForms[c.form];
+    const Stacked at(c);
+    const int M = (int)c.M, LM = (int)at.LM, C = c.C, hb = f.hidden_bf16, ob = f.out_bf16[c.kind == MSDA_HEADS_ASSEMBLY];
     const bool shc = (c.flags & MSDA_HEADS_SHARED_CLS) != 0, shm = (c.flags & MSDA_HEADS_SHARED_MLP) != 0;
     const int Lw = shm ? 1 : c.L;
     for (int d = 0; d < 3; ++d) {
@@ -447,37 +418,37 @@ int heads_plan_forward(const HeadsCall &c, HeadsFwdPlan &plan)
         a.C = C;
         a.R = c.R;
         int ng = 0, tiles = 0;
-        auto add = [&](const float *x, int row0, int rows, int epi, float *sig) -> HeadsFwdProb & {
+        auto add = [&](const void *x, int x_bf16, int row0, int rows, int epi, float *sig) -> HeadsFwdProb & {
             HeadsFwdProb &p = a.p[a.nprob++];
-            p.a = x; p.sig = sig; p.row0 = row0; p.rows = rows; p.epi = epi; p.g0 = ng; p.ng = 0; p.n = 0; p.tile0 = tiles;
+            p.a = x; p.a_bf16 = x_bf16; p.sig = sig; p.row0 = row0; p.rows = rows; p.epi = epi; p.g0 = ng; p.ng = 0; p.n = 0;
+            p.tile0 = tiles;
             return p;
         };
-        auto group = [&](HeadsFwdProb &p, const float *w, const float *b, float *out, int n) {
+        auto group = [&](HeadsFwdProb &p, const float *w, const float *b, void *out, int out_bf16, int n) {
             HeadsFwdGroup &g = a.g[ng++];
-            g.w = w; g.b = b; g.out = out; g.n = n; g.off = p.n;
+            g.w = w; g.b = b; g.out = out; g.out_bf16 = out_bf16; g.n = n; g.off = p.n;
             p.n += n;
             ++p.ng;
         };
         for (int l = 0; l < c.L; ++l) {
             if (d == 0) {
-                HeadsFwdProb &p = add(c.hs, l * M, M, kHeadsEpiBias, nullptr);
-                group(p, c.cls_w[shc ? 0 : l], c.cls_b[shc ? 0 : l], c.logits, c.K);
+                HeadsFwdProb &p = add(c.hs, 0, l * M, M, kHeadsEpiBias, nullptr);
+                group(p, c.cls_w[shc ? 0 : l], c.cls_b[shc ? 0 : l], c.logits, ob, c.K);
                 tiles += tiles_of(M, p.n);
             }
             for (int h = 0; h < c.n_mlp; ++h) {
                 const int wi = (h * 3 + d) * Lw + (shm ? 0 : l);
-                float *H1 = c.hidden + (long long)(h * 2) * LM * C, *H2 = H1 + LM * C;
-                const float *x = d == 0 ? c.hs : d == 1 ? H1 : H2;
-                float *out = d == 0 ? H1 : d == 1 ? H2 : c.kp_out[h];
+                const void *x = d == 0 ? c.hs : at.hidden(c.hidden, h, d - 1);
+                void *out = d < 2 ? at.hidden(c.hidden, h, d) : c.kp_out[h];
                 const int epi = d < 2 ? kHeadsEpiRelu : c.kind == MSDA_HEADS_ARCTIC ? kHeadsEpiArctic : kHeadsEpiAssembly;
-                HeadsFwdProb &p = add(x, l * M, M, epi, d == 2 ? c.sig + (long long)h * LM * D : nullptr);
-                group(p, c.mlp_w[wi], c.mlp_b[wi], out, d < 2 ? C : D);
+                HeadsFwdProb &p = add(x, d == 0 ? 0 : hb, l * M, M, epi, d == 2 ? at.sig(c.sig, h) : nullptr);
+                group(p, c.mlp_w[wi], c.mlp_b[wi], out, d < 2 ? hb : ob, d < 2 ? C : at.D);
                 tiles += tiles_of(M, p.n);
             }
         }
         if (d == 0 && c.kind == MSDA_HEADS_ARCTIC) {                    // the six shared Linears: ONE problem over L * M rows
-            HeadsFwdProb &p = add(c.hs, 0, (int)LM, kHeadsEpiBias, nullptr);
-            for (int g = 0; g < kHeadsShared; ++g) group(p, c.shared_w[g], c.shared_b[g], c.shared_out[g], kSharedN[g]);
+            HeadsFwdProb &p = add(c.hs, 0, 0, LM, kHeadsEpiBias, nullptr);
+            for (int g = 0; g < kHeadsShared; ++g) group(p, c.shared_w[g], c.shared_b[g], c.shared_out[g], hb, kSharedN[g]);
             tiles += tiles_of(LM, p.n);
         }
         plan.tiles[d] = tiles;
@@ -490,67 +461,65 @@ int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan)
     int rc = heads_check(c, true);
     if (rc != MSDA_OK) return rc;
     std::memset(&plan, 0, sizeof(plan));
-    const long long LM = (long long)c.L * c.M;
-    const int M = (int)c.M, C = c.C, D = heads_D(c.kind);
+    plan.form = c.form;
+    const Form &f = kForms[c.form];
+    const Stacked at(c);
+    const int M = (int)c.M, C = c.C, hb = f.hidden_bf16, ob = f.out_bf16[c.kind == MSDA_HEADS_ASSEMBLY];
     const bool shc = (c.flags & MSDA_HEADS_SHARED_CLS) != 0, shm = (c.flags & MSDA_HEADS_SHARED_MLP) != 0;
     const int Lw = shm ? 1 : c.L;
-    float *dH = static_cast<float *>(c.ws);
-    // input gradients: d[0] depth 3 -> dH2, d[1] depth 2 -> dH1, d[2] depth 1 -> grad_hs
+    // input gradients: d[0] depth 3 -> dH2, d[1] depth 2 -> dH1 (the workspace's hidden gradients), d[2] depth 1 -> fp32 grad_hs
     for (int step = 0; step < 3; ++step) {
         HeadsDgradArgs &a = plan.d[step];
         a.C = C;
         int ns = 0, tiles = 0;
         for (int l = 0; l < c.L; ++l) {
-            auto seg = [&](const float *x, const float *aux, const float *w, int k, int mode) {
+            auto seg = [&](const void *x, int x_bf16, const void *aux, const float *w, int k, int mode) {
                 HeadsDgradSeg &s = a.s[ns++];
-                s.a = x; s.aux = aux; s.w = w; s.k = k; s.mode = mode;
+                s.a = x; s.a_bf16 = x_bf16; s.aux = aux; s.w = w; s.k = k; s.mode = mode;
+                s.vec = vec_ok(x, aux, k, mode);
             };
-            auto prob = [&](float *out, int s0) {
+            auto prob = [&](void *out, int out_bf16, int s0) {
                 HeadsDgradProb &p = a.p[a.nprob++];
-                p.out = out; p.row0 = l * M; p.rows = M; p.s0 = s0; p.ns = ns - s0; p.tile0 = tiles;
+                p.out = out; p.out_bf16 = out_bf16; p.row0 = l * M; p.rows = M; p.s0 = s0; p.ns = ns - s0; p.tile0 = tiles;
                 tiles += tiles_of(M, C);
             };
             if (step < 2) {
                 for (int h = 0; h < c.n_mlp; ++h) {
-                    const float *H1 = c.hidden + (long long)(h * 2) * LM * C, *H2 = H1 + LM * C;
-                    float *dH1 = dH + (long long)(h * 2) * LM * C, *dH2 = dH1 + LM * C;
                     const int layer = 2 - step, wi = (h * 3 + layer) * Lw + (shm ? 0 : l);
                     const int s0 = ns;
-                    if (step == 0) seg(c.grad_kp[h], c.sig + (long long)h * LM * D, c.mlp_w[wi], D, kHeadsModeSigmoid);
-                    else seg(dH2, H2, c.mlp_w[wi], C, kHeadsModeRelu);
-                    prob(step == 0 ? dH2 : dH1, s0);
+                    if (step == 0) seg(c.grad_kp[h], ob, at.sig(c.sig, h), c.mlp_w[wi], at.D, kHeadsModeSigmoid);
+                    else seg(at.hidden(c.ws, h, 1), hb, at.hidden(c.hidden, h, 1), c.mlp_w[wi], C, kHeadsModeRelu);
+                    prob(at.hidden(c.ws, h, 1 - step), hb, s0);
                 }
             } else {
                 const int s0 = ns;
-                seg(c.grad_logits, nullptr, c.cls_w[shc ? 0 : l], c.K, kHeadsModePlain);
-                for (int h = 0; h < c.n_mlp; ++h) {
-                    const float *H1 = c.hidden + (long long)(h * 2) * LM * C;
-                    seg(dH + (long long)(h * 2) * LM * C, H1, c.mlp_w[(h * 3) * Lw + (shm ? 0 : l)], C, kHeadsModeRelu);
-                }
+                seg(c.grad_logits, ob, nullptr, c.cls_w[shc ? 0 : l], c.K, kHeadsModePlain);
+                for (int h = 0; h < c.n_mlp; ++h)
+                    seg(at.hidden(c.ws, h, 0), hb, at.hidden(c.hidden, h, 0), c.mlp_w[(h * 3) * Lw + (shm ? 0 : l)], C, kHeadsModeRelu);
                 if (c.kind == MSDA_HEADS_ARCTIC)
-                    for (int g = 0; g < kHeadsShared; ++g) seg(c.grad_shared[g], nullptr, c.shared_w[g], kSharedN[g], kHeadsModePlain);
-                prob(c.grad_hs, s0);
+                    for (int g = 0; g < kHeadsShared; ++g) seg(c.grad_shared[g], hb, nullptr, c.shared_w[g], kSharedN[g], kHeadsModePlain);
+                prob(c.grad_hs, 0, s0);
             }
         }
         plan.dtiles[step] = tiles;
     }
-    // weight gradients: partials per chunk, then the chunk-ordered sums
-    long long off = (long long)c.n_mlp * 2 * LM * C;
-    plan.w.ws = dH;
+    // weight gradients: fp32 partials per chunk behind the hidden gradients, then the chunk-ordered sums
+    long long off = partials_offset(c);
+    plan.w.ws = static_cast<float *>(c.ws);
     plan.w.C = C;
-    plan.r.ws = dH;
+    plan.r.ws = plan.w.ws;
     plan.r.C = C;
     int wt = 0, rb = 0;
-    heads_weight_problems(c, [&](const float *dy, const float *aux, const float *x, int row0, int rows, int n, int mode, float *dw,
-                                 float *db) {
+    weight_problems(c, [&](const WeightProblem &w) {
         HeadsWgradProb &p = plan.w.p[plan.w.nprob++];
-        p.dy = dy; p.aux = aux; p.x = x; p.part = off; p.row0 = row0; p.rows = rows; p.n = n; p.mode = mode;
-        p.chunks = chunks_of(rows); p.tile0 = wt;
-        wt += p.chunks * ((n + kHT - 1) / kHT) * ((C + kHT - 1) / kHT);
+        p.dy = w.dy; p.aux = w.aux; p.x = w.x; p.x_bf16 = w.x_bf16; p.part = off; p.row0 = w.row0; p.rows = w.rows; p.n = w.n;
+        p.dy_flags = (w.dy_bf16 ? kHeadsSrcBf16 : 0) | (vec_ok(w.dy, w.aux, w.n, w.mode) ? kHeadsSrcVec : 0);
+        p.mode = w.mode; p.chunks = chunks_of(w.rows); p.tile0 = wt;
+        wt += p.chunks * tiles_of(w.n, C);
         HeadsReduceProb &r = plan.r.p[plan.r.nprob++];
-        r.part = off; r.dw = dw; r.db = db; r.n = n; r.chunks = p.chunks; r.blk0 = rb;
-        rb += (int)(((long long)n * (C + 1) + kHBlock - 1) / kHBlock);
-        off += (long long)p.chunks * n * (C + 1);
+        r.part = off; r.dw = w.dw; r.db = w.db; r.n = w.n; r.chunks = p.chunks; r.tile0 = rb;
+        rb += (int)(((long long)w.n * (C + 1) + kHBlock - 1) / kHBlock);
+        off += (long long)p.chunks * w.n * (C + 1);
     });
     plan.wtiles = wt;
     plan.rblocks = rb;
@@ -560,7 +529,8 @@ int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan)
 int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream)
 {
     for (int d = 0; d < 3; ++d) {
-        const int rc = launch_heads_forward(plan.a[d], plan.tiles[d], stream);
+        const int rc = plan.form == kHeadsBf16 ? launch_heads_forward_bf16(plan.a[d], plan.tiles[d], stream)
+                                               : heads_launch(heads_fwd_kernel, "heads_fwd_kernel", plan.a[d], plan.tiles[d], stream);
         if (rc != MSDA_OK) return rc;
     }
     return MSDA_OK;
@@ -568,13 +538,16 @@ int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream)
 
 int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream)
 {
+    const bool bf = plan.form == kHeadsBf16;
     for (int s = 0; s < 3; ++s) {
-        const int rc = launch_heads_dgrad(plan.d[s], plan.dtiles[s], stream);
+        const int rc = bf ? launch_heads_dgrad_bf16(plan.d[s], plan.dtiles[s], stream)
+                          : heads_launch(heads_dgrad_kernel, "heads_dgrad_kernel", plan.d[s], plan.dtiles[s], stream);
         if (rc != MSDA_OK) return rc;
     }
-    int rc = launch_heads_wgrad(plan.w, plan.wtiles, stream);
+    const int rc = bf ? launch_heads_wgrad_bf16(plan.w, plan.wtiles, stream)
+                      : heads_launch(heads_wgrad_kernel, "heads_wgrad_kernel", plan.w, plan.wtiles, stream);
     if (rc != MSDA_OK) return rc;
-    return launch_heads_reduce(plan.r, plan.rblocks, stream);
+    return heads_launch(heads_reduce_kernel, "heads_reduce_kernel", plan.r, plan.rblocks, stream);
 }
 
 }  // namespace msda

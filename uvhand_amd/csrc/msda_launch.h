@@ -217,21 +217,27 @@ int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, in
 int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
                          const int32_t *stats, hipStream_t stream);
 
-// ---- the DeformableDETR prediction heads as grouped fp32 GEMMs (msda_heads.hip) ----
-// Every problem table travels by value in the kernel arguments (each struct below stays under 4 KB).
+// ---- the DeformableDETR prediction heads as grouped GEMMs: fp32 (msda_heads.hip) and bf16 autocast (msda_heads_bf16.hip) ----
+// One set of problem tables, one planner (msda_heads.hip) and one workspace layout serve both forms; a table says beside every
+// pointer that can be either whether it is bf16, and the fp32 kernels ignore those flags.  Every problem table travels by value
+// in the kernel arguments (each struct below stays under 4 KB).
+constexpr int kHeadsF32 = 0, kHeadsBf16 = 1;                        // the form of a call / a plan
 constexpr int kHeadsMaxLevels = 8, kHeadsMaxMlp = 2, kHeadsShared = 6;
+constexpr int kHeadsTile = 64;                                      // output tile edge of every GEMM kernel of both forms
+constexpr int kHeadsReduceBlock = 256;                              // heads_reduce_kernel's workgroup: elements per block
 constexpr int kHeadsWgradChunk = 2048;                              // rows per weight-gradient partial
 constexpr int kHeadsEpiBias = 0, kHeadsEpiRelu = 1, kHeadsEpiArctic = 2, kHeadsEpiAssembly = 3;
 constexpr int kHeadsModePlain = 0, kHeadsModeSigmoid = 1, kHeadsModeRelu = 2;
+constexpr int kHeadsSrcBf16 = 1, kHeadsSrcVec = 2;                  // HeadsWgradProb::dy_flags
 struct HeadsFwdGroup {          // columns [off, off + n) of a problem: one weight [n, C], its bias, its output [L * M, n]
     const float *w, *b;
-    float *out;
-    int n, off;
+    void *out;
+    int n, off, out_bf16, pad;
 };
 struct HeadsFwdProb {           // rows [row0, row0 + rows) of the flattened input a [L * M, C]
-    const float *a;
+    const void *a;
     float *sig;                 // keypoint epilogues: the saved sigmoid [L * M, n]
-    int row0, rows, n, epi, g0, ng, tile0, pad;
+    int row0, rows, n, epi, g0, ng, tile0, a_bf16;
 };
 constexpr int kHeadsFwdMaxProbs = kHeadsMaxLevels * (1 + kHeadsMaxMlp) + 1;
 constexpr int kHeadsFwdMaxGroups = kHeadsFwdMaxProbs + kHeadsShared;
@@ -241,13 +247,14 @@ struct HeadsFwdArgs {
     const float *init_ref, *inter_ref;
     int nprob, M, C, R;
 };
-struct HeadsDgradSeg {          // one reduction segment: dy [L * M, k] (o mode, aux of the same layout) times w [k, C]
-    const float *a, *aux, *w;
-    int k, mode;
+struct HeadsDgradSeg {          // one reduction segment: dy [L * M, k] o mode (aux: fp32 sigmoids / saved activations) times w [k, C]
+    const void *a, *aux;
+    const float *w;
+    int k, mode, a_bf16, vec;   // vec (bf16 form): k % 8 == 0, 16-byte aligned rows, no sigmoid: 8 elements per load
 };
 struct HeadsDgradProb {
-    float *out;                 // [L * M, C]
-    int row0, rows, s0, ns, tile0, pad;
+    void *out;                  // [L * M, C]: a hidden gradient, or fp32 grad_hs
+    int row0, rows, s0, ns, tile0, out_bf16;
 };
 constexpr int kHeadsDgradMaxProbs = kHeadsMaxLevels * kHeadsMaxMlp;
 constexpr int kHeadsDgradMaxSegs = kHeadsMaxLevels * (1 + kHeadsMaxMlp + kHeadsShared);
@@ -257,9 +264,9 @@ struct HeadsDgradArgs {
     int nprob, C;
 };
 struct HeadsWgradProb {         // dW [n, C] of one weight over rows [row0, row0 + rows): dy / aux [L * M, n], x [L * M, C]
-    const float *dy, *aux, *x;
+    const void *dy, *aux, *x;
     long long part;             // float offset of its partials in the workspace: [chunks][n][C], then [chunks][n]
-    int row0, rows, n, mode, chunks, tile0;
+    int row0, rows, n, mode, chunks, tile0, dy_flags, x_bf16;      // dy_flags: kHeadsSrcBf16 | kHeadsSrcVec (as HeadsDgradSeg::vec)
 };
 constexpr int kHeadsWgradMaxProbs = kHeadsMaxLevels * (1 + 3 * kHeadsMaxMlp) + kHeadsShared;
 struct HeadsWgradArgs {
@@ -270,7 +277,7 @@ struct HeadsWgradArgs {
 struct HeadsReduceProb {
     long long part;
     float *dw, *db;
-    int n, chunks, blk0, pad;
+    int n, chunks, tile0, pad;  // tile0: its first workgroup
 };
 struct HeadsReduceArgs {
     HeadsReduceProb p[kHeadsWgradMaxProbs];
@@ -279,21 +286,20 @@ struct HeadsReduceArgs {
 };
 static_assert(sizeof(HeadsFwdArgs) <= 4000 && sizeof(HeadsDgradArgs) <= 4000 && sizeof(HeadsWgradArgs) <= 4000
               && sizeof(HeadsReduceArgs) <= 4000, "kernel argument tables");
-int launch_heads_forward(const HeadsFwdArgs &a, int tiles, hipStream_t stream);
-int launch_heads_dgrad(const HeadsDgradArgs &a, int tiles, hipStream_t stream);
-int launch_heads_wgrad(const HeadsWgradArgs &a, int tiles, hipStream_t stream);
-int launch_heads_reduce(const HeadsReduceArgs &a, int blocks, hipStream_t stream);
 
-// One call's operands as the C entries receive them (include/msda.h, msda_heads_*); the plan functions check them and build
-// the problem tables without launching anything, the run functions launch.
+// One call's operands as the C entries receive them (include/msda.h, msda_heads_*), in either form.  hs, the parameters, the
+// references, sig and every parameter gradient are fp32 in both; the operands behind void pointers are fp32 in the fp32 form
+// and carry the dtypes of torch's bf16 autocast in the bf16 form: hidden, the shared outputs and their gradients bf16; logits /
+// keypoints and their gradients fp32 (ARCTIC) or bf16 (AssemblyHands).
 struct HeadsCall {
-    int kind, L, n_mlp, R, C, K;
+    int form, kind, L, n_mlp, R, C, K;
     long long M;
     unsigned flags;
     const float *hs, *init_ref, *inter_ref;
     const float *const *cls_w, *const *cls_b, *const *mlp_w, *const *mlp_b, *const *shared_w, *const *shared_b;
-    float *logits, *const *kp_out, *const *shared_out, *hidden, *sig;
-    const float *grad_logits, *const *grad_kp, *const *grad_shared;
+    void *logits, *const *kp_out, *const *shared_out, *hidden;
+    float *sig;
+    const void *grad_logits, *const *grad_kp, *const *grad_shared;
     float *grad_hs, *const *grad_cls_w, *const *grad_cls_b, *const *grad_mlp_w, *const *grad_mlp_b, *const *grad_shared_w,
         *const *grad_shared_b;
     void *ws;
@@ -301,7 +307,7 @@ struct HeadsCall {
 };
 struct HeadsFwdPlan {
     HeadsFwdArgs a[3];
-    int tiles[3];
+    int tiles[3], form;
 };
 struct HeadsBwdPlan {
     HeadsDgradArgs d[3];
@@ -309,42 +315,28 @@ struct HeadsBwdPlan {
     HeadsWgradArgs w;
     int wtiles;
     HeadsReduceArgs r;
-    int rblocks;
+    int rblocks, form;
 };
-int heads_check(const HeadsCall &c, bool backward);
-unsigned long long heads_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
+// The planner (msda_heads.hip): plan_* checks the call and builds the problem tables without launching anything, run_* launches
+// the plan's tables on its form's kernels.
+bool heads_supported(int form, int C);
+unsigned long long heads_workspace_bytes(int form, int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
 int heads_plan_forward(const HeadsCall &c, HeadsFwdPlan &plan);
 int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan);
 int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream);
 int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream);
-
-// ---- the same heads under bf16 autocast, on the bf16 MFMA (msda_heads_bf16.hip; C entries msda_heads_*_bf16) ----
-// HeadsCall's operands with the dtypes of torch's bf16 autocast: hs, parameters, references, sig and every parameter gradient
-// fp32; hidden, the shared outputs and their gradients bf16; logits / keypoints and their gradients fp32 (ARCTIC) or bf16
-// (AssemblyHands).  plan_* checks the call and builds this thread's problem tables without launching, run_* launches them.
-constexpr int kHeadsReduceBlock = 256;                              // launch_heads_reduce's workgroup: elements per block
-struct HeadsBf16Call {
-    int kind, L, n_mlp, R, C, K;
-    long long M;
-    unsigned flags;
-    const float *hs, *init_ref, *inter_ref;
-    const float *const *cls_w, *const *cls_b, *const *mlp_w, *const *mlp_b, *const *shared_w, *const *shared_b;
-    void *logits, *const *kp_out;
-    uint16_t *const *shared_out, *hidden;
-    float *sig;
-    const void *grad_logits, *const *grad_kp;
-    const uint16_t *const *grad_shared;
-    float *grad_hs, *const *grad_cls_w, *const *grad_cls_b, *const *grad_mlp_w, *const *grad_mlp_b, *const *grad_shared_w,
-        *const *grad_shared_b;
-    void *ws;
-    unsigned long long ws_bytes;
-};
-bool heads_bf16_supported(int C);
-unsigned long long heads_bf16_workspace_bytes(int kind, int L, long long M, int C, int K, int n_mlp, unsigned flags);
-int heads_bf16_plan_forward(const HeadsBf16Call &c);
-int heads_bf16_plan_backward(const HeadsBf16Call &c);
-int heads_bf16_run_forward(hipStream_t stream);
-int heads_bf16_run_backward(hipStream_t stream);
+// the bf16 form's kernels (msda_heads_bf16.hip); zero tiles: no launch
+int launch_heads_forward_bf16(const HeadsFwdArgs &a, int tiles, hipStream_t stream);
+int launch_heads_dgrad_bf16(const HeadsDgradArgs &a, int tiles, hipStream_t stream);
+int launch_heads_wgrad_bf16(const HeadsWgradArgs &a, int tiles, hipStream_t stream);
+// one grid of `groups` workgroups of 256 threads, none when groups == 0
+template <class Args>
+int heads_launch(void (*kernel)(Args), const char *name, const Args &a, int groups, hipStream_t stream)
+{
+    if (groups == 0) return MSDA_OK;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(256), 0, stream, a);
+    return check_launch(name);
+}
 
 // ---- Swin window attention, head_dim 32, windows up to 12 x 12 (msda_swin.hip; C entries msda_swin_attn_*) ----
 bool swin_supported(int B, int H, int W, int C, int nH, int ws, int shift);

@@ -648,6 +648,38 @@ int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_m
                              float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                              unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* ---- The layers' FFN under bf16 autocast: linear2(dropout(relu(linear1(x)))) of every encoder and decoder layer
+ * (models/arctic_transformer.py:283-287, :366-370) -------------------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
+ *
+ * x [M, C] (fp32, or bf16 bits when x_is_bf16), w1 [F, C], b1 [F], w2 [C, F], b2 [C] fp32; a [M, F] and y [M, C] bf16 bits.
+ * Every product runs on the bf16 MFMA with fp32 accumulation; x, w1 and w2 are rounded to bf16 (nearest even) in the loads that
+ * stage them.  h = rnd(x . w1^T + b1) (fp32 bias, one rounding; never stored), a = rnd(relu(h) * keep / (1 - p)),
+ * y = rnd(a . w2^T + b2).  p == 0: no dropout (evaluation); p > 0: keep is a hash of (*seed, row * F + column) (seed: device),
+ * not nn.Dropout's stream, and the backward reads a > 0 instead of a mask.
+ *   msda_ffn_forward_bf16   (models/arctic_transformer.py:283-287, :366-370) ONE launch.  Writes a, y and, for an fp32 x, its
+ *       bf16 rounding xb [M, C] (null for a bf16 x, which is then the backward's xb itself).
+ *   msda_ffn_backward_bf16  (the gradient of models/arctic_transformer.py:283-287, :366-370) at most 5 launches:
+ *       gh = rnd((grad_out . w2) / (1 - p) * [a > 0]) (bf16, in the workspace), grad_x = gh . w1 (fp32, or rounded once to bf16
+ *       when grad_x_is_bf16), the two weight gradients' first stages (grad_w2 = grad_out^T . a, grad_w1 = gh^T . xb, fp32 with
+ *       their bias gradients, as msda_linear_wgrad_multi) and their one second stage.  A null grad_x, grad_w1 (with grad_b1) or
+ *       grad_w2 (with grad_b2) is not computed; gh only when grad_x or grad_w1 is asked for.  workspace: at least
+ *       msda_ffn_bf16_workspace_bytes(M, C, F) bytes (gh and the weight gradients' partial sums).
+ *   msda_ffn_bf16_supported (models/arctic_transformer.py:283-287, :366-370: C = 256, F = 1024 or 2048) 1 when C % 64 == 0,
+ *       64 <= C <= 256, F % 64 == 0 and 64 <= F <= 8192.
+ *   msda_ffn_bf16_workspace_bytes  (the backward of models/arctic_transformer.py:283-287, :366-370) 0 for sizes the entries
+ *       refuse.
+ * M >= 1, M * F < 2^31, 0 <= p < 1; x, xb, a, y, grad_out, grad_x, the weights and the workspace 16-byte aligned.
+ * Fixed summation order: bitwise reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+int msda_ffn_bf16_supported(int C, int F);
+unsigned long long msda_ffn_bf16_workspace_bytes(long long M, int C, int F);
+int msda_ffn_forward_bf16(long long M, int C, int F, const void *x, int x_is_bf16, const float *w1, const float *b1, const float *w2,
+                          const float *b2, double p, const long long *seed, uint16_t *xb, uint16_t *a, uint16_t *y,
+                          msda_stream_t stream);
+int msda_ffn_backward_bf16(long long M, int C, int F, const uint16_t *grad_out, const uint16_t *xb, const uint16_t *a, const float *w1,
+                           const float *w2, double p, void *grad_x, int grad_x_is_bf16, float *grad_w1, float *grad_b1,
+                           float *grad_w2, float *grad_b2, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream);
+
 /* ---- SmoothNet (models/smoothnet.py:7-178): MotionSmoother modules as grouped fp32 GEMMs, and get_arctic_item's query
  * selection (arctic_tools/process.py:20-70) ---------------------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

@@ -109,6 +109,10 @@ SIGNATURES = {
     "msda_heads_backward_f32": "i ii l iiii u ppppppppp ppppp pppppppp U p",
     "msda_heads_bf16_supported": "i i",
     "msda_heads_bf16_workspace_bytes": "U ii l iii u",
+    "msda_ffn_bf16_supported": "i ii",
+    "msda_ffn_bf16_workspace_bytes": "U l ii",
+    "msda_ffn_forward_bf16": "i l ii p i pppp d p ppp p",
+    "msda_ffn_backward_bf16": "i l ii ppppp d p i pppp p U p",
     "msda_heads_forward_bf16": "i ii l iiii u ppppppppp pppppp",
     "msda_heads_backward_bf16": "i ii l iiii u ppppppppp ppppp pppppppp U p",
     # SmoothNet and get_arctic_item's selection
@@ -1353,6 +1357,56 @@ def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
     _launch(dev, "msda_criterion_bwd_f32", "criterion_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
             _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None, _ptr_array(g_obj) if g_obj else None)
     return g_logits, g_hand, g_obj
+
+
+# ---- the layers' FFN under bf16 autocast (csrc/msda_ffn_bf16.hip) ------------------------------------------------------------
+def ffn_bf16_supported(C, F):
+    """msda_ffn_bf16_supported (include/msda.h): 1 when the bf16-autocast FFN kernels take model width C and hidden width F."""
+    return bool((_lib or load()).msda_ffn_bf16_supported(int(C), int(F)))
+
+
+def ffn_bf16_workspace_bytes(M, C, F):
+    """msda_ffn_bf16_workspace_bytes (include/msda.h): the backward's workspace; 0 for sizes the entries refuse."""
+    return int((_lib or load()).msda_ffn_bf16_workspace_bytes(int(M), int(C), int(F)))
+
+
+def ffn_forward_bf16(x2, w1, b1, w2, b2, p=0.0, seed=None):
+    """msda_ffn_forward_bf16 (include/msda.h): the FFN of x2 [M, C] (contiguous fp32 or bf16) in ONE launch.  p > 0 needs a
+    one-element int64 CUDA ``seed``.  Returns (xb, a, y): x2 as bf16 (x2 itself when it is bf16), a [M, F] and y [M, C], bf16."""
+    M, C = x2.shape
+    F = w1.shape[0]
+    bf = x2.dtype == torch.bfloat16
+    if p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise RuntimeError("ffn_forward_bf16: dropout needs a one-element int64 CUDA seed tensor")
+    xb = x2 if bf else torch.empty((M, C), dtype=torch.bfloat16, device=x2.device)
+    a = torch.empty((M, F), dtype=torch.bfloat16, device=x2.device)
+    y = torch.empty((M, C), dtype=torch.bfloat16, device=x2.device)
+    _launch(x2.device, "msda_ffn_forward_bf16", "ffn_forward_bf16", M, C, F, x2.data_ptr(), int(bf), w1.data_ptr(), b1.data_ptr(),
+            w2.data_ptr(), b2.data_ptr(), float(p), seed.data_ptr() if p > 0 else None, None if bf else xb.data_ptr(),
+            a.data_ptr(), y.data_ptr())
+    return xb, a, y
+
+
+def ffn_backward_bf16(go2, xb, a, w1, w2, p, x_dtype, need_x, need_w1, need_b1, need_w2, need_b2):
+    """msda_ffn_backward_bf16 (include/msda.h): (gx, gw1, gb1, gw2, gb2) of the node, None where not needed; gx [M, C] in
+    ``x_dtype``, the parameter gradients fp32.  At most 5 launches: gh, gx, two weight-gradient first stages, one second
+    stage; a gradient that is not needed costs none (a bias gradient alone still computes its weight gradient)."""
+    M, C = xb.shape
+    F = a.shape[1]
+    dev, f32 = xb.device, torch.float32
+    w1g, w2g = need_w1 or need_b1, need_w2 or need_b2
+    gx = torch.empty((M, C), dtype=x_dtype, device=dev) if need_x else None
+    gw1 = torch.empty((F, C), dtype=f32, device=dev) if w1g else None
+    gb1 = torch.empty((F,), dtype=f32, device=dev) if need_b1 else None
+    gw2 = torch.empty((C, F), dtype=f32, device=dev) if w2g else None
+    gb2 = torch.empty((C,), dtype=f32, device=dev) if need_b2 else None
+    nbytes = ffn_bf16_workspace_bytes(M, C, F)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _launch(dev, "msda_ffn_backward_bf16", "ffn_backward_bf16", M, C, F, go2.data_ptr(), xb.data_ptr(), a.data_ptr(),
+            w1.data_ptr(), w2.data_ptr(), float(p), ptr(gx), int(x_dtype == torch.bfloat16), ptr(gw1), ptr(gb1), ptr(gw2),
+            ptr(gb2), ws.data_ptr(), nbytes)
+    return gx, (gw1 if need_w1 else None), gb1, (gw2 if need_w2 else None), gb2
 
 
 # ---- the DeformableDETR prediction heads, fp32 and bf16 autocast (csrc/msda_heads.hip, csrc/msda_heads_bf16.hip) ------------

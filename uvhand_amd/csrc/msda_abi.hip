@@ -1277,6 +1277,32 @@ int msda_heads_backward_bf16(int kind, int L, long long M, int C, int K, int n_m
                           grad_shared_w, grad_shared_b, workspace, workspace_bytes, stream);
 }
 
+/* ---- the layers' FFN under bf16 autocast (msda_ffn_bf16.hip): models/arctic_transformer.py:283-287, :366-370 ---- */
+int msda_ffn_bf16_supported(int C, int F) { return msda::ffn_bf16_supported(C, F) ? 1 : 0; }
+
+unsigned long long msda_ffn_bf16_workspace_bytes(long long M, int C, int F) { return msda::ffn_bf16_workspace_bytes(M, C, F); }
+
+int msda_ffn_forward_bf16(long long M, int C, int F, const void *x, int x_is_bf16, const float *w1, const float *b1, const float *w2,
+                          const float *b2, double p, const long long *seed, uint16_t *xb, uint16_t *a, uint16_t *y,
+                          msda_stream_t stream)
+{
+    if (int rc = msda::ffn_check_forward_bf16(M, C, F, x, x_is_bf16, w1, b1, w2, b2, p, seed, xb, a, y)) return rc;
+    msda::begin_call();
+    return msda::launch_ffn_forward_bf16(M, C, F, x, x_is_bf16, w1, b1, w2, b2, p, seed, xb, a, y, (hipStream_t)stream);
+}
+
+int msda_ffn_backward_bf16(long long M, int C, int F, const uint16_t *grad_out, const uint16_t *xb, const uint16_t *a, const float *w1,
+                           const float *w2, double p, void *grad_x, int grad_x_is_bf16, float *grad_w1, float *grad_b1,
+                           float *grad_w2, float *grad_b2, void *workspace, unsigned long long workspace_bytes, msda_stream_t stream)
+{
+    if (int rc = msda::ffn_check_backward_bf16(M, C, F, grad_out, xb, a, w1, w2, p, grad_x, grad_w1, grad_b1, grad_w2, grad_b2,
+                                               workspace, workspace_bytes))
+        return rc;
+    msda::begin_call();
+    return msda::launch_ffn_backward_bf16(M, C, F, grad_out, xb, a, w1, w2, p, grad_x, grad_x_is_bf16, grad_w1, grad_b1, grad_w2,
+                                          grad_b2, workspace, (hipStream_t)stream);
+}
+
 /* ---- Swin window attention (msda_swin.hip): replaces models/swin_transformer.py:126-142 (WindowAttention.forward's scores,
  * relative position bias, mask, softmax and weighted sum), :210-240 (SwinTransformerBlock's pad, roll, partition, reverse, roll
  * back and crop) and :339-357 (BasicLayer's shift mask) ---- */

@@ -29,21 +29,7 @@ constexpr int kAtWaves = MSDA_AT_WAVES, kAtBlock = kAtWaves * 64, kAtMaxTiles = 
 
 struct AtView { float *p; long long sn, sl; };          // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
 
-// 32 bits per (pair, query, key): the counter (query << 16) + key + mix — mix = seed and pair, uniform — through the two
-// multiply-xorshift rounds of the usual 32-bit finalizer; its last xor-shift is left out (it only folds high bits into low ones,
-// and the result is compared with a threshold).  v_mul_lo_u32 is a quarter-rate instruction and the vector unit is as busy as the
-// matrix pipe in these kernels: a lane adds its part of the counter once per tile, an element one constant.
-__device__ __forceinline__ unsigned at_mix(unsigned long long seed, unsigned pair)
-{
-    return (unsigned)seed + pair * 0x9E3779B1u + (unsigned)(seed >> 32) * 0x85EBCA6Bu;
-}
-__device__ __forceinline__ unsigned at_hash(unsigned counter)
-{
-    unsigned x = counter;
-    x ^= x >> 16; x *= 0x85EBCA6Bu;
-    x ^= x >> 13; x *= 0xC2B2AE35u;
-    return x;
-}
+// Dropout: 32 bits per (pair, query, key) from at_hash of the counter (query << 16) + key + at_mix(seed, pair) (msda_attn_tile.h)
 
 // rows [0, L) of two [L][32] slices (row strides sl0 / sl1) -> dst0 / dst1 [Lp][kAtRow]; rows [L, Lp) zero.  Lp * 8 float4 per
 // slice on 640 threads: at most four rounds (Lp <= 320); all the loads of a thread are issued before its first LDS store.

@@ -37,6 +37,23 @@ typedef __attribute__((address_space(3))) at_bf4 at_lds_bf4;
 __device__ __forceinline__ at_f4 at_mfma(float a, float b, at_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ at_f4 ab_mfma(at_bf8 a, at_bf8 b, at_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
+// ---- the dropout hash (msda_attn.hip: attention dropout; msda_ffn_bf16.hip: the FFN's) -------------------------------------
+// 32 bits per element: a counter + mix — mix = seed and pair, uniform — through the two multiply-xorshift rounds of the usual
+// 32-bit finalizer; its last xor-shift is left out (it only folds high bits into low ones, and the result is compared with a
+// threshold).  v_mul_lo_u32 is a quarter-rate instruction and the vector unit is as busy as the matrix pipe in these kernels:
+// a lane adds its part of the counter once per tile, an element one constant.
+__device__ __forceinline__ unsigned at_mix(unsigned long long seed, unsigned pair)
+{
+    return (unsigned)seed + pair * 0x9E3779B1u + (unsigned)(seed >> 32) * 0x85EBCA6Bu;
+}
+__device__ __forceinline__ unsigned at_hash(unsigned counter)
+{
+    unsigned x = counter;
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    return x;
+}
+
 // ---- fp32 ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float4 at_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 

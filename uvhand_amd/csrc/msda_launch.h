@@ -338,6 +338,22 @@ int heads_launch(void (*kernel)(Args), const char *name, const Args &a, int grou
     return check_launch(name);
 }
 
+// ---- the layers' FFN under bf16 autocast (msda_ffn_bf16.hip; C entries msda_ffn_*_bf16): the checks return MSDA_OK or an
+// argument error and launch nothing; the launchers take checked arguments ----
+bool ffn_bf16_supported(int C, int F);
+size_t ffn_bf16_workspace_bytes(long long M, int C, int F);
+int ffn_check_forward_bf16(long long M, int C, int F, const void *x, int x_is_bf16, const float *w1, const float *b1, const float *w2,
+                           const float *b2, double p, const long long *seed, const uint16_t *xb, const uint16_t *a, const uint16_t *y);
+int launch_ffn_forward_bf16(long long M, int C, int F, const void *x, int x_is_bf16, const float *w1, const float *b1, const float *w2,
+                            const float *b2, double p, const long long *seed, uint16_t *xb, uint16_t *a, uint16_t *y,
+                            hipStream_t stream);
+int ffn_check_backward_bf16(long long M, int C, int F, const uint16_t *grad_out, const uint16_t *xb, const uint16_t *a, const float *w1,
+                            const float *w2, double p, const void *grad_x, const float *grad_w1, const float *grad_b1,
+                            const float *grad_w2, const float *grad_b2, const void *workspace, unsigned long long workspace_bytes);
+int launch_ffn_backward_bf16(long long M, int C, int F, const uint16_t *grad_out, const uint16_t *xb, const uint16_t *a, const float *w1,
+                             const float *w2, double p, void *grad_x, int grad_x_is_bf16, float *grad_w1, float *grad_b1,
+                             float *grad_w2, float *grad_b2, void *workspace, hipStream_t stream);
+
 // ---- Swin window attention, head_dim 32, windows up to 12 x 12 (msda_swin.hip; C entries msda_swin_attn_*) ----
 bool swin_supported(int B, int H, int W, int C, int nH, int ws, int shift);
 unsigned long long swin_workspace_bytes(int B, int H, int W, int C, int nH, int ws, int shift, int which);

@@ -13,6 +13,10 @@ Under ``torch.autocast(bfloat16)`` the same is done on bf16 operands (``_Bracket
 ``F.linear`` — PyTorch's own implementation of the same layer, not an alternative implementation of the op —
 whenever the kernels' preconditions do not hold (CPU tensors, other dtypes, fp16 autocast, feature counts not
 multiples of 4), so the module keeps working everywhere nn.Linear does.
+
+``fused_ffn`` — the layers' FFN as one node: ``_FusedFFNFn`` in fp32, and under bf16 autocast with ``MSDA_FFN_BF16=1`` the
+library's own bf16 MFMA kernels (``_FusedFFNAmpFn``, csrc/msda_ffn_bf16.hip); ``ffn_keep_mask`` and
+``fused_ffn_bf16_reference`` restate that node's dropout mask and rounding points in torch ops.
 """
 import os
 
@@ -211,13 +215,116 @@ class _FusedFFNFn(Function):
         return gx, gw1, gb1, gw2, gb2, None, None
 
 
+_M32 = 0xFFFFFFFF
+
+
+def ffn_keep_mask(seed, rows, F, p):
+    """The dropout keep mask [rows, F] (bool) of the bf16 FFN node for ``seed`` (an int, or a one-element int64 tensor on any
+    device: the mask is built there, without a host read): the host restatement of the kernel's counter hash (at_mix /
+    at_hash, csrc/msda_attn_tile.h) in integer torch ops — element (row, col) has the counter ``row * F + col`` and is kept
+    iff its 32 hash bits are >= p * 2^32.  p == 0 keeps everything."""
+    dev = seed.device if torch.is_tensor(seed) else torch.device("cpu")
+    if p <= 0:
+        return torch.ones((rows, F), dtype=torch.bool, device=dev)
+    s = seed.reshape(()).to(torch.int64) if torch.is_tensor(seed) else torch.tensor(
+        (int(seed) & 0xFFFFFFFFFFFFFFFF) - (1 << 64 if int(seed) & (1 << 63) else 0), dtype=torch.int64)
+    mix = ((s & _M32) + ((s >> 32) & _M32) * 0x85EBCA6B) & _M32
+    x = (torch.arange(rows * F, dtype=torch.int64, device=dev) + mix) & _M32
+    x = ((x ^ (x >> 16)) * 0x85EBCA6B) & _M32
+    x = ((x ^ (x >> 13)) * 0xC2B2AE35) & _M32
+    return (x >= int(min(4294967295.0, float(p) * 4294967296.0))).view(rows, F)
+
+
+def fused_ffn_bf16_reference(x, w1, b1, w2, b2, p, keep):
+    """The rounding points of the bf16 FFN node (_FusedFFNAmpFn) in plain torch ops, on any device and differentiable:
+    operands rounded to bf16, fp32 products and sums, the fp32 bias added before the one rounding of ``h``,
+    ``a = rnd(relu(h) * keep / (1 - p))`` (``keep``: a bool mask [rows, F], or None for evaluation / p == 0) and
+    ``y = rnd(a @ W2^T + b2)``, bf16 with ``x``'s leading shape.  Its autograd rounds where the node's backward rounds (the
+    gradient of ``h`` once to bf16; ``gx`` once when ``x`` is bf16; parameter gradients unrounded fp32)."""
+    bf, f32 = torch.bfloat16, torch.float32
+
+    def rnd(t):                             # fp32 tensor of bf16 values; the gradient passes through unrounded
+        t = t.to(f32)
+        return t + (t.to(bf).to(f32) - t).detach()
+
+    with torch.autocast(x.device.type, enabled=False):             # the roundings are spelled out: no autocast inside
+        x2 = x.reshape(-1, x.shape[-1])
+        x2 = x2.to(f32) if x2.dtype == bf else rnd(x2)              # a bf16 x receives its gradient rounded once to bf16
+        h = (x2 @ rnd(w1).t() + b1.to(f32)).to(bf)                  # the one bf16 tensor inside: its gradient is gh, rounded once
+        a = torch.relu(h.to(f32))
+        if keep is not None and p > 0:
+            a = rnd(a * torch.tensor(1.0 / (1.0 - p), dtype=f32, device=a.device) * keep.to(f32))
+        y = (a @ rnd(w2).t() + b2.to(f32)).to(bf)
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+
+class _FusedFFNAmpFn(Function):
+    """``linear2(dropout(relu(linear1(x))))`` under ``torch.autocast(dtype=torch.bfloat16)`` as one node on the library's bf16
+    MFMA kernels (csrc/msda_ffn_bf16.hip; opt-in: ``MSDA_FFN_BF16=1``).  Rounding points as ``fused_ffn_bf16_reference``:
+    ``h`` exists in registers only, ``a`` is written once as bf16 and saved together with the bf16 ``x`` (written by the same
+    launch when ``x`` is fp32) — no ``h``, no mask, no seed.  The dropout mask is the kernel's counter hash (``ffn_keep_mask``)
+    of a seed drawn with one ``random_()`` on a device scalar: reproducible under ``manual_seed``, capturable in a HIP graph,
+    not ``nn.Dropout``'s Philox stream.  The weights are rounded to bf16 in the kernels' staging loads: no bf16 copies.
+    Library launches: forward 1; backward at most 5 (gh, gx, the two weight gradients' first stages, their one second stage),
+    fewer when a gradient is not needed.  No host sync."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, p, training):
+        x2 = x.reshape(-1, x.shape[-1])
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        if x2.data_ptr() % 16:                                            # a view at an odd offset: the kernels move 16 bytes
+            x2 = x2.clone()
+        drop = bool(training) and 0.0 < p < 1.0
+        seed = torch.empty((), dtype=torch.int64, device=x.device).random_().view(1) if drop else None
+        xb, a, y = MSDA.ffn_forward_bf16(x2, w1, b1, w2, b2, p if drop else 0.0, seed)
+        ctx.save_for_backward(xb, a, w1, w2)
+        ctx.p = p if drop else 0.0
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.seed = seed                                                   # for tests; the backward does not read it
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        xb, a, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        go2 = grad_out.reshape(-1, grad_out.shape[-1]).to(torch.bfloat16).contiguous()
+        if go2.data_ptr() % 16:
+            go2 = go2.clone()
+        gx, gw1, gb1, gw2, gb2 = MSDA.ffn_backward_bf16(go2, xb, a, w1, w2, ctx.p, ctx.x_dtype, need[0], need[1], need[2],
+                                                        need[3], need[4])
+        return (gx.view(ctx.x_shape) if gx is not None else None), gw1, gb1, gw2, gb2, None, None
+
+
+def _ffn_bf16_knob():
+    return os.environ.get("MSDA_FFN_BF16", "") not in ("", "0")      # opt-in, read at call time
+
+
+def _ffn_amp_applies(x, linear1, activation, dropout, linear2):
+    return (_ffn_bf16_knob() and torch.is_autocast_enabled() and _autocast_dtype() == torch.bfloat16
+            and activation is F.relu and type(linear1) is nn.Linear and type(linear2) is nn.Linear
+            and type(dropout) is nn.Dropout and not dropout.inplace and dropout.p < 1.0
+            and linear1.bias is not None and linear2.bias is not None
+            and all(t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0
+                    for t in (linear1.weight, linear1.bias, linear2.weight, linear2.bias))
+            and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0
+            and linear1.in_features == linear2.out_features and linear1.out_features == linear2.in_features
+            and MSDA.ffn_bf16_supported(linear1.in_features, linear1.out_features)
+            and (x.numel() // x.shape[-1]) * linear1.out_features < 2 ** 31)
+
+
 _FUSED_FFN = os.environ.get("MSDA_FUSED_FFN", "1") != "0"            # A/B knob: 0 = the composition of bracket_linear / F.relu / nn.Dropout
 
 
 def fused_ffn(x, linear1, activation, dropout, linear2):
     """``linear2(dropout(activation(linear1(x))))`` for two ``nn.Linear`` layers and an ``nn.Dropout``: one autograd node
-    (_FusedFFNFn) when the activation is ReLU and the layers are plain float32 CUDA layers with biases outside autocast,
-    else the composition of the same modules (bracket_linear keeps the weight-gradient kernel there)."""
+    (_FusedFFNFn) when the activation is ReLU and the layers are plain float32 CUDA layers with biases outside autocast;
+    under bf16 autocast with ``MSDA_FFN_BF16=1`` the bf16 node (_FusedFFNAmpFn) where its kernels take the widths; else the
+    composition of the same modules (bracket_linear keeps the weight-gradient kernel there)."""
+    if _ffn_amp_applies(x, linear1, activation, dropout, linear2):
+        return _FusedFFNAmpFn.apply(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias, float(dropout.p),
+                                    dropout.training)
     if (_FUSED_FFN and _ENABLED and activation is F.relu and type(linear1) is nn.Linear and type(linear2) is nn.Linear
             and type(dropout) is nn.Dropout and not dropout.inplace and dropout.p < 1.0
             and linear1.bias is not None and linear2.bias is not None and x.is_cuda and x.dtype == torch.float32

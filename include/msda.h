@@ -387,7 +387,8 @@ int msda_relu_dropout_backward_f32(float *grad, const float *act, float scale, l
  * floats, multiples of 4; 16-byte aligned bases) — the column blocks of a packed in-projection output [L, N, 3E] are such views.
  * Dropout: keep(seed, pair, query, key) is an integer hash compared with p * 2^32 — the kernel's own random stream.  `seed` is a
  * DEVICE pointer to one 64-bit value (drawn by the caller with its generator; the same value must reach the backward); NULL is
- * allowed when dropout_p == 0.  No attention mask / key-padding mask (the reference's decoder passes none). */
+ * allowed when dropout_p == 0.  No attention mask / key-padding mask (the reference's ARCTIC decoder passes none; the masked,
+ * long-sequence form is msda_attn32x_* below). */
 int msda_attn32_supported(int Lq, int Lk, int head_dim);
 int msda_attn32_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
                             const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
@@ -416,6 +417,32 @@ int msda_attn32_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl,
                               int Lk, float scale, float dropout_p, const unsigned long long *seed, uint16_t *grad_q,
                               long long gq_sn, long long gq_sl, uint16_t *grad_k, long long gk_sn, long long gk_sl,
                               uint16_t *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream);
+/* The masked, long-sequence form of the fp32 core (the DINO decoder: models/dino/deformable_transformer.py:966 runs the
+ * module over pad_size + num_queries rows, about 200 + 900, under the contrastive-denoising mask of
+ * models/dino/dn_components.py:125-137):
+ *     out = dropout(softmax(q k^T * scale + M), p) v,   head_dim 32, fp32, any 1 <= Lq, Lk <= 2048 (msda_attn32x_supported).
+ * Views, lse [N*H, Lq] (natural log), seed and the dropout hash are those of msda_attn32_*_f32: for one seed the two cores drop
+ * the same (pair, query, key) entries.  Neither operand is resident in LDS as a whole: the forward and dQ own 128 queries per
+ * workgroup and stream the keys in chunks of 64 (online softmax in the forward), dK / dV owns 128 keys and streams the queries;
+ * ceil(L / 128) workgroups per (batch, head) pair, 18 KB of LDS each.  The backward is two launches (dK / dV, dQ) and forms
+ * delta = rowsum(dO * O) itself.  No float atomics, fixed summation order: bitwise reproducible.  No host sync, no allocation.
+ * mask: DEVICE bytes [Lq, Lk], row stride mask_sq >= Lk, elements contiguous, shared by every batch entry and head (torch's 2-D
+ * boolean attn_mask); nonzero = the key is not visible (M = -inf), zero = visible (M = 0); NULL = no mask.  A hidden entry's
+ * probability and dS are exactly 0 in the backward.  A query whose every key is hidden: its out row is NaN (as the module's),
+ * its lse -inf, no other row is affected; its gradients are outside the contract (the same mask must reach the backward).
+ * Argument errors (lengths, head_dim, misaligned views, p >= 1, p > 0 without a seed, mask_sq < Lk) return MSDA_ERR_ARGUMENT
+ * before any launch.  There is no bf16 form: under autocast the caller keeps the module. */
+int msda_attn32x_supported(int Lq, int Lk, int head_dim);
+int msda_attn32x_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
+                             const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                             float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
+                             float *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream);
+int msda_attn32x_backward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
+                              const float *v, long long v_sn, long long v_sl, const float *out, long long o_sn, long long o_sl,
+                              const float *lse, const float *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                              int Lk, float scale, float dropout_p, const unsigned long long *seed, const unsigned char *mask,
+                              long long mask_sq, float *grad_q, long long gq_sn, long long gq_sl, float *grad_k, long long gk_sn,
+                              long long gk_sl, float *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream);
 
 /* ---- Transformer input assembly -----------------------------------------------------
  * The flatten block of DeformableTransformer.forward (models/arctic_transformer.py:162-173): per level

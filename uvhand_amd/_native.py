@@ -80,6 +80,9 @@ SIGNATURES = {
     "msda_attn32_backward_f32": "i pll pll pll pll p pll iiii ff p pll pll pll p",
     "msda_attn32_forward_bf16": "i pll pll pll iiii ff p pll pp",
     "msda_attn32_backward_bf16": "i pll pll pll pll p pll iiii ff p pll pll pll p",
+    "msda_attn32x_supported": "i iii",
+    "msda_attn32x_forward_f32": "i pll pll pll iiii ff p pl pll pp",
+    "msda_attn32x_backward_f32": "i pll pll pll pll p pll iiii ff p pl pll pll pll p",
     # transformer input assembly
     "msda_flatten_levels_f32": "i i ppppp ii ppp",
     "msda_unflatten_levels_f32": "i i pppp ii ppppp",
@@ -819,6 +822,63 @@ def attn32_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, se
     _launch(q.device, "msda_attn32_backward_bf16" if dt == torch.bfloat16 else "msda_attn32_backward_f32", "attn32_backward",
             *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale),
             float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *gviews[0], *gviews[1], *gviews[2])
+    return grad_q, grad_k, grad_v
+
+
+def attn32x_supported(Lq, Lk, head_dim):
+    lib = _lib or load()
+    return bool(lib.msda_attn32x_supported(int(Lq), int(Lk), int(head_dim)))
+
+
+def _attn_mask_bytes(mask, Lq, Lk, who):
+    """A 2-D bool (or uint8) CUDA mask [Lq, Lk], True = hidden -> (its bytes, row stride); no copy when its last dimension is
+    contiguous.  The returned tensor keeps the bytes alive for the call."""
+    if mask is None:
+        return None, None, 0
+    if not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8) and tuple(mask.shape) == (Lq, Lk)):
+        raise RuntimeError("%s: mask must be a bool CUDA tensor [Lq, Lk] = [%d, %d]" % (who, Lq, Lk))
+    if mask.stride(1) != 1 or (Lq > 1 and mask.stride(0) < Lk):
+        mask = mask.contiguous()
+    mbytes = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    return mbytes, mbytes.data_ptr(), (mbytes.stride(0) if Lq > 1 else max(Lk, mbytes.stride(0)))
+
+
+def attn32x_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None, mask=None):
+    """msda_attn32x_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale + M)) v per (batch, head), head_dim 32, float32,
+    1 <= Lq, Lk <= 2048.  Arguments as attn32_forward; mask: a 2-D bool CUDA tensor [Lq, Lk] shared by every batch entry and
+    head, True = the key is hidden (passed as its bytes), or None.  Returns (out [Lq, N, E], lse [N*heads, Lq])."""
+    Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
+    qv, kv, vv = _attn_view(q, "q", heads), _attn_view(k, "k", heads), _attn_view(v, "v", heads)
+    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise RuntimeError("attn32x_forward: dropout needs a one-element int64 CUDA seed tensor")
+    mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_forward")
+    out = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device)
+    lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
+    ov = _attn_view(out, "out", heads)
+    _launch(q.device, "msda_attn32x_forward_f32", "attn32x_forward", *qv, *kv, *vv, N, heads, Lq, Lk, float(scale),
+            float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, mptr, msq, *ov, lse.data_ptr())
+    return out, lse
+
+
+def attn32x_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, mask=None, grad_q=None, grad_k=None,
+                     grad_v=None):
+    """msda_attn32x_backward_f32: gradients of q, k, v under the forward's mask and seed (written into grad_q / grad_k / grad_v
+    when given — views like the inputs — else into new contiguous tensors)."""
+    Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
+    grad_q = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device) if grad_q is None else grad_q
+    grad_k = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_k is None else grad_k
+    grad_v = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_v is None else grad_v
+    if grad_out.stride(2) != 1:
+        grad_out = grad_out.contiguous()
+    views = [_attn_view(t, nm, heads) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
+    gov = _attn_view(grad_out, "grad_out", heads)
+    gviews = [_attn_view(t, nm, heads) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
+    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise RuntimeError("attn32x_backward: dropout needs a one-element int64 CUDA seed tensor")
+    mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_backward")
+    _launch(q.device, "msda_attn32x_backward_f32", "attn32x_backward", *views[0], *views[1], *views[2], *views[3],
+            lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None,
+            mptr, msq, *gviews[0], *gviews[1], *gviews[2])
     return grad_q, grad_k, grad_v
 
 

@@ -1,0 +1,419 @@
+// Masked, long-sequence form of the decoder self-attention core (msda_attn32x_*_f32, include/msda.h):
+//     out = dropout(softmax(q k^T * scale + M), p) v,   head_dim 32, fp32, 1 <= Lq, Lk <= 2048, M = -inf where mask != 0.
+// The DINO decoder (models/dino/deformable_transformer.py:966) runs nn.MultiheadAttention over pad_size + num_queries rows
+// (about 200 + 900) under the contrastive-denoising mask of models/dino/dn_components.py:125-137.  One (batch, head) pair's K
+// and V in msda_attn.hip's resident [rows][36 floats] layout would take 317 KB of LDS at 1100 rows; a CU has 160 KB.  So these
+// kernels STREAM the other operand through LDS in chunks of kAxChunk = 64 rows, and several workgroups share a pair:
+//   * forward and dQ: a workgroup of 8 wavefronts owns kAxRows = 128 queries (16 per wavefront) and walks the key chunks.
+//     The forward keeps an online softmax per query (running maximum m, running sum, O rescaled by 2^(m_old - m_new) at each
+//     chunk) and normalises once at the end; dQ recomputes the probabilities from the forward's log-sum-exp.
+//   * dK / dV: a workgroup owns 128 keys and walks the query chunks; delta = rowsum(dO * O) and the log-sum-exp of a chunk's
+//     queries are formed while the chunk is loaded.
+// LDS: two [64][36] fp32 slices = 18 KB (dK / dV: + 768 B) — under the 64 KB that need no opt-in, eight workgroups to a CU.
+// Every product runs on v_mfma_f32_16x16x4_f32 through the fragment helpers of msda_attn_tile.h, in msda_attn.hip's layouts:
+// S^T tiles (rows = keys) in the forward and dQ, S tiles (rows = queries) in dK / dV.  No atomics; every sum has one fixed order
+// (chunks in order, tiles in order), so all three kernels are bitwise reproducible.
+// Mask: bytes [Lq][Lk], row stride mask_sq, shared by every pair; nonzero = hidden.  A hidden entry's score is -inf in the
+// forward and its probability and dS are exactly 0 in the backward (selected, not computed), so a hidden key receives exactly
+// nothing from the rows that cannot see it.  A query with every key hidden has sum = 0: its out row is 0 * inf = NaN, as the
+// module's, its lse -inf; no other row sees it (the product sums over keys within a query's column).  Its gradients are outside
+// the contract.
+// Long sums (ax_tile_sums): a 16-row tile's product starts from a zero accumulator and the tile's partial is added to the running
+// result on the vector unit, so a sum over 2048 rows is 128 rounded additions of partials, not a chain of 512 dependent MFMA
+// accumulations — dV of a query block that attends to one key is a plain sum of its dO rows, and the chain measured 5 ulp there.
+// Hidden tiles: dQ skips a 16 x 16 tile that the mask hides from all 16 queries of its wavefront (one ballot per tile, only when
+// a mask is given; rows past Lq count as hidden).  The tile's dS are exact zeros and its partial product +0, so no result bit
+// changes (checked against a build without the skip).  At 1098 rows under the denoising mask dQ went from 824 to 690 us.  The
+// same skip in the forward and in dK / dV was measured and left out: 601 -> 590 and 1149 -> 1131 us masked, but 349 -> 389
+// and 650 -> 678 us at 900 rows unmasked (the forward then holds the tiles' mask bits across its products: 90 VGPRs against 80).
+// Dropout: msda_attn.hip's hash and counter — at_hash((query << 16) + key + at_mix(seed, pair)) — seed read from device memory.
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "msda_attn_tile.h"
+#include "msda_common.h"
+#include "msda_launch.h"
+
+namespace msda {
+
+constexpr int kAxWaves = 8, kAxBlock = kAxWaves * 64, kAxRows = kAxWaves * 16, kAxChunk = 64, kAxTiles = kAxChunk / 16;
+constexpr int kAxMaxLen = 2048;
+static_assert(kAxChunk * 8 == kAxBlock, "one float4 per thread and slice in ax_load_chunk2");
+
+struct AxView { float *p; long long sn, sl; };          // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
+
+struct AxArgs {
+    AxView q, k, v, o, go, gq, gk, gv;
+    float *lse;                         // [N*H][Lq]
+    const unsigned long long *seed;     // device; null when thresh == 0
+    const unsigned char *mask;          // [Lq][Lk] bytes, row stride mask_sq; null: none
+    long long mask_sq;
+    int H, Lq, Lk, nblk;                // nblk: workgroups per pair
+    float scale, scale2, keep_scale;    // as AtArgs (msda_attn.hip)
+    unsigned thresh;
+};
+
+// rows [row0, row0 + kAxChunk) of two [L][32] slices -> dst0 / dst1 [kAxChunk][kAtRow]; rows past L zero
+__device__ __forceinline__ void ax_load_chunk2(float *dst0, const float *src0, long long sl0, float *dst1, const float *src1,
+                                               long long sl1, int row0, int L)
+{
+    const int row = threadIdx.x >> 3, c = (threadIdx.x & 7) * 4, g = row0 + row;
+    const bool live = g < L;
+    const float4 v0 = live ? ld4(src0 + (long long)g * sl0 + c) : at_zero4();
+    const float4 v1 = live ? ld4(src1 + (long long)g * sl1 + c) : at_zero4();
+    *reinterpret_cast<float4 *>(dst0 + row * kAtRow + c) = v0;
+    *reinterpret_cast<float4 *>(dst1 + row * kAtRow + c) = v1;
+}
+
+// bit v set: key0 + v is hidden from this lane's query (mrow = its mask row, or null) or lies past Lk
+__device__ __forceinline__ unsigned ax_hidden4(const unsigned char *mrow, int key0, int Lk)
+{
+    unsigned bits = 0;
+    if (key0 + 3 < Lk) {
+        if (mrow) {
+            unsigned w;
+            memcpy(&w, mrow + key0, 4);                 // (no alignment promised: mask_sq is any length)
+            bits = ((w & 0xffu) ? 1u : 0u) | ((w & 0xff00u) ? 2u : 0u) | ((w & 0xff0000u) ? 4u : 0u) | ((w & 0xff000000u) ? 8u : 0u);
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (key0 + v >= Lk || (mrow && mrow[key0 + v])) bits |= 1u << v;
+    }
+    return bits;
+}
+
+// The log-sum-exp crosses the ABI as an fp32 natural logarithm and the kernels work in base 2.  A plain product on each side
+// would add a rounding of ulp(lse) / 2 twice to EVERY exponent of a row — a common factor of about 2e-7 on the row's
+// probabilities and gradients; both conversions therefore carry the product's low part.
+// forward: (m + l) * ln 2 rounded once (m + l by a two-sum, the constant as hi + lo)
+__device__ __forceinline__ float ax_lse_natural(float m, float l)
+{
+    const float t = m + l;
+    if (!(fabsf(t) < INFINITY)) return t;               // (-inf: every key hidden)
+    const float bb = t - m, e = (m - (t - bb)) + (l - bb);
+    return fmaf(t, 0.693147182464599609375f, fmaf(t, -1.904654299957e-9f, e * 0.693147182464599609375f));
+}
+// backward: lse * log2 e as hi + lo; a score's exponent is (s - hi) - lo.  +inf (rows past Lq) stays (+inf, 0).
+__device__ __forceinline__ void ax_lse_base2(float lse, float &hi, float &lo)
+{
+    hi = lse * 1.44269502162933349609375f;
+    lo = fabsf(hi) < INFINITY ? fmaf(lse, 1.44269502162933349609375f, -hi) + lse * 1.925963033500e-8f : 0.f;
+}
+
+// at_dot32 as four chains of two MFMA steps (eight channels each, every chain from a zero accumulator) summed pairwise on the
+// vector unit.  dP = dO . v reaches |13| at unit-variance inputs, and every step of at_dot32's one chain of eight rounds at that
+// magnitude: measured against fp64, the single chain left dq / dk of a one-query problem at up to 4.9 times torch's fp32 error,
+// the split at up to 3.1.  The four chains are independent: the matrix pipe overlaps them.
+__device__ __forceinline__ at_f4 ax_dot32(const float *arow, const float4 &b0, const float4 &b1)
+{
+    const float4 a0 = ld4(arow), a1 = ld4(arow + 16);
+    const at_f4 z = {0.f, 0.f, 0.f, 0.f};
+    at_f4 w = at_mfma(a0.x, b0.x, z), x = at_mfma(a0.z, b0.z, z), y = at_mfma(a1.x, b1.x, z), u = at_mfma(a1.z, b1.z, z);
+    w = at_mfma(a0.y, b0.y, w); x = at_mfma(a0.w, b0.w, x); y = at_mfma(a1.y, b1.y, y); u = at_mfma(a1.w, b1.w, u);
+    return (w + x) + (y + u);
+}
+
+__device__ __forceinline__ void ax_scale4(float4 &x, float s) { x.x *= s; x.y *= s; x.z *= s; x.w *= s; }
+
+__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_kernel(const AxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float Ks[kAxChunk * kAtRow], Vs[kAxChunk * kAtRow];
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = blk * kAxRows + wave * 16 + c;
+    const bool qok = qi < a.Lq;
+    float4 q0 = at_zero4(), q1 = at_zero4();
+    if (qok) {
+        const float *qr = a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 4 * r;
+        q0 = ld4(qr); q1 = ld4(qr + 16);
+    }
+    ax_scale4(q0, a.scale2); ax_scale4(q1, a.scale2);
+    const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
+    const float *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
+    const unsigned ctr = ((unsigned)qi << 16) + 4 * r + mix;
+    float m = -INFINITY, sum = 0.f;                     // running maximum (base 2) of the query; this lane's share of the sum
+    at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+    for (int k0 = 0; k0 < a.Lk; k0 += kAxChunk) {
+        __syncthreads();                                // (the last chunk's readers are done)
+        ax_load_chunk2(Ks, kp, a.k.sl, Vs, vp, a.v.sl, k0, a.Lk);
+        __syncthreads();
+        const int nt = min(kAxTiles, (a.Lk - k0 + 15) >> 4);
+        // S^T tiles: s[t][v] = score (times log2 e) of key k0 + 16 t + 4 r + v for query qi
+        at_f4 s[kAxTiles];
+#pragma unroll
+        for (int t = 0; t < kAxTiles; ++t)
+            if (t < nt) s[t] = ax_dot32(Ks + (16 * t + c) * kAtRow + 4 * r, q0, q1);
+        float cm = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < kAxTiles; ++t) {
+            if (t < nt) {
+                const unsigned hid = ax_hidden4(mrow, k0 + 16 * t + 4 * r, a.Lk);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    s[t][v] = (hid >> v & 1u) ? -INFINITY : s[t][v];
+                    cm = fmaxf(cm, s[t][v]);
+                }
+            }
+        }
+        const float m_new = fmaxf(m, at_rmax(cm));
+        const float m_ref = m_new == -INFINITY ? 0.f : m_new;       // (nothing visible yet: every term below is exp2(-inf) = 0)
+        const float alpha = __builtin_amdgcn_exp2f(m - m_ref);
+        sum *= alpha;
+        o0 *= alpha; o1 *= alpha;
+        m = m_new;
+#pragma unroll
+        for (int t = 0; t < kAxTiles; ++t) {
+            if (t < nt) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const float p = __builtin_amdgcn_exp2f(s[t][v] - m_ref);
+                    sum += p;
+                    const bool keep = at_hash(ctr + (unsigned)(k0 + 16 * t + v)) >= a.thresh;      // (thresh 0: always)
+                    s[t][v] = keep ? p : 0.f;
+                }
+                at_f4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = t0;
+                at_accum_t(Vs + 16 * t * kAtRow, r, c, s[t], t0, t1);       // O^T[channel][query] += V^T . P (ax_tile_sums)
+                o0 += t0; o1 += t1;
+            }
+        }
+    }
+    sum = at_rsum(sum);
+    if (qok) {
+        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = ax_lse_natural(m, __builtin_amdgcn_logf(sum));
+        const float inv = a.keep_scale / sum;           // (sum 0 — every key hidden: inf, and the row 0 * inf = NaN)
+        float *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
+        *reinterpret_cast<float4 *>(orow) = make_float4(o0[0] * inv, o0[1] * inv, o0[2] * inv, o0[3] * inv);
+        *reinterpret_cast<float4 *>(orow + 16) = make_float4(o1[0] * inv, o1[1] * inv, o1[2] * inv, o1[3] * inv);
+    }
+}
+
+// dK, dV: a wavefront owns 16 keys; the workgroup walks the query chunks
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_kernel(const AxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float Qs[kAxChunk * kAtRow], Gs[kAxChunk * kAtRow], lse_s[kAxChunk], lsl_s[kAxChunk],
+        del_s[kAxChunk];
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int key = blk * kAxRows + wave * 16 + c;
+    const bool kok = key < a.Lk;
+    float4 k0 = at_zero4(), k1 = at_zero4(), v0 = at_zero4(), v1 = at_zero4();
+    if (kok) {
+        const float *kr = a.k.p + n * a.k.sn + h * 32 + (long long)key * a.k.sl + 4 * r;
+        const float *vr = a.v.p + n * a.v.sn + h * 32 + (long long)key * a.v.sl + 4 * r;
+        k0 = ld4(kr); k1 = ld4(kr + 16); v0 = ld4(vr); v1 = ld4(vr + 16);
+    }
+    ax_scale4(k0, a.scale2); ax_scale4(k1, a.scale2);
+    const unsigned char *mcol = (a.mask && kok) ? a.mask + key : nullptr;
+    const float *qp = a.q.p + n * a.q.sn + h * 32, *gp = a.go.p + n * a.go.sn + h * 32, *op = a.o.p + n * a.o.sn + h * 32;
+    const unsigned ctr = (unsigned)key + ((unsigned)(4 * r) << 16) + mix;
+    at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+    for (int c0 = 0; c0 < a.Lq; c0 += kAxChunk) {
+        __syncthreads();
+        ax_load_chunk2(Qs, qp, a.q.sl, Gs, gp, a.go.sl, c0, a.Lq);
+        // per query of the chunk: delta = <dO, O> — four threads a query, the dQ kernel's terms in the dQ kernel's order — and
+        // the log-sum-exp in base 2 (+inf for the rows past Lq: their probabilities vanish)
+        if (threadIdx.x < 4 * kAxChunk) {               // (whole wavefronts)
+            const int ql = threadIdx.x >> 2, part = threadIdx.x & 3, g = c0 + ql;
+            float d = 0.f;
+            if (g < a.Lq) {
+                const float *gr = gp + (long long)g * a.go.sl + 4 * part, *orw = op + (long long)g * a.o.sl + 4 * part;
+                const float4 g0 = ld4(gr), g1 = ld4(gr + 16), o0 = ld4(orw), o1 = ld4(orw + 16);
+                d = g0.x * o0.x + g0.y * o0.y + g0.z * o0.z + g0.w * o0.w + g1.x * o1.x + g1.y * o1.y + g1.z * o1.z + g1.w * o1.w;
+            }
+            d += __shfl_xor(d, 1);
+            d += __shfl_xor(d, 2);
+            if (part == 0) {
+                float hi, lo;
+                ax_lse_base2(g < a.Lq ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
+                del_s[ql] = d; lse_s[ql] = hi; lsl_s[ql] = lo;
+            }
+        }
+        __syncthreads();
+        const int nt = min(kAxTiles, (a.Lq - c0 + 15) >> 4);
+        // S and dP tiles: entry v = (query c0 + 16 t + 4 r + v, key)
+#pragma unroll 1
+        for (int t = 0; t < nt; ++t) {
+            const at_f4 s = ax_dot32(Qs + (16 * t + c) * kAtRow + 4 * r, k0, k1);
+            const at_f4 dp = ax_dot32(Gs + (16 * t + c) * kAtRow + 4 * r, v0, v1);
+            const float4 ls = ld4(lse_s + 16 * t + 4 * r), ll = ld4(lsl_s + 16 * t + 4 * r), dl = ld4(del_s + 16 * t + 4 * r);
+            const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, llv[4] = {ll.x, ll.y, ll.z, ll.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
+            const int qrow = c0 + 16 * t + 4 * r;
+            at_f4 pd, ds;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const bool hid = mcol != nullptr && qrow + v < a.Lq && mcol[(long long)(qrow + v) * a.mask_sq] != 0;
+                const float p = hid ? 0.f : __builtin_amdgcn_exp2f((s[v] - lsv[v]) - llv[v]);
+                const bool keep = at_hash(ctr + ((unsigned)(c0 + 16 * t + v) << 16)) >= a.thresh;
+                pd[v] = keep ? p * a.keep_scale : 0.f;
+                ds[v] = hid ? 0.f : p * ((keep ? dp[v] * a.keep_scale : 0.f) - dlv[v]);
+            }
+            at_f4 tv0 = {0.f, 0.f, 0.f, 0.f}, tv1 = tv0, tk0 = tv0, tk1 = tv0;
+            at_accum_t(Gs + 16 * t * kAtRow, r, c, pd, tv0, tv1);           // dV^T[channel][key] += dO^T . P_drop
+            at_accum_t(Qs + 16 * t * kAtRow, r, c, ds, tk0, tk1);           // dK^T[channel][key] += Q^T . dS
+            dv0 += tv0; dv1 += tv1; dk0 += tk0; dk1 += tk1;
+        }
+    }
+    if (kok) {
+        float *gvr = a.gv.p + n * a.gv.sn + h * 32 + (long long)key * a.gv.sl + 4 * r;
+        float *gkr = a.gk.p + n * a.gk.sn + h * 32 + (long long)key * a.gk.sl + 4 * r;
+        *reinterpret_cast<float4 *>(gvr) = make_float4(dv0[0], dv0[1], dv0[2], dv0[3]);
+        *reinterpret_cast<float4 *>(gvr + 16) = make_float4(dv1[0], dv1[1], dv1[2], dv1[3]);
+        *reinterpret_cast<float4 *>(gkr) = make_float4(dk0[0] * a.scale, dk0[1] * a.scale, dk0[2] * a.scale, dk0[3] * a.scale);
+        *reinterpret_cast<float4 *>(gkr + 16) = make_float4(dk1[0] * a.scale, dk1[1] * a.scale, dk1[2] * a.scale, dk1[3] * a.scale);
+    }
+}
+
+// dQ: a wavefront owns 16 queries; the workgroup walks the key chunks (S^T tiles, as the forward)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_kernel(const AxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float Ks[kAxChunk * kAtRow], Vs[kAxChunk * kAtRow];
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = blk * kAxRows + wave * 16 + c;
+    const bool qok = qi < a.Lq;
+    float4 q0 = at_zero4(), q1 = at_zero4(), g0 = at_zero4(), g1 = at_zero4(), o0 = at_zero4(), o1 = at_zero4();
+    float lse_n = INFINITY;                             // (rows past Lq: probabilities vanish)
+    if (qok) {
+        const float *qr = a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 4 * r;
+        const float *gr = a.go.p + n * a.go.sn + h * 32 + (long long)qi * a.go.sl + 4 * r;
+        const float *orw = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
+        q0 = ld4(qr); q1 = ld4(qr + 16); g0 = ld4(gr); g1 = ld4(gr + 16); o0 = ld4(orw); o1 = ld4(orw + 16);
+        lse_n = a.lse[(long long)pair * a.Lq + qi];
+    }
+    float lse, lse_lo;
+    ax_lse_base2(lse_n, lse, lse_lo);
+    ax_scale4(q0, a.scale2); ax_scale4(q1, a.scale2);
+    const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
+    const float *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
+    const unsigned ctr = ((unsigned)qi << 16) + 4 * r + mix;
+    const float delta = at_rsum(g0.x * o0.x + g0.y * o0.y + g0.z * o0.z + g0.w * o0.w + g1.x * o1.x + g1.y * o1.y + g1.z * o1.z +
+                                g1.w * o1.w);
+    at_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+    for (int k0 = 0; k0 < a.Lk; k0 += kAxChunk) {
+        __syncthreads();
+        ax_load_chunk2(Ks, kp, a.k.sl, Vs, vp, a.v.sl, k0, a.Lk);
+        __syncthreads();
+        const int nt = min(kAxTiles, (a.Lk - k0 + 15) >> 4);
+        // S^T and dP^T tiles: entry v = (key k0 + 16 t + 4 r + v, query qi)
+#pragma unroll 1
+        for (int t = 0; t < nt; ++t) {
+            const unsigned hid = ax_hidden4(mrow, k0 + 16 * t + 4 * r, a.Lk);
+            if (a.mask != nullptr && __all(!qok || hid == 0xfu)) continue;      // hidden from the whole wavefront: exact zeros, skipped
+            const at_f4 s = ax_dot32(Ks + (16 * t + c) * kAtRow + 4 * r, q0, q1);
+            const at_f4 dp = ax_dot32(Vs + (16 * t + c) * kAtRow + 4 * r, g0, g1);
+            at_f4 ds;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const float p = __builtin_amdgcn_exp2f((s[v] - lse) - lse_lo);
+                const bool keep = at_hash(ctr + (unsigned)(k0 + 16 * t + v)) >= a.thresh;
+                ds[v] = (hid >> v & 1u) ? 0.f : p * ((keep ? dp[v] * a.keep_scale : 0.f) - delta);
+            }
+            at_f4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = t0;
+            at_accum_t(Ks + 16 * t * kAtRow, r, c, ds, t0, t1);             // dQ^T[channel][query] += K^T . dS^T
+            dq0 += t0; dq1 += t1;
+        }
+    }
+    if (qok) {
+        float *gq = a.gq.p + n * a.gq.sn + h * 32 + (long long)qi * a.gq.sl + 4 * r;
+        *reinterpret_cast<float4 *>(gq) = make_float4(dq0[0] * a.scale, dq0[1] * a.scale, dq0[2] * a.scale, dq0[3] * a.scale);
+        *reinterpret_cast<float4 *>(gq + 16) = make_float4(dq1[0] * a.scale, dq1[1] * a.scale, dq1[2] * a.scale, dq1[3] * a.scale);
+    }
+}
+
+static bool ax_view_ok(const AxView &v)
+{
+    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 3) == 0 && (v.sl & 3) == 0;
+}
+
+// LDS above 64 KB would be requested as msda_attn.hip's at_allow_lds does; the three kernels' static 18 KB need no opt-in.
+static_assert((2 * kAxChunk * kAtRow + 3 * kAxChunk) * sizeof(float) <= 64 * 1024, "static LDS");
+
+}  // namespace msda
+
+using msda::AxArgs;
+using msda::AxView;
+
+extern "C" {
+
+int msda_attn32x_supported(int Lq, int Lk, int head_dim)
+{
+    return head_dim == 32 && Lq >= 1 && Lk >= 1 && Lq <= msda::kAxMaxLen && Lk <= msda::kAxMaxLen;
+}
+
+// every check of the geometry, the dropout and the mask; launches nothing
+static int ax_fill(AxArgs &a, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p, const unsigned long long *seed,
+                   const unsigned char *mask, long long mask_sq)
+{
+    char buf[200];
+    if (N <= 0 || H <= 0 || !msda_attn32x_supported(Lq, Lk, 32)) {
+        snprintf(buf, sizeof(buf), "%s: head_dim 32, 1 <= Lq, Lk <= 2048", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (!(dropout_p >= 0.f && dropout_p < 1.f) || (dropout_p > 0.f && seed == nullptr)) {
+        snprintf(buf, sizeof(buf), "%s: 0 <= p < 1 (seed required for p > 0)", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (mask != nullptr && mask_sq < Lk) {
+        snprintf(buf, sizeof(buf), "%s: mask row stride mask_sq must be at least Lk", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
+    a.scale2 = scale * 1.4426950408889634f;
+    a.keep_scale = 1.f / (1.f - dropout_p);
+    a.thresh = dropout_p > 0.f ? (unsigned)fmin(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
+    a.seed = seed;
+    a.mask = mask; a.mask_sq = mask_sq;
+    return MSDA_OK;
+}
+
+int msda_attn32x_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
+                             const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                             float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
+                             float *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream)
+{
+    AxArgs a{};
+    if (int rc = ax_fill(a, "msda_attn32x_forward_f32", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
+    a.q = AxView{const_cast<float *>(q), q_sn, q_sl}; a.k = AxView{const_cast<float *>(k), k_sn, k_sl};
+    a.v = AxView{const_cast<float *>(v), v_sn, v_sl}; a.o = AxView{out, o_sn, o_sl}; a.lse = lse;
+    if (!msda::ax_view_ok(a.q) || !msda::ax_view_ok(a.k) || !msda::ax_view_ok(a.v) || !msda::ax_view_ok(a.o) || lse == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
+    a.nblk = (Lq + msda::kAxRows - 1) / msda::kAxRows;
+    if ((long long)N * H * a.nblk > 0x7fffffffLL) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_f32: too many (batch, head) pairs");
+    hipLaunchKernelGGL(msda::attn32x_fwd_kernel, dim3((unsigned)(N * H * a.nblk)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    return msda::check_launch("msda long attention forward (head_dim 32)");
+}
+
+int msda_attn32x_backward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
+                              const float *v, long long v_sn, long long v_sl, const float *out, long long o_sn, long long o_sl,
+                              const float *lse, const float *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                              int Lk, float scale, float dropout_p, const unsigned long long *seed, const unsigned char *mask,
+                              long long mask_sq, float *grad_q, long long gq_sn, long long gq_sl, float *grad_k, long long gk_sn,
+                              long long gk_sl, float *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream)
+{
+    AxArgs a{};
+    if (int rc = ax_fill(a, "msda_attn32x_backward_f32", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
+    a.q = AxView{const_cast<float *>(q), q_sn, q_sl}; a.k = AxView{const_cast<float *>(k), k_sn, k_sl};
+    a.v = AxView{const_cast<float *>(v), v_sn, v_sl}; a.o = AxView{const_cast<float *>(out), o_sn, o_sl};
+    a.go = AxView{const_cast<float *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
+    a.gq = AxView{grad_q, gq_sn, gq_sl}; a.gk = AxView{grad_k, gk_sn, gk_sl}; a.gv = AxView{grad_v, gv_sn, gv_sl};
+    for (const AxView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
+        if (!msda::ax_view_ok(*w))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
+    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: lse required");
+    const int nblk_q = (Lq + msda::kAxRows - 1) / msda::kAxRows, nblk_k = (Lk + msda::kAxRows - 1) / msda::kAxRows;
+    if ((long long)N * H * (nblk_q > nblk_k ? nblk_q : nblk_k) > 0x7fffffffLL)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: too many (batch, head) pairs");
+    a.nblk = nblk_k;
+    hipLaunchKernelGGL(msda::attn32x_bwd_kv_kernel, dim3((unsigned)(N * H * nblk_k)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    if (int rc = msda::check_launch("msda long attention backward (dK, dV)")) return rc;
+    a.nblk = nblk_q;
+    hipLaunchKernelGGL(msda::attn32x_bwd_q_kernel, dim3((unsigned)(N * H * nblk_q)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    return msda::check_launch("msda long attention backward (dQ)");
+}
+
+}  // extern "C"

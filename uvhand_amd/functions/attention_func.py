@@ -15,8 +15,17 @@ Under ``torch.autocast("cuda", dtype=torch.bfloat16)`` the inputs are still the 
 amp path and return bf16, and the core runs on the bf16 kernels (msda_attn32_*_bf16): bf16 operands, fp32 softmax and
 accumulation, bf16 output and bf16 gradients of the projections' outputs — the dtypes the stock module has under the same
 autocast.  The attention dropout then draws from the same kernel hash (for one seed the bf16 and fp32 cores drop the same
-entries), not from ``nn.functional.dropout``.  fp16 autocast stays with the module."""
+entries), not from ``nn.functional.dropout``.  fp16 autocast stays with the module.
+
+Masked and long inputs (DINO's decoder, models/dino/deformable_transformer.py:966: ``pad_size + num_queries`` rows, about 1100,
+under the contrastive-denoising mask of models/dino/dn_components.py:125-137).  A 2-D ``torch.bool`` CUDA ``attn_mask`` [L, L]
+(True = hidden) routes the core through the streaming kernels (msda_attn32x_*_f32: head_dim 32, fp32, 1 <= L <= 2048) outside
+autocast; ``MSDA_ATTN_LONG=1`` (read at call time) sends unmasked inputs of 320 < L <= 2048 there too — the 900-query
+evaluation.  The projections, their weight gradients and the dropout stream are the ones above.  Float masks, 3-D masks, other
+head sizes, L > 2048, CPU tensors and any autocast (there is no bf16 form of the long core) go to the module with the mask.
+A query row whose every key is hidden is NaN, as the module's; its gradients are outside the kernels' contract."""
 import math
+import os
 
 import torch
 from torch import nn
@@ -55,25 +64,78 @@ class _Attn32Fn(Function):
         return g_qk, g_v, None, None
 
 
-def _takes(mha, x_qk, x_v):
+class _Attn32xFn(Function):
+    """core(qk [L, N, 2E], v [L, N, E], mask [L, L] bool or None) -> [L, N, E]; fp32, streaming kernels (msda_attn32x_*_f32)"""
+
+    @staticmethod
+    def forward(ctx, qk, v, mask, heads, dropout_p):
+        E = v.shape[2]
+        q, k = qk[..., :E], qk[..., E:]
+        scale = 1.0 / math.sqrt(E // heads)
+        seed = torch.empty((), dtype=torch.int64, device=v.device).random_().view(1) if dropout_p > 0 else None
+        out, lse = MSDA.attn32x_forward(q, k, v, heads, scale, dropout_p, seed, mask)
+        ctx.save_for_backward(qk, v, out, lse, *([mask] if mask is not None else []), *([seed] if seed is not None else []))
+        ctx.heads, ctx.scale, ctx.dropout_p, ctx.masked = heads, scale, dropout_p, mask is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        qk, v, out, lse = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        mask = rest.pop(0) if ctx.masked else None
+        seed = rest.pop(0) if rest else None
+        E = v.shape[2]
+        g_qk = torch.empty_like(qk, memory_format=torch.contiguous_format)
+        if grad_out.dtype != qk.dtype:
+            grad_out = grad_out.to(qk.dtype)
+        _, _, g_v = MSDA.attn32x_backward(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, ctx.scale, ctx.dropout_p, seed,
+                                          mask, grad_q=g_qk[..., :E], grad_k=g_qk[..., E:])
+        return g_qk, g_v, None, None, None
+
+
+def _takes_common(mha, x_qk, x_v):
     E = mha.embed_dim
     return (type(mha) is nn.MultiheadAttention and mha._qkv_same_embed_dim and not mha.batch_first and mha.bias_k is None
             and mha.bias_v is None and not mha.add_zero_attn and mha.in_proj_bias is not None and mha.head_dim == 32
             and x_qk.is_cuda and x_qk.dtype == torch.float32 and x_v.dtype == torch.float32 and x_qk.dim() == 3
-            and x_qk.shape == x_v.shape and x_qk.shape[2] == E
+            and x_qk.shape == x_v.shape and x_qk.shape[2] == E)
+
+
+def _takes_long(mha, x_qk, x_v, attn_mask):
+    """The streaming core: _takes' conditions with its length bound (fp32 outside autocast only), for a 2-D bool CUDA mask
+    [L, L] — or, unmasked, for 320 < L when MSDA_ATTN_LONG=1."""
+    if attn_mask is None:
+        if os.environ.get("MSDA_ATTN_LONG", "0") in ("", "0"):
+            return False
+    elif not (torch.is_tensor(attn_mask) and attn_mask.dtype == torch.bool and attn_mask.is_cuda and attn_mask.dim() == 2
+              and attn_mask.shape[0] == attn_mask.shape[1] == x_qk.shape[0] and attn_mask.device == x_qk.device):
+        return False
+    if not _takes_common(mha, x_qk, x_v) or torch.is_autocast_enabled():
+        return False
+    L = x_qk.shape[0]
+    if attn_mask is None and MSDA.attn32_supported(L, L, mha.head_dim):
+        return False                                     # (unmasked and short: the resident core's)
+    return MSDA.attn32x_supported(L, L, mha.head_dim)
+
+
+def _takes(mha, x_qk, x_v):
+    return (_takes_common(mha, x_qk, x_v)
             and (not torch.is_autocast_enabled() or _autocast_dtype() == torch.bfloat16)
             and MSDA.attn32_supported(x_qk.shape[0], x_v.shape[0], mha.head_dim))
 
 
-def self_attention(mha, x_qk, x_v):
-    """``mha(x_qk, x_qk, x_v, need_weights=False)[0]`` for sequence-first inputs [L, N, E]."""
-    if not _takes(mha, x_qk, x_v):
-        return mha(x_qk, x_qk, x_v, need_weights=False)[0]
+def self_attention(mha, x_qk, x_v, attn_mask=None):
+    """``mha(x_qk, x_qk, x_v, attn_mask=attn_mask, need_weights=False)[0]`` for sequence-first inputs [L, N, E]."""
+    long_core = _takes_long(mha, x_qk, x_v, attn_mask)
+    if not long_core and (attn_mask is not None or not _takes(mha, x_qk, x_v)):
+        return mha(x_qk, x_qk, x_v, attn_mask=attn_mask, need_weights=False)[0]
     E = mha.embed_dim
     w, b = mha.in_proj_weight, mha.in_proj_bias
     # (the three projections through bracket_linear_wb: nn.Linear's forward, the weight gradients on the library's split-M MFMA
     # kernel — torch runs the 9600-row ones at a third of its rate, 61 against 26 us each, tools/wgrad_time.py)
     qk = bracket_linear_wb(x_qk, w[:2 * E], b[:2 * E])
     v = bracket_linear_wb(x_v, w[2 * E:], b[2 * E:])
-    core = _Attn32Fn.apply(qk, v, mha.num_heads, float(mha.dropout) if mha.training else 0.0)
+    p = float(mha.dropout) if mha.training else 0.0
+    core = _Attn32xFn.apply(qk, v, attn_mask, mha.num_heads, p) if long_core else _Attn32Fn.apply(qk, v, mha.num_heads, p)
     return bracket_linear_wb(core, mha.out_proj.weight, mha.out_proj.bias)

@@ -107,7 +107,9 @@ class DeformableTransformerDecoderLayer(nn.Module):
         tgt2 = fused_ffn(tgt, self.linear1, self.activation, self.dropout3, self.linear2)
         return add_layer_norm(tgt, self.dropout4(tgt2), self.norm3)
 
-    def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask=None):
+    def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask=None,
+                self_attn_mask=None):
+        """``self_attn_mask``: the self-attention's ``attn_mask`` (DINO's denoising mask, utils.cdn_attention_mask), or None."""
         self.inter_rp(reference_points)
         # the queries attend to each other first (sequence-first, as the reference feeds nn.MultiheadAttention)
         q = k = self.with_pos_embed(tgt, query_pos)
@@ -117,10 +119,11 @@ class DeformableTransformerDecoderLayer(nn.Module):
         # too: the core then runs on the bf16 kernels, with the same mask for the same seed).
         listened = self.always_attention_matrix or _has_listener(self.attn_matrix)
         if listened:
-            tgt2, attn_matrix = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1), need_weights=True)
+            tgt2, attn_matrix = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1), attn_mask=self_attn_mask,
+                                                   need_weights=True)
             self.attn_matrix(attn_matrix)
         else:                                            # the library's attention core where it applies (functions/attention_func.py)
-            tgt2 = self_attention(self.self_attn, q.transpose(0, 1), tgt.transpose(0, 1))
+            tgt2 = self_attention(self.self_attn, q.transpose(0, 1), tgt.transpose(0, 1), self_attn_mask)
         tgt = add_layer_norm(tgt, self.dropout2(tgt2.transpose(0, 1)), self.norm2)
         # then sample the feature pyramid
         tgt2 = self.cross_attn(self.with_pos_embed(tgt, query_pos), reference_points, src, src_spatial_shapes,
@@ -205,7 +208,7 @@ class DeformableTransformerDecoder(nn.Module):
         return (unsig.sigmoid() * 2 - 1).detach()
 
     def forward(self, tgt, reference_points, src, src_spatial_shapes, src_level_start_index, src_valid_ratios,
-                query_pos=None, src_padding_mask=None):
+                query_pos=None, src_padding_mask=None, tgt_mask=None):
         output = tgt
         intermediate, intermediate_reference_points = [], []
         for lid, layer in enumerate(self.layers):
@@ -213,7 +216,7 @@ class DeformableTransformerDecoder(nn.Module):
                 raise AssertionError("reference_points must have 2 or 42 coordinates per query")
             reference_points_input = decoder_reference_points(reference_points, src_valid_ratios)
             output = layer(output, query_pos, reference_points_input, src, src_spatial_shapes, src_level_start_index,
-                           src_padding_mask)
+                           src_padding_mask, tgt_mask)
             if self.cls_embed is not None:
                 reference_points = self._refine(lid, output, reference_points)
             if self.return_intermediate:

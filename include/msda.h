@@ -431,7 +431,7 @@ int msda_attn32_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl,
  * probability and dS are exactly 0 in the backward.  A query whose every key is hidden: its out row is NaN (as the module's),
  * its lse -inf, no other row is affected; its gradients are outside the contract (the same mask must reach the backward).
  * Argument errors (lengths, head_dim, misaligned views, p >= 1, p > 0 without a seed, mask_sq < Lk) return MSDA_ERR_ARGUMENT
- * before any launch.  There is no bf16 form: under autocast the caller keeps the module. */
+ * before any launch.  The bf16 form for autocast is msda_attn32x_*_bf16 below. */
 int msda_attn32x_supported(int Lq, int Lk, int head_dim);
 int msda_attn32x_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
                              const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
@@ -443,6 +443,32 @@ int msda_attn32x_backward_f32(const float *q, long long q_sn, long long q_sl, co
                               int Lk, float scale, float dropout_p, const unsigned long long *seed, const unsigned char *mask,
                               long long mask_sq, float *grad_q, long long gq_sn, long long gq_sl, float *grad_k, long long gk_sn,
                               long long gk_sl, float *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream);
+/* The masked, long-sequence core with bf16 q, k, v, out, grad_out, grad_q, grad_k, grad_v (uint16_t) — what the DINO decoder's
+ * self-attention runs under bf16 autocast.  Added after MSDA_ABI_VERSION 116 without a version bump: purely additive.
+ * Argument lists, geometry (msda_attn32x_supported), mask, seed, dropout hash, fully-hidden rows and error handling are the
+ * _f32 entries'; views as msda_attn32_*_bf16 (strides in elements, multiples of 8; 16-byte aligned bases); lse fp32 [N*H, Lq],
+ * natural log.  For one seed all four cores (resident / long, fp32 / bf16) drop the same (pair, query, key) entries.
+ * Work split: the forward and dQ own 128 queries per workgroup and stream K and V in chunks of 128 rows, dK / dV owns 128 keys
+ * and streams Q and dO (forming the chunk's delta and base-2 lse while loading); 20 KB of LDS (dK / dV 23.5 KB); two backward
+ * launches.  Every product on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  Rounding points (msda_attn32_*_bf16's, carried
+ * to the online softmax): scores scaled by scale * log2 e in fp32 after the product; running maximum, running sum and
+ * rescaling in fp32; the forward rounds to bf16 only the operand of P v, which is the chunk's UN-NORMALISED, dropout-selected
+ * 2^(s - m) — keep_scale / sum is applied once in fp32 at the end and out rounded once (the resident core rounds the normalised
+ * P instead: it has the sum before the product).  Backward: P = 2^(s - lse), delta = rowsum(dO * O) from the saved bf16 out in
+ * fp32, dP = dO v^T in fp32; P_drop rounded to bf16 as dV's operand, dS = P (dP_drop - delta) rounded to bf16 as dQ's and dK's
+ * operand; dQ and dK scaled in fp32, every gradient rounded once.  Hidden and padding entries' P and dS are selected to 0.
+ * No atomics, fixed summation order: bitwise reproducible.  No host sync, no allocation; captures in a HIP graph. */
+int msda_attn32x_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                              const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                              float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
+                              uint16_t *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream);
+int msda_attn32x_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                               const uint16_t *v, long long v_sn, long long v_sl, const uint16_t *out, long long o_sn, long long o_sl,
+                               const float *lse, const uint16_t *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                               int Lk, float scale, float dropout_p, const unsigned long long *seed, const unsigned char *mask,
+                               long long mask_sq, uint16_t *grad_q, long long gq_sn, long long gq_sl, uint16_t *grad_k,
+                               long long gk_sn, long long gk_sl, uint16_t *grad_v, long long gv_sn, long long gv_sl,
+                               msda_stream_t stream);
 
 /* ---- Transformer input assembly -----------------------------------------------------
  * The flatten block of DeformableTransformer.forward (models/arctic_transformer.py:162-173): per level

@@ -11,8 +11,12 @@ from device events, host syncs per step (torch.cuda.set_sync_debug_mode("warn"))
 step's peak memory above what was allocated before it; then one `summary` row per route and shape with the median of the three
 runs.  One JSON line each, on stdout and appended to --out (default profiles/attn_long_time.jsonl).
 
-    python tools/attn_long_time.py [--iters N] [--only ROUTE] [--out FILE]
-    python tools/attn_long_time.py --trace-steps 5        # a few long_core steps and nothing else: the run to put under rocprofv3"""
+--autocast: the same two shapes under torch.autocast("cuda", dtype=torch.bfloat16) with MSDA_ATTN_LONG_BF16=1 (DESIGN.md
+§4.27a): `module` is then the stock module under autocast — what such an input gets with the knob unset — and `long_core` the
+node on the bf16 streaming kernels; the rows carry "autocast": "bf16".
+
+    python tools/attn_long_time.py [--autocast] [--iters N] [--only ROUTE] [--out FILE]
+    python tools/attn_long_time.py [--autocast] --trace-steps 5   # a few long_core steps and nothing else: the run to put under rocprofv3"""
 import argparse
 import json
 import os
@@ -33,7 +37,7 @@ SHAPES = (("dino_train_masked", 1098, True), ("eval_900_unmasked", 900, False))
 ROUTES = ("module", "long_core")
 
 
-def build(L, masked):
+def build(L, masked, autocast=False):
     torch.manual_seed(0)
     mha = torch.nn.MultiheadAttention(E, HEADS, dropout=P).to(DEV).train()
     x_qk = torch.randn(L, N, E, device=DEV, requires_grad=True)
@@ -44,11 +48,12 @@ def build(L, masked):
     params = list(mha.parameters())
 
     def step(route):
-        if route == "module":
-            y = mha(x_qk, x_qk, x_v, attn_mask=mask, need_weights=False)[0]
-        else:
-            y = self_attention(mha, x_qk, x_v, attn_mask=mask)
-        torch.autograd.grad(y, [x_qk, x_v] + params, go)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            if route == "module":
+                y = mha(x_qk, x_qk, x_v, attn_mask=mask, need_weights=False)[0]
+            else:
+                y = self_attention(mha, x_qk, x_v, attn_mask=mask)
+        torch.autograd.grad(y, [x_qk, x_v] + params, go.to(y.dtype))
     return step
 
 
@@ -57,13 +62,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default=None)
     ap.add_argument("--trace-steps", type=int, default=0)
+    ap.add_argument("--autocast", action="store_true", help="bf16 autocast, MSDA_ATTN_LONG_BF16=1")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_long_time.jsonl"))
     args = ap.parse_args()
     os.environ["MSDA_ATTN_LONG"] = "1"                  # (read at call time; only the long_core route calls the wrapper)
+    if args.autocast:
+        os.environ["MSDA_ATTN_LONG_BF16"] = "1"
+    extra = {"autocast": "bf16"} if args.autocast else {}
 
     if args.trace_steps:
         for shape, L, masked in SHAPES:
-            step = build(L, masked)
+            step = build(L, masked, args.autocast)
             for _ in range(args.trace_steps):
                 step("long_core")
         torch.cuda.synchronize()
@@ -76,7 +85,7 @@ def main():
             f.write(line + "\n")
 
     for shape, L, masked in SHAPES:
-        step = build(L, masked)
+        step = build(L, masked, args.autocast)
         gpu_ms = {r: [] for r in ROUTES}
         last = {}
         for run in range(3):                                          # the two routes interleaved, run by run
@@ -89,7 +98,7 @@ def main():
                 last[route] = {"tool": "attn_long_time", "shape": shape, "route": route, "L": L, "masked": masked, "N": N,
                                "heads": HEADS, "E": E, "p": P, "iters": args.iters, "device": torch.cuda.get_device_name(DEV),
                                "host_syncs_per_step": count_syncs(fn), "kernels_per_step": count_kernels(fn),
-                               "peak_mib_per_step": round(peak_mib(fn), 1)}
+                               "peak_mib_per_step": round(peak_mib(fn), 1), **extra}
                 emit(dict(last[route], run=run, wall_ms_per_step=round(wall, 4), gpu_event_ms_per_step=round(gpu, 4)))
         for route in ROUTES:
             if gpu_ms[route]:

@@ -83,6 +83,8 @@ SIGNATURES = {
     "msda_attn32x_supported": "i iii",
     "msda_attn32x_forward_f32": "i pll pll pll iiii ff p pl pll pp",
     "msda_attn32x_backward_f32": "i pll pll pll pll p pll iiii ff p pl pll pll pll p",
+    "msda_attn32x_forward_bf16": "i pll pll pll iiii ff p pl pll pp",
+    "msda_attn32x_backward_bf16": "i pll pll pll pll p pll iiii ff p pl pll pll pll p",
     # transformer input assembly
     "msda_flatten_levels_f32": "i i ppppp ii ppp",
     "msda_unflatten_levels_f32": "i i pppp ii ppppp",
@@ -846,39 +848,44 @@ def _attn_mask_bytes(mask, Lq, Lk, who):
 def attn32x_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None, mask=None):
     """msda_attn32x_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale + M)) v per (batch, head), head_dim 32, float32,
     1 <= Lq, Lk <= 2048.  Arguments as attn32_forward; mask: a 2-D bool CUDA tensor [Lq, Lk] shared by every batch entry and
-    head, True = the key is hidden (passed as its bytes), or None.  Returns (out [Lq, N, E], lse [N*heads, Lq])."""
+    head, True = the key is hidden (passed as its bytes), or None.  Returns (out [Lq, N, E], lse [N*heads, Lq]).
+    bfloat16 q, k, v take msda_attn32x_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
-    qv, kv, vv = _attn_view(q, "q", heads), _attn_view(k, "k", heads), _attn_view(v, "v", heads)
+    dt = _attn_dtype(q)
+    qv, kv, vv = _attn_view(q, "q", heads, dt), _attn_view(k, "k", heads, dt), _attn_view(v, "v", heads, dt)
     if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise RuntimeError("attn32x_forward: dropout needs a one-element int64 CUDA seed tensor")
     mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_forward")
-    out = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device)
+    out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
     lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
-    ov = _attn_view(out, "out", heads)
-    _launch(q.device, "msda_attn32x_forward_f32", "attn32x_forward", *qv, *kv, *vv, N, heads, Lq, Lk, float(scale),
-            float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, mptr, msq, *ov, lse.data_ptr())
+    ov = _attn_view(out, "out", heads, dt)
+    _launch(q.device, "msda_attn32x_forward_bf16" if dt == torch.bfloat16 else "msda_attn32x_forward_f32", "attn32x_forward",
+            *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, mptr, msq,
+            *ov, lse.data_ptr())
     return out, lse
 
 
 def attn32x_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, mask=None, grad_q=None, grad_k=None,
                      grad_v=None):
     """msda_attn32x_backward_f32: gradients of q, k, v under the forward's mask and seed (written into grad_q / grad_k / grad_v
-    when given — views like the inputs — else into new contiguous tensors)."""
+    when given — views like the inputs — else into new contiguous tensors).  bfloat16 q takes msda_attn32x_backward_bf16: every
+    tensor but lse bfloat16, gradients included."""
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
-    grad_q = torch.empty((Lq, N, heads * 32), dtype=torch.float32, device=q.device) if grad_q is None else grad_q
-    grad_k = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_k is None else grad_k
-    grad_v = torch.empty((Lk, N, heads * 32), dtype=torch.float32, device=q.device) if grad_v is None else grad_v
+    dt = _attn_dtype(q)
+    grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
+    grad_k = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_k is None else grad_k
+    grad_v = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_v is None else grad_v
     if grad_out.stride(2) != 1:
         grad_out = grad_out.contiguous()
-    views = [_attn_view(t, nm, heads) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
-    gov = _attn_view(grad_out, "grad_out", heads)
-    gviews = [_attn_view(t, nm, heads) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
+    views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
+    gov = _attn_view(grad_out, "grad_out", heads, dt)
+    gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
     if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise RuntimeError("attn32x_backward: dropout needs a one-element int64 CUDA seed tensor")
     mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_backward")
-    _launch(q.device, "msda_attn32x_backward_f32", "attn32x_backward", *views[0], *views[1], *views[2], *views[3],
-            lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None,
-            mptr, msq, *gviews[0], *gviews[1], *gviews[2])
+    _launch(q.device, "msda_attn32x_backward_bf16" if dt == torch.bfloat16 else "msda_attn32x_backward_f32", "attn32x_backward",
+            *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p),
+            seed.data_ptr() if dropout_p > 0 else None, mptr, msq, *gviews[0], *gviews[1], *gviews[2])
     return grad_q, grad_k, grad_v
 
 

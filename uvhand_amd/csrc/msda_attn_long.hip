@@ -27,6 +27,7 @@
 // same skip in the forward and in dK / dV was measured and left out: 601 -> 590 and 1149 -> 1131 us masked, but 349 -> 389
 // and 650 -> 678 us at 900 rows unmasked (the forward then holds the tiles' mask bits across its products: 90 VGPRs against 80).
 // Dropout: msda_attn.hip's hash and counter — at_hash((query << 16) + key + at_mix(seed, pair)) — seed read from device memory.
+// The bf16 form for bf16 autocast (msda_attn32x_*_bf16) follows the fp32 kernels below.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -333,6 +334,304 @@ static bool ax_view_ok(const AxView &v)
 // LDS above 64 KB would be requested as msda_attn.hip's at_allow_lds does; the three kernels' static 18 KB need no opt-in.
 static_assert((2 * kAxChunk * kAtRow + 3 * kAxChunk) * sizeof(float) <= 64 * 1024, "static LDS");
 
+// ---- bf16 operands (msda_attn32x_*_bf16) -----------------------------------------------------------------------------------------
+// The same three kernels and the same work split with q, k, v, out, dO and the gradients in bf16 and every product on
+// v_mfma_f32_16x16x32_bf16 (fp32 accumulate) through the ab_* helpers of msda_attn_tile.h: a workgroup of 8 wavefronts owns
+// kAxRows = 128 queries (keys), 16 per wavefront, and streams the other operand in chunks of kAxbChunk = 128 rows = 4 tile
+// pairs of 32 — bf16 rows are [rows][kAbRow = 40], so two slices of 128 rows are 20 KB (dK / dV: + 3.5 KB), what the fp32
+// kernels' 64-row chunks cost, with half the barriers per key; one 16-byte load per thread and slice fills a chunk.
+// A lane (c, r) holds the 8 keys (queries) 32T + 8r + j of a pair (msda_attn_tile.h, "Relabelling").
+// Rounding points — msda_attn32_*_bf16's, carried over to the online softmax:
+//   * scores: the bf16 product accumulated in fp32, times scale * log2 e AFTER the product (a bf16 q cannot be prescaled without
+//     a rounding); running maximum, running sum (of the unrounded, undropped 2^(s - m)) and the rescaling of O in fp32;
+//   * forward: the operand of P . V is the chunk's UN-NORMALISED, dropout-selected 2^(s - m) rounded to bf16 — a value in
+//     [0, 1], so its rounding error relative to the row's largest term is that of the resident core's normalised P; the row's
+//     keep_scale / sum is applied once in fp32 at the end and out rounded once.  (The resident core rounds the normalised
+//     P * keep_scale / sum: it knows the sum before the product.  The two differ by the rounding of one bf16 operand.)
+//   * backward: P = 2^(s - lse) from the hi + lo lse, delta = rowsum(dO * O) from the saved bf16 out in fp32 (one function,
+//     one order, in both launches), dP = dO v^T in fp32; P_drop rounded to bf16 as dV's operand, dS = P (dP_drop - delta) rounded
+//     to bf16 as dQ's and dK's; dQ and dK scaled in fp32, then every gradient rounded once.
+// Kept from the fp32 kernels: every 32-row pair's product starts from a zero accumulator and is added on the vector unit
+// (ax_tile_sums — with bf16 operands the terms are exact products, but the chain's intermediate roundings are the same fp32
+// ones); hidden and padding entries' P and dS selected to 0; the tile skip of dQ, now a 32-key pair decided by one ballot —
+// every loop around ab_tr stays wave-uniform (the transposed LDS read needs all 64 lanes); the whole chunk zero-filled past
+// L (a stale NaN row would meet P = 0 in the product); the dropout counter on the real (query, key) indices.
+constexpr int kAxbChunk = 128, kAxbPairs = kAxbChunk / 32;
+static_assert(kAxbChunk * 4 == kAxBlock, "one 16-byte load per thread and slice in axb_load_chunk2");
+
+struct AxbView { uint16_t *p; long long sn, sl; };     // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
+struct AxbArgs {
+    AxbView q, k, v, o, go, gq, gk, gv;
+    float *lse;
+    const unsigned long long *seed;
+    const unsigned char *mask;
+    long long mask_sq;
+    int H, Lq, Lk, nblk;
+    float scale, scale2, keep_scale;
+    unsigned thresh;
+};
+
+// rows [row0, row0 + kAxbChunk) of two [L][32] bf16 slices -> dst0 / dst1 [kAxbChunk][kAbRow]; rows past L zero
+__device__ __forceinline__ void axb_load_chunk2(uint16_t *dst0, const uint16_t *src0, long long sl0, uint16_t *dst1,
+                                                const uint16_t *src1, long long sl1, int row0, int L)
+{
+    const int row = threadIdx.x >> 2, c = (threadIdx.x & 3) * 8, g = row0 + row;
+    const bool live = g < L;
+    const at_bf8 v0 = live ? ab_ld8(src0 + (long long)g * sl0 + c) : ab_zero8();
+    const at_bf8 v1 = live ? ab_ld8(src1 + (long long)g * sl1 + c) : ab_zero8();
+    *reinterpret_cast<at_bf8 *>(dst0 + row * kAbRow + c) = v0;
+    *reinterpret_cast<at_bf8 *>(dst1 + row * kAbRow + c) = v1;
+}
+
+// bit j set: key0 + j (j = 0..7) is hidden from this lane's query or lies past Lk
+__device__ __forceinline__ unsigned axb_hidden8(const unsigned char *mrow, int key0, int Lk)
+{
+    return ax_hidden4(mrow, key0, Lk) | (ax_hidden4(mrow, key0 + 4, Lk) << 4);
+}
+
+// 8 channels of <dO, O> in fp32; both backward launches sum a row's four parts as (0 + 1) + (2 + 3)
+__device__ __forceinline__ float axb_dot8(const at_bf8 &g, const at_bf8 &o)
+{
+    float d = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d = fmaf(ab_f(g[j]), ab_f(o[j]), d);
+    return d;
+}
+
+__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_bf16_kernel(const AxbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t Ks[kAxbChunk * kAbRow], Vs[kAxbChunk * kAbRow];
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = blk * kAxRows + wave * 16 + c;
+    const bool qok = qi < a.Lq;
+    at_bf8 qf = ab_zero8();
+    if (qok) qf = ab_ld8(a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 8 * r);
+    const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
+    const uint16_t *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
+    const unsigned ctr = ((unsigned)qi << 16) + 8 * r + mix;
+    float m = -INFINITY, sum = 0.f;                     // running maximum (base 2) of the query; this lane's share of the sum
+    at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
+    for (int k0 = 0; k0 < a.Lk; k0 += kAxbChunk) {
+        __syncthreads();                                // (the last chunk's readers are done)
+        axb_load_chunk2(Ks, kp, a.k.sl, Vs, vp, a.v.sl, k0, a.Lk);
+        __syncthreads();
+        const int np = min(kAxbPairs, (a.Lk - k0 + 31) >> 5);
+        // s[2T + b][v] = score of key k0 + 32T + 8r + 4b + v for query qi (raw, then times scale * log2 e)
+        at_f4 s[2 * kAxbPairs];
+#pragma unroll
+        for (int T = 0; T < kAxbPairs; ++T)
+            if (T < np) ab_pair(Ks, T, r, c, qf, s[2 * T], s[2 * T + 1]);
+        float cm = -INFINITY;
+#pragma unroll
+        for (int T = 0; T < kAxbPairs; ++T) {
+            if (T < np) {
+                const unsigned hid = axb_hidden8(mrow, k0 + 32 * T + 8 * r, a.Lk);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float x = (hid >> j & 1u) ? -INFINITY : s[2 * T + (j >> 2)][j & 3] * a.scale2;
+                    s[2 * T + (j >> 2)][j & 3] = x;
+                    cm = fmaxf(cm, x);
+                }
+            }
+        }
+        const float m_new = fmaxf(m, at_rmax(cm));
+        const float m_ref = m_new == -INFINITY ? 0.f : m_new;       // (nothing visible yet: every term below is exp2(-inf) = 0)
+        const float alpha = __builtin_amdgcn_exp2f(m - m_ref);
+        sum *= alpha;
+        o0 *= alpha; o1 *= alpha;
+        m = m_new;
+#pragma unroll
+        for (int T = 0; T < kAxbPairs; ++T) {
+            if (T < np) {                               // (uniform over the workgroup: ab_tr sees all 64 lanes)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float p = __builtin_amdgcn_exp2f(s[2 * T + (j >> 2)][j & 3] - m_ref);
+                    sum += p;
+                    const bool keep = at_hash(ctr + (unsigned)(k0 + 32 * T + j)) >= a.thresh;       // (thresh 0: always)
+                    s[2 * T + (j >> 2)][j & 3] = keep ? p : 0.f;
+                }
+                const at_bf8 pb = ab_pack(s[2 * T], s[2 * T + 1]);          // P^T[key k0 + 32T + 8r + j][query qi], un-normalised
+                const at_f4 z = {0.f, 0.f, 0.f, 0.f};
+                o0 += ab_mfma(ab_tr(Vs, T, 0, r, c), pb, z);                // O^T[channel][query] += V^T . P^T (ax_tile_sums)
+                o1 += ab_mfma(ab_tr(Vs, T, 1, r, c), pb, z);
+            }
+        }
+    }
+    sum = at_rsum(sum);
+    if (qok) {
+        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = ax_lse_natural(m, __builtin_amdgcn_logf(sum));
+        const float inv = a.keep_scale / sum;           // (sum 0 — every key hidden: inf, and the row 0 * inf = NaN)
+        uint16_t *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
+        ab_st4(orow, o0, inv);
+        ab_st4(orow + 16, o1, inv);
+    }
+}
+
+// dK, dV: a wavefront owns 16 keys; the workgroup walks the query chunks
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_bf16_kernel(const AxbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t Qs[kAxbChunk * kAbRow], Gs[kAxbChunk * kAbRow];
+    __shared__ __attribute__((aligned(16))) float lse_s[kAxbChunk], lsl_s[kAxbChunk], del_s[kAxbChunk];
+    __shared__ __attribute__((aligned(16))) unsigned msk_s[4 * kAxbChunk];  // [32-key part of the block][query]: hidden bits
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int key = blk * kAxRows + wave * 16 + c;
+    const bool kok = key < a.Lk;
+    at_bf8 kf = ab_zero8(), vf = ab_zero8();
+    if (kok) {
+        kf = ab_ld8(a.k.p + n * a.k.sn + h * 32 + (long long)key * a.k.sl + 8 * r);
+        vf = ab_ld8(a.v.p + n * a.v.sn + h * 32 + (long long)key * a.v.sl + 8 * r);
+    }
+    const int mpart = wave >> 1, mbit = (wave & 1) * 16 + c;       // this lane's key in msk_s: word [mpart][query], bit mbit
+    const uint16_t *qp = a.q.p + n * a.q.sn + h * 32, *gp = a.go.p + n * a.go.sn + h * 32, *op = a.o.p + n * a.o.sn + h * 32;
+    const unsigned ctr = (unsigned)key + ((unsigned)(8 * r) << 16) + mix;
+    at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
+    for (int c0 = 0; c0 < a.Lq; c0 += kAxbChunk) {
+        __syncthreads();
+        {
+            // a thread loads 8 channels of one query's q, dO and O: the chunk's two slices, and its part of delta = <dO, O>;
+            // the log-sum-exp in base 2 is +inf for the rows past Lq (their probabilities vanish).  The mask is read here too,
+            // along the queries' rows (ax_hidden4's 4-byte reads) and kept as bits: a lane reading its key's column byte by
+            // byte in the tile loop cost dK / dV 320 us of 653 at 1098 rows under the denoising mask.
+            const int row = threadIdx.x >> 2, part = threadIdx.x & 3, g = c0 + row;
+            const bool live = g < a.Lq;
+            const at_bf8 qv = live ? ab_ld8(qp + (long long)g * a.q.sl + 8 * part) : ab_zero8();
+            const at_bf8 gv = live ? ab_ld8(gp + (long long)g * a.go.sl + 8 * part) : ab_zero8();
+            const at_bf8 ov = live ? ab_ld8(op + (long long)g * a.o.sl + 8 * part) : ab_zero8();
+            *reinterpret_cast<at_bf8 *>(Qs + row * kAbRow + 8 * part) = qv;
+            *reinterpret_cast<at_bf8 *>(Gs + row * kAbRow + 8 * part) = gv;
+            float d = axb_dot8(gv, ov);
+            d += __shfl_xor(d, 1);
+            d += __shfl_xor(d, 2);
+            if (part == 0) {
+                float hi, lo;
+                ax_lse_base2(live ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
+                del_s[row] = d; lse_s[row] = hi; lsl_s[row] = lo;
+            }
+            if (a.mask != nullptr) {                    // the query's mask row over 32 of the block's keys as one word of bits
+                const unsigned char *mrow = live ? a.mask + (long long)g * a.mask_sq : nullptr;
+                const int key0 = blk * kAxRows + 32 * part;
+                unsigned w = 0;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) w |= ax_hidden4(mrow, key0 + 4 * i, a.Lk) << (4 * i);
+                msk_s[part * kAxbChunk + row] = w;
+            }
+        }
+        __syncthreads();
+        const int np = min(kAxbPairs, (a.Lq - c0 + 31) >> 5);
+#pragma unroll 1
+        for (int T = 0; T < np; ++T) {                  // (uniform over the workgroup)
+            // S and dP tiles of the pair: entry (b, v) = (query c0 + 32T + 8r + 4b + v, key)
+            at_f4 s[2], dp[2];
+            ab_pair(Qs, T, r, c, kf, s[0], s[1]);
+            ab_pair(Gs, T, r, c, vf, dp[0], dp[1]);
+            const int ql = 32 * T + 8 * r, qrow = c0 + ql;
+            const float4 h0 = ld4(lse_s + ql), h1 = ld4(lse_s + ql + 4), w0 = ld4(lsl_s + ql), w1 = ld4(lsl_s + ql + 4);
+            const float4 e0 = ld4(del_s + ql), e1 = ld4(del_s + ql + 4);
+            const float lsv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w}, llv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            const float dlv[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+            unsigned hb = 0;                            // bit j: this lane's key is hidden from query qrow + j
+            if (a.mask != nullptr) {
+                const uint4 m0 = *reinterpret_cast<const uint4 *>(msk_s + mpart * kAxbChunk + ql);
+                const uint4 m1 = *reinterpret_cast<const uint4 *>(msk_s + mpart * kAxbChunk + ql + 4);
+                const unsigned mw[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) hb |= (mw[j] >> mbit & 1u) << j;
+            }
+            at_f4 pd[2], ds[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int b = j >> 2, v = j & 3;
+                const bool hid = (hb >> j & 1u) != 0;
+                const float p = hid ? 0.f : __builtin_amdgcn_exp2f(fmaf(s[b][v], a.scale2, -lsv[j]) - llv[j]);
+                const bool keep = at_hash(ctr + ((unsigned)(qrow - 8 * r + j) << 16)) >= a.thresh;
+                pd[b][v] = keep ? p * a.keep_scale : 0.f;
+                ds[b][v] = hid ? 0.f : p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - dlv[j]);
+            }
+            const at_bf8 pb = ab_pack(pd[0], pd[1]), sb = ab_pack(ds[0], ds[1]);
+            const at_f4 z = {0.f, 0.f, 0.f, 0.f};
+            dv0 += ab_mfma(ab_tr(Gs, T, 0, r, c), pb, z);                   // dV^T[channel][key] += dO^T . P_drop
+            dv1 += ab_mfma(ab_tr(Gs, T, 1, r, c), pb, z);
+            dk0 += ab_mfma(ab_tr(Qs, T, 0, r, c), sb, z);                   // dK^T[channel][key] += Q^T . dS
+            dk1 += ab_mfma(ab_tr(Qs, T, 1, r, c), sb, z);
+        }
+    }
+    if (kok) {
+        uint16_t *gvr = a.gv.p + n * a.gv.sn + h * 32 + (long long)key * a.gv.sl + 4 * r;
+        uint16_t *gkr = a.gk.p + n * a.gk.sn + h * 32 + (long long)key * a.gk.sl + 4 * r;
+        ab_st4(gvr, dv0, 1.f); ab_st4(gvr + 16, dv1, 1.f);
+        ab_st4(gkr, dk0, a.scale); ab_st4(gkr + 16, dk1, a.scale);
+    }
+}
+
+// dQ: a wavefront owns 16 queries; the workgroup walks the key chunks (S^T tiles, as the forward)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_bf16_kernel(const AxbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t Ks[kAxbChunk * kAbRow], Vs[kAxbChunk * kAbRow];
+    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
+    const int qi = blk * kAxRows + wave * 16 + c;
+    const bool qok = qi < a.Lq;
+    at_bf8 qf = ab_zero8(), gf = ab_zero8(), of = ab_zero8();
+    float lse_n = INFINITY;                             // (rows past Lq: probabilities vanish)
+    if (qok) {
+        qf = ab_ld8(a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 8 * r);
+        gf = ab_ld8(a.go.p + n * a.go.sn + h * 32 + (long long)qi * a.go.sl + 8 * r);
+        of = ab_ld8(a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 8 * r);
+        lse_n = a.lse[(long long)pair * a.Lq + qi];
+    }
+    float lse, lse_lo;
+    ax_lse_base2(lse_n, lse, lse_lo);
+    const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
+    const uint16_t *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
+    const unsigned ctr = ((unsigned)qi << 16) + 8 * r + mix;
+    const float delta = at_rsum(axb_dot8(gf, of));
+    at_f4 dq0 = {0.f, 0.f, 0.f, 0.f}, dq1 = dq0;
+    for (int k0 = 0; k0 < a.Lk; k0 += kAxbChunk) {
+        __syncthreads();
+        axb_load_chunk2(Ks, kp, a.k.sl, Vs, vp, a.v.sl, k0, a.Lk);
+        __syncthreads();
+        const int np = min(kAxbPairs, (a.Lk - k0 + 31) >> 5);
+#pragma unroll 1
+        for (int T = 0; T < np; ++T) {
+            const unsigned hid = axb_hidden8(mrow, k0 + 32 * T + 8 * r, a.Lk);
+            // hidden from the whole wavefront (rows past Lq count as hidden): exact zeros, skipped — one ballot, so the loop
+            // stays wave-uniform around ab_tr
+            if (a.mask != nullptr && __all(!qok || hid == 0xffu)) continue;
+            // S^T and dP^T tiles of the pair: entry (b, v) = (key k0 + 32T + 8r + 4b + v, query qi)
+            at_f4 s[2], dp[2];
+            ab_pair(Ks, T, r, c, qf, s[0], s[1]);
+            ab_pair(Vs, T, r, c, gf, dp[0], dp[1]);
+            at_f4 ds[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int b = j >> 2, v = j & 3;
+                const float p = __builtin_amdgcn_exp2f(fmaf(s[b][v], a.scale2, -lse) - lse_lo);
+                const bool keep = at_hash(ctr + (unsigned)(k0 + 32 * T + j)) >= a.thresh;
+                ds[b][v] = (hid >> j & 1u) ? 0.f : p * ((keep ? dp[b][v] * a.keep_scale : 0.f) - delta);
+            }
+            const at_bf8 sb = ab_pack(ds[0], ds[1]);
+            const at_f4 z = {0.f, 0.f, 0.f, 0.f};
+            dq0 += ab_mfma(ab_tr(Ks, T, 0, r, c), sb, z);                   // dQ^T[channel][query] += K^T . dS^T
+            dq1 += ab_mfma(ab_tr(Ks, T, 1, r, c), sb, z);
+        }
+    }
+    if (qok) {
+        uint16_t *gq = a.gq.p + n * a.gq.sn + h * 32 + (long long)qi * a.gq.sl + 4 * r;
+        ab_st4(gq, dq0, a.scale); ab_st4(gq + 16, dq1, a.scale);
+    }
+}
+
+static bool axb_view_ok(const AxbView &v)
+{
+    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 7) == 0 && (v.sl & 7) == 0;
+}
+static_assert(2 * kAxbChunk * kAbRow * sizeof(uint16_t) + 7 * kAxbChunk * sizeof(float) <= 64 * 1024, "static LDS");
+
 }  // namespace msda
 
 using msda::AxArgs;
@@ -414,6 +713,65 @@ int msda_attn32x_backward_f32(const float *q, long long q_sn, long long q_sl, co
     a.nblk = nblk_q;
     hipLaunchKernelGGL(msda::attn32x_bwd_q_kernel, dim3((unsigned)(N * H * nblk_q)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     return msda::check_launch("msda long attention backward (dQ)");
+}
+
+// bf16 operands: ax_fill's checks (all of them before any launch), the fp32 entries' random stream
+static int axb_fill(msda::AxbArgs &b, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p,
+                    const unsigned long long *seed, const unsigned char *mask, long long mask_sq)
+{
+    AxArgs a{};
+    if (int rc = ax_fill(a, who, N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
+    b.H = a.H; b.Lq = a.Lq; b.Lk = a.Lk; b.scale = a.scale; b.scale2 = a.scale2; b.keep_scale = a.keep_scale; b.thresh = a.thresh;
+    b.seed = a.seed; b.mask = a.mask; b.mask_sq = a.mask_sq;
+    return MSDA_OK;
+}
+
+int msda_attn32x_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                              const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
+                              float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
+                              uint16_t *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream)
+{
+    using msda::AxbView;
+    msda::AxbArgs a{};
+    if (int rc = axb_fill(a, "msda_attn32x_forward_bf16", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
+    a.q = AxbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AxbView{const_cast<uint16_t *>(k), k_sn, k_sl};
+    a.v = AxbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AxbView{out, o_sn, o_sl}; a.lse = lse;
+    if (!msda::axb_view_ok(a.q) || !msda::axb_view_ok(a.k) || !msda::axb_view_ok(a.v) || !msda::axb_view_ok(a.o) || lse == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
+    a.nblk = (Lq + msda::kAxRows - 1) / msda::kAxRows;
+    if ((long long)N * H * a.nblk > 0x7fffffffLL) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_bf16: too many (batch, head) pairs");
+    hipLaunchKernelGGL(msda::attn32x_fwd_bf16_kernel, dim3((unsigned)(N * H * a.nblk)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    return msda::check_launch("msda long attention forward (head_dim 32, bf16)");
+}
+
+int msda_attn32x_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
+                               const uint16_t *v, long long v_sn, long long v_sl, const uint16_t *out, long long o_sn, long long o_sl,
+                               const float *lse, const uint16_t *grad_out, long long go_sn, long long go_sl, int N, int H, int Lq,
+                               int Lk, float scale, float dropout_p, const unsigned long long *seed, const unsigned char *mask,
+                               long long mask_sq, uint16_t *grad_q, long long gq_sn, long long gq_sl, uint16_t *grad_k,
+                               long long gk_sn, long long gk_sl, uint16_t *grad_v, long long gv_sn, long long gv_sl,
+                               msda_stream_t stream)
+{
+    using msda::AxbView;
+    msda::AxbArgs a{};
+    if (int rc = axb_fill(a, "msda_attn32x_backward_bf16", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
+    a.q = AxbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AxbView{const_cast<uint16_t *>(k), k_sn, k_sl};
+    a.v = AxbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AxbView{const_cast<uint16_t *>(out), o_sn, o_sl};
+    a.go = AxbView{const_cast<uint16_t *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
+    a.gq = AxbView{grad_q, gq_sn, gq_sl}; a.gk = AxbView{grad_k, gk_sn, gk_sl}; a.gv = AxbView{grad_v, gv_sn, gv_sl};
+    for (const AxbView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
+        if (!msda::axb_view_ok(*w))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
+    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: lse required");
+    const int nblk_q = (Lq + msda::kAxRows - 1) / msda::kAxRows, nblk_k = (Lk + msda::kAxRows - 1) / msda::kAxRows;
+    if ((long long)N * H * (nblk_q > nblk_k ? nblk_q : nblk_k) > 0x7fffffffLL)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: too many (batch, head) pairs");
+    a.nblk = nblk_k;
+    hipLaunchKernelGGL(msda::attn32x_bwd_kv_bf16_kernel, dim3((unsigned)(N * H * nblk_k)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    if (int rc = msda::check_launch("msda long attention backward (dK, dV; bf16)")) return rc;
+    a.nblk = nblk_q;
+    hipLaunchKernelGGL(msda::attn32x_bwd_q_bf16_kernel, dim3((unsigned)(N * H * nblk_q)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    return msda::check_launch("msda long attention backward (dQ; bf16)");
 }
 
 }  // extern "C"

@@ -22,8 +22,14 @@ under the contrastive-denoising mask of models/dino/dn_components.py:125-137).  
 (True = hidden) routes the core through the streaming kernels (msda_attn32x_*_f32: head_dim 32, fp32, 1 <= L <= 2048) outside
 autocast; ``MSDA_ATTN_LONG=1`` (read at call time) sends unmasked inputs of 320 < L <= 2048 there too — the 900-query
 evaluation.  The projections, their weight gradients and the dropout stream are the ones above.  Float masks, 3-D masks, other
-head sizes, L > 2048, CPU tensors and any autocast (there is no bf16 form of the long core) go to the module with the mask.
-A query row whose every key is hidden is NaN, as the module's; its gradients are outside the kernels' contract."""
+head sizes, L > 2048 and CPU tensors go to the module with the mask.
+A query row whose every key is hidden is NaN, as the module's; its gradients are outside the kernels' contract.
+
+Under bf16 autocast the same two rules apply only when ``MSDA_ATTN_LONG_BF16=1`` is set (read at call time, off by default): the
+projections return bf16 and the core runs on the streaming bf16 kernels (msda_attn32x_*_bf16: bf16 operands, fp32 online softmax
+and accumulation, bf16 output and gradients).  A 2-D bool CUDA mask routes there; unmasked 320 < L <= 2048 needs
+``MSDA_ATTN_LONG=1`` as well; unmasked L <= 320 stays on the resident bf16 core.  With the knob unset every masked or long input
+under autocast is the module's, as before; fp16 autocast always is."""
 import math
 import os
 
@@ -65,7 +71,8 @@ class _Attn32Fn(Function):
 
 
 class _Attn32xFn(Function):
-    """core(qk [L, N, 2E], v [L, N, E], mask [L, L] bool or None) -> [L, N, E]; fp32, streaming kernels (msda_attn32x_*_f32)"""
+    """core(qk [L, N, 2E], v [L, N, E], mask [L, L] bool or None) -> [L, N, E]; streaming kernels, fp32 or bf16 (msda_attn32x_*:
+    dispatch on qk's dtype)"""
 
     @staticmethod
     def forward(ctx, qk, v, mask, heads, dropout_p):
@@ -103,16 +110,19 @@ def _takes_common(mha, x_qk, x_v):
 
 
 def _takes_long(mha, x_qk, x_v, attn_mask):
-    """The streaming core: _takes' conditions with its length bound (fp32 outside autocast only), for a 2-D bool CUDA mask
-    [L, L] — or, unmasked, for 320 < L when MSDA_ATTN_LONG=1."""
+    """The streaming core: _takes' conditions with its length bound, for a 2-D bool CUDA mask [L, L] — or, unmasked, for
+    320 < L when MSDA_ATTN_LONG=1.  Outside autocast (fp32), or under bf16 autocast when MSDA_ATTN_LONG_BF16=1."""
     if attn_mask is None:
         if os.environ.get("MSDA_ATTN_LONG", "0") in ("", "0"):
             return False
     elif not (torch.is_tensor(attn_mask) and attn_mask.dtype == torch.bool and attn_mask.is_cuda and attn_mask.dim() == 2
               and attn_mask.shape[0] == attn_mask.shape[1] == x_qk.shape[0] and attn_mask.device == x_qk.device):
         return False
-    if not _takes_common(mha, x_qk, x_v) or torch.is_autocast_enabled():
+    if not _takes_common(mha, x_qk, x_v):
         return False
+    if torch.is_autocast_enabled() and (_autocast_dtype() != torch.bfloat16
+                                        or os.environ.get("MSDA_ATTN_LONG_BF16", "0") in ("", "0")):
+        return False                                     # (bf16 autocast: the bf16 kernels, opt-in; fp16: the module)
     L = x_qk.shape[0]
     if attn_mask is None and MSDA.attn32_supported(L, L, mha.head_dim):
         return False                                     # (unmasked and short: the resident core's)

@@ -549,6 +549,40 @@ int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stri
 int msda_assembly_select_f32(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
                              int left, int right, int64_t *indices, float *reference_points, msda_stream_t stream);
 
+/* ---- The DINO decoder's query positions and refinement (models/dino/deformable_transformer.py:730-746, :781-798) ----------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the five entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ * Rows are sequence-first: ref [M, width] (width 2 or 42, 1 or 21 (x, y) pairs) with row m in frame m % N, so M % N == 0;
+ * valid_xy [N, 2] the level-0 valid ratios (x, y), NULL = 1; dim_t [64] torch's table at even indices (utils.py:142-143).
+ * All fp32, contiguous rows.
+ *   msda_dino_sine_embed_f32   gen_sineembed_for_position (utils.py:138-165) of ref * valid ratios: pe [M, 256] (16-byte
+ *       aligned); ex = 2 pi * mean_k(ref[m, 2k] * valid_x), ey likewise from the odd columns; pe[m, 2i + s] = s ?
+ *       cos(ey / dim_t[i]) : sin(ey / dim_t[i]) for i < 64, columns 128 .. 255 the same from ex (y first).  One launch.
+ *   msda_dino_query_pos_forward_f32  ref_point_head of that table in one launch: h [M, 256] = relu(pe @ w1^T + b1), y [M, 256]
+ *       = h @ w2^T + b2, with w1, w2 [256, 256] (16-byte aligned) and b1, b2 [256].  The table never exists in memory and h is
+ *       written exactly once.  fp32 MFMA, fixed summation order.  msda_dino_query_pos_supported(width, N, M, hidden, out)
+ *       tells beforehand (1 = the call runs): hidden = out = 256 only.
+ *   msda_dino_refine_forward_f32   the refinement (:781-798) without its boolean-mask adds: ref, delta_key, delta_obj [M, 42],
+ *       cls [M, K]; per row c = argmax(cls) (first maximum, NaN highest), code = 2 if c is hand0 / hand1, 1 if c is neither and
+ *       not 0, else 0; u = inverse_sigmoid(ref) (util/misc.py:614-618) + (code 1: delta_obj, code 2: delta_key);
+ *       out [M, 42] = sigmoid(u) * 2 - 1, code [M] bytes.  One launch, no synchronisation.
+ *   msda_dino_refine_backward_f32  g_u = grad_out * (1 - out^2) / 2; grad_key = g_u where code == 2, else 0; grad_obj = g_u
+ *       where code == 1, else 0 (either may be NULL: not written).  cls and ref get no gradient.  One launch.
+ * No allocation, no synchronisation, no atomics: bitwise reproducible, capturable in a graph.  Argument errors
+ * (MSDA_ERR_ARGUMENT before any launch): width not 2 or 42, N <= 0, M % N != 0, K < 1, tensors beyond 2^31 elements, a null
+ * or misaligned pointer. */
+int msda_dino_sine_embed_f32(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t, float *pe,
+                             msda_stream_t stream);
+int msda_dino_query_pos_supported(int width, int N, long long M, int hidden, int out_features);
+int msda_dino_query_pos_forward_f32(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t,
+                                    const float *w1, const float *b1, const float *w2, const float *b2, float *h, float *y,
+                                    msda_stream_t stream);
+int msda_dino_refine_forward_f32(const float *ref, const float *cls, int K, const float *delta_key, const float *delta_obj, int hand0,
+                                 int hand1, long long M, float *out, uint8_t *code, msda_stream_t stream);
+int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const uint8_t *code, long long M, float *grad_key,
+                                  float *grad_obj, msda_stream_t stream);
+
 /* ---- The Hungarian matchers (models/matcher.py: ArcticMatcher :20-125, AssemblyMatcher :128-230) -------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
  * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.

@@ -100,6 +100,12 @@ SIGNATURES = {
     "msda_assembly_refine_f32": "i p i p i p l pp",
     "msda_assembly_proposals_f32": "i p l p l iiii pppp",
     "msda_assembly_select_f32": "i ppp iiiiiii ppp",
+    # the DINO decoder's query positions and refinement
+    "msda_dino_sine_embed_f32": "i p i p i l pp p",
+    "msda_dino_query_pos_supported": "i ii l ii",
+    "msda_dino_query_pos_forward_f32": "i p i p i l ppppp pp p",
+    "msda_dino_refine_forward_f32": "i pp i pp ii l pp p",
+    "msda_dino_refine_backward_f32": "i ppp l pp p",
     # the Hungarian matchers
     "msda_match_arctic_f32": "i ppp iiiii ppp l p i ff ppp",
     "msda_match_assembly_f32": "i pp iiiii ppp l i ff ppp",
@@ -1279,6 +1285,82 @@ def assembly_select(cls, hand, obj, obj_classes=(1, 8), left=9, right=10):
     _launch(cls.device, "msda_assembly_select_f32", "assembly_select", cls.data_ptr(), hand.data_ptr(), obj.data_ptr(), N, S,
             K, int(obj_classes[0]), int(obj_classes[1]), int(left), int(right), idx.data_ptr(), refp.data_ptr())
     return idx, refp
+
+
+# ---- the DINO decoder's query positions and refinement (csrc/msda_dino.hip) -----------------------------------------------
+DINO_PE_WIDTH = 256                                   # gen_sineembed_for_position's columns = ref_point_head's in / hidden / out
+
+
+def _check_dino_rows(what, ref2, valid_xy, n_frames, dim_t):
+    if not (_f32_cuda(ref2) and ref2.dim() == 2 and ref2.shape[1] in (2, 42) and n_frames > 0 and ref2.shape[0] % n_frames == 0
+            and _f32_cuda(dim_t) and dim_t.numel() == 64 and dim_t.device == ref2.device
+            and (valid_xy is None or (_f32_cuda(valid_xy) and tuple(valid_xy.shape) == (n_frames, 2)
+                                      and valid_xy.device == ref2.device))):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA ref [L * N, 2 | 42] (sequence-first rows), valid_xy [N, 2] or None "
+                           "and dim_t [64]" % what)
+
+
+def dino_sine_embed(ref2, valid_xy, n_frames, dim_t):
+    """pe [M, 256] of sequence-first rows ref2 [M, 2 | 42] (row m in frame m % n_frames) — msda_dino_sine_embed_f32."""
+    _check_dino_rows("dino_sine_embed", ref2, valid_xy, n_frames, dim_t)
+    M, W = ref2.shape
+    pe = torch.empty((M, DINO_PE_WIDTH), dtype=torch.float32, device=ref2.device)
+    _launch(ref2.device, "msda_dino_sine_embed_f32", "dino_sine_embed", ref2.data_ptr(), W,
+            valid_xy.data_ptr() if valid_xy is not None else None, int(n_frames), M, dim_t.data_ptr(), pe.data_ptr())
+    return pe
+
+
+def dino_query_pos_supported(width, n_frames, rows, hidden, out_features):
+    """Whether msda_dino_query_pos_forward_f32 takes this geometry (width 2 | 42, rows % frames == 0, hidden = out = 256)."""
+    return bool((_lib or load()).msda_dino_query_pos_supported(int(width), int(n_frames), int(rows), int(hidden), int(out_features)))
+
+
+def dino_query_pos_forward(ref2, valid_xy, n_frames, dim_t, w1, b1, w2, b2):
+    """(h, y) [M, 256] each: h = relu(pe(ref2) @ w1^T + b1), y = h @ w2^T + b2 — msda_dino_query_pos_forward_f32, one launch."""
+    _check_dino_rows("dino_query_pos_forward", ref2, valid_xy, n_frames, dim_t)
+    ws, bs = (w1, w2), (b1, b2)
+    if not (all(_f32_cuda(w) and tuple(w.shape) == (DINO_PE_WIDTH, DINO_PE_WIDTH) and w.device == ref2.device
+                and w.data_ptr() % 16 == 0 for w in ws)
+            and all(_f32_cuda(b) and b.numel() == DINO_PE_WIDTH and b.device == ref2.device for b in bs)):
+        raise RuntimeError("dino_query_pos_forward: expected contiguous fp32 CUDA weights [256, 256] (16-byte aligned) and biases [256]")
+    M, W = ref2.shape
+    h = torch.empty((M, DINO_PE_WIDTH), dtype=torch.float32, device=ref2.device)
+    y = torch.empty((M, DINO_PE_WIDTH), dtype=torch.float32, device=ref2.device)
+    _launch(ref2.device, "msda_dino_query_pos_forward_f32", "dino_query_pos_forward", ref2.data_ptr(), W,
+            valid_xy.data_ptr() if valid_xy is not None else None, int(n_frames), M, dim_t.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+            w2.data_ptr(), b2.data_ptr(), h.data_ptr(), y.data_ptr())
+    return h, y
+
+
+def dino_refine_forward(ref, cls, delta_key, delta_obj, hand_classes=(12, 13)):
+    """(out [..., 42], code [...] uint8) — msda_dino_refine_forward_f32: ref / delta_key / delta_obj [..., 42] and cls [..., K],
+    contiguous fp32 CUDA with the same leading shape.  One launch, no host synchronisation."""
+    lead = tuple(ref.shape[:-1])
+    ts = (ref, cls, delta_key, delta_obj)
+    if not (all(_f32_cuda(t) and t.device == ref.device for t in ts) and ref.shape[-1] == 42 and cls.dim() == ref.dim()
+            and tuple(cls.shape[:-1]) == lead and cls.shape[-1] > 0
+            and tuple(delta_key.shape) == tuple(ref.shape) and tuple(delta_obj.shape) == tuple(ref.shape)):
+        raise RuntimeError("dino_refine_forward: expected contiguous fp32 CUDA ref / delta_key / delta_obj [..., 42] and cls [..., K] "
+                           "with the same leading shape")
+    M = ref.numel() // 42
+    out = torch.empty_like(ref)
+    code = torch.empty(lead, dtype=torch.uint8, device=ref.device)
+    _launch(ref.device, "msda_dino_refine_forward_f32", "dino_refine_forward", ref.data_ptr(), cls.data_ptr(), cls.shape[-1],
+            delta_key.data_ptr(), delta_obj.data_ptr(), int(hand_classes[0]), int(hand_classes[1]), M, out.data_ptr(), code.data_ptr())
+    return out, code
+
+
+def dino_refine_backward(grad_out, out, code, want_key=True, want_obj=True):
+    """(grad_key, grad_obj) [..., 42] (None where not wanted) — msda_dino_refine_backward_f32."""
+    if not (_f32_cuda(grad_out) and _f32_cuda(out) and tuple(grad_out.shape) == tuple(out.shape) and out.shape[-1] == 42
+            and code.is_cuda and code.dtype == torch.uint8 and code.is_contiguous() and code.numel() * 42 == out.numel()
+            and grad_out.device == out.device == code.device):
+        raise RuntimeError("dino_refine_backward: expected contiguous fp32 CUDA grad_out / out [..., 42] and uint8 code [...]")
+    gk = torch.empty_like(out) if want_key else None
+    go = torch.empty_like(out) if want_obj else None
+    _launch(out.device, "msda_dino_refine_backward_f32", "dino_refine_backward", grad_out.data_ptr(), out.data_ptr(), code.data_ptr(),
+            code.numel(), gk.data_ptr() if want_key else None, go.data_ptr() if want_obj else None)
+    return gk, go
 
 
 # ---- the Hungarian matchers (csrc/msda_matcher.hip) ----------------------------------------------------------------------

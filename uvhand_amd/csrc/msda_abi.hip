@@ -926,6 +926,68 @@ int msda_assembly_refine_f32(const float *reference_points, int width, const flo
     return msda::launch_assembly_refine(reference_points, width, cls, K, keypoints, M, out, (hipStream_t)stream);
 }
 
+/* ---- the DINO decoder's query positions and refinement (msda_dino.hip) ---- */
+static const char *dino_rows_error(int width, int N, long long M)
+{
+    if (width != 2 && width != 42) return "width must be 2 or 42";
+    if (N <= 0 || M < 0 || M % N != 0) return "need N > 0, M >= 0 and M a multiple of N (rows are sequence-first)";
+    if (M * 256 >= (1LL << 31)) return "tensors beyond 2^31 elements";
+    return nullptr;
+}
+
+int msda_dino_sine_embed_f32(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t, float *pe,
+                             msda_stream_t stream)
+{
+    if (dino_rows_error(width, N, M)) return msda::set_error(MSDA_ERR_ARGUMENT, dino_rows_error(width, N, M));
+    if (dim_t == nullptr || (M > 0 && (ref == nullptr || pe == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_sine_embed_f32: null device pointer");
+    if (misaligned16(pe)) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_sine_embed_f32: pe must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_dino_sine_embed(ref, width, valid_xy, N, M, dim_t, pe, (hipStream_t)stream);
+}
+
+int msda_dino_query_pos_supported(int width, int N, long long M, int hidden, int out_features)
+{
+    return dino_rows_error(width, N, M) == nullptr && hidden == 256 && out_features == 256;
+}
+
+int msda_dino_query_pos_forward_f32(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t,
+                                    const float *w1, const float *b1, const float *w2, const float *b2, float *h, float *y,
+                                    msda_stream_t stream)
+{
+    if (dino_rows_error(width, N, M)) return msda::set_error(MSDA_ERR_ARGUMENT, dino_rows_error(width, N, M));
+    if (dim_t == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr ||
+        (M > 0 && (ref == nullptr || h == nullptr || y == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_query_pos_forward_f32: null device pointer");
+    if (misaligned16(w1) || misaligned16(w2))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_query_pos_forward_f32: weights must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_dino_query_pos(ref, width, valid_xy, N, M, dim_t, w1, b1, w2, b2, h, y, (hipStream_t)stream);
+}
+
+int msda_dino_refine_forward_f32(const float *ref, const float *cls, int K, const float *delta_key, const float *delta_obj, int hand0,
+                                 int hand1, long long M, float *out, uint8_t *code, msda_stream_t stream)
+{
+    if (M < 0 || K < 1) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_refine_forward_f32: need M >= 0 and K >= 1");
+    if (M * (K > 42 ? K : 42) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_refine_forward_f32: tensors beyond 2^31 elements");
+    if (M > 0 && (ref == nullptr || cls == nullptr || delta_key == nullptr || delta_obj == nullptr || out == nullptr || code == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_refine_forward_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_dino_refine_fwd(ref, cls, K, delta_key, delta_obj, hand0, hand1, M, out, code, (hipStream_t)stream);
+}
+
+int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const uint8_t *code, long long M, float *grad_key,
+                                  float *grad_obj, msda_stream_t stream)
+{
+    if (M < 0 || M * 42 >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_refine_backward_f32: need 0 <= M and M * 42 < 2^31");
+    if (M > 0 && (grad_out == nullptr || out == nullptr || code == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_refine_backward_f32: null device pointer");
+    msda::begin_call();
+    return msda::launch_dino_refine_bwd(grad_out, out, code, M, grad_key, grad_obj, (hipStream_t)stream);
+}
+
 int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stride, const uint8_t *padding_mask,
                                 long long mask_frame_stride, int N, int H, int W, int C, float *proposals, float *memory_out,
                                 uint8_t *row_mask, msda_stream_t stream)

@@ -168,6 +168,16 @@ int launch_assembly_level_proposals(const float *memory, long long mem_frame_str
 int launch_assembly_select(const float *cls, const float *hand, const float *obj, int N, int S, int K, int obj_first, int obj_last,
                            int left, int right, int64_t *indices, float *refp, hipStream_t stream);
 
+// ---- the DINO decoder's query positions and refinement (msda_dino.hip) ----
+int launch_dino_sine_embed(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t, float *pe,
+                           hipStream_t stream);
+int launch_dino_query_pos(const float *ref, int width, const float *valid_xy, int N, long long M, const float *dim_t, const float *w1,
+                          const float *b1, const float *w2, const float *b2, float *h, float *y, hipStream_t stream);
+int launch_dino_refine_fwd(const float *ref, const float *cls, int K, const float *dkey, const float *dobj, int hand0, int hand1,
+                           long long M, float *out, uint8_t *code, hipStream_t stream);
+int launch_dino_refine_bwd(const float *gout, const float *out, const uint8_t *code, long long M, float *gkey, float *gobj,
+                           hipStream_t stream);
+
 // ---- the Hungarian matchers: cost block + assignment per (prediction set, frame) (msda_matcher.hip) ----
 constexpr int kMatchMaxQueries = 1024;  // queries of a frame (one workgroup, one thread per query)
 constexpr int kMatchMaxTargets = 16;    // targets of a frame (rows of the solved problem, held per thread)

@@ -4,6 +4,8 @@ from .deformable_layers import (DeformableTransformerDecoder, DeformableTransfor
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
 from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
+from .dino_transformer import DeformableTransformerDecoderLayer as DinoDeformableTransformerDecoderLayer
+from .dino_transformer import TransformerDecoder as DinoTransformerDecoder
 from .ms_deform_attn import MSDeformAttn
 from .smoothnet import ArcticSmoother, MotionSmoother, SmoothCriterion, Smoother, SmootherResBlock
 from .swin import (BasicLayer, Joiner, Mlp, PatchEmbed, PatchMerging, PositionEmbeddingSine, SwinTransformer,
@@ -13,6 +15,7 @@ __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTrans
            "DeformableTransformerEncoder", "DeformableTransformerDecoder", "DeformableTransformer",
            "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
            "ArcticDeformableDETR", "AssemblyDeformableDETR",
+           "DinoDeformableTransformerDecoderLayer", "DinoTransformerDecoder",
            "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother", "SmoothCriterion",
            "Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
            "build_swin_transformer", "PositionEmbeddingSine", "Joiner", "build_backbone"]

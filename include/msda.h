@@ -583,6 +583,44 @@ int msda_dino_refine_forward_f32(const float *ref, const float *cls, int K, cons
 int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const uint8_t *code, long long M, float *grad_key,
                                   float *grad_obj, msda_stream_t stream);
 
+/* ---- DINO's contrastive-denoising queries (models/dino/dn_components.py:20-150, prepare_for_cdn) ---------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ * The targets are the matcher's packed form: labels [T] int64, offsets [B + 1] int64 (frame b owns targets offsets[b] ..
+ * offsets[b + 1] - 1), keypoints [T, width] fp32; weight [rows_book, hidden] fp32 is label_enc's table (16-byte aligned).
+ * single_pad (the largest target count of a frame), groups (dn_number after the division of :46-58) and so every shape are
+ * HOST values (:49-58 read them back from the device); pad = 2 * single_pad * groups.
+ *   msda_cdn_supported(hidden, width, rows_book, E)   1 = the kernels take it: hidden a multiple of 4 in 4..1024, width in
+ *       1..64, rows_book >= 1, rows_book * hidden < 2^31, and every draw counter of E = 2 * groups * T flat elements below
+ *       2^32: 2 E (1 + width) < 2^32.
+ *   msda_cdn_prepare_forward_f32   ONE launch writes every element of input_query_label [B, pad, hidden], input_query_key
+ *       [B, pad, width] and noised_labels [B, pad] int32 (:107-123; no memset).  Row (b, r * single_pad + j) with
+ *       j < offsets[b + 1] - offsets[b] holds target t = offsets[b] + j in repetition r of 2 * groups (:67-70, :119-120; even r
+ *       = positive_idx, odd r = negative_idx, :82-85): weight[label'] (:108), inverse_sigmoid(key') (:109, util/misc.py:614-618)
+ *       and label'; the other rows are zero with label -1 (:111-115), as is a row whose offsets or label do not address the
+ *       tables.  Draws (:74-78, :94-103), from the library's counter hash with base = mix(seed[0], 0), flat element
+ *       e = r * T + t: label' = (hash(base + 2e + 1) * num_classes) >> 32 iff hash(base + 2e) < flip_threshold, else the
+ *       label (flip_threshold 0: no draw).  key_noise_scale > 0 (the noise the reference computes at :94-103 and drops,
+ *       :104-105): for column c with k = 2E + 2 (e * width + c): sign = hash(base + k) >> 31 ? +1 : -1, u = (hash(base + k +
+ *       1) >> 8) * 2^-24, part = (u + (r odd ? 1 : 0)) * sign, key' = clamp(key + (part * key) * key_noise_scale, 0, 1), each
+ *       product and sum rounded on its own; key_noise_scale 0: key' = key.  seed: device int64, NULL allowed when nothing is
+ *       drawn.  key_debug (tests; NULL = not written): key' [B, pad, width] before inverse_sigmoid, 0 in padding rows.
+ *   msda_cdn_prepare_backward_f32  ONE launch: grad_weight [rows_book, hidden] (16-byte aligned, every element written)
+ *       = per class c the sum of the rows of grad_label [rows, hidden] whose noised_labels [rows] equal c, summed in an order
+ *       that depends on the labels alone (:108's embedding backward without atomics): bitwise reproducible.
+ * No allocation, no synchronisation, no atomics, capturable in a graph.  Argument errors (MSDA_ERR_ARGUMENT before any launch):
+ * sizes outside msda_cdn_supported, negative sizes, groups or num_classes < 1, num_classes > rows_book, key_noise_scale < 0,
+ * tensors beyond 2^31 elements, draws without a seed, a null or misaligned pointer.  pad == 0: MSDA_OK, no launch. */
+int msda_cdn_supported(int hidden, int width, long long rows_book, long long E);
+int msda_cdn_prepare_forward_f32(const int64_t *labels, const int64_t *offsets, const float *keypoints, const float *weight,
+                                 const long long *seed, int B, long long T, int width, int hidden, long long rows_book,
+                                 int single_pad, int groups, int num_classes, unsigned flip_threshold, float key_noise_scale,
+                                 float *input_query_label, float *input_query_key, int32_t *noised_labels, float *key_debug,
+                                 msda_stream_t stream);
+int msda_cdn_prepare_backward_f32(const float *grad_label, const int32_t *noised_labels, long long rows, int hidden,
+                                  long long rows_book, float *grad_weight, msda_stream_t stream);
+
 /* ---- The Hungarian matchers (models/matcher.py: ArcticMatcher :20-125, AssemblyMatcher :128-230) -------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
  * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.

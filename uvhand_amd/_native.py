@@ -106,6 +106,10 @@ SIGNATURES = {
     "msda_dino_query_pos_forward_f32": "i p i p i l ppppp pp p",
     "msda_dino_refine_forward_f32": "i pp i pp ii l pp p",
     "msda_dino_refine_backward_f32": "i ppp l pp p",
+    # DINO's contrastive-denoising queries
+    "msda_cdn_supported": "i ii ll",
+    "msda_cdn_prepare_forward_f32": "i ppppp i l ii l iii u f pppp p",
+    "msda_cdn_prepare_backward_f32": "i pp l i l p p",
     # the Hungarian matchers
     "msda_match_arctic_f32": "i ppp iiiii ppp l p i ff ppp",
     "msda_match_assembly_f32": "i pp iiiii ppp l i ff ppp",
@@ -1361,6 +1365,59 @@ def dino_refine_backward(grad_out, out, code, want_key=True, want_obj=True):
     _launch(out.device, "msda_dino_refine_backward_f32", "dino_refine_backward", grad_out.data_ptr(), out.data_ptr(), code.data_ptr(),
             code.numel(), gk.data_ptr() if want_key else None, go.data_ptr() if want_obj else None)
     return gk, go
+
+
+# ---- DINO's contrastive-denoising queries (csrc/msda_cdn.hip) --------------------------------------------------------------
+def cdn_supported(hidden, width, rows_book, E):
+    """msda_cdn_supported: hidden a multiple of 4 in 4..1024, width 1..64, every draw counter of E flat elements below 2^32."""
+    return bool((_lib or load()).msda_cdn_supported(int(hidden), int(width), int(rows_book), int(E)))
+
+
+def cdn_flip_threshold(label_noise_ratio):
+    """The 32-bit threshold of the label draw: a label is replaced iff its hash is below min(2^32 - 1, floor(ratio * 0.5 * 2^32))
+    (dn_components.py:76, ``p < label_noise_ratio * 0.5``); 0 = nothing is drawn."""
+    return int(min(4294967295.0, max(0.0, float(label_noise_ratio) * 0.5 * 4294967296.0)))
+
+
+def cdn_prepare_forward(labels, offsets, keypoints, weight, seed, single_pad, groups, num_classes, flip_threshold=0,
+                        key_noise_scale=0.0, key_debug=False):
+    """(input_query_label [B, pad, H], input_query_key [B, pad, W], noised_labels [B, pad] int32[, key' [B, pad, W]]) —
+    msda_cdn_prepare_forward_f32, one launch (none when pad == 0): labels [T] / offsets [B + 1] int64, keypoints [T, W] and
+    weight [rows, H] contiguous fp32 CUDA, seed a one-element int64 CUDA tensor or None when nothing is drawn; single_pad, groups
+    (after the reference's division) and num_classes host ints.  ``key_debug``: also the noised, clamped keys before
+    inverse_sigmoid (tests)."""
+    dev = weight.device
+    if not (_f32_cuda(weight) and weight.dim() == 2 and _f32_cuda(keypoints) and keypoints.dim() == 2 and keypoints.device == dev
+            and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1 and t.device == dev
+                    for t in (labels, offsets))
+            and labels.shape[0] == keypoints.shape[0] and offsets.shape[0] >= 1
+            and (seed is None or (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == dev))):
+        raise RuntimeError("cdn_prepare_forward: expected int64 CUDA labels [T] / offsets [B + 1], contiguous fp32 CUDA keypoints "
+                           "[T, W] and weight [rows, H], and a one-element int64 CUDA seed or None, on one device")
+    B, T, W = offsets.shape[0] - 1, labels.shape[0], keypoints.shape[1]
+    rows_book, H = weight.shape
+    pad = 2 * int(single_pad) * int(groups)
+    out_l = torch.empty((B, pad, H), dtype=torch.float32, device=dev)
+    out_k = torch.empty((B, pad, W), dtype=torch.float32, device=dev)
+    noised = torch.empty((B, pad), dtype=torch.int32, device=dev)
+    dbg = torch.empty((B, pad, W), dtype=torch.float32, device=dev) if key_debug else None
+    _launch(dev, "msda_cdn_prepare_forward_f32", "cdn_prepare_forward", labels.data_ptr(), offsets.data_ptr(), keypoints.data_ptr(),
+            weight.data_ptr(), seed.data_ptr() if seed is not None else None, B, T, W, H, rows_book, int(single_pad), int(groups),
+            int(num_classes), int(flip_threshold), float(key_noise_scale), out_l.data_ptr(), out_k.data_ptr(), noised.data_ptr(),
+            dbg.data_ptr() if key_debug else None)
+    return (out_l, out_k, noised, dbg) if key_debug else (out_l, out_k, noised)
+
+
+def cdn_prepare_backward(grad_label, noised, rows_book):
+    """grad_weight [rows_book, H] of the label embedding — msda_cdn_prepare_backward_f32: one launch, fixed summation order."""
+    if not (_f32_cuda(grad_label) and grad_label.dim() == 3 and noised.is_cuda and noised.dtype == torch.int32
+            and noised.is_contiguous() and tuple(noised.shape) == tuple(grad_label.shape[:2]) and noised.device == grad_label.device):
+        raise RuntimeError("cdn_prepare_backward: expected contiguous fp32 CUDA grad_label [B, pad, H] and int32 noised_labels [B, pad]")
+    H = grad_label.shape[2]
+    gw = torch.empty((int(rows_book), H), dtype=torch.float32, device=grad_label.device)
+    _launch(grad_label.device, "msda_cdn_prepare_backward_f32", "cdn_prepare_backward", grad_label.data_ptr(), noised.data_ptr(),
+            noised.numel(), H, int(rows_book), gw.data_ptr())
+    return gw
 
 
 # ---- the Hungarian matchers (csrc/msda_matcher.hip) ----------------------------------------------------------------------

@@ -988,6 +988,59 @@ int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const
     return msda::launch_dino_refine_bwd(grad_out, out, code, M, grad_key, grad_obj, (hipStream_t)stream);
 }
 
+/* ---- DINO's contrastive-denoising queries (msda_cdn.hip) ---- */
+int msda_cdn_supported(int hidden, int width, long long rows_book, long long E)
+{
+    if (hidden < 4 || hidden > 1024 || (hidden & 3) || width < 1 || width > 64 || rows_book < 1 || E < 0) return 0;
+    if (E >= (1LL << 31) || 2 * E * (1 + (long long)width) >= (1LL << 32)) return 0;      /* the last key-noise counter */
+    return rows_book * hidden < (1LL << 31);
+}
+
+int msda_cdn_prepare_forward_f32(const int64_t *labels, const int64_t *offsets, const float *keypoints, const float *weight,
+                                 const long long *seed, int B, long long T, int width, int hidden, long long rows_book,
+                                 int single_pad, int groups, int num_classes, unsigned flip_threshold, float key_noise_scale,
+                                 float *input_query_label, float *input_query_key, int32_t *noised_labels, float *key_debug,
+                                 msda_stream_t stream)
+{
+    if (B < 0 || T < 0 || single_pad < 0 || groups < 1 || num_classes < 1 || !(key_noise_scale >= 0.f))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: need B, T, single_pad >= 0, groups, num_classes >= 1 "
+                                                  "and key_noise_scale >= 0");
+    if ((long long)groups * T >= (1LL << 30) || !msda_cdn_supported(hidden, width, rows_book, 2LL * groups * T))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: outside msda_cdn_supported (hidden a multiple of 4 in "
+                                                  "4..1024, width 1..64, counters below 2^32)");
+    if (num_classes > rows_book)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: num_classes exceeds the embedding's rows");
+    const long long rows = 2LL * single_pad * groups * B;
+    if (2LL * single_pad * groups >= (1LL << 31) || rows * (hidden > width ? hidden : width) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: tensors beyond 2^31 elements");
+    if (rows == 0) return MSDA_OK;
+    if (offsets == nullptr || weight == nullptr || input_query_label == nullptr || input_query_key == nullptr ||
+        noised_labels == nullptr || (T > 0 && (labels == nullptr || keypoints == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: null device pointer");
+    if ((flip_threshold != 0u || key_noise_scale > 0.f) && seed == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: draws need a seed");
+    if (misaligned16(weight) || misaligned16(input_query_label))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_forward_f32: weight and input_query_label must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_cdn_prepare_fwd(labels, offsets, keypoints, weight, seed, B, T, width, hidden, rows_book, single_pad, groups,
+                                        num_classes, flip_threshold, key_noise_scale, input_query_label, input_query_key,
+                                        noised_labels, key_debug, (hipStream_t)stream);
+}
+
+int msda_cdn_prepare_backward_f32(const float *grad_label, const int32_t *noised_labels, long long rows, int hidden,
+                                  long long rows_book, float *grad_weight, msda_stream_t stream)
+{
+    if (rows < 0 || !msda_cdn_supported(hidden, 1, rows_book, 0) || rows * hidden >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_backward_f32: need rows >= 0, hidden a multiple of 4 in 4..1024, "
+                                                  "rows_book >= 1 and tensors below 2^31 elements");
+    if (grad_weight == nullptr || (rows > 0 && (grad_label == nullptr || noised_labels == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_backward_f32: null device pointer");
+    if (misaligned16(grad_label) || misaligned16(grad_weight))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_cdn_prepare_backward_f32: grad_label and grad_weight must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_cdn_prepare_bwd(grad_label, noised_labels, rows, hidden, rows_book, grad_weight, (hipStream_t)stream);
+}
+
 int msda_assembly_proposals_f32(const float *memory, long long memory_frame_stride, const uint8_t *padding_mask,
                                 long long mask_frame_stride, int N, int H, int W, int C, float *proposals, float *memory_out,
                                 uint8_t *row_mask, msda_stream_t stream)

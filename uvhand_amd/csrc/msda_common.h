@@ -94,4 +94,14 @@ __device__ __forceinline__ float4 ld4(const uint16_t *p)
 
 __device__ __forceinline__ float sq(float x) { return x * x; }
 
+// inverse_sigmoid of util/misc.py:614-618 (eps = 1e-5) with torch's NaN-propagating clamp; plain fp32
+__device__ __forceinline__ float inverse_sigmoid_f32(float x)
+{
+    x = x != x ? x : fminf(fmaxf(x, 0.f), 1.f);
+    const float x1 = x != x ? x : fmaxf(x, 1e-5f);
+    const float om = 1.f - x;
+    const float x2 = om != om ? om : fmaxf(om, 1e-5f);
+    return logf(x1 / x2);
+}
+
 }  // namespace msda

@@ -29,15 +29,6 @@ constexpr float kDnTwoPi = 6.283185307179586f; // 2 * math.pi as torch casts it 
 
 __device__ __forceinline__ float dn_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
-__device__ __forceinline__ float dn_inverse_sigmoid(float x)
-{
-    x = x != x ? x : fminf(fmaxf(x, 0.f), 1.f);
-    const float x1 = x != x ? x : fmaxf(x, 1e-5f);
-    const float om = 1.f - x;
-    const float x2 = om != om ? om : fmaxf(om, 1e-5f);
-    return logf(x1 / x2);
-}
-
 // (sin, cos) of a / d0 and of a / d1: table columns 4q .. 4q+3 of one axis
 __device__ __forceinline__ float4 dn_quad(float a, float d0, float d1)
 {
@@ -232,7 +223,7 @@ __global__ __launch_bounds__(kDnBlock) void dino_refine_fwd_kernel(
     for (int t = tid; t < rows * 42; t += kDnBlock) {
         const long long o = r0 * 42 + t;
         const int k = cd[t / 42];
-        float u = dn_inverse_sigmoid(ref[o]);
+        float u = inverse_sigmoid_f32(ref[o]);
         if (k == 1) u += dobj[o];
         if (k == 2) u += dkey[o];
         out[o] = dn_sigmoid(u) * 2.f - 1.f;

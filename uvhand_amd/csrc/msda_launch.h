@@ -178,6 +178,14 @@ int launch_dino_refine_fwd(const float *ref, const float *cls, int K, const floa
 int launch_dino_refine_bwd(const float *gout, const float *out, const uint8_t *code, long long M, float *gkey, float *gobj,
                            hipStream_t stream);
 
+// ---- DINO's contrastive-denoising queries and the label embedding's gradient (msda_cdn.hip); checked arguments ----
+int launch_cdn_prepare_fwd(const int64_t *labels, const int64_t *offsets, const float *keys, const float *weight, const long long *seed,
+                           int B, long long T, int W, int H, long long rows_book, int single_pad, int groups, int num_classes,
+                           unsigned thr, float scale, float *out_label, float *out_key, int32_t *noised, float *key_debug,
+                           hipStream_t stream);
+int launch_cdn_prepare_bwd(const float *grad_label, const int32_t *noised, long long rows, int H, long long rows_book, float *grad_weight,
+                           hipStream_t stream);
+
 // ---- the Hungarian matchers: cost block + assignment per (prediction set, frame) (msda_matcher.hip) ----
 constexpr int kMatchMaxQueries = 1024;  // queries of a frame (one workgroup, one thread per query)
 constexpr int kMatchMaxTargets = 16;    // targets of a frame (rows of the solved problem, held per thread)

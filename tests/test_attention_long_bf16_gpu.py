@@ -246,7 +246,7 @@ def test_mixed_dtypes_raise_before_any_launch():
 
 
 def test_masked_bf16_node_captures_in_a_graph():
-    from uvhand_amd.functions.attention_func import _Attn32xFn
+    from uvhand_amd.functions.attention_func import _AttnFn
     from uvhand_amd.utils import cdn_attention_mask
     L, N, heads = 200, 2, 2
     E = heads * 32
@@ -257,7 +257,7 @@ def test_masked_bf16_node_captures_in_a_graph():
     m = cdn_attention_mask(3, 4, L - 24, "cuda")
 
     def step():
-        out = _Attn32xFn.apply(qk, v, m, heads, 0.0)
+        out = _AttnFn.apply("attn32x", qk, v, m, heads, 0.0)
         return (out,) + torch.autograd.grad(out, (qk, v), go)
 
     s = torch.cuda.Stream()

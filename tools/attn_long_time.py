@@ -5,7 +5,7 @@ cdn_attention_mask(3, 33, 900), and L = 900 unmasked (the 900-query evaluation s
 N = 32 frames, 8 heads, E = 256, p = 0.1, fp32, training mode.
 
 Routes: `module` (nn.MultiheadAttention itself: what a masked or long input gets without the streaming core) and `long_core`
-(the _Attn32xFn node on csrc/msda_attn_long.hip: the mask routes it at 1098, MSDA_ATTN_LONG=1 at 900), three runs of each,
+(the _AttnFn node on csrc/msda_attn_long.hip: the mask routes it at 1098, MSDA_ATTN_LONG=1 at 900), three runs of each,
 interleaved, in one process.  Per run: wall ms per step (host clock around the steps, ending in a device synchronise), GPU ms
 from device events, host syncs per step (torch.cuda.set_sync_debug_mode("warn")), kernels per step (torch.profiler) and the
 step's peak memory above what was allocated before it; then one `summary` row per route and shape with the median of the three

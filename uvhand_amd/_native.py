@@ -798,45 +798,6 @@ def attn32_supported(Lq, Lk, head_dim):
     return bool(lib.msda_attn32_supported(int(Lq), int(Lk), int(head_dim)))
 
 
-def attn32_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None):
-    """msda_attn32_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale)) v per (batch, head), head_dim 32.
-    q [Lq, N, E], k / v [Lk, N, E] (sequence first, as nn.MultiheadAttention projects them; column-block views allowed);
-    seed: a one-element int64 CUDA tensor (required when dropout_p > 0).  Returns (out [Lq, N, E], lse [N*heads, Lq]).
-    bfloat16 q, k, v take msda_attn32_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
-    Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
-    dt = _attn_dtype(q)
-    qv, kv, vv = _attn_view(q, "q", heads, dt), _attn_view(k, "k", heads, dt), _attn_view(v, "v", heads, dt)
-    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
-        raise RuntimeError("attn32_forward: dropout needs a one-element int64 CUDA seed tensor")
-    out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
-    lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
-    ov = _attn_view(out, "out", heads, dt)
-    _launch(q.device, "msda_attn32_forward_bf16" if dt == torch.bfloat16 else "msda_attn32_forward_f32", "attn32_forward",
-            *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *ov,
-            lse.data_ptr())
-    return out, lse
-
-
-def attn32_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, grad_q=None, grad_k=None, grad_v=None):
-    """msda_attn32_backward_f32: gradients of q, k, v (written into grad_q / grad_k / grad_v when given — views like the inputs,
-    e.g. the two column blocks of one packed [L, N, 2E] tensor — else into new contiguous tensors).  bfloat16 q takes
-    msda_attn32_backward_bf16: every tensor but lse bfloat16, gradients included."""
-    Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
-    dt = _attn_dtype(q)
-    grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
-    grad_k = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_k is None else grad_k
-    grad_v = torch.empty((Lk, N, heads * 32), dtype=dt, device=q.device) if grad_v is None else grad_v
-    if grad_out.stride(2) != 1:
-        grad_out = grad_out.contiguous()
-    views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
-    gov = _attn_view(grad_out, "grad_out", heads, dt)
-    gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
-    _launch(q.device, "msda_attn32_backward_bf16" if dt == torch.bfloat16 else "msda_attn32_backward_f32", "attn32_backward",
-            *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale),
-            float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, *gviews[0], *gviews[1], *gviews[2])
-    return grad_q, grad_k, grad_v
-
-
 def attn32x_supported(Lq, Lk, head_dim):
     lib = _lib or load()
     return bool(lib.msda_attn32x_supported(int(Lq), int(Lk), int(head_dim)))
@@ -855,31 +816,33 @@ def _attn_mask_bytes(mask, Lq, Lk, who):
     return mbytes, mbytes.data_ptr(), (mbytes.stride(0) if Lq > 1 else max(Lk, mbytes.stride(0)))
 
 
-def attn32x_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None, mask=None):
-    """msda_attn32x_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale + M)) v per (batch, head), head_dim 32, float32,
-    1 <= Lq, Lk <= 2048.  Arguments as attn32_forward; mask: a 2-D bool CUDA tensor [Lq, Lk] shared by every batch entry and
-    head, True = the key is hidden (passed as its bytes), or None.  Returns (out [Lq, N, E], lse [N*heads, Lq]).
-    bfloat16 q, k, v take msda_attn32x_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
+def _attn_entry(family, who, dt, Lq, Lk, dropout_p, seed, mask):
+    """The C entry of a family ("attn32": resident, "attn32x": streaming, with a mask) and operand type, and its seed (and mask)
+    arguments after the seed check; the last item keeps the mask's bytes alive for the call."""
+    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise RuntimeError("%s: dropout needs a one-element int64 CUDA seed tensor" % who)
+    tail, mkeep = [seed.data_ptr() if dropout_p > 0 else None], None
+    if family == "attn32x":
+        mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, who)
+        tail += [mptr, msq]
+    return "msda_%s_%s" % (who, "bf16" if dt == torch.bfloat16 else "f32"), tail, mkeep
+
+
+def _attn_forward(family, q, k, v, heads, scale, dropout_p, seed, mask=None):
+    who = family + "_forward"
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
     dt = _attn_dtype(q)
     qv, kv, vv = _attn_view(q, "q", heads, dt), _attn_view(k, "k", heads, dt), _attn_view(v, "v", heads, dt)
-    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
-        raise RuntimeError("attn32x_forward: dropout needs a one-element int64 CUDA seed tensor")
-    mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_forward")
+    entry, tail, mkeep = _attn_entry(family, who, dt, Lq, Lk, dropout_p, seed, mask)
     out = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device)
     lse = torch.empty((N * heads, Lq), dtype=torch.float32, device=q.device)
     ov = _attn_view(out, "out", heads, dt)
-    _launch(q.device, "msda_attn32x_forward_bf16" if dt == torch.bfloat16 else "msda_attn32x_forward_f32", "attn32x_forward",
-            *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), seed.data_ptr() if dropout_p > 0 else None, mptr, msq,
-            *ov, lse.data_ptr())
+    _launch(q.device, entry, who, *qv, *kv, *vv, N, heads, Lq, Lk, float(scale), float(dropout_p), *tail, *ov, lse.data_ptr())
     return out, lse
 
 
-def attn32x_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, mask=None, grad_q=None, grad_k=None,
-                     grad_v=None):
-    """msda_attn32x_backward_f32: gradients of q, k, v under the forward's mask and seed (written into grad_q / grad_k / grad_v
-    when given — views like the inputs — else into new contiguous tensors).  bfloat16 q takes msda_attn32x_backward_bf16: every
-    tensor but lse bfloat16, gradients included."""
+def _attn_backward(family, q, k, v, out, lse, grad_out, heads, scale, dropout_p, seed, mask, grad_q, grad_k, grad_v):
+    who = family + "_backward"
     Lq, N, Lk = q.shape[0], q.shape[1], k.shape[0]
     dt = _attn_dtype(q)
     grad_q = torch.empty((Lq, N, heads * 32), dtype=dt, device=q.device) if grad_q is None else grad_q
@@ -890,13 +853,41 @@ def attn32x_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, s
     views = [_attn_view(t, nm, heads, dt) for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"))]
     gov = _attn_view(grad_out, "grad_out", heads, dt)
     gviews = [_attn_view(t, nm, heads, dt) for t, nm in ((grad_q, "grad_q"), (grad_k, "grad_k"), (grad_v, "grad_v"))]
-    if dropout_p > 0 and not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
-        raise RuntimeError("attn32x_backward: dropout needs a one-element int64 CUDA seed tensor")
-    mkeep, mptr, msq = _attn_mask_bytes(mask, Lq, Lk, "attn32x_backward")
-    _launch(q.device, "msda_attn32x_backward_bf16" if dt == torch.bfloat16 else "msda_attn32x_backward_f32", "attn32x_backward",
-            *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale), float(dropout_p),
-            seed.data_ptr() if dropout_p > 0 else None, mptr, msq, *gviews[0], *gviews[1], *gviews[2])
+    entry, tail, mkeep = _attn_entry(family, who, dt, Lq, Lk, dropout_p, seed, mask)
+    _launch(q.device, entry, who, *views[0], *views[1], *views[2], *views[3], lse.data_ptr(), *gov, N, heads, Lq, Lk, float(scale),
+            float(dropout_p), *tail, *gviews[0], *gviews[1], *gviews[2])
     return grad_q, grad_k, grad_v
+
+
+def attn32_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None):
+    """msda_attn32_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale)) v per (batch, head), head_dim 32.
+    q [Lq, N, E], k / v [Lk, N, E] (sequence first, as nn.MultiheadAttention projects them; column-block views allowed);
+    seed: a one-element int64 CUDA tensor (required when dropout_p > 0).  Returns (out [Lq, N, E], lse [N*heads, Lq]).
+    bfloat16 q, k, v take msda_attn32_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
+    return _attn_forward("attn32", q, k, v, heads, scale, dropout_p, seed)
+
+
+def attn32_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, grad_q=None, grad_k=None, grad_v=None):
+    """msda_attn32_backward_f32: gradients of q, k, v (written into grad_q / grad_k / grad_v when given — views like the inputs,
+    e.g. the two column blocks of one packed [L, N, 2E] tensor — else into new contiguous tensors).  bfloat16 q takes
+    msda_attn32_backward_bf16: every tensor but lse bfloat16, gradients included."""
+    return _attn_backward("attn32", q, k, v, out, lse, grad_out, heads, scale, dropout_p, seed, None, grad_q, grad_k, grad_v)
+
+
+def attn32x_forward(q, k, v, heads, scale, dropout_p=0.0, seed=None, mask=None):
+    """msda_attn32x_forward_f32 (include/msda.h): dropout(softmax(q k^T * scale + M)) v per (batch, head), head_dim 32, float32,
+    1 <= Lq, Lk <= 2048.  Arguments as attn32_forward; mask: a 2-D bool CUDA tensor [Lq, Lk] shared by every batch entry and
+    head, True = the key is hidden (passed as its bytes), or None.  Returns (out [Lq, N, E], lse [N*heads, Lq]).
+    bfloat16 q, k, v take msda_attn32x_forward_bf16 (out bfloat16, lse float32; the same dropout mask for the same seed)."""
+    return _attn_forward("attn32x", q, k, v, heads, scale, dropout_p, seed, mask)
+
+
+def attn32x_backward(q, k, v, out, lse, grad_out, heads, scale, dropout_p=0.0, seed=None, mask=None, grad_q=None, grad_k=None,
+                     grad_v=None):
+    """msda_attn32x_backward_f32: gradients of q, k, v under the forward's mask and seed (written into grad_q / grad_k / grad_v
+    when given — views like the inputs — else into new contiguous tensors).  bfloat16 q takes msda_attn32x_backward_bf16: every
+    tensor but lse bfloat16, gradients included."""
+    return _attn_backward("attn32x", q, k, v, out, lse, grad_out, heads, scale, dropout_p, seed, mask, grad_q, grad_k, grad_v)
 
 
 def add_layernorm_supported(x, residual, weight, bias):

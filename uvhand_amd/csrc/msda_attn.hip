@@ -16,6 +16,7 @@
 // safe under HIP-graph capture).  This is the kernel's own random stream, not nn.functional.dropout's.
 #include <math.h>
 
+#include "msda_attn_args.h"
 #include "msda_attn_tile.h"
 #include "msda_common.h"
 #include "msda_launch.h"
@@ -26,8 +27,6 @@ namespace msda {
 #define MSDA_AT_WAVES 12
 #endif
 constexpr int kAtWaves = MSDA_AT_WAVES, kAtBlock = kAtWaves * 64, kAtMaxTiles = 20, kAtMaxLen = 16 * kAtMaxTiles;
-
-struct AtView { float *p; long long sn, sl; };          // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
 
 // Dropout: 32 bits per (pair, query, key) from at_hash of the counter (query << 16) + key + at_mix(seed, pair) (msda_attn_tile.h)
 
@@ -55,26 +54,17 @@ __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, lo
     }
 }
 
-struct AtArgs {
-    AtView q, k, v, o, go, gq, gk, gv;
-    float *lse;                         // [N*H][Lq]
-    const unsigned long long *seed;     // device; null when thresh == 0
-    int H, Lq, Lk, halves;
-    float scale, scale2, keep_scale;    // scale2 = scale * log2(e): scores are kept in base 2; keep_scale = 1 / (1 - p)
-    unsigned thresh;                    // keep iff hash >= thresh (p * 2^32; 0: no dropout)
-};
-
-__global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AtArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AttnArgs<float> a)
 {
     extern __shared__ __attribute__((aligned(16))) float at_smem[];
     const int Lkp = (a.Lk + 15) & ~15, ntk = Lkp >> 4, ntq = (a.Lq + 15) >> 4;
     float *Ks = at_smem, *Vs = at_smem + Lkp * kAtRow;
-    const int pair = (int)blockIdx.x / a.halves, part = (int)blockIdx.x % a.halves, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, part = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     at_load_rows2(Ks, a.k.p + n * a.k.sn + h * 32, a.k.sl, Vs, a.v.p + n * a.v.sn + h * 32, a.v.sl, a.Lk, Lkp);
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
-    const int per = (ntq + a.halves - 1) / a.halves, t_end = min(ntq, (part + 1) * per);
+    const int per = (ntq + a.wpp - 1) / a.wpp, t_end = min(ntq, (part + 1) * per);
     const float *qp = a.q.p + n * a.q.sn + h * 32;
     float *op = a.o.p + n * a.o.sn + h * 32;
     for (int tq = part * per + wave; tq < t_end; tq += kAtWaves) {
@@ -137,12 +127,12 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AtArgs a)
 }
 
 // dK, dV: a wavefront owns 16 keys and walks the query tiles
-__global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<float> a)
 {
     extern __shared__ __attribute__((aligned(16))) float at_smem[];
     const int Lqp = (a.Lq + 15) & ~15, ntq = Lqp >> 4, ntk = (a.Lk + 15) >> 4;
     float *Qs = at_smem, *Gs = at_smem + Lqp * kAtRow, *lse_s = Gs + Lqp * kAtRow, *del_s = lse_s + Lqp;
-    const int pair = (int)blockIdx.x / a.halves, part = (int)blockIdx.x % a.halves, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, part = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     at_load_rows2(Qs, a.q.p + n * a.q.sn + h * 32, a.q.sl, Gs, a.go.p + n * a.go.sn + h * 32, a.go.sl, a.Lq, Lqp);
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     __syncthreads();
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
-    const int per = (ntk + a.halves - 1) / a.halves, t_end = min(ntk, (part + 1) * per);
+    const int per = (ntk + a.wpp - 1) / a.wpp, t_end = min(ntk, (part + 1) * per);
     for (int tk = part * per + wave; tk < t_end; tk += kAtWaves) {
         const int key = tk * 16 + c;
         const bool kok = key < a.Lk;
@@ -211,17 +201,17 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AtArgs a)
 }
 
 // dQ: a wavefront owns 16 queries and walks the key tiles (S^T tiles, as the forward)
-__global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_kernel(const AtArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_kernel(const AttnArgs<float> a)
 {
     extern __shared__ __attribute__((aligned(16))) float at_smem[];
     const int Lkp = (a.Lk + 15) & ~15, ntk = Lkp >> 4, ntq = (a.Lq + 15) >> 4;
     float *Ks = at_smem, *Vs = at_smem + Lkp * kAtRow;
-    const int pair = (int)blockIdx.x / a.halves, part = (int)blockIdx.x % a.halves, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, part = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     at_load_rows2(Ks, a.k.p + n * a.k.sn + h * 32, a.k.sl, Vs, a.v.p + n * a.v.sn + h * 32, a.v.sl, a.Lk, Lkp);
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
-    const int per = (ntq + a.halves - 1) / a.halves, t_end = min(ntq, (part + 1) * per);
+    const int per = (ntq + a.wpp - 1) / a.wpp, t_end = min(ntq, (part + 1) * per);
     for (int tq = part * per + wave; tq < t_end; tq += kAtWaves) {
         const int qi = tq * 16 + c;
         const bool qok = qi < a.Lq;
@@ -274,11 +264,6 @@ static int at_allow_lds(const void *fn, size_t bytes)
     return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
 }
 
-static bool at_view_ok(const AtView &v)
-{
-    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 3) == 0 && (v.sl & 3) == 0;
-}
-
 
 // ---- bf16 operands (msda_attn32_*_bf16) ------------------------------------------------------------------------------------------
 // The same three kernels and the same work split with q, k, v, out, dO and the gradients in bf16 and every product on
@@ -288,7 +273,7 @@ static bool at_view_ok(const AtView &v)
 // ([rows][40]: 80-byte rows, 16-byte aligned) and are read two ways: a row (8 channels of one key / query) with one
 // ds_read_b128 as the operand of the products over channels, and transposed (4 keys / queries of one channel) with
 // ds_read_b64_tr_b16 as the operand of the products over keys / queries.  Every kernel keeps its loops wave-uniform: the
-// transposed read needs all 64 lanes active.  LDS <= 2 * 320 * 80 B + 2 * 320 * 4 B = 53.8 KB: no opt-in.
+// transposed read needs all 64 lanes active.  LDS <= 2 * 320 * 80 B + 2 * 320 * 4 B = 53.8 KB: at_allow_lds has nothing to ask for.
 // The row and transposed reads and the relabelling of the score-tile pairs: msda_attn_tile.h.
 // Padding: rows up to a multiple of 32 are zero in LDS; padding keys get -inf scores / zero probabilities, padding queries
 // an lse of +inf.  The dropout hash takes the real (query, key) indices: the mask is the fp32 kernels' bit for bit.
@@ -316,17 +301,7 @@ __device__ __forceinline__ void ab_load_rows2(uint16_t *dst0, const uint16_t *sr
     }
 }
 
-struct AbView { uint16_t *p; long long sn, sl; };
-struct AbArgs {
-    AbView q, k, v, o, go, gq, gk, gv;
-    float *lse;
-    const unsigned long long *seed;
-    int H, Lq, Lk;
-    float scale, scale2, keep_scale;
-    unsigned thresh;
-};
-
-__global__ __launch_bounds__(kAtBlock) void attn32_fwd_bf16_kernel(const AbArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_fwd_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
     const int Lkp = (a.Lk + 31) & ~31, npair = Lkp >> 5, ntq = (a.Lq + 15) >> 4;
@@ -397,7 +372,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_bf16_kernel(const AbArgs 
 }
 
 // dK, dV: a wavefront owns 16 keys and walks the query pairs
-__global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_bf16_kernel(const AbArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
     const int Lqp = (a.Lq + 31) & ~31, npair = Lqp >> 5, ntk = (a.Lk + 15) >> 4;
@@ -468,7 +443,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_bf16_kernel(const AbAr
 }
 
 // dQ: a wavefront owns 16 queries and walks the key pairs
-__global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_bf16_kernel(const AbArgs a)
+__global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t ab_smem[];
     const int Lkp = (a.Lk + 31) & ~31, npair = Lkp >> 5, ntq = (a.Lq + 15) >> 4;
@@ -521,17 +496,9 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_bf16_kernel(const AbArg
     }
 }
 
-static bool ab_view_ok(const AbView &v)
-{
-    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 7) == 0 && (v.sl & 7) == 0;
-}
-
 }  // namespace msda
 
-using msda::AtArgs;
-using msda::AtView;
-using msda::AbArgs;
-using msda::AbView;
+using msda::attn_view;
 
 extern "C" {
 
@@ -540,33 +507,23 @@ int msda_attn32_supported(int Lq, int Lk, int head_dim)
     return head_dim == 32 && Lq >= 1 && Lk >= 1 && Lq <= msda::kAtMaxLen && Lk <= msda::kAtMaxLen;
 }
 
-static int at_fill(AtArgs &a, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p, const unsigned long long *seed)
-{
-    if (N <= 0 || H <= 0 || !msda_attn32_supported(Lq, Lk, 32)) return msda::set_error(MSDA_ERR_ARGUMENT, who);
-    if (!(dropout_p >= 0.f && dropout_p < 1.f) || (dropout_p > 0.f && seed == nullptr)) return msda::set_error(MSDA_ERR_ARGUMENT, who);
-    a.H = H; a.Lq = Lq; a.Lk = Lk; a.halves = msda::tuning_int("MSDA_ATTN_HALVES", 1) == 2 ? 2 : 1; a.scale = scale;
-    a.scale2 = scale * 1.4426950408889634f;
-    a.keep_scale = 1.f / (1.f - dropout_p);
-    a.thresh = dropout_p > 0.f ? (unsigned)fmin(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
-    a.seed = seed;
-    return MSDA_OK;
-}
+// Each entry: check, bind (msda_attn_args.h: every refusal comes before any launch), size the grid and the LDS, launch.
+// One workgroup per pair, or two of the fp32 kernels under MSDA_ATTN_HALVES=2; a row of LDS per key (forward, dQ) or query (dK / dV).
 
 int msda_attn32_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
                             const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
                             float dropout_p, const unsigned long long *seed, float *out, long long o_sn, long long o_sl, float *lse,
                             msda_stream_t stream)
 {
-    AtArgs a{};
-    if (int rc = at_fill(a, "msda_attn32_forward_f32: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq, Lk,
-                         scale, dropout_p, seed)) return rc;
-    a.q = AtView{const_cast<float *>(q), q_sn, q_sl}; a.k = AtView{const_cast<float *>(k), k_sn, k_sl};
-    a.v = AtView{const_cast<float *>(v), v_sn, v_sl}; a.o = AtView{out, o_sn, o_sl}; a.lse = lse;
-    if (!msda::at_view_ok(a.q) || !msda::at_view_ok(a.k) || !msda::at_view_ok(a.v) || !msda::at_view_ok(a.o) || lse == nullptr)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_forward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
+    const char *who = "msda_attn32_forward_f32";
+    msda::AttnArgs<float> a{};
+    const int halves = msda::tuning_int("MSDA_ATTN_HALVES", 1) == 2 ? 2 : 1;
+    if (int rc = msda::attn_check(a, who, msda::kAtMaxLen, N, H, Lq, Lk, halves, scale, dropout_p, seed, nullptr, 0)) return rc;
+    if (int rc = msda::attn_bind_forward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                         attn_view(out, o_sn, o_sl), lse)) return rc;
     const size_t lds = (size_t)2 * ((Lk + 15) & ~15) * msda::kAtRow * sizeof(float);
     if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_fwd_kernel), lds)) return rc;
-    hipLaunchKernelGGL(msda::attn32_fwd_kernel, dim3((unsigned)(N * H * a.halves)), dim3(msda::kAtBlock), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(msda::attn32_fwd_kernel, dim3((unsigned)(N * H * a.wpp)), dim3(msda::kAtBlock), lds, (hipStream_t)stream, a);
     return msda::check_launch("msda attention forward (head_dim 32)");
 }
 
@@ -577,51 +534,38 @@ int msda_attn32_backward_f32(const float *q, long long q_sn, long long q_sl, con
                              long long gq_sl, float *grad_k, long long gk_sn, long long gk_sl, float *grad_v, long long gv_sn,
                              long long gv_sl, msda_stream_t stream)
 {
-    AtArgs a{};
-    if (int rc = at_fill(a, "msda_attn32_backward_f32: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq, Lk,
-                         scale, dropout_p, seed)) return rc;
-    a.q = AtView{const_cast<float *>(q), q_sn, q_sl}; a.k = AtView{const_cast<float *>(k), k_sn, k_sl};
-    a.v = AtView{const_cast<float *>(v), v_sn, v_sl}; a.o = AtView{const_cast<float *>(out), o_sn, o_sl};
-    a.go = AtView{const_cast<float *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
-    a.gq = AtView{grad_q, gq_sn, gq_sl}; a.gk = AtView{grad_k, gk_sn, gk_sl}; a.gv = AtView{grad_v, gv_sn, gv_sl};
-    for (const AtView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
-        if (!msda::at_view_ok(*w))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
-    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_f32: lse required");
+    const char *who = "msda_attn32_backward_f32";
+    msda::AttnArgs<float> a{};
+    const int halves = msda::tuning_int("MSDA_ATTN_HALVES", 1) == 2 ? 2 : 1;
+    if (int rc = msda::attn_check(a, who, msda::kAtMaxLen, N, H, Lq, Lk, halves, scale, dropout_p, seed, nullptr, 0)) return rc;
+    if (int rc = msda::attn_bind_backward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                          attn_view(out, o_sn, o_sl), lse, attn_view(grad_out, go_sn, go_sl),
+                                          attn_view(grad_q, gq_sn, gq_sl), attn_view(grad_k, gk_sn, gk_sl),
+                                          attn_view(grad_v, gv_sn, gv_sl))) return rc;
     const int Lqp = (Lq + 15) & ~15, Lkp = (Lk + 15) & ~15;
     const size_t lds_kv = ((size_t)2 * Lqp * msda::kAtRow + 2 * Lqp) * sizeof(float), lds_q = (size_t)2 * Lkp * msda::kAtRow * sizeof(float);
     if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_kv_kernel), lds_kv)) return rc;
     if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_q_kernel), lds_q)) return rc;
-    const dim3 grid((unsigned)(N * H * a.halves));
+    const dim3 grid((unsigned)(N * H * a.wpp));
     hipLaunchKernelGGL(msda::attn32_bwd_kv_kernel, grid, dim3(msda::kAtBlock), lds_kv, (hipStream_t)stream, a);
     if (int rc = msda::check_launch("msda attention backward (dK, dV)")) return rc;
     hipLaunchKernelGGL(msda::attn32_bwd_q_kernel, grid, dim3(msda::kAtBlock), lds_q, (hipStream_t)stream, a);
     return msda::check_launch("msda attention backward (dQ)");
 }
 
-// bf16 operands: the same checks (all of them before any launch), the fp32 entries' random stream
-static int ab_fill(AbArgs &a, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p, const unsigned long long *seed)
-{
-    AtArgs t{};
-    if (int rc = at_fill(t, who, N, H, Lq, Lk, scale, dropout_p, seed)) return rc;
-    a.H = t.H; a.Lq = t.Lq; a.Lk = t.Lk; a.scale = t.scale; a.scale2 = t.scale2; a.keep_scale = t.keep_scale; a.thresh = t.thresh;
-    a.seed = t.seed;
-    return MSDA_OK;
-}
-
+// bf16 operands: the same checks, the fp32 entries' random stream; one workgroup per pair, rows padded to a multiple of 32
 int msda_attn32_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
                              const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
                              float dropout_p, const unsigned long long *seed, uint16_t *out, long long o_sn, long long o_sl,
                              float *lse, msda_stream_t stream)
 {
-    AbArgs a{};
-    if (int rc = ab_fill(a, "msda_attn32_forward_bf16: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq,
-                         Lk, scale, dropout_p, seed)) return rc;
-    a.q = AbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AbView{const_cast<uint16_t *>(k), k_sn, k_sl};
-    a.v = AbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AbView{out, o_sn, o_sl}; a.lse = lse;
-    if (!msda::ab_view_ok(a.q) || !msda::ab_view_ok(a.k) || !msda::ab_view_ok(a.v) || !msda::ab_view_ok(a.o) || lse == nullptr)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_forward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
+    const char *who = "msda_attn32_forward_bf16";
+    msda::AttnArgs<uint16_t> a{};
+    if (int rc = msda::attn_check(a, who, msda::kAtMaxLen, N, H, Lq, Lk, 1, scale, dropout_p, seed, nullptr, 0)) return rc;
+    if (int rc = msda::attn_bind_forward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                         attn_view(out, o_sn, o_sl), lse)) return rc;
     const size_t lds = (size_t)2 * ((Lk + 31) & ~31) * msda::kAbRow * sizeof(uint16_t);
+    if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_fwd_bf16_kernel), lds)) return rc;
     hipLaunchKernelGGL(msda::attn32_fwd_bf16_kernel, dim3((unsigned)(N * H)), dim3(msda::kAtBlock), lds, (hipStream_t)stream, a);
     return msda::check_launch("msda attention forward (head_dim 32, bf16)");
 }
@@ -633,20 +577,18 @@ int msda_attn32_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl,
                               long long gq_sn, long long gq_sl, uint16_t *grad_k, long long gk_sn, long long gk_sl,
                               uint16_t *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream)
 {
-    AbArgs a{};
-    if (int rc = ab_fill(a, "msda_attn32_backward_bf16: head_dim 32, 1 <= Lq, Lk <= 320, 0 <= p < 1 (seed required for p > 0)", N, H, Lq,
-                         Lk, scale, dropout_p, seed)) return rc;
-    a.q = AbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AbView{const_cast<uint16_t *>(k), k_sn, k_sl};
-    a.v = AbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AbView{const_cast<uint16_t *>(out), o_sn, o_sl};
-    a.go = AbView{const_cast<uint16_t *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
-    a.gq = AbView{grad_q, gq_sn, gq_sl}; a.gk = AbView{grad_k, gk_sn, gk_sl}; a.gv = AbView{grad_v, gv_sn, gv_sl};
-    for (const AbView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
-        if (!msda::ab_view_ok(*w))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
-    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32_backward_bf16: lse required");
+    const char *who = "msda_attn32_backward_bf16";
+    msda::AttnArgs<uint16_t> a{};
+    if (int rc = msda::attn_check(a, who, msda::kAtMaxLen, N, H, Lq, Lk, 1, scale, dropout_p, seed, nullptr, 0)) return rc;
+    if (int rc = msda::attn_bind_backward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                          attn_view(out, o_sn, o_sl), lse, attn_view(grad_out, go_sn, go_sl),
+                                          attn_view(grad_q, gq_sn, gq_sl), attn_view(grad_k, gk_sn, gk_sl),
+                                          attn_view(grad_v, gv_sn, gv_sl))) return rc;
     const int Lqp = (Lq + 31) & ~31, Lkp = (Lk + 31) & ~31;
     const size_t lds_kv = (size_t)2 * Lqp * msda::kAbRow * sizeof(uint16_t) + (size_t)2 * Lqp * sizeof(float);
     const size_t lds_q = (size_t)2 * Lkp * msda::kAbRow * sizeof(uint16_t);
+    if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_kv_bf16_kernel), lds_kv)) return rc;
+    if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_q_bf16_kernel), lds_q)) return rc;
     const dim3 grid((unsigned)(N * H));
     hipLaunchKernelGGL(msda::attn32_bwd_kv_bf16_kernel, grid, dim3(msda::kAtBlock), lds_kv, (hipStream_t)stream, a);
     if (int rc = msda::check_launch("msda attention backward (dK, dV; bf16)")) return rc;

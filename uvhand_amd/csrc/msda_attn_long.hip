@@ -29,9 +29,9 @@
 // Dropout: msda_attn.hip's hash and counter — at_hash((query << 16) + key + at_mix(seed, pair)) — seed read from device memory.
 // The bf16 form for bf16 autocast (msda_attn32x_*_bf16) follows the fp32 kernels below.
 #include <math.h>
-#include <stdio.h>
 #include <string.h>
 
+#include "msda_attn_args.h"
 #include "msda_attn_tile.h"
 #include "msda_common.h"
 #include "msda_launch.h"
@@ -41,19 +41,6 @@ namespace msda {
 constexpr int kAxWaves = 8, kAxBlock = kAxWaves * 64, kAxRows = kAxWaves * 16, kAxChunk = 64, kAxTiles = kAxChunk / 16;
 constexpr int kAxMaxLen = 2048;
 static_assert(kAxChunk * 8 == kAxBlock, "one float4 per thread and slice in ax_load_chunk2");
-
-struct AxView { float *p; long long sn, sl; };          // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
-
-struct AxArgs {
-    AxView q, k, v, o, go, gq, gk, gv;
-    float *lse;                         // [N*H][Lq]
-    const unsigned long long *seed;     // device; null when thresh == 0
-    const unsigned char *mask;          // [Lq][Lk] bytes, row stride mask_sq; null: none
-    long long mask_sq;
-    int H, Lq, Lk, nblk;                // nblk: workgroups per pair
-    float scale, scale2, keep_scale;    // as AtArgs (msda_attn.hip)
-    unsigned thresh;
-};
 
 // rows [row0, row0 + kAxChunk) of two [L][32] slices -> dst0 / dst1 [kAxChunk][kAtRow]; rows past L zero
 __device__ __forceinline__ void ax_load_chunk2(float *dst0, const float *src0, long long sl0, float *dst1, const float *src1,
@@ -118,10 +105,10 @@ __device__ __forceinline__ at_f4 ax_dot32(const float *arow, const float4 &b0, c
 
 __device__ __forceinline__ void ax_scale4(float4 &x, float s) { x.x *= s; x.y *= s; x.z *= s; x.w *= s; }
 
-__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_kernel(const AxArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_kernel(const AttnArgs<float> a)
 {
     __shared__ __attribute__((aligned(16))) float Ks[kAxChunk * kAtRow], Vs[kAxChunk * kAtRow];
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int qi = blk * kAxRows + wave * 16 + c;
@@ -192,11 +179,11 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_fwd_kernel(const AxArgs a)
 }
 
 // dK, dV: a wavefront owns 16 keys; the workgroup walks the query chunks
-__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_kernel(const AxArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_kernel(const AttnArgs<float> a)
 {
     __shared__ __attribute__((aligned(16))) float Qs[kAxChunk * kAtRow], Gs[kAxChunk * kAtRow], lse_s[kAxChunk], lsl_s[kAxChunk],
         del_s[kAxChunk];
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int key = blk * kAxRows + wave * 16 + c;
@@ -269,10 +256,10 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_kernel(const AxArgs a
 }
 
 // dQ: a wavefront owns 16 queries; the workgroup walks the key chunks (S^T tiles, as the forward)
-__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_kernel(const AxArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_kernel(const AttnArgs<float> a)
 {
     __shared__ __attribute__((aligned(16))) float Ks[kAxChunk * kAtRow], Vs[kAxChunk * kAtRow];
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int qi = blk * kAxRows + wave * 16 + c;
@@ -326,11 +313,6 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_kernel(const AxArgs a)
     }
 }
 
-static bool ax_view_ok(const AxView &v)
-{
-    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 3) == 0 && (v.sl & 3) == 0;
-}
-
 // LDS above 64 KB would be requested as msda_attn.hip's at_allow_lds does; the three kernels' static 18 KB need no opt-in.
 static_assert((2 * kAxChunk * kAtRow + 3 * kAxChunk) * sizeof(float) <= 64 * 1024, "static LDS");
 
@@ -359,17 +341,6 @@ static_assert((2 * kAxChunk * kAtRow + 3 * kAxChunk) * sizeof(float) <= 64 * 102
 constexpr int kAxbChunk = 128, kAxbPairs = kAxbChunk / 32;
 static_assert(kAxbChunk * 4 == kAxBlock, "one 16-byte load per thread and slice in axb_load_chunk2");
 
-struct AxbView { uint16_t *p; long long sn, sl; };     // element (n, h, l, d) at p + n*sn + h*32 + l*sl + d
-struct AxbArgs {
-    AxbView q, k, v, o, go, gq, gk, gv;
-    float *lse;
-    const unsigned long long *seed;
-    const unsigned char *mask;
-    long long mask_sq;
-    int H, Lq, Lk, nblk;
-    float scale, scale2, keep_scale;
-    unsigned thresh;
-};
 
 // rows [row0, row0 + kAxbChunk) of two [L][32] bf16 slices -> dst0 / dst1 [kAxbChunk][kAbRow]; rows past L zero
 __device__ __forceinline__ void axb_load_chunk2(uint16_t *dst0, const uint16_t *src0, long long sl0, uint16_t *dst1,
@@ -398,10 +369,10 @@ __device__ __forceinline__ float axb_dot8(const at_bf8 &g, const at_bf8 &o)
     return d;
 }
 
-__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_bf16_kernel(const AxbArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_fwd_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     __shared__ __attribute__((aligned(16))) uint16_t Ks[kAxbChunk * kAbRow], Vs[kAxbChunk * kAbRow];
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int qi = blk * kAxRows + wave * 16 + c;
@@ -470,12 +441,12 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_fwd_bf16_kernel(const AxbArg
 }
 
 // dK, dV: a wavefront owns 16 keys; the workgroup walks the query chunks
-__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_bf16_kernel(const AxbArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     __shared__ __attribute__((aligned(16))) uint16_t Qs[kAxbChunk * kAbRow], Gs[kAxbChunk * kAbRow];
     __shared__ __attribute__((aligned(16))) float lse_s[kAxbChunk], lsl_s[kAxbChunk], del_s[kAxbChunk];
     __shared__ __attribute__((aligned(16))) unsigned msk_s[4 * kAxbChunk];  // [32-key part of the block][query]: hidden bits
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int key = blk * kAxRows + wave * 16 + c;
@@ -568,10 +539,10 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_bf16_kernel(const Axb
 }
 
 // dQ: a wavefront owns 16 queries; the workgroup walks the key chunks (S^T tiles, as the forward)
-__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_bf16_kernel(const AxbArgs a)
+__global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_bf16_kernel(const AttnArgs<uint16_t> a)
 {
     __shared__ __attribute__((aligned(16))) uint16_t Ks[kAxbChunk * kAbRow], Vs[kAxbChunk * kAbRow];
-    const int pair = (int)blockIdx.x / a.nblk, blk = (int)blockIdx.x % a.nblk, n = pair / a.H, h = pair % a.H;
+    const int pair = (int)blockIdx.x / a.wpp, blk = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int qi = blk * kAxRows + wave * 16 + c;
@@ -626,16 +597,15 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_bf16_kernel(const AxbA
     }
 }
 
-static bool axb_view_ok(const AxbView &v)
-{
-    return v.p != nullptr && ((uintptr_t)v.p & 15) == 0 && (v.sn & 7) == 0 && (v.sl & 7) == 0;
-}
 static_assert(2 * kAxbChunk * kAbRow * sizeof(uint16_t) + 7 * kAxbChunk * sizeof(float) <= 64 * 1024, "static LDS");
+
+// workgroups that share a pair: kAxRows queries (forward, dQ) or keys (dK / dV) each
+static int ax_blocks(int L) { return (int)(((long long)L + kAxRows - 1) / kAxRows); }
 
 }  // namespace msda
 
-using msda::AxArgs;
-using msda::AxView;
+using msda::attn_view;
+using msda::ax_blocks;
 
 extern "C" {
 
@@ -644,46 +614,20 @@ int msda_attn32x_supported(int Lq, int Lk, int head_dim)
     return head_dim == 32 && Lq >= 1 && Lk >= 1 && Lq <= msda::kAxMaxLen && Lk <= msda::kAxMaxLen;
 }
 
-// every check of the geometry, the dropout and the mask; launches nothing
-static int ax_fill(AxArgs &a, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p, const unsigned long long *seed,
-                   const unsigned char *mask, long long mask_sq)
-{
-    char buf[200];
-    if (N <= 0 || H <= 0 || !msda_attn32x_supported(Lq, Lk, 32)) {
-        snprintf(buf, sizeof(buf), "%s: head_dim 32, 1 <= Lq, Lk <= 2048", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (!(dropout_p >= 0.f && dropout_p < 1.f) || (dropout_p > 0.f && seed == nullptr)) {
-        snprintf(buf, sizeof(buf), "%s: 0 <= p < 1 (seed required for p > 0)", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (mask != nullptr && mask_sq < Lk) {
-        snprintf(buf, sizeof(buf), "%s: mask row stride mask_sq must be at least Lk", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    a.H = H; a.Lq = Lq; a.Lk = Lk; a.scale = scale;
-    a.scale2 = scale * 1.4426950408889634f;
-    a.keep_scale = 1.f / (1.f - dropout_p);
-    a.thresh = dropout_p > 0.f ? (unsigned)fmin(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
-    a.seed = seed;
-    a.mask = mask; a.mask_sq = mask_sq;
-    return MSDA_OK;
-}
+// Each entry: check, bind (msda_attn_args.h: every refusal comes before any launch), size the grid, launch.  The check is given
+// the larger of a backward's two grids; each launch then sets its own workgroups per pair.  LDS is static.
 
 int msda_attn32x_forward_f32(const float *q, long long q_sn, long long q_sl, const float *k, long long k_sn, long long k_sl,
                              const float *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
                              float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
                              float *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream)
 {
-    AxArgs a{};
-    if (int rc = ax_fill(a, "msda_attn32x_forward_f32", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
-    a.q = AxView{const_cast<float *>(q), q_sn, q_sl}; a.k = AxView{const_cast<float *>(k), k_sn, k_sl};
-    a.v = AxView{const_cast<float *>(v), v_sn, v_sl}; a.o = AxView{out, o_sn, o_sl}; a.lse = lse;
-    if (!msda::ax_view_ok(a.q) || !msda::ax_view_ok(a.k) || !msda::ax_view_ok(a.v) || !msda::ax_view_ok(a.o) || lse == nullptr)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
-    a.nblk = (Lq + msda::kAxRows - 1) / msda::kAxRows;
-    if ((long long)N * H * a.nblk > 0x7fffffffLL) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_f32: too many (batch, head) pairs");
-    hipLaunchKernelGGL(msda::attn32x_fwd_kernel, dim3((unsigned)(N * H * a.nblk)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    const char *who = "msda_attn32x_forward_f32";
+    msda::AttnArgs<float> a{};
+    if (int rc = msda::attn_check(a, who, msda::kAxMaxLen, N, H, Lq, Lk, ax_blocks(Lq), scale, dropout_p, seed, mask, mask_sq)) return rc;
+    if (int rc = msda::attn_bind_forward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                         attn_view(out, o_sn, o_sl), lse)) return rc;
+    hipLaunchKernelGGL(msda::attn32x_fwd_kernel, dim3((unsigned)(N * H * a.wpp)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     return msda::check_launch("msda long attention forward (head_dim 32)");
 }
 
@@ -694,53 +638,35 @@ int msda_attn32x_backward_f32(const float *q, long long q_sn, long long q_sl, co
                               long long mask_sq, float *grad_q, long long gq_sn, long long gq_sl, float *grad_k, long long gk_sn,
                               long long gk_sl, float *grad_v, long long gv_sn, long long gv_sl, msda_stream_t stream)
 {
-    AxArgs a{};
-    if (int rc = ax_fill(a, "msda_attn32x_backward_f32", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
-    a.q = AxView{const_cast<float *>(q), q_sn, q_sl}; a.k = AxView{const_cast<float *>(k), k_sn, k_sl};
-    a.v = AxView{const_cast<float *>(v), v_sn, v_sl}; a.o = AxView{const_cast<float *>(out), o_sn, o_sl};
-    a.go = AxView{const_cast<float *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
-    a.gq = AxView{grad_q, gq_sn, gq_sl}; a.gk = AxView{grad_k, gk_sn, gk_sl}; a.gv = AxView{grad_v, gv_sn, gv_sl};
-    for (const AxView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
-        if (!msda::ax_view_ok(*w))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: 16-byte aligned tensors, strides multiples of 4 floats");
-    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: lse required");
-    const int nblk_q = (Lq + msda::kAxRows - 1) / msda::kAxRows, nblk_k = (Lk + msda::kAxRows - 1) / msda::kAxRows;
-    if ((long long)N * H * (nblk_q > nblk_k ? nblk_q : nblk_k) > 0x7fffffffLL)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_f32: too many (batch, head) pairs");
-    a.nblk = nblk_k;
+    const char *who = "msda_attn32x_backward_f32";
+    msda::AttnArgs<float> a{};
+    const int nblk_q = ax_blocks(Lq), nblk_k = ax_blocks(Lk);
+    if (int rc = msda::attn_check(a, who, msda::kAxMaxLen, N, H, Lq, Lk, nblk_q > nblk_k ? nblk_q : nblk_k, scale, dropout_p, seed, mask,
+                                  mask_sq)) return rc;
+    if (int rc = msda::attn_bind_backward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                          attn_view(out, o_sn, o_sl), lse, attn_view(grad_out, go_sn, go_sl),
+                                          attn_view(grad_q, gq_sn, gq_sl), attn_view(grad_k, gk_sn, gk_sl),
+                                          attn_view(grad_v, gv_sn, gv_sl))) return rc;
+    a.wpp = nblk_k;
     hipLaunchKernelGGL(msda::attn32x_bwd_kv_kernel, dim3((unsigned)(N * H * nblk_k)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     if (int rc = msda::check_launch("msda long attention backward (dK, dV)")) return rc;
-    a.nblk = nblk_q;
+    a.wpp = nblk_q;
     hipLaunchKernelGGL(msda::attn32x_bwd_q_kernel, dim3((unsigned)(N * H * nblk_q)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     return msda::check_launch("msda long attention backward (dQ)");
 }
 
-// bf16 operands: ax_fill's checks (all of them before any launch), the fp32 entries' random stream
-static int axb_fill(msda::AxbArgs &b, const char *who, int N, int H, int Lq, int Lk, float scale, float dropout_p,
-                    const unsigned long long *seed, const unsigned char *mask, long long mask_sq)
-{
-    AxArgs a{};
-    if (int rc = ax_fill(a, who, N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
-    b.H = a.H; b.Lq = a.Lq; b.Lk = a.Lk; b.scale = a.scale; b.scale2 = a.scale2; b.keep_scale = a.keep_scale; b.thresh = a.thresh;
-    b.seed = a.seed; b.mask = a.mask; b.mask_sq = a.mask_sq;
-    return MSDA_OK;
-}
-
+// bf16 operands: the same checks, the fp32 entries' random stream and grids
 int msda_attn32x_forward_bf16(const uint16_t *q, long long q_sn, long long q_sl, const uint16_t *k, long long k_sn, long long k_sl,
                               const uint16_t *v, long long v_sn, long long v_sl, int N, int H, int Lq, int Lk, float scale,
                               float dropout_p, const unsigned long long *seed, const unsigned char *mask, long long mask_sq,
                               uint16_t *out, long long o_sn, long long o_sl, float *lse, msda_stream_t stream)
 {
-    using msda::AxbView;
-    msda::AxbArgs a{};
-    if (int rc = axb_fill(a, "msda_attn32x_forward_bf16", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
-    a.q = AxbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AxbView{const_cast<uint16_t *>(k), k_sn, k_sl};
-    a.v = AxbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AxbView{out, o_sn, o_sl}; a.lse = lse;
-    if (!msda::axb_view_ok(a.q) || !msda::axb_view_ok(a.k) || !msda::axb_view_ok(a.v) || !msda::axb_view_ok(a.o) || lse == nullptr)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
-    a.nblk = (Lq + msda::kAxRows - 1) / msda::kAxRows;
-    if ((long long)N * H * a.nblk > 0x7fffffffLL) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_forward_bf16: too many (batch, head) pairs");
-    hipLaunchKernelGGL(msda::attn32x_fwd_bf16_kernel, dim3((unsigned)(N * H * a.nblk)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
+    const char *who = "msda_attn32x_forward_bf16";
+    msda::AttnArgs<uint16_t> a{};
+    if (int rc = msda::attn_check(a, who, msda::kAxMaxLen, N, H, Lq, Lk, ax_blocks(Lq), scale, dropout_p, seed, mask, mask_sq)) return rc;
+    if (int rc = msda::attn_bind_forward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                         attn_view(out, o_sn, o_sl), lse)) return rc;
+    hipLaunchKernelGGL(msda::attn32x_fwd_bf16_kernel, dim3((unsigned)(N * H * a.wpp)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     return msda::check_launch("msda long attention forward (head_dim 32, bf16)");
 }
 
@@ -752,24 +678,19 @@ int msda_attn32x_backward_bf16(const uint16_t *q, long long q_sn, long long q_sl
                                long long gk_sn, long long gk_sl, uint16_t *grad_v, long long gv_sn, long long gv_sl,
                                msda_stream_t stream)
 {
-    using msda::AxbView;
-    msda::AxbArgs a{};
-    if (int rc = axb_fill(a, "msda_attn32x_backward_bf16", N, H, Lq, Lk, scale, dropout_p, seed, mask, mask_sq)) return rc;
-    a.q = AxbView{const_cast<uint16_t *>(q), q_sn, q_sl}; a.k = AxbView{const_cast<uint16_t *>(k), k_sn, k_sl};
-    a.v = AxbView{const_cast<uint16_t *>(v), v_sn, v_sl}; a.o = AxbView{const_cast<uint16_t *>(out), o_sn, o_sl};
-    a.go = AxbView{const_cast<uint16_t *>(grad_out), go_sn, go_sl}; a.lse = const_cast<float *>(lse);
-    a.gq = AxbView{grad_q, gq_sn, gq_sl}; a.gk = AxbView{grad_k, gk_sn, gk_sl}; a.gv = AxbView{grad_v, gv_sn, gv_sl};
-    for (const AxbView *w : {&a.q, &a.k, &a.v, &a.o, &a.go, &a.gq, &a.gk, &a.gv})
-        if (!msda::axb_view_ok(*w))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: 16-byte aligned tensors, strides multiples of 8 elements");
-    if (lse == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: lse required");
-    const int nblk_q = (Lq + msda::kAxRows - 1) / msda::kAxRows, nblk_k = (Lk + msda::kAxRows - 1) / msda::kAxRows;
-    if ((long long)N * H * (nblk_q > nblk_k ? nblk_q : nblk_k) > 0x7fffffffLL)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_attn32x_backward_bf16: too many (batch, head) pairs");
-    a.nblk = nblk_k;
+    const char *who = "msda_attn32x_backward_bf16";
+    msda::AttnArgs<uint16_t> a{};
+    const int nblk_q = ax_blocks(Lq), nblk_k = ax_blocks(Lk);
+    if (int rc = msda::attn_check(a, who, msda::kAxMaxLen, N, H, Lq, Lk, nblk_q > nblk_k ? nblk_q : nblk_k, scale, dropout_p, seed, mask,
+                                  mask_sq)) return rc;
+    if (int rc = msda::attn_bind_backward(a, who, attn_view(q, q_sn, q_sl), attn_view(k, k_sn, k_sl), attn_view(v, v_sn, v_sl),
+                                          attn_view(out, o_sn, o_sl), lse, attn_view(grad_out, go_sn, go_sl),
+                                          attn_view(grad_q, gq_sn, gq_sl), attn_view(grad_k, gk_sn, gk_sl),
+                                          attn_view(grad_v, gv_sn, gv_sl))) return rc;
+    a.wpp = nblk_k;
     hipLaunchKernelGGL(msda::attn32x_bwd_kv_bf16_kernel, dim3((unsigned)(N * H * nblk_k)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     if (int rc = msda::check_launch("msda long attention backward (dK, dV; bf16)")) return rc;
-    a.nblk = nblk_q;
+    a.wpp = nblk_q;
     hipLaunchKernelGGL(msda::attn32x_bwd_q_bf16_kernel, dim3((unsigned)(N * H * nblk_q)), dim3(msda::kAxBlock), 0, (hipStream_t)stream, a);
     return msda::check_launch("msda long attention backward (dQ; bf16)");
 }

@@ -42,47 +42,21 @@ from .. import _native as MSDA
 from .linear_func import _autocast_dtype, bracket_linear_wb
 
 
-class _Attn32Fn(Function):
-    """core(qk [L, N, 2E] = packed q | k projections, v [L, N, E]) -> [L, N, E]; fp32 or bf16 (dispatch on qk's dtype)"""
+class _AttnFn(Function):
+    """core(family, qk [L, N, 2E] = packed q | k projections, v [L, N, E], mask [L, L] bool or None) -> [L, N, E].  family
+    "attn32": the resident kernels (msda_attn32_*, no mask); "attn32x": the streaming ones (msda_attn32x_*).  fp32 or bf16:
+    dispatch on qk's dtype."""
 
     @staticmethod
-    def forward(ctx, qk, v, heads, dropout_p):
+    def forward(ctx, family, qk, v, mask, heads, dropout_p):
         E = v.shape[2]
         q, k = qk[..., :E], qk[..., E:]
         scale = 1.0 / math.sqrt(E // heads)
         seed = torch.empty((), dtype=torch.int64, device=v.device).random_().view(1) if dropout_p > 0 else None
-        out, lse = MSDA.attn32_forward(q, k, v, heads, scale, dropout_p, seed)
-        ctx.save_for_backward(qk, v, out, lse, *([seed] if seed is not None else []))
-        ctx.heads, ctx.scale, ctx.dropout_p = heads, scale, dropout_p
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        qk, v, out, lse = ctx.saved_tensors[:4]
-        seed = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        E = v.shape[2]
-        g_qk = torch.empty_like(qk, memory_format=torch.contiguous_format)
-        if grad_out.dtype != qk.dtype:                   # (the core's output type: fp32, or bf16 under autocast)
-            grad_out = grad_out.to(qk.dtype)
-        _, _, g_v = MSDA.attn32_backward(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, ctx.scale, ctx.dropout_p, seed,
-                                         grad_q=g_qk[..., :E], grad_k=g_qk[..., E:])
-        return g_qk, g_v, None, None
-
-
-class _Attn32xFn(Function):
-    """core(qk [L, N, 2E], v [L, N, E], mask [L, L] bool or None) -> [L, N, E]; streaming kernels, fp32 or bf16 (msda_attn32x_*:
-    dispatch on qk's dtype)"""
-
-    @staticmethod
-    def forward(ctx, qk, v, mask, heads, dropout_p):
-        E = v.shape[2]
-        q, k = qk[..., :E], qk[..., E:]
-        scale = 1.0 / math.sqrt(E // heads)
-        seed = torch.empty((), dtype=torch.int64, device=v.device).random_().view(1) if dropout_p > 0 else None
-        out, lse = MSDA.attn32x_forward(q, k, v, heads, scale, dropout_p, seed, mask)
+        extra = (mask,) if family == "attn32x" else ()   # (the resident binding takes no mask; the public names, looked up per call)
+        out, lse = getattr(MSDA, family + "_forward")(q, k, v, heads, scale, dropout_p, seed, *extra)
         ctx.save_for_backward(qk, v, out, lse, *([mask] if mask is not None else []), *([seed] if seed is not None else []))
-        ctx.heads, ctx.scale, ctx.dropout_p, ctx.masked = heads, scale, dropout_p, mask is not None
+        ctx.family, ctx.heads, ctx.scale, ctx.dropout_p, ctx.masked = family, heads, scale, dropout_p, mask is not None
         return out
 
     @staticmethod
@@ -94,11 +68,12 @@ class _Attn32xFn(Function):
         seed = rest.pop(0) if rest else None
         E = v.shape[2]
         g_qk = torch.empty_like(qk, memory_format=torch.contiguous_format)
-        if grad_out.dtype != qk.dtype:
+        if grad_out.dtype != qk.dtype:                   # (the core's output type: fp32, or bf16 under autocast)
             grad_out = grad_out.to(qk.dtype)
-        _, _, g_v = MSDA.attn32x_backward(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, ctx.scale, ctx.dropout_p, seed,
-                                          mask, grad_q=g_qk[..., :E], grad_k=g_qk[..., E:])
-        return g_qk, g_v, None, None, None
+        extra = (mask,) if ctx.family == "attn32x" else ()
+        _, _, g_v = getattr(MSDA, ctx.family + "_backward")(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, ctx.scale,
+                                                            ctx.dropout_p, seed, *extra, grad_q=g_qk[..., :E], grad_k=g_qk[..., E:])
+        return None, g_qk, g_v, None, None, None
 
 
 def _takes_common(mha, x_qk, x_v):
@@ -147,5 +122,5 @@ def self_attention(mha, x_qk, x_v, attn_mask=None):
     qk = bracket_linear_wb(x_qk, w[:2 * E], b[:2 * E])
     v = bracket_linear_wb(x_v, w[2 * E:], b[2 * E:])
     p = float(mha.dropout) if mha.training else 0.0
-    core = _Attn32xFn.apply(qk, v, attn_mask, mha.num_heads, p) if long_core else _Attn32Fn.apply(qk, v, mha.num_heads, p)
+    core = _AttnFn.apply("attn32x" if long_core else "attn32", qk, v, attn_mask, mha.num_heads, p)     # (resident: no mask got here)
     return bracket_linear_wb(core, mha.out_proj.weight, mha.out_proj.bias)

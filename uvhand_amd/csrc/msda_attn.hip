@@ -31,9 +31,11 @@ constexpr int kAtWaves = MSDA_AT_WAVES, kAtBlock = kAtWaves * 64, kAtMaxTiles = 
 // Dropout: 32 bits per (pair, query, key) from at_hash of the counter (query << 16) + key + at_mix(seed, pair) (msda_attn_tile.h)
 
 // rows [0, L) of two [L][32] slices (row strides sl0 / sl1) -> dst0 / dst1 [Lp][kAtRow]; rows [L, Lp) zero.  Lp * 8 float4 per
-// slice on 640 threads: at most four rounds (Lp <= 320); all the loads of a thread are issued before its first LDS store.
+// slice on 768 threads: at most four rounds (Lp <= 320); all the loads of a thread are issued before its first LDS store.
+// kScaled: slice 0 is stored times mul0 (dK / dV: Q times scale2, the forward's own operand of the scores).
+template <bool kScaled = false>
 __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, long long sl0, float *dst1, const float *src1,
-                                              long long sl1, int L, int Lp)
+                                              long long sl1, int L, int Lp, float mul0 = 1.f)
 {
     constexpr int R = (kAtMaxLen * 8 + kAtBlock - 1) / kAtBlock;
     float4 v0[R], v1[R];
@@ -43,6 +45,7 @@ __device__ __forceinline__ void at_load_rows2(float *dst0, const float *src0, lo
         const bool live = row < L;
         v0[k] = live ? ld4(src0 + (long long)row * sl0 + c) : at_zero4();
         v1[k] = live ? ld4(src1 + (long long)row * sl1 + c) : at_zero4();
+        if (kScaled) { v0[k].x *= mul0; v0[k].y *= mul0; v0[k].z *= mul0; v0[k].w *= mul0; }
     }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AttnArgs<flo
             }
         }
         sum = at_rsum(sum);
-        if (qok && r == 0) a.lse[(long long)pair * a.Lq + qi] = (m + __builtin_amdgcn_logf(sum)) * 0.6931471805599453f;   // natural log
+        if (qok && r == 0) a.lse[(long long)pair * a.Lq + qi] = at_lse_natural(m, __builtin_amdgcn_logf(sum));   // natural log, rounded once
         const float inv = a.keep_scale / sum;
         at_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
         const unsigned ctr = ((unsigned)qi << 16) + 4 * r + mix;
@@ -126,14 +129,20 @@ __global__ __launch_bounds__(kAtBlock) void attn32_fwd_kernel(const AttnArgs<flo
     }
 }
 
-// dK, dV: a wavefront owns 16 keys and walks the query tiles
+// The backward's probabilities are exp2(s - lse * log2 e) with lse one fp32 number per row: whatever is lost between the
+// forward's scores and that difference lands on every probability, the ones near 1 included (a peaked row: |s| of 30 .. 80
+// in base 2, an ulp of which is 4e-6 .. 8e-6).  So both backward kernels form the scores from the forward's own products —
+// (q * scale2) . k, in the forward's channel order — and take lse * log2 e as hi + lo (at_lse_base2; the forward rounds lse
+// once, at_lse_natural): what remains is that one rounding of lse, half an ulp of |lse| on every probability of the row.
+
+// dK, dV: a wavefront owns 16 keys and walks the query tiles; Q sits in LDS times scale2 (dK is scaled back at the end)
 __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<float> a)
 {
     extern __shared__ __attribute__((aligned(16))) float at_smem[];
     const int Lqp = (a.Lq + 15) & ~15, ntq = Lqp >> 4, ntk = (a.Lk + 15) >> 4;
-    float *Qs = at_smem, *Gs = at_smem + Lqp * kAtRow, *lse_s = Gs + Lqp * kAtRow, *del_s = lse_s + Lqp;
+    float *Qs = at_smem, *Gs = at_smem + Lqp * kAtRow, *lse_s = Gs + Lqp * kAtRow, *del_s = lse_s + Lqp, *lsl_s = del_s + Lqp;
     const int pair = (int)blockIdx.x / a.wpp, part = (int)blockIdx.x % a.wpp, n = pair / a.H, h = pair % a.H;
-    at_load_rows2(Qs, a.q.p + n * a.q.sn + h * 32, a.q.sl, Gs, a.go.p + n * a.go.sn + h * 32, a.go.sl, a.Lq, Lqp);
+    at_load_rows2<true>(Qs, a.q.p + n * a.q.sn + h * 32, a.q.sl, Gs, a.go.p + n * a.go.sn + h * 32, a.go.sl, a.Lq, Lqp, a.scale2);
     const unsigned mix = at_mix(a.thresh ? a.seed[0] : 0ull, (unsigned)pair);
     __syncthreads();
     // per query: log-sum-exp (+inf for the padding rows: their probabilities vanish) and delta = <dO, O>
@@ -148,11 +157,12 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<
             }
         }
         del_s[qi] = d;
-        lse_s[qi] = qi < a.Lq ? a.lse[(long long)pair * a.Lq + qi] * 1.4426950408889634f : INFINITY;      // base 2, like the scores
+        at_lse_base2(qi < a.Lq ? a.lse[(long long)pair * a.Lq + qi] : INFINITY, lse_s[qi], lsl_s[qi]);      // base 2, like the scores
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, r = lane >> 4;
     const int per = (ntk + a.wpp - 1) / a.wpp, t_end = min(ntk, (part + 1) * per);
+    const float unscale = a.scale2 != 0.f ? a.scale / a.scale2 : 0.f;       // dK = scale * Q^T dS, and Qs holds Q * scale2
     for (int tk = part * per + wave; tk < t_end; tk += kAtWaves) {
         const int key = tk * 16 + c;
         const bool kok = key < a.Lk;
@@ -162,8 +172,6 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<
             const float *vr = a.v.p + n * a.v.sn + h * 32 + (long long)key * a.v.sl + 4 * r;
             k0 = ld4(kr); k1 = ld4(kr + 16); v0 = ld4(vr); v1 = ld4(vr + 16);
         }
-        k0.x *= a.scale2; k0.y *= a.scale2; k0.z *= a.scale2; k0.w *= a.scale2;
-        k1.x *= a.scale2; k1.y *= a.scale2; k1.z *= a.scale2; k1.w *= a.scale2;
         const unsigned ctr = (unsigned)key + ((unsigned)(4 * r) << 16) + mix;
         at_f4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = dv0, dk0 = dv0, dk1 = dv0;
         // S and dP tiles: entry v = (query 16 t + 4 r + v, key).  The next tile's two products are issued before this tile's
@@ -175,12 +183,12 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<
             const at_f4 s_next = at_dot32(Qs + (16 * tn + c) * kAtRow + 4 * r, k0, k1);
             const at_f4 dp_next = at_dot32(Gs + (16 * tn + c) * kAtRow + 4 * r, v0, v1);
             __builtin_amdgcn_sched_barrier(0);
-            const float4 ls = ld4(lse_s + 16 * t + 4 * r), dl = ld4(del_s + 16 * t + 4 * r);
-            const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
+            const float4 ls = ld4(lse_s + 16 * t + 4 * r), ll = ld4(lsl_s + 16 * t + 4 * r), dl = ld4(del_s + 16 * t + 4 * r);
+            const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, llv[4] = {ll.x, ll.y, ll.z, ll.w}, dlv[4] = {dl.x, dl.y, dl.z, dl.w};
             at_f4 pd, ds;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const float p = __builtin_amdgcn_exp2f(s[v] - lsv[v]);
+                const float p = __builtin_amdgcn_exp2f((s[v] - lsv[v]) - llv[v]);
                 const bool keep = at_hash(ctr + ((unsigned)(16 * t + v) << 16)) >= a.thresh;
                 pd[v] = keep ? p * a.keep_scale : 0.f;
                 ds[v] = p * ((keep ? dp[v] * a.keep_scale : 0.f) - dlv[v]);
@@ -194,8 +202,8 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_kv_kernel(const AttnArgs<
             float *gkr = a.gk.p + n * a.gk.sn + h * 32 + (long long)key * a.gk.sl + 4 * r;
             *reinterpret_cast<float4 *>(gvr) = make_float4(dv0[0], dv0[1], dv0[2], dv0[3]);
             *reinterpret_cast<float4 *>(gvr + 16) = make_float4(dv1[0], dv1[1], dv1[2], dv1[3]);
-            *reinterpret_cast<float4 *>(gkr) = make_float4(dk0[0] * a.scale, dk0[1] * a.scale, dk0[2] * a.scale, dk0[3] * a.scale);
-            *reinterpret_cast<float4 *>(gkr + 16) = make_float4(dk1[0] * a.scale, dk1[1] * a.scale, dk1[2] * a.scale, dk1[3] * a.scale);
+            *reinterpret_cast<float4 *>(gkr) = make_float4(dk0[0] * unscale, dk0[1] * unscale, dk0[2] * unscale, dk0[3] * unscale);
+            *reinterpret_cast<float4 *>(gkr + 16) = make_float4(dk1[0] * unscale, dk1[1] * unscale, dk1[2] * unscale, dk1[3] * unscale);
         }
     }
 }
@@ -216,14 +224,16 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_kernel(const AttnArgs<f
         const int qi = tq * 16 + c;
         const bool qok = qi < a.Lq;
         float4 q0 = at_zero4(), q1 = at_zero4(), g0 = at_zero4(), g1 = at_zero4(), o0 = at_zero4(), o1 = at_zero4();
-        float lse = INFINITY;
+        float lse_n = INFINITY;
         if (qok) {
             const float *qr = a.q.p + n * a.q.sn + h * 32 + (long long)qi * a.q.sl + 4 * r;
             const float *gr = a.go.p + n * a.go.sn + h * 32 + (long long)qi * a.go.sl + 4 * r;
             const float *orw = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
             q0 = ld4(qr); q1 = ld4(qr + 16); g0 = ld4(gr); g1 = ld4(gr + 16); o0 = ld4(orw); o1 = ld4(orw + 16);
-            lse = a.lse[(long long)pair * a.Lq + qi] * 1.4426950408889634f;
+            lse_n = a.lse[(long long)pair * a.Lq + qi];
         }
+        float lse, lse_lo;
+        at_lse_base2(lse_n, lse, lse_lo);
         q0.x *= a.scale2; q0.y *= a.scale2; q0.z *= a.scale2; q0.w *= a.scale2;
         q1.x *= a.scale2; q1.y *= a.scale2; q1.z *= a.scale2; q1.w *= a.scale2;
         const unsigned ctr = ((unsigned)qi << 16) + 4 * r + mix;
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(kAtBlock) void attn32_bwd_q_kernel(const AttnArgs<f
             at_f4 ds;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                float p = __builtin_amdgcn_exp2f(s[v] - lse);
+                float p = __builtin_amdgcn_exp2f((s[v] - lse) - lse_lo);
                 if (t == ntk - 1) p = 16 * t + 4 * r + v < a.Lk ? p : 0.f;      // (uniform: only the last tile has padding keys)
                 const bool keep = at_hash(ctr + (16 * t + v)) >= a.thresh;
                 ds[v] = p * ((keep ? dp[v] * a.keep_scale : 0.f) - delta);
@@ -543,7 +553,7 @@ int msda_attn32_backward_f32(const float *q, long long q_sn, long long q_sl, con
                                           attn_view(grad_q, gq_sn, gq_sl), attn_view(grad_k, gk_sn, gk_sl),
                                           attn_view(grad_v, gv_sn, gv_sl))) return rc;
     const int Lqp = (Lq + 15) & ~15, Lkp = (Lk + 15) & ~15;
-    const size_t lds_kv = ((size_t)2 * Lqp * msda::kAtRow + 2 * Lqp) * sizeof(float), lds_q = (size_t)2 * Lkp * msda::kAtRow * sizeof(float);
+    const size_t lds_kv = ((size_t)2 * Lqp * msda::kAtRow + 3 * Lqp) * sizeof(float), lds_q = (size_t)2 * Lkp * msda::kAtRow * sizeof(float);
     if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_kv_kernel), lds_kv)) return rc;
     if (int rc = msda::at_allow_lds(reinterpret_cast<const void *>(msda::attn32_bwd_q_kernel), lds_q)) return rc;
     const dim3 grid((unsigned)(N * H * a.wpp));

@@ -72,23 +72,7 @@ __device__ __forceinline__ unsigned ax_hidden4(const unsigned char *mrow, int ke
     return bits;
 }
 
-// The log-sum-exp crosses the ABI as an fp32 natural logarithm and the kernels work in base 2.  A plain product on each side
-// would add a rounding of ulp(lse) / 2 twice to EVERY exponent of a row — a common factor of about 2e-7 on the row's
-// probabilities and gradients; both conversions therefore carry the product's low part.
-// forward: (m + l) * ln 2 rounded once (m + l by a two-sum, the constant as hi + lo)
-__device__ __forceinline__ float ax_lse_natural(float m, float l)
-{
-    const float t = m + l;
-    if (!(fabsf(t) < INFINITY)) return t;               // (-inf: every key hidden)
-    const float bb = t - m, e = (m - (t - bb)) + (l - bb);
-    return fmaf(t, 0.693147182464599609375f, fmaf(t, -1.904654299957e-9f, e * 0.693147182464599609375f));
-}
-// backward: lse * log2 e as hi + lo; a score's exponent is (s - hi) - lo.  +inf (rows past Lq) stays (+inf, 0).
-__device__ __forceinline__ void ax_lse_base2(float lse, float &hi, float &lo)
-{
-    hi = lse * 1.44269502162933349609375f;
-    lo = fabsf(hi) < INFINITY ? fmaf(lse, 1.44269502162933349609375f, -hi) + lse * 1.925963033500e-8f : 0.f;
-}
+// (the log-sum-exp crosses the ABI as an fp32 natural logarithm: at_lse_natural / at_lse_base2, msda_attn_tile.h)
 
 // at_dot32 as four chains of two MFMA steps (eight channels each, every chain from a zero accumulator) summed pairwise on the
 // vector unit.  dP = dO . v reaches |13| at unit-variance inputs, and every step of at_dot32's one chain of eight rounds at that
@@ -170,7 +154,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_fwd_kernel(const AttnArgs<fl
     }
     sum = at_rsum(sum);
     if (qok) {
-        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = ax_lse_natural(m, __builtin_amdgcn_logf(sum));
+        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = at_lse_natural(m, __builtin_amdgcn_logf(sum));
         const float inv = a.keep_scale / sum;           // (sum 0 — every key hidden: inf, and the row 0 * inf = NaN)
         float *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
         *reinterpret_cast<float4 *>(orow) = make_float4(o0[0] * inv, o0[1] * inv, o0[2] * inv, o0[3] * inv);
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_kernel(const AttnArgs
             d += __shfl_xor(d, 2);
             if (part == 0) {
                 float hi, lo;
-                ax_lse_base2(g < a.Lq ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
+                at_lse_base2(g < a.Lq ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
                 del_s[ql] = d; lse_s[ql] = hi; lsl_s[ql] = lo;
             }
         }
@@ -274,7 +258,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_kernel(const AttnArgs<
         lse_n = a.lse[(long long)pair * a.Lq + qi];
     }
     float lse, lse_lo;
-    ax_lse_base2(lse_n, lse, lse_lo);
+    at_lse_base2(lse_n, lse, lse_lo);
     ax_scale4(q0, a.scale2); ax_scale4(q1, a.scale2);
     const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
     const float *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
@@ -432,7 +416,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_fwd_bf16_kernel(const AttnAr
     }
     sum = at_rsum(sum);
     if (qok) {
-        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = ax_lse_natural(m, __builtin_amdgcn_logf(sum));
+        if (r == 0) a.lse[(long long)pair * a.Lq + qi] = at_lse_natural(m, __builtin_amdgcn_logf(sum));
         const float inv = a.keep_scale / sum;           // (sum 0 — every key hidden: inf, and the row 0 * inf = NaN)
         uint16_t *orow = a.o.p + n * a.o.sn + h * 32 + (long long)qi * a.o.sl + 4 * r;
         ab_st4(orow, o0, inv);
@@ -479,7 +463,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_kv_bf16_kernel(const Att
             d += __shfl_xor(d, 2);
             if (part == 0) {
                 float hi, lo;
-                ax_lse_base2(live ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
+                at_lse_base2(live ? a.lse[(long long)pair * a.Lq + g] : INFINITY, hi, lo);
                 del_s[row] = d; lse_s[row] = hi; lsl_s[row] = lo;
             }
             if (a.mask != nullptr) {                    // the query's mask row over 32 of the block's keys as one word of bits
@@ -556,7 +540,7 @@ __global__ __launch_bounds__(kAxBlock) void attn32x_bwd_q_bf16_kernel(const Attn
         lse_n = a.lse[(long long)pair * a.Lq + qi];
     }
     float lse, lse_lo;
-    ax_lse_base2(lse_n, lse, lse_lo);
+    at_lse_base2(lse_n, lse, lse_lo);
     const unsigned char *mrow = (a.mask && qok) ? a.mask + (long long)qi * a.mask_sq : nullptr;
     const uint16_t *kp = a.k.p + n * a.k.sn + h * 32, *vp = a.v.p + n * a.v.sn + h * 32;
     const unsigned ctr = ((unsigned)qi << 16) + 8 * r + mix;

@@ -24,6 +24,8 @@
 // pair give lane (c, r) keys 32T + 8r + j in natural order (j = 4b + v) — exactly the 8 k of the next product's operand.
 // Rows up to a multiple of 32 are zero in LDS.
 #pragma once
+#include <math.h>
+
 #include "msda_common.h"
 
 namespace msda {
@@ -101,6 +103,25 @@ __device__ __forceinline__ float at_rmax(float x)
     x = fmaxf(x, __shfl_xor(x, 16));
     x = fmaxf(x, __shfl_xor(x, 32));
     return x;
+}
+
+// ---- the log-sum-exp across the ABI (resident fp32 and streaming cores) ----------------------------------------------------------
+// The log-sum-exp crosses the ABI as an fp32 natural logarithm and the kernels work in base 2.  A plain product on each side
+// would add a rounding of ulp(lse) / 2 twice to EVERY exponent of a row — a common factor of about 2e-7 on the row's
+// probabilities and gradients; both conversions therefore carry the product's low part.
+// forward: (m + l) * ln 2 rounded once (m + l by a two-sum, the constant as hi + lo)
+__device__ __forceinline__ float at_lse_natural(float m, float l)
+{
+    const float t = m + l;
+    if (!(fabsf(t) < INFINITY)) return t;               // (-inf: every key hidden)
+    const float bb = t - m, e = (m - (t - bb)) + (l - bb);
+    return fmaf(t, 0.693147182464599609375f, fmaf(t, -1.904654299957e-9f, e * 0.693147182464599609375f));
+}
+// backward: lse * log2 e as hi + lo; a score's exponent is (s - hi) - lo.  +inf (rows past Lq) stays (+inf, 0).
+__device__ __forceinline__ void at_lse_base2(float lse, float &hi, float &lo)
+{
+    hi = lse * 1.44269502162933349609375f;
+    lo = fabsf(hi) < INFINITY ? fmaf(lse, 1.44269502162933349609375f, -hi) + lse * 1.925963033500e-8f : 0.f;
 }
 
 // ---- bf16 ---------------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // selection, error reporting.  No torch types, no allocation, no device synchronisation.
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include <atomic>
@@ -42,23 +43,22 @@ int check_launch(const char *what)
     return set_error(MSDA_ERR_LAUNCH, buf);
 }
 
-static int check_args(const void *const *ptrs, int nptrs, int N, int S, int M, int D, int L, int Lq,
-                      int P)
+// ---- the sampling op: every entry fills the records of msda_op_args.h and calls one of the four bodies below ----
+static int check_args(const OpGeom &g, std::initializer_list<const void *> ptrs)
 {
-    if (N < 0 || S < 0 || M <= 0 || D <= 0 || L <= 0 || Lq < 0 || P <= 0)
+    if (g.N < 0 || g.S < 0 || g.M <= 0 || g.D <= 0 || g.L <= 0 || g.Lq < 0 || g.P <= 0)
         return set_error(MSDA_ERR_ARGUMENT, "msda: sizes must be positive (N, S, Lq may be 0)");
-    if (N == 0 || Lq == 0 || S == 0) return MSDA_OK;               // nothing to read
-    for (int i = 0; i < nptrs; ++i)
-        if (ptrs[i] == nullptr) return set_error(MSDA_ERR_ARGUMENT, "msda: null device pointer");
+    if (g.N == 0 || g.Lq == 0 || g.S == 0) return MSDA_OK;        // nothing to read
+    for (const void *p : ptrs)
+        if (p == nullptr) return set_error(MSDA_ERR_ARGUMENT, "msda: null device pointer");
     return MSDA_OK;
 }
 
 // Row strides of the fused-prologue tensors: 0 selects the dense layout; otherwise at least the dense
 // width, and for the (x, y) pairs an even stride on an 8-byte aligned base (the kernels move float2).
-static int check_row_strides(const char *who, int M, int L, int P, const void *offsets, long long *ld_offsets,
-                             long long *ld_logits)
+static int check_row_strides(const char *who, const OpGeom &g, const void *offsets, long long *ld_offsets, long long *ld_logits)
 {
-    const long long dense = (long long)M * L * P;
+    const long long dense = (long long)g.M * g.L * g.P;
     if (*ld_offsets == 0) *ld_offsets = 2 * dense;
     if (*ld_logits == 0) *ld_logits = dense;
     char buf[200];
@@ -71,9 +71,16 @@ static int check_row_strides(const char *who, int M, int L, int P, const void *o
     return MSDA_OK;
 }
 
-// The D = 32 kernels move rows as 16-byte (fp32) / 8-byte (bf16) vectors and locations as (x, y) pairs.
-// Tensors straight from an allocator always qualify; a contiguous VIEW at an odd element offset does not —
+// The D = 32 kernels move rows as 16-byte (fp32) / 8-byte (bf16) vectors — grad_value by ITS storage — and locations as
+// (x, y) pairs.  Tensors straight from an allocator always qualify; a contiguous VIEW at an odd element offset does not —
 // fp32 / bf16 op calls then take the generic kernels (element-wise accesses); the prologue and wgrad entries refuse.
+template <typename VT, typename GT = VT>
+static bool rows_aligned(std::initializer_list<const void *> rows, const void *grad_value, std::initializer_list<const void *> xy)
+{
+    for (const void *p : rows) if (!aligned_to(p, sizeof(VT) * 4)) return false;
+    for (const void *p : xy) if (!aligned_to(p, 8)) return false;
+    return aligned_to(grad_value, sizeof(GT) * 4);
+}
 
 static int refuse_unaligned(const char *who)
 {
@@ -83,110 +90,100 @@ static int refuse_unaligned(const char *who)
     return set_error(MSDA_ERR_ARGUMENT, buf);
 }
 
-static bool use_d32(int N, int S, int M, int D, int L, int Lq, int P)
+static bool use_d32(const OpGeom &g) { return g_force_path != MSDA_PATH_GENERIC && d32_supported(g); }
+static bool prologue_ok(const OpGeom &g) { return g.nonempty() && g_force_path != MSDA_PATH_GENERIC && prologue_supported(g); }
+// bytes of the table a forward of this geometry leaves for its backward (msda_forward_workspace_bytes)
+static size_t table_need(const OpGeom &g, bool prologue)
 {
-    const int f = g_force_path;
-    if (f == MSDA_PATH_GENERIC) return false;
-    return d32_supported(N, S, M, D, L, Lq, P);
+    return (g.nonempty() && g_force_path != MSDA_PATH_GENERIC) ? forward_table_bytes(g, prologue) : 0;
 }
 
-template <typename T>
-static int forward_impl(const T *value, const int64_t *shapes, const int64_t *level_start,
-                        const T *loc, const T *attn, int N, int S, int M, int D, int L, int Lq, int P,
-                        T *out, hipStream_t stream, bool d32, void *table = nullptr)
+// An empty problem's outputs: the spans that have bytes are zero-filled on the stream.
+struct ZeroSpan { void *p; size_t bytes; };
+static int zero_fill(hipStream_t stream, std::initializer_list<ZeroSpan> spans)
 {
-    const void *ptrs[] = {value, shapes, level_start, loc, attn, out};
-    if (int rc = check_args(ptrs, 6, N, S, M, D, L, Lq, P)) return rc;
-    begin_call();
-    if (N == 0 || Lq == 0) return MSDA_OK;                          // empty output
-    if (S == 0) {                                                   // no pixels: every tap is outside
-        const hipError_t e = hipMemsetAsync(out, 0, sizeof(T) * (size_t)N * Lq * M * D, stream);
-        return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
+    for (const ZeroSpan &s : spans) {
+        if (s.bytes == 0) continue;
+        const hipError_t e = hipMemsetAsync(s.p, 0, s.bytes, stream);
+        if (e != hipSuccess) return set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
     }
-    if constexpr (sizeof(T) == 4) {
-        if (d32 && aligned_to(value, 16) && aligned_to(out, 16) && aligned_to(loc, 8))
-            return launch_fwd_d32<float>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, stream, table);
+    return MSDA_OK;
+}
+
+// The four bodies.  fp64 rows never take the D = 32 family; fp32 / bf16 rows take it where the geometry qualifies (use_d32)
+// and every tensor is aligned for its vector accesses, else the generic kernels.
+template <typename VT>
+static int forward_body(const OpGeom &g, const FwdTensors<VT> &t, const OpOptions &o)
+{
+    if (int rc = check_args(g, {t.value, t.shapes, t.level_start, t.loc, t.attn, t.out})) return rc;
+    begin_call();
+    if (g.N == 0 || g.Lq == 0) return MSDA_OK;                      // empty output
+    if (g.S == 0) return zero_fill(t.stream, {{t.out, sizeof(VT) * (size_t)g.items() * g.D}});   // no pixels: every tap is outside
+    void *table = table_of(o.workspace, o.ws_bytes, table_need(g, false));
+    if constexpr (sizeof(VT) != 8) {
+        if (use_d32(g) && rows_aligned<VT>({t.value, t.out}, nullptr, {t.loc})) return launch_fwd_d32<VT>(g, t, table);
     }
     // (the generic kernels write no table: a buffer the caller handed over gets its stamp cleared)
-    if (table) if (int rc = invalidate_forward_table(table, N, S, M, L, Lq, P, stream)) return rc;
-    return launch_fwd_generic<T>(value, shapes, level_start, loc, attn, N, S, M, D, L, Lq, P, out, stream);
+    if (table) if (int rc = invalidate_forward_table(table, g, t.stream)) return rc;
+    return launch_fwd_generic<VT>(g, t);
 }
 
-template <typename T>
-static int backward_impl(const T *grad_out, const T *value, const int64_t *shapes,
-                         const int64_t *level_start, const T *loc, const T *attn, int N, int S, int M,
-                         int D, int L, int Lq, int P, T *grad_value, T *grad_loc, T *grad_attn,
-                         hipStream_t stream, bool d32, void *workspace = nullptr, size_t ws_bytes = 0, unsigned flags = 0)
+template <typename VT, typename GT>
+static int backward_body(const OpGeom &g, const BwdTensors<VT, GT> &t, const OpOptions &o)
 {
-    const void *ptrs[] = {grad_out, value, shapes, level_start, loc, attn, grad_value, grad_loc, grad_attn};
-    if (int rc = check_args(ptrs, 9, N, S, M, D, L, Lq, P)) return rc;
+    if (int rc = check_args(g, {t.grad_out, t.value, t.shapes, t.level_start, t.loc, t.attn, t.grad_value, t.grad_loc, t.grad_attn}))
+        return rc;
     begin_call();
-    if (N == 0) return MSDA_OK;
-    if (Lq == 0 || S == 0) {                                        // no contributions at all
-        hipError_t e = hipSuccess;
-        if (S > 0) e = hipMemsetAsync(grad_value, 0, sizeof(T) * (size_t)N * S * M * D, stream);
-        if (e == hipSuccess && Lq > 0) {
-            e = hipMemsetAsync(grad_loc, 0, sizeof(T) * (size_t)N * Lq * M * L * P * 2, stream);
-            if (e == hipSuccess)
-                e = hipMemsetAsync(grad_attn, 0, sizeof(T) * (size_t)N * Lq * M * L * P, stream);
-        }
-        return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
+    if (g.N == 0) return MSDA_OK;
+    if (g.Lq == 0 || g.S == 0) {                                    // no contributions at all
+        const size_t points = (size_t)g.items() * g.L * g.P, real = sizeof(op_real_t<VT>);
+        return zero_fill(t.stream, {{t.grad_value, sizeof(GT) * (size_t)g.N * g.S * g.M * g.D}, {t.grad_loc, real * points * 2},
+                                    {t.grad_attn, real * points}});
     }
-    if constexpr (sizeof(T) == 4) {
-        if (d32 && aligned_to(grad_out, 16) && aligned_to(value, 16) && aligned_to(grad_value, 16) && aligned_to(loc, 8) &&
-            aligned_to(grad_loc, 8))
-        {
-            return launch_bwd_d32<float, float>(grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                                grad_loc, grad_attn, stream, (flags & MSDA_FLAG_DETERMINISTIC) != 0, workspace,
-                                                ws_bytes, (flags & MSDA_FLAG_FORWARD_TABLE) != 0,
-                                                (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
-        }
+    if constexpr (sizeof(VT) != 8) {
+        if (use_d32(g) && rows_aligned<VT, GT>({t.grad_out, t.value}, t.grad_value, {t.loc, t.grad_loc}))
+            return launch_bwd_d32<VT, GT>(g, t, o);
     }
-    return launch_bwd_generic<T>(grad_out, value, shapes, level_start, loc, attn, N, S, M, D, L, Lq, P,
-                                 grad_value, grad_loc, grad_attn, stream, (flags & MSDA_FLAG_DETERMINISTIC) != 0);
+    if constexpr (sizeof(GT) == 2)
+        return set_error(MSDA_ERR_ARGUMENT, "msda_backward_bf16: bf16 grad_value needs the D=32 kernel family (D == 32, "
+                                            "L <= 16, L*P <= 32, 8-byte aligned rows); msda_backward_bf16_gv32 serves "
+                                            "every other shape");
+    else                                                            // element-wise accesses: any D, any element offset
+        return launch_bwd_generic<VT>(g, t, o);
+}
+
+static int refuse_geometry(const char *who)
+{
+    char buf[120];
+    std::snprintf(buf, sizeof(buf), "%s: geometry not supported (msda_prologue_supported)", who);
+    return set_error(MSDA_ERR_ARGUMENT, buf);
+}
+
+// who: the entry's name in messages (the _ws_ forms report under the plain names).  t by value: the row strides are resolved here.
+template <typename VT>
+static int forward_prologue_body(const char *who, const OpGeom &g, FwdTensors<VT> t, const OpOptions &o)
+{
+    if (int rc = check_args(g, {t.value, t.shapes, t.level_start, t.ref, t.loc, t.attn, t.out, t.loc_out, t.attn_out})) return rc;
+    if (!prologue_ok(g)) return refuse_geometry(who);
+    if (int rc = check_row_strides(who, g, t.loc, &t.ld_offsets, &t.ld_logits)) return rc;
+    if (!rows_aligned<VT>({t.value, t.out}, nullptr, {t.ref, t.loc_out})) return refuse_unaligned(who);
+    begin_call();
+    return launch_fwd_prologue<VT>(g, t, table_of(o.workspace, o.ws_bytes, table_need(g, true)));
+}
+
+template <typename VT>
+static int backward_prologue_body(const char *who, const OpGeom &g, BwdTensors<VT, float> t, const OpOptions &o)
+{
+    if (int rc = check_args(g, {t.grad_out, t.value, t.shapes, t.level_start, t.loc, t.attn, t.grad_value, t.grad_loc, t.grad_attn,
+                                t.grad_ref})) return rc;
+    if (!prologue_ok(g)) return refuse_geometry(who);
+    if (int rc = check_row_strides(who, g, t.grad_loc, &t.ld_grad_offsets, &t.ld_grad_logits)) return rc;
+    if (!rows_aligned<VT, float>({t.grad_out, t.value}, t.grad_value, {t.loc, t.grad_ref})) return refuse_unaligned(who);
+    begin_call();
+    return launch_bwd_prologue<VT>(g, t, o);
 }
 
 }  // namespace msda
-
-template <typename GT>
-static int backward_bf16_impl(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
-                              const int64_t *level_start, const float *sampling_loc, const float *attn_weight, int N,
-                              int S, int M, int D, int L, int Lq, int P, GT *grad_value, float *grad_sampling_loc,
-                              float *grad_attn_weight, msda_stream_t stream, void *workspace = nullptr, size_t ws_bytes = 0,
-                              unsigned flags = 0)
-{
-    const void *ptrs[] = {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
-                          grad_sampling_loc, grad_attn_weight};
-    if (int rc = msda::check_args(ptrs, 9, N, S, M, D, L, Lq, P)) return rc;
-    msda::begin_call();
-    if (N == 0) return MSDA_OK;
-    if (Lq == 0 || S == 0) {
-        hipError_t e = hipSuccess;
-        if (S > 0) e = hipMemsetAsync(grad_value, 0, sizeof(GT) * (size_t)N * S * M * D, (hipStream_t)stream);
-        if (e == hipSuccess && Lq > 0) {
-            e = hipMemsetAsync(grad_sampling_loc, 0, 4 * (size_t)N * Lq * M * L * P * 2, (hipStream_t)stream);
-            if (e == hipSuccess) e = hipMemsetAsync(grad_attn_weight, 0, 4 * (size_t)N * Lq * M * L * P, (hipStream_t)stream);
-        }
-        return e == hipSuccess ? MSDA_OK : msda::set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
-    }
-    const bool d32 = msda::use_d32(N, S, M, D, L, Lq, P) && msda::aligned_to(grad_out, 8) && msda::aligned_to(value, 8) &&
-                     msda::aligned_to(grad_value, sizeof(GT) * 4) && msda::aligned_to(sampling_loc, 8) &&
-                     msda::aligned_to(grad_sampling_loc, 8);
-    if (!d32) {
-        if constexpr (sizeof(GT) == 2)
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_backward_bf16: bf16 grad_value needs the D=32 kernel family (D == 32, "
-                                                      "L <= 16, L*P <= 32, 8-byte aligned rows); msda_backward_bf16_gv32 serves "
-                                                      "every other shape");
-        else                                                        // element-wise accesses: any D, any element offset
-            return msda::launch_bwd_generic<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N,
-                                                   S, M, D, L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight,
-                                                   (hipStream_t)stream, (flags & MSDA_FLAG_DETERMINISTIC) != 0);
-    }
-    return msda::launch_bwd_d32<uint16_t, GT>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
-                                              Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream,
-                                              (flags & MSDA_FLAG_DETERMINISTIC) != 0, workspace, ws_bytes,
-                                              (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
-}
 
 extern "C" {
 
@@ -194,9 +191,8 @@ int msda_forward_f32(const float *value, const int64_t *spatial_shapes, const in
                      const float *sampling_loc, const float *attn_weight, int N, int S, int M, int D,
                      int L, int Lq, int P, float *out, msda_stream_t stream)
 {
-    return msda::forward_impl<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S,
-                                     M, D, L, Lq, P, out, (hipStream_t)stream,
-                                     msda::use_d32(N, S, M, D, L, Lq, P));
+    return msda::forward_body<float>({N, S, M, D, L, Lq, P}, {value, spatial_shapes, level_start, sampling_loc, attn_weight, out,
+                                                              (hipStream_t)stream}, {});
 }
 
 int msda_backward_f32(const float *grad_out, const float *value, const int64_t *spatial_shapes,
@@ -204,18 +200,16 @@ int msda_backward_f32(const float *grad_out, const float *value, const int64_t *
                       int N, int S, int M, int D, int L, int Lq, int P, float *grad_value,
                       float *grad_sampling_loc, float *grad_attn_weight, msda_stream_t stream)
 {
-    return msda::backward_impl<float>(grad_out, value, spatial_shapes, level_start, sampling_loc,
-                                      attn_weight, N, S, M, D, L, Lq, P, grad_value, grad_sampling_loc,
-                                      grad_attn_weight, (hipStream_t)stream,
-                                      msda::use_d32(N, S, M, D, L, Lq, P));
+    return msda_backward_ws_f32(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
+                                grad_value, grad_sampling_loc, grad_attn_weight, nullptr, 0, 0, stream);
 }
 
 int msda_forward_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start,
                      const double *sampling_loc, const double *attn_weight, int N, int S, int M, int D,
                      int L, int Lq, int P, double *out, msda_stream_t stream)
 {
-    return msda::forward_impl<double>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S,
-                                      M, D, L, Lq, P, out, (hipStream_t)stream, false);
+    return msda::forward_body<double>({N, S, M, D, L, Lq, P}, {value, spatial_shapes, level_start, sampling_loc, attn_weight, out,
+                                                               (hipStream_t)stream}, {});
 }
 
 int msda_backward_f64(const double *grad_out, const double *value, const int64_t *spatial_shapes,
@@ -224,66 +218,38 @@ int msda_backward_f64(const double *grad_out, const double *value, const int64_t
                       double *grad_value, double *grad_sampling_loc, double *grad_attn_weight,
                       msda_stream_t stream)
 {
-    return msda::backward_impl<double>(grad_out, value, spatial_shapes, level_start, sampling_loc,
-                                       attn_weight, N, S, M, D, L, Lq, P, grad_value, grad_sampling_loc,
-                                       grad_attn_weight, (hipStream_t)stream, false);
-}
-
-static int forward_bf16_impl(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                             const float *sampling_loc, const float *attn_weight, int N, int S, int M, int D, int L,
-                             int Lq, int P, uint16_t *out, msda_stream_t stream, void *table)
-{
-    const void *ptrs[] = {value, spatial_shapes, level_start, sampling_loc, attn_weight, out};
-    if (int rc = msda::check_args(ptrs, 6, N, S, M, D, L, Lq, P)) return rc;
-    msda::begin_call();
-    if (N == 0 || Lq == 0) return MSDA_OK;
-    if (S == 0) {
-        const hipError_t e = hipMemsetAsync(out, 0, 2 * (size_t)N * Lq * M * D, (hipStream_t)stream);
-        return e == hipSuccess ? MSDA_OK : msda::set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
-    }
-    if (!msda::use_d32(N, S, M, D, L, Lq, P) || !msda::aligned_to(value, 8) || !msda::aligned_to(out, 8) ||
-        !msda::aligned_to(sampling_loc, 8)) {
-        // (the generic kernels write no table: a buffer the caller handed over gets its stamp cleared)
-        if (table) if (int rc = msda::invalidate_forward_table(table, N, S, M, L, Lq, P, (hipStream_t)stream)) return rc;
-        return msda::launch_fwd_generic<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq,
-                                               P, out, (hipStream_t)stream);
-    }
-    return msda::launch_fwd_d32<uint16_t>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L, Lq, P,
-                                          out, (hipStream_t)stream, table);
+    return msda_backward_ws_f64(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
+                                grad_value, grad_sampling_loc, grad_attn_weight, nullptr, 0, 0, stream);
 }
 
 int msda_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
                       const float *sampling_loc, const float *attn_weight, int N, int S, int M, int D, int L,
                       int Lq, int P, uint16_t *out, msda_stream_t stream)
 {
-    return forward_bf16_impl(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, out, stream, nullptr);
+    return msda::forward_body<uint16_t>({N, S, M, D, L, Lq, P}, {value, spatial_shapes, level_start, sampling_loc, attn_weight, out,
+                                                                 (hipStream_t)stream}, {});
 }
 
 // ---- forward that leaves the point table for the backward of the same autograd node (include/msda.h) ----
 unsigned long long msda_forward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags)
 {
-    if (N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return 0;
-    if (msda::g_force_path == MSDA_PATH_GENERIC) return 0;
-    return (unsigned long long)msda::forward_table_bytes(N, S, M, D, L, Lq, P, (flags & MSDA_FLAG_PROLOGUE) != 0);
+    return (unsigned long long)msda::table_need({N, S, M, D, L, Lq, P}, (flags & MSDA_FLAG_PROLOGUE) != 0);
 }
 
 int msda_forward_ws_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start, const float *sampling_loc,
                         const float *attn_weight, int N, int S, int M, int D, int L, int Lq, int P, float *out, void *workspace,
                         unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    return msda::forward_impl<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, out,
-                                     (hipStream_t)stream, msda::use_d32(N, S, M, D, L, Lq, P),
-                                     msda::table_of(workspace, (size_t)workspace_bytes,
-                                                    (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, 0)));
+    return msda::forward_body<float>({N, S, M, D, L, Lq, P}, {value, spatial_shapes, level_start, sampling_loc, attn_weight, out,
+                                                              (hipStream_t)stream}, {workspace, workspace_bytes});
 }
 
 int msda_forward_ws_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start, const float *sampling_loc,
                          const float *attn_weight, int N, int S, int M, int D, int L, int Lq, int P, uint16_t *out, void *workspace,
                          unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    return forward_bf16_impl(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, out, stream,
-                             msda::table_of(workspace, (size_t)workspace_bytes,
-                                            (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, 0)));
+    return msda::forward_body<uint16_t>({N, S, M, D, L, Lq, P}, {value, spatial_shapes, level_start, sampling_loc, attn_weight, out,
+                                                                 (hipStream_t)stream}, {workspace, workspace_bytes});
 }
 
 int msda_backward_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -291,8 +257,8 @@ int msda_backward_bf16(const uint16_t *grad_out, const uint16_t *value, const in
                        int S, int M, int D, int L, int Lq, int P, uint16_t *grad_value, float *grad_sampling_loc,
                        float *grad_attn_weight, msda_stream_t stream)
 {
-    return backward_bf16_impl<uint16_t>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D,
-                                        L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, stream);
+    return msda_backward_ws_bf16(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
+                                 grad_value, grad_sampling_loc, grad_attn_weight, nullptr, 0, 0, stream);
 }
 
 int msda_backward_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -300,28 +266,28 @@ int msda_backward_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, con
                             int S, int M, int D, int L, int Lq, int P, float *grad_value, float *grad_sampling_loc,
                             float *grad_attn_weight, msda_stream_t stream)
 {
-    return backward_bf16_impl<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L,
-                                     Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, stream);
+    return msda_backward_ws_bf16_gv32(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
+                                      grad_value, grad_sampling_loc, grad_attn_weight, nullptr, 0, 0, stream);
 }
 
 int msda_backward_passes(int Lq, int P) { return (Lq > 0 && P > 0) ? msda::backward_passes(Lq, P) : 0; }
 
 unsigned long long msda_backward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags)
 {
-    if (N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return 0;
-    if (msda::g_force_path == MSDA_PATH_GENERIC) return 0;
+    const msda::OpGeom g{N, S, M, D, L, Lq, P};
+    if (!g.nonempty() || msda::g_force_path == MSDA_PATH_GENERIC) return 0;
     // with MSDA_FLAG_FORWARD_TABLE: the forward's table (rounded up to 256 bytes) first, the call's scratch behind it
-    const bool prologue = (flags & MSDA_FLAG_PROLOGUE) != 0;
-    const size_t table = (flags & MSDA_FLAG_FORWARD_TABLE) ? msda::forward_table_bytes(N, S, M, D, L, Lq, P, prologue) : 0;
-    const size_t scratch = msda::backward_workspace_bytes(N, S, M, D, L, Lq, P, flags);
+    const size_t table = (flags & MSDA_FLAG_FORWARD_TABLE) ? msda::forward_table_bytes(g, (flags & MSDA_FLAG_PROLOGUE) != 0) : 0;
+    const size_t scratch = msda::backward_workspace_bytes(g, flags);
     if (table == 0) return (unsigned long long)scratch;
     return (unsigned long long)(scratch ? msda::table_span(table) + scratch : table);
 }
 
 int msda_deterministic_supported(int elem_bytes, int N, int S, int M, int D, int L, int Lq, int P)
 {
-    if (N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return 1;              // (nothing to order)
-    if (elem_bytes != 8 && msda::g_force_path != MSDA_PATH_GENERIC && msda::d32_supported(N, S, M, D, L, Lq, P)) return 1;
+    const msda::OpGeom g{N, S, M, D, L, Lq, P};
+    if (!g.nonempty()) return 1;                                                                      // (nothing to order)
+    if (elem_bytes != 8 && msda::use_d32(g)) return 1;
     return (double)N * (double)S * (double)M * (double)Lq * (double)P <= 68719476736.0 ? 1 : 0;      // msda_generic.hip: 2^36 point tests
 }
 
@@ -331,9 +297,10 @@ int msda_backward_ws_f32(const float *grad_out, const float *value, const int64_
                          float *grad_sampling_loc, float *grad_attn_weight, void *workspace,
                          unsigned long long workspace_bytes, unsigned flags, msda_stream_t stream)
 {
-    return msda::backward_impl<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D,
-                                      L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream,
-                                      msda::use_d32(N, S, M, D, L, Lq, P), workspace, (size_t)workspace_bytes, flags);
+    return msda::backward_body<float, float>({N, S, M, D, L, Lq, P},
+                                             {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
+                                              grad_sampling_loc, grad_attn_weight, (hipStream_t)stream},
+                                             {workspace, workspace_bytes, flags});
 }
 
 int msda_backward_ws_f64(const double *grad_out, const double *value, const int64_t *spatial_shapes,
@@ -342,9 +309,10 @@ int msda_backward_ws_f64(const double *grad_out, const double *value, const int6
                          double *grad_sampling_loc, double *grad_attn_weight, void *workspace,
                          unsigned long long workspace_bytes, unsigned flags, msda_stream_t stream)
 {
-    return msda::backward_impl<double>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D,
-                                       L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream, false,
-                                       workspace, (size_t)workspace_bytes, flags);
+    return msda::backward_body<double, double>({N, S, M, D, L, Lq, P},
+                                               {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
+                                                grad_sampling_loc, grad_attn_weight, (hipStream_t)stream},
+                                               {workspace, workspace_bytes, flags});
 }
 
 int msda_backward_ws_bf16(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -353,9 +321,10 @@ int msda_backward_ws_bf16(const uint16_t *grad_out, const uint16_t *value, const
                           float *grad_attn_weight, void *workspace, unsigned long long workspace_bytes,
                           unsigned flags, msda_stream_t stream)
 {
-    return backward_bf16_impl<uint16_t>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D,
-                                        L, Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, stream, workspace,
-                                        (size_t)workspace_bytes, flags);
+    return msda::backward_body<uint16_t, uint16_t>({N, S, M, D, L, Lq, P},
+                                                   {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight,
+                                                    grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream},
+                                                   {workspace, workspace_bytes, flags});
 }
 
 int msda_backward_ws_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -364,19 +333,13 @@ int msda_backward_ws_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, 
                                float *grad_attn_weight, void *workspace, unsigned long long workspace_bytes,
                                unsigned flags, msda_stream_t stream)
 {
-    return backward_bf16_impl<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L,
-                                     Lq, P, grad_value, grad_sampling_loc, grad_attn_weight, stream, workspace,
-                                     (size_t)workspace_bytes, flags);
+    return msda::backward_body<uint16_t, float>({N, S, M, D, L, Lq, P},
+                                                {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight,
+                                                 grad_value, grad_sampling_loc, grad_attn_weight, (hipStream_t)stream},
+                                                {workspace, workspace_bytes, flags});
 }
 
-
-
-int msda_prologue_supported(int N, int S, int M, int D, int L, int Lq, int P)
-{
-    if (N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return 0;
-    if (msda::g_force_path == MSDA_PATH_GENERIC) return 0;
-    return msda::prologue_supported(N, S, M, D, L, Lq, P) ? 1 : 0;
-}
+int msda_prologue_supported(int N, int S, int M, int D, int L, int Lq, int P) { return msda::prologue_ok({N, S, M, D, L, Lq, P}) ? 1 : 0; }
 
 int msda_forward_prologue_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
                               const float *reference_points, const float *sampling_offsets, const float *attn_logits,
@@ -393,20 +356,10 @@ int msda_forward_prologue_ws_f32(const float *value, const int64_t *spatial_shap
                                  float *out, float *sampling_loc_out, float *attn_weight_out, void *workspace,
                                  unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    const void *ptrs[] = {value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits, out,
-                          sampling_loc_out, attn_weight_out};
-    if (int rc = msda::check_args(ptrs, 9, N, S, M, D, L, Lq, P)) return rc;
-    if (!msda_prologue_supported(N, S, M, D, L, Lq, P))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_forward_prologue_f32: geometry not supported (msda_prologue_supported)");
-    if (int rc = msda::check_row_strides("msda_forward_prologue_f32", M, L, P, sampling_offsets, &ld_offsets, &ld_logits)) return rc;
-    if (!msda::aligned_to(value, 16) || !msda::aligned_to(out, 16) || !msda::aligned_to(reference_points, 8) ||
-        !msda::aligned_to(sampling_loc_out, 8))
-        return msda::refuse_unaligned("msda_forward_prologue_f32");
-    msda::begin_call();
-    const size_t table = (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, MSDA_FLAG_PROLOGUE);
-    return msda::launch_fwd_prologue<float>(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits, N,
-                                            S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
-                                            (hipStream_t)stream, msda::table_of(workspace, (size_t)workspace_bytes, table));
+    return msda::forward_prologue_body<float>("msda_forward_prologue_f32", {N, S, M, D, L, Lq, P},
+                                              {value, spatial_shapes, level_start, sampling_offsets, attn_logits, out, (hipStream_t)stream,
+                                               reference_points, sampling_loc_out, attn_weight_out, ld_offsets, ld_logits},
+                                              {workspace, workspace_bytes});
 }
 
 int msda_backward_prologue_f32(const float *grad_out, const float *value, const int64_t *spatial_shapes,
@@ -427,22 +380,11 @@ int msda_backward_prologue_ws_f32(const float *grad_out, const float *value, con
                                   float *grad_attn_logits, float *grad_reference_points, void *workspace,
                                   unsigned long long workspace_bytes, unsigned flags, msda_stream_t stream)
 {
-    const void *ptrs[] = {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
-                          grad_sampling_offsets, grad_attn_logits, grad_reference_points};
-    if (int rc = msda::check_args(ptrs, 10, N, S, M, D, L, Lq, P)) return rc;
-    if (!msda_prologue_supported(N, S, M, D, L, Lq, P))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_backward_prologue_f32: geometry not supported (msda_prologue_supported)");
-    if (int rc = msda::check_row_strides("msda_backward_prologue_f32", M, L, P, grad_sampling_offsets, &ld_grad_offsets,
-                                         &ld_grad_logits)) return rc;
-    if (!msda::aligned_to(grad_out, 16) || !msda::aligned_to(value, 16) || !msda::aligned_to(grad_value, 16) ||
-        !msda::aligned_to(sampling_loc, 8) || !msda::aligned_to(grad_reference_points, 8))
-        return msda::refuse_unaligned("msda_backward_prologue_f32");
-    msda::begin_call();
-    return msda::launch_bwd_prologue<float>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
-                                            Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets, grad_attn_logits,
-                                            grad_reference_points, (hipStream_t)stream, workspace, (size_t)workspace_bytes,
-                                            (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                            (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+    return msda::backward_prologue_body<float>("msda_backward_prologue_f32", {N, S, M, D, L, Lq, P},
+                                               {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
+                                                grad_sampling_offsets, grad_attn_logits, (hipStream_t)stream, grad_reference_points,
+                                                ld_grad_offsets, ld_grad_logits},
+                                               {workspace, workspace_bytes, flags});
 }
 
 int msda_forward_prologue_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -460,20 +402,10 @@ int msda_forward_prologue_ws_bf16(const uint16_t *value, const int64_t *spatial_
                                   uint16_t *out, float *sampling_loc_out, float *attn_weight_out, void *workspace,
                                   unsigned long long workspace_bytes, msda_stream_t stream)
 {
-    const void *ptrs[] = {value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits, out,
-                          sampling_loc_out, attn_weight_out};
-    if (int rc = msda::check_args(ptrs, 9, N, S, M, D, L, Lq, P)) return rc;
-    if (!msda_prologue_supported(N, S, M, D, L, Lq, P))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_forward_prologue_bf16: geometry not supported (msda_prologue_supported)");
-    if (int rc = msda::check_row_strides("msda_forward_prologue_bf16", M, L, P, sampling_offsets, &ld_offsets, &ld_logits)) return rc;
-    if (!msda::aligned_to(value, 8) || !msda::aligned_to(out, 8) || !msda::aligned_to(reference_points, 8) ||
-        !msda::aligned_to(sampling_loc_out, 8))
-        return msda::refuse_unaligned("msda_forward_prologue_bf16");
-    msda::begin_call();
-    const size_t table = (size_t)msda_forward_workspace_bytes(N, S, M, D, L, Lq, P, MSDA_FLAG_PROLOGUE);
-    return msda::launch_fwd_prologue<uint16_t>(value, spatial_shapes, level_start, reference_points, sampling_offsets, attn_logits,
-                                               N, S, M, L, Lq, P, ld_offsets, ld_logits, out, sampling_loc_out, attn_weight_out,
-                                               (hipStream_t)stream, msda::table_of(workspace, (size_t)workspace_bytes, table));
+    return msda::forward_prologue_body<uint16_t>("msda_forward_prologue_bf16", {N, S, M, D, L, Lq, P},
+                                                 {value, spatial_shapes, level_start, sampling_offsets, attn_logits, out, (hipStream_t)stream,
+                                                  reference_points, sampling_loc_out, attn_weight_out, ld_offsets, ld_logits},
+                                                 {workspace, workspace_bytes});
 }
 
 int msda_backward_prologue_bf16_gv32(const uint16_t *grad_out, const uint16_t *value, const int64_t *spatial_shapes,
@@ -483,22 +415,11 @@ int msda_backward_prologue_bf16_gv32(const uint16_t *grad_out, const uint16_t *v
                                      float *grad_attn_logits, float *grad_reference_points, void *workspace,
                                      unsigned long long workspace_bytes, unsigned flags, msda_stream_t stream)
 {
-    const void *ptrs[] = {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
-                          grad_sampling_offsets, grad_attn_logits, grad_reference_points};
-    if (int rc = msda::check_args(ptrs, 10, N, S, M, D, L, Lq, P)) return rc;
-    if (!msda_prologue_supported(N, S, M, D, L, Lq, P))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_backward_prologue_bf16_gv32: geometry not supported (msda_prologue_supported)");
-    if (int rc = msda::check_row_strides("msda_backward_prologue_bf16_gv32", M, L, P, grad_sampling_offsets, &ld_grad_offsets,
-                                         &ld_grad_logits)) return rc;
-    if (!msda::aligned_to(grad_out, 8) || !msda::aligned_to(value, 8) || !msda::aligned_to(grad_value, 16) ||
-        !msda::aligned_to(sampling_loc, 8) || !msda::aligned_to(grad_reference_points, 8))
-        return msda::refuse_unaligned("msda_backward_prologue_bf16_gv32");
-    msda::begin_call();
-    return msda::launch_bwd_prologue<uint16_t>(grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, L,
-                                               Lq, P, grad_value, ld_grad_offsets, ld_grad_logits, grad_sampling_offsets, grad_attn_logits,
-                                               grad_reference_points, (hipStream_t)stream, workspace, (size_t)workspace_bytes,
-                                               (flags & MSDA_FLAG_FORWARD_TABLE) != 0, (flags & MSDA_FLAG_DETERMINISTIC) != 0,
-                                               (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+    return msda::backward_prologue_body<uint16_t>("msda_backward_prologue_bf16_gv32", {N, S, M, D, L, Lq, P},
+                                                  {grad_out, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_value,
+                                                   grad_sampling_offsets, grad_attn_logits, (hipStream_t)stream, grad_reference_points,
+                                                   ld_grad_offsets, ld_grad_logits},
+                                                  {workspace, workspace_bytes, flags});
 }
 
 unsigned long long msda_linear_wgrad_workspace_bytes(int M, int N, int K)
@@ -812,7 +733,7 @@ int msda_version(void) { return MSDA_ABI_VERSION; }
 int msda_path_for(int elem_bytes, int M, int D, int L, int P)
 {
     // N, S, Lq only matter through the int32-offset limits; probe with small ones.
-    return ((elem_bytes == 4 || elem_bytes == 2) && msda::use_d32(1, 1, M, D, L, 1, P)) ? MSDA_PATH_D32 : MSDA_PATH_GENERIC;
+    return ((elem_bytes == 4 || elem_bytes == 2) && msda::use_d32({1, 1, M, D, L, 1, P})) ? MSDA_PATH_D32 : MSDA_PATH_GENERIC;
 }
 
 void msda_force_path(int path) { msda::g_force_path = path; }
@@ -824,18 +745,19 @@ int msda_describe_plan(int row_bytes, int grad_value_bytes, int N, int S, int M,
 {
     if (!buf || buf_len <= 0) return 0;
     buf[0] = 0;
-    if (N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return 0;
-    if ((row_bytes != 4 && row_bytes != 2) || msda::g_force_path == MSDA_PATH_GENERIC || !msda::use_d32(N, S, M, D, L, Lq, P)) {
+    const msda::OpGeom g{N, S, M, D, L, Lq, P};
+    if (!g.nonempty()) return 0;
+    if ((row_bytes != 4 && row_bytes != 2) || !msda::use_d32(g)) {
         const int k = snprintf(buf, (size_t)buf_len, "generic");
         return k < buf_len ? k : buf_len - 1;
     }
     const bool prologue = (flags & MSDA_FLAG_PROLOGUE) != 0;
-    if (prologue && !msda::prologue_supported(N, S, M, D, L, Lq, P)) {
+    if (prologue && !msda::prologue_supported(g)) {
         const int k = snprintf(buf, (size_t)buf_len, "prologue unsupported");
         return k < buf_len ? k : buf_len - 1;
     }
-    const int k = msda::describe_plan(row_bytes, row_bytes == 4 ? 4 : grad_value_bytes, N, S, M, L, Lq, P, prologue, has_workspace != 0,
-                                      (flags & MSDA_FLAG_DETERMINISTIC) != 0, buf, buf_len, (flags & MSDA_FLAG_EXACT_NONFINITE) != 0);
+    const int k = msda::describe_plan(row_bytes, row_bytes == 4 ? 4 : grad_value_bytes, g, prologue,
+                                      msda::OpOptions(nullptr, has_workspace != 0, flags), buf, buf_len);
     return k < buf_len ? k : buf_len - 1;
 }
 

@@ -728,10 +728,11 @@ __global__ __launch_bounds__(kSBlock, 4) void bwd_fused_lds_d32_kernel(
 // host side
 // ------------------------------------------------------------------------------------------
 #if MSDA_D32_HAS(0)
-bool d32_supported(int N, int S, int M, int D, int L, int Lq, int P)
+bool d32_supported(const OpGeom &g)
 {
-    if (D != kD || L > kMaxLevels || L * P > 32) return false;
-    const long long items = (long long)N * Lq * M;
+    const int N = g.N, S = g.S, M = g.M, L = g.L, Lq = g.Lq, P = g.P;
+    if (g.D != kD || L > kMaxLevels || L * P > 32) return false;
+    const long long items = g.items();
     if ((long long)N * S * M * kD >= (1LL << 31)) return false;        // int32 element offsets (value / grad_value)
     if (items * kD >= (1LL << 31)) return false;                       // ... and of out / grad_out rows (q * M*32 in role B's gathers)
     if (items * L * P * 2 >= (1LL << 31) || items >= (1LL << 30)) return false;
@@ -749,36 +750,32 @@ bool d32_supported(int N, int S, int M, int D, int L, int Lq, int P)
 
 // Every MSDA_* knob named in this file is read in DIAGNOSTIC builds only (-DMSDA_TUNING, msda_launch.h); the shipped
 // library gets the defaults.
-static int env_int(const char *name, int dflt) { return tuning_int(name, dflt); }
-
 static int bwd_target_wgs()
 {
-    static const int v = [] { int t = env_int("MSDA_BWD_WGS", 256); return t < 1 ? 1 : t; }();
+    static const int v = [] { int t = tuning_int("MSDA_BWD_WGS", 256); return t < 1 ? 1 : t; }();
     return v;
 }
 
 // coarse levels on the matrix cores (msda_d32_dense.h); MSDA_DENSE=0: every level through the sort + gather bodies (A/B knob)
 static int dense_on()
 {
-    static const int v = env_int("MSDA_DENSE", 1) != 0;
+    static const int v = tuning_int("MSDA_DENSE", 1) != 0;
     return v;
 }
 
 // XCD-aware workgroup numbering (xcd_block); MSDA_XCD=0 keeps the hardware's round-robin order (A/B knob)
 static int xcd_remap()
 {
-    static const int v = env_int("MSDA_XCD", 1) != 0;
+    static const int v = tuning_int("MSDA_XCD", 1) != 0;
     return v;
 }
-
-static int pow2_shift(int x) { return (x > 0 && (x & (x - 1)) == 0) ? __builtin_ctz((unsigned)x) : -1; }
 
 // Wavefronts per octet (SPLIT).  Small problems are latency-bound: more wavefronts with fewer
 // points each keep more row loads in flight; large ones want no cross-wave reduction.
 // MSDA_SPLIT=1|2|4 overrides (tuning knob, read once).
 static int pick_split(int items, int LP)
 {
-    static const int forced = env_int("MSDA_SPLIT", 0);
+    static const int forced = tuning_int("MSDA_SPLIT", 0);
     if (forced == 1 || forced == 2 || forced == 4) return (LP >= forced) ? forced : 1;
     const int octets = (items + 7) / 8;
     if (LP >= 4 && octets <= 2048) return 4;
@@ -804,11 +801,12 @@ static int allow_lds(const void *fn, size_t bytes)
 // CU, 512 threads each) unless that would leave fewer than one sub-batch per workgroup; MSDA_LDS=0/1 overrides (tuning).
 struct LdsPlan { bool use; int chunks, qw, stage_rows; size_t lds; };
 template <typename VT>
-static LdsPlan plan_lds(int N, int S, int M, int L, int Lq, int P, long long role_b_wgs = 0)
+static LdsPlan plan_lds(const OpGeom &g, long long role_b_wgs = 0)
 {
-    static const int mode = env_int("MSDA_LDS", -1);
-    static const int target_alone = env_int("MSDA_LDS_WGS", 512);        // two 512-thread workgroups per CU: ONE round
-    static const int target_fused = env_int("MSDA_LDS_WGS_BWD", 0);      // role A inside the fused backward launch (0: rule below)
+    const int N = g.N, S = g.S, M = g.M, L = g.L, Lq = g.Lq, P = g.P;
+    static const int mode = tuning_int("MSDA_LDS", -1);
+    static const int target_alone = tuning_int("MSDA_LDS_WGS", 512);        // two 512-thread workgroups per CU: ONE round
+    static const int target_fused = tuning_int("MSDA_LDS_WGS_BWD", 0);      // role A inside the fused backward launch (0: rule below)
     // Inside the fused backward role B's workgroups are dispatched first.  If they leave slots free (a launch of fewer than
     // the 512 resident workgroups), role A gets one round in exactly those slots; behind several rounds of role B it is cut
     // finer, so that the launch does not end on a few long role-A workgroups (cfg-2 encoder: 384 role-B workgroups -> 128
@@ -848,19 +846,19 @@ static LdsPlan plan_lds(int N, int S, int M, int L, int Lq, int P, long long rol
 struct ValuePlan { int W, tp_cap, ppt, acc; size_t lds; };
 
 template <typename VT>
-static ValuePlan plan_value(int N, int S, int M, int L, int Lq, int P, int target_wgs, bool det = false)
+static ValuePlan plan_value(const OpGeom &g, int target_wgs, bool det = false)
 {
     ValuePlan pl;
-    const int NP = Lq * P, pairs_levels = N * M * L;
+    const int S = g.S, NP = g.Lq * g.P, pairs_levels = g.N * g.M * g.L;
     const bool multipass = NP > kSingleMaxPoints;
-    static const int wide = env_int("MSDA_BWD_WIDE", 1);             // A/B knob: 0 = the chunked kAccRmw passes
+    static const int wide = tuning_int("MSDA_BWD_WIDE", 1);             // A/B knob: 0 = the chunked kAccRmw passes
     pl.acc = !multipass ? kAccNone : (sizeof(VT) == 4 ? (wide ? kAccWide : kAccRmw) : kAccTile);
     if (pl.acc == kAccWide) {
         // enough ranges per level that the taps a workgroup keeps (4*NP/W on average) fit its record array with
         // 15 % to spare, and at least one workgroup per CU.  No more than that: every range re-scans its level
         // (cfg-2 encoder: 67 us with 6 ranges = 384 workgroups, 73 with 8 = 512, 84 with 12; role A's workgroups take
         // the free slots from the start)
-        static const int wide_wgs = env_int("MSDA_WIDE_WGS", 1);     // x target_wgs
+        static const int wide_wgs = tuning_int("MSDA_WIDE_WGS", 1);     // x target_wgs
         const int w_max = max(1, S / 16);
         pl.W = max(1, min(max(ceil_div(S, kSingleMaxRows), ceil_div(wide_wgs * target_wgs, pairs_levels)), w_max));
         for (;; ++pl.W) {                                            // the record capacity depends on the rows per range
@@ -884,7 +882,7 @@ static ValuePlan plan_value(int N, int S, int M, int L, int Lq, int P, int targe
         pl.W = max(ceil_div(S, kSingleMaxRows), ceil_div(multipass ? 2 * target_wgs : target_wgs, pairs_levels));
         pl.W = max(1, min(pl.W, max(1, S / 16)));
         pl.tp_cap = ceil_div(S, pl.W);
-        static const int force_ppt = env_int("MSDA_BWD_PPT", 0);         // tuning knob: kSinglePPT or kMultiPPT
+        static const int force_ppt = tuning_int("MSDA_BWD_PPT", 0);         // tuning knob: kSinglePPT or kMultiPPT
         pl.ppt = (multipass && force_ppt == kMultiPPT) ? kMultiPPT : kSinglePPT;
     }
     pl.tp_cap = (pl.tp_cap + 3) & ~3;                                 // keeps the LDS arrays 16-B aligned
@@ -898,20 +896,20 @@ static ValuePlan plan_value(int N, int S, int M, int L, int Lq, int P, int targe
 // Per-point range masks (MaskHeader) for role B plan `pl` of a large problem: only the kept-taps pass with 4 .. 8 ranges per
 // level reads them.
 struct MaskPlan { bool use; int W; size_t bytes; };
-static MaskPlan plan_masks(const ValuePlan &pl, int N, int M, int L, int Lq, int P)
+static MaskPlan plan_masks(const ValuePlan &pl, const OpGeom &g)
 {
-    static const int enabled = env_int("MSDA_MASKS", 1);                // A/B knob (tuning build): 0 = role B scans sampling_loc
+    static const int enabled = tuning_int("MSDA_MASKS", 1);                // A/B knob (tuning build): 0 = role B scans sampling_loc
     MaskPlan mp{false, 0, 0};
     if (!enabled) return mp;
-    const long long NP = (long long)Lq * P;
+    const long long NP = (long long)g.Lq * g.P;
     // W >= kMinMaskRanges: the byte costs the forward ~35 instructions per point lane (+10 % of its time), and each range's
     // workgroup saves the strided float scan of all Lq*P points — a trade that pays from four ranges per level on (cfg-2
     // encoder, W = 6: forward +1.7 us, backward -2.5 ... -4 us) and loses with two (cfg-4 encoder: forward +4.5 us, backward
     // +2 us — its scan reads every point twice either way; profiles/r05_notes.md section 1)
-    static const int min_w = env_int("MSDA_MASKS_MIN_W", kMinMaskRanges);
-    if (pl.acc != kAccWide || pl.ppt != kSinglePPT || pl.W > kMaxMaskRanges || pl.W < min_w || (NP & 3) || (long long)L * NP >= (1LL << 31)) return mp;
+    static const int min_w = tuning_int("MSDA_MASKS_MIN_W", kMinMaskRanges);
+    if (pl.acc != kAccWide || pl.ppt != kSinglePPT || pl.W > kMaxMaskRanges || pl.W < min_w || (NP & 3) || (long long)g.L * NP >= (1LL << 31)) return mp;
     mp.use = true; mp.W = pl.W;
-    mp.bytes = sizeof(MaskHeader) + (size_t)N * M * L * (size_t)NP;
+    mp.bytes = sizeof(MaskHeader) + (size_t)g.N * g.M * g.L * (size_t)NP;
     return mp;
 }
 
@@ -922,10 +920,11 @@ static MaskPlan plan_masks(const ValuePlan &pl, int N, int M, int L, int Lq, int
 // the backward is one latency chain and role B takes the short sort (FIXED, see SOvf); bigger problems keep
 // the prefix-sum sort, whose phases hide behind other workgroups' gathers.  MSDA_BWD_FIXED=0 disables both.
 struct FusedPlan { int split; bool fixed; };
-static FusedPlan plan_fused(int items, int LP, int split, long long nB, int acc, int whole_queries_of = 0, bool det = false)
+static FusedPlan plan_fused(const OpGeom &g, int split, long long nB, int acc, bool prologue)
 {
-    // whole_queries_of = M when role A must hold whole queries per workgroup (fused prologue), else 0
-    static const int enabled = env_int("MSDA_BWD_FIXED", 1);
+    // prologue: role A must hold whole queries (M items) per workgroup
+    const int items = (int)g.items(), LP = g.LP(), whole_queries_of = prologue ? g.M : 0;
+    static const int enabled = tuning_int("MSDA_BWD_FIXED", 1);
     constexpr long long kResident = 512;
     FusedPlan fp{split, false};
     if (!enabled || acc != kAccNone) return fp;
@@ -933,12 +932,12 @@ static FusedPlan plan_fused(int items, int LP, int split, long long nB, int acc,
     if (nB + n_a(split) > kResident && split == 4 && LP >= 2 && nB + n_a(2) <= kResident &&
         (whole_queries_of == 0 || (64 / 2) % whole_queries_of == 0))
         fp.split = 2;
-    fp.fixed = nB + n_a(fp.split) <= kResident;              // (det: the small body's per-wavefront-counter variant, round 5)
+    fp.fixed = nB + n_a(fp.split) <= kResident;
     return fp;
 }
 
 // per-head reference-point gradients of the fused-prologue backward on large problems, padded to 16 bytes
-static size_t prologue_heads_bytes(int N, int M, int L, int Lq) { return ((size_t)N * Lq * M * L * sizeof(float2) + 15) & ~(size_t)15; }
+static size_t prologue_heads_bytes(const OpGeom &g) { return ((size_t)g.N * g.Lq * g.M * g.L * sizeof(float2) + 15) & ~(size_t)15; }
 
 // What a forward leaves in the table buffer for the backward of the same autograd node (msda_forward_ws_*): large problems
 // (LDS-stage forward) the per-point range masks, where role B reads them; small ones the point table and its range header,
@@ -948,21 +947,20 @@ static size_t prologue_heads_bytes(int N, int M, int L, int Lq) { return ((size_
 // backward reads masks only where its own role-B plan is that one: plan_backward.)
 // prologue: the fused-prologue entry points (whole queries per role-A workgroup change the split).
 struct TablePlan { bool large; ValuePlan value; MaskPlan masks; size_t bytes; };
-static TablePlan plan_table(int N, int S, int M, int L, int Lq, int P, bool prologue)
+static TablePlan plan_table(const OpGeom &g, bool prologue)
 {
     TablePlan tp{};
-    tp.large = plan_lds<float>(N, S, M, L, Lq, P).use;
+    tp.large = plan_lds<float>(g).use;
     // (value.W >= 1 always: the range header's magic is the point table's "written" stamp; a plan with more slots than the
     // header holds gets the stamp and no entries — write_range_header)
-    tp.value = plan_value<float>(N, S, M, L, Lq, P, bwd_target_wgs(), false);
+    tp.value = plan_value<float>(g, bwd_target_wgs(), false);
     if (tp.large) {
-        tp.masks = plan_masks(tp.value, N, M, L, Lq, P);
+        tp.masks = plan_masks(tp.value, g);
         tp.bytes = tp.masks.use ? tp.masks.bytes : 0;
     } else if (tp.value.acc == kAccNone && tp.value.ppt == kSinglePPT) {
-        const int items = N * Lq * M;
-        const FusedPlan fp = plan_fused(items, L * P, pick_split(items, L * P), (long long)tp.value.W * N * M * L, tp.value.acc,
-                                        prologue ? M : 0, false);
-        if (fp.fixed) tp.bytes = (size_t)N * M * L * Lq * P * sizeof(PointEntry) + range_header_bytes();
+        const FusedPlan fp = plan_fused(g, pick_split((int)g.items(), g.LP()), (long long)tp.value.W * g.N * g.M * g.L, tp.value.acc,
+                                        prologue);
+        if (fp.fixed) tp.bytes = (size_t)g.N * g.M * g.L * g.Lq * g.P * sizeof(PointEntry) + range_header_bytes();
     }
     return tp;
 }
@@ -994,11 +992,12 @@ struct BwdPlan {
 // forward's table where the call has one (plan_table), else null; scratch_bytes / scratch_aligned: the scratch the caller
 // handed over (8-byte alignment).
 template <typename VT, typename GT>
-static BwdPlan plan_backward(int N, int S, int M, int L, int Lq, int P, bool prologue, bool deterministic, bool no_dense,
-                             const TablePlan *table, size_t scratch_bytes, bool scratch_aligned)
+static BwdPlan plan_backward(const OpGeom &g, bool prologue, const OpOptions &o, const TablePlan *table, size_t scratch_bytes,
+                             bool scratch_aligned)
 {
     constexpr long long kMaxGrid = 0x7fffffffLL;
-    const int items = N * Lq * M, LP = L * P;
+    const int N = g.N, M = g.M, L = g.L, items = (int)g.items(), LP = g.LP();
+    const bool deterministic = o.deterministic;
     const int item_stride = LP * kRecBytes + kItemPad;
     BwdPlan bp{};
     // deterministic (MSDA_FLAG_DETERMINISTIC): the same launches with role B's DET instantiations (per-wavefront counters,
@@ -1021,23 +1020,22 @@ static BwdPlan plan_backward(int N, int S, int M, int L, int Lq, int P, bool pro
     }
     // (an fp32 grad_value without the deterministic flag is the combination the table was planned for: role B is planned once)
     const bool as_table = table && sizeof(GT) == 4 && !deterministic;
-    const ValuePlan &pl = bp.value = as_table ? table->value : plan_value<GT>(N, S, M, L, Lq, P, bwd_target_wgs(), deterministic);
+    const ValuePlan &pl = bp.value = as_table ? table->value : plan_value<GT>(g, bwd_target_wgs(), deterministic);
     bp.nB = (long long)pl.W * N * M * L;
-    bp.lds_a = plan_lds<VT>(N, S, M, L, Lq, P, bp.nB);
+    bp.lds_a = plan_lds<VT>(g, bp.nB);
     // the fused kernels hold the single-pass and the kept-taps role B
     const bool fusable = mode == 0 && pl.ppt == kSinglePPT && pl.acc != kAccTile;
-    const FusedPlan fp = (prologue || !bp.lds_a.use) ? plan_fused(items, LP, bp.fused.split, bp.nB, pl.acc, prologue ? M : 0, deterministic)
-                                                     : bp.fused;
+    const FusedPlan fp = (prologue || !bp.lds_a.use) ? plan_fused(g, bp.fused.split, bp.nB, pl.acc, prologue) : bp.fused;
     const int ipw_f = kSWaves * 8 / fp.split;              // 512-thread role-A workgroups
     const long long nA_tiled = ceil_div(items, ipw_f), nA_lds = (long long)N * M * bp.lds_a.chunks;
     if (prologue && (!fusable || bp.nB + nA_tiled > kMaxGrid)) return refuse("msda backward (fused prologue): geometry not supported");
-    const bool scratch_ok = !prologue || (scratch_aligned && scratch_bytes >= prologue_heads_bytes(N, M, L, Lq));
+    const bool scratch_ok = !prologue || (scratch_aligned && scratch_bytes >= prologue_heads_bytes(g));
     if (fusable && bp.lds_a.use && (pl.acc == kAccNone || pl.acc == kAccWide) && scratch_ok && bp.nB + nA_lds <= kMaxGrid) {
         bp.kind = kBwdFusedLds;
         bp.nA = nA_lds;
         // (at least what the dense coarse-level body needs: two such workgroups still share a CU)
         bp.lds = max(max(pl.lds, bp.lds_a.lds), (size_t)dense_lds_bytes());
-        bp.dense = dense_on() && pl.W <= MSDA_DENSE_MAX_W && !no_dense;
+        bp.dense = dense_on() && pl.W <= MSDA_DENSE_MAX_W && !o.exact_nonfinite;
         // (only for the role-B plan the forward wrote them for; table->large is lds_a.use: see plan_lds)
         bp.masks = as_table && table->masks.use;
         bp.heads_scratch = prologue;
@@ -1072,62 +1070,61 @@ static MaskIn mask_in(const void *table, bool use)
     return MaskIn{reinterpret_cast<const MaskHeader *>(b), b + sizeof(MaskHeader)};
 }
 // the header behind the point entries of a table (null: no table)
-static const RangeHeader *table_header_of(const PointEntry *table, int N, int M, int L, int Lq, int P)
+static const RangeHeader *table_header_of(const PointEntry *table, const OpGeom &g)
 {
     if (!table) return nullptr;
-    return reinterpret_cast<const RangeHeader *>(table + (long long)N * M * L * Lq * P);
+    return reinterpret_cast<const RangeHeader *>(table + (long long)g.N * g.M * g.L * g.Lq * g.P);
 }
 
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 template <typename VT, bool FUSED>
-static int launch_fwd_lds(const LdsPlan &lp, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                          const float *attn, int N, int S, int M, int L, int Lq, int P, VT *out, const PrologueIn &pro,
-                          hipStream_t stream, const MaskOut mo = MaskOut{nullptr, nullptr, 0})
+static int launch_fwd_lds(const LdsPlan &lp, const OpGeom &g, const FwdTensors<VT> &t, const PrologueIn &pro, const MaskOut mo)
 {
-    const dim3 grid((unsigned)(N * M * lp.chunks));
+    const dim3 grid((unsigned)(g.N * g.M * lp.chunks));
     // (with masks to write: the ranges' first pixels [L][W + 1] and a float scale per level behind the records)
-    const size_t lds = lp.lds + (mo.masks ? (size_t)(L * (mo.W + 1) + L) * sizeof(int) : 0);
+    const size_t lds = lp.lds + (mo.masks ? (size_t)(g.L * (mo.W + 1) + g.L) * sizeof(int) : 0);
 #define MSDA_LAUNCH_FL(NS_)                                                                            \
     do { if (int rc = allow_lds(reinterpret_cast<const void *>(fwd_d32_lds_kernel<VT, FUSED, NS_>), lds)) return rc;               \
-         hipLaunchKernelGGL((fwd_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lds, stream, value, shapes, level_start,    \
-                            loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw, lp.stage_rows, out,   \
-                            pro, xcd_remap(), mo); } while (0)
-    if (8 * L * P <= kWave) MSDA_LAUNCH_FL(1); else MSDA_LAUNCH_FL(2);             // plan_lds: L*P <= 16
+         hipLaunchKernelGGL((fwd_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lds, t.stream, t.value, t.shapes,           \
+                            t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, g.p_shift(), g.lp_shift(), lp.chunks, lp.qw,  \
+                            lp.stage_rows, t.out, pro, xcd_remap(), mo); } while (0)
+    if (8 * g.LP() <= kWave) MSDA_LAUNCH_FL(1); else MSDA_LAUNCH_FL(2);            // plan_lds: L*P <= 16
 #undef MSDA_LAUNCH_FL
     return check_launch("msda forward (d32, LDS stage)");
 }
 
-template <typename VT, bool FUSED>
-static int launch_query_lds(const LdsPlan &lp, const VT *grad_out, const VT *value, const int64_t *shapes,
-                            const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L, int Lq,
-                            int P, float *grad_loc, float *grad_attn, const PrologueOut &pro, hipStream_t stream)
+template <typename VT, bool FUSED, typename GT>
+static int launch_query_lds(const LdsPlan &lp, const OpGeom &g, const BwdTensors<VT, GT> &t, const PrologueOut &pro)
 {
-    const dim3 grid((unsigned)(N * M * lp.chunks));
+    const dim3 grid((unsigned)(g.N * g.M * lp.chunks));
 #define MSDA_LAUNCH_QL(NS_)                                                                            \
     do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_query_d32_lds_kernel<VT, FUSED, NS_>), lp.lds)) return rc;      \
-         hipLaunchKernelGGL((bwd_query_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lp.lds, stream, grad_out, value,      \
-                            shapes, level_start, loc, attn, S, M, L, Lq, P, pow2_shift(P), pow2_shift(L * P), lp.chunks, lp.qw,  \
-                            lp.stage_rows, grad_loc, grad_attn, pro, xcd_remap()); } while (0)
-    if (8 * L * P <= kWave) MSDA_LAUNCH_QL(1); else MSDA_LAUNCH_QL(2);             // plan_lds: L*P <= 16
+         hipLaunchKernelGGL((bwd_query_d32_lds_kernel<VT, FUSED, NS_>), grid, dim3(kLBlock), lp.lds, t.stream, t.grad_out,         \
+                            t.value, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, g.p_shift(), g.lp_shift(), \
+                            lp.chunks, lp.qw, lp.stage_rows, t.grad_loc, t.grad_attn, pro, xcd_remap()); } while (0)
+    if (8 * g.LP() <= kWave) MSDA_LAUNCH_QL(1); else MSDA_LAUNCH_QL(2);            // plan_lds: L*P <= 16
 #undef MSDA_LAUNCH_QL
     return check_launch("msda backward (d32, query-major, LDS stage)");
 }
 
-// The forward, plain (FUSED = false: `loc` / `attn` are the sampling locations and attention weights, `pro` is empty) or with
-// the fused prologue (raw offsets and logits; see PrologueIn).  table (may be null): the buffer to fill per plan_table.
+// (row padding of the raw offsets / logits and of their gradients, PrologueIn / PrologueOut: ld_* minus the dense width)
+static int offsets_pad(long long ld, const OpGeom &g) { return (int)((ld - 2LL * g.M * g.LP()) / 2); }
+static int logits_pad(long long ld, const OpGeom &g) { return (int)(ld - (long long)g.M * g.LP()); }
+
+// The forward, plain (FUSED = false: `loc` / `attn` are the sampling locations and attention weights, the prologue's part of
+// `t` is not read) or with the fused prologue (raw offsets and logits; see PrologueIn).  table (may be null): the buffer to
+// fill per plan_table.
 template <typename VT, bool FUSED>
-static int launch_fwd_d32_t(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                            const float *attn, int N, int S, int M, int L, int Lq, int P, VT *out, const PrologueIn &pro,
-                            hipStream_t stream, PointEntry *table)
+static int launch_fwd_d32_t(const OpGeom &g, const FwdTensors<VT> &t, PointEntry *table)
 {
-    const TablePlan tp = table ? plan_table(N, S, M, L, Lq, P, FUSED) : TablePlan{};
-    const LdsPlan lp = plan_lds<VT>(N, S, M, L, Lq, P);
-    if (lp.use)
-        return launch_fwd_lds<VT, FUSED>(lp, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out, pro, stream,
-                                         mask_out(table, tp.masks));
-    const int items = N * Lq * M, LP = L * P;
+    const PrologueIn pro = FUSED ? PrologueIn{t.ref, t.loc_out, t.attn_out, offsets_pad(t.ld_offsets, g), logits_pad(t.ld_logits, g)}
+                                 : PrologueIn{nullptr, nullptr, nullptr, 0, 0};
+    const TablePlan tp = table ? plan_table(g, FUSED) : TablePlan{};
+    const LdsPlan lp = plan_lds<VT>(g);
+    if (lp.use) return launch_fwd_lds<VT, FUSED>(lp, g, t, pro, mask_out(table, tp.masks));
+    const int items = (int)g.items(), LP = g.LP();
     const int item_stride = LP * kRecBytes + kItemPad;
     const int split = pick_split(items, LP);
     const int ipw = 32 / split;
@@ -1135,9 +1132,9 @@ static int launch_fwd_d32_t(const VT *value, const int64_t *shapes, const int64_
     const int hdr_W = table ? tp.value.W : 0, hdr_tp_cap = table ? tp.value.tp_cap : 0;   // role B's ranges, for the table's header
     const dim3 grid((items + ipw - 1) / ipw + (hdr_W > 0 ? 1 : 0)), block(kBlock);      // (+ the header's workgroup)
 #define MSDA_LAUNCH_FWD(SP)                                                                            \
-    hipLaunchKernelGGL((fwd_d32_kernel<SP, VT, FUSED>), grid, block, lds, stream, value, shapes, level_start, loc, attn, \
-                       S, M, L, Lq, P, items, pow2_shift(P), pow2_shift(LP), pow2_shift(M), out, pro, xcd, table, hdr_W,  \
-                       hdr_tp_cap, kSmallRecCap)
+    hipLaunchKernelGGL((fwd_d32_kernel<SP, VT, FUSED>), grid, block, lds, t.stream, t.value, t.shapes, t.level_start, t.loc,  \
+                       t.attn, g.S, g.M, g.L, g.Lq, g.P, items, g.p_shift(), g.lp_shift(), g.m_shift(), t.out, pro, xcd, table, \
+                       hdr_W, hdr_tp_cap, kSmallRecCap)
     const int xcd = xcd_remap();
     if (split == 4) MSDA_LAUNCH_FWD(4); else if (split == 2) MSDA_LAUNCH_FWD(2); else MSDA_LAUNCH_FWD(1);
 #undef MSDA_LAUNCH_FWD
@@ -1148,45 +1145,43 @@ static int launch_fwd_d32_t(const VT *value, const int64_t *shapes, const int64_
 // A forward call that was handed a table buffer but runs kernels that write none (the generic family: rows that are not
 // 16-byte aligned) clears the table's stamp, so that the backward can never mistake an earlier call's contents — the caching
 // allocator may hand the same block out again — for this call's.
-int invalidate_forward_table(void *table, int N, int S, int M, int L, int Lq, int P, hipStream_t stream)
+int invalidate_forward_table(void *table, const OpGeom &g, hipStream_t stream)
 {
-    const size_t off = plan_table(N, S, M, L, Lq, P, false).large ? 0 : (size_t)N * M * L * Lq * P * sizeof(PointEntry);
+    const size_t off = plan_table(g, false).large ? 0 : (size_t)g.N * g.M * g.L * g.Lq * g.P * sizeof(PointEntry);
     static_assert(offsetof(RangeHeader, magic) == 0 && offsetof(MaskHeader, magic) == 0, "the stamp is the header's first word");
     const hipError_t e = hipMemsetAsync(static_cast<unsigned char *>(table) + off, 0, sizeof(int), stream);
     return e == hipSuccess ? MSDA_OK : set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
 }
 
 // Bytes of the table a forward of this geometry can leave for its backward (msda_forward_workspace_bytes): plan_table.
-size_t forward_table_bytes(int N, int S, int M, int D, int L, int Lq, int P, bool prologue)
+size_t forward_table_bytes(const OpGeom &g, bool prologue)
 {
-    if (!d32_supported(N, S, M, D, L, Lq, P) || (prologue && !prologue_supported(N, S, M, D, L, Lq, P))) return 0;
-    return plan_table(N, S, M, L, Lq, P, prologue).bytes;
+    if (!d32_supported(g) || (prologue && !prologue_supported(g))) return 0;
+    return plan_table(g, prologue).bytes;
 }
 
 // Only the fused-prologue backward on large problems needs scratch (BwdPlan::heads_scratch): the deterministic kernels
 // (MSDA_FLAG_DETERMINISTIC) order a row's records through per-wavefront counters in LDS.  Like the table, the answer must not
 // depend on the row storage of the call that follows: it is planned for fp32 rows.
-size_t backward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags)
+size_t backward_workspace_bytes(const OpGeom &g, unsigned flags)
 {
-    if (!d32_supported(N, S, M, D, L, Lq, P) || !(flags & MSDA_FLAG_PROLOGUE)) return 0;
-    const BwdPlan bp = plan_backward<float, float>(N, S, M, L, Lq, P, true, (flags & MSDA_FLAG_DETERMINISTIC) != 0, false, nullptr,
-                                                   ~(size_t)0, true);
-    return bp.heads_scratch ? prologue_heads_bytes(N, M, L, Lq) : 0;
+    if (!d32_supported(g) || !(flags & MSDA_FLAG_PROLOGUE)) return 0;
+    const BwdPlan bp = plan_backward<float, float>(g, true, OpOptions(nullptr, 0, flags & MSDA_FLAG_DETERMINISTIC), nullptr, ~(size_t)0, true);
+    return bp.heads_scratch ? prologue_heads_bytes(g) : 0;
 }
 #endif
 
-// Launches what `bp` says (plan_backward) and decides nothing.  FUSED: the fused prologue — grad_loc / grad_attn are the
+// Launches what `bp` says (plan_backward) and decides nothing.  FUSED: the fused prologue — t.grad_loc / t.grad_attn are the
 // gradients of the raw offsets / logits and `pro` carries grad_ref and their row padding (PrologueOut); its kernels exist for
 // an fp32 grad_value and the single-launch plans only.  scratch: BwdPlan::heads_scratch.  table: the forward's, or null.
 template <typename VT, typename GT, bool FUSED>
-static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *value, const int64_t *shapes,
-                            const int64_t *level_start, const float *loc, const float *attn, int N, int S, int M, int L, int Lq,
-                            int P, GT *grad_value, float *grad_loc, float *grad_attn, const PrologueOut &pro, void *scratch,
-                            const void *table, hipStream_t stream)
+static int launch_bwd_d32_t(const BwdPlan &bp, const OpGeom &g, const BwdTensors<VT, GT> &t, void *scratch, const void *table)
 {
     if (bp.kind == kBwdUnsupported) return set_error(MSDA_ERR_ARGUMENT, bp.why);
-    const int items = N * Lq * M, LP = L * P;
-    const int ps = pow2_shift(P), lps = pow2_shift(LP), ms = pow2_shift(M);
+    const PrologueOut pro = FUSED ? PrologueOut{t.grad_ref, offsets_pad(t.ld_grad_offsets, g), logits_pad(t.ld_grad_logits, g)}
+                                  : PrologueOut{nullptr, 0, 0};
+    const int items = (int)g.items();
+    const int ps = g.p_shift(), lps = g.lp_shift(), ms = g.m_shift();
     const int xcd = xcd_remap();
     const ValuePlan &pl = bp.value;
     const LdsPlan &la = bp.lds_a;
@@ -1197,13 +1192,13 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
         const MaskIn masks = mask_in(table, bp.masks);
 #define MSDA_LAUNCH_FLD__(AC, NS_, DT, DN)                                                             \
         do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_lds_d32_kernel<AC, VT, FUSED, GT, NS_, DT, DN>), bp.lds)) return rc; \
-        hipLaunchKernelGGL((bwd_fused_lds_d32_kernel<AC, VT, FUSED, GT, NS_, DT, DN>), fgrid, dim3(kSBlock), bp.lds, stream, grad_out, \
-                           value, shapes, level_start, loc, attn, S, M, L, Lq, P, ps, lps, pl.tp_cap, pl.W, (int)bp.nB,          \
-                           la.chunks, la.qw, la.stage_rows, grad_value, grad_loc, grad_attn, pro_a, xcd,                         \
-                           (DN) ? (int)bp.lds : 0, masks); } while (0)
+        hipLaunchKernelGGL((bwd_fused_lds_d32_kernel<AC, VT, FUSED, GT, NS_, DT, DN>), fgrid, dim3(kSBlock), bp.lds, t.stream,   \
+                           t.grad_out, t.value, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, ps, lps,       \
+                           pl.tp_cap, pl.W, (int)bp.nB, la.chunks, la.qw, la.stage_rows, t.grad_value, t.grad_loc, t.grad_attn,  \
+                           pro_a, xcd, (DN) ? (int)bp.lds : 0, masks); } while (0)
 #define MSDA_LAUNCH_FLD_(AC, NS_, DT) do { if (bp.dense) MSDA_LAUNCH_FLD__(AC, NS_, DT, true); else MSDA_LAUNCH_FLD__(AC, NS_, DT, false); } while (0)
 #define MSDA_LAUNCH_FLD(AC, NS_) do { if (bp.det) MSDA_LAUNCH_FLD_(AC, NS_, true); else MSDA_LAUNCH_FLD_(AC, NS_, false); } while (0)
-        const bool one_slot = 8 * LP <= kWave;
+        const bool one_slot = 8 * g.LP() <= kWave;
         if (pl.acc == kAccNone) { if (one_slot) MSDA_LAUNCH_FLD(kAccNone, 1); else MSDA_LAUNCH_FLD(kAccNone, 2); }
         else                    { if (one_slot) MSDA_LAUNCH_FLD(kAccWide, 1); else MSDA_LAUNCH_FLD(kAccWide, 2); }
 #undef MSDA_LAUNCH_FLD
@@ -1212,9 +1207,9 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
         const int rc = check_launch(FUSED ? "msda backward (d32, fused prologue, LDS stage)" : "msda backward (d32, fused, LDS stage)");
         if constexpr (FUSED) {
             if (rc) return rc;
-            const long long cells = (long long)N * Lq * L;
-            hipLaunchKernelGGL(ref_heads_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream,
-                               reinterpret_cast<const float2 *>(scratch), N * Lq, M, L, reinterpret_cast<float2 *>(pro.grad_ref));
+            const long long cells = (long long)g.N * g.Lq * g.L;
+            hipLaunchKernelGGL(ref_heads_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, t.stream,
+                               reinterpret_cast<const float2 *>(scratch), g.N * g.Lq, g.M, g.L, reinterpret_cast<float2 *>(pro.grad_ref));
             return check_launch("msda backward (d32, reference-point gradient over heads)");
         }
         return rc;
@@ -1224,10 +1219,10 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
         const PointEntry *points = static_cast<const PointEntry *>(table);    // read by the small-problem role B only
 #define MSDA_LAUNCH_F_(SP, AC, FX, DT)                                                                 \
         do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_fused_d32_kernel<SP, AC, VT, FUSED, GT, FX, DT>), bp.lds)) return rc; \
-        hipLaunchKernelGGL((bwd_fused_d32_kernel<SP, AC, VT, FUSED, GT, FX, DT>), fgrid, dim3(kSBlock), bp.lds, stream,      \
-                           grad_out, value, shapes, level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms,              \
-                           pl.tp_cap, pl.W, (int)bp.nB, grad_value, grad_loc, grad_attn, pro, xcd,                           \
-                           (FX) ? points : nullptr, (FX) ? table_header_of(points, N, M, L, Lq, P) : nullptr); } while (0)
+        hipLaunchKernelGGL((bwd_fused_d32_kernel<SP, AC, VT, FUSED, GT, FX, DT>), fgrid, dim3(kSBlock), bp.lds, t.stream,    \
+                           t.grad_out, t.value, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, items, ps, \
+                           lps, ms, pl.tp_cap, pl.W, (int)bp.nB, t.grad_value, t.grad_loc, t.grad_attn, pro, xcd,            \
+                           (FX) ? points : nullptr, (FX) ? table_header_of(points, g) : nullptr); } while (0)
 #define MSDA_LAUNCH_F(SP, AC, FX) do { if (bp.det) MSDA_LAUNCH_F_(SP, AC, FX, true); else MSDA_LAUNCH_F_(SP, AC, FX, false); } while (0)
         if (fp.fixed)                { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, true); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, true); else MSDA_LAUNCH_F(1, kAccNone, true); }
         else if (pl.acc == kAccNone) { if (fp.split == 4) MSDA_LAUNCH_F(4, kAccNone, false); else if (fp.split == 2) MSDA_LAUNCH_F(2, kAccNone, false); else MSDA_LAUNCH_F(1, kAccNone, false); }
@@ -1247,7 +1242,7 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
         // ---- kBwdTwoLaunches: role B (large record arrays / bf16 tile / A-B knob), then role A ----
 #ifdef MSDA_TUNING
         if (bp.atomic) {
-            const hipError_t e = hipMemsetAsync(grad_value, 0, sizeof(GT) * (size_t)N * S * M * kD, stream);
+            const hipError_t e = hipMemsetAsync(t.grad_value, 0, sizeof(GT) * (size_t)g.N * g.S * g.M * kD, t.stream);
             if (e != hipSuccess) return set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
         } else
 #endif
@@ -1255,8 +1250,9 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
             const dim3 grid((unsigned)bp.nB);
 #define MSDA_LAUNCH_B_(AC, PPT_, DT)                                                                   \
             do { if (int rc = allow_lds(reinterpret_cast<const void *>(bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), pl.lds)) return rc; \
-                 hipLaunchKernelGGL((bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), grid, dim3(kSBlock), pl.lds, stream, grad_out,    \
-                                    shapes, level_start, loc, attn, S, M, L, Lq, P, ps, pl.tp_cap, pl.W, grad_value, xcd); } while (0)
+                 hipLaunchKernelGGL((bwd_value_d32_kernel<AC, PPT_, VT, GT, DT>), grid, dim3(kSBlock), pl.lds, t.stream, t.grad_out, \
+                                    t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, ps, pl.tp_cap, pl.W,          \
+                                    t.grad_value, xcd); } while (0)
 #define MSDA_LAUNCH_B(AC, PPT_) do { if (bp.det) MSDA_LAUNCH_B_(AC, PPT_, true); else MSDA_LAUNCH_B_(AC, PPT_, false); } while (0)
             if (pl.acc == kAccNone) MSDA_LAUNCH_B(kAccNone, kSinglePPT);
             else if (pl.acc == kAccTile) MSDA_LAUNCH_B(kAccTile, kMultiPPT);
@@ -1271,16 +1267,15 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
 #undef MSDA_LAUNCH_B_
             if (int rc = check_launch("msda backward (d32, grad_value sort+gather)")) return rc;
         }
-        if (la.use)
-            return launch_query_lds<VT, false>(la, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_loc,
-                                               grad_attn, pro, stream);
+        if (la.use) return launch_query_lds<VT, false>(la, g, t, pro);
         const int split = bp.fused.split;
         const dim3 grid((unsigned)bp.nA), block(kBlock);
 #define MSDA_LAUNCH_A(SP, AT)                                                                          \
-        hipLaunchKernelGGL((bwd_query_d32_kernel<SP, AT, VT>), grid, block, bp.lds, stream, grad_out, value, shapes, \
-                           level_start, loc, attn, S, M, L, Lq, P, items, ps, lps, ms, gv_atomic, grad_loc, grad_attn, xcd)
+        hipLaunchKernelGGL((bwd_query_d32_kernel<SP, AT, VT>), grid, block, bp.lds, t.stream, t.grad_out, t.value, t.shapes,      \
+                           t.level_start, t.loc, t.attn, g.S, g.M, g.L, g.Lq, g.P, items, ps, lps, ms, gv_atomic, t.grad_loc,     \
+                           t.grad_attn, xcd)
         VT *gv_atomic = nullptr;                                        // only the v1 atomic scatter writes grad_value here
-        if constexpr (sizeof(VT) == sizeof(GT)) gv_atomic = grad_value;
+        if constexpr (sizeof(VT) == sizeof(GT)) gv_atomic = t.grad_value;
 #ifdef MSDA_TUNING
         if (bp.atomic) { if (split == 4) MSDA_LAUNCH_A(4, true); else if (split == 2) MSDA_LAUNCH_A(2, true); else MSDA_LAUNCH_A(1, true); }
         else
@@ -1293,82 +1288,52 @@ static int launch_bwd_d32_t(const BwdPlan &bp, const VT *grad_out, const VT *val
 
 // ---- fused prologue (fp32 only): see PrologueIn / PrologueOut ----
 #if MSDA_D32_HAS(0)
-bool prologue_supported(int N, int S, int M, int D, int L, int Lq, int P)
+bool prologue_supported(const OpGeom &g)
 {
-    if (!d32_supported(N, S, M, D, L, Lq, P)) return false;
-    const int LP = L * P;
-    if (pow2_shift(LP) < 0 || pow2_shift(P) < 0 || LP > 64) return false;     // lane-group reductions
-    const int split = pick_split(N * Lq * M, LP);
-    if ((kSWaves * 8 / split) % M != 0) return false;                           // whole queries per role-A workgroup
+    if (!d32_supported(g)) return false;
+    const int LP = g.LP();
+    if (g.lp_shift() < 0 || g.p_shift() < 0 || LP > 64) return false;         // lane-group reductions
+    const int split = pick_split((int)g.items(), LP);
+    if ((kSWaves * 8 / split) % g.M != 0) return false;                           // whole queries per role-A workgroup
     static const bool plain_modes = tuning_str("MSDA_BWD_MODE") != nullptr;
     return !plain_modes;                                                        // A/B knobs select the unfused kernels
 }
 #endif
 
 // ---- exported entries (msda_launch.h): each storage-type combination is instantiated in the object that holds its kernels ----
-// (row padding of the raw offsets / logits and of their gradients, PrologueIn / PrologueOut: ld_* minus the dense width)
-static int offsets_pad(long long ld, int M, int LP) { return (int)((ld - 2LL * M * LP) / 2); }
-static int logits_pad(long long ld, int M, int LP) { return (int)(ld - (long long)M * LP); }
-
 template <typename VT>
-int launch_fwd_d32(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc, const float *attn,
-                   int N, int S, int M, int L, int Lq, int P, VT *out, hipStream_t stream, void *table)
+int launch_fwd_d32(const OpGeom &g, const FwdTensors<VT> &t, void *table)
 {
-    return launch_fwd_d32_t<VT, false>(value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, out,
-                                       PrologueIn{nullptr, nullptr, nullptr, 0, 0}, stream, static_cast<PointEntry *>(table));
+    return launch_fwd_d32_t<VT, false>(g, t, static_cast<PointEntry *>(table));
 }
 template <typename VT>
-int launch_fwd_prologue(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
-                        const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                        long long ld_offsets, long long ld_logits, VT *out, float *loc_out, float *attn_out,
-                        hipStream_t stream, void *table)
+int launch_fwd_prologue(const OpGeom &g, const FwdTensors<VT> &t, void *table)
 {
-    const PrologueIn pro{ref, loc_out, attn_out, offsets_pad(ld_offsets, M, L * P), logits_pad(ld_logits, M, L * P)};
-    return launch_fwd_d32_t<VT, true>(value, shapes, level_start, offsets, logits, N, S, M, L, Lq, P, out, pro, stream,
-                                      static_cast<PointEntry *>(table));
+    return launch_fwd_d32_t<VT, true>(g, t, static_cast<PointEntry *>(table));
 }
 template <typename VT, typename GT>
-int launch_bwd_d32(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                   const float *attn, int N, int S, int M, int L, int Lq, int P, GT *grad_value, float *grad_loc,
-                   float *grad_attn, hipStream_t stream, bool deterministic, void *workspace, size_t ws_bytes, bool forward_table,
-                   bool no_dense)
+int launch_bwd_d32(const OpGeom &g, const BwdTensors<VT, GT> &t, const OpOptions &o)
 {
-    const TablePlan tp = forward_table ? plan_table(N, S, M, L, Lq, P, false) : TablePlan{};
-    const void *table = table_of(workspace, ws_bytes, tp.bytes);
-    const BwdPlan bp = plan_backward<VT, GT>(N, S, M, L, Lq, P, false, deterministic, no_dense, table ? &tp : nullptr, 0, false);
-    return launch_bwd_d32_t<VT, GT, false>(bp, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                           grad_loc, grad_attn, PrologueOut{nullptr, 0, 0}, nullptr, table, stream);
+    const TablePlan tp = o.forward_table ? plan_table(g, false) : TablePlan{};
+    const void *table = table_of(o.workspace, o.ws_bytes, tp.bytes);
+    const BwdPlan bp = plan_backward<VT, GT>(g, false, o, table ? &tp : nullptr, 0, false);
+    return launch_bwd_d32_t<VT, GT, false>(bp, g, t, nullptr, table);
 }
 template <typename VT>
-int launch_bwd_prologue(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start,
-                        const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
-                        long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                        float *grad_ref, hipStream_t stream, void *workspace, size_t ws_bytes, bool forward_table,
-                        bool deterministic, bool no_dense)
+int launch_bwd_prologue(const OpGeom &g, const BwdTensors<VT, float> &t, const OpOptions &o)
 {
-    const TablePlan tp = forward_table ? plan_table(N, S, M, L, Lq, P, true) : TablePlan{};
-    const void *table = table_of(workspace, ws_bytes, tp.bytes);
-    const Scratch sc = scratch_behind(workspace, ws_bytes, tp.bytes);
-    const BwdPlan bp = plan_backward<VT, float>(N, S, M, L, Lq, P, true, deterministic, no_dense, table ? &tp : nullptr, sc.bytes,
-                                                aligned_to(sc.p, 8));
-    const PrologueOut pro{grad_ref, offsets_pad(ld_grad_offsets, M, L * P), logits_pad(ld_grad_logits, M, L * P)};
-    return launch_bwd_d32_t<VT, float, true>(bp, grad_out, value, shapes, level_start, loc, attn, N, S, M, L, Lq, P, grad_value,
-                                             grad_offsets, grad_logits, pro, sc.p, table, stream);
+    const TablePlan tp = o.forward_table ? plan_table(g, true) : TablePlan{};
+    const void *table = table_of(o.workspace, o.ws_bytes, tp.bytes);
+    const Scratch sc = scratch_behind(o.workspace, o.ws_bytes, tp.bytes);
+    const BwdPlan bp = plan_backward<VT, float>(g, true, o, table ? &tp : nullptr, sc.bytes, aligned_to(sc.p, 8));
+    return launch_bwd_d32_t<VT, float, true>(bp, g, t, sc.p, table);
 }
 
-#define MSDA_GEOMETRY int, int, int, int, int, int
-#define MSDA_INSTANTIATE_FWD(VT)                                                                                                 \
-    template int launch_fwd_d32<VT>(const VT *, const int64_t *, const int64_t *, const float *, const float *, MSDA_GEOMETRY,   \
-                                    VT *, hipStream_t, void *);                                                                  \
-    template int launch_fwd_prologue<VT>(const VT *, const int64_t *, const int64_t *, const float *, const float *, const float *, \
-                                         MSDA_GEOMETRY, long long, long long, VT *, float *, float *, hipStream_t, void *)
-#define MSDA_INSTANTIATE_BWD(VT, GT)                                                                                             \
-    template int launch_bwd_d32<VT, GT>(const VT *, const VT *, const int64_t *, const int64_t *, const float *, const float *,  \
-                                        MSDA_GEOMETRY, GT *, float *, float *, hipStream_t, bool, void *, size_t, bool, bool)
-#define MSDA_INSTANTIATE_BWD_PROLOGUE(VT)                                                                                        \
-    template int launch_bwd_prologue<VT>(const VT *, const VT *, const int64_t *, const int64_t *, const float *, const float *, \
-                                         MSDA_GEOMETRY, float *, long long, long long, float *, float *, float *, hipStream_t,   \
-                                         void *, size_t, bool, bool, bool)
+#define MSDA_INSTANTIATE_FWD(VT)                                                              \
+    template int launch_fwd_d32<VT>(const OpGeom &, const FwdTensors<VT> &, void *);          \
+    template int launch_fwd_prologue<VT>(const OpGeom &, const FwdTensors<VT> &, void *)
+#define MSDA_INSTANTIATE_BWD(VT, GT) template int launch_bwd_d32<VT, GT>(const OpGeom &, const BwdTensors<VT, GT> &, const OpOptions &)
+#define MSDA_INSTANTIATE_BWD_PROLOGUE(VT) template int launch_bwd_prologue<VT>(const OpGeom &, const BwdTensors<VT, float> &, const OpOptions &)
 #if MSDA_D32_HAS(0)
 MSDA_INSTANTIATE_FWD(float);
 MSDA_INSTANTIATE_BWD(float, float);
@@ -1390,16 +1355,17 @@ int backward_passes(int Lq, int P) { return (Lq * P + kSingleMaxPoints - 1) / kS
 // pick_split and the BwdPlan launch_bwd_d32_t would be handed — with the forward's table, and with or without enough
 // scratch (has_ws) — nothing launched.  row_bytes = 4 (fp32 rows) or 2 (bf16 rows); gv_bytes the same for grad_value.
 template <typename VT, typename GT>
-static int describe_plan_t(int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det, char *buf, int len, bool no_dense)
+static int describe_plan_t(const OpGeom &g, bool prologue, const OpOptions &o, char *buf, int len)
 {
-    const int items = N * Lq * M, LP = L * P;
+    const int items = (int)g.items(), LP = g.LP();
+    const bool det = o.deterministic;
     int n = 0;
     auto put = [&](const char *fmt, auto... a) { if (n < len) { const int k = snprintf(buf + n, (size_t)(len - n), fmt, a...); n += k > 0 ? k : 0; } };
-    const LdsPlan lf = plan_lds<VT>(N, S, M, L, Lq, P);
-    if (lf.use) put("fwd=lds(chunks=%d,qw=%d,stage_rows=%d,wgs=%d)", lf.chunks, lf.qw, lf.stage_rows, N * M * lf.chunks);
+    const LdsPlan lf = plan_lds<VT>(g);
+    if (lf.use) put("fwd=lds(chunks=%d,qw=%d,stage_rows=%d,wgs=%d)", lf.chunks, lf.qw, lf.stage_rows, g.N * g.M * lf.chunks);
     else { const int sp = pick_split(items, LP); put("fwd=tiled(split=%d,wgs=%d)", sp, (items + 32 / sp - 1) / (32 / sp)); }
-    const TablePlan tp = plan_table(N, S, M, L, Lq, P, prologue);
-    const BwdPlan bp = plan_backward<VT, GT>(N, S, M, L, Lq, P, prologue, det, no_dense, &tp, has_ws ? ~(size_t)0 : 0, true);
+    const TablePlan tp = plan_table(g, prologue);
+    const BwdPlan bp = plan_backward<VT, GT>(g, prologue, o, &tp, o.ws_bytes ? ~(size_t)0 : 0, true);
     const ValuePlan &pl = bp.value;
     const char *acc = bp.atomic ? "atomic" : pl.acc == kAccNone ? "single" : pl.acc == kAccWide ? "wide" : pl.acc == kAccTile ? "tile" : "rmw";
     const int nA = (int)bp.nA;
@@ -1425,12 +1391,11 @@ static int describe_plan_t(int N, int S, int M, int L, int Lq, int P, bool prolo
     }
     return n;
 }
-int describe_plan(int row_bytes, int gv_bytes, int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det,
-                  char *buf, int len, bool no_dense)
+int describe_plan(int row_bytes, int gv_bytes, const OpGeom &g, bool prologue, const OpOptions &o, char *buf, int len)
 {
-    if (row_bytes == 4) return describe_plan_t<float, float>(N, S, M, L, Lq, P, prologue, has_ws, det, buf, len, no_dense);
-    if (gv_bytes == 4) return describe_plan_t<bf16_t, float>(N, S, M, L, Lq, P, prologue, has_ws, det, buf, len, no_dense);
-    return describe_plan_t<bf16_t, bf16_t>(N, S, M, L, Lq, P, prologue, has_ws, det, buf, len, no_dense);
+    if (row_bytes == 4) return describe_plan_t<float, float>(g, prologue, o, buf, len);
+    if (gv_bytes == 4) return describe_plan_t<bf16_t, float>(g, prologue, o, buf, len);
+    return describe_plan_t<bf16_t, bf16_t>(g, prologue, o, buf, len);
 }
 #endif
 

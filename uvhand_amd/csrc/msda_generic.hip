@@ -217,62 +217,59 @@ __global__ __launch_bounds__(kGenericBlock) void bwd_generic_value_det_kernel(
     }
 }
 
-template <typename T, typename VT>
-int launch_fwd_generic(const VT *value, const int64_t *shapes, const int64_t *level_start,
-                       const T *loc, const T *attn, int N, int S, int M, int D, int L, int Lq, int P,
-                       VT *out, hipStream_t stream)
+// The launchers: T = the type loc, attn and every gradient are held in (op_real_t), VT = the row storage.
+template <typename VT>
+int launch_fwd_generic(const OpGeom &g, const FwdTensors<VT> &t)
 {
-    const long long items = (long long)N * Lq * M;
+    using T = op_real_t<VT>;
+    const long long items = g.items();
     const long long blocks = (items + kGenericItemsPerBlock - 1) / kGenericItemsPerBlock;
     if (blocks * kGenericBlock > 0xffffffffLL) return set_error(MSDA_ERR_ARGUMENT, "N*Lq*M too large for one launch");
-    hipLaunchKernelGGL((fwd_generic_kernel<T, VT>), dim3((unsigned)blocks), dim3(kGenericBlock), 0, stream,
-                       value, shapes, level_start, loc, attn, S, M, D, L, Lq, P, items, out);
+    hipLaunchKernelGGL((fwd_generic_kernel<T, VT>), dim3((unsigned)blocks), dim3(kGenericBlock), 0, t.stream,
+                       t.value, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.D, g.L, g.Lq, g.P, items, t.out);
     return check_launch("msda forward (generic)");
 }
 
-template <typename T, typename VT>
-int launch_bwd_generic(const VT *grad_out, const VT *value, const int64_t *shapes,
-                       const int64_t *level_start, const T *loc, const T *attn, int N, int S, int M,
-                       int D, int L, int Lq, int P, T *grad_value, T *grad_loc, T *grad_attn,
-                       hipStream_t stream, bool deterministic)
+template <typename VT>
+int launch_bwd_generic(const OpGeom &g, const BwdTensors<VT, op_real_t<VT>> &t, const OpOptions &o)
 {
-    const long long items = (long long)N * Lq * M;
+    using T = op_real_t<VT>;
+    const long long items = g.items();
     const long long blocks = (items + kGenericItemsPerBlock - 1) / kGenericItemsPerBlock;
     if (blocks * kGenericBlock > 0xffffffffLL) return set_error(MSDA_ERR_ARGUMENT, "N*Lq*M too large for one launch");
-    if (deterministic) {
-        const long long rows = (long long)N * S * M;
+#define MSDA_LAUNCH_GENERIC_BWD(ATOMIC)                                                                                   \
+    hipLaunchKernelGGL((bwd_generic_kernel<T, VT, ATOMIC>), dim3((unsigned)blocks), dim3(kGenericBlock), 0, t.stream,     \
+                       t.grad_out, t.value, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.D, g.L, g.Lq, g.P, items, \
+                       t.grad_value, t.grad_loc, t.grad_attn)
+    if (o.deterministic) {
+        const long long rows = (long long)g.N * g.S * g.M;
         // brute force (rows x Lq*P point tests): bounded, so that a flag set for the whole program (torch.use_deterministic_
         // algorithms) cannot silently turn an encoder-sized fp64 / odd-D call into seconds of work — refuse it like a framework
         // refuses an op that has no deterministic form (include/msda.h, MSDA_FLAG_DETERMINISTIC)
-        if ((double)rows * (double)Lq * (double)P > 68719476736.0)       // 2^36 point tests, ~50 ms
+        if ((double)rows * (double)g.Lq * (double)g.P > 68719476736.0)       // 2^36 point tests, ~50 ms
             return set_error(MSDA_ERR_ARGUMENT, "msda backward: MSDA_FLAG_DETERMINISTIC outside the D = 32 family tests every sampling point "
                                                 "against every pixel row (N*S*M x Lq*P > 2^36 here): use D = 32 fp32 / bf16 tensors or clear the flag");
         long long rblocks = (rows + kGenericItemsPerBlock - 1) / kGenericItemsPerBlock;
         if (rblocks > (1LL << 22)) rblocks = 1LL << 22;                  // the kernel strides over the rows
-        hipLaunchKernelGGL((bwd_generic_kernel<T, VT, false>), dim3((unsigned)blocks), dim3(kGenericBlock), 0, stream,
-                           grad_out, value, shapes, level_start, loc, attn, S, M, D, L, Lq, P, items,
-                           grad_value, grad_loc, grad_attn);
+        MSDA_LAUNCH_GENERIC_BWD(false);
         if (int rc = check_launch("msda backward (generic, grad_loc / grad_attn)")) return rc;
-        hipLaunchKernelGGL((bwd_generic_value_det_kernel<T, VT>), dim3((unsigned)rblocks), dim3(kGenericBlock), 0, stream,
-                           grad_out, shapes, level_start, loc, attn, S, M, D, L, Lq, P, rows, grad_value);
+        hipLaunchKernelGGL((bwd_generic_value_det_kernel<T, VT>), dim3((unsigned)rblocks), dim3(kGenericBlock), 0, t.stream,
+                           t.grad_out, t.shapes, t.level_start, t.loc, t.attn, g.S, g.M, g.D, g.L, g.Lq, g.P, rows, t.grad_value);
         return check_launch("msda backward (generic, deterministic grad_value)");
     }
-    hipError_t e = hipMemsetAsync(grad_value, 0, sizeof(T) * (size_t)N * S * M * D, stream);
+    hipError_t e = hipMemsetAsync(t.grad_value, 0, sizeof(T) * (size_t)g.N * g.S * g.M * g.D, t.stream);
     if (e != hipSuccess) return set_error(MSDA_ERR_LAUNCH, hipGetErrorString(e));
-    hipLaunchKernelGGL((bwd_generic_kernel<T, VT, true>), dim3((unsigned)blocks), dim3(kGenericBlock), 0, stream,
-                       grad_out, value, shapes, level_start, loc, attn, S, M, D, L, Lq, P, items,
-                       grad_value, grad_loc, grad_attn);
+    MSDA_LAUNCH_GENERIC_BWD(true);
+#undef MSDA_LAUNCH_GENERIC_BWD
     return check_launch("msda backward (generic)");
 }
 
-#define MSDA_GENERIC_INST(T, VT)                                                                                        \
-    template int launch_fwd_generic<T, VT>(const VT *, const int64_t *, const int64_t *, const T *, const T *, int, int, int, \
-                                           int, int, int, int, VT *, hipStream_t);                                            \
-    template int launch_bwd_generic<T, VT>(const VT *, const VT *, const int64_t *, const int64_t *, const T *, const T *,    \
-                                           int, int, int, int, int, int, int, T *, T *, T *, hipStream_t, bool);
-MSDA_GENERIC_INST(float, float)
-MSDA_GENERIC_INST(double, double)
-MSDA_GENERIC_INST(float, uint16_t)       // bf16 rows, fp32 grad_value
+#define MSDA_GENERIC_INST(VT)                                                                       \
+    template int launch_fwd_generic<VT>(const OpGeom &, const FwdTensors<VT> &);                    \
+    template int launch_bwd_generic<VT>(const OpGeom &, const BwdTensors<VT, op_real_t<VT>> &, const OpOptions &);
+MSDA_GENERIC_INST(float)
+MSDA_GENERIC_INST(double)
+MSDA_GENERIC_INST(uint16_t)              // bf16 rows, fp32 grad_value
 #undef MSDA_GENERIC_INST
 
 }  // namespace msda

@@ -7,6 +7,7 @@
 
 #include "msda.h"
 #include "msda_common.h"
+#include "msda_op_args.h"
 
 namespace msda {
 
@@ -26,16 +27,12 @@ int set_error(int code, const char *msg);
 // Returns MSDA_OK, or records hipGetLastError() (prefixed by `what`) and returns MSDA_ERR_LAUNCH.
 int check_launch(const char *what);
 
-// ---- generic family (msda_generic.hip): any D, float / double; VT = T, or uint16_t (bf16 rows) with T = float --------
-template <typename T, typename VT>
-int launch_fwd_generic(const VT *value, const int64_t *shapes, const int64_t *level_start,
-                       const T *loc, const T *attn, int N, int S, int M, int D, int L, int Lq, int P,
-                       VT *out, hipStream_t stream);
-template <typename T, typename VT>
-int launch_bwd_generic(const VT *grad_out, const VT *value, const int64_t *shapes,
-                       const int64_t *level_start, const T *loc, const T *attn, int N, int S, int M,
-                       int D, int L, int Lq, int P, T *grad_value, T *grad_loc, T *grad_attn,
-                       hipStream_t stream, bool deterministic = false);
+// ---- the sampling op: one call = its geometry, tensors and options (msda_op_args.h) ----
+// generic family (msda_generic.hip): any D; VT = float, double, or uint16_t (bf16 rows, fp32 everything else)
+template <typename VT>
+int launch_fwd_generic(const OpGeom &g, const FwdTensors<VT> &t);
+template <typename VT>
+int launch_bwd_generic(const OpGeom &g, const BwdTensors<VT, op_real_t<VT>> &t, const OpOptions &o);
 
 // ---- D = 32 family (msda_d32.hip): the model's shape -------------------------------------------
 // VT = storage of value / out / grad_out: float, or uint16_t (bf16 bits); loc, attn and their gradients are fp32.
@@ -43,17 +40,13 @@ int launch_bwd_generic(const VT *grad_out, const VT *value, const int64_t *shape
 // and a caller whose value tensor is fp32 needs no conversion of the result).
 // table: the buffer a forward can leave for its backward (forward: written, backward: read), or null.
 // A backward call's workspace: with forward_table (MSDA_FLAG_FORWARD_TABLE) that table first, the call's scratch behind it.
-bool d32_supported(int N, int S, int M, int D, int L, int Lq, int P);
+bool d32_supported(const OpGeom &g);
 template <typename VT>
-int launch_fwd_d32(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc, const float *attn,
-                   int N, int S, int M, int L, int Lq, int P, VT *out, hipStream_t stream, void *table = nullptr);
+int launch_fwd_d32(const OpGeom &g, const FwdTensors<VT> &t, void *table);
 template <typename VT, typename GT>
-int launch_bwd_d32(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start, const float *loc,
-                   const float *attn, int N, int S, int M, int L, int Lq, int P, GT *grad_value, float *grad_loc,
-                   float *grad_attn, hipStream_t stream, bool deterministic = false, void *workspace = nullptr, size_t ws_bytes = 0,
-                   bool forward_table = false, bool no_dense = false);
+int launch_bwd_d32(const OpGeom &g, const BwdTensors<VT, GT> &t, const OpOptions &o);
 // bytes of that table (0 = the backward's plan reads none)
-size_t forward_table_bytes(int N, int S, int M, int D, int L, int Lq, int P, bool prologue);
+size_t forward_table_bytes(const OpGeom &g, bool prologue);
 inline bool aligned_to(const void *p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 // The table inside `workspace` (include/msda.h: msda_forward_ws_* fills the start of it, a backward call with
 // MSDA_FLAG_FORWARD_TABLE finds it there).  `need` = forward_table_bytes of the geometry: used only where the plan has a
@@ -72,31 +65,23 @@ inline Scratch scratch_behind(void *workspace, size_t ws_bytes, size_t table_byt
     return Scratch{static_cast<unsigned char *>(workspace) + span, ws_bytes - span};
 }
 // clears the 'written' stamp of a table buffer that a forward call could not fill (see msda_d32.hip)
-int invalidate_forward_table(void *table, int N, int S, int M, int L, int Lq, int P, hipStream_t stream);
+int invalidate_forward_table(void *table, const OpGeom &g, hipStream_t stream);
 // scratch a D = 32 backward call with these flags can use (0 = none needed); see msda.h
-size_t backward_workspace_bytes(int N, int S, int M, int D, int L, int Lq, int P, unsigned flags);
+size_t backward_workspace_bytes(const OpGeom &g, unsigned flags);
 // number of query chunks ("passes") role B of the D = 32 backward takes for Lq*P sampling points per (b, m, l)
 int backward_passes(int Lq, int P);
-// text form of the launch plan of a D = 32 geometry (msda_describe_plan); returns the length written
-int describe_plan(int row_bytes, int gv_bytes, int N, int S, int M, int L, int Lq, int P, bool prologue, bool has_ws, bool det,
-                  char *buf, int len, bool no_dense = false);
+// text form of the launch plan of a D = 32 geometry (msda_describe_plan); returns the length written.  Of `o` it reads the
+// flags and whether there is a workspace (ws_bytes != 0)
+int describe_plan(int row_bytes, int gv_bytes, const OpGeom &g, bool prologue, const OpOptions &o, char *buf, int len);
 
 // ---- fused prologue (D = 32 family): softmax over L*P and loc = ref + offset/(W,H) inside the kernels.  Offsets, logits,
-// reference points and every gradient are fp32 (grad_value included, for bf16 rows too).
-// ld_* = floats between consecutive (batch, query) rows of the raw offsets / logits and of their gradients
-// (validated by the ABI layer: >= the dense width, offsets' even).
-bool prologue_supported(int N, int S, int M, int D, int L, int Lq, int P);
+// reference points and every gradient are fp32 (grad_value included, for bf16 rows too).  The records' ld_* are validated by
+// the ABI layer (>= the dense width, offsets' even).
+bool prologue_supported(const OpGeom &g);
 template <typename VT>
-int launch_fwd_prologue(const VT *value, const int64_t *shapes, const int64_t *level_start, const float *ref,
-                        const float *offsets, const float *logits, int N, int S, int M, int L, int Lq, int P,
-                        long long ld_offsets, long long ld_logits, VT *out, float *loc_out, float *attn_out,
-                        hipStream_t stream, void *table = nullptr);
+int launch_fwd_prologue(const OpGeom &g, const FwdTensors<VT> &t, void *table);
 template <typename VT>
-int launch_bwd_prologue(const VT *grad_out, const VT *value, const int64_t *shapes, const int64_t *level_start,
-                        const float *loc, const float *attn, int N, int S, int M, int L, int Lq, int P, float *grad_value,
-                        long long ld_grad_offsets, long long ld_grad_logits, float *grad_offsets, float *grad_logits,
-                        float *grad_ref, hipStream_t stream, void *workspace = nullptr, size_t ws_bytes = 0, bool forward_table = false,
-                        bool deterministic = false, bool no_dense = false);
+int launch_bwd_prologue(const OpGeom &g, const BwdTensors<VT, float> &t, const OpOptions &o);
 
 // ---- weight / bias gradient of the bracketing nn.Linear layers (msda_linear.hip) -----------------
 size_t linear_wgrad_workspace_bytes(int M, int N, int K);

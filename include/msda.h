@@ -693,6 +693,55 @@ int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const floa
                            const float *grad_losses, const int32_t *stats, float *const *grad_logits,
                            float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream);
 
+/* ---- The DINO criterion's matched and denoising losses (models/dino/dino.py SetCriterion: loss_labels, loss_cardinality and
+ * loss_boxes :453-532, the denoising losses :615-664) --------------------------------------------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump, as the matcher and criterion blocks above: purely additive entries;
+ * msda_criterion_fwd_f32 / msda_criterion_bwd_f32 are unchanged.
+ *
+ *   msda_criterion_dino_fwd_f32  `sets` <= 16 prediction sets that may differ in query count.  HOST arrays of length `sets`,
+ *       read at call time into the kernels' argument record: device pointers pred_logits [bs, Q[s], K] and, with target
+ *       keypoints, pred_hand_key / pred_obj_key [bs, Q[s], D] (fp32 contiguous; NULL arrays with D = 0 otherwise), the query
+ *       counts Q[s], and match_set[s]: the set's index inside `match` (the int64 result of msda_match_arctic_f32 for
+ *       match_sets sets and t_max), or -1 for a DENOISING set, which needs Q[s] = groups * single_pad and reads no match
+ *       buffer (match may be NULL when every set is one).  The targets as for the matcher (labels, keypoints [n_targets, D]
+ *       or NULL, offsets [bs + 1], is_valid [bs]), hand_mask (bit l for each hand label l < 64), num_boxes a device fp32
+ *       scalar, focal_alpha.  Slot k of every set pairs output frame k with the k-th valid frame f's n_f targets: a matched
+ *       set through slot k of its matcher set; a denoising set pairs query g * single_pad + j with target offsets[f] + j for
+ *       every g < groups and j < n_f (:623-633).  n_f > single_pad / 2 sets status bit 2 and the frame gives no pair.
+ *       losses fp32 [sets, 4]: loss_ce = focal(alpha, gamma 2).mean(1).sum() / num_boxes * Q[s] (a denoising set divides by
+ *       num_boxes * groups), loss_hand_keypoint (L1 of the hand head over paired rows with a hand label / their count / 21;
+ *       0 without one), loss_obj_keypoint (the object head over the other paired rows / their count / 21; 0 / 0 = nan
+ *       without one), cardinality_error (mean over frames f of |#(argmax of output frame f's rows != K - 1) - n_f|: the
+ *       empty class is K - 1).  Every term is 0 when no valid frame has a target.  stats int32 [sets, 4]: status bits (1 a
+ *       paired label outside [0, K), 2 offsets / target indices that do not describe the targets, 8 a matcher slot status),
+ *       hand rows, object rows, and 1 when no valid frame has a target.
+ *       Two launches: one workgroup per chunk (up to MSDA_CRITERION_DINO_CHUNK_ROWS rows of one set and output frame)
+ *       writes a record of fp64 partial sums and integer counts to `workspace` (8-byte aligned, at least
+ *       MSDA_CRITERION_DINO_PARTIAL_BYTES * bs * sum over s of ceil(Q[s] / MSDA_CRITERION_DINO_CHUNK_ROWS) bytes), then one
+ *       workgroup per set adds its records in a fixed order.  No float atomics: bitwise reproducible, and a set's row does
+ *       not depend on the other sets of the call.
+ *   msda_criterion_dino_bwd_f32  one launch: from grad_losses fp32 [sets, 4] (cardinality_error gets none) and the forward's
+ *       stats, writes every element of grad_logits and, with keypoints, of grad_hand_key / grad_obj_key (HOST arrays of
+ *       device pointers shaped as the predictions): zero except paired rows.
+ *   Limits: 1 <= bs <= 1024, 1 <= Q[s], 1 <= K, 0 <= t_max <= 16, bs * Q[s] * max(K, D) < 2^31.  No allocation, no
+ *   synchronisation, nothing read on the host; argument errors return MSDA_ERR_ARGUMENT before any launch. */
+#define MSDA_CRITERION_DINO_CHUNK_ROWS 256
+#define MSDA_CRITERION_DINO_PARTIAL_BYTES 64
+int msda_criterion_dino_fwd_f32(const float *const *pred_logits, const float *const *pred_hand_key,
+                                const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
+                                int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
+                                const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                                const int32_t *is_valid, unsigned long long hand_mask, const float *num_boxes,
+                                float focal_alpha, void *workspace, unsigned long long workspace_bytes, float *losses,
+                                int32_t *stats, msda_stream_t stream);
+int msda_criterion_dino_bwd_f32(const float *const *pred_logits, const float *const *pred_hand_key,
+                                const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
+                                int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
+                                const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                                const int32_t *is_valid, unsigned long long hand_mask, const float *num_boxes,
+                                float focal_alpha, const float *grad_losses, const int32_t *stats, float *const *grad_logits,
+                                float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream);
+
 /* ---- The DeformableDETR prediction heads (models/actic_detr.py DeformableDETR.forward :245-287, models/assembly_detr.py
  * DeformableDETR.forward :172-210) as grouped fp32 GEMMs --------------------------------------------------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.

@@ -117,6 +117,9 @@ SIGNATURES = {
     # the set criteria's matched losses
     "msda_criterion_fwd_f32": "i i ppp iiiii p i ppp l pp U p f ppp",
     "msda_criterion_bwd_f32": "i i ppp iiiii p i ppp l pp U p f pppppp",
+    # the DINO criterion's matched and denoising losses
+    "msda_criterion_dino_fwd_f32": "i ppp pp iiiiii p ii ppp l p U p f p U pp p",
+    "msda_criterion_dino_bwd_f32": "i ppp pp iiiiii p ii ppp l p U p f pp ppp p",
     # the DeformableDETR prediction heads
     "msda_heads_supported": "i i",
     "msda_heads_workspace_bytes": "U ii l iii u",
@@ -1553,6 +1556,103 @@ def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
     g_obj = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D and kind == CRIT_ARCTIC else []
     _launch(dev, "msda_criterion_bwd_f32", "criterion_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
             _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None, _ptr_array(g_obj) if g_obj else None)
+    return g_logits, g_hand, g_obj
+
+
+# ---- the DINO criterion's matched and denoising losses (csrc/msda_criterion_dino.hip) -----------------------------------
+CRIT_DINO_CHUNK_ROWS, CRIT_DINO_PARTIAL_BYTES = 256, 64     # MSDA_CRITERION_DINO_* (include/msda.h)
+
+
+def criterion_dino_workspace_bytes(bs, queries):
+    """The forward's workspace (include/msda.h): one record per chunk of every set."""
+    return CRIT_DINO_PARTIAL_BYTES * sum(bs * ((q + CRIT_DINO_CHUNK_ROWS - 1) // CRIT_DINO_CHUNK_ROWS) for q in queries)
+
+
+def _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels, keypoints, offsets, is_valid,
+                      hand_mask, num_boxes, focal_alpha, single_pad, groups):
+    """Checks shared by criterion_dino_fwd / criterion_dino_bwd; returns the C arguments in order, the tensors' device and
+    (bs, K, D).  ``match_set[s]``: the set's index in the matcher's result ``match`` (of ``match_sets`` sets), -1 for a
+    denoising set."""
+    sets, dev = len(logits), logits[0].device
+    has_kp = keypoints is not None
+    D = keypoints.shape[1] if has_kp else 0
+    if not (0 < sets <= MATCH_MAX_SETS and len(match_set) == sets and (not has_kp or len(hand) == len(obj) == sets)):
+        raise RuntimeError("criterion_dino: 1 to %d prediction sets, one match_set entry each" % MATCH_MAX_SETS)
+    bs, _, K = logits[0].shape
+    for s, t in enumerate(logits):
+        if not (_f32_cuda(t) and t.device == dev and t.dim() == 3 and t.shape[0] == bs and t.shape[2] == K):
+            raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA pred_logits [bs, Q_s, K] in every set")
+        for h in ((hand[s], obj[s]) if has_kp else ()):
+            if not (_f32_cuda(h) and h.device == dev and tuple(h.shape) == (bs, t.shape[1], D)):
+                raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA keypoint heads [bs, Q_s, %d]" % D)
+    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 1
+            and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous()
+            and tuple(offsets.shape) == (bs + 1,) and labels.device == dev and offsets.device == dev):
+        raise RuntimeError("criterion_dino: expected int64 CUDA labels [n] and offsets [bs + 1]")
+    if has_kp and not (_f32_cuda(keypoints) and keypoints.dim() == 2 and keypoints.device == dev
+                       and keypoints.shape[0] == labels.shape[0]):
+        raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA target keypoints [n, D]")
+    if any(m >= 0 for m in match_set) and not (
+            match is not None and match.is_cuda and match.dtype == torch.int64 and match.is_contiguous()
+            and match.device == dev and 0 <= int(t_max) <= MATCH_MAX_TARGETS
+            and match.numel() == 2 * match_sets * bs * t_max + 2 * match_sets * bs + 1):
+        raise RuntimeError("criterion_dino: expected the matcher's int64 CUDA result for %d sets" % match_sets)
+    if not (is_valid is not None and is_valid.is_cuda and is_valid.dtype == torch.int32 and tuple(is_valid.shape) == (bs,)
+            and is_valid.is_contiguous() and is_valid.device == dev):
+        raise RuntimeError("criterion_dino: expected int32 CUDA is_valid [bs]")
+    if not (_f32_cuda(num_boxes) and num_boxes.numel() == 1 and num_boxes.device == dev):
+        raise RuntimeError("criterion_dino: expected an fp32 CUDA num_boxes scalar")
+    queries = [t.shape[1] for t in logits]
+    ints = ctypes.c_int * sets
+    args = [_ptr_array(logits), _ptr_array(hand) if has_kp else None, _ptr_array(obj) if has_kp else None, ints(*queries),
+            ints(*[int(m) for m in match_set]), sets, bs, K, D, int(single_pad), int(groups),
+            match.data_ptr() if match is not None else None, int(match_sets), int(t_max), labels.data_ptr(),
+            keypoints.data_ptr() if has_kp else None, offsets.data_ptr(), labels.shape[0], is_valid.data_ptr(),
+            int(hand_mask), num_boxes.data_ptr(), float(focal_alpha)]
+    return args, dev, (bs, K, D), queries
+
+
+def criterion_dino_fwd(logits, hand, obj, match_set, match, match_sets, t_max, labels, keypoints, offsets, is_valid, hand_mask,
+                       num_boxes, focal_alpha, single_pad, groups):
+    """(losses fp32 [sets, 4], stats int32 [sets, 4]) — msda_criterion_dino_fwd_f32 (include/msda.h).  Two launches, no host
+    synchronisation."""
+    args, dev, (bs, _K, _D), queries = _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels,
+                                                         keypoints, offsets, is_valid, hand_mask, num_boxes, focal_alpha,
+                                                         single_pad, groups)
+    sets = len(logits)
+    nbytes = criterion_dino_workspace_bytes(bs, queries)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
+    stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
+    _launch(dev, "msda_criterion_dino_fwd_f32", "criterion_dino_fwd", *args, ws.data_ptr(), nbytes, losses.data_ptr(),
+            stats.data_ptr())
+    return losses, stats
+
+
+def criterion_dino_bwd(logits, hand, obj, match_set, match, match_sets, t_max, labels, keypoints, offsets, is_valid, hand_mask,
+                       num_boxes, focal_alpha, single_pad, groups, grad_losses, stats, out=None):
+    """(grad_logits, grad_hand, grad_obj) lists, every element written — msda_criterion_dino_bwd_f32.  One launch.  ``out``
+    (tests): the three lists, already allocated in the predictions' shapes."""
+    args, dev, (bs, K, D), queries = _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels,
+                                                       keypoints, offsets, is_valid, hand_mask, num_boxes, focal_alpha,
+                                                       single_pad, groups)
+    sets = len(logits)
+    if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
+            and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
+        raise RuntimeError("criterion_dino_bwd: expected fp32 grad_losses and int32 stats [%d, 4]" % sets)
+    if out is not None:
+        g_logits, g_hand, g_obj = out
+        want = [(bs, q, K) for q in queries] + [(bs, q, D) for q in queries] * (2 if D else 0)
+        if not (len(g_hand) == len(g_obj) == (sets if D else 0) and len(g_logits) == sets
+                and all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == w
+                        for t, w in zip(list(g_logits) + list(g_hand) + list(g_obj), want))):
+            raise RuntimeError("criterion_dino_bwd: out must hold contiguous fp32 CUDA tensors shaped as the predictions")
+    else:
+        g_logits = [torch.empty(bs, q, K, dtype=torch.float32, device=dev) for q in queries]
+        g_hand = [torch.empty(bs, q, D, dtype=torch.float32, device=dev) for q in queries] if D else []
+        g_obj = [torch.empty(bs, q, D, dtype=torch.float32, device=dev) for q in queries] if D else []
+    _launch(dev, "msda_criterion_dino_bwd_f32", "criterion_dino_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
+            _ptr_array(g_logits), _ptr_array(g_hand) if D else None, _ptr_array(g_obj) if D else None)
     return g_logits, g_hand, g_obj
 
 

@@ -1,5 +1,6 @@
 """The set criteria of UVHand (models/actic_detr.py SetArcticCriterion :365-569, models/assembly_detr.py SetAssemblyCriterion
-:248-446) over the device result of ``matcher.match`` (csrc/msda_criterion.hip, include/msda.h).
+:248-446, models/dino/dino.py SetCriterion :428-781) over the device result of ``matcher.match`` (csrc/msda_criterion.hip,
+csrc/msda_criterion_dino.hip, include/msda.h).
 
 The reference turns every set's (final, aux, interm / enc) CPU index lists into index tensors, masks with booleans (a
 ``nonzero`` and a host sync each), reads counts with ``.item()`` and launches some 15-25 small kernels per set, as many
@@ -14,6 +15,10 @@ again backward.  Here:
     and clamped on the device under torch.distributed); the values are 0-d device views.  The AssemblyHands forward makes
     no host sync; the ARCTIC one makes none besides the MANO / ARCTIC small losses, which stay the reference's code
     (``small_loss``) unless ``small_loss`` is a ``small_loss.ArcticSmallLoss``, whose ``many`` covers every set sync-free.
+
+  * ``dino_set_losses`` / ``SetDinoCriterion``  DINO's criterion: sets that differ in query count in one node, the
+    matched final / aux / interm sets followed by the denoising sets, whose fixed pairs (dino.py:623-633) need no matcher;
+    the empty class is K - 1; two forward launches (chunks, then a finish) and one backward launch, no host sync.
 
 Reference behaviour kept: slot k of a set pairs output frame k with the k-th VALID frame's targets (ARCTIC, as the matcher);
 AssemblyHands' ``joint_valid`` rows go with matched rows in query order (row r of a frame's matched block uses the frame's
@@ -198,11 +203,12 @@ def _top1_error(logits, labels):
     return 100 - correct.mul_(100.0 / labels.size(0))
 
 
-def arctic_set_losses(outputs, targets, indices, num_boxes, losses, num_classes, focal_alpha=0.25):
-    """One ARCTIC set's DETR terms from the matcher's host ``indices`` (or 0: every requested key 0, not omitted)."""
+def arctic_set_losses(outputs, targets, indices, num_boxes, losses, num_classes, focal_alpha=0.25, empty=0, log=False):
+    """One ARCTIC set's DETR terms from the matcher's host ``indices`` (or 0: every requested key 0, not omitted).  DINO's
+    criterion is the same maths with the empty class ``empty`` = K - 1 and, for its final set (``log``), ``class_error``."""
     if not isinstance(indices, list):
         zero = outputs["pred_logits"].new_zeros(())
-        return {k: zero for k in _arctic_keys(losses)}
+        return {k: zero for k in _arctic_keys(losses, log)}
     logits = outputs["pred_logits"]
     dev = logits.device
     valid = [f for f in range(len(targets["labels"])) if targets["is_valid"][f] == 1]
@@ -213,6 +219,8 @@ def arctic_set_losses(outputs, targets, indices, num_boxes, losses, num_classes,
     for loss in losses:
         if loss == "labels":
             out["loss_ce"] = _focal_ce(logits, idx, matched, num_classes, num_boxes, focal_alpha)
+            if log:
+                out["class_error"] = _top1_error(logits[idx], matched)
         elif loss == "boxes":
             tgt = torch.cat([targets["keypoints"][f][indices[k][1]] for k, f in enumerate(valid)]).to(dev)
             hand = (matched == ARCTIC_HANDS[0]) + (matched == ARCTIC_HANDS[1])
@@ -222,7 +230,7 @@ def arctic_set_losses(outputs, targets, indices, num_boxes, losses, num_classes,
             out["loss_hand_keypoint"] = (l_hand.sum() / n_hand) / KEYPOINT_DIV if len(l_hand) else logits.new_zeros(())
             out["loss_obj_keypoint"] = (l_obj.sum() / int((~hand).sum())) / KEYPOINT_DIV
         elif loss == "cardinality":
-            out["cardinality_error"] = _cardinality(logits, [len(t) for t in targets["labels"]], 0)
+            out["cardinality_error"] = _cardinality(logits, [len(t) for t in targets["labels"]], empty)
         else:
             raise AssertionError(f"do you really want to compute {loss} loss?")
     return out
@@ -255,10 +263,11 @@ def assembly_set_losses(outputs, targets, indices, num_boxes, losses, num_classe
     return out
 
 
-def _arctic_keys(losses):
+def _arctic_keys(losses, log=False):
     keys = []
     for loss in losses:
-        keys += {"labels": ["loss_ce"], "boxes": ["loss_hand_keypoint", "loss_obj_keypoint"],
+        keys += {"labels": ["loss_ce", "class_error"] if log else ["loss_ce"],
+                 "boxes": ["loss_hand_keypoint", "loss_obj_keypoint"],
                  "cardinality": ["cardinality_error"]}.get(loss, [])
     return keys
 
@@ -468,4 +477,242 @@ class SetAssemblyCriterion(nn.Module):
                 bt["labels"] = torch.zeros_like(bt["labels"])
             d = assembly_set_losses(enc, bin_targets, self.matcher(enc, bin_targets), nb, log=False, **kw)
             losses.update({k + "_enc": v for k, v in d.items()})
+        return losses
+
+
+# ---- DINO (models/dino/dino.py SetCriterion :428-781): matched sets and denoising sets in one node ------------------------
+DINO_ZERO_DN_KEYS = ("loss_bbox_dn", "loss_giou_dn", "loss_ce_dn", "loss_xy_dn", "loss_hw_dn", "cardinality_error_dn")
+_PRED_KEYS = ("pred_logits", "pred_hand_key", "pred_obj_key")
+
+
+class _DinoSetLossFunction(torch.autograd.Function):
+    @staticmethod
+    def _split(meta, preds):
+        n = meta["sets"]
+        has_kp = len(preds) > n
+        return list(preds[:n]), list(preds[n:2 * n]) if has_kp else None, list(preds[2 * n:3 * n]) if has_kp else None
+
+    @staticmethod
+    def forward(ctx, meta, *preds):
+        logits, hand, obj = _DinoSetLossFunction._split(meta, preds)
+        losses, stats = MSDA.criterion_dino_fwd(logits, hand, obj, *meta["args"])
+        ctx.meta, ctx.stats = meta, stats
+        ctx.save_for_backward(*preds)
+        ctx.mark_non_differentiable(stats)
+        return losses, stats
+
+    @staticmethod
+    def backward(ctx, grad_losses, _grad_stats):
+        logits, hand, obj = _DinoSetLossFunction._split(ctx.meta, ctx.saved_tensors)
+        g_logits, g_hand, g_obj = MSDA.criterion_dino_bwd(logits, hand, obj, *ctx.meta["args"], grad_losses.contiguous(),
+                                                          ctx.stats)
+        return (None, *g_logits, *g_hand, *g_obj)
+
+
+def dino_set_losses(outputs_list, packed, result, num_boxes, dn_outputs_list=(), single_pad=0, groups=0, focal_alpha=0.25):
+    """DINO's matched losses of every prediction dict of ``outputs_list`` (the sets ``match`` was given, same order) followed
+    by the denoising losses of every dict of ``dn_outputs_list`` ([bs, groups * single_pad, .] predictions, paired with the
+    targets as dino.py:623-633 does), in one autograd node: two forward launches, one backward launch, no host sync.
+    ``packed``: ``matcher.pack_targets`` of the ARCTIC targets dict; ``result``: ``matcher.match``'s MatchResult (None
+    without matched sets); ``num_boxes``: a device scalar (or a number); a denoising set divides its focal loss by
+    ``num_boxes * groups``.  Returns ``SetLosses`` with ``len(outputs_list) + len(dn_outputs_list)`` rows in ``ARCTIC_TERMS``
+    order; the empty class is K - 1."""
+    matched, dn = list(outputs_list), list(dn_outputs_list)
+    if packed.kind != "arctic":
+        raise ValueError("dino_set_losses: the targets are the ARCTIC dict (labels, keypoints, is_valid)")
+    if not matched and not dn:
+        raise ValueError("dino_set_losses: no prediction set")
+    if matched and result is None:
+        raise ValueError("dino_set_losses: matched sets need matcher.match's result")
+    logits = [o["pred_logits"].contiguous() for o in matched + dn]
+    preds = list(logits)
+    if packed.keypoints is not None:
+        preds += [o["pred_hand_key"].contiguous() for o in matched + dn]
+        preds += [o["pred_obj_key"].contiguous() for o in matched + dn]
+    match_sets = int(result.count.shape[0]) if result is not None else 0
+    if len(matched) > match_sets:
+        raise ValueError("dino_set_losses: %d matched sets, the match result has %d" % (len(matched), match_sets))
+    meta = {"sets": len(logits),
+            "args": ([*range(len(matched))] + [-1] * len(dn), result.buffer if result is not None else None, match_sets,
+                     packed.t_max, packed.labels, packed.keypoints, packed.offsets, packed.is_valid,
+                     _hand_mask(ARCTIC_HANDS), _num_boxes_tensor(num_boxes, logits[0].device), float(focal_alpha),
+                     int(single_pad), int(groups))}
+    losses, stats = _DinoSetLossFunction.apply(meta, *preds)
+    return SetLosses(losses, ARCTIC_TERMS, stats[:, 0], stats)
+
+
+def _class_error_device(logits, packed, result, none_flag, set_index=0):
+    """``100 - accuracy(src_logits[idx], target_classes_o)[0]`` of one matched set from the device match result: torch ops,
+    no host sync.  0 where ``none_flag`` (no valid frame has a target) is set."""
+    bs, Q, _ = logits.shape
+    W, n = packed.t_max, int(packed.labels.shape[0])
+    if W == 0 or n == 0:
+        return logits.new_zeros(())
+    dev = logits.device
+    order = torch.argsort((packed.is_valid == 0).to(torch.int8), stable=True)      # slot k -> the k-th valid frame
+    mask = torch.arange(W, device=dev)[None, :] < result.count[set_index][:, None]
+    q = result.query_idx[set_index].clamp(0, Q - 1)
+    rows = (packed.offsets[:-1][order][:, None] + result.target_idx[set_index].clamp(min=0)).clamp(0, n - 1)
+    pred = logits.detach().argmax(-1).gather(1, q)
+    correct = ((pred == packed.labels[rows]) & mask).sum().to(torch.float32)
+    pairs = mask.sum()
+    scale = (100.0 / pairs.to(torch.float64)).to(torch.float32)                     # accuracy: correct.mul_(100.0 / n)
+    err = torch.where(pairs > 0, 100 - correct * scale, torch.full_like(correct, 100.0))
+    return torch.where(none_flag != 0, torch.zeros_like(err), err)
+
+
+class SetDinoCriterion(SetArcticCriterion):
+    """Drop-in for models/dino/dino.py:428-781 (``loss_masks`` left out): the reference's constructor order and
+    ``forward(outputs, targets, args, meta_info, return_indices=False)``, returning the reference's dict in the reference's
+    key order.  The final, aux and interm sets and the denoising set of ``outputs['dn_meta']`` take one ``pack_targets``, one
+    ``match`` and one ``dino_set_losses``; values are 0-d views of its tensor; ``class_error`` comes from the match result
+    with torch ops; no host sync (``return_indices=True`` copies the match buffer once).  Without denoising outputs (not
+    training, falsy ``dn_meta``, no ``output_known_lbs_bboxes``) the reference's six zero keys are returned and no
+    denoising set is launched.  When no valid frame has a target every key is 0 (the reference's matcher raises).
+    ``enc_outputs`` without keypoint heads raise the reference's ``loss_boxes`` assertion before anything is launched."""
+
+    def __init__(self, num_classes, matcher, weight_dict, focal_alpha, losses, cfg, pre_process_models, small_loss=None):
+        super().__init__(num_classes, matcher, weight_dict, losses, focal_alpha, cfg, pre_process_models, small_loss)
+
+    @staticmethod
+    def _sets(outputs):
+        skip = ("aux_outputs", "interm_outputs", "enc_outputs", "dn_meta")
+        final = {k: v for k, v in outputs.items() if k not in skip}
+        return final, list(outputs.get("aux_outputs", [])), outputs.get("interm_outputs")
+
+    def _dn(self, outputs):
+        """(output_known_lbs_bboxes, single_pad, groups) as ``prep_for_dn`` (:775-781), or None: the six zero keys."""
+        dn_meta = outputs["dn_meta"]
+        if not (self.training and dn_meta and "output_known_lbs_bboxes" in dn_meta):
+            return None
+        groups, pad = dn_meta["num_dn_group"], dn_meta["pad_size"]
+        assert pad % groups == 0
+        return dn_meta["output_known_lbs_bboxes"], pad // groups, groups
+
+    def _fused_ok(self, sets, dn, targets):
+        has_kp = "keypoints" in targets
+        keys = _PRED_KEYS if has_kp else _PRED_KEYS[:1]
+        if not all(k in o for o in sets + ([dn[0]] if dn else []) for k in keys):
+            return False
+        preds = [o[k] for k in keys for o in sets]
+        sizes = [len(t) for t in targets["labels"]]
+        kps = list(targets["keypoints"]) if has_kp else []
+        bs = sets[0]["pred_logits"].shape[0]
+        if not (_fusable(preds, sizes, bs, len(sets) + (1 if dn else 0))
+                and all(t.shape[:2] == preds[0].shape[:2] for t in preds)
+                and set(self.losses) <= {"labels", "boxes", "cardinality"} and ("boxes" not in self.losses or has_kp)
+                and getattr(self.matcher, "focal_alpha", MT.ALPHA) == MT.ALPHA
+                and all(torch.is_tensor(k) and k.dtype == torch.float32 and k.shape[-1] == preds[-1].shape[-1] for k in kps)):
+            return False
+        if dn:
+            known, single_pad, groups = dn
+            dn_preds = [known[k] for k in keys]
+            if not (all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == preds[0].device
+                        and t.dim() == 3 and tuple(t.shape[:2]) == (bs, groups * single_pad) for t in dn_preds)
+                    and groups >= 1 and single_pad >= 2 and single_pad % 2 == 0 and max(sizes, default=0) <= single_pad // 2):
+                return False
+        return True
+
+    def forward(self, outputs, targets, args, meta_info, return_indices=False):
+        final, aux, interm = self._sets(outputs)
+        if "boxes" in self.losses:
+            for enc in outputs.get("enc_outputs", ()):       # the reference's loss_boxes assertion, before any launch
+                assert "pred_hand_key" in enc and "pred_obj_key" in enc
+        dn = self._dn(outputs)
+        sets = [final] + aux + ([interm] if interm is not None else [])
+        if "enc_outputs" in outputs or not self._fused_ok(sets, dn, targets):
+            return self._forward_reference(outputs, targets, args, meta_info, return_indices)
+        dev = final["pred_logits"].device
+        bs = final["pred_logits"].shape[0]
+        packed = MT.pack_targets(targets, dev)
+        result = MT.match(sets, packed, self.matcher.cost_class, self.matcher.cost_keypoint)
+        nb = _num_boxes_device(sum(packed.sizes), dev)
+        out = dino_set_losses(sets, packed, result, nb, [dn[0]] if dn else [], dn[1] if dn else 0, dn[2] if dn else 0,
+                              self.focal_alpha)
+        if _check_enabled():
+            self._raise_on_status(result, out, len(sets), bs, packed.t_max)
+        L = out.losses
+        col = {name: c for c, name in enumerate(ARCTIC_TERMS)}
+        keys = _arctic_keys(self.losses)
+        if dn:
+            losses = {k + "_dn": L[len(sets), col[k]] for k in keys}
+        else:
+            zero = torch.zeros((), device=dev)
+            losses = {k: zero for k in DINO_ZERO_DN_KEYS}
+        for k in _arctic_keys(self.losses, log=True):
+            losses[k] = (_class_error_device(final["pred_logits"], packed, result, out.stats[0, 3]) if k == "class_error"
+                         else L[0, col[k]])
+        small = self._small_many(final, aux, targets, meta_info, args)
+        losses.update(small[0] if small else self._small(final, targets, meta_info, args, ""))
+        for i in range(len(aux)):
+            losses.update({k + f"_{i}": L[1 + i, col[k]] for k in keys})
+            losses.update(small[1 + i] if small else self._small(aux[i], targets, meta_info, args, f"_{i}"))
+        if interm is not None:
+            losses.update({k + "_interm": L[len(sets) - 1, col[k]] for k in keys})
+        if return_indices:
+            per_set = MT.indices_from_host(result.buffer.cpu(), len(sets), bs, packed.t_max, zero_if_empty=True)
+            return losses, per_set[1:] + per_set[:1]         # the reference's order: aux..., interm, final
+        return losses
+
+    @staticmethod
+    def _raise_on_status(result, out, match_sets, bs, t_max):
+        """``MSDA_CRITERION_CHECK=1``: one copy to the host (the step's one sync), then the reference's error."""
+        rows = out.stats.shape[0]
+        host = torch.cat([result.buffer, out.stats.reshape(-1).to(torch.int64)]).cpu()
+        buf, stats = host[:result.buffer.numel()], host[result.buffer.numel():].view(rows, 4).tolist()
+        MT.indices_from_host(buf, match_sets, bs, t_max, True)
+        for st, *_ in stats:
+            if st & MSDA.CRIT_BAD_LABEL:
+                raise IndexError("a target label is out of bounds for the class dimension")
+            if st & MSDA.CRIT_BAD_TARGETS:
+                raise RuntimeError("criterion: target offsets do not describe the targets")
+
+    def _forward_reference(self, outputs, targets, args, meta_info, return_indices=False):
+        """The torch restatement: the matcher per set, host indices, the denoising index lists of :620-634, host num_boxes."""
+        if "masks" in self.losses:
+            raise NotImplementedError("SetDinoCriterion: loss_masks is left out")
+        final, aux, interm = self._sets(outputs)
+        dev = final["pred_logits"].device
+
+        def terms(o, indices, num_boxes, log=False):
+            return arctic_set_losses(o, targets, indices, num_boxes, losses=self.losses, num_classes=self.num_classes,
+                                     focal_alpha=self.focal_alpha, empty=o["pred_logits"].shape[-1] - 1, log=log)
+
+        indices0 = self.matcher(final, targets)
+        indices_list = []
+        nb = _num_boxes_host(sum(len(t) for t in targets["labels"]), dev)
+        dn = self._dn(outputs)
+        if dn:
+            known, single_pad, scalar = dn
+            dn_pos_idx = 0
+            if isinstance(indices0, list):
+                dn_pos_idx = []
+                for f in range(len(targets["labels"])):
+                    if targets["is_valid"][f] != 1:
+                        continue
+                    t = torch.arange(len(targets["labels"][f]), dtype=torch.int64).unsqueeze(0).repeat(scalar, 1)
+                    out_idx = (torch.arange(scalar, dtype=torch.int64) * single_pad).unsqueeze(1) + t
+                    dn_pos_idx.append((out_idx.flatten(), t.flatten()))
+            losses = {k + "_dn": v for k, v in terms(known, dn_pos_idx, nb * scalar).items()}
+        else:
+            zero = torch.zeros((), device=dev)
+            losses = {k: zero for k in DINO_ZERO_DN_KEYS}
+        losses.update(terms(final, indices0, nb, log=True))
+        small = self._small_many(final, aux, targets, meta_info, args)
+        losses.update(small[0] if small else self._small(final, targets, meta_info, args, ""))
+        for i, a in enumerate(aux):
+            indices = self.matcher(a, targets)
+            indices_list.append(indices)
+            losses.update({k + f"_{i}": v for k, v in terms(a, indices, nb).items()})
+            losses.update(small[1 + i] if small else self._small(a, targets, meta_info, args, f"_{i}"))
+        if interm is not None:
+            indices = self.matcher(interm, targets)
+            indices_list.append(indices)
+            losses.update({k + "_interm": v for k, v in terms(interm, indices, nb).items()})
+        for i, enc in enumerate(outputs.get("enc_outputs", ())):
+            indices = self.matcher(enc, targets)
+            indices_list.append(indices)
+            losses.update({k + f"_enc_{i}": v for k, v in terms(enc, indices, nb).items()})
+        if return_indices:
+            return losses, indices_list + [indices0]
         return losses

@@ -1198,6 +1198,144 @@ int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const floa
     return msda::launch_criterion_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
 }
 
+/* ---- the DINO criterion's matched and denoising losses (msda_criterion_dino.hip) ---- */
+static int check_criterion_dino(const char *who, const float *const *pred_logits, const float *const *pred_hand_key,
+                                const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
+                                int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
+                                const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                                const int32_t *is_valid, const float *num_boxes, msda::DinoCritArgs &a, msda::CritSets &p)
+{
+    char buf[256];
+    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 1 || bs > msda::kMatchMaxQueries) {
+        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 1 <= bs <= %d", who, msda::kMatchMaxSets,
+                      msda::kMatchMaxQueries);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (K < 1 || D < 0 || n_targets < 0) {
+        std::snprintf(buf, sizeof(buf), "%s: need K >= 1, D >= 0 and n_targets >= 0", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    const bool has_kp = keypoints != nullptr;
+    if (has_kp != (D > 0)) {
+        std::snprintf(buf, sizeof(buf), "%s: need D >= 1 with target keypoints, D = 0 without", who);
+        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+    }
+    if (pred_logits == nullptr || Q == nullptr || match_set == nullptr || offsets == nullptr || num_boxes == nullptr
+        || is_valid == nullptr || (n_targets > 0 && labels == nullptr)
+        || (has_kp && (pred_hand_key == nullptr || pred_obj_key == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+    if (n_targets * (D > 1 ? D : 1) >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: tensors beyond 2^31 elements");
+    p = {};
+    a = {};
+    long long chunks = 0;
+    for (int s = 0; s < sets; ++s) {
+        if (Q[s] < 1) {
+            std::snprintf(buf, sizeof(buf), "%s: need Q[s] >= 1 in every set", who);
+            return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+        }
+        if (match_set[s] < 0) {
+            if (groups < 1 || single_pad < 1 || (long long)groups * single_pad != Q[s]) {
+                std::snprintf(buf, sizeof(buf), "%s: a denoising set needs groups >= 1, single_pad >= 1 and Q[s] = groups * "
+                                                "single_pad", who);
+                return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+            }
+        } else {
+            if (match_set[s] >= match_sets || t_max < 0 || t_max > msda::kMatchMaxTargets) {
+                std::snprintf(buf, sizeof(buf), "%s: a matched set needs match_set[s] < match_sets and 0 <= t_max <= %d", who,
+                              msda::kMatchMaxTargets);
+                return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+            }
+            if (match == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer (match)");
+        }
+        if ((long long)bs * Q[s] * (K > D ? K : D) >= (1LL << 31))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: tensors beyond 2^31 elements");
+        if (pred_logits[s] == nullptr || (has_kp && (pred_hand_key[s] == nullptr || pred_obj_key[s] == nullptr)))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+        p.logits[s] = pred_logits[s];
+        p.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
+        p.obj[s] = has_kp ? pred_obj_key[s] : nullptr;
+        a.Q[s] = Q[s];
+        a.match_set[s] = match_set[s] < 0 ? -1 : match_set[s];
+        a.chunk_base[s] = (int)chunks;
+        chunks += (long long)bs * ((Q[s] + msda::kDinoCritChunkRows - 1) / msda::kDinoCritChunkRows);   // < 2^31 / 256 * 16
+    }
+    a.sets = sets;
+    a.bs = bs;
+    a.K = K;
+    a.D = D;
+    a.t_max = t_max;
+    a.match_sets = match_sets;
+    a.single_pad = single_pad;
+    a.groups = groups;
+    a.match = match;
+    a.labels = labels;
+    a.tgt_kp = keypoints;
+    a.offsets = offsets;
+    a.n_targets = n_targets;
+    a.is_valid = is_valid;
+    a.num_boxes = num_boxes;
+    a.chunks = (int)chunks;
+    return MSDA_OK;
+}
+
+int msda_criterion_dino_fwd_f32(const float *const *pred_logits, const float *const *pred_hand_key,
+                                const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
+                                int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
+                                const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                                const int32_t *is_valid, unsigned long long hand_mask, const float *num_boxes,
+                                float focal_alpha, void *workspace, unsigned long long workspace_bytes, float *losses,
+                                int32_t *stats, msda_stream_t stream)
+{
+    msda::DinoCritArgs a;
+    msda::CritSets p;
+    int rc = check_criterion_dino("msda_criterion_dino_fwd_f32", pred_logits, pred_hand_key, pred_obj_key, Q, match_set, sets, bs,
+                                  K, D, single_pad, groups, match, match_sets, t_max, labels, keypoints, offsets, n_targets,
+                                  is_valid, num_boxes, a, p);
+    if (rc != MSDA_OK) return rc;
+    if (losses == nullptr || stats == nullptr || workspace == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+    if (((uintptr_t)workspace & 7u) != 0 || workspace_bytes < (unsigned long long)a.chunks * msda::kDinoCritPartialBytes)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino_fwd_f32: the workspace needs 8-byte alignment and "
+                                                  "MSDA_CRITERION_DINO_PARTIAL_BYTES per chunk");
+    a.hand_mask = hand_mask;
+    a.alpha = focal_alpha;
+    msda::begin_call();
+    return msda::launch_criterion_dino_fwd(a, p, workspace, losses, stats, (hipStream_t)stream);
+}
+
+int msda_criterion_dino_bwd_f32(const float *const *pred_logits, const float *const *pred_hand_key,
+                                const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
+                                int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
+                                const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
+                                const int32_t *is_valid, unsigned long long hand_mask, const float *num_boxes,
+                                float focal_alpha, const float *grad_losses, const int32_t *stats, float *const *grad_logits,
+                                float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream)
+{
+    msda::DinoCritArgs a;
+    msda::CritSets p;
+    int rc = check_criterion_dino("msda_criterion_dino_bwd_f32", pred_logits, pred_hand_key, pred_obj_key, Q, match_set, sets, bs,
+                                  K, D, single_pad, groups, match, match_sets, t_max, labels, keypoints, offsets, n_targets,
+                                  is_valid, num_boxes, a, p);
+    if (rc != MSDA_OK) return rc;
+    const bool has_kp = keypoints != nullptr;
+    if (grad_losses == nullptr || stats == nullptr || grad_logits == nullptr
+        || (has_kp && (grad_hand_key == nullptr || grad_obj_key == nullptr)))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+    msda::CritGrads g = {};
+    for (int s = 0; s < sets; ++s) {
+        if (grad_logits[s] == nullptr || (has_kp && (grad_hand_key[s] == nullptr || grad_obj_key[s] == nullptr)))
+            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+        g.logits[s] = grad_logits[s];
+        g.hand[s] = has_kp ? grad_hand_key[s] : nullptr;
+        g.obj[s] = has_kp ? grad_obj_key[s] : nullptr;
+    }
+    a.hand_mask = hand_mask;
+    a.alpha = focal_alpha;
+    msda::begin_call();
+    return msda::launch_criterion_dino_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
+}
+
 /* ---- the DETR prediction heads, fp32 and under bf16 autocast (msda_heads.hip plans both; msda_heads_bf16.hip) ---- */
 int msda_heads_supported(int C) { return msda::heads_supported(msda::kHeadsF32, C) ? 1 : 0; }
 int msda_heads_bf16_supported(int C) { return msda::heads_supported(msda::kHeadsBf16, C) ? 1 : 0; }

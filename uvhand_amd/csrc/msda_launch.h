@@ -220,6 +220,30 @@ int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, in
 int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
                          const int32_t *stats, hipStream_t stream);
 
+// ---- the DINO criterion's matched and denoising losses (msda_criterion_dino.hip); status bits and columns as above ----
+constexpr int kDinoCritChunkRows = 256;      // rows of one frame a forward / backward workgroup covers (include/msda.h)
+constexpr int kDinoCritPartialBytes = 64;    // one forward workgroup's partial record in the workspace
+struct DinoCritArgs {
+    int sets, bs, K, D, t_max, match_sets, single_pad, groups;
+    const int64_t *match;       // the matcher's result buffer (match_sets sets); NULL when every set is a denoising set
+    const int64_t *labels;
+    const float *tgt_kp;        // [n_targets, D] or NULL (D = 0)
+    const int64_t *offsets;
+    long long n_targets;
+    const int32_t *is_valid;    // slot k pairs with the k-th valid frame
+    unsigned long long hand_mask;
+    const float *num_boxes;     // device scalar
+    float alpha;
+    int Q[kMatchMaxSets];
+    int match_set[kMatchMaxSets];    // the set's index in `match`, or -1: a denoising set
+    int chunk_base[kMatchMaxSets];   // the set's first chunk; chunk = (set, frame, kDinoCritChunkRows rows of the frame)
+    int chunks;                      // of all sets
+};
+int launch_criterion_dino_fwd(const DinoCritArgs &a, const CritSets &p, void *workspace, float *losses, int32_t *stats,
+                              hipStream_t stream);
+int launch_criterion_dino_bwd(const DinoCritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
+                              const int32_t *stats, hipStream_t stream);
+
 // ---- the DeformableDETR prediction heads as grouped GEMMs: fp32 (msda_heads.hip) and bf16 autocast (msda_heads_bf16.hip) ----
 // One set of problem tables, one planner (msda_heads.hip) and one workspace layout serve both forms; a table says beside every
 // pointer that can be either whether it is bf16, and the fp32 kernels ignore those flags.  Every problem table travels by value

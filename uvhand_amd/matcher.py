@@ -1,5 +1,5 @@
 """The Hungarian matchers of UVHand's criterion (models/matcher.py: ArcticMatcher :20-125, AssemblyMatcher :128-230) on HIP
-(csrc/msda_matcher.hip, include/msda.h).
+(csrc/msda_matcher.hip, include/msda.h), and DINO's HungarianMatcher (models/dino/matcher.py:25-130) over the same kernel.
 
 The reference builds the cost matrix of every query of every frame against every target of the batch, copies it to the
 host and runs scipy's ``linear_sum_assignment`` per frame; its ``is_valid[idx] == 1`` comprehensions sync once per frame
@@ -155,10 +155,10 @@ def indices_from_host(buffer, sets, bs, t_max, zero_if_empty=False):
 
 
 # ---- the reference's composition --------------------------------------------------------------------------------------
-def _class_cost(logits, ids):
+def _class_cost(logits, ids, alpha=ALPHA):
     prob = logits.flatten(0, 1).sigmoid()
-    neg = (1 - ALPHA) * (prob ** GAMMA) * (-(1 - prob + 1e-8).log())
-    pos = ALPHA * ((1 - prob) ** GAMMA) * (-(prob + 1e-8).log())
+    neg = (1 - alpha) * (prob ** GAMMA) * (-(1 - prob + 1e-8).log())
+    pos = alpha * ((1 - prob) ** GAMMA) * (-(prob + 1e-8).log())
     return pos[:, ids] - neg[:, ids]
 
 
@@ -168,8 +168,9 @@ def _solve_blocks(C, sizes):
     return [(torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64)) for i, j in pairs]
 
 
-def arctic_composition(outputs, targets, cost_class, cost_keypoint):
-    """ArcticMatcher.forward as the reference computes it (host reads of is_valid, torch cost, .cpu(), scipy)."""
+def arctic_composition(outputs, targets, cost_class, cost_keypoint, alpha=ALPHA):
+    """ArcticMatcher.forward as the reference computes it (host reads of is_valid, torch cost, .cpu(), scipy); ``alpha``:
+    the focal cost's alpha (fixed in ArcticMatcher, a constructor argument of DINO's HungarianMatcher)."""
     logits = outputs["pred_logits"]
     bs, Q = logits.shape[:2]
     valid = [f for f in range(len(targets["labels"])) if targets["is_valid"][f] == 1]
@@ -177,7 +178,7 @@ def arctic_composition(outputs, targets, cost_class, cost_keypoint):
     if not ids:
         return 0
     ids = torch.tensor(ids, device=logits.device)
-    cost = _class_cost(logits, ids)
+    cost = _class_cost(logits, ids, alpha)
     if "keypoints" in targets:
         tgt = torch.cat([targets["keypoints"][f] for f in valid], dim=0)
         hand = (ids == HAND_LABELS[0]) | (ids == HAND_LABELS[1])
@@ -221,26 +222,54 @@ class _MatcherBase(nn.Module):
         assert cost_class != 0 or cost_keypoint != 0, "all costs cant be 0"
 
 
+def _arctic_forward(outputs, targets, cost_class, cost_keypoint, alpha=ALPHA):
+    """One set's host index lists over ARCTIC-style targets: one launch and one copy, or the composition."""
+    with torch.no_grad():
+        logits = outputs["pred_logits"]
+        preds = [logits]
+        if "keypoints" in targets:
+            preds += [outputs["pred_hand_key"], outputs["pred_obj_key"]]
+        sizes = [len(t) for t in targets["labels"]]
+        kps = list(targets["keypoints"]) if "keypoints" in targets else []
+        if not (alpha == ALPHA and _fused_ok(preds, sizes, logits.shape[0], [k for k in kps if torch.is_tensor(k)])
+                and all(torch.is_tensor(k) and k.dtype == torch.float32 for k in kps)
+                and all(k.shape[-1] == preds[-1].shape[-1] <= MSDA.MATCH_MAX_DIM for k in kps)):
+            return arctic_composition(outputs, targets, cost_class, cost_keypoint, alpha)
+        packed = pack_targets(targets, logits.device)
+        res = match([outputs], packed, cost_class, cost_keypoint)
+        return indices_from_host(res.buffer.cpu(), 1, logits.shape[0], packed.t_max, zero_if_empty=True)[0]
+
+
 class ArcticMatcher(_MatcherBase):
     """Drop-in for models/matcher.py:20-125.  ``forward(outputs, targets)``: ``outputs`` has ``pred_logits`` [bs, Q, K] and
     (when ``targets`` has ``keypoints``) ``pred_hand_key`` / ``pred_obj_key`` [bs, Q, D]; ``targets`` is the reference's
     dict.  Returns one ``(query_idx, target_idx)`` pair of int64 CPU tensors per valid frame, or 0 without any label."""
 
     def forward(self, outputs, targets):
-        with torch.no_grad():
-            logits = outputs["pred_logits"]
-            preds = [logits]
-            if "keypoints" in targets:
-                preds += [outputs["pred_hand_key"], outputs["pred_obj_key"]]
-            sizes = [len(t) for t in targets["labels"]]
-            kps = list(targets["keypoints"]) if "keypoints" in targets else []
-            if not (_fused_ok(preds, sizes, logits.shape[0], [k for k in kps if torch.is_tensor(k)])
-                    and all(torch.is_tensor(k) and k.dtype == torch.float32 for k in kps)
-                    and all(k.shape[-1] == preds[-1].shape[-1] <= MSDA.MATCH_MAX_DIM for k in kps)):
-                return arctic_composition(outputs, targets, self.cost_class, self.cost_keypoint)
-            packed = pack_targets(targets, logits.device)
-            res = match([outputs], packed, self.cost_class, self.cost_keypoint)
-            return indices_from_host(res.buffer.cpu(), 1, logits.shape[0], packed.t_max, zero_if_empty=True)[0]
+        return _arctic_forward(outputs, targets, self.cost_class, self.cost_keypoint)
+
+
+class DinoHungarianMatcher(nn.Module):
+    """Drop-in for DINO's HungarianMatcher (models/dino/matcher.py:25-130): the reference's constructor and assertion, and
+    ``forward(outputs, targets)`` over the ARCTIC targets dict.  Its cost is ArcticMatcher's with ``cost_bbox`` in the place of
+    ``cost_keypoint`` (``cost_giou`` is kept and, as in the reference, unused), so ``cost_keypoint`` reads ``cost_bbox`` for
+    ``match``'s callers.  The kernel's focal alpha is 0.25; any other ``focal_alpha`` takes the torch composition.  (The
+    reference raises without any valid label, where this returns 0 as ArcticMatcher does.)"""
+
+    def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1, focal_alpha=0.25):
+        super().__init__()
+        self.cost_class = cost_class
+        self.cost_bbox = cost_bbox
+        self.cost_giou = cost_giou
+        assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0, "all costs cant be 0"
+        self.focal_alpha = focal_alpha
+
+    @property
+    def cost_keypoint(self):
+        return self.cost_bbox
+
+    def forward(self, outputs, targets):
+        return _arctic_forward(outputs, targets, self.cost_class, self.cost_bbox, self.focal_alpha)
 
 
 class AssemblyMatcher(_MatcherBase):

@@ -583,6 +583,38 @@ int msda_dino_refine_forward_f32(const float *ref, const float *cls, int K, cons
 int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const uint8_t *code, long long M, float *grad_key,
                                   float *grad_obj, msda_stream_t stream);
 
+/* ---- DINO's two-stage query selection (models/dino/deformable_transformer.py:348-387) -------------------------------------
+ * Added after MSDA_ABI_VERSION 116 without a version bump: the four entries below are purely additive (no existing
+ * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.
+ *
+ * The rule is msda_two_stage_select_f32's, for any number of rows per frame: per frame the Q rows with the largest max_k
+ * cls[n, s, k], descending; ties: the lower row first; NaN above every number, -0 equal to +0; per-row max / argmax as
+ * torch.max(-1) / argmax(-1) (first maximum; NaN wins).
+ *   msda_dino_select_supported(S, K, Q, C)  1 = the kernels take it: 1 <= Q <= min(S, 2048), S <= 1048576, 1 <= K <= 256,
+ *       C a multiple of 4 in 4..2048.
+ *   msda_dino_select_workspace_bytes(N, S)  the size of `workspace` (a host function of N and S; 0 for an empty problem).
+ *   msda_dino_select_forward_f32   cls [N, S, K], memory [N, S, C], proposals [N, S, 42], all fp32 contiguous.  Replaces the
+ *       torch.topk of :349, the class gather of :353-355, the gathers of :369 and :387 and — with the caller's two
+ *       torch.where — the boolean-mask assignments of :376-377 (a nonzero and a host synchronisation each).  Writes topk
+ *       [N, Q] int64; slot [N, S] int32, the inverse map (q at a selected row, -1 elsewhere: every element written); tgt
+ *       [N, Q, C], the selected rows of memory (:387); prop_sel [N, Q, 42], the selected rows of proposals (:369; +inf rows are
+ *       copied as +inf); code [N, Q] bytes: 2 if the row's class argmax is hand_class0 / hand_class1, 1 if it is neither and
+ *       not 0, else 0 (:353-355).  Two launches: the rows' keys, then one workgroup per frame (radix select of the Q-th key,
+ *       a sort of the Q selected keys, the gathers).  memory, tgt and workspace 16-byte aligned.
+ *   msda_dino_select_backward_f32  the gradient of tgt with respect to memory (the gather of :387): grad_memory [N, S, C] =
+ *       grad_tgt[n, slot[n, s]] where slot >= 0, else 0.  Every element is written by the one launch: no memset before it.
+ *       grad_tgt and grad_memory 16-byte aligned.
+ * No allocation, no synchronisation, integer LDS atomics only: bitwise reproducible, capturable in a graph.  Argument
+ * errors (MSDA_ERR_ARGUMENT before any launch): Q > S, sizes msda_dino_select_supported refuses, N above 65535, tensors
+ * beyond 2^31 elements, a null or misaligned pointer with N > 0.  N == 0 returns MSDA_OK. */
+int msda_dino_select_supported(int S, int K, int Q, int C);
+unsigned long long msda_dino_select_workspace_bytes(int N, int S);
+int msda_dino_select_forward_f32(const float *cls, const float *memory, const float *proposals, int N, int S, int K, int Q, int C,
+                                 int hand_class0, int hand_class1, int64_t *topk, int32_t *slot, float *tgt, float *prop_sel,
+                                 uint8_t *code, void *workspace, msda_stream_t stream);
+int msda_dino_select_backward_f32(const int32_t *slot, const float *grad_tgt, int N, int S, int Q, int C, float *grad_memory,
+                                  msda_stream_t stream);
+
 /* ---- DINO's contrastive-denoising queries (models/dino/dn_components.py:20-150, prepare_for_cdn) ---------------------------
  * Added after MSDA_ABI_VERSION 116 without a version bump: the three entries below are purely additive (no existing
  * declaration changed), so a binding compiled against 116 keeps working; callers probe them by symbol.

@@ -106,6 +106,11 @@ SIGNATURES = {
     "msda_dino_query_pos_forward_f32": "i p i p i l ppppp pp p",
     "msda_dino_refine_forward_f32": "i pp i pp ii l pp p",
     "msda_dino_refine_backward_f32": "i ppp l pp p",
+    # DINO's two-stage query selection for any number of rows per frame
+    "msda_dino_select_supported": "i iiii",
+    "msda_dino_select_workspace_bytes": "U ii",
+    "msda_dino_select_forward_f32": "i ppp iiiiiii ppppp p p",
+    "msda_dino_select_backward_f32": "i pp iiii p p",
     # DINO's contrastive-denoising queries
     "msda_cdn_supported": "i ii ll",
     "msda_cdn_prepare_forward_f32": "i ppppp i l ii l iii u f pppp p",
@@ -1359,6 +1364,60 @@ def dino_refine_backward(grad_out, out, code, want_key=True, want_obj=True):
     _launch(out.device, "msda_dino_refine_backward_f32", "dino_refine_backward", grad_out.data_ptr(), out.data_ptr(), code.data_ptr(),
             code.numel(), gk.data_ptr() if want_key else None, go.data_ptr() if want_obj else None)
     return gk, go
+
+
+# ---- DINO's two-stage query selection (csrc/msda_dino_select.hip) ------------------------------------------------------------
+DINO_SELECT_MAX_FRAMES = 65535                        # frames per call (a grid dimension)
+
+
+def dino_select_supported(S, K, Q, C):
+    """msda_dino_select_supported: 1 <= Q <= min(S, 2048), S <= 2^20, 1 <= K <= 256, C a multiple of 4 in 4..2048."""
+    return bool((_lib or load()).msda_dino_select_supported(int(S), int(K), int(Q), int(C)))
+
+
+def dino_select_workspace_bytes(N, S):
+    """msda_dino_select_workspace_bytes: the bytes of scratch one forward of N frames of S rows needs."""
+    return int((_lib or load()).msda_dino_select_workspace_bytes(int(N), int(S)))
+
+
+def dino_select_forward(cls, memory, proposals, num_queries, hand_classes=(12, 13)):
+    """(topk [N,Q] int64, slot [N,S] int32, tgt [N,Q,C], prop_sel [N,Q,42], code [N,Q] uint8) — msda_dino_select_forward_f32:
+    two launches, no host synchronisation.  Raises RuntimeError when Q exceeds the rows per frame (as torch.topk does)."""
+    ts = (cls, memory, proposals)
+    if not (all(_f32_cuda(t) and t.dim() == 3 and t.device == cls.device and tuple(t.shape[:2]) == tuple(cls.shape[:2]) for t in ts)
+            and proposals.shape[-1] == 42):
+        raise RuntimeError("dino_select_forward: expected contiguous fp32 CUDA cls [N,S,K], memory [N,S,C] and proposals [N,S,42]")
+    N, S, K = cls.shape
+    C, Q = memory.shape[-1], int(num_queries)
+    if Q > S:
+        raise RuntimeError("selected index k out of range")
+    dev = cls.device
+    topk = torch.empty((N, Q), dtype=torch.int64, device=dev)
+    slot = torch.empty((N, S), dtype=torch.int32, device=dev)
+    tgt = torch.empty((N, Q, C), dtype=torch.float32, device=dev)
+    prop_sel = torch.empty((N, Q, 42), dtype=torch.float32, device=dev)
+    code = torch.empty((N, Q), dtype=torch.uint8, device=dev)
+    workspace = torch.empty((max(16, dino_select_workspace_bytes(N, S)),), dtype=torch.uint8, device=dev)
+    _launch(dev, "msda_dino_select_forward_f32", "dino_select_forward", cls.data_ptr(), memory.data_ptr(), proposals.data_ptr(),
+            N, S, K, Q, C, int(hand_classes[0]), int(hand_classes[1]), topk.data_ptr(), slot.data_ptr(), tgt.data_ptr(),
+            prop_sel.data_ptr(), code.data_ptr(), workspace.data_ptr())
+    return topk, slot, tgt, prop_sel, code
+
+
+def dino_select_backward(slot, grad_tgt, out=None):
+    """grad_memory [N,S,C] — msda_dino_select_backward_f32: every element written by the one launch (``out``: a buffer to fill)."""
+    if not (slot.is_cuda and slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and _f32_cuda(grad_tgt)
+            and grad_tgt.dim() == 3 and grad_tgt.shape[0] == slot.shape[0] and grad_tgt.device == slot.device):
+        raise RuntimeError("dino_select_backward: expected contiguous CUDA int32 slot [N,S] and fp32 grad_tgt [N,Q,C]")
+    N, S = slot.shape
+    Q, C = grad_tgt.shape[1], grad_tgt.shape[2]
+    if out is None:
+        out = torch.empty((N, S, C), dtype=torch.float32, device=slot.device)
+    elif not (_f32_cuda(out) and tuple(out.shape) == (N, S, C) and out.device == slot.device):
+        raise RuntimeError("dino_select_backward: out must be contiguous fp32 CUDA [N,S,C]")
+    _launch(slot.device, "msda_dino_select_backward_f32", "dino_select_backward", slot.data_ptr(), grad_tgt.data_ptr(), N, S, Q, C,
+            out.data_ptr())
+    return out
 
 
 # ---- DINO's contrastive-denoising queries (csrc/msda_cdn.hip) --------------------------------------------------------------

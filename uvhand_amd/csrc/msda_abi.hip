@@ -910,6 +910,60 @@ int msda_dino_refine_backward_f32(const float *grad_out, const float *out, const
     return msda::launch_dino_refine_bwd(grad_out, out, code, M, grad_key, grad_obj, (hipStream_t)stream);
 }
 
+/* ---- DINO's two-stage query selection (msda_dino_select.hip) ---- */
+int msda_dino_select_supported(int S, int K, int Q, int C)
+{
+    return S >= 1 && S <= msda::kDinoSelMaxRows && Q >= 1 && Q <= S && Q <= msda::kDinoSelMaxQueries && K >= 1 && K <= 256 &&
+           C >= 4 && (C & 3) == 0 && C <= 2048;
+}
+
+unsigned long long msda_dino_select_workspace_bytes(int N, int S)
+{
+    if (N <= 0 || S <= 0) return 0;
+    return (unsigned long long)msda::dino_select_workspace_bytes(N, S);
+}
+
+int msda_dino_select_forward_f32(const float *cls, const float *memory, const float *proposals, int N, int S, int K, int Q, int C,
+                                 int hand_class0, int hand_class1, int64_t *topk, int32_t *slot, float *tgt, float *prop_sel,
+                                 uint8_t *code, void *workspace, msda_stream_t stream)
+{
+    if (N < 0 || N > msda::kDinoSelMaxFrames)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: need 0 <= N <= 65535");
+    if (S >= 1 && Q > S) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: selected index k out of range (Q > S)");
+    if (!msda_dino_select_supported(S, K, Q, C))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: need 1 <= Q <= min(S, 2048), S <= 2^20, 1 <= K <= 256 "
+                                                  "and C a multiple of 4 in 4..2048");
+    const int widest = C > K ? (C > 42 ? C : 42) : (K > 42 ? K : 42);
+    if ((long long)N * S * widest >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: tensors beyond 2^31 elements");
+    if (N == 0) return MSDA_OK;
+    if (cls == nullptr || memory == nullptr || proposals == nullptr || topk == nullptr || slot == nullptr || tgt == nullptr ||
+        prop_sel == nullptr || code == nullptr || workspace == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: null device pointer");
+    if (misaligned16(memory) || misaligned16(tgt) || misaligned16(workspace))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_forward_f32: memory, tgt and workspace must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_dino_select_fwd(cls, memory, proposals, N, S, K, Q, C, hand_class0, hand_class1, topk, slot, tgt, prop_sel,
+                                        code, workspace, (hipStream_t)stream);
+}
+
+int msda_dino_select_backward_f32(const int32_t *slot, const float *grad_tgt, int N, int S, int Q, int C, float *grad_memory,
+                                  msda_stream_t stream)
+{
+    if (N < 0 || S < 1 || Q < 1 || Q > S || Q > msda::kDinoSelMaxQueries || C < 4 || (C & 3) || C > 2048)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_backward_f32: need N >= 0, 1 <= Q <= min(S, 2048) and C a multiple "
+                                                  "of 4 in 4..2048");
+    if ((long long)N * S * C >= (1LL << 31))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_backward_f32: tensors beyond 2^31 elements");
+    if (N == 0) return MSDA_OK;
+    if (slot == nullptr || grad_tgt == nullptr || grad_memory == nullptr)
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_backward_f32: null device pointer");
+    if (misaligned16(grad_tgt) || misaligned16(grad_memory))
+        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_dino_select_backward_f32: grad_tgt and grad_memory must be 16-byte aligned");
+    msda::begin_call();
+    return msda::launch_dino_select_bwd(slot, grad_tgt, N, S, Q, C, grad_memory, (hipStream_t)stream);
+}
+
 /* ---- DINO's contrastive-denoising queries (msda_cdn.hip) ---- */
 int msda_cdn_supported(int hidden, int width, long long rows_book, long long E)
 {

@@ -163,6 +163,17 @@ int launch_dino_refine_fwd(const float *ref, const float *cls, int K, const floa
 int launch_dino_refine_bwd(const float *gout, const float *out, const uint8_t *code, long long M, float *gkey, float *gobj,
                            hipStream_t stream);
 
+// ---- DINO's two-stage query selection for any number of rows per frame (msda_dino_select.hip); checked arguments ----
+constexpr int kDinoSelMaxQueries = 2048;    // queries of a frame (their 64-bit keys are sorted in 16 KB of LDS)
+constexpr int kDinoSelMaxRows = 1 << 20;    // rows of a frame (one workgroup reads a frame's keys once per radix digit)
+constexpr int kDinoSelMaxFrames = 65535;    // frames (a grid dimension)
+size_t dino_select_workspace_bytes(int N, int S);
+int launch_dino_select_fwd(const float *cls, const float *memory, const float *proposals, int N, int S, int K, int Q, int C,
+                           int hand0, int hand1, int64_t *topk, int32_t *slot, float *tgt, float *prop_sel, uint8_t *code,
+                           void *workspace, hipStream_t stream);
+int launch_dino_select_bwd(const int32_t *slot, const float *grad_tgt, int N, int S, int Q, int C, float *grad_memory,
+                           hipStream_t stream);
+
 // ---- DINO's contrastive-denoising queries and the label embedding's gradient (msda_cdn.hip); checked arguments ----
 int launch_cdn_prepare_fwd(const int64_t *labels, const int64_t *offsets, const float *keys, const float *weight, const long long *seed,
                            int B, long long T, int W, int H, long long rows_book, int single_pad, int groups, int num_classes,

@@ -14,7 +14,11 @@ models/dino/utils.py:138-165) on HIP (csrc/msda_dino.hip, include/msda.h):
   * ``refine``  the per-layer refinement: the reference adds the key / object head's output to the rows its class argmax
     selects with boolean-mask indexing (``outputs_unsig[obj_idx] += ...``, :796-797 — a ``nonzero`` and a host
     synchronisation each); here one launch per direction.  Unlike ARCTIC's refinement the result is not detached where the
-    model reads it (dino.py:329-337, "look forward twice"), so the node has a backward: gradient to the two deltas.
+    model reads it (dino.py:329-337, "look forward twice"), so the node has a backward: gradient to the two deltas;
+  * ``select_queries_dino``  the transformer's two-stage selection (:348-387) for any number of encoder rows per frame
+    (csrc/msda_dino_select.hip): the top ``num_queries`` rows by their largest class logit, the rows of ``output_memory`` and
+    of the proposals they select and the class rule's code per row, as ONE autograd node — two launches forward, and a backward
+    of one launch that writes every element of ``output_memory``'s gradient.
 
 Every piece runs the reference's composition instead — the same torch ops the reference runs, boolean-index adds and their
 synchronisations included — on CPU tensors, other dtypes, under autocast, with hooks on the MLP, for reference points that
@@ -235,3 +239,61 @@ def refine(reference_points, cls_out, delta_key, delta_obj, hand_classes=HAND_CL
         unsig = torch.where(hand[..., None], unsig + delta_key, unsig)
         return unsig.sigmoid() * 2 - 1
     return refine_composition(reference_points, cls_out, delta_key, delta_obj, hand_classes)
+
+
+# ---- two-stage query selection ------------------------------------------------------------------------------------------------
+def dino_select_composition(enc_class, output_memory, output_proposals, topk, hand_classes=HAND_CLASSES):
+    """(topk_idx [N, Q] int64, tgt_undetach [N, Q, C], prop_sel [N, Q, 42], code [N, Q] uint8): the reference's selection
+    (:348-355, :369, :387) in torch ops, on any device and without a host synchronisation.  The rule the kernels follow: per
+    frame the Q rows with the largest row maximum, descending; ties: the lower row first; NaN above every number, -0 equal to
+    +0.  ``torch.topk`` promises no order among equal values, so the order is a stable descending sort of the row maxima."""
+    row_max = enc_class.max(-1)[0]
+    if int(topk) > row_max.shape[1]:
+        return torch.topk(row_max, int(topk), dim=1)                 # torch's own error ("selected index k out of range")
+    topk_idx = torch.sort(row_max.detach(), dim=1, descending=True, stable=True)[1][:, :int(topk)]
+    classes = torch.gather(enc_class.argmax(dim=-1), 1, topk_idx)
+    hand = (classes == hand_classes[0]) | (classes == hand_classes[1])
+    code = hand.to(torch.uint8) * 2 + (~hand & (classes != 0)).to(torch.uint8)
+    tgt = torch.gather(output_memory, 1, topk_idx.unsqueeze(-1).expand(-1, -1, output_memory.shape[-1]))
+    prop_sel = torch.gather(output_proposals.detach(), 1, topk_idx.unsqueeze(-1).expand(-1, -1, output_proposals.shape[-1]))
+    return topk_idx, tgt, prop_sel, code
+
+
+class _DinoSelectFn(Function):
+    """The selection as one node (msda_dino_select_forward_f32): only the gathered rows of ``output_memory`` are
+    differentiable, and only with respect to it; the inverse map ``slot`` is what the backward reads — one launch that writes
+    every element of the gradient (selected rows copied, the others zero)."""
+
+    @staticmethod
+    def forward(ctx, enc_class, output_memory, output_proposals, topk, hand_classes):
+        idx, slot, tgt, prop_sel, code = MSDA.dino_select_forward(enc_class, output_memory, output_proposals, topk, hand_classes)
+        ctx.save_for_backward(slot)
+        ctx.mark_non_differentiable(idx, prop_sel, code)
+        return idx, tgt, prop_sel, code
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_idx, g_tgt, g_prop, g_code):
+        (slot,) = ctx.saved_tensors
+        gm = MSDA.dino_select_backward(slot, g_tgt.contiguous()) if ctx.needs_input_grad[1] else None
+        return None, gm, None, None, None
+
+
+def select_fusable(enc_class, output_memory, output_proposals, topk):
+    ts = (enc_class, output_memory, output_proposals)
+    return (_plain_cuda_f32(*ts) and all(t.dim() == 3 for t in ts) and output_proposals.shape[-1] == 42
+            and tuple(output_memory.shape[:2]) == tuple(enc_class.shape[:2]) == tuple(output_proposals.shape[:2])
+            and 0 < enc_class.shape[0] <= MSDA.DINO_SELECT_MAX_FRAMES and all(t.numel() < (1 << 31) for t in ts)
+            and MSDA.dino_select_supported(enc_class.shape[1], enc_class.shape[2], int(topk), output_memory.shape[-1]))
+
+
+def select_queries_dino(enc_class, output_memory, output_proposals, topk, hand_classes=HAND_CLASSES):
+    """(topk_idx [N, Q] int64, tgt_undetach [N, Q, C], prop_sel [N, Q, 42], code [N, Q] uint8) for class logits [N, S, K],
+    ``output_memory`` [N, S, C] and ``output_proposals`` [N, S, 42]: the top ``topk`` rows per frame by their largest class
+    logit, the rows of the two tensors they select and the class rule's code per row (2 hand, 1 object, 0 neither).  Only
+    ``tgt_undetach`` carries gradient, to ``output_memory``.  HIP kernels for fp32 CUDA tensors outside autocast within
+    msda_dino_select_supported's envelope; ``dino_select_composition`` otherwise."""
+    if select_fusable(enc_class, output_memory, output_proposals, topk):
+        return _DinoSelectFn.apply(enc_class.detach().contiguous(), output_memory.contiguous(),
+                                   output_proposals.detach().contiguous(), int(topk), tuple(hand_classes))
+    return dino_select_composition(enc_class, output_memory, output_proposals, topk, hand_classes)

@@ -4,6 +4,10 @@ from .deformable_layers import (DeformableTransformerDecoder, DeformableTransfor
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
 from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
+from .dino_deformable_transformer import DeformableTransformer as DinoDeformableTransformer
+from .dino_deformable_transformer import DeformableTransformerEncoderLayer as DinoDeformableTransformerEncoderLayer
+from .dino_deformable_transformer import TransformerEncoder as DinoTransformerEncoder
+from .dino_deformable_transformer import build_deformable_transformer as build_dino_deformable_transformer
 from .dino_transformer import DeformableTransformerDecoderLayer as DinoDeformableTransformerDecoderLayer
 from .dino_transformer import TransformerDecoder as DinoTransformerDecoder
 from .ms_deform_attn import MSDeformAttn
@@ -16,6 +20,8 @@ __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTrans
            "AssemblyDeformableTransformer", "AssemblyDeformableTransformerDecoder",
            "ArcticDeformableDETR", "AssemblyDeformableDETR",
            "DinoDeformableTransformerDecoderLayer", "DinoTransformerDecoder",
+           "DinoDeformableTransformer", "DinoTransformerEncoder", "DinoDeformableTransformerEncoderLayer",
+           "build_dino_deformable_transformer",
            "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother", "SmoothCriterion",
            "Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
            "build_swin_transformer", "PositionEmbeddingSine", "Joiner", "build_backbone"]

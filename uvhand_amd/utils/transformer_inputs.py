@@ -58,32 +58,33 @@ def get_valid_ratio(mask):
     return torch.stack([valid_w, valid_h], -1)
 
 
-def flatten_feature_levels(srcs, masks, pos_embeds, level_embed):
-    """srcs / pos_embeds: lists of [N,C,H_l,W_l]; masks: list of [N,H_l,W_l] bool; level_embed [L,C].
-    Returns (src_flatten[N,S,C], mask_flatten[N,S], lvl_pos_embed_flatten[N,S,C], spatial_shapes int64[L,2],
-    level_start_index int64[L], valid_ratios[N,L,2])."""
+def level_tensors(shapes, device):
+    """(spatial_shapes int64 [L, 2], level_start_index int64 [L]) on `device` for the levels' (H, W): one host-to-device copy."""
+    spatial_shapes = torch.as_tensor([(int(h), int(w)) for h, w in shapes], dtype=torch.long, device=device)
+    return spatial_shapes, torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
+
+
+def flatten_feature_levels(srcs, masks, pos_embeds, level_embed, pyramid=None):
+    """srcs / pos_embeds: lists of [N,C,H_l,W_l]; masks: list of [N,H_l,W_l] bool; level_embed [L,C], or None for no
+    per-level offset.  Returns (src_flatten[N,S,C], mask_flatten[N,S], lvl_pos_embed_flatten[N,S,C], spatial_shapes
+    int64[L,2], level_start_index int64[L], valid_ratios[N,L,2]).  ``pyramid``: ``level_tensors`` of these levels kept from an
+    earlier call — returned as they are instead of new ones, so that the call copies nothing from the host (a caller that
+    runs under graph capture, and MSDeformAttn's once-per-tensor check of the shapes, want the same tensors every step)."""
     srcs, masks, pos_embeds = list(srcs), list(masks), list(pos_embeds)
-    if (not torch.is_autocast_enabled() and _native.flatten_levels_supported(srcs, pos_embeds, level_embed)):
+    if (level_embed is not None and not torch.is_autocast_enabled()
+            and _native.flatten_levels_supported(srcs, pos_embeds, level_embed)):
         # MI355X path: both flattened tensors from one kernel (and one for their gradients)
-        shapes = [(s.shape[2], s.shape[3]) for s in srcs]
         src_flatten, pos_flatten = _FlattenLevelsFn.apply(level_embed, *srcs, *pos_embeds)
-        spatial_shapes = torch.as_tensor(shapes, dtype=torch.long, device=src_flatten.device)
-        level_start_index = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
-        valid_ratios = torch.stack([get_valid_ratio(m) for m in masks], 1)
-        return (src_flatten, torch.cat([m.flatten(1) for m in masks], 1), pos_flatten, spatial_shapes, level_start_index,
-                valid_ratios)
-    src_parts, mask_parts, pos_parts, shapes = [], [], [], []
-    for lvl, (src, mask, pos) in enumerate(zip(srcs, masks, pos_embeds)):
-        shapes.append((src.shape[2], src.shape[3]))
-        src_parts.append(src.flatten(2).transpose(1, 2))
-        mask_parts.append(mask.flatten(1))
-        pos_parts.append(pos.flatten(2).transpose(1, 2) + level_embed[lvl].view(1, 1, -1))
-    src_flatten = torch.cat(src_parts, 1)
-    spatial_shapes = torch.as_tensor(shapes, dtype=torch.long, device=src_flatten.device)
-    level_start_index = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
+    else:
+        src_flatten = torch.cat([src.flatten(2).transpose(1, 2) for src in srcs], 1)
+        pos_parts = [pos.flatten(2).transpose(1, 2) for pos in pos_embeds]
+        if level_embed is not None:
+            pos_parts = [pos + level_embed[lvl].view(1, 1, -1) for lvl, pos in enumerate(pos_parts)]
+        pos_flatten = torch.cat(pos_parts, 1)
+    if pyramid is None:
+        pyramid = level_tensors([(src.shape[2], src.shape[3]) for src in srcs], src_flatten.device)
     valid_ratios = torch.stack([get_valid_ratio(m) for m in masks], 1)
-    return (src_flatten, torch.cat(mask_parts, 1), torch.cat(pos_parts, 1), spatial_shapes, level_start_index,
-            valid_ratios)
+    return src_flatten, torch.cat([m.flatten(1) for m in masks], 1), pos_flatten, pyramid[0], pyramid[1], valid_ratios
 
 
 def encoder_reference_points(spatial_shapes, valid_ratios, device=None):

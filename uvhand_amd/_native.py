@@ -1482,31 +1482,75 @@ def _ptr_array(ts):
     return (_VP * len(ts))(*[t.data_ptr() for t in ts])
 
 
-def _match_checks(what, logits, heads, labels, keypoints, offsets, t_max):
-    dev = logits[0].device
-    if not (0 < len(logits) <= MATCH_MAX_SETS and all(len(h) == len(logits) for h in heads)):
-        raise RuntimeError("%s: 1 to %d prediction sets" % (what, MATCH_MAX_SETS))
-    shape = tuple(logits[0].shape)
-    if not (len(shape) == 3 and all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == shape for t in logits)):
-        raise RuntimeError("%s: expected contiguous fp32 CUDA pred_logits [bs, Q, K] of one shape in every set" % what)
-    D = keypoints.shape[1] if keypoints is not None else 0
+def match_layout(sets, bs, t_max):
+    """(numel, slices) of the matchers' int64 result (include/msda.h; MatchView in csrc/msda_set_args.h): the slices of
+    query_idx and target_idx [sets, bs, t_max], count and status [sets, bs] and the valid-frame count [1]."""
+    n, W = sets * bs, int(t_max)
+    t, c, s, v = n * W, 2 * n * W, 2 * n * W + n, 2 * n * W + 2 * n
+    return v + 1, (slice(0, t), slice(t, c), slice(c, s), slice(s, v), slice(v, v + 1))
+
+
+def match_views(buffer, sets, bs, t_max):
+    """(query_idx, target_idx, count, status, num_valid []) views of a result buffer, shaped as ``match_layout`` says."""
+    q, t, count, status, nvalid = match_layout(sets, bs, t_max)[1]
+    return (buffer[q].view(sets, bs, t_max), buffer[t].view(sets, bs, t_max), buffer[count].view(sets, bs),
+            buffer[status].view(sets, bs), buffer[nvalid.start])
+
+
+def _pred_sets_check(what, logits, heads, D, per_set_q=False, sets_ok=True):
+    """Per-set lists of fp32 CUDA pred_logits [bs, Q, K] and, per keypoint head of ``heads``, [bs, Q, D] on one device;
+    ``per_set_q`` (DINO): the sets may differ in Q.  Returns (dev, bs, the sets' Q, K)."""
+    sets = len(logits)
+    if not (0 < sets <= MATCH_MAX_SETS and all(len(h) == sets for h in heads) and sets_ok):
+        raise RuntimeError("%s: 1 to %d prediction sets%s" % (what, MATCH_MAX_SETS,
+                                                              ", one match_set entry each" if per_set_q else ""))
+    dev, shapes, q = logits[0].device, [tuple(t.shape) for t in logits], "Q_s" if per_set_q else "Q"
+    first = shapes[0] if len(shapes[0]) == 3 else None
+    if first is None or not all(_f32_cuda(t) and t.device == dev
+                                and (s == first or (per_set_q and len(s) == 3 and s[::2] == first[::2]))
+                                for t, s in zip(logits, shapes)):
+        raise RuntimeError("%s: expected contiguous fp32 CUDA pred_logits [bs, %s, K]%s in every set"
+                           % (what, q, "" if per_set_q else " of one shape"))
+    want = [s[:2] + (D,) for s in shapes]
     for h in heads:
-        if not all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == shape[:2] + (D,) for t in h):
-            raise RuntimeError("%s: expected contiguous fp32 CUDA keypoint heads [bs, Q, %d]" % (what, D))
+        if not all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == w for t, w in zip(h, want)):
+            raise RuntimeError("%s: expected contiguous fp32 CUDA keypoint heads [bs, %s, %d]" % (what, q, D))
+    return dev, first[0], [s[1] for s in shapes], first[2]
+
+
+def _set_targets_check(what, dev, bs, labels, keypoints, offsets, t_max=None):
+    """One step's targets on ``dev``; ``t_max`` for the callers that bound it here (is_valid: ``_is_valid_check``)."""
     if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 1
             and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous()
-            and tuple(offsets.shape) == (shape[0] + 1,) and labels.device == dev and offsets.device == dev):
+            and tuple(offsets.shape) == (bs + 1,) and labels.device == dev and offsets.device == dev):
         raise RuntimeError("%s: expected int64 CUDA labels [n] and offsets [bs + 1]" % what)
     if keypoints is not None and not (_f32_cuda(keypoints) and keypoints.dim() == 2 and keypoints.device == dev
                                       and keypoints.shape[0] == labels.shape[0]):
         raise RuntimeError("%s: expected contiguous fp32 CUDA target keypoints [n, D]" % what)
-    if not 0 <= int(t_max) <= MATCH_MAX_TARGETS:
+    if t_max is not None and not 0 <= int(t_max) <= MATCH_MAX_TARGETS:
         raise RuntimeError("%s: at most %d targets per frame" % (what, MATCH_MAX_TARGETS))
-    return dev, shape, D
+
+
+def _is_valid_check(what, dev, bs, is_valid):
+    if not (torch.is_tensor(is_valid) and is_valid.is_cuda and is_valid.dtype == torch.int32 and is_valid.is_contiguous()
+            and tuple(is_valid.shape) == (bs,) and is_valid.device == dev):
+        raise RuntimeError("%s: expected int32 CUDA is_valid [bs]" % what)
+
+
+def _match_buffer_check(what, dev, match, sets, bs, t_max):
+    if not (match is not None and match.is_cuda and match.dtype == torch.int64 and match.is_contiguous()
+            and match.device == dev and 0 <= int(t_max) <= MATCH_MAX_TARGETS
+            and match.numel() == match_layout(sets, bs, t_max)[0]):
+        raise RuntimeError("%s: expected the matcher's int64 CUDA result for %d sets" % (what, sets))
+
+
+def _num_boxes_check(what, dev, num_boxes):
+    if not (_f32_cuda(num_boxes) and num_boxes.numel() == 1 and num_boxes.device == dev):
+        raise RuntimeError("%s: expected an fp32 CUDA num_boxes scalar" % what)
 
 
 def _match_out(dev, sets, bs, t_max, Q, cost_debug):
-    out = torch.empty(2 * sets * bs * t_max + 2 * sets * bs + 1, dtype=torch.int64, device=dev)
+    out = torch.empty(match_layout(sets, bs, t_max)[0], dtype=torch.int64, device=dev)
     if cost_debug is not None and not (_f32_cuda(cost_debug) and cost_debug.device == dev
                                        and tuple(cost_debug.shape) == (sets, bs, Q, t_max)):
         raise RuntimeError("match: cost_debug must be contiguous fp32 CUDA [sets, bs, Q, t_max]")
@@ -1518,10 +1562,10 @@ def match_arctic(logits, hand, obj, labels, keypoints, offsets, is_valid, t_max,
     target keypoints) pred_hand_key / pred_obj_key [bs, Q, D]; labels [n] / offsets [bs + 1] int64, keypoints [n, D] fp32 or
     None, is_valid [bs] int32 on the same device.  One launch, no host synchronisation."""
     heads = (hand, obj) if keypoints is not None else ()
-    dev, (bs, Q, K), D = _match_checks("match_arctic", logits, heads, labels, keypoints, offsets, t_max)
-    if not (is_valid.is_cuda and is_valid.dtype == torch.int32 and is_valid.is_contiguous() and tuple(is_valid.shape) == (bs,)
-            and is_valid.device == dev):
-        raise RuntimeError("match_arctic: expected int32 CUDA is_valid [bs]")
+    D = keypoints.shape[1] if keypoints is not None else 0
+    dev, bs, (Q, *_), K = _pred_sets_check("match_arctic", logits, heads, D)
+    _set_targets_check("match_arctic", dev, bs, labels, keypoints, offsets, t_max)
+    _is_valid_check("match_arctic", dev, bs, is_valid)
     sets = len(logits)
     out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
     _launch(dev, "msda_match_arctic_f32", "match_arctic", _ptr_array(logits), _ptr_array(hand) if heads else None,
@@ -1534,7 +1578,9 @@ def match_arctic(logits, hand, obj, labels, keypoints, offsets, is_valid, t_max,
 
 def match_assembly(logits, pred_keypoints, labels, keypoints, offsets, t_max, cost_class, cost_keypoint, cost_debug=None):
     """The int64 result buffer of msda_match_assembly_f32: as match_arctic with one keypoint head per set and no is_valid."""
-    dev, (bs, Q, K), D = _match_checks("match_assembly", logits, (pred_keypoints,), labels, keypoints, offsets, t_max)
+    D = keypoints.shape[1]
+    dev, bs, (Q, *_), K = _pred_sets_check("match_assembly", logits, (pred_keypoints,), D)
+    _set_targets_check("match_assembly", dev, bs, labels, keypoints, offsets, t_max)
     sets = len(logits)
     out = _match_out(dev, sets, bs, t_max, Q, cost_debug)
     _launch(dev, "msda_match_assembly_f32", "match_assembly", _ptr_array(logits), _ptr_array(pred_keypoints), sets, bs, Q, K,
@@ -1550,10 +1596,11 @@ def lsap(cost):
         raise RuntimeError("lsap: expected a contiguous fp32 CUDA cost [B, Q, T]")
     B, Q, T = cost.shape
     W = min(Q, T)
-    out = torch.empty(2 * B * W + 2 * B, dtype=torch.int64, device=cost.device)
+    numel, slices = match_layout(B, 1, W)                 # B one-frame sets, without the trailing valid-frame count
+    out = torch.empty(numel - 1, dtype=torch.int64, device=cost.device)
     _launch(cost.device, "msda_lsap_f32", "lsap", cost.data_ptr(), B, Q, T, out.data_ptr())
-    return (out[:B * W].view(B, W), out[B * W:2 * B * W].view(B, W), out[2 * B * W:2 * B * W + B],
-            out[2 * B * W + B:])
+    qi, ti, count, status = (out[sl] for sl in slices[:4])
+    return qi.view(B, W), ti.view(B, W), count, status
 
 
 # ---- the set criteria's matched losses (csrc/msda_criterion.hip) ---------------------------------------------------------
@@ -1564,40 +1611,61 @@ CRIT_BAD_LABEL, CRIT_BAD_TARGETS, CRIT_MASK_MISMATCH, CRIT_MATCH_STATUS = 1, 2, 
 
 def _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
                  num_boxes, focal_alpha):
-    """Checks shared by criterion_fwd / criterion_bwd; returns the C arguments in order and (dev, sets, bs, Q, K, D)."""
+    """Checks shared by criterion_fwd / criterion_bwd; returns the C arguments in order and (dev, bs, Q, K, D)."""
     arctic = kind == CRIT_ARCTIC
     heads = ((hand, obj) if arctic else (hand,)) if keypoints is not None else ()
-    dev, (bs, Q, K), D = _match_checks("criterion", logits, heads, labels, keypoints, offsets, t_max)
+    D = keypoints.shape[1] if keypoints is not None else 0
+    dev, bs, (Q, *_), K = _pred_sets_check("criterion", logits, heads, D)
+    _set_targets_check("criterion", dev, bs, labels, keypoints, offsets, t_max)
     sets = len(logits)
-    if not (match.is_cuda and match.dtype == torch.int64 and match.is_contiguous() and match.device == dev
-            and match.numel() == 2 * sets * bs * t_max + 2 * sets * bs + 1):
-        raise RuntimeError("criterion: expected the matcher's int64 CUDA result for %d sets" % sets)
-    if arctic and not (is_valid is not None and is_valid.is_cuda and is_valid.dtype == torch.int32
-                       and tuple(is_valid.shape) == (bs,) and is_valid.is_contiguous() and is_valid.device == dev):
-        raise RuntimeError("criterion: expected int32 CUDA is_valid [bs]")
+    _match_buffer_check("criterion", dev, match, sets, bs, t_max)
+    if arctic:
+        _is_valid_check("criterion", dev, bs, is_valid)
     jv_needed = not arctic and keypoints is not None
     if jv_needed and not (joint_valid is not None and joint_valid.is_cuda and joint_valid.dtype == torch.uint8
                           and joint_valid.is_contiguous() and tuple(joint_valid.shape) == (labels.shape[0], D)
                           and joint_valid.device == dev):
         raise RuntimeError("criterion: expected uint8 CUDA joint_valid [n, %d]" % D)
-    if not (_f32_cuda(num_boxes) and num_boxes.numel() == 1 and num_boxes.device == dev):
-        raise RuntimeError("criterion: expected an fp32 CUDA num_boxes scalar")
+    _num_boxes_check("criterion", dev, num_boxes)
     args = [kind, _ptr_array(logits), _ptr_array(hand) if heads else None, _ptr_array(obj) if heads and arctic else None,
             sets, bs, Q, K, D, match.data_ptr(), int(t_max), labels.data_ptr(),
             keypoints.data_ptr() if keypoints is not None else None, offsets.data_ptr(), labels.shape[0],
             is_valid.data_ptr() if arctic else None, joint_valid.data_ptr() if jv_needed else None, int(hand_mask),
             num_boxes.data_ptr(), float(focal_alpha)]
-    return args, (dev, sets, bs, Q, K, D)
+    return args, (dev, bs, Q, K, D)
+
+
+def _set_grads(what, dev, bs, queries, K, D, want_obj, grad_losses, stats, out=None):
+    """Checks a backward entry's ``grad_losses`` and ``stats``; returns the (grad_logits, grad_hand, grad_obj) lists shaped
+    as the predictions (``out``'s when given) and the entry's trailing C arguments."""
+    sets = len(queries)
+    if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
+            and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
+        raise RuntimeError("%s: expected fp32 grad_losses and int32 stats [%d, 4]" % (what, sets))
+    n_hand, n_obj = (sets if D else 0), (sets if D and want_obj else 0)
+    want = [(bs, q, K) for q in queries] + [(bs, q, D) for q in queries[:n_hand]] + [(bs, q, D) for q in queries[:n_obj]]
+    if out is not None:
+        g_logits, g_hand, g_obj = (list(g) for g in out)
+        if not (len(g_logits) == sets and len(g_hand) == n_hand and len(g_obj) == n_obj
+                and all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == w
+                        for t, w in zip(g_logits + g_hand + g_obj, want))):
+            raise RuntimeError("%s: out must hold contiguous fp32 CUDA tensors shaped as the predictions" % what)
+    else:
+        flat = [torch.empty(w, dtype=torch.float32, device=dev) for w in want]
+        g_logits, g_hand, g_obj = flat[:sets], flat[sets:sets + n_hand], flat[sets + n_hand:]
+    args = [grad_losses.data_ptr(), stats.data_ptr(), _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None,
+            _ptr_array(g_obj) if g_obj else None]
+    return (g_logits, g_hand, g_obj), args
 
 
 def criterion_fwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
                   num_boxes, focal_alpha):
     """(losses fp32 [sets, 4], stats int32 [sets, 4]) — msda_criterion_fwd_f32 (include/msda.h).  One launch, no host
     synchronisation."""
-    args, (dev, sets, *_rest) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
-                                            joint_valid, hand_mask, num_boxes, focal_alpha)
-    losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
-    stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
+    args, (dev, *_rest) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
+                                       joint_valid, hand_mask, num_boxes, focal_alpha)
+    losses = torch.empty(len(logits), CRIT_TERMS, dtype=torch.float32, device=dev)
+    stats = torch.empty(len(logits), 4, dtype=torch.int32, device=dev)
     _launch(dev, "msda_criterion_fwd_f32", "criterion_fwd", *args, losses.data_ptr(), stats.data_ptr())
     return losses, stats
 
@@ -1605,17 +1673,11 @@ def criterion_fwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offs
 def criterion_bwd(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid, joint_valid, hand_mask,
                   num_boxes, focal_alpha, grad_losses, stats):
     """(grad_logits, grad_hand, grad_obj) lists, every element written — msda_criterion_bwd_f32.  One launch."""
-    args, (dev, sets, bs, Q, K, D) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
-                                                  joint_valid, hand_mask, num_boxes, focal_alpha)
-    if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
-            and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
-        raise RuntimeError("criterion_bwd: expected fp32 grad_losses and int32 stats [%d, 4]" % sets)
-    g_logits = [torch.empty(bs, Q, K, dtype=torch.float32, device=dev) for _ in range(sets)]
-    g_hand = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D else []
-    g_obj = [torch.empty(bs, Q, D, dtype=torch.float32, device=dev) for _ in range(sets)] if D and kind == CRIT_ARCTIC else []
-    _launch(dev, "msda_criterion_bwd_f32", "criterion_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
-            _ptr_array(g_logits), _ptr_array(g_hand) if g_hand else None, _ptr_array(g_obj) if g_obj else None)
-    return g_logits, g_hand, g_obj
+    args, (dev, bs, Q, K, D) = _crit_common(kind, logits, hand, obj, match, t_max, labels, keypoints, offsets, is_valid,
+                                            joint_valid, hand_mask, num_boxes, focal_alpha)
+    grads, g_args = _set_grads("criterion_bwd", dev, bs, [Q] * len(logits), K, D, kind == CRIT_ARCTIC, grad_losses, stats)
+    _launch(dev, "msda_criterion_bwd_f32", "criterion_bwd", *args, *g_args)
+    return grads
 
 
 # ---- the DINO criterion's matched and denoising losses (csrc/msda_criterion_dino.hip) -----------------------------------
@@ -1630,38 +1692,17 @@ def criterion_dino_workspace_bytes(bs, queries):
 def _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels, keypoints, offsets, is_valid,
                       hand_mask, num_boxes, focal_alpha, single_pad, groups):
     """Checks shared by criterion_dino_fwd / criterion_dino_bwd; returns the C arguments in order, the tensors' device and
-    (bs, K, D).  ``match_set[s]``: the set's index in the matcher's result ``match`` (of ``match_sets`` sets), -1 for a
-    denoising set."""
-    sets, dev = len(logits), logits[0].device
-    has_kp = keypoints is not None
+    (bs, K, D) and the sets' query counts.  ``match_set[s]``: the set's index in the matcher's result ``match`` (of
+    ``match_sets`` sets), -1 for a denoising set."""
+    sets, has_kp = len(logits), keypoints is not None
     D = keypoints.shape[1] if has_kp else 0
-    if not (0 < sets <= MATCH_MAX_SETS and len(match_set) == sets and (not has_kp or len(hand) == len(obj) == sets)):
-        raise RuntimeError("criterion_dino: 1 to %d prediction sets, one match_set entry each" % MATCH_MAX_SETS)
-    bs, _, K = logits[0].shape
-    for s, t in enumerate(logits):
-        if not (_f32_cuda(t) and t.device == dev and t.dim() == 3 and t.shape[0] == bs and t.shape[2] == K):
-            raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA pred_logits [bs, Q_s, K] in every set")
-        for h in ((hand[s], obj[s]) if has_kp else ()):
-            if not (_f32_cuda(h) and h.device == dev and tuple(h.shape) == (bs, t.shape[1], D)):
-                raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA keypoint heads [bs, Q_s, %d]" % D)
-    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 1
-            and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous()
-            and tuple(offsets.shape) == (bs + 1,) and labels.device == dev and offsets.device == dev):
-        raise RuntimeError("criterion_dino: expected int64 CUDA labels [n] and offsets [bs + 1]")
-    if has_kp and not (_f32_cuda(keypoints) and keypoints.dim() == 2 and keypoints.device == dev
-                       and keypoints.shape[0] == labels.shape[0]):
-        raise RuntimeError("criterion_dino: expected contiguous fp32 CUDA target keypoints [n, D]")
-    if any(m >= 0 for m in match_set) and not (
-            match is not None and match.is_cuda and match.dtype == torch.int64 and match.is_contiguous()
-            and match.device == dev and 0 <= int(t_max) <= MATCH_MAX_TARGETS
-            and match.numel() == 2 * match_sets * bs * t_max + 2 * match_sets * bs + 1):
-        raise RuntimeError("criterion_dino: expected the matcher's int64 CUDA result for %d sets" % match_sets)
-    if not (is_valid is not None and is_valid.is_cuda and is_valid.dtype == torch.int32 and tuple(is_valid.shape) == (bs,)
-            and is_valid.is_contiguous() and is_valid.device == dev):
-        raise RuntimeError("criterion_dino: expected int32 CUDA is_valid [bs]")
-    if not (_f32_cuda(num_boxes) and num_boxes.numel() == 1 and num_boxes.device == dev):
-        raise RuntimeError("criterion_dino: expected an fp32 CUDA num_boxes scalar")
-    queries = [t.shape[1] for t in logits]
+    dev, bs, queries, K = _pred_sets_check("criterion_dino", logits, (hand, obj) if has_kp else (), D, per_set_q=True,
+                                           sets_ok=len(match_set) == sets)
+    _set_targets_check("criterion_dino", dev, bs, labels, keypoints, offsets)
+    if any(m >= 0 for m in match_set):
+        _match_buffer_check("criterion_dino", dev, match, match_sets, bs, t_max)
+    _is_valid_check("criterion_dino", dev, bs, is_valid)
+    _num_boxes_check("criterion_dino", dev, num_boxes)
     ints = ctypes.c_int * sets
     args = [_ptr_array(logits), _ptr_array(hand) if has_kp else None, _ptr_array(obj) if has_kp else None, ints(*queries),
             ints(*[int(m) for m in match_set]), sets, bs, K, D, int(single_pad), int(groups),
@@ -1678,11 +1719,10 @@ def criterion_dino_fwd(logits, hand, obj, match_set, match, match_sets, t_max, l
     args, dev, (bs, _K, _D), queries = _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels,
                                                          keypoints, offsets, is_valid, hand_mask, num_boxes, focal_alpha,
                                                          single_pad, groups)
-    sets = len(logits)
     nbytes = criterion_dino_workspace_bytes(bs, queries)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    losses = torch.empty(sets, CRIT_TERMS, dtype=torch.float32, device=dev)
-    stats = torch.empty(sets, 4, dtype=torch.int32, device=dev)
+    losses = torch.empty(len(logits), CRIT_TERMS, dtype=torch.float32, device=dev)
+    stats = torch.empty(len(logits), 4, dtype=torch.int32, device=dev)
     _launch(dev, "msda_criterion_dino_fwd_f32", "criterion_dino_fwd", *args, ws.data_ptr(), nbytes, losses.data_ptr(),
             stats.data_ptr())
     return losses, stats
@@ -1695,24 +1735,9 @@ def criterion_dino_bwd(logits, hand, obj, match_set, match, match_sets, t_max, l
     args, dev, (bs, K, D), queries = _crit_dino_common(logits, hand, obj, match_set, match, match_sets, t_max, labels,
                                                        keypoints, offsets, is_valid, hand_mask, num_boxes, focal_alpha,
                                                        single_pad, groups)
-    sets = len(logits)
-    if not (_f32_cuda(grad_losses) and tuple(grad_losses.shape) == (sets, CRIT_TERMS) and grad_losses.device == dev
-            and stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (sets, 4) and stats.is_contiguous()):
-        raise RuntimeError("criterion_dino_bwd: expected fp32 grad_losses and int32 stats [%d, 4]" % sets)
-    if out is not None:
-        g_logits, g_hand, g_obj = out
-        want = [(bs, q, K) for q in queries] + [(bs, q, D) for q in queries] * (2 if D else 0)
-        if not (len(g_hand) == len(g_obj) == (sets if D else 0) and len(g_logits) == sets
-                and all(_f32_cuda(t) and t.device == dev and tuple(t.shape) == w
-                        for t, w in zip(list(g_logits) + list(g_hand) + list(g_obj), want))):
-            raise RuntimeError("criterion_dino_bwd: out must hold contiguous fp32 CUDA tensors shaped as the predictions")
-    else:
-        g_logits = [torch.empty(bs, q, K, dtype=torch.float32, device=dev) for q in queries]
-        g_hand = [torch.empty(bs, q, D, dtype=torch.float32, device=dev) for q in queries] if D else []
-        g_obj = [torch.empty(bs, q, D, dtype=torch.float32, device=dev) for q in queries] if D else []
-    _launch(dev, "msda_criterion_dino_bwd_f32", "criterion_dino_bwd", *args, grad_losses.data_ptr(), stats.data_ptr(),
-            _ptr_array(g_logits), _ptr_array(g_hand) if D else None, _ptr_array(g_obj) if D else None)
-    return g_logits, g_hand, g_obj
+    grads, g_args = _set_grads("criterion_dino_bwd", dev, bs, queries, K, D, True, grad_losses, stats, out)
+    _launch(dev, "msda_criterion_dino_bwd_f32", "criterion_dino_bwd", *args, *g_args)
+    return grads
 
 
 # ---- the layers' FFN under bf16 autocast (csrc/msda_ffn_bf16.hip) ------------------------------------------------------------

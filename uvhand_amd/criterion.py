@@ -38,6 +38,7 @@ The package's torch restatement of the reference's maths (``arctic_set_losses`` 
 indices) runs instead for CPU tensors, non-fp32 predictions (bf16 autocast heads), anything over the matcher's limits
 (Q > 1024, more than 16 targets in a frame, more than 16 sets) and with ``MSDA_CRITERION_FUSED=0`` (A/B knob)."""
 import copy
+import functools
 import os
 from typing import NamedTuple
 
@@ -87,29 +88,28 @@ def _hand_mask(labels):
     return mask
 
 
-class _SetLossFunction(torch.autograd.Function):
+def _split_preds(sets, preds):
+    """(logits, hand, obj) lists of a node's flat ``preds`` (the sets' logits, then each keypoint head's; None: no such head)."""
+    heads = [list(preds[i:i + sets]) for i in range(0, len(preds), sets)] + [None, None]
+    return heads[0], heads[1], heads[2]
+
+
+class _SetLossNode(torch.autograd.Function):
+    """One criterion's losses as an autograd node over ``fwd`` / ``bwd``, its pair of ``_native`` functions: both take
+    (logits, hand, obj, *args), ``bwd`` the losses' gradient and the forward's stats after them."""
+
     @staticmethod
-    def forward(ctx, meta, *preds):
-        n = meta["sets"]
-        logits, heads = list(preds[:n]), [list(preds[n * (i + 1):n * (i + 2)]) for i in range(len(preds) // n - 1)]
-        hand = heads[0] if heads else None
-        obj = heads[1] if len(heads) > 1 else None
-        losses, stats = MSDA.criterion_fwd(meta["kind"], logits, hand, obj, *meta["args"])
-        ctx.meta, ctx.stats = meta, stats
+    def forward(ctx, fwd, bwd, sets, args, *preds):
+        losses, stats = fwd(*_split_preds(sets, preds), *args)
+        ctx.bwd, ctx.sets, ctx.args, ctx.stats = bwd, sets, args, stats
         ctx.save_for_backward(*preds)
         ctx.mark_non_differentiable(stats)
         return losses, stats
 
     @staticmethod
     def backward(ctx, grad_losses, _grad_stats):
-        meta, n = ctx.meta, ctx.meta["sets"]
-        preds = ctx.saved_tensors
-        logits, heads = list(preds[:n]), [list(preds[n * (i + 1):n * (i + 2)]) for i in range(len(preds) // n - 1)]
-        hand = heads[0] if heads else None
-        obj = heads[1] if len(heads) > 1 else None
-        g_logits, g_hand, g_obj = MSDA.criterion_bwd(meta["kind"], logits, hand, obj, *meta["args"],
-                                                     grad_losses.contiguous(), ctx.stats)
-        return (None, *g_logits, *g_hand, *g_obj)
+        grads = ctx.bwd(*_split_preds(ctx.sets, ctx.saved_tensors), *ctx.args, grad_losses.contiguous(), ctx.stats)
+        return (None, None, None, None, *grads[0], *grads[1], *grads[2])
 
 
 def _num_boxes_tensor(num_boxes, device):
@@ -139,12 +139,12 @@ def set_losses(outputs_list, packed, result, num_boxes, kind=None, focal_alpha=0
         preds += [o["pred_keypoints"].contiguous() for o in outputs_list]
         if joint_valid is None:
             raise ValueError("set_losses: AssemblyHands needs joint_valid (pack_joint_valid)")
-    meta = {"sets": len(logits), "kind": MSDA.CRIT_ARCTIC if arctic else MSDA.CRIT_ASSEMBLY,
-            "args": (result.buffer, packed.t_max, packed.labels, packed.keypoints, packed.offsets,
-                     packed.is_valid if arctic else None, joint_valid if not arctic else None,
-                     _hand_mask(ARCTIC_HANDS if arctic else hand_idx), _num_boxes_tensor(num_boxes, dev),
-                     float(focal_alpha))}
-    losses, stats = _SetLossFunction.apply(meta, *preds)
+    kind = MSDA.CRIT_ARCTIC if arctic else MSDA.CRIT_ASSEMBLY
+    args = (result.buffer, packed.t_max, packed.labels, packed.keypoints, packed.offsets,
+            packed.is_valid if arctic else None, joint_valid if not arctic else None,
+            _hand_mask(ARCTIC_HANDS if arctic else hand_idx), _num_boxes_tensor(num_boxes, dev), float(focal_alpha))
+    losses, stats = _SetLossNode.apply(functools.partial(MSDA.criterion_fwd, kind), functools.partial(MSDA.criterion_bwd, kind),
+                                       len(logits), args, *preds)
     return SetLosses(losses, ARCTIC_TERMS if arctic else ASSEMBLY_TERMS, stats[:, 0], stats)
 
 
@@ -485,30 +485,6 @@ DINO_ZERO_DN_KEYS = ("loss_bbox_dn", "loss_giou_dn", "loss_ce_dn", "loss_xy_dn",
 _PRED_KEYS = ("pred_logits", "pred_hand_key", "pred_obj_key")
 
 
-class _DinoSetLossFunction(torch.autograd.Function):
-    @staticmethod
-    def _split(meta, preds):
-        n = meta["sets"]
-        has_kp = len(preds) > n
-        return list(preds[:n]), list(preds[n:2 * n]) if has_kp else None, list(preds[2 * n:3 * n]) if has_kp else None
-
-    @staticmethod
-    def forward(ctx, meta, *preds):
-        logits, hand, obj = _DinoSetLossFunction._split(meta, preds)
-        losses, stats = MSDA.criterion_dino_fwd(logits, hand, obj, *meta["args"])
-        ctx.meta, ctx.stats = meta, stats
-        ctx.save_for_backward(*preds)
-        ctx.mark_non_differentiable(stats)
-        return losses, stats
-
-    @staticmethod
-    def backward(ctx, grad_losses, _grad_stats):
-        logits, hand, obj = _DinoSetLossFunction._split(ctx.meta, ctx.saved_tensors)
-        g_logits, g_hand, g_obj = MSDA.criterion_dino_bwd(logits, hand, obj, *ctx.meta["args"], grad_losses.contiguous(),
-                                                          ctx.stats)
-        return (None, *g_logits, *g_hand, *g_obj)
-
-
 def dino_set_losses(outputs_list, packed, result, num_boxes, dn_outputs_list=(), single_pad=0, groups=0, focal_alpha=0.25):
     """DINO's matched losses of every prediction dict of ``outputs_list`` (the sets ``match`` was given, same order) followed
     by the denoising losses of every dict of ``dn_outputs_list`` ([bs, groups * single_pad, .] predictions, paired with the
@@ -532,12 +508,10 @@ def dino_set_losses(outputs_list, packed, result, num_boxes, dn_outputs_list=(),
     match_sets = int(result.count.shape[0]) if result is not None else 0
     if len(matched) > match_sets:
         raise ValueError("dino_set_losses: %d matched sets, the match result has %d" % (len(matched), match_sets))
-    meta = {"sets": len(logits),
-            "args": ([*range(len(matched))] + [-1] * len(dn), result.buffer if result is not None else None, match_sets,
-                     packed.t_max, packed.labels, packed.keypoints, packed.offsets, packed.is_valid,
-                     _hand_mask(ARCTIC_HANDS), _num_boxes_tensor(num_boxes, logits[0].device), float(focal_alpha),
-                     int(single_pad), int(groups))}
-    losses, stats = _DinoSetLossFunction.apply(meta, *preds)
+    args = ([*range(len(matched))] + [-1] * len(dn), result.buffer if result is not None else None, match_sets,
+            packed.t_max, packed.labels, packed.keypoints, packed.offsets, packed.is_valid, _hand_mask(ARCTIC_HANDS),
+            _num_boxes_tensor(num_boxes, logits[0].device), float(focal_alpha), int(single_pad), int(groups))
+    losses, stats = _SetLossNode.apply(MSDA.criterion_dino_fwd, MSDA.criterion_dino_bwd, len(logits), args, *preds)
     return SetLosses(losses, ARCTIC_TERMS, stats[:, 0], stats)
 
 

@@ -1,5 +1,6 @@
 // C ABI of libmsda_hip.so (declared in include/msda.h): argument validation, kernel-family
 // selection, error reporting.  No torch types, no allocation, no device synchronisation.
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
@@ -1058,28 +1059,82 @@ int msda_assembly_select_f32(const float *cls, const float *hand, const float *o
                                         (hipStream_t)stream);
 }
 
+/* ---- what the Hungarian matchers and the set criteria share: refusals and the binding of the prediction sets ---- */
+// `who`: an entry's name, or the prefix ("msda_match", ...) of a message that a family's entries share.  The entries differ
+// in what they check between the shared conditions, so each condition is a function that an entry calls in its own place.
+static int refuse_set(const char *who, const char *fmt, ...)
+{
+    char buf[256];
+    const int n = std::snprintf(buf, sizeof(buf), "%s: ", who);
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf + n, sizeof(buf) - n, fmt, ap);
+    va_end(ap);
+    return msda::set_error(MSDA_ERR_ARGUMENT, buf);
+}
+
+static int check_set_range(const char *who, int sets, int bs, int bs_min)
+{
+    if (sets < 1 || sets > msda::kMatchMaxSets || bs < bs_min || bs > msda::kMatchMaxQueries)
+        return refuse_set(who, "need 1 <= sets <= %d and %d <= bs <= %d", msda::kMatchMaxSets, bs_min, msda::kMatchMaxQueries);
+    return MSDA_OK;
+}
+
+// D >= 1 (and <= d_max when that is not 0) exactly when there are target keypoints
+static int check_target_dim(const char *who, bool has_kp, int D, int d_max)
+{
+    if (has_kp ? (D < 1 || (d_max && D > d_max)) : D != 0) {
+        if (d_max) return refuse_set(who, "need 1 <= D <= %d with target keypoints, D = 0 without", d_max);
+        return refuse_set(who, "need D >= 1 with target keypoints, D = 0 without");
+    }
+    return MSDA_OK;
+}
+
+// the 2^31-element bounds: the targets' tensors, and one set's largest prediction tensor
+static bool targets_beyond_2g(long long n_targets, int D) { return n_targets < 0 || n_targets * (D > 1 ? D : 1) >= (1LL << 31); }
+static bool preds_beyond_2g(int bs, int Q, int K, int D) { return (long long)bs * Q * (K > D ? K : D) >= (1LL << 31); }
+static int refuse_beyond_2g(const char *family) { return refuse_set(family, "tensors beyond 2^31 elements"); }
+
+extern "C++" {   // templates over const float (predictions) and float (gradients)
+// Set s's pointers into `out`; false when one that is wanted is null.  An array that is not wanted is not read.
+template <class T>
+static bool bind_set(int s, T *const *logits, T *const *hand, T *const *obj, bool want_hand, bool want_obj,
+                     msda::PredSets<T> &out)
+{
+    out.logits[s] = logits[s];
+    out.hand[s] = want_hand ? hand[s] : nullptr;
+    out.obj[s] = want_obj ? obj[s] : nullptr;
+    return out.logits[s] != nullptr && (!want_hand || out.hand[s] != nullptr) && (!want_obj || out.obj[s] != nullptr);
+}
+
+// Every set's; `null_msg` is the family's whole message for a null array or a null pointer in one.
+template <class T>
+static int bind_sets(const char *null_msg, int sets, T *const *logits, T *const *hand, T *const *obj, bool want_hand,
+                     bool want_obj, msda::PredSets<T> &out)
+{
+    out = {};
+    if (logits == nullptr || (want_hand && hand == nullptr) || (want_obj && obj == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, null_msg);
+    for (int s = 0; s < sets; ++s)
+        if (!bind_set(s, logits, hand, obj, want_hand, want_obj, out)) return msda::set_error(MSDA_ERR_ARGUMENT, null_msg);
+    return MSDA_OK;
+}
+}   // extern "C++"
+
 /* ---- the Hungarian matchers (msda_matcher.hip) ---- */
+static const char kMatchNull[] = "msda_match: null device pointer";
 static int check_match(const char *who, int sets, int bs, int Q, int K, int D, bool has_kp, const int64_t *labels,
                        const int64_t *offsets, long long n_targets, int t_max, const int64_t *out)
 {
-    char buf[256];
-    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 0 || bs > msda::kMatchMaxQueries) {
-        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 0 <= bs <= %d", who, msda::kMatchMaxSets, msda::kMatchMaxQueries);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (Q < 1 || Q > msda::kMatchMaxQueries || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets) {
-        std::snprintf(buf, sizeof(buf), "%s: need 1 <= Q <= %d, K >= 1 and 0 <= t_max <= %d", who, msda::kMatchMaxQueries,
-                      msda::kMatchMaxTargets);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (has_kp ? (D < 1 || D > msda::kMatchMaxDim) : D != 0) {
-        std::snprintf(buf, sizeof(buf), "%s: need 1 <= D <= %d with target keypoints, D = 0 without", who, msda::kMatchMaxDim);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (n_targets < 0 || n_targets * (D > 1 ? D : 1) >= (1LL << 31) || (long long)bs * Q * (K > D ? K : D) >= (1LL << 31))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: tensors beyond 2^31 elements");
+    int rc = check_set_range(who, sets, bs, 0);
+    if (rc != MSDA_OK) return rc;
+    if (Q < 1 || Q > msda::kMatchMaxQueries || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets)
+        return refuse_set(who, "need 1 <= Q <= %d, K >= 1 and 0 <= t_max <= %d", msda::kMatchMaxQueries, msda::kMatchMaxTargets);
+    rc = check_target_dim(who, has_kp, D, msda::kMatchMaxDim);
+    if (rc != MSDA_OK) return rc;
+    if (targets_beyond_2g(n_targets, D) || preds_beyond_2g(bs, Q, K, D)) return refuse_beyond_2g("msda_match");
     if (bs > 0 && (offsets == nullptr || out == nullptr || (n_targets > 0 && labels == nullptr)))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
+        return msda::set_error(MSDA_ERR_ARGUMENT, kMatchNull);
     return MSDA_OK;
 }
 
@@ -1091,19 +1146,12 @@ int msda_match_arctic_f32(const float *const *pred_logits, const float *const *p
     const bool has_kp = keypoints != nullptr;
     int rc = check_match("msda_match_arctic_f32", sets, bs, Q, K, D, has_kp, labels, offsets, n_targets, t_max, out);
     if (rc != MSDA_OK) return rc;
-    if (bs > 0 && is_valid == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
-    if (pred_logits == nullptr || (has_kp && (pred_hand_key == nullptr || pred_obj_key == nullptr)))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
-    msda::MatchSets ms = {};
-    for (int s = 0; s < sets; ++s) {
-        if (pred_logits[s] == nullptr || (has_kp && (pred_hand_key[s] == nullptr || pred_obj_key[s] == nullptr)))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
-        ms.logits[s] = pred_logits[s];
-        ms.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
-        ms.obj[s] = has_kp ? pred_obj_key[s] : nullptr;
-    }
+    if (bs > 0 && is_valid == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kMatchNull);
+    msda::PredSets<const float> ms;
+    rc = bind_sets(kMatchNull, sets, pred_logits, pred_hand_key, pred_obj_key, has_kp, has_kp, ms);
+    if (rc != MSDA_OK) return rc;
     msda::begin_call();
-    return msda::launch_match(ms, sets, bs, Q, K, D, labels, keypoints, offsets, n_targets, is_valid, t_max, cost_class,
+    return msda::launch_match(ms, sets, bs, Q, K, D, {labels, keypoints, offsets, n_targets, is_valid, t_max}, cost_class,
                               cost_keypoint, out, cost_debug, (hipStream_t)stream);
 }
 
@@ -1114,17 +1162,12 @@ int msda_match_assembly_f32(const float *const *pred_logits, const float *const 
 {
     int rc = check_match("msda_match_assembly_f32", sets, bs, Q, K, D, true, labels, offsets, n_targets, t_max, out);
     if (rc != MSDA_OK) return rc;
-    if (pred_logits == nullptr || pred_keypoints == nullptr || (bs > 0 && n_targets > 0 && keypoints == nullptr))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
-    msda::MatchSets ms = {};
-    for (int s = 0; s < sets; ++s) {
-        if (pred_logits[s] == nullptr || pred_keypoints[s] == nullptr)
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_match: null device pointer");
-        ms.logits[s] = pred_logits[s];
-        ms.hand[s] = ms.obj[s] = pred_keypoints[s];
-    }
+    if (bs > 0 && n_targets > 0 && keypoints == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kMatchNull);
+    msda::PredSets<const float> ms;   // the one keypoint head is both the hand and the object head
+    rc = bind_sets(kMatchNull, sets, pred_logits, pred_keypoints, pred_keypoints, true, true, ms);
+    if (rc != MSDA_OK) return rc;
     msda::begin_call();
-    return msda::launch_match(ms, sets, bs, Q, K, D, labels, keypoints, offsets, n_targets, nullptr, t_max, cost_class,
+    return msda::launch_match(ms, sets, bs, Q, K, D, {labels, keypoints, offsets, n_targets, nullptr, t_max}, cost_class,
                               cost_keypoint, out, cost_debug, (hipStream_t)stream);
 }
 
@@ -1141,47 +1184,29 @@ int msda_lsap_f32(const float *cost, int B, int Q, int T, int64_t *out, msda_str
 }
 
 /* ---- the set criteria's matched losses (msda_criterion.hip) ---- */
+static const char kCritNull[] = "msda_criterion: null pointer";
 static int check_criterion(const char *who, int kind, const float *const *pred_logits, const float *const *pred_hand_key,
                            const float *const *pred_obj_key, int sets, int bs, int Q, int K, int D, const int64_t *match,
                            int t_max, const int64_t *labels, const float *keypoints, const int64_t *offsets,
                            long long n_targets, const int32_t *is_valid, const uint8_t *joint_valid,
-                           const float *num_boxes, msda::CritArgs &a, msda::CritSets &p)
+                           unsigned long long hand_mask, const float *num_boxes, float focal_alpha, msda::CritArgs &a,
+                           msda::PredSets<const float> &p)
 {
-    char buf[256];
-    if (kind != MSDA_CRITERION_ARCTIC && kind != MSDA_CRITERION_ASSEMBLY) {
-        std::snprintf(buf, sizeof(buf), "%s: kind must be 0 (ARCTIC) or 1 (AssemblyHands)", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 1 || bs > msda::kMatchMaxQueries) {
-        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 1 <= bs <= %d", who, msda::kMatchMaxSets,
-                      msda::kMatchMaxQueries);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (Q < 1 || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets || D < 0) {
-        std::snprintf(buf, sizeof(buf), "%s: need Q >= 1, K >= 1, D >= 0 and 0 <= t_max <= %d", who, msda::kMatchMaxTargets);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    const bool has_kp = keypoints != nullptr;
-    if (has_kp != (D > 0)) {
-        std::snprintf(buf, sizeof(buf), "%s: need D >= 1 with target keypoints, D = 0 without", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (n_targets < 0 || n_targets * (D > 1 ? D : 1) >= (1LL << 31) || (long long)bs * Q * (K > D ? K : D) >= (1LL << 31))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: tensors beyond 2^31 elements");
-    if (pred_logits == nullptr || match == nullptr || offsets == nullptr || num_boxes == nullptr
-        || (n_targets > 0 && labels == nullptr) || (kind == MSDA_CRITERION_ARCTIC && is_valid == nullptr)
-        || (has_kp && pred_hand_key == nullptr) || (has_kp && kind == MSDA_CRITERION_ARCTIC && pred_obj_key == nullptr)
-        || (has_kp && kind == MSDA_CRITERION_ASSEMBLY && joint_valid == nullptr))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
-    p = {};
-    for (int s = 0; s < sets; ++s) {
-        if (pred_logits[s] == nullptr || (has_kp && pred_hand_key[s] == nullptr)
-            || (has_kp && kind == MSDA_CRITERION_ARCTIC && pred_obj_key[s] == nullptr))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
-        p.logits[s] = pred_logits[s];
-        p.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
-        p.obj[s] = has_kp && kind == MSDA_CRITERION_ARCTIC ? pred_obj_key[s] : nullptr;
-    }
+    if (kind != MSDA_CRITERION_ARCTIC && kind != MSDA_CRITERION_ASSEMBLY)
+        return refuse_set(who, "kind must be 0 (ARCTIC) or 1 (AssemblyHands)");
+    int rc = check_set_range(who, sets, bs, 1);
+    if (rc != MSDA_OK) return rc;
+    if (Q < 1 || K < 1 || t_max < 0 || t_max > msda::kMatchMaxTargets || D < 0)
+        return refuse_set(who, "need Q >= 1, K >= 1, D >= 0 and 0 <= t_max <= %d", msda::kMatchMaxTargets);
+    const bool has_kp = keypoints != nullptr, arctic = kind == MSDA_CRITERION_ARCTIC;
+    rc = check_target_dim(who, has_kp, D, 0);
+    if (rc != MSDA_OK) return rc;
+    if (targets_beyond_2g(n_targets, D) || preds_beyond_2g(bs, Q, K, D)) return refuse_beyond_2g("msda_criterion");
+    if (match == nullptr || offsets == nullptr || num_boxes == nullptr || (n_targets > 0 && labels == nullptr)
+        || (arctic && is_valid == nullptr) || (has_kp && !arctic && joint_valid == nullptr))
+        return msda::set_error(MSDA_ERR_ARGUMENT, kCritNull);
+    rc = bind_sets(kCritNull, sets, pred_logits, pred_hand_key, pred_obj_key, has_kp, has_kp && arctic, p);
+    if (rc != MSDA_OK) return rc;
     a = {};
     a.kind = kind;
     a.sets = sets;
@@ -1189,15 +1214,12 @@ static int check_criterion(const char *who, int kind, const float *const *pred_l
     a.Q = Q;
     a.K = K;
     a.D = D;
-    a.t_max = t_max;
     a.match = match;
-    a.labels = labels;
-    a.tgt_kp = keypoints;
-    a.offsets = offsets;
-    a.n_targets = n_targets;
-    a.is_valid = kind == MSDA_CRITERION_ARCTIC ? is_valid : nullptr;
-    a.joint_valid = kind == MSDA_CRITERION_ASSEMBLY && has_kp ? joint_valid : nullptr;
+    a.tg = {labels, keypoints, offsets, n_targets, arctic ? is_valid : nullptr, t_max};
+    a.joint_valid = !arctic && has_kp ? joint_valid : nullptr;
+    a.hand_mask = hand_mask;
     a.num_boxes = num_boxes;
+    a.alpha = focal_alpha;
     return MSDA_OK;
 }
 
@@ -1209,13 +1231,12 @@ int msda_criterion_fwd_f32(int kind, const float *const *pred_logits, const floa
                            int32_t *stats, msda_stream_t stream)
 {
     msda::CritArgs a;
-    msda::CritSets p;
+    msda::PredSets<const float> p;
     int rc = check_criterion("msda_criterion_fwd_f32", kind, pred_logits, pred_hand_key, pred_obj_key, sets, bs, Q, K, D, match,
-                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, num_boxes, a, p);
+                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, hand_mask, num_boxes,
+                             focal_alpha, a, p);
     if (rc != MSDA_OK) return rc;
-    if (losses == nullptr || stats == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
-    a.hand_mask = hand_mask;
-    a.alpha = focal_alpha;
+    if (losses == nullptr || stats == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kCritNull);
     msda::begin_call();
     return msda::launch_criterion_fwd(a, p, losses, stats, (hipStream_t)stream);
 }
@@ -1229,86 +1250,57 @@ int msda_criterion_bwd_f32(int kind, const float *const *pred_logits, const floa
                            float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream)
 {
     msda::CritArgs a;
-    msda::CritSets p;
+    msda::PredSets<const float> p;
     int rc = check_criterion("msda_criterion_bwd_f32", kind, pred_logits, pred_hand_key, pred_obj_key, sets, bs, Q, K, D, match,
-                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, num_boxes, a, p);
+                             t_max, labels, keypoints, offsets, n_targets, is_valid, joint_valid, hand_mask, num_boxes,
+                             focal_alpha, a, p);
     if (rc != MSDA_OK) return rc;
-    const bool has_kp = keypoints != nullptr;
-    if (grad_losses == nullptr || stats == nullptr || grad_logits == nullptr || (has_kp && grad_hand_key == nullptr)
-        || (has_kp && kind == MSDA_CRITERION_ARCTIC && grad_obj_key == nullptr))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
-    msda::CritGrads g = {};
-    for (int s = 0; s < sets; ++s) {
-        if (grad_logits[s] == nullptr || (has_kp && grad_hand_key[s] == nullptr)
-            || (has_kp && kind == MSDA_CRITERION_ARCTIC && grad_obj_key[s] == nullptr))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion: null pointer");
-        g.logits[s] = grad_logits[s];
-        g.hand[s] = has_kp ? grad_hand_key[s] : nullptr;
-        g.obj[s] = has_kp && kind == MSDA_CRITERION_ARCTIC ? grad_obj_key[s] : nullptr;
-    }
-    a.hand_mask = hand_mask;
-    a.alpha = focal_alpha;
+    if (grad_losses == nullptr || stats == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kCritNull);
+    const bool has_kp = keypoints != nullptr, arctic = kind == MSDA_CRITERION_ARCTIC;
+    msda::PredSets<float> g;
+    rc = bind_sets(kCritNull, sets, grad_logits, grad_hand_key, grad_obj_key, has_kp, has_kp && arctic, g);
+    if (rc != MSDA_OK) return rc;
     msda::begin_call();
     return msda::launch_criterion_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
 }
 
 /* ---- the DINO criterion's matched and denoising losses (msda_criterion_dino.hip) ---- */
+static const char kDinoCritNull[] = "msda_criterion_dino: null pointer";
 static int check_criterion_dino(const char *who, const float *const *pred_logits, const float *const *pred_hand_key,
                                 const float *const *pred_obj_key, const int *Q, const int *match_set, int sets, int bs, int K,
                                 int D, int single_pad, int groups, const int64_t *match, int match_sets, int t_max,
                                 const int64_t *labels, const float *keypoints, const int64_t *offsets, long long n_targets,
-                                const int32_t *is_valid, const float *num_boxes, msda::DinoCritArgs &a, msda::CritSets &p)
+                                const int32_t *is_valid, unsigned long long hand_mask, const float *num_boxes,
+                                float focal_alpha, msda::DinoCritArgs &a, msda::PredSets<const float> &p)
 {
-    char buf[256];
-    if (sets < 1 || sets > msda::kMatchMaxSets || bs < 1 || bs > msda::kMatchMaxQueries) {
-        std::snprintf(buf, sizeof(buf), "%s: need 1 <= sets <= %d and 1 <= bs <= %d", who, msda::kMatchMaxSets,
-                      msda::kMatchMaxQueries);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
-    if (K < 1 || D < 0 || n_targets < 0) {
-        std::snprintf(buf, sizeof(buf), "%s: need K >= 1, D >= 0 and n_targets >= 0", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
+    int rc = check_set_range(who, sets, bs, 1);
+    if (rc != MSDA_OK) return rc;
+    if (K < 1 || D < 0 || n_targets < 0) return refuse_set(who, "need K >= 1, D >= 0 and n_targets >= 0");
     const bool has_kp = keypoints != nullptr;
-    if (has_kp != (D > 0)) {
-        std::snprintf(buf, sizeof(buf), "%s: need D >= 1 with target keypoints, D = 0 without", who);
-        return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-    }
+    rc = check_target_dim(who, has_kp, D, 0);
+    if (rc != MSDA_OK) return rc;
     if (pred_logits == nullptr || Q == nullptr || match_set == nullptr || offsets == nullptr || num_boxes == nullptr
         || is_valid == nullptr || (n_targets > 0 && labels == nullptr)
         || (has_kp && (pred_hand_key == nullptr || pred_obj_key == nullptr)))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
-    if (n_targets * (D > 1 ? D : 1) >= (1LL << 31))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: tensors beyond 2^31 elements");
+        return msda::set_error(MSDA_ERR_ARGUMENT, kDinoCritNull);
+    if (targets_beyond_2g(n_targets, D)) return refuse_beyond_2g("msda_criterion_dino");
     p = {};
     a = {};
     long long chunks = 0;
-    for (int s = 0; s < sets; ++s) {
-        if (Q[s] < 1) {
-            std::snprintf(buf, sizeof(buf), "%s: need Q[s] >= 1 in every set", who);
-            return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-        }
+    for (int s = 0; s < sets; ++s) {   // a set's own conditions come before its pointers, so they bind one set at a time
+        if (Q[s] < 1) return refuse_set(who, "need Q[s] >= 1 in every set");
         if (match_set[s] < 0) {
-            if (groups < 1 || single_pad < 1 || (long long)groups * single_pad != Q[s]) {
-                std::snprintf(buf, sizeof(buf), "%s: a denoising set needs groups >= 1, single_pad >= 1 and Q[s] = groups * "
-                                                "single_pad", who);
-                return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-            }
+            if (groups < 1 || single_pad < 1 || (long long)groups * single_pad != Q[s])
+                return refuse_set(who, "a denoising set needs groups >= 1, single_pad >= 1 and Q[s] = groups * single_pad");
         } else {
-            if (match_set[s] >= match_sets || t_max < 0 || t_max > msda::kMatchMaxTargets) {
-                std::snprintf(buf, sizeof(buf), "%s: a matched set needs match_set[s] < match_sets and 0 <= t_max <= %d", who,
-                              msda::kMatchMaxTargets);
-                return msda::set_error(MSDA_ERR_ARGUMENT, buf);
-            }
+            if (match_set[s] >= match_sets || t_max < 0 || t_max > msda::kMatchMaxTargets)
+                return refuse_set(who, "a matched set needs match_set[s] < match_sets and 0 <= t_max <= %d",
+                                  msda::kMatchMaxTargets);
             if (match == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer (match)");
         }
-        if ((long long)bs * Q[s] * (K > D ? K : D) >= (1LL << 31))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: tensors beyond 2^31 elements");
-        if (pred_logits[s] == nullptr || (has_kp && (pred_hand_key[s] == nullptr || pred_obj_key[s] == nullptr)))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
-        p.logits[s] = pred_logits[s];
-        p.hand[s] = has_kp ? pred_hand_key[s] : nullptr;
-        p.obj[s] = has_kp ? pred_obj_key[s] : nullptr;
+        if (preds_beyond_2g(bs, Q[s], K, D)) return refuse_beyond_2g("msda_criterion_dino");
+        if (!bind_set(s, pred_logits, pred_hand_key, pred_obj_key, has_kp, has_kp, p))
+            return msda::set_error(MSDA_ERR_ARGUMENT, kDinoCritNull);
         a.Q[s] = Q[s];
         a.match_set[s] = match_set[s] < 0 ? -1 : match_set[s];
         a.chunk_base[s] = (int)chunks;
@@ -1318,17 +1310,14 @@ static int check_criterion_dino(const char *who, const float *const *pred_logits
     a.bs = bs;
     a.K = K;
     a.D = D;
-    a.t_max = t_max;
     a.match_sets = match_sets;
     a.single_pad = single_pad;
     a.groups = groups;
     a.match = match;
-    a.labels = labels;
-    a.tgt_kp = keypoints;
-    a.offsets = offsets;
-    a.n_targets = n_targets;
-    a.is_valid = is_valid;
+    a.tg = {labels, keypoints, offsets, n_targets, is_valid, t_max};
+    a.hand_mask = hand_mask;
     a.num_boxes = num_boxes;
+    a.alpha = focal_alpha;
     a.chunks = (int)chunks;
     return MSDA_OK;
 }
@@ -1342,18 +1331,15 @@ int msda_criterion_dino_fwd_f32(const float *const *pred_logits, const float *co
                                 int32_t *stats, msda_stream_t stream)
 {
     msda::DinoCritArgs a;
-    msda::CritSets p;
+    msda::PredSets<const float> p;
     int rc = check_criterion_dino("msda_criterion_dino_fwd_f32", pred_logits, pred_hand_key, pred_obj_key, Q, match_set, sets, bs,
                                   K, D, single_pad, groups, match, match_sets, t_max, labels, keypoints, offsets, n_targets,
-                                  is_valid, num_boxes, a, p);
+                                  is_valid, hand_mask, num_boxes, focal_alpha, a, p);
     if (rc != MSDA_OK) return rc;
-    if (losses == nullptr || stats == nullptr || workspace == nullptr)
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
+    if (losses == nullptr || stats == nullptr || workspace == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kDinoCritNull);
     if (((uintptr_t)workspace & 7u) != 0 || workspace_bytes < (unsigned long long)a.chunks * msda::kDinoCritPartialBytes)
         return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino_fwd_f32: the workspace needs 8-byte alignment and "
                                                   "MSDA_CRITERION_DINO_PARTIAL_BYTES per chunk");
-    a.hand_mask = hand_mask;
-    a.alpha = focal_alpha;
     msda::begin_call();
     return msda::launch_criterion_dino_fwd(a, p, workspace, losses, stats, (hipStream_t)stream);
 }
@@ -1367,25 +1353,16 @@ int msda_criterion_dino_bwd_f32(const float *const *pred_logits, const float *co
                                 float *const *grad_hand_key, float *const *grad_obj_key, msda_stream_t stream)
 {
     msda::DinoCritArgs a;
-    msda::CritSets p;
+    msda::PredSets<const float> p;
     int rc = check_criterion_dino("msda_criterion_dino_bwd_f32", pred_logits, pred_hand_key, pred_obj_key, Q, match_set, sets, bs,
                                   K, D, single_pad, groups, match, match_sets, t_max, labels, keypoints, offsets, n_targets,
-                                  is_valid, num_boxes, a, p);
+                                  is_valid, hand_mask, num_boxes, focal_alpha, a, p);
     if (rc != MSDA_OK) return rc;
+    if (grad_losses == nullptr || stats == nullptr) return msda::set_error(MSDA_ERR_ARGUMENT, kDinoCritNull);
     const bool has_kp = keypoints != nullptr;
-    if (grad_losses == nullptr || stats == nullptr || grad_logits == nullptr
-        || (has_kp && (grad_hand_key == nullptr || grad_obj_key == nullptr)))
-        return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
-    msda::CritGrads g = {};
-    for (int s = 0; s < sets; ++s) {
-        if (grad_logits[s] == nullptr || (has_kp && (grad_hand_key[s] == nullptr || grad_obj_key[s] == nullptr)))
-            return msda::set_error(MSDA_ERR_ARGUMENT, "msda_criterion_dino: null pointer");
-        g.logits[s] = grad_logits[s];
-        g.hand[s] = has_kp ? grad_hand_key[s] : nullptr;
-        g.obj[s] = has_kp ? grad_obj_key[s] : nullptr;
-    }
-    a.hand_mask = hand_mask;
-    a.alpha = focal_alpha;
+    msda::PredSets<float> g;
+    rc = bind_sets(kDinoCritNull, sets, grad_logits, grad_hand_key, grad_obj_key, has_kp, has_kp, g);
+    if (rc != MSDA_OK) return rc;
     msda::begin_call();
     return msda::launch_criterion_dino_bwd(a, p, g, grad_losses, stats, (hipStream_t)stream);
 }

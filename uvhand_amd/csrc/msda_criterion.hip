@@ -58,16 +58,17 @@ struct CrEntry {
 // Matched pair m of slot k of set s: 0 and the entry, or a status bit (no pair: -1).
 __device__ int cr_entry(const CritArgs &a, int s, int k, int m, const int *frame_of, CrEntry &e)
 {
-    const long long slots = (long long)a.sets * a.bs, slot = (long long)s * a.bs + k;
-    const long long cnt = a.match[2 * slots * a.t_max + slot];
+    const MatchView mv(a.sets, a.bs, a.tg.t_max);
+    const long long slot = (long long)s * a.bs + k;
+    const long long cnt = a.match[mv.count(slot)];
     if (m >= cnt) return -1;
-    const long long q = a.match[slot * a.t_max + m], j = a.match[slots * a.t_max + slot * a.t_max + m];
+    const long long q = a.match[mv.query(slot, m)], j = a.match[mv.target(slot, m)];
     const int f = frame_of[k];
     if (f < 0) return kCritBadTargets;
-    const long long lo = a.offsets[f], hi = a.offsets[f + 1];
-    if (lo < 0 || hi < lo || hi > a.n_targets || j < 0 || j >= hi - lo || m >= hi - lo || q < 0 || q >= a.Q)
+    long long lo, hi;
+    if (!cr_frame_targets(a.tg, f, lo, hi) || j < 0 || j >= hi - lo || m >= hi - lo || q < 0 || q >= a.Q)
         return kCritBadTargets;
-    const long long lab = a.labels[lo + j];
+    const long long lab = a.tg.labels[lo + j];
     if (lab < 0 || lab >= a.K) return kCritBadLabel;
     e.q = (int)q;
     e.row = lo + j;
@@ -76,50 +77,46 @@ __device__ int cr_entry(const CritArgs &a, int s, int k, int m, const int *frame
     return 0;
 }
 
-__device__ __forceinline__ bool cr_hand(const CritArgs &a, int label)
-{
-    return label < 64 && ((a.hand_mask >> label) & 1ull);
-}
-
 // The matched pair of row q of slot k, if any (pairs are in ascending query order).
 __device__ bool cr_row_entry(const CritArgs &a, int s, int k, int q, const int *frame_of, CrEntry &e)
 {
-    const long long slots = (long long)a.sets * a.bs, slot = (long long)s * a.bs + k;
-    const long long cnt = a.match[2 * slots * a.t_max + slot];
-    for (int m = 0; m < cnt && m < a.t_max; ++m) {
-        const long long qm = a.match[slot * a.t_max + m];
+    const MatchView mv(a.sets, a.bs, a.tg.t_max);
+    const long long slot = (long long)s * a.bs + k;
+    const long long cnt = a.match[mv.count(slot)];
+    for (int m = 0; m < cnt && m < mv.W; ++m) {
+        const long long qm = a.match[mv.query(slot, m)];
         if (qm == q) return cr_entry(a, s, k, m, frame_of, e) == 0;
         if (qm > q) break;
     }
     return false;
 }
 
-__global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a, CritSets p, float *__restrict__ losses,
-                                                                     int32_t *__restrict__ stats)
+__global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a, PredSets<const float> p,
+                                                                     float *__restrict__ losses, int32_t *__restrict__ stats)
 {
     __shared__ CrShared sh;
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int bs = a.bs, Q = a.Q, K = a.K, D = a.D, W = a.t_max;
+    const int bs = a.bs, Q = a.Q, K = a.K, D = a.D, W = a.tg.t_max;
     const bool assembly = a.kind == kCritAssembly;
-    cr_slot_frames(a.is_valid, bs, sh.frame_of, sh.wcnt);
+    cr_slot_frames(a.tg.is_valid, bs, sh.frame_of, sh.wcnt);
     for (int k = tid; k < bs; k += nt) sh.card[k] = 0;
     if (tid < 7) sh.ints[tid] = 0;
     __syncthreads();
 
     int status = 0, n_hand = 0, n_obj = 0, n_matched = 0, correct = 0, valid_targets = 0;
     // per slot: matcher status, AssemblyHands' fully matched frames, ARCTIC's valid targets
-    const long long slots = (long long)a.sets * bs;
+    const MatchView mv(a.sets, bs, W);
     for (int k = tid; k < bs; k += nt) {
         const long long slot = (long long)s * bs + k;
-        if (a.match[2 * slots * W + slots + slot] != 0) status |= kCritMatchStatus;
+        if (a.match[mv.status(slot)] != 0) status |= kCritMatchStatus;
         const int f = sh.frame_of[k];
         if (f >= 0) {
-            const long long lo = a.offsets[f], hi = a.offsets[f + 1];
-            if (lo < 0 || hi < lo || hi > a.n_targets) {
+            long long lo, hi;
+            if (!cr_frame_targets(a.tg, f, lo, hi)) {
                 status |= kCritBadTargets;
             } else {
                 valid_targets += (int)(hi - lo > 0);
-                if (assembly && a.match[2 * slots * W + slot] != hi - lo) status |= kCritMaskMismatch;
+                if (assembly && a.match[mv.count(slot)] != hi - lo) status |= kCritMaskMismatch;
             }
         }
     }
@@ -129,7 +126,7 @@ __global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a
         const int rc = cr_entry(a, s, e / W, e % W, sh.frame_of, en);
         if (rc > 0) status |= rc;
         if (rc != 0) continue;
-        const bool hand = cr_hand(a, en.label);
+        const bool hand = cr_hand(a.hand_mask, en.label);
         n_hand += hand;
         n_obj += !hand;
         if (assembly && !hand) status |= kCritMaskMismatch;
@@ -138,16 +135,16 @@ __global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a
     }
     // keypoint L1 sums over the matched rows
     double hsum = 0.0, osum = 0.0, csum = 0.0;
-    if (a.tgt_kp) {
+    if (a.tg.tgt_kp) {
         for (long long i = tid; i < (long long)bs * W * D; i += nt) {
             const int e = (int)(i / D), d = (int)(i % D), k = e / W;
             CrEntry en;
             if (cr_entry(a, s, k, e % W, sh.frame_of, en) != 0) continue;
-            const bool hand = cr_hand(a, en.label);
+            const bool hand = cr_hand(a.hand_mask, en.label);
             const long long src = ((long long)k * Q + en.q) * D + d;
-            const float t = a.tgt_kp[en.row * D + d];
+            const float t = a.tg.tgt_kp[en.row * D + d];
             if (assembly) {
-                const long long jrow = a.offsets[k] + en.m;   // the frame's en.m-th joint_valid row
+                const long long jrow = a.tg.offsets[k] + en.m;   // the frame's en.m-th joint_valid row
                 if (hand && a.joint_valid[jrow * D + d]) hsum += (double)fabsf(p.hand[s][src] - t);
             } else if (hand) {
                 hsum += (double)fabsf(p.hand[s][src] - t);
@@ -177,7 +174,7 @@ __global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a
     __syncthreads();
     int card_err = 0;
     for (int f = tid; f < bs; f += nt) {
-        const long long n = a.offsets[f + 1] - a.offsets[f];
+        const long long n = a.tg.offsets[f + 1] - a.tg.offsets[f];
         const long long d = sh.card[f] - n;
         card_err += (int)(d < 0 ? -d : d);
     }
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(kCrFwdThreads) void criterion_fwd_kernel(CritArgs a
     }
 }
 
-__global__ __launch_bounds__(kCrBwdRows) void criterion_bwd_kernel(CritArgs a, CritSets p, CritGrads g,
+__global__ __launch_bounds__(kCrBwdRows) void criterion_bwd_kernel(CritArgs a, PredSets<const float> p, PredSets<float> g,
                                                                    const float *__restrict__ grad_losses,
                                                                    const int32_t *__restrict__ stats)
 {
@@ -240,7 +237,7 @@ __global__ __launch_bounds__(kCrBwdRows) void criterion_bwd_kernel(CritArgs a, C
     const bool assembly = a.kind == kCritAssembly;
     const long long rows = (long long)bs * Q, r0 = (long long)blockIdx.x * kCrBwdRows;
     const int nr = (int)(rows - r0 < kCrBwdRows ? rows - r0 : kCrBwdRows);
-    cr_slot_frames(a.is_valid, bs, frame_of, wcnt);
+    cr_slot_frames(a.tg.is_valid, bs, frame_of, wcnt);
     __syncthreads();
 
     const int32_t *st = stats + (long long)s * kCritStats;
@@ -282,15 +279,15 @@ __global__ __launch_bounds__(kCrBwdRows) void criterion_bwd_kernel(CritArgs a, C
         const int rl = i / D, d = i % D;
         const long long tr = trow[rl];
         float vh = 0.f, vo = 0.f;
-        if (tr >= 0 && a.tgt_kp) {
-            const float t = a.tgt_kp[tr * D + d];
-            const bool hand = cr_hand(a, lab[rl]);
+        if (tr >= 0 && a.tg.tgt_kp) {
+            const float t = a.tg.tgt_kp[tr * D + d];
+            const bool hand = cr_hand(a.hand_mask, lab[rl]);
             if (assembly) {
                 if (hand && !mismatch) {
                     const int k = (int)((r0 + rl) / Q);
                     const float diff = ph[i] - t;
                     const float sg = (float)((diff > 0.f) - (diff < 0.f));
-                    vh = a.joint_valid[(a.offsets[k] + jrow_m[rl]) * D + d] ? h_scale * sg : 0.f;
+                    vh = a.joint_valid[(a.tg.offsets[k] + jrow_m[rl]) * D + d] ? h_scale * sg : 0.f;
                 }
             } else if (hand) {
                 const float diff = ph[i] - t;
@@ -307,14 +304,15 @@ __global__ __launch_bounds__(kCrBwdRows) void criterion_bwd_kernel(CritArgs a, C
 
 }  // namespace
 
-int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, int32_t *stats, hipStream_t stream)
+int launch_criterion_fwd(const CritArgs &a, const PredSets<const float> &p, float *losses, int32_t *stats,
+                         hipStream_t stream)
 {
     hipLaunchKernelGGL(criterion_fwd_kernel, dim3((unsigned)a.sets), dim3(kCrFwdThreads), 0, stream, a, p, losses, stats);
     return check_launch("criterion_fwd_kernel");
 }
 
-int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
-                         const int32_t *stats, hipStream_t stream)
+int launch_criterion_bwd(const CritArgs &a, const PredSets<const float> &p, const PredSets<float> &g,
+                         const float *grad_losses, const int32_t *stats, hipStream_t stream)
 {
     const long long rows = (long long)a.bs * a.Q;
     if (rows == 0) return MSDA_OK;

@@ -1,10 +1,12 @@
 // Device helpers shared by the set criteria's kernel files (msda_criterion.hip, msda_criterion_dino.hip): the focal loss
-// element and its derivative, the slot -> frame map of the reference's valid-frame pairing, the fixed-order block sum
-// and torch's argmax rule.  Plain fp32 / fp64 with contraction off in both files, so either file gives the same bits.
+// element and its derivative, the slot -> frame map of the reference's valid-frame pairing, the fixed-order block sum,
+// torch's argmax rule, the hand-label test and a frame's target range.  Plain fp32 / fp64 with contraction off in both
+// files, so either file gives the same bits.
 #pragma once
 #include <math.h>
 
 #include "msda_common.h"
+#include "msda_set_args.h"
 
 #pragma clang fp contract(off)   // from here to the end of the including file: every product and sum rounds on its own
 
@@ -34,6 +36,20 @@ static __device__ void cr_slot_frames(const int32_t *is_valid, int bs, int *fram
         base += total;
         __syncthreads();
     }
+}
+
+// a label whose keypoints are the hand head's (bit `label` of hand_mask)
+__device__ __forceinline__ bool cr_hand(unsigned long long hand_mask, int label)
+{
+    return label < 64 && ((hand_mask >> label) & 1ull);
+}
+
+// The targets of frame f: true and [lo, hi) when the offsets describe them.
+__device__ __forceinline__ bool cr_frame_targets(const SetTargets &tg, int f, long long &lo, long long &hi)
+{
+    lo = tg.offsets[f];
+    hi = tg.offsets[f + 1];
+    return !(lo < 0 || hi < lo || hi > tg.n_targets);
 }
 
 // torch's sigmoid_focal_loss element (binary_cross_entropy_with_logits via log_sigmoid), t in {0, 1}

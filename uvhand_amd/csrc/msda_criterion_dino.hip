@@ -67,19 +67,6 @@ __device__ __forceinline__ DcChunk dc_chunk(const DinoCritArgs &a, int chunk)
     return ch;
 }
 
-__device__ __forceinline__ bool dc_hand(const DinoCritArgs &a, int label)
-{
-    return label < 64 && ((a.hand_mask >> label) & 1ull);
-}
-
-// The targets of frame f: true and [lo, hi) when the offsets describe them.
-__device__ __forceinline__ bool dc_frame_targets(const DinoCritArgs &a, int f, long long &lo, long long &hi)
-{
-    lo = a.offsets[f];
-    hi = a.offsets[f + 1];
-    return !(lo < 0 || hi < lo || hi > a.n_targets);
-}
-
 // The positive of row q of slot k of set s: true with its label and target row; status bits are or-ed into st.
 __device__ bool dc_positive(const DinoCritArgs &a, const DcChunk &ch, int q, const int *frame_of, int &label, long long &trow,
                             int &st)
@@ -87,7 +74,7 @@ __device__ bool dc_positive(const DinoCritArgs &a, const DcChunk &ch, int q, con
     const int f = frame_of[ch.k];
     if (f < 0) return false;   // past the valid frames
     long long lo, hi, j = -1;
-    if (!dc_frame_targets(a, f, lo, hi)) {
+    if (!cr_frame_targets(a.tg, f, lo, hi)) {
         st |= kCritBadTargets;
         return false;
     }
@@ -100,22 +87,23 @@ __device__ bool dc_positive(const DinoCritArgs &a, const DcChunk &ch, int q, con
         j = q % a.single_pad;
         if (j >= n) return false;
     } else {
-        const long long slots = (long long)a.match_sets * a.bs, slot = (long long)a.match_set[ch.s] * a.bs + ch.k;
-        const long long cnt = a.match[2 * slots * a.t_max + slot];
+        const MatchView mv(a.match_sets, a.bs, a.tg.t_max);
+        const long long slot = (long long)a.match_set[ch.s] * a.bs + ch.k;
+        const long long cnt = a.match[mv.count(slot)];
         int m = 0;
-        for (; m < cnt && m < a.t_max; ++m) {   // pairs are in ascending query order
-            const long long qm = a.match[slot * a.t_max + m];
+        for (; m < cnt && m < mv.W; ++m) {   // pairs are in ascending query order
+            const long long qm = a.match[mv.query(slot, m)];
             if (qm == q) break;
             if (qm > q) return false;
         }
-        if (!(m < cnt && m < a.t_max)) return false;
-        j = a.match[slots * a.t_max + slot * a.t_max + m];
+        if (!(m < cnt && m < mv.W)) return false;
+        j = a.match[mv.target(slot, m)];
         if (j < 0 || j >= n || m >= n) {
             st |= kCritBadTargets;
             return false;
         }
     }
-    const long long lab = a.labels[lo + j];
+    const long long lab = a.tg.labels[lo + j];
     if (lab < 0 || lab >= a.K) {
         st |= kCritBadLabel;
         return false;
@@ -131,17 +119,18 @@ __device__ int dc_slot_status(const DinoCritArgs &a, const DcChunk &ch, const in
     const int tid = threadIdx.x, f = frame_of[ch.k];
     int st = 0;
     long long lo = 0, hi = 0;
-    const bool ok = f >= 0 && dc_frame_targets(a, f, lo, hi);
+    const bool ok = f >= 0 && cr_frame_targets(a.tg, f, lo, hi);
     if (tid == 0 && f >= 0 && !ok) st |= kCritBadTargets;
     if (ch.dn) {
         if (tid == 0 && ok && hi - lo > a.single_pad / 2) st |= kCritBadTargets;
         return st;
     }
-    const long long slots = (long long)a.match_sets * a.bs, slot = (long long)a.match_set[ch.s] * a.bs + ch.k;
-    if (tid == 0 && a.match[2 * slots * a.t_max + slots + slot] != 0) st |= kCritMatchStatus;
-    const long long cnt = a.match[2 * slots * a.t_max + slot];
-    if (tid < a.t_max && tid < cnt) {
-        const long long q = a.match[slot * a.t_max + tid];
+    const MatchView mv(a.match_sets, a.bs, a.tg.t_max);
+    const long long slot = (long long)a.match_set[ch.s] * a.bs + ch.k;
+    if (tid == 0 && a.match[mv.status(slot)] != 0) st |= kCritMatchStatus;
+    const long long cnt = a.match[mv.count(slot)];
+    if (tid < mv.W && tid < cnt) {
+        const long long q = a.match[mv.query(slot, tid)];
         if (!ok || q < 0 || q >= a.Q[ch.s]) st |= kCritBadTargets;
     }
     return st;
@@ -156,13 +145,14 @@ struct DcShared {
     int ints[4];                      // status bits, hand rows, object rows, non-empty rows
 };
 
-__global__ __launch_bounds__(kDcThreads) void criterion_dino_chunk_kernel(DinoCritArgs a, CritSets p, DcPartial *__restrict__ part)
+__global__ __launch_bounds__(kDcThreads) void criterion_dino_chunk_kernel(DinoCritArgs a, PredSets<const float> p,
+                                                                          DcPartial *__restrict__ part)
 {
     __shared__ DcShared sh;
     const int tid = threadIdx.x;
     const DcChunk ch = dc_chunk(a, blockIdx.x);
     const int K = a.K, D = a.D, Q = a.Q[ch.s];
-    cr_slot_frames(a.is_valid, a.bs, sh.frame_of, sh.wcnt);
+    cr_slot_frames(a.tg.is_valid, a.bs, sh.frame_of, sh.wcnt);
     if (tid < 4) sh.ints[tid] = 0;
     __syncthreads();
 
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_chunk_kernel(DinoCr
         int label = -1;
         long long trow = -1;
         if (dc_positive(a, ch, ch.q0 + tid, sh.frame_of, label, trow, status)) {
-            const bool hand = dc_hand(a, label);
+            const bool hand = cr_hand(a.hand_mask, label);
             n_hand += hand;
             n_obj += !hand;
         }
@@ -188,14 +178,14 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_chunk_kernel(DinoCr
         const int rl = i / K, c = i % K;
         csum += (double)cr_focal(x[i], c == sh.lab[rl] ? 1.f : 0.f, a.alpha);
     }
-    if (a.tgt_kp) {
+    if (a.tg.tgt_kp) {
         const float *ph = p.hand[ch.s] + r0 * D, *po = p.obj[ch.s] + r0 * D;
         for (int i = tid; i < ch.nr * D; i += kDcThreads) {
             const int rl = i / D, d = i % D;
             const long long tr = sh.trow[rl];
             if (tr < 0) continue;
-            const float t = a.tgt_kp[tr * D + d];
-            if (dc_hand(a, sh.lab[rl])) hsum += (double)fabsf(ph[i] - t);
+            const float t = a.tg.tgt_kp[tr * D + d];
+            if (cr_hand(a.hand_mask, sh.lab[rl])) hsum += (double)fabsf(ph[i] - t);
             else osum += (double)fabsf(po[i] - t);
         }
     }
@@ -247,10 +237,10 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_finish_kernel(DinoC
         int full = 0;
         for (int c = 0; c < cpf; ++c) full += mine[f * cpf + c].card;
         long long lo, hi;
-        const bool ok = dc_frame_targets(a, f, lo, hi);
+        const bool ok = cr_frame_targets(a.tg, f, lo, hi);
         const long long d = full - (hi - lo);
         card_err += (int)(d < 0 ? -d : d);
-        if (a.is_valid[f] != 0) {
+        if (a.tg.is_valid[f] != 0) {
             if (!ok) status |= kCritBadTargets;
             else valid_targets += (int)(hi - lo > 0);
         }
@@ -281,7 +271,8 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_finish_kernel(DinoC
     }
 }
 
-__global__ __launch_bounds__(kDcThreads) void criterion_dino_bwd_kernel(DinoCritArgs a, CritSets p, CritGrads g,
+__global__ __launch_bounds__(kDcThreads) void criterion_dino_bwd_kernel(DinoCritArgs a, PredSets<const float> p,
+                                                                        PredSets<float> g,
                                                                         const float *__restrict__ grad_losses,
                                                                         const int32_t *__restrict__ stats)
 {
@@ -292,7 +283,7 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_bwd_kernel(DinoCrit
     const int tid = threadIdx.x;
     const DcChunk ch = dc_chunk(a, blockIdx.x);
     const int K = a.K, D = a.D, Q = a.Q[ch.s];
-    cr_slot_frames(a.is_valid, a.bs, frame_of, wcnt);
+    cr_slot_frames(a.tg.is_valid, a.bs, frame_of, wcnt);
     __syncthreads();
 
     const int32_t *st = stats + (long long)ch.s * kCritStats;
@@ -328,8 +319,8 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_bwd_kernel(DinoCrit
         const long long tr = trow[rl];
         float vh = 0.f, vo = 0.f;
         if (tr >= 0) {
-            const float t = a.tgt_kp[tr * D + d];
-            if (dc_hand(a, lab[rl])) {
+            const float t = a.tg.tgt_kp[tr * D + d];
+            if (cr_hand(a.hand_mask, lab[rl])) {
                 const float diff = ph[i] - t;
                 vh = h_scale * (float)((diff > 0.f) - (diff < 0.f));
             } else {
@@ -344,8 +335,8 @@ __global__ __launch_bounds__(kDcThreads) void criterion_dino_bwd_kernel(DinoCrit
 
 }  // namespace
 
-int launch_criterion_dino_fwd(const DinoCritArgs &a, const CritSets &p, void *workspace, float *losses, int32_t *stats,
-                              hipStream_t stream)
+int launch_criterion_dino_fwd(const DinoCritArgs &a, const PredSets<const float> &p, void *workspace, float *losses,
+                              int32_t *stats, hipStream_t stream)
 {
     DcPartial *part = static_cast<DcPartial *>(workspace);
     hipLaunchKernelGGL(criterion_dino_chunk_kernel, dim3((unsigned)a.chunks), dim3(kDcThreads), 0, stream, a, p, part);
@@ -355,8 +346,8 @@ int launch_criterion_dino_fwd(const DinoCritArgs &a, const CritSets &p, void *wo
     return check_launch("criterion_dino_finish_kernel");
 }
 
-int launch_criterion_dino_bwd(const DinoCritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
-                              const int32_t *stats, hipStream_t stream)
+int launch_criterion_dino_bwd(const DinoCritArgs &a, const PredSets<const float> &p, const PredSets<float> &g,
+                              const float *grad_losses, const int32_t *stats, hipStream_t stream)
 {
     hipLaunchKernelGGL(criterion_dino_bwd_kernel, dim3((unsigned)a.chunks), dim3(kDcThreads), 0, stream, a, p, g, grad_losses, stats);
     return check_launch("criterion_dino_bwd_kernel");

@@ -8,6 +8,7 @@
 #include "msda.h"
 #include "msda_common.h"
 #include "msda_op_args.h"
+#include "msda_set_args.h"
 
 namespace msda {
 
@@ -183,20 +184,10 @@ int launch_cdn_prepare_bwd(const float *grad_label, const int32_t *noised, long 
                            hipStream_t stream);
 
 // ---- the Hungarian matchers: cost block + assignment per (prediction set, frame) (msda_matcher.hip) ----
-constexpr int kMatchMaxQueries = 1024;  // queries of a frame (one workgroup, one thread per query)
-constexpr int kMatchMaxTargets = 16;    // targets of a frame (rows of the solved problem, held per thread)
-constexpr int kMatchMaxSets = 16;       // prediction sets per launch (their pointers travel as kernel arguments)
-constexpr int kMatchMaxDim = 64;        // keypoint values per target
-// per-slot status codes (include/msda.h)
+// per-slot status codes (include/msda.h); the limits, PredSets, SetTargets and MatchView are msda_set_args.h's
 constexpr int kMatchInvalid = 1, kMatchInfeasible = 2, kMatchBadLabel = 3, kMatchBadTargets = 4;
-struct MatchSets {
-    const float *logits[kMatchMaxSets];
-    const float *hand[kMatchMaxSets];
-    const float *obj[kMatchMaxSets];
-};
-int launch_match(const MatchSets &sets, int n_sets, int bs, int Q, int K, int D, const int64_t *labels, const float *tgt_kp,
-                 const int64_t *offsets, long long n_targets, const int32_t *is_valid, int t_max, float w_cls, float w_kp,
-                 int64_t *out, float *cost_debug, hipStream_t stream);
+int launch_match(const PredSets<const float> &sets, int n_sets, int bs, int Q, int K, int D, const SetTargets &tg, float w_cls,
+                 float w_kp, int64_t *out, float *cost_debug, hipStream_t stream);
 int launch_lsap(const float *cost, int B, int Q, int T, int64_t *out, hipStream_t stream);
 
 // ---- the set criteria's matched losses over the matcher's device result (msda_criterion.hip) ----
@@ -205,43 +196,25 @@ constexpr int kCritTerms = 4;   // loss columns per set (include/msda.h)
 constexpr int kCritStats = 4;   // status bits, hand rows, object rows, no valid target (ARCTIC)
 constexpr int kCritBadLabel = 1, kCritBadTargets = 2, kCritMaskMismatch = 4, kCritMatchStatus = 8;
 struct CritArgs {
-    int kind, sets, bs, Q, K, D, t_max;
+    int kind, sets, bs, Q, K, D;
     const int64_t *match;       // the matcher's result buffer
-    const int64_t *labels;
-    const float *tgt_kp;        // [n_targets, D] or NULL (D = 0)
-    const int64_t *offsets;
-    long long n_targets;
-    const int32_t *is_valid;    // ARCTIC: slot k pairs with the k-th valid frame; NULL: frame k
+    SetTargets tg;              // is_valid: ARCTIC; NULL for AssemblyHands
     const uint8_t *joint_valid; // AssemblyHands [n_targets, D]
     unsigned long long hand_mask;
     const float *num_boxes;     // device scalar
     float alpha;
 };
-struct CritSets {
-    const float *logits[kMatchMaxSets];
-    const float *hand[kMatchMaxSets];
-    const float *obj[kMatchMaxSets];
-};
-struct CritGrads {
-    float *logits[kMatchMaxSets];
-    float *hand[kMatchMaxSets];
-    float *obj[kMatchMaxSets];
-};
-int launch_criterion_fwd(const CritArgs &a, const CritSets &p, float *losses, int32_t *stats, hipStream_t stream);
-int launch_criterion_bwd(const CritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
+int launch_criterion_fwd(const CritArgs &a, const PredSets<const float> &p, float *losses, int32_t *stats, hipStream_t stream);
+int launch_criterion_bwd(const CritArgs &a, const PredSets<const float> &p, const PredSets<float> &g, const float *grad_losses,
                          const int32_t *stats, hipStream_t stream);
 
 // ---- the DINO criterion's matched and denoising losses (msda_criterion_dino.hip); status bits and columns as above ----
 constexpr int kDinoCritChunkRows = 256;      // rows of one frame a forward / backward workgroup covers (include/msda.h)
 constexpr int kDinoCritPartialBytes = 64;    // one forward workgroup's partial record in the workspace
 struct DinoCritArgs {
-    int sets, bs, K, D, t_max, match_sets, single_pad, groups;
+    int sets, bs, K, D, match_sets, single_pad, groups;
     const int64_t *match;       // the matcher's result buffer (match_sets sets); NULL when every set is a denoising set
-    const int64_t *labels;
-    const float *tgt_kp;        // [n_targets, D] or NULL (D = 0)
-    const int64_t *offsets;
-    long long n_targets;
-    const int32_t *is_valid;    // slot k pairs with the k-th valid frame
+    SetTargets tg;
     unsigned long long hand_mask;
     const float *num_boxes;     // device scalar
     float alpha;
@@ -250,10 +223,10 @@ struct DinoCritArgs {
     int chunk_base[kMatchMaxSets];   // the set's first chunk; chunk = (set, frame, kDinoCritChunkRows rows of the frame)
     int chunks;                      // of all sets
 };
-int launch_criterion_dino_fwd(const DinoCritArgs &a, const CritSets &p, void *workspace, float *losses, int32_t *stats,
-                              hipStream_t stream);
-int launch_criterion_dino_bwd(const DinoCritArgs &a, const CritSets &p, const CritGrads &g, const float *grad_losses,
-                              const int32_t *stats, hipStream_t stream);
+int launch_criterion_dino_fwd(const DinoCritArgs &a, const PredSets<const float> &p, void *workspace, float *losses,
+                              int32_t *stats, hipStream_t stream);
+int launch_criterion_dino_bwd(const DinoCritArgs &a, const PredSets<const float> &p, const PredSets<float> &g,
+                              const float *grad_losses, const int32_t *stats, hipStream_t stream);
 
 // ---- the DeformableDETR prediction heads as grouped GEMMs: fp32 (msda_heads.hip) and bf16 autocast (msda_heads_bf16.hip) ----
 // One set of problem tables, one planner (msda_heads.hip) and one workspace layout serve both forms; a table says beside every

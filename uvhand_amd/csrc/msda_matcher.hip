@@ -168,16 +168,17 @@ __device__ int mt_solve(int nr, int nc, const MtCol &col, MtShared &sh)
 
 // Solves the block (T < Q: targets are the rows; else queries are) and writes slot `slot` of the output: pairs sorted by
 // query index, -1 padding to W, count, status.  col = this thread's column as mt_solve wants it.
-__device__ void mt_finish(int Q, int T, int W, const MtCol &col, int status, MtShared &sh, int64_t *out,
-                          long long slots, long long slot)
+__device__ void mt_finish(int Q, int T, const MtCol &col, int status, MtShared &sh, int64_t *out, const MatchView &mv,
+                          long long slot)
 {
+    const int W = mv.W;
     const int nr = T < Q ? T : Q;
     const int nc = T < Q ? Q : T;
     if (status == 0 && nr > 0) status = mt_solve(nr, nc, col, sh);
     __syncthreads();
     const int count = status == 0 ? nr : 0;
-    int64_t *qo = out + slot * W;
-    int64_t *to = out + slots * W + slot * W;
+    int64_t *qo = out + mv.query(slot, 0);
+    int64_t *to = out + mv.target(slot, 0);
     const int t = threadIdx.x;
     if (t < W) {
         if (t >= count) {
@@ -195,14 +196,14 @@ __device__ void mt_finish(int Q, int T, int W, const MtCol &col, int status, MtS
         }
     }
     if (t == 0) {
-        out[2 * slots * W + slot] = count;
-        out[2 * slots * W + slots + slot] = status;
+        out[mv.count(slot)] = count;
+        out[mv.status(slot)] = status;
     }
 }
 
 __device__ __forceinline__ bool mt_bad(float c) { return c != c || c == -INFINITY; }
 
-__global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(MatchSets sets, int bs, int Q, int K, int D,
+__global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(PredSets<const float> sets, int bs, int Q, int K, int D,
                                                                  const int64_t *__restrict__ labels,
                                                                  const float *__restrict__ tgt_kp,
                                                                  const int64_t *__restrict__ offsets, long long n_targets,
@@ -212,7 +213,8 @@ __global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(MatchSets sets,
 {
     __shared__ MtShared sh;
     const int k = blockIdx.x, s = blockIdx.y;
-    const long long slots = (long long)gridDim.y * bs, slot = (long long)s * bs + k;
+    const MatchView mv(gridDim.y, bs, t_max);
+    const long long slot = (long long)s * bs + k;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
 
     // the frame whose targets go with output slot k: the k-th valid frame (a prefix over is_valid)
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(MatchSets sets,
         }
         nvalid = base;
     }
-    if (slot == 0 && tid == 0) out[2 * slots * t_max + 2 * slots] = nvalid;
+    if (slot == 0 && tid == 0) out[mv.nvalid()] = nvalid;
 
     if (tid == 0) {
         int status = 0, T = 0;
@@ -258,12 +260,12 @@ __global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(MatchSets sets,
     __syncthreads();
     if (sh.frame < 0) {   // past the valid frames: no chunk pairs with this slot
         if (tid < t_max) {
-            out[slot * t_max + tid] = -1;
-            out[slots * t_max + slot * t_max + tid] = -1;
+            out[mv.query(slot, tid)] = -1;
+            out[mv.target(slot, tid)] = -1;
         }
         if (tid == 0) {
-            out[2 * slots * t_max + slot] = -1;
-            out[2 * slots * t_max + slots + slot] = 0;
+            out[mv.count(slot)] = -1;
+            out[mv.status(slot)] = 0;
         }
         return;
     }
@@ -324,7 +326,7 @@ __global__ __launch_bounds__(kMatchMaxQueries) void match_kernel(MatchSets sets,
 #pragma unroll
         for (int i = 0; i < kMtRows; ++i) col[i] = (tid < T && i < Q) ? sh.stage[i * kMtRows + tid] : 0.f;
     }
-    mt_finish(Q, T, t_max, col, status, sh, out, slots, slot);
+    mt_finish(Q, T, col, status, sh, out, mv, slot);
 }
 
 __global__ __launch_bounds__(kMatchMaxQueries) void lsap_kernel(const float *__restrict__ cost, int Q, int T, int W, long long B,
@@ -348,19 +350,19 @@ __global__ __launch_bounds__(kMatchMaxQueries) void lsap_kernel(const float *__r
         col[i] = x;
     }
     const int status = __syncthreads_or(bad) ? kMatchInvalid : 0;
-    mt_finish(Q, T, W, col, status, sh, out, B, b);
+    mt_finish(Q, T, col, status, sh, out, MatchView(B, 1, W), b);   // B one-frame sets, no valid-frame count
 }
 
 }  // namespace
 
-int launch_match(const MatchSets &sets, int n_sets, int bs, int Q, int K, int D, const int64_t *labels, const float *tgt_kp,
-                 const int64_t *offsets, long long n_targets, const int32_t *is_valid, int t_max, float w_cls, float w_kp,
-                 int64_t *out, float *cost_debug, hipStream_t stream)
+int launch_match(const PredSets<const float> &sets, int n_sets, int bs, int Q, int K, int D, const SetTargets &tg, float w_cls,
+                 float w_kp, int64_t *out, float *cost_debug, hipStream_t stream)
 {
     if (bs == 0) return MSDA_OK;
     const int threads = ((Q > kMtRows ? Q : kMtRows) + 63) / 64 * 64;
-    hipLaunchKernelGGL(match_kernel, dim3((unsigned)bs, (unsigned)n_sets), dim3(threads), 0, stream, sets, bs, Q, K, D, labels,
-                       tgt_kp, offsets, n_targets, is_valid, t_max, w_cls, w_kp, out, cost_debug);
+    // the kernel takes the targets member by member: its pointers are __restrict__, which a record's members cannot be
+    hipLaunchKernelGGL(match_kernel, dim3((unsigned)bs, (unsigned)n_sets), dim3(threads), 0, stream, sets, bs, Q, K, D, tg.labels,
+                       tg.tgt_kp, tg.offsets, tg.n_targets, tg.is_valid, tg.t_max, w_cls, w_kp, out, cost_debug);
     return check_launch("match_kernel");
 }
 

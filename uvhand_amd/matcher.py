@@ -119,22 +119,15 @@ def match(outputs_list, packed, cost_class=1, cost_keypoint=1, cost_debug=None):
         kp = [o["pred_keypoints"].contiguous() for o in outputs_list]
         buf = MSDA.match_assembly(logits, kp, packed.labels, packed.keypoints, packed.offsets, packed.t_max, cost_class,
                                   cost_keypoint, cost_debug)
-    n, W = sets * bs, packed.t_max
-    return MatchResult(buf[:n * W].view(sets, bs, W), buf[n * W:2 * n * W].view(sets, bs, W),
-                       buf[2 * n * W:2 * n * W + n].view(sets, bs), buf[2 * n * W + n:2 * n * W + 2 * n].view(sets, bs),
-                       buf[-1], buf)
+    return MatchResult(*MSDA.match_views(buf, sets, bs, packed.t_max), buf)
 
 
 def indices_from_host(buffer, sets, bs, t_max, zero_if_empty=False):
     """The reference's per-set result from ``MatchResult.buffer`` copied to the host: a list (per set) of lists of
     ``(query_idx, target_idx)`` int64 CPU tensors, one per valid frame, or 0 for a set whose valid frames have no label
     (``zero_if_empty``, ARCTIC).  Raises scipy's ValueError on a slot whose status says so, frames in order."""
-    n = sets * bs
-    qi = buffer[:n * t_max].view(sets, bs, t_max)
-    ti = buffer[n * t_max:2 * n * t_max].view(sets, bs, t_max)
-    count = buffer[2 * n * t_max:2 * n * t_max + n].view(sets, bs).tolist()
-    status = buffer[2 * n * t_max + n:2 * n * t_max + 2 * n].view(sets, bs).tolist()
-    nvalid = int(buffer[-1])
+    qi, ti, count, status, nvalid = MSDA.match_views(buffer, sets, bs, t_max)
+    count, status, nvalid = count.tolist(), status.tolist(), int(nvalid)
     result = []
     for s in range(sets):
         if zero_if_empty and all(count[s][k] == 0 and status[s][k] == 0 for k in range(nvalid)):

@@ -820,6 +820,24 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
                             float *const *grad_shared_w, float *const *grad_shared_b, void *workspace,
                             unsigned long long workspace_bytes, msda_stream_t stream);
 
+/* The reference gradient of the ARCTIC keypoint epilogue, for callers whose references carry a gradient: DINO's decoder hands
+ * its refined reference points on undetached, and models/dino/dino.py:333-334 feed them to
+ * (delta + inverse_sigmoid(ref)).sigmoid() * 2 - 1 (util/misc.py inverse_sigmoid).  Added after MSDA_ABI_VERSION 116 without a
+ * version bump: a purely additive entry beside msda_heads_backward_f32, which stops at delta.
+ * For every level whose reference needs a gradient and every element e = (level row, j), j < R = 42:
+ *   grad_ref[e] = dinv(ref[e]) * sum over the n_mlp = 2 heads h of (grad_kp[h][e] * 2) * (1 - sig[h][e]) * sig[h][e]
+ *   dinv(x)     = [0 <= x <= 1] * ([x >= eps] / max(x, eps) + [1 - x >= eps] / max(1 - x, eps)),  eps = 1e-5f
+ * (what autograd makes of inverse_sigmoid's three clamps and its log: torch's clamp passes the gradient at its bounds; the head
+ * terms in the order and grouping of the backward's depth-3 operand).  init_ref [M, R], inter_ref [L - 1, M, R], the forward's
+ * saved sig [n_mlp, L, M, R], grad_kp: HOST array of the n_mlp gradients [L, M, R]; all fp32 contiguous.  grad_init_ref [M, R]
+ * and grad_inter_ref [L - 1, M, R] may each be NULL: that reference needs no gradient, and nothing of its levels is read (its
+ * reference pointer may be NULL too).  Every element of a non-NULL output is written.  1 <= L <= 8, M >= 1, R == 42,
+ * n_mlp == 2, L * M * R < 2^31.  One launch (none when both outputs are NULL); no atomics, fixed order: bitwise
+ * reproducible.  No allocation, no synchronisation; argument errors before any launch. */
+int msda_heads_ref_backward_f32(int L, long long M, int n_mlp, int R, const float *init_ref, const float *inter_ref,
+                                const float *sig, const float *const *grad_kp, float *grad_init_ref, float *grad_inter_ref,
+                                msda_stream_t stream);
+
 /* The bf16-autocast form of the same node.  Added after MSDA_ABI_VERSION 116 without a version bump: purely additive entries.
  * Same problems, host pointer arrays, launch budget (3 forward, 5 backward) and flags as the fp32 entries; every product runs
  * on the bf16 MFMA with fp32 accumulation, and the dtypes and roundings are those of torch's bf16 autocast over the

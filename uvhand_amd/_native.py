@@ -130,6 +130,7 @@ SIGNATURES = {
     "msda_heads_workspace_bytes": "U ii l iii u",
     "msda_heads_forward_f32": "i ii l iiii u ppppppppp pppppp",
     "msda_heads_backward_f32": "i ii l iiii u ppppppppp ppppp pppppppp U p",
+    "msda_heads_ref_backward_f32": "i i l ii pppp pp p",
     "msda_heads_bf16_supported": "i i",
     "msda_heads_bf16_workspace_bytes": "U ii l iii u",
     "msda_ffn_bf16_supported": "i ii",
@@ -1908,6 +1909,27 @@ def heads_backward_bf16(*args):
     """msda_heads_backward_bf16: heads_backward for that form; the parameter gradients and grad_hs are fp32, the output
     gradients carry the outputs' dtypes."""
     return _heads_backward("bf16", *args)
+
+
+def heads_ref_backward(init_ref, inter_ref, sig, grad_kp, want_init=True, want_inter=True):
+    """msda_heads_ref_backward_f32 (include/msda.h): the gradients of the ARCTIC keypoint epilogue with respect to its
+    references, from the forward's saved sig [2, L, M, 42] and the two keypoint gradients [L, M, 42].  Returns
+    (grad_init_ref [M, 42] or None, grad_inter_ref [L - 1, M, 42] or None); nothing of a level that is not wanted is read.
+    One launch, no host synchronisation."""
+    n_mlp, L, M, R = sig.shape
+    want_inter = bool(want_inter) and L > 1
+    tensors = [sig] + list(grad_kp) + ([init_ref] if want_init else []) + ([inter_ref] if want_inter else [])
+    _check_f32("dino_heads", sig.device, tensors)
+    if len(grad_kp) != n_mlp or any(tuple(g.shape) != (L, M, R) for g in grad_kp):
+        raise RuntimeError("dino_heads: expected one keypoint gradient [L, M, R] per head")
+    if (want_init and tuple(init_ref.shape) != (M, R)) or (want_inter and tuple(inter_ref.shape) != (L - 1, M, R)):
+        raise RuntimeError("dino_heads: expected init_ref [M, R] and inter_ref [L - 1, M, R]")
+    g_init = torch.empty_like(init_ref) if want_init else None
+    g_inter = torch.empty_like(inter_ref) if want_inter else None
+    _launch(sig.device, "msda_heads_ref_backward_f32", "heads_ref_backward", int(L), int(M), int(n_mlp), int(R),
+            init_ref.data_ptr() if want_init else None, inter_ref.data_ptr() if want_inter else None, sig.data_ptr(),
+            _ptr_array(grad_kp), g_init.data_ptr() if want_init else None, g_inter.data_ptr() if want_inter else None)
+    return g_init, g_inter
 
 
 # ---- SmoothNet: MotionSmoother modules and get_arctic_item's selection (msda_smoother.hip, msda_arctic_item.hip) ----------

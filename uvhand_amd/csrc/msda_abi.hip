@@ -1456,6 +1456,17 @@ int msda_heads_backward_f32(int kind, int L, long long M, int C, int K, int n_ml
                           grad_shared_w, grad_shared_b, workspace, workspace_bytes, stream);
 }
 
+int msda_heads_ref_backward_f32(int L, long long M, int n_mlp, int R, const float *init_ref, const float *inter_ref,
+                                const float *sig, const float *const *grad_kp, float *grad_init_ref, float *grad_inter_ref,
+                                msda_stream_t stream)
+{
+    msda::HeadsRefBwdPlan plan;
+    const int rc = msda::heads_plan_ref_backward(L, M, n_mlp, R, init_ref, inter_ref, sig, grad_kp, grad_init_ref, grad_inter_ref, plan);
+    if (rc != MSDA_OK) return rc;
+    msda::begin_call();
+    return msda::heads_run_ref_backward(plan, (hipStream_t)stream);
+}
+
 int msda_heads_forward_bf16(int kind, int L, long long M, int C, int K, int n_mlp, int R, unsigned flags, const float *hs,
                             const float *init_ref, const float *inter_ref, const float *const *cls_w,
                             const float *const *cls_b, const float *const *mlp_w, const float *const *mlp_b,

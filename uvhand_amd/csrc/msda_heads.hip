@@ -11,7 +11,11 @@
 //   dgrad     dx = sum over segments (dy o mode) . W  (NN): depth 3, depth 2, then depth 1, whose reduction runs over the
 //             concatenated outputs of every head that reads hs[l]; mode = sigmoid' from the saved s, or the ReLU mask of the
 //             saved activation (threshold_backward's `out > 0`)
-//   wgrad     partial dW[chunk] = (dy o mode)^T . x  over row chunks of kHeadsWgradChunk rows, the bias column sums beside them
+//   wgrad     partial dW[chunk] = (dy o mode)^T . x  over row chunks of kHeadsWgradChunk rows, the bias column sums beside them;
+//             a chunk's rows are summed 32 at a time (one stage of the tile loop) from zero and the stage sums added to a
+//             second accumulator, and the bias column sums are kept in fp64 until the chunk's one rounding: these are sums
+//             over hundreds of rows whose terms cancel, and one running fp32 sum missed the fp64 rule there (DESIGN.md §4.32,
+//             "The weight gradient's summation order")
 //   reduce    dW = sum over chunks, in chunk order
 //
 // Kernel: fp32 MFMA (v_mfma_f32_32x32x2_f32), 64 x 64 output tile per 256-thread workgroup, 2 x 2 wavefronts of 32 x 32,
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
 {
     __shared__ __attribute__((aligned(16))) float As[2][kLds];
     __shared__ __attribute__((aligned(16))) float Bs[2][kLds];
-    __shared__ float bred[4][kHT];
+    __shared__ double bred[4][kHT];
     const HeadsWgradProb &p = P.p[heads_problem(P)];
     const int C = P.C, tiles_j = (C + kHT - 1) / kHT, tiles_i = (p.n + kHT - 1) / kHT;
     const int local = (int)blockIdx.x - p.tile0;
@@ -202,8 +206,9 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
             rb[4 * u] = v.x; rb[4 * u + 1] = v.y; rb[4 * u + 2] = v.z; rb[4 * u + 3] = v.w;
         }
     };
-    // bias: the column tile 0 workgroups also sum their staged dy o mode, thread (q, i) over 8 rows of each stage
-    float bsum = 0.f;
+    // bias: the column tile 0 workgroups also sum their staged dy o mode, thread (q, i) over 8 rows of each stage; in fp64, so
+    // that a chunk's column sum is rounded once (a bias gradient is often a single element whose terms cancel)
+    double bsum = 0.0;
     const bool with_bias = j0t == 0;
     auto per_stage = [&](const float *S) {
         if (with_bias) {
@@ -212,14 +217,15 @@ __global__ __launch_bounds__(kHBlock) void heads_wgrad_kernel(HeadsWgradArgs P)
             for (int u = 0; u < 8; ++u) bsum += S[(8 * q + u) * kRowN + i];
         }
     };
-    const f32x16 acc = tile_loop<false, false, false, true>(As, Bs, (nrows + kHS - 1) / kHS, load, per_stage);
+    // the rows are summed stage by stage (32 rows) and the stage sums added up: see tile_loop_impl
+    const f32x16 acc = tile_loop_impl<false, false, false, true, true>(As, Bs, (nrows + kHS - 1) / kHS, load, per_stage);
     float *part = P.ws + p.part;
     if (with_bias) {                                                            // uniform per workgroup
         bred[tid >> 6][tid & 63] = bsum;
         __syncthreads();
         if (tid < kHT && i0t + tid < p.n)
             part[(long long)p.chunks * p.n * C + (long long)chunk * p.n + i0t + tid] =
-                ((bred[0][tid] + bred[1][tid]) + bred[2][tid]) + bred[3][tid];
+                (float)(((bred[0][tid] + bred[1][tid]) + bred[2][tid]) + bred[3][tid]);
     }
     const int wave = tid >> 6, lane = tid & 63;
     const int i0 = (wave >> 1) * 32, g = lane >> 5, j = j0t + (wave & 1) * 32 + (lane & 31);
@@ -247,6 +253,43 @@ __global__ __launch_bounds__(kHBlock) void heads_reduce_kernel(HeadsReduceArgs P
         const long long i = e - nw;
         for (int c = 0; c < p.chunks; ++c) s += part[p.chunks * nw + (long long)c * p.n + i];
         p.db[i] = s;
+    }
+}
+
+// ---- reference gradient of the ARCTIC keypoint epilogue (DINO: models/dino/dino.py:333-334 with references that carry a gradient)
+// The flat space is that of the stacked tensors, [L * M * R] with R = D = 42: level 0 reads init_ref, levels >= 1 inter_ref.
+// A thread moves groups of W consecutive elements, [e0 + W * i, e0 + W * (i + 1)); the host picks W from the flat element index
+// (M * R and every base are multiples of W), so no group crosses from init_ref into inter_ref and every access is W * 4 bytes.
+// Per element: the two heads' depth-3 operands in apply_mode's order and grouping, summed head 0 then head 1, times what
+// autograd makes of inverse_sigmoid's three clamps and its log (torch's clamp passes the gradient at its bounds).
+__device__ __forceinline__ float ref_dinv(float x)
+{
+    const float eps = 1e-5f, y = 1.f - x;
+    const float d = (x >= eps ? 1.f / fmaxf(x, eps) : 0.f) + (y >= eps ? 1.f / fmaxf(y, eps) : 0.f);
+    return x >= 0.f && x <= 1.f ? d : 0.f;
+}
+
+template <int W>
+__global__ __launch_bounds__(kHBlock) void heads_ref_bwd_kernel(HeadsRefBwdArgs P)
+{
+#pragma clang fp contract(off)     // every width rounds each product and sum on its own: the same bits whichever width serves a call
+    struct __attribute__((aligned(W * 4))) Vec { float v[W]; };
+    const long long stride = (long long)gridDim.x * kHBlock;
+    for (long long i = (long long)blockIdx.x * kHBlock + threadIdx.x; i < P.groups; i += stride) {
+        const long long e = P.e0 + i * W;
+        const bool first = e < P.MR;
+        const Vec x = *reinterpret_cast<const Vec *>(first ? P.init_ref + e : P.inter_ref + (e - P.MR));
+        const Vec g0 = *reinterpret_cast<const Vec *>(P.grad_kp[0] + e), g1 = *reinterpret_cast<const Vec *>(P.grad_kp[1] + e);
+        const Vec s0 = *reinterpret_cast<const Vec *>(P.sig + e), s1 = *reinterpret_cast<const Vec *>(P.sig + P.LMR + e);
+        Vec out;
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            // each head's term rounded as the depth-3 operand is, then one rounded add
+            const float t = (g0.v[u] * 2.f) * (1.f - s0.v[u]) * s0.v[u] + (g1.v[u] * 2.f) * (1.f - s1.v[u]) * s1.v[u];
+            const float d = ref_dinv(x.v[u]);
+            out.v[u] = d != 0.f ? d * t : 0.f;                  // outside [0, 1]: exactly zero, whatever t holds
+        }
+        *reinterpret_cast<Vec *>(first ? P.grad_init_ref + e : P.grad_inter_ref + (e - P.MR)) = out;
     }
 }
 
@@ -548,6 +591,49 @@ int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream)
                       : heads_launch(heads_wgrad_kernel, "heads_wgrad_kernel", plan.w, plan.wtiles, stream);
     if (rc != MSDA_OK) return rc;
     return heads_launch(heads_reduce_kernel, "heads_reduce_kernel", plan.r, plan.rblocks, stream);
+}
+
+// The reference gradient beside the backward above: one launch over the levels whose output is given, none when both are null.
+int heads_plan_ref_backward(int L, long long M, int n_mlp, int R, const float *init_ref, const float *inter_ref, const float *sig,
+                            const float *const *grad_kp, float *grad_init_ref, float *grad_inter_ref, HeadsRefBwdPlan &plan)
+{
+    plan.blocks = 0;
+    plan.width = 1;
+    if (L < 1 || L > kHeadsMaxLevels) return herr("msda_heads_ref_backward: need 1 <= L <= 8 levels");
+    if (M < 1) return herr("msda_heads_ref_backward: need M >= 1");
+    if (n_mlp != 2) return herr("msda_heads_ref_backward: n_mlp must be 2 (key_embed, obj_key_embed)");
+    if (R != 42) return herr("msda_heads_ref_backward: reference width R must be 42");
+    if (M >= (1LL << 31) || (long long)L * M * R >= (1LL << 31)) return herr("msda_heads_ref_backward: tensors beyond 2^31 elements");
+    const bool want0 = grad_init_ref != nullptr, want1 = grad_inter_ref != nullptr && L > 1;
+    if (sig == nullptr || grad_kp == nullptr || grad_kp[0] == nullptr || grad_kp[1] == nullptr || (want0 && init_ref == nullptr)
+        || (want1 && inter_ref == nullptr))
+        return herr("msda_heads_ref_backward: null pointer");
+    if (!want0 && !want1) return MSDA_OK;
+    HeadsRefBwdArgs &a = plan.a;
+    a.init_ref = init_ref; a.inter_ref = inter_ref; a.sig = sig; a.grad_kp[0] = grad_kp[0]; a.grad_kp[1] = grad_kp[1];
+    a.grad_init_ref = grad_init_ref; a.grad_inter_ref = grad_inter_ref;
+    a.MR = M * R; a.LMR = (long long)L * a.MR;
+    a.e0 = want0 ? 0 : a.MR;
+    const long long n = (want1 ? a.LMR : a.MR) - a.e0;
+    // the access width: M * R is even, and a multiple of 4 when M is; every base must be as aligned as the width it is read with
+    int W = M % 2 == 0 ? 4 : 2;
+    // (the pointers of a level that is not wanted are not read and do not count)
+    for (const void *p : {(const void *)(want0 ? init_ref : nullptr), (const void *)(want1 ? inter_ref : nullptr), (const void *)sig,
+                          (const void *)grad_kp[0], (const void *)grad_kp[1], (const void *)(want0 ? grad_init_ref : nullptr),
+                          (const void *)(want1 ? grad_inter_ref : nullptr)})
+        while (W > 1 && (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(W * 4 - 1)) != 0) W /= 2;
+    a.groups = n / W;                                                           // n is a multiple of M * R, so of W
+    const long long blocks = (a.groups + kHBlock - 1) / kHBlock;
+    plan.blocks = (int)(blocks < 2048 ? blocks : 2048);                         // the kernel strides over the rest
+    plan.width = W;
+    return MSDA_OK;
+}
+
+int heads_run_ref_backward(const HeadsRefBwdPlan &plan, hipStream_t stream)
+{
+    if (plan.width == 4) return heads_launch(heads_ref_bwd_kernel<4>, "heads_ref_bwd_kernel", plan.a, plan.blocks, stream);
+    if (plan.width == 2) return heads_launch(heads_ref_bwd_kernel<2>, "heads_ref_bwd_kernel", plan.a, plan.blocks, stream);
+    return heads_launch(heads_ref_bwd_kernel<1>, "heads_ref_bwd_kernel", plan.a, plan.blocks, stream);
 }
 
 }  // namespace msda

@@ -336,6 +336,19 @@ int heads_plan_forward(const HeadsCall &c, HeadsFwdPlan &plan);
 int heads_plan_backward(const HeadsCall &c, HeadsBwdPlan &plan);
 int heads_run_forward(const HeadsFwdPlan &plan, hipStream_t stream);
 int heads_run_backward(const HeadsBwdPlan &plan, hipStream_t stream);
+// the reference gradient of the ARCTIC keypoint epilogue (msda_heads_ref_backward_f32): the flat element space [L * M * R]
+struct HeadsRefBwdArgs {
+    const float *init_ref, *inter_ref, *sig, *grad_kp[kHeadsMaxMlp];
+    float *grad_init_ref, *grad_inter_ref;
+    long long MR, LMR, e0, groups;          // M * R, L * M * R, the first element written, groups of the access width
+};
+struct HeadsRefBwdPlan {
+    HeadsRefBwdArgs a;
+    int blocks, width;                      // zero blocks: no output asked for, no launch
+};
+int heads_plan_ref_backward(int L, long long M, int n_mlp, int R, const float *init_ref, const float *inter_ref, const float *sig,
+                            const float *const *grad_kp, float *grad_init_ref, float *grad_inter_ref, HeadsRefBwdPlan &plan);
+int heads_run_ref_backward(const HeadsRefBwdPlan &plan, hipStream_t stream);
 // the bf16 form's kernels (msda_heads_bf16.hip); zero tiles: no launch
 int launch_heads_forward_bf16(const HeadsFwdArgs &a, int tiles, hipStream_t stream);
 int launch_heads_dgrad_bf16(const HeadsDgradArgs &a, int tiles, hipStream_t stream);

@@ -38,14 +38,16 @@ __device__ __forceinline__ float4 frag(const float *S, int rc, int i, int g)
 
 // The stage loop shared by the three GEMM kernels: `load(s, r_a, r_b)` fills the registers of stage s; `per_stage(buf)` runs
 // after the MFMAs of a stage with that stage's LDS buffer still intact (the wgrad bias sums).
-template <bool AKM, bool AVEC, bool BKM, bool BVEC, class Load, class PerStage>
-__device__ __forceinline__ f32x16 tile_loop(float (*As)[kLds], float (*Bs)[kLds], int nstages, Load load, PerStage per_stage)
+// BLOCKED: each stage's 32 reduction indices are summed on their own and added to the running total once (a long reduction
+// of terms that cancel then loses about sqrt(stages) less than one running sum does; the weight gradients reduce over rows).
+template <bool AKM, bool AVEC, bool BKM, bool BVEC, bool BLOCKED, class Load, class PerStage>
+__device__ __forceinline__ f32x16 tile_loop_impl(float (*As)[kLds], float (*Bs)[kLds], int nstages, Load load, PerStage per_stage)
 {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32, g = lane >> 5, c = lane & 31;
-    f32x16 acc;
+    f32x16 acc, total;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = total[r] = 0.f;
     float ra[8], rb[8];
     load(0, ra, rb);
     stage_store<AKM, AVEC>(As[0], tid, ra);
@@ -63,6 +65,13 @@ __device__ __forceinline__ f32x16 tile_loop(float (*As)[kLds], float (*Bs)[kLds]
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
         }
+        if (BLOCKED) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                total[r] += acc[r];
+                acc[r] = 0.f;
+            }
+        }
         per_stage(As[cur]);
         if (more) {
             stage_store<AKM, AVEC>(As[cur ^ 1], tid, ra);
@@ -71,7 +80,13 @@ __device__ __forceinline__ f32x16 tile_loop(float (*As)[kLds], float (*Bs)[kLds]
         __syncthreads();
         cur ^= 1;
     }
-    return acc;
+    return BLOCKED ? total : acc;
+}
+
+template <bool AKM, bool AVEC, bool BKM, bool BVEC, class Load, class PerStage>
+__device__ __forceinline__ f32x16 tile_loop(float (*As)[kLds], float (*Bs)[kLds], int nstages, Load load, PerStage per_stage)
+{
+    return tile_loop_impl<AKM, AVEC, BKM, BVEC, false>(As, Bs, nstages, load, per_stage);
 }
 
 struct NoStage {

@@ -210,3 +210,94 @@ def detr_heads(kind, hs, init_reference, inter_references, cls_embed, mlps, shar
                                     inter_references if mlps and hs.shape[0] > 1 else None, *params)
     n_kp = len(mlps)
     return outs[0], list(outs[1:1 + n_kp]), list(outs[1 + n_kp:])
+
+
+# ---- DINO (models/dino/dino.py:323-347): the ARCTIC heads over references that carry a gradient ---------------------------
+def dino_heads_reference(hs, references, class_embed, key_embed, obj_key_embed, shared):
+    """The reference's per-layer composition and stacks (dino.py:329-347); same arguments and results as ``dino_heads``.
+    Unlike ARCTIC's, DINO's logits keep the dtype autocast gives them (no ``.to(float32)``)."""
+    levels = len(hs)
+    classes, keys, outs = [], [[], []], [[] for _ in shared]
+    for lvl in range(levels):
+        hs_lvl, ref = hs[lvl], references[lvl]
+        keys[0].append((key_embed[lvl](hs_lvl) + inverse_sigmoid(ref)).sigmoid() * 2 - 1)
+        keys[1].append((obj_key_embed[lvl](hs_lvl) + inverse_sigmoid(ref)).sigmoid() * 2 - 1)
+        classes.append(class_embed[lvl](hs_lvl))
+        for g, lin in enumerate(shared):
+            outs[g].append(lin(hs_lvl))
+    return torch.stack(classes), [torch.stack(k) for k in keys], [torch.stack(o) for o in outs]
+
+
+class _DinoHeadsFunction(torch.autograd.Function):
+    """``_DetrHeadsFunction``'s fp32 ARCTIC node whose references may require grad: the same three forward and five backward
+    launches, and one more (``msda_heads_ref_backward_f32``) when ``init_ref`` or ``inter_ref`` needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, meta, hs, init_ref, inter_ref, *params):
+        return _DetrHeadsFunction.forward(ctx, meta, hs, init_ref, inter_ref, *params)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        kind, flags, n_cls, n_mlp, n_sh, _ = ctx.meta
+        hs3, init3, inter3, hidden, sig, *params = ctx.saved_tensors
+        L, B, Q = ctx.shape
+        g = [x.contiguous().view(L, B * Q, x.shape[-1]) for x in grads]
+        grad_logits, grad_kp, grad_sh = g[0], g[1:1 + ctx.n_kp], g[1 + ctx.n_kp:]
+        groups = _split(params, n_cls, n_mlp, n_sh)
+        grad_hs, g_cls, g_mlp, g_sh = _native.heads_backward(kind, hs3, init3, inter3, *groups, flags, hidden, sig, grad_logits,
+                                                             grad_kp, grad_sh)
+        need_init, need_inter = ctx.needs_input_grad[2], ctx.needs_input_grad[3] and L > 1
+        g_init = g_inter = None
+        if need_init or need_inter:
+            R = init3.shape[-1]
+            g_init, g_inter = _native.heads_ref_backward(init3.view(B * Q, R), inter3.view(L - 1, B * Q, R) if L > 1 else None,
+                                                         sig, grad_kp, need_init, need_inter)
+            g_init = g_init.view(B, Q, R) if need_init else None
+            g_inter = g_inter.view(L - 1, B, Q, R) if need_inter else None
+        pgrads = g_cls[0] + g_cls[1] + g_mlp[0] + g_mlp[1] + g_sh[0] + g_sh[1]
+        return (None, grad_hs.view(L, B, Q, -1), g_init, g_inter) + tuple(pgrads)
+
+
+def _dino_fused_operands(hs, references, class_embed, key_embed, obj_key_embed, shared):
+    """(meta, params, hs [L, N, Lq, C], init_ref, inter_ref) where the node runs, None where the composition does.  The
+    module and shape conditions are ``_fused_plan``'s, asked with the references detached: whether they require grad is the one
+    condition this node lifts."""
+    L = len(hs)
+    first = hs[0]
+    if not (_fused_enabled() and 1 <= L <= MAX_LEVELS and len(references) >= L and first.is_cuda
+            and first.dtype == torch.float32 and not torch.is_autocast_enabled()):
+        return None
+    refs = [references[lvl] for lvl in range(L)]
+    if any(t.shape != first.shape or t.dtype != first.dtype or t.device != first.device for t in hs) \
+            or any(r.shape != refs[0].shape or r.dtype != torch.float32 or r.device != first.device for r in refs):
+        return None
+    hs4 = hs if torch.is_tensor(hs) else torch.stack(list(hs))
+    init_ref = refs[0]
+    inter_ref = None if L == 1 else references[1:L] if torch.is_tensor(references) else torch.stack(refs[1:])
+    plan = _fused_plan(ARCTIC, hs4, init_ref.detach(), inter_ref.detach() if L > 1 else None, class_embed,
+                       [key_embed, obj_key_embed], shared)
+    if plan is None:
+        return None
+    return plan + (hs4, init_ref, inter_ref)
+
+
+def dino_heads(hs, references, class_embed, key_embed, obj_key_embed, shared):
+    """Every decoder layer's prediction heads of the DINO model (models/dino/dino.py:323-347).
+
+    hs: the decoder's list of L tensors [N, Lq, C], or one stacked [L, N, Lq, C].  references: ``reference[:-1]``, L tensors
+    [N, Lq, 42] (a stacked tensor is taken too); in DINO all but the first carry a gradient back into the decoder ("look
+    forward twice").  class_embed, key_embed, obj_key_embed: per-layer modules (one module repeated means shared weights).
+    shared: the six Linears (mano_pose, mano_beta, hand_cam, obj_cam, obj_rot, obj_rad).
+
+    On CUDA fp32 without autocast (and ``MSDA_HEADS_FUSED`` not ``0``, a hidden size the kernels take, L <= 8, module lists that
+    are one module repeated or L distinct ones) it is one autograd node: three forward launches, five backward ones and one
+    more for the references' gradients, which go to each reference that requires one.  Everything else runs
+    ``dino_heads_reference``.  Returns what ``detr_heads("arctic", ...)`` returns:
+    (logits [L, N, Lq, K], [hand keypoints, object keypoints] [L, N, Lq, 42], [six shared outputs [L, N, Lq, n]])."""
+    shared = list(shared)
+    ops = _dino_fused_operands(hs, references, class_embed, key_embed, obj_key_embed, shared)
+    if ops is None:
+        return dino_heads_reference(hs, references, class_embed, key_embed, obj_key_embed, shared)
+    meta, params, hs4, init_ref, inter_ref = ops
+    outs = _DinoHeadsFunction.apply(meta, hs4, init_ref, inter_ref, *params)
+    return outs[0], list(outs[1:3]), list(outs[3:])

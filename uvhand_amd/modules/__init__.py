@@ -4,6 +4,7 @@ from .deformable_layers import (DeformableTransformerDecoder, DeformableTransfor
                                 DeformableTransformerEncoder, DeformableTransformerEncoderLayer)
 from .deformable_transformer import DeformableTransformer
 from .detr import ArcticDeformableDETR, AssemblyDeformableDETR
+from .dino import DINO, build_dino_model
 from .dino_deformable_transformer import DeformableTransformer as DinoDeformableTransformer
 from .dino_deformable_transformer import DeformableTransformerEncoderLayer as DinoDeformableTransformerEncoderLayer
 from .dino_deformable_transformer import TransformerEncoder as DinoTransformerEncoder
@@ -21,7 +22,7 @@ __all__ = ["MSDeformAttn", "DeformableTransformerEncoderLayer", "DeformableTrans
            "ArcticDeformableDETR", "AssemblyDeformableDETR",
            "DinoDeformableTransformerDecoderLayer", "DinoTransformerDecoder",
            "DinoDeformableTransformer", "DinoTransformerEncoder", "DinoDeformableTransformerEncoderLayer",
-           "build_dino_deformable_transformer",
+           "build_dino_deformable_transformer", "DINO", "build_dino_model",
            "SmootherResBlock", "Smoother", "MotionSmoother", "ArcticSmoother", "SmoothCriterion",
            "Mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer",
            "build_swin_transformer", "PositionEmbeddingSine", "Joiner", "build_backbone"]
